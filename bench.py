@@ -21,7 +21,8 @@ on its launch stream inside the timed region; `cpu_baseline` times the oracle's 
 TF1 CPU op chain on a bounded row sample of the same graph (rank 0, N = 1 only), next to which
 the GPU results of the user-side sample, an item-side slice holding the heaviest hub rows and a
 >= 100k-row slice of the fused embeddings are compared with the oracle.
-Prints exactly one JSON line on rank 0.
+Prints exactly one JSON line on rank 0. `--dump-outputs DIR` also writes what the last timed step computed
+(DIR/<name>.npy, float32, a fixed seeded row sample where an output exceeds the budget: dump_outputs).
 """
 from __future__ import annotations
 
@@ -51,6 +52,7 @@ WORKLOADS = {
     "yelp-shaped": dict(users=19_751, items=38_386, nnz=126_000, t_total=12, d=64, layers=3),
 }
 HBM_PEAK_GBPS = 8000.0     # MI355X HBM3E spec (MI355X_MICROARCH.md, chip-level parameters)
+DUMP_BYTES = 56 << 20      # --dump-outputs: the arrays' bytes in all (the files stay under 64 MB)
 
 
 def log(*a):
@@ -97,6 +99,10 @@ def parse():
     p.add_argument("--graph", action="store_true",
                    help="N=1: time a hipGraph replay of the step (launch-bound small workloads); the "
                         "per-kernel event timing then comes from an extra eager pass before it")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32; rank 0): "
+                        "the fused user / item embeddings, or with --stages spmm the propagated interval embeddings; "
+                        "outputs too large for the budget keep a fixed seeded sample of their rows (see dump_outputs)")
     return p.parse_args()
 
 
@@ -105,6 +111,25 @@ def position_checksum(f: torch.Tensor) -> float:
     n = f.shape[0]
     w = torch.arange(1, n + 1, device=f.device, dtype=torch.float64)
     return float((f.abs().sum(dim=1, dtype=torch.float64) * w).sum() / (n * (n + 1) / 2.0))
+
+
+def dump_outputs(directory: str, arrays: dict) -> dict:
+    """Writes each array [..., n_rows, d] as <directory>/<name>.npy in float32. An array whose rows do not fit its share
+    of DUMP_BYTES keeps the rows np.random.default_rng(0).choice(n_rows, k, replace=False), sorted: the same rows in
+    every run of the same arguments. Returns {name: {"shape": stored shape, "rows_of": n_rows}} for the result line."""
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_BYTES // max(len(arrays), 1)
+    written = {}
+    for name, x in arrays.items():
+        n_rows = x.shape[-2]
+        k = min(n_rows, share // max(x.numel() // max(n_rows, 1) * 4, 1))
+        if k < n_rows:
+            rows = np.sort(np.random.default_rng(0).choice(n_rows, k, replace=False))
+            x = x.index_select(x.dim() - 2, torch.from_numpy(rows).to(x.device))
+        y = x.detach().float().cpu().numpy()
+        np.save(os.path.join(directory, name + ".npy"), y)
+        written[name] = {"shape": list(y.shape), "rows_of": int(n_rows)}
+    return written
 
 
 def launch_command(n_ranks: int, argv: list, port: int) -> list:
@@ -274,6 +299,7 @@ def main():
                 acc_u, acc_i = runner.run(ops.spmm, frac_plans, frac_emb, L, 0.5)
             else:
                 acc_u, acc_i = runner.run(ops.spmm, plans[0][0], plans[0][1], emb[0][0], emb[0][1], L, 0.5)
+            state["stack"] = (acc_u, acc_i)
             if post:
                 ex_u.post(acc_u.to(comm_dev))
                 ex_i.post(acc_i.to(comm_dev))
@@ -451,6 +477,14 @@ def main():
         sync()
         elapsed = time.perf_counter() - t1
         step_ms = [marks[s_].elapsed_time(marks[s_ + 1]) for s_ in range(a.steps)]
+    dumped = None
+    if a.dump_outputs and rank == 0:         # before any untimed pass below overwrites the last timed step's outputs
+        if "final" in state:
+            outs = {"final_user_vector": state["final"][0], "final_item_vector": state["final"][1]}
+        else:                                # --stages spmm: the L-layer stacks (this rank's intervals / row slices)
+            su, si = state["stack"] if split else (out_u, out_i)
+            outs = {"user_interval_embeddings": su, "item_interval_embeddings": si}
+        dumped = dump_outputs(a.dump_outputs, outs)
     redo_tiles = ops.range_redo_count()       # tiles the f16 x 2 kernels re-evaluated in fp32 during the timed steps (0 = fast path throughout)
     elapsed = allmax(elapsed)
     if multi:
@@ -559,6 +593,7 @@ def main():
                      "by_direction": side},
         "range_redo_tiles_rank0": redo_tiles,
         "stage_ms_per_step_rank0": stage_ms, "final_abs_mean": final_abs_mean, "final_position_checksum": final_pos,
+        "dumped_outputs": dumped,
         "spmm_only_edges_per_sec_rank0": (local_launch_edges * L) / ((stage_ms["spmm_rows"] + stage_ms["spmm_fixup"]) * 1e-3)
         if stage_ms["spmm_rows"] > 0 else None,
     }

@@ -48,3 +48,22 @@ def test_dataset_shaped_config_against_the_oracle(workload, launch):
     assert set(fc["by_node_type"]) == {"users", "items"} and fc["intervals"] == w["T"]
     assert fc["worst_over_tolerance"] <= 1.0, fc
     assert fc["by_node_type"]["items"]["rows"] == min(65_536, w["items"])
+
+
+def test_dump_outputs_hold_the_last_timed_step(tmp_path):
+    """--dump-outputs writes the fused embeddings of the last timed step: on a dataset-sized graph every row fits the
+    budget, so the files reproduce the result line's statistics of the full arrays (taken after the same-run fp32-engine
+    passes, which end with one more f16 x 2 step on the same inputs)."""
+    import numpy as np
+    w = SHAPES["gowalla-shaped"]
+    r = _bench("--workload", "gowalla-shaped", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+               "--dump-outputs", str(tmp_path))
+    assert r["steps"] == 3 and r["ms_per_step"] > 0
+    for j, (name, n) in enumerate((("final_user_vector", w["users"]), ("final_item_vector", w["items"]))):
+        x = np.load(tmp_path / (name + ".npy"))
+        assert x.dtype == np.float32 and x.shape == (n, w["d"]) and np.isfinite(x).all()
+        assert r["dumped_outputs"][name] == {"shape": [n, w["d"]], "rows_of": n}
+        a = np.abs(x.astype(np.float64))
+        assert abs(a.mean() - r["final_abs_mean"][j]) <= 1e-6 * r["final_abs_mean"][j]
+        pos = float((a.sum(axis=1) * np.arange(1, n + 1)).sum() / (n * (n + 1) / 2.0))
+        assert abs(pos - r["final_position_checksum"][j]) <= 1e-6 * r["final_position_checksum"][j]

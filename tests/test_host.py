@@ -354,3 +354,24 @@ def test_bench_starts_its_own_ranks_when_started_bare(monkeypatch):
     with pytest.raises(SystemExit) as e:
         bench.main()
     assert "agree" in str(e.value.code)
+
+
+def test_bench_dump_outputs_samples_rows_within_budget(tmp_path, monkeypatch):
+    """bench.dump_outputs: float32 files, whole arrays when they fit, else the same seeded, sorted row sample in every
+    call; the files stay under the budget."""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 1 << 20)
+    g = torch.Generator().manual_seed(0)
+    big = torch.randn((3, 20_000, 16), generator=g)                    # 3.8 MB: sampled
+    small = torch.randn((1000, 16), generator=g, dtype=torch.float64)  # 64 kB: whole, stored as float32
+    info = [bench.dump_outputs(str(tmp_path / s), {"big": big, "small": small}) for s in ("a", "b")]
+    assert info[0] == info[1]
+    k = (1 << 19) // (3 * 16 * 4)
+    assert info[0] == {"big": {"shape": [3, k, 16], "rows_of": 20_000}, "small": {"shape": [1000, 16], "rows_of": 1000}}
+    rows = np.sort(np.random.default_rng(0).choice(20_000, k, replace=False))
+    for s in ("a", "b"):
+        b, m = np.load(tmp_path / s / "big.npy"), np.load(tmp_path / s / "small.npy")
+        assert b.dtype == np.float32 and m.dtype == np.float32
+        np.testing.assert_array_equal(b, big.numpy()[:, rows, :])
+        np.testing.assert_array_equal(m, small.float().numpy())
+    assert sum(os.path.getsize(p) for p in (tmp_path / "a").iterdir()) <= (1 << 20) + 2 * 128

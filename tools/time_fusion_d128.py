@@ -1,6 +1,6 @@
 import os, sys, time
 import numpy as np, torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from oracle import selfgnn_oracle as O
 from sa_gnn_amd import ops
 from sa_gnn_amd.model import random_fusion_params
