@@ -521,6 +521,34 @@ int sagnn_dense_tn_f32(const float* X, int64_t ldx, const float* G, int64_t ldg,
 int sagnn_dense_tn_seg_f32(const float* X, int64_t ldx, int64_t x_seg, const float* G, int64_t ldg, int64_t g_seg,
                            int64_t seg_rows, int n_seg, int din, int dout, float* dW, float* db, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Full-catalogue retrieval (retrieval.hip): the best k items of every query row over the whole item table.
+ *   score(b, i) = <Q[b], I[i]> in fp32 on the exact-fp32 matrix cores (v_mfma_f32_16x16x4_f32): every score is
+ *   a fixed fmaf chain over k, a function of the query row and the item row alone. sagnn_set_engine does NOT
+ *   apply to this entry. The model's head score <fu[u], fi[i]> + <leaky(att[b]), fi[i]> is this product with
+ *   Q[b] = leaky(att[b]) + fu[u] (sagnn_leaky_add_f32) and I = fi.
+ * Order (strict, total): higher score first; equal scores go to the lower item id (-0.0 == +0.0); a NaN score
+ *   ranks below every number and is never returned.
+ * Eligible items: every item of [0, n_items) except row b's exclusions. The optional exclusion list is a CSR
+ *   (excl_rowptr [n_queries + 1], excl_items) of ascending ids per row, duplicates allowed; the ids are only
+ *   compared, never used as addresses. target[b] is always eligible, even when its row excludes it.
+ * Outputs: topk_items / topk_scores [n_queries, k] (contiguous), best first; slots past the number of eligible
+ *   non-NaN items hold id -1 and score -inf. target_rank[b] (with target only) = the number of eligible items
+ *   that come before target[b], from the same score values as the top k, so rank < k <=> topk_items[b, rank] ==
+ *   target[b]; a NaN target score gives the number of eligible items (a miss); a target outside [0, n_items)
+ *   gives -1.
+ * A row's outputs depend on that row's inputs only (not on n_queries or its place in the batch) and are
+ *   bit-identical between runs.
+ * Limits: d in {32, 64, 128}; 1 <= k <= 128; 1 <= n_items < 2^31; ldq, ldi multiples of 4 and >= d; Q, I and
+ *   workspace 16-byte aligned; workspace_bytes >= sagnn_score_topk_workspace_bytes(...). Every argument is
+ *   checked before any device work. Two launches on `stream`, no allocation, no synchronisation (capturable).
+ * -------------------------------------------------------------------------------- */
+size_t sagnn_score_topk_workspace_bytes(int64_t n_queries, int64_t n_items, int d, int k);
+int sagnn_score_topk_f32(const float* Q, int64_t ldq, const float* I, int64_t ldi, int64_t n_queries, int64_t n_items,
+                         int d, int k, const int32_t* excl_rowptr, const int32_t* excl_items, const int32_t* target,
+                         int32_t* topk_items, float* topk_scores, int64_t* target_rank, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

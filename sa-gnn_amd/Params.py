@@ -57,6 +57,7 @@ _FLAGS = [
     ("test", bool, True, "test (True) or validation"),
     ("ssl", bool, True, "unused"),
     ("uid", int, 0, "debug print index"),
+    ("full_rank", int, 0, "also report HR / NDCG over the full item catalogue (not in the reference)"),
 ]
 
 

@@ -149,6 +149,9 @@ SIGNATURES = {
                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_int64, c_void_p, c_size_t, c_void_p]),
     "sagnn_interval_fusion_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "sagnn_score_topk_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int, c_int]),
+    "sagnn_score_topk_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 _lib = None

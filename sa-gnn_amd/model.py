@@ -225,8 +225,15 @@ class Recommender:
     def predict(self, uids, iids, sequence, mask, uLocs_seq):
         """self.preds of the reference (model.py:156-173) for one batch, on the cached
         final_user_vector / final_item_vector. sequence/mask: [args.batch, pos_length]."""
-        heads, leaky = args.num_attention_heads, NNs.leaky
         fu, fi = self.final_user_vector, self.final_item_vector
+        att = self._head_att(sequence, mask)
+        as_i32 = lambda v: torch.as_tensor(np.asarray(v, dtype=np.int32), device=self.device)
+        return ops.pair_score(fu, fi, as_i32(uids), as_i32(iids), S=att, A=fi, locs=as_i32(uLocs_seq), leaky=NNs.leaky)
+
+    def _head_att(self, sequence, mask):
+        """The head's sequence representation att [args.batch, d] (model.py:158-168) on the cached final vectors."""
+        heads, leaky = args.num_attention_heads, NNs.leaky
+        fi = self.final_item_vector
         pi, pp = self._masked_sum_plans(sequence, mask)
         seq_tok = ops.spmm(pi, fi, 1.0)                                   # [B, d] masked item sum
         pos_tok = ops.spmm(pp, self.posEmbed.detach(), 1.0)               # [B, d] masked position sum
@@ -236,8 +243,33 @@ class Recommender:
         for i, mh in enumerate(self.multihead_self_attention_sequence):
             a1 = mh.attention_mean(ln(att, self.head_ln[2 + i]).view(B, 1, d))      # length-1 sequence
             att = ops.leaky_add(a1, att, leaky)
-        as_i32 = lambda v: torch.as_tensor(np.asarray(v, dtype=np.int32), device=self.device)
-        return ops.pair_score(fu, fi, as_i32(uids), as_i32(iids), S=att, A=fi, locs=as_i32(uLocs_seq), leaky=leaky)
+        return att
+
+    def _query_rows(self, uids, sequence, mask):
+        """The head's user-side row q[b] = leaky(att[b]) + fu[uids[b]]: the head score of (uids[b], i) is
+        <fu[u], fi[i]> + <leaky(att[b]), fi[i]> = <q[b], fi[i]> (model.py:169-170), so ranking the whole catalogue
+        is one product of these rows with final_item_vector."""
+        uids = torch.as_tensor(np.asarray(uids, dtype=np.int64), device=self.device)
+        att = self._head_att(sequence, mask)[:uids.numel()]
+        return ops.leaky_add(att, self.final_user_vector.index_select(0, uids), NNs.leaky)
+
+    def _test_sequences(self, batIds):
+        """The sequences sampleTestBatch feeds the head: the user's whole sequence (args.test) or all but its last
+        item (validation), the last min(len, pos_length) items right-aligned. Returns sequence, mask [args.batch,
+        pos_length], and per user the flat range [start, seq_end) the sequence was cut from."""
+        batIds = np.asarray(batIds, dtype=np.int64)
+        P = args.pos_length
+        flat, ptr = self._flat_sequences()
+        start, end = ptr[batIds], ptr[batIds + 1]
+        seq_end = end if args.test else np.maximum(end - 1, start)
+        k = np.minimum(seq_end - start, P)
+        sequence = np.zeros((args.batch, P), dtype=np.int64)
+        mask = np.zeros((args.batch, P), dtype=np.float32)
+        rws = np.repeat(np.arange(len(batIds), dtype=np.int64), k)
+        within = np.arange(int(k.sum()), dtype=np.int64) - np.repeat(np.cumsum(k) - k, k)
+        sequence[rws, P - k[rws] + within] = flat[seq_end[rws] - k[rws] + within]
+        mask[rws, P - k[rws] + within] = 1
+        return sequence, mask, start, seq_end
 
     def _test_candidates(self):
         """test_dict (1-indexed user -> 1-indexed candidate items, preprocess_to_sequence.ipynb cell 11) as one int32
@@ -265,17 +297,15 @@ class Recommender:
         sequence, right-aligned into pos_length slots. Vectorised over the batch (users outside
         handler.tstUsrs take the reference's per-user path)."""
         batIds = np.asarray(batIds, dtype=np.int64)
-        batch, P = len(batIds), args.pos_length
+        batch = len(batIds)
         temTst = self.handler.tstInt[batIds]
-        flat, ptr = self._flat_sequences()
-        start, end = ptr[batIds], ptr[batIds + 1]
+        flat, _ = self._flat_sequences()
+        sequence, mask, start, seq_end = self._test_sequences(batIds)
         val_list = [None] * args.batch
         if args.test:
             posloc = np.array([(-1 if t is None else t) for t in temTst], dtype=np.int64)
-            seq_end = end                                         # posset = the whole sequence
         else:
-            posloc = flat[np.maximum(end - 1, start)]             # last item held out for validation
-            seq_end = np.maximum(end - 1, start)
+            posloc = flat[seq_end]                                # last item held out for validation
             for i in range(batch):
                 val_list[i] = int(posloc[i])
         neg_all, row_of = self._test_candidates()
@@ -287,15 +317,6 @@ class Recommender:
             neg = neg_all[rows].astype(np.int64)
         locs = np.concatenate([neg, posloc[:, None]], axis=1)     # [batch, testSize], positive LAST
         tstLocs = list(locs)
-        # sequences: the last min(len, P) items, right-aligned
-        n_pos = seq_end - start
-        k = np.minimum(n_pos, P)
-        sequence = np.zeros((args.batch, P), dtype=np.int64)
-        mask = np.zeros((args.batch, P), dtype=np.float32)
-        rws = np.repeat(np.arange(batch, dtype=np.int64), k)
-        within = np.arange(int(k.sum()), dtype=np.int64) - np.repeat(np.cumsum(k) - k, k)
-        sequence[rws, P - k[rws] + within] = flat[seq_end[rws] - k[rws] + within]
-        mask[rws, P - k[rws] + within] = 1
         C = locs.shape[1]
         uLocs = np.repeat(batIds, C)
         uLocs_seq = np.repeat(np.arange(batch, dtype=np.int64), C)
@@ -342,6 +363,58 @@ class Recommender:
             preds = self.predict(uLocs, iLocs, sequence, mask, uLocs_seq).cpu().numpy()
             target = temTst if args.test else val_list
             tot += np.array(self.calcRes(preds.reshape(len(batIds), -1), target, tstLocs))
+        return {"HR": tot[0] / num, "NDCG": tot[1] / num, "HR5": tot[2] / num, "NDCG5": tot[3] / num,
+                "HR20": tot[4] / num, "NDCG20": tot[5] / num}
+
+    def recommend(self, uids, k=None, exclude_seen=True):
+        """The k best items of the whole catalogue for each user (sagnn_score_topk_f32 on _query_rows), on the cached
+        final vectors (run forward() first). The head reads each user's sequence as sampleTestBatch builds it;
+        exclude_seen leaves out the user's training items (handler.trnMat row). Returns numpy (items int32,
+        scores float32), both [len(uids), k], best first; -1 / -inf where fewer than k items are eligible."""
+        k = args.shoot if k is None else int(k)
+        uids = np.asarray(uids, dtype=np.int64).reshape(-1)
+        items, scores = [], []
+        for st in range(0, len(uids), args.batch):
+            bat = uids[st:st + args.batch]
+            sequence, mask, _, _ = self._test_sequences(bat)
+            excl = None
+            if exclude_seen:
+                rows = self.handler.trnMat[bat].tocsr()
+                rows.sort_indices()
+                excl = (rows.indptr, rows.indices)
+            it, sc, _ = ops.score_topk(self._query_rows(bat, sequence, mask), self.final_item_vector, k, excl=excl)
+            items.append(it.cpu().numpy())
+            scores.append(sc.cpu().numpy())
+        if not items:
+            return np.zeros((0, k), np.int32), np.zeros((0, k), np.float32)
+        return np.concatenate(items), np.concatenate(scores)
+
+    def testEpochFull(self):
+        """Full-catalogue HR / NDCG at shoot, 5 and 20: testEpoch()'s users, targets and batches, with the target
+        ranked against every item instead of testSize - 1 sampled ones. A user's exclusions are the items of the
+        sequence its head reads (the target stays eligible: sagnn_score_topk_f32 never excludes it). Same keys and
+        normalisation as testEpoch(); forward() runs once."""
+        self.forward()
+        ids = self.handler.tstUsrs
+        num = len(ids)
+        flat, _ = self._flat_sequences()
+        tot = np.zeros(6)
+        for st in range(0, num, args.batch):
+            batIds = np.asarray(ids[st:st + args.batch], dtype=np.int64)
+            _, _, temTst, _, sequence, mask, _, val_list = self.sampleTestBatch(batIds)
+            target = temTst if args.test else val_list
+            tgt = np.asarray([(-1 if t is None else t) for t in target[:len(batIds)]], dtype=np.int32)
+            _, _, start, seq_end = self._test_sequences(batIds)
+            rowptr = np.zeros(len(batIds) + 1, dtype=np.int64)
+            np.cumsum(seq_end - start, out=rowptr[1:])
+            excl = np.concatenate([np.sort(flat[a:e]) for a, e in zip(start, seq_end)]) if len(batIds) else []
+            _, _, rank = ops.score_topk(self._query_rows(batIds, sequence, mask), self.final_item_vector, 1,
+                                        excl=(rowptr, excl), target=tgt)
+            rank = rank.cpu().numpy()
+            for j, kk in enumerate((args.shoot, 5, 20)):
+                hit = (rank >= 0) & (rank < kk)
+                tot[2 * j] += hit.sum()
+                tot[2 * j + 1] += (1.0 / np.log2(rank[hit] + 2)).sum()
         return {"HR": tot[0] / num, "NDCG": tot[1] / num, "HR5": tot[2] / num, "NDCG5": tot[3] / num,
                 "HR20": tot[4] / num, "NDCG20": tot[5] / num}
 
@@ -643,10 +716,14 @@ class Recommender:
             if test:
                 reses = self.testEpoch()
                 print(self.makePrint("Test", ep, reses, test))
+                if args.full_rank:
+                    print(self.makePrint("TestFull", ep, self.testEpochFull(), False))
                 if reses["NDCG"] > maxndcg:
                     self.saveHistory()
                     maxndcg, maxres, maxepoch = reses["NDCG"], reses, ep
         reses = self.testEpoch()
         print(self.makePrint("Test", args.epoch, reses, True))
+        if args.full_rank:
+            print(self.makePrint("TestFull", args.epoch, self.testEpochFull(), False))
         print(self.makePrint("max", maxepoch, maxres, True))
         return reses

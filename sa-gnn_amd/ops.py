@@ -706,3 +706,64 @@ def pair_score(U: torch.Tensor, I: torch.Tensor, uids: torch.Tensor, iids: torch
         0 if S is None else _f32_rows("S", S, d), _ptr(A), 0 if A is None else _f32_rows("A", A, d),
         uids.data_ptr(), iids.data_ptr(), _ptr(locs), float(leaky), out.data_ptr(), n, d, _stream()))
     return out
+
+
+_topk_ws: dict = {}      # device -> workspace of sagnn_score_topk_f32, grown on demand (no allocation once warm)
+
+
+def _topk_workspace(device: torch.device, nbytes: int) -> torch.Tensor:
+    ws = _topk_ws.get(device)
+    if ws is None or ws.numel() < nbytes:
+        ws = _topk_ws[device] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
+    return ws
+
+
+def check_exclusions(rowptr, items, n_rows: int, n_items: int):
+    """Validates an exclusion CSR on the host (rowptr [n_rows + 1] from 0, monotone, ending at len(items); ids in
+    [0, n_items), ascending within a row) and returns it as int32 numpy arrays."""
+    as_np = lambda v: v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+    rp, it = as_np(rowptr).astype(np.int64).reshape(-1), as_np(items).astype(np.int64).reshape(-1)
+    if rp.size != n_rows + 1 or rp[0] != 0 or rp[-1] != it.size:
+        raise ValueError(f"excl rowptr: need {n_rows + 1} entries from 0 to len(items) = {it.size}")
+    if (np.diff(rp) < 0).any():
+        raise ValueError("excl rowptr: not monotone")
+    if it.size and (it.min() < 0 or it.max() >= n_items):
+        raise ValueError(f"excl items: ids outside [0, {n_items})")
+    row = np.repeat(np.arange(n_rows), np.diff(rp))
+    if ((np.diff(it) < 0) & (row[1:] == row[:-1])).any():
+        raise ValueError("excl items: ids must be ascending within a row")
+    return rp.astype(np.int32), it.astype(np.int32)
+
+
+def score_topk(Q: torch.Tensor, I: torch.Tensor, k: int, excl=None, target=None):
+    """The best k items of every row of Q over the whole item table I (sagnn_score_topk_f32): score <Q[b], I[i]> in
+    fp32, higher first, equal scores to the lower id, NaN never returned. excl = (rowptr, items): a CSR of item ids
+    per row left out (checked on the host, then uploaded); target [B]: items whose rank is returned (always eligible).
+    Returns (items int32 [B, k], scores float32 [B, k], rank int64 [B] or None); empty slots hold -1 / -inf."""
+    lib = _lib.load()
+    if Q.dim() != 2:
+        raise ValueError(f"Q: expected [B, d], got {tuple(Q.shape)}")
+    B, d = int(Q.shape[0]), int(Q.shape[1])
+    n_items = int(I.shape[0]) if I.dim() == 2 else 0
+    ex = None if excl is None else check_exclusions(excl[0], excl[1], B, n_items)
+    ldq, ldi = _f32_rows("Q", Q, d), _f32_rows("I", I, d)
+    dev = Q.device
+    if I.device != dev:
+        raise ValueError(f"I on {I.device}, Q on {dev}")
+    rp_d = it_d = tg_d = rank = None
+    if ex is not None:
+        rp, it = ex
+        rp_d = torch.from_numpy(rp).to(dev)
+        it_d = torch.from_numpy(it).to(dev) if it.size else torch.zeros(1, dtype=torch.int32, device=dev)
+    if target is not None:
+        tg_d = torch.as_tensor(target, device=dev)
+        if tg_d.dtype != torch.int32 or tg_d.dim() != 1 or tg_d.numel() != B or not tg_d.is_contiguous():
+            raise ValueError(f"target: need a contiguous int32 vector of {B} elements")
+        rank = torch.empty(B, dtype=torch.int64, device=dev)
+    items = torch.empty((B, int(k)), dtype=torch.int32, device=dev)
+    scores = torch.empty((B, int(k)), dtype=torch.float32, device=dev)
+    need = int(lib.sagnn_score_topk_workspace_bytes(B, n_items, d, int(k)))
+    ws = _topk_workspace(dev, need) if need else None
+    check(lib.sagnn_score_topk_f32(Q.data_ptr(), ldq, I.data_ptr(), ldi, B, n_items, d, int(k), _ptr(rp_d), _ptr(it_d),
+                                   _ptr(tg_d), items.data_ptr(), scores.data_ptr(), _ptr(rank), _ptr(ws), need, _stream()))
+    return items, scores, rank
