@@ -51,9 +51,10 @@ int sagnn_version(void);
  * attention, their backward products), selected PER CALLING THREAD — there is no environment switch and no
  * process-wide state: a thread that never calls sagnn_set_engine runs SAGNN_ENGINE_F16X2.
  *   SAGNN_ENGINE_F16X2  the default: 16-bit matrix cores over two-piece split fp32 operands (see ARITHMETIC below)
- *   SAGNN_ENGINE_F32    v_mfma_f32_32x32x2_f32 kernels: an fp32 fmaf chain bit for bit (d in {32, 64}; the exact-fp32
- *                       reference the default engine is measured against)
- *   SAGNN_ENGINE_VALU   the plain VALU formulations (any d)
+ *   SAGNN_ENGINE_F32    v_mfma_f32_32x32x2_f32 kernels: an fp32 fmaf chain bit for bit (the exact-fp32 reference the
+ *                       default engine is measured against)
+ *   SAGNN_ENGINE_VALU   the plain VALU formulations
+ * Which kernel a fusion call runs, per engine, shape and alignment: the table in sa-gnn_amd/csrc/engine.cpp.
  * sagnn_set_engine returns SAGNN_OK or SAGNN_ERR_ARG; sagnn_get_engine the calling thread's engine. The SpMM is
  * plain fp32 under every engine. */
 enum { SAGNN_ENGINE_F16X2 = 0, SAGNN_ENGINE_F32 = 1, SAGNN_ENGINE_VALU = 2 };
@@ -293,7 +294,7 @@ int sagnn_gnn_stack_bwd_f32(const sagnn_spmm_batch* batch, const float* G_u, int
  *   normalised in place; only out [n, d] is a result.
  *
  * ARITHMETIC of the GEMM-shaped stages (the gate product [x_t | h] W and the three dense layers)
- *   for d in {32, 64, 128}, 16 heads, under the default engine: fp32 in, fp32 out, evaluated on the 16-bit
+ *   where the default engine takes its f16 x 2 kernels (csrc/engine.cpp): fp32 in, fp32 out, evaluated on the 16-bit
  *   matrix cores over SPLIT operands: two round-to-nearest f16 pieces per value (v = v1 + v2'/4096), three piece
  *   products, fp32 accumulation. The split represents v to 2^-23 |v| inside a window — |v| < 32768 at the top, and an
  *   ABSOLUTE floor of 2^-37 at the bottom — so what is guaranteed is:
@@ -391,8 +392,8 @@ int sagnn_layernorm_td_bwd_f32(const float* h, int64_t ld_h, const float* dy, in
 int sagnn_lstm_bwd_step_f32(const float* gates, const float* cell, const float* dh_ext, int64_t ld_dhe,
                             const float* drop_scale, const float* dh_rec, int64_t ld_dhr, const float* dc_in,
                             float* dgates, float* dc_out, int64_t n, int t, int d, int ts, void* stream);
-/* Front of the attention backward pass in one launch (sagnn_attn_bwd_front_supported: d in {32, 64},
- * d_k in {2, 4}, t in {1..6, 8}; on the default engine with 16 heads also t in {12, 16}, and d = 128 with t <= 6): y = layer_norm(x) when apply_ln (else x), Q|K|V = y W + b, attention
+/* Front of the attention backward pass in one launch (shapes: sagnn_attn_bwd_front_supported, csrc/engine.cpp):
+ * y = layer_norm(x) when apply_ln (else x), Q|K|V = y W + b, attention
  * backward given g_out = dL/d(mean context) [n, d] -> dqkv [n*t, 3d] (dQ | dK | dV rows) and, when
  * y_out is not NULL, y [n*t, d]. Replaces layernorm_td + dense_nn + attn_bwd of the recompute path. */
 int sagnn_attn_bwd_front_supported(int d, int t, int heads);
@@ -416,8 +417,8 @@ int sagnn_lstm_bwd_f32(const float* x, int64_t ld_n, int64_t ld_t, const float* 
  * dW product (fp32 MFMA: the larger part of its time) and stores the gate gradients time-major into the caller's
  * scratch ([t, n, 4d] floats = sagnn_lstm_bwd_workspace_bytes, 16-byte aligned); one pass over them then takes
  * dW += [x_s | h_{s-1}]^T dG_s on the 16-bit matrix cores over split operands, gate-gradient rows scaled by exact
- * powers of two as in the attention tail (ARITHMETIC above). Same arguments and results otherwise; with
- * workspace == NULL, or under SAGNN_ENGINE_F32 / SAGNN_ENGINE_VALU, the call IS sagnn_lstm_bwd_f32. */
+ * powers of two as in the attention tail (ARITHMETIC above). Same arguments and results otherwise; where
+ * csrc/engine.cpp does not select this form (no workspace, another engine), the call IS sagnn_lstm_bwd_f32. */
 size_t sagnn_lstm_bwd_workspace_bytes(int64_t n, int t, int d);
 int sagnn_lstm_bwd_ws_f32(const float* x, int64_t ld_n, int64_t ld_t, const float* h, const float* gates,
                           const float* cell, const float* dh_ext, int64_t ld_dhe, const float* drop_scale,

@@ -232,25 +232,13 @@ __global__ __launch_bounds__(kBlock, 2) void attn_bwd_tail_kernel(float* __restr
   if (tid < Q3) atomicAdd(db + tid, colsum);
 }
 
-int cu_count() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, v = 0;
-    cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess &&
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-      cus = v;
-  }
-  return cus;
-}
-
 template <int D>
 int launch(float* y, const float* dqkv, int64_t rows, const float* W, float* dW, float* db, hipStream_t s) {
   constexpr int WD = 4 * D, NCT = D / 32;
   const size_t lds = ((size_t)2 * kRows * WD + (size_t)2 * (4 - NCT) * 1024) * sizeof(float);   // 80 KB at D = 64
   if (int rc = sagnn::ensure_dynamic_lds(reinterpret_cast<const void*>(&attn_bwd_tail_kernel<D>), lds)) return rc;
   const int64_t n_chunks = (rows + kRows - 1) / kRows;
-  const int64_t want = 2 * (int64_t)cu_count();
+  const int64_t want = 2 * (int64_t)sagnn::cu_count_current();
   const int64_t blocks = n_chunks < want ? n_chunks : want;
   hipLaunchKernelGGL(attn_bwd_tail_kernel<D>, dim3((unsigned)blocks), dim3(kBlock), lds, s, y, dqkv, rows, W, dW, db,
                      n_chunks);
@@ -260,18 +248,22 @@ int launch(float* y, const float* dqkv, int64_t rows, const float* W, float* dW,
 
 }  // namespace
 
-extern "C" int sagnn_attn_bwd_tail_supported(int d) { return (d == 32 || d == 64) && !sagnn::force_valu(); }
+extern "C" int sagnn_attn_bwd_tail_supported(int d) {
+  const sagnn::Engine e = sagnn::calling_engine();
+  return e != sagnn::Engine::Valu && sagnn::select_attn_bwd_tail(e, d) != sagnn::AttnBwdTail::None;
+}
 
 extern "C" int sagnn_attn_bwd_tail_f32(float* y, const float* dqkv, int64_t rows, int d, const float* Wqkv, float* dWqkv,
                                        float* dbqkv, void* stream) {
   if (rows < 0) return sagnn::fail(SAGNN_ERR_DIM, "bad row count");
-  if (d != 32 && d != 64) return sagnn::fail(SAGNN_ERR_DIM, "attn_bwd_tail: d must be 32 or 64 (got %d)", d);
+  const sagnn::AttnBwdTail k = sagnn::select_attn_bwd_tail(sagnn::calling_engine(), d);
+  if (k == sagnn::AttnBwdTail::None) return sagnn::fail(SAGNN_ERR_DIM, "attn_bwd_tail: d must be 32 or 64 (got %d)", d);
   if (!y || !dqkv || !Wqkv || !dWqkv || !dbqkv) return sagnn::fail(SAGNN_ERR_NULL, "null tensor pointer");
   if (!sagnn::aligned16(y) || !sagnn::aligned16(dqkv) || !sagnn::aligned16(Wqkv))
     return sagnn::fail(SAGNN_ERR_ALIGN, "attn_bwd_tail: need 16-byte aligned buffers");
   if (rows == 0) return SAGNN_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (!sagnn::force_f32_mfma()) return sagnn::attn_bwd_tail_f16(y, dqkv, rows, d, Wqkv, dWqkv, dbqkv, s);
+  if (k == sagnn::AttnBwdTail::F16x2) return sagnn::attn_bwd_tail_f16(y, dqkv, rows, d, Wqkv, dWqkv, dbqkv, s);
   if (d == 64) return launch<64>(y, dqkv, rows, Wqkv, dWqkv, dbqkv, s);
   return launch<32>(y, dqkv, rows, Wqkv, dWqkv, dbqkv, s);
 }

@@ -537,11 +537,6 @@ __global__ __launch_bounds__(64 * (D >= 64 ? 4 : D / 16), (D == 128 || (BWD && T
 
 namespace sagnn {
 
-bool mhsa_split_supported(int d, int t, int heads) {
-  if (heads != 16 || !(d == 32 || d == 64 || d == 128)) return false;
-  return (t >= 1 && t <= 6) || t == 8 || t == 12 || t == 16;
-}
-
 template <int D, int T, bool BWD = false>
 static int launch_split(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, const float* gamma, const float* beta,
                         float eps, int apply_ln, const float* Wq, const float* bq, const float* Wk, const float* bk,
@@ -594,12 +589,6 @@ int ln_mhsa_mean_split(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, in
 // pair up to t = 6, 2 lanes at t = 8 / 12 and 4 at t = 16, one workgroup per CU above t = 8 for the registers; d = 128,
 // t <= 6: d_k = 8, one lane per pair, a pair's k / v / dk vectors take 144 of the 512 registers of a one-workgroup-per-CU wave):
 // y = LN(x) (or x), Q|K|V, attention backward -> dqkv [n*t, 3d] and, when y is not NULL, y [n*t, d].
-bool attn_bwd_front_split_supported(int d, int t, int heads) {
-  if (heads != 16) return false;
-  if (d == 128) return t >= 1 && t <= 6;
-  return (d == 32 || d == 64) && ((t >= 1 && t <= 6) || t == 8 || t == 12 || t == 16);
-}
-
 template <int D>
 static int dispatch_bwd_t(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, const float* gamma, const float* beta,
                           float eps, int apply_ln, const float* Wq, const float* bq, const float* Wk, const float* bk,

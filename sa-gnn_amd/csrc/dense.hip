@@ -257,26 +257,14 @@ __global__ __launch_bounds__(kBlock, TPW <= 4 ? 2 : 1) void dense_tn_kernel(cons
   if (db && (int)threadIdx.x < dout) atomicAdd(db + threadIdx.x, colsum);
 }
 
-int cu_count() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, v = 0;
-    cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess &&
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-      cus = v;
-  }
-  return cus;
-}
-
 template <int CT>
 int launch_nn(const float* X, int64_t ldx, int64_t n, int din, const float* W, int64_t ldw, const float* bias,
               float* Y, int64_t ldy, int accumulate, hipStream_t s) {
   const size_t lds = ((size_t)din * CT * 32 + 4 * 32 * 32) * sizeof(float);
   if (lds > 160 * 1024) return sagnn::fail(SAGNN_ERR_DIM, "dense_nn: W %d x %d does not fit LDS", din, CT * 32);
   if (int rc = sagnn::ensure_dynamic_lds(reinterpret_cast<const void*>(&dense_nn_kernel<CT>), lds)) return rc;
-  const int64_t n_tiles = (n + 127) / 128;
-  const int64_t blocks = n_tiles < cu_count() ? n_tiles : cu_count();
+  const int64_t n_tiles = (n + 127) / 128, cus = sagnn::cu_count_current();
+  const int64_t blocks = n_tiles < cus ? n_tiles : cus;
   hipLaunchKernelGGL(dense_nn_kernel<CT>, dim3((unsigned)blocks), dim3(kBlock), lds, s, X, ldx, n, din, W, ldw, bias,
                      Y, ldy, accumulate, n_tiles);
   SAGNN_HIP_TRY(hipGetLastError());
@@ -289,7 +277,7 @@ int launch_tn_rc(const float* X, int64_t ldx, const float* G, int64_t ldg, int64
   const size_t lds = (size_t)2 * RC * (din + dout) * sizeof(float);
   if (int rc = sagnn::ensure_dynamic_lds(reinterpret_cast<const void*>(&dense_tn_kernel<TPW, RC, NV>), lds)) return rc;
   const int64_t n_chunks = (n + RC - 1) / RC;
-  const int64_t want = (int64_t)cu_count() * ((TPW <= 4 && lds <= 72 * 1024) ? 2 : 1);
+  const int64_t want = (int64_t)sagnn::cu_count_current() * ((TPW <= 4 && lds <= 72 * 1024) ? 2 : 1);
   const int64_t blocks = n_chunks < want ? n_chunks : want;
   hipLaunchKernelGGL((dense_tn_kernel<TPW, RC, NV>), dim3((unsigned)blocks), dim3(kBlock), lds, s, X, ldx, G, ldg, n,
                      din, dout, dW, lddw, db, n_chunks);

@@ -305,8 +305,6 @@ int mhsa_mean_valu(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t,
 
 namespace sagnn {
 
-bool wide_supported(int d) { return d % 32 == 0 && d >= 32 && d <= 256; }
-
 // MHSA + mean for any d % 32 == 0: Q|K|V by three MFMA products per interval into ws [n, t, 3d],
 // then the per-node attention kernel.
 int mhsa_mean_wide(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int d, int heads, const float* Wq,
@@ -357,38 +355,59 @@ extern "C" int sagnn_mhsa_mean_wide_f32(const float* x, int64_t ld_n, int64_t ld
                                static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
 }
 
-extern "C" int sagnn_lstm_fwd_state_f32(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int d,
-                                        const float* W, const float* b, float forget_bias,
-                                        const float* drop_scale, const float* h_init, int64_t ld_hi,
-                                        const float* c_init, float* h, int64_t ld_h, float* c_final, void* stream) {
+// The three LSTM forward entries: inference (h_init / c_init / c_final optional) and training (gates / cell saved).
+static int lstm_fwd(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int d, const float* W, const float* b,
+                    float forget_bias, const float* drop, float* h, int64_t ld_h, bool train, float* gates, float* cell,
+                    const float* h_init, int64_t ld_hi, const float* c_init, float* c_final, void* stream) {
   if (int rc = check_dims(n, t, d)) return rc;
-  if (!x || !W || !b || !h) return sagnn::fail(SAGNN_ERR_NULL, "null tensor pointer");
+  if (!x || !W || !b || !h || (train && (!gates || !cell))) return sagnn::fail(SAGNN_ERR_NULL, "null tensor pointer");
   if ((h_init == nullptr) != (c_init == nullptr)) return sagnn::fail(SAGNN_ERR_NULL, "give both h_init and c_init or neither");
   if (int rc = check_strides(ld_n, ld_t, n, t, d)) return rc;
   if (ld_h < (int64_t)t * d) return sagnn::fail(SAGNN_ERR_ARG, "ld_h smaller than t*d");
   if (h_init && ld_hi < d) return sagnn::fail(SAGNN_ERR_ARG, "ld_hi smaller than d");
   if (n == 0) return SAGNN_OK;
-  // matrix-core path: d = 32 / 64 with 16-byte aligned rows; SAGNN_FUSION=valu forces the
-  // VALU formulation (A/B runs)
-  const bool vec_ok = sagnn::aligned16(x) && (ld_n & 3) == 0 && (ld_t & 3) == 0 &&
-                      (!h_init || (sagnn::aligned16(h_init) && (ld_hi & 3) == 0));
+  const bool vec = sagnn::aligned16(x) && (ld_n & 3) == 0 && (ld_t & 3) == 0 &&
+                   (!h_init || (sagnn::aligned16(h_init) && (ld_hi & 3) == 0));
+  const bool h_vec = (ld_h & 3) == 0 && sagnn::aligned16(h);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (sagnn::lstm_mfma_supported(d) && vec_ok && !sagnn::force_valu())
-    return sagnn::lstm_fwd_mfma(x, ld_n, ld_t, n, t, d, W, b, forget_bias, drop_scale, h, ld_h, nullptr, nullptr, h_init,
-                                ld_hi, c_init, c_final, s);
-  if (sagnn::lstm_split128_supported(d) && vec_ok && !drop_scale && (ld_h & 3) == 0 && sagnn::aligned16(h) &&
-      !sagnn::force_valu() && !sagnn::force_f32_mfma())
-    return sagnn::lstm_fwd_split128(x, ld_n, ld_t, n, t, W, b, forget_bias, nullptr, h, ld_h, nullptr, nullptr, h_init, ld_hi,
-                                    c_init, c_final, s);
-  return sagnn::lstm_fwd_valu(x, ld_n, ld_t, n, t, d, W, b, forget_bias, drop_scale, h, ld_h, nullptr, nullptr, h_init,
-                              ld_hi, c_init, c_final, s);
+  switch (sagnn::select_lstm_fwd(sagnn::calling_engine(), d, t, vec, ld_h, h_vec, train, drop != nullptr,
+                                 !drop || sagnn::aligned16(drop))) {
+    case sagnn::LstmFwd::F16x2:
+      return sagnn::lstm_fwd_f16(x, ld_n, ld_t, n, t, d, W, b, forget_bias, drop, h, ld_h, gates, cell, h_init, ld_hi, c_init,
+                                 c_final, s);
+    case sagnn::LstmFwd::F32Mfma:
+      return sagnn::lstm_fwd_mfma(x, ld_n, ld_t, n, t, d, W, b, forget_bias, drop, h, ld_h, gates, cell, h_init, ld_hi, c_init,
+                                  c_final, s);
+    case sagnn::LstmFwd::Split128:
+      return sagnn::lstm_fwd_split128(x, ld_n, ld_t, n, t, W, b, forget_bias, drop, h, ld_h, gates, cell, h_init, ld_hi, c_init,
+                                      c_final, s);
+    default:
+      return sagnn::lstm_fwd_valu(x, ld_n, ld_t, n, t, d, W, b, forget_bias, drop, h, ld_h, gates, cell, h_init, ld_hi, c_init,
+                                  c_final, s);
+  }
+}
+
+extern "C" int sagnn_lstm_fwd_state_f32(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int d,
+                                        const float* W, const float* b, float forget_bias,
+                                        const float* drop_scale, const float* h_init, int64_t ld_hi,
+                                        const float* c_init, float* h, int64_t ld_h, float* c_final, void* stream) {
+  return lstm_fwd(x, ld_n, ld_t, n, t, d, W, b, forget_bias, drop_scale, h, ld_h, false, nullptr, nullptr, h_init, ld_hi,
+                  c_init, c_final, stream);
 }
 
 extern "C" int sagnn_lstm_fwd_f32(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int d,
                                   const float* W, const float* b, float forget_bias,
                                   const float* drop_scale, float* h, int64_t ld_h, void* stream) {
-  return sagnn_lstm_fwd_state_f32(x, ld_n, ld_t, n, t, d, W, b, forget_bias, drop_scale, nullptr, 0, nullptr, h, ld_h,
-                                  nullptr, stream);
+  return lstm_fwd(x, ld_n, ld_t, n, t, d, W, b, forget_bias, drop_scale, h, ld_h, false, nullptr, nullptr, nullptr, 0, nullptr,
+                  nullptr, stream);
+}
+
+extern "C" int sagnn_lstm_fwd_train_f32(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int d,
+                                        const float* W, const float* b, float forget_bias,
+                                        const float* drop_scale, float* h, int64_t ld_h, float* gates,
+                                        float* cell, void* stream) {
+  return lstm_fwd(x, ld_n, ld_t, n, t, d, W, b, forget_bias, drop_scale, h, ld_h, true, gates, cell, nullptr, 0, nullptr,
+                  nullptr, stream);
 }
 
 extern "C" int sagnn_layernorm_td_f32(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int d,
@@ -408,11 +427,16 @@ extern "C" int sagnn_layernorm_td_f32(const float* x, int64_t ld_n, int64_t ld_t
   return SAGNN_OK;
 }
 
-// layer norm + Q|K|V + attention + mean in ONE kernel: the f32-MFMA kernel (d = 32 / 64) or the split-bf16 one
-// (d = 32 / 64 / 128, 16 heads, specialised interval counts)
-static bool fused_attention(int d, int t, int heads) {
-  if (sagnn::force_valu()) return false;
-  return sagnn::mhsa_mfma_supported(d, t, heads) || (sagnn::mhsa_split_supported(d, t, heads) && !sagnn::force_f32_mfma());
+// layer norm + Q|K|V + attention + mean in ONE kernel: AttnFwd::Split or AttnFwd::F32Mfma
+static bool fused(sagnn::AttnFwd k) { return k == sagnn::AttnFwd::Split || k == sagnn::AttnFwd::F32Mfma; }
+
+static int fused_attention(sagnn::AttnFwd k, const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int d, int heads,
+                           const float* gamma, const float* beta, float eps, int apply_ln, const float* Wq, const float* bq,
+                           const float* Wk, const float* bk, const float* Wv, const float* bv, float* out, int64_t ld_out,
+                           void* stream) {
+  const auto launch = k == sagnn::AttnFwd::Split ? sagnn::ln_mhsa_mean_split : sagnn::ln_mhsa_mean_mfma;
+  return launch(x, ld_n, ld_t, n, t, d, heads, gamma, beta, eps, apply_ln, Wq, bq, Wk, bk, Wv, bv, out, ld_out,
+                static_cast<hipStream_t>(stream));
 }
 
 extern "C" int sagnn_mhsa_mean_f32(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int d, int heads,
@@ -426,20 +450,21 @@ extern "C" int sagnn_mhsa_mean_f32(const float* x, int64_t ld_n, int64_t ld_t, i
   if (int rc = check_strides(ld_n, ld_t, n, t, d)) return rc;
   if (ld_out < d) return sagnn::fail(SAGNN_ERR_ARG, "ld_out smaller than d");
   if (n == 0) return SAGNN_OK;
-  const bool vec_ok = sagnn::aligned16(x) && (ld_n & 3) == 0 && (ld_t & 3) == 0;
-  if (fused_attention(d, t, heads) && vec_ok)
-    return sagnn::ln_mhsa_mean_mfma(x, ld_n, ld_t, n, t, d, heads, nullptr, nullptr, 0.f, 0, Wq, bq, Wk,
-                                    bk, Wv, bv, out, ld_out, static_cast<hipStream_t>(stream));
-  return sagnn::mhsa_mean_valu(x, ld_n, ld_t, n, t, d, heads, Wq, bq, Wk, bk, Wv, bv, out, ld_out,
+  const bool vec = sagnn::aligned16(x) && (ld_n & 3) == 0 && (ld_t & 3) == 0;
+  const sagnn::AttnFwd k = sagnn::select_attn_fwd(sagnn::calling_engine(), d, t, heads, vec);
+  if (fused(k))
+    return fused_attention(k, x, ld_n, ld_t, n, t, d, heads, nullptr, nullptr, 0.f, 0, Wq, bq, Wk, bk, Wv, bv, out, ld_out,
+                           stream);
+  return sagnn::mhsa_mean_valu(x, ld_n, ld_t, n, t, d, heads, Wq, bq, Wk, bk, Wv, bv, out, ld_out,   // Wide too: no workspace
                                static_cast<hipStream_t>(stream));
 }
-
-static bool use_wide(int d) { return !sagnn::lstm_mfma_supported(d) && sagnn::wide_supported(d) && !sagnn::force_valu(); }
 
 extern "C" size_t sagnn_interval_fusion_workspace_bytes(int64_t n, int t, int d) {
   if (n <= 0 || t <= 0 || d <= 0) return 0;
   size_t bytes = (size_t)n * (size_t)t * (size_t)d * sizeof(float);  // h, normalised in place
-  if (use_wide(d)) bytes += sagnn_mhsa_wide_workspace_bytes(n, t, d);  // Q|K|V of the wide attention (when it is taken)
+  // Q|K|V wherever the wide attention is the fall-back (no heads here: also where a fused kernel is taken)
+  if (sagnn::select_attn_fwd(sagnn::calling_engine(), d, t, 1, false) == sagnn::AttnFwd::Wide)
+    bytes += sagnn_mhsa_wide_workspace_bytes(n, t, d);
   return bytes;
 }
 
@@ -461,20 +486,16 @@ extern "C" int sagnn_interval_fusion_f32(const float* x, int64_t ld_n, int64_t l
   if (!ln_gamma || !ln_beta || !Wq || !bq || !Wk || !bk || !Wv || !bv || !out)
     return sagnn::fail(SAGNN_ERR_NULL, "null tensor pointer");
   if (n == 0) return SAGNN_OK;
-  if (use_wide(d) && !fused_attention(d, t, heads)) {  // d = 96, 160, ...: MFMA products + per-node kernel for the attention
-    float* scratch = h + n * ldw;
-    const size_t sbytes = workspace_bytes - (size_t)n * ldw * sizeof(float);
-    if (int rc = sagnn_lstm_fwd_f32(x, ld_n, ld_t, n, t, d, lstm_W, lstm_b, forget_bias, nullptr, h, ldw, stream)) return rc;
-    if (int rc = sagnn_layernorm_td_f32(h, ldw, d, n, t, d, ln_gamma, ln_beta, ln_eps, h, ldw, stream)) return rc;
-    return sagnn_mhsa_mean_wide_f32(h, ldw, d, n, t, d, heads, Wq, bq, Wk, bk, Wv, bv, out, ld_out, scratch, sbytes, stream);
-  }
+  const sagnn::AttnFwd k = sagnn::select_attn_fwd(sagnn::calling_engine(), d, t, heads, true);   // h: workspace rows
   if (int rc = sagnn_lstm_fwd_f32(x, ld_n, ld_t, n, t, d, lstm_W, lstm_b, forget_bias, nullptr, h, ldw, stream)) return rc;
-  // layer norm rides on the attention kernel's A operand when the matrix-core path applies:
-  // h is read once and never rewritten
-  if (fused_attention(d, t, heads))
-    return sagnn::ln_mhsa_mean_mfma(h, ldw, d, n, t, d, heads, ln_gamma, ln_beta, ln_eps, 1, Wq, bq, Wk, bk,
-                                    Wv, bv, out, ld_out, static_cast<hipStream_t>(stream));
+  // layer norm rides on the fused kernel's A operand: h is read once and never rewritten
+  if (fused(k))
+    return fused_attention(k, h, ldw, d, n, t, d, heads, ln_gamma, ln_beta, ln_eps, 1, Wq, bq, Wk, bk, Wv, bv, out, ld_out,
+                           stream);
   if (int rc = sagnn_layernorm_td_f32(h, ldw, d, n, t, d, ln_gamma, ln_beta, ln_eps, h, ldw, stream)) return rc;
+  if (k == sagnn::AttnFwd::Wide)   // d = 96, 160, ...: MFMA products + per-node kernel
+    return sagnn_mhsa_mean_wide_f32(h, ldw, d, n, t, d, heads, Wq, bq, Wk, bk, Wv, bv, out, ld_out, h + n * ldw,
+                                    workspace_bytes - (size_t)n * ldw * sizeof(float), stream);
   return sagnn_mhsa_mean_f32(h, ldw, d, n, t, d, heads, Wq, bq, Wk, bk, Wv, bv, out, ld_out, stream);
 }
 
@@ -483,9 +504,10 @@ extern "C" int sagnn_interval_fusion_f32(const float* x, int64_t ld_n, int64_t l
 // forward runs the LSTM separately (it stores gates / cell) and comes here with the emitted h.
 extern "C" size_t sagnn_ln_mhsa_mean_workspace_bytes(int64_t n, int t, int d, int heads) {
   if (n <= 0 || t <= 0 || d <= 0) return 0;
-  if (fused_attention(d, t, heads)) return 0;  // normalised on the way into the product
+  const sagnn::AttnFwd k = sagnn::select_attn_fwd(sagnn::calling_engine(), d, t, heads, true);
+  if (fused(k)) return 0;  // normalised on the way into the product
   size_t bytes = (size_t)n * (size_t)t * (size_t)d * sizeof(float);
-  if (use_wide(d)) bytes += sagnn_mhsa_wide_workspace_bytes(n, t, d);
+  if (k == sagnn::AttnFwd::Wide) bytes += sagnn_mhsa_wide_workspace_bytes(n, t, d);
   return bytes;
 }
 
@@ -501,28 +523,30 @@ extern "C" int sagnn_ln_mhsa_mean_f32(const float* x, int64_t ld_n, int64_t ld_t
   if (int rc = check_strides(ld_n, ld_t, n, t, d)) return rc;
   if (ld_out < d) return sagnn::fail(SAGNN_ERR_ARG, "ld_out smaller than d");
   if (n == 0) return SAGNN_OK;
-  const bool vec_ok = sagnn::aligned16(x) && (ld_n & 3) == 0 && (ld_t & 3) == 0;
-  if (fused_attention(d, t, heads) && vec_ok)
-    return sagnn::ln_mhsa_mean_mfma(x, ld_n, ld_t, n, t, d, heads, ln_gamma, ln_beta, ln_eps, 1, Wq, bq, Wk, bk,
-                                    Wv, bv, out, ld_out, static_cast<hipStream_t>(stream));
+  const bool vec = sagnn::aligned16(x) && (ld_n & 3) == 0 && (ld_t & 3) == 0;
+  const sagnn::AttnFwd k = sagnn::select_attn_fwd(sagnn::calling_engine(), d, t, heads, vec);
+  if (fused(k))
+    return fused_attention(k, x, ld_n, ld_t, n, t, d, heads, ln_gamma, ln_beta, ln_eps, 1, Wq, bq, Wk, bk, Wv, bv, out, ld_out,
+                           stream);
   const size_t ybytes = (size_t)n * t * d * sizeof(float);
-  size_t need = ybytes + (use_wide(d) ? sagnn_mhsa_wide_workspace_bytes(n, t, d) : 0);
+  size_t need = ybytes + (k == sagnn::AttnFwd::Wide ? sagnn_mhsa_wide_workspace_bytes(n, t, d) : 0);
   if (!workspace || workspace_bytes < need)
     return sagnn::fail(SAGNN_ERR_WORKSPACE, "ln_mhsa_mean workspace needs %zu bytes", need);
   float* y = static_cast<float*>(workspace);
   const int64_t ldw = (int64_t)t * d;
   if (int rc = sagnn_layernorm_td_f32(x, ld_n, ld_t, n, t, d, ln_gamma, ln_beta, ln_eps, y, ldw, stream)) return rc;
-  if (use_wide(d))
+  if (k == sagnn::AttnFwd::Wide)
     return sagnn_mhsa_mean_wide_f32(y, ldw, d, n, t, d, heads, Wq, bq, Wk, bk, Wv, bv, out, ld_out, y + n * ldw,
                                     workspace_bytes - ybytes, stream);
   return sagnn_mhsa_mean_f32(y, ldw, d, n, t, d, heads, Wq, bq, Wk, bk, Wv, bv, out, ld_out, stream);
 }
 
-// Front of the attention backward pass in one launch (d in {32, 64}, d_k in {2, 4}, t in {1..6, 8}):
-// y = LN(x) (apply_ln) or x, Q|K|V = y W + b on the matrix cores, attention backward per (node, head)
-// in registers -> dqkv [n*t, 3d]; y [n*t, d] is written when y_out is given (operand of dW = y^T dQKV).
+// Front of the attention backward pass in one launch (shapes: engine.cpp): y = LN(x) (apply_ln) or x, Q|K|V = y W + b on
+// the matrix cores, attention backward per (node, head) in registers -> dqkv [n*t, 3d]; y [n*t, d] is written when y_out
+// is given (operand of dW = y^T dQKV).
 extern "C" int sagnn_attn_bwd_front_supported(int d, int t, int heads) {
-  return sagnn::attn_bwd_front_supported(d, t, heads) && !sagnn::force_valu();
+  const sagnn::Engine e = sagnn::calling_engine();
+  return e != sagnn::Engine::Valu && sagnn::select_attn_bwd_front(e, d, t, heads) != sagnn::AttnBwdFront::None;
 }
 
 extern "C" int sagnn_attn_bwd_front_f32(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int d, int heads,
@@ -531,7 +555,8 @@ extern "C" int sagnn_attn_bwd_front_f32(const float* x, int64_t ld_n, int64_t ld
                                         const float* Wv, const float* bv, const float* g_out, int64_t ld_g,
                                         float* dqkv, float* y_out, void* stream) {
   if (int rc = check_dims(n, t, d)) return rc;
-  if (!sagnn::attn_bwd_front_supported(d, t, heads))
+  const sagnn::AttnBwdFront k = sagnn::select_attn_bwd_front(sagnn::calling_engine(), d, t, heads);
+  if (k == sagnn::AttnBwdFront::None)
     return sagnn::fail(SAGNN_ERR_DIM, "attn_bwd_front: unsupported d = %d, t = %d, heads = %d", d, t, heads);
   if (!x || !Wq || !bq || !Wk || !bk || !Wv || !bv || !g_out || !dqkv || (apply_ln && (!ln_gamma || !ln_beta)))
     return sagnn::fail(SAGNN_ERR_NULL, "null tensor pointer");
@@ -541,27 +566,7 @@ extern "C" int sagnn_attn_bwd_front_f32(const float* x, int64_t ld_n, int64_t ld
       !sagnn::aligned16(dqkv) || (y_out && !sagnn::aligned16(y_out)))
     return sagnn::fail(SAGNN_ERR_ALIGN, "attn_bwd_front: need 16-byte aligned rows");
   if (n == 0) return SAGNN_OK;
-  return sagnn::attn_bwd_front_mfma(x, ld_n, ld_t, n, t, d, heads, ln_gamma, ln_beta, ln_eps, apply_ln, Wq, bq, Wk, bk,
-                                    Wv, bv, g_out, ld_g, dqkv, y_out, static_cast<hipStream_t>(stream));
-}
-
-extern "C" int sagnn_lstm_fwd_train_f32(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int d,
-                                        const float* W, const float* b, float forget_bias,
-                                        const float* drop_scale, float* h, int64_t ld_h, float* gates,
-                                        float* cell, void* stream) {
-  if (int rc = check_dims(n, t, d)) return rc;
-  if (!x || !W || !b || !h || !gates || !cell) return sagnn::fail(SAGNN_ERR_NULL, "null tensor pointer");
-  if (int rc = check_strides(ld_n, ld_t, n, t, d)) return rc;
-  if (ld_h < (int64_t)t * d) return sagnn::fail(SAGNN_ERR_ARG, "ld_h smaller than t*d");
-  if (n == 0) return SAGNN_OK;
-  const bool vec_ok = sagnn::aligned16(x) && (ld_n & 3) == 0 && (ld_t & 3) == 0;
-  if (sagnn::lstm_mfma_supported(d) && vec_ok && !sagnn::force_valu())
-    return sagnn::lstm_fwd_mfma(x, ld_n, ld_t, n, t, d, W, b, forget_bias, drop_scale, h, ld_h, gates, cell, nullptr, 0,
-                                nullptr, nullptr, static_cast<hipStream_t>(stream));
-  if (sagnn::lstm_split128_supported(d) && vec_ok && (ld_h & 3) == 0 && sagnn::aligned16(h) &&
-      (!drop_scale || sagnn::aligned16(drop_scale)) && !sagnn::force_valu() && !sagnn::force_f32_mfma())
-    return sagnn::lstm_fwd_split128(x, ld_n, ld_t, n, t, W, b, forget_bias, drop_scale, h, ld_h, gates, cell, nullptr, 0, nullptr,
-                                    nullptr, static_cast<hipStream_t>(stream));
-  return sagnn::lstm_fwd_valu(x, ld_n, ld_t, n, t, d, W, b, forget_bias, drop_scale, h, ld_h, gates, cell, nullptr, 0,
-                              nullptr, nullptr, static_cast<hipStream_t>(stream));
+  const auto launch = k == sagnn::AttnBwdFront::Split ? sagnn::attn_bwd_front_split : sagnn::attn_bwd_front_mfma;
+  return launch(x, ld_n, ld_t, n, t, d, heads, ln_gamma, ln_beta, ln_eps, apply_ln, Wq, bq, Wk, bk, Wv, bv, g_out, ld_g, dqkv,
+                y_out, static_cast<hipStream_t>(stream));
 }

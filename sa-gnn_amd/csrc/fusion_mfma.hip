@@ -938,8 +938,6 @@ __global__ __launch_bounds__(kBlock, 1) void ln_mhsa_mean_mfma_kernel(
 
 namespace sagnn {
 
-bool lstm_mfma_supported(int d) { return d == 32 || d == 64; }
-
 template <int D, bool SAVE>
 static int launch_lstm_mfma(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t,
                             const float* W, const float* b, float forget_bias, const float* drop,
@@ -947,11 +945,7 @@ static int launch_lstm_mfma(const float* x, int64_t ld_n, int64_t ld_t, int64_t 
                             int64_t ld_hi, const float* c_init, float* c_final, hipStream_t s) {
   const size_t lds = (size_t)(2 * D * 4 * D + 4 * kRowsPerWave * D) * sizeof(float);
   if (int rc = sagnn::ensure_dynamic_lds(reinterpret_cast<const void*>(&lstm_fwd_mfma_kernel<D, SAVE>), lds)) return rc;
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-  }
+  const int cus = cu_count_current();
   const int64_t n_tiles = (n + kRowsPerBlock - 1) / kRowsPerBlock;
   const int64_t blocks = n_tiles < cus ? n_tiles : cus;
   ProfileScope prof(kProfLstm, s, n, t);
@@ -966,10 +960,6 @@ int lstm_fwd_mfma(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, 
                   float* gates_out, float* c_out, const float* h_init, int64_t ld_hi, const float* c_init,
                   float* c_final, hipStream_t s) {
   const bool save = gates_out != nullptr;
-  const bool split_ok = !force_f32_mfma() && !(save && drop) && ld_h < (1 << 22) && (int64_t)t * d < (1 << 18);
-  if (lstm_f16_supported(d) && split_ok)
-    return lstm_fwd_f16(x, ld_n, ld_t, n, t, d, W, b, forget_bias, drop, h, ld_h, gates_out, c_out, h_init, ld_hi, c_init,
-                        c_final, s);
   // 32-row tiles are addressed with 32-bit byte offsets from a per-tile base
   if (ld_n >= (1 << 24) || ld_h >= (1 << 24) || (int64_t)t * d >= (1 << 20))
     return fail(SAGNN_ERR_ARG, "MFMA LSTM: row strides must stay below 2^24 floats");
@@ -983,12 +973,6 @@ int lstm_fwd_mfma(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, 
   return fail(SAGNN_ERR_DIM, "MFMA LSTM supports d = 32 or 64, got %d", d);
 }
 
-bool mhsa_mfma_supported(int d, int t, int heads) {
-  if (!(d == 32 || d == 64) || t < 1 || t > 32 || heads < 1 || d % heads) return false;
-  const int dk = d / heads;
-  return (dk & (dk - 1)) == 0;  // the per-head lane reduction needs a power of two
-}
-
 template <int D, int TT, bool BWD>
 static int launch_ln_mhsa_t(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int heads,
                             const float* gamma, const float* beta, float eps, int apply_ln,
@@ -997,11 +981,7 @@ static int launch_ln_mhsa_t(const float* x, int64_t ld_n, int64_t ld_t, int64_t 
                             float* dqkv_out, float* y_out, hipStream_t s) {
   const size_t lds = (size_t)(3 * D * D + 4 * kRowsPerWave * (3 * D + 4)) * sizeof(float);
   if (int rc = sagnn::ensure_dynamic_lds(reinterpret_cast<const void*>(&ln_mhsa_mean_mfma_kernel<D, TT, BWD>), lds)) return rc;
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-  }
+  const int cus = cu_count_current();
   const int64_t nodes_per_tile = 4 * (kRowsPerWave / t);
   const int64_t n_tiles = (n + nodes_per_tile - 1) / nodes_per_tile;
   const int64_t blocks = n_tiles < cus ? n_tiles : cus;
@@ -1035,22 +1015,11 @@ int ln_mhsa_mean_mfma(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int
                       const float* gamma, const float* beta, float eps, int apply_ln, const float* Wq,
                       const float* bq, const float* Wk, const float* bk, const float* Wv,
                       const float* bv, float* out, int64_t ld_out, hipStream_t s) {
-  if (mhsa_split_supported(d, t, heads) && !force_f32_mfma())
-    return ln_mhsa_mean_split(x, ld_n, ld_t, n, t, d, heads, gamma, beta, eps, apply_ln, Wq, bq, Wk, bk, Wv, bv, out,
-                              ld_out, s);
   if (d == 64)
     return launch_ln_mhsa<64>(x, ld_n, ld_t, n, t, heads, gamma, beta, eps, apply_ln, Wq, bq, Wk, bk, Wv, bv, out, ld_out, s);
   if (d == 32)
     return launch_ln_mhsa<32>(x, ld_n, ld_t, n, t, heads, gamma, beta, eps, apply_ln, Wq, bq, Wk, bk, Wv, bv, out, ld_out, s);
   return fail(SAGNN_ERR_DIM, "MFMA attention supports d = 32 or 64, got %d", d);
-}
-
-bool attn_bwd_front_supported(int d, int t, int heads) {
-  if (d == 128) return attn_bwd_front_split_supported(d, t, heads) && !force_f32_mfma();   // split engine only (attn_split.hip)
-  if (attn_bwd_front_split_supported(d, t, heads) && !force_f32_mfma()) return true;   // t = 12 / 16: split engine only
-  if (!mhsa_mfma_supported(d, t, heads)) return false;
-  const int dk = d / heads;
-  return (dk == 2 || dk == 4) && ((t >= 1 && t <= 6) || t == 8);
 }
 
 template <int D>
@@ -1072,9 +1041,6 @@ int attn_bwd_front_mfma(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, i
                         const float* gamma, const float* beta, float eps, int apply_ln, const float* Wq,
                         const float* bq, const float* Wk, const float* bk, const float* Wv, const float* bv,
                         const float* g_out, int64_t ld_g, float* dqkv, float* y, hipStream_t s) {
-  if (attn_bwd_front_split_supported(d, t, heads) && !force_f32_mfma())
-    return attn_bwd_front_split(x, ld_n, ld_t, n, t, d, heads, gamma, beta, eps, apply_ln, Wq, bq, Wk, bk, Wv, bv, g_out, ld_g,
-                                dqkv, y, s);
   if (d == 64)
     return launch_attn_bwd_front<64>(x, ld_n, ld_t, n, t, heads, gamma, beta, eps, apply_ln, Wq, bq, Wk, bk, Wv, bv, g_out, ld_g, dqkv, y, s);
   if (d == 32)

@@ -405,24 +405,12 @@ __global__ __launch_bounds__(kBlock, 1) void lstm_bwd_mfma_kernel(
   }
 }
 
-int cu_count() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, v = 0;
-    cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess &&
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-      cus = v;
-  }
-  return cus;
-}
-
 template <int D, bool DW = true>
 int launch(const float* x, int64_t ld_n, int64_t ld_t, const float* h, const float* gates, const float* cell,
            const float* dh_ext, int64_t ld_dhe, const float* drop, const float* W, float* dx, float* dW, float* db,
            int64_t n, int t, hipStream_t s, float* dg_out = nullptr) {
-  const int64_t n_chunks = (n + kRows - 1) / kRows;
-  const int64_t blocks = n_chunks < cu_count() ? n_chunks : cu_count();
+  const int64_t n_chunks = (n + kRows - 1) / kRows, cus = sagnn::cu_count_current();
+  const int64_t blocks = n_chunks < cus ? n_chunks : cus;
   const int nq = 4 * D / 8, ql = nq - (D == 64 ? 2 : 0), nw1 = 2 * D / 32;
   const size_t lds = (size_t)kRows * (4 * D + D) * sizeof(float) + (size_t)nw1 * ql * 64 * sizeof(float4);
   if (int rc = sagnn::ensure_dynamic_lds(reinterpret_cast<const void*>(&lstm_bwd_mfma_kernel<D, DW>), lds)) return rc;
@@ -434,14 +422,12 @@ int launch(const float* x, int64_t ld_n, int64_t ld_t, const float* h, const flo
 
 }  // namespace
 
-extern "C" int sagnn_lstm_bwd_supported(int d) { return d == 32 || d == 64; }
-
-extern "C" int sagnn_lstm_bwd_f32(const float* x, int64_t ld_n, int64_t ld_t, const float* h, const float* gates,
-                                  const float* cell, const float* dh_ext, int64_t ld_dhe, const float* drop_scale,
-                                  const float* W, float* dx, float* dW, float* db, int64_t n, int t, int d,
-                                  void* stream) {
+// Argument checks of both BPTT entries; the two-pass form (workspace given) also reads x and h as 16-byte rows.
+static int check_lstm_bwd(const float* x, int64_t ld_n, int64_t ld_t, const float* h, const float* gates, const float* cell,
+                          const float* dh_ext, int64_t ld_dhe, const float* drop_scale, const float* W, float* dx, float* dW,
+                          float* db, int64_t n, int t, int d, const void* workspace) {
   if (n < 0 || t < 1) return sagnn::fail(SAGNN_ERR_DIM, "bad n/t");
-  if (!sagnn_lstm_bwd_supported(d)) return sagnn::fail(SAGNN_ERR_DIM, "lstm_bwd: d must be 32 or 64 (got %d)", d);
+  if (d != 32 && d != 64) return sagnn::fail(SAGNN_ERR_DIM, "lstm_bwd: d must be 32 or 64 (got %d)", d);
   if (!x || !h || !gates || !cell || !dh_ext || !W || !dx || !dW || !db)
     return sagnn::fail(SAGNN_ERR_NULL, "null tensor pointer");
   if (ld_n < d || (t > 1 && ld_t < d) || ld_dhe < (int64_t)t * d)
@@ -449,8 +435,22 @@ extern "C" int sagnn_lstm_bwd_f32(const float* x, int64_t ld_n, int64_t ld_t, co
   if (ld_n >= (1 << 25) || ld_dhe >= (1 << 25) || (int64_t)t * d >= (1 << 20))
     return sagnn::fail(SAGNN_ERR_ARG, "lstm_bwd: row strides must stay below 2^25 floats (32-bit lane offsets)");
   if ((ld_dhe & 3) || !sagnn::aligned16(dh_ext) || !sagnn::aligned16(gates) || !sagnn::aligned16(cell) ||
-      !sagnn::aligned16(W) || (drop_scale && !sagnn::aligned16(drop_scale)))
+      !sagnn::aligned16(W) || (drop_scale && !sagnn::aligned16(drop_scale)) ||
+      (workspace && ((ld_n & 3) || (ld_t & 3) || !sagnn::aligned16(x) || !sagnn::aligned16(h) || !sagnn::aligned16(workspace))))
     return sagnn::fail(SAGNN_ERR_ALIGN, "lstm_bwd: need 16-byte aligned rows");
+  return SAGNN_OK;
+}
+
+extern "C" int sagnn_lstm_bwd_supported(int d) {
+  return sagnn::select_lstm_bwd(sagnn::calling_engine(), d, false) != sagnn::LstmBwd::None;
+}
+
+extern "C" int sagnn_lstm_bwd_f32(const float* x, int64_t ld_n, int64_t ld_t, const float* h, const float* gates,
+                                  const float* cell, const float* dh_ext, int64_t ld_dhe, const float* drop_scale,
+                                  const float* W, float* dx, float* dW, float* db, int64_t n, int t, int d,
+                                  void* stream) {
+  if (int rc = check_lstm_bwd(x, ld_n, ld_t, h, gates, cell, dh_ext, ld_dhe, drop_scale, W, dx, dW, db, n, t, d, nullptr))
+    return rc;
   if (n == 0) return SAGNN_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (d == 64) return launch<64>(x, ld_n, ld_t, h, gates, cell, dh_ext, ld_dhe, drop_scale, W, dx, dW, db, n, t, s);
@@ -466,21 +466,10 @@ extern "C" int sagnn_lstm_bwd_ws_f32(const float* x, int64_t ld_n, int64_t ld_t,
                                      const float* cell, const float* dh_ext, int64_t ld_dhe, const float* drop_scale,
                                      const float* W, float* dx, float* dW, float* db, int64_t n, int t, int d,
                                      void* workspace, size_t workspace_bytes, void* stream) {
-  // the exact-fp32 engines keep the one-launch form (its dW product IS the fp32 MFMA); so does a call without scratch
-  if (!workspace || sagnn::force_f32_mfma() || sagnn::force_valu())
+  if (sagnn::select_lstm_bwd(sagnn::calling_engine(), d, workspace != nullptr) != sagnn::LstmBwd::SplitDw)
     return sagnn_lstm_bwd_f32(x, ld_n, ld_t, h, gates, cell, dh_ext, ld_dhe, drop_scale, W, dx, dW, db, n, t, d, stream);
-  if (n < 0 || t < 1) return sagnn::fail(SAGNN_ERR_DIM, "bad n/t");
-  if (!sagnn_lstm_bwd_supported(d)) return sagnn::fail(SAGNN_ERR_DIM, "lstm_bwd: d must be 32 or 64 (got %d)", d);
-  if (!x || !h || !gates || !cell || !dh_ext || !W || !dx || !dW || !db)
-    return sagnn::fail(SAGNN_ERR_NULL, "null tensor pointer");
-  if (ld_n < d || (t > 1 && ld_t < d) || ld_dhe < (int64_t)t * d)
-    return sagnn::fail(SAGNN_ERR_ARG, "strides smaller than the rows they address");
-  if (ld_n >= (1 << 25) || ld_dhe >= (1 << 25) || (int64_t)t * d >= (1 << 20))
-    return sagnn::fail(SAGNN_ERR_ARG, "lstm_bwd: row strides must stay below 2^25 floats (32-bit lane offsets)");
-  if ((ld_dhe & 3) || (ld_n & 3) || (ld_t & 3) || !sagnn::aligned16(x) || !sagnn::aligned16(h) || !sagnn::aligned16(dh_ext) ||
-      !sagnn::aligned16(gates) || !sagnn::aligned16(cell) || !sagnn::aligned16(W) || !sagnn::aligned16(workspace) ||
-      (drop_scale && !sagnn::aligned16(drop_scale)))
-    return sagnn::fail(SAGNN_ERR_ALIGN, "lstm_bwd: need 16-byte aligned rows");
+  if (int rc = check_lstm_bwd(x, ld_n, ld_t, h, gates, cell, dh_ext, ld_dhe, drop_scale, W, dx, dW, db, n, t, d, workspace))
+    return rc;
   if (workspace_bytes < sagnn_lstm_bwd_workspace_bytes(n, t, d))
     return sagnn::fail(SAGNN_ERR_WORKSPACE, "lstm_bwd: workspace of %zu bytes, need %zu", workspace_bytes,
                        sagnn_lstm_bwd_workspace_bytes(n, t, d));

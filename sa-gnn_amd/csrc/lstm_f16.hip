@@ -3,8 +3,6 @@
 
 namespace sagnn {
 
-bool lstm_f16_supported(int d) { return d == 32 || d == 64; }
-
 int lstm_fwd_f16(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int d, const float* W, const float* b,
                  float forget_bias, const float* drop, float* h, int64_t ld_h, float* gates_out, float* c_out,
                  const float* h_init, int64_t ld_hi, const float* c_init, float* c_final, hipStream_t s) {

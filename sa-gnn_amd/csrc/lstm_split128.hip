@@ -259,8 +259,6 @@ __global__ __launch_bounds__(256, 2) void lstm_step128_kernel(
 
 namespace sagnn {
 
-bool lstm_split128_supported(int d) { return d == 128; }
-
 template <bool SAVE, bool FIRST>
 static int launch_step(const float* x_t, int64_t ld_x, const float* h_prev, int64_t ld_hp, const float* c_prev,
                        int64_t ld_cp, const float* W, const float* b, float forget_bias, float* h_out, int64_t ld_h,

@@ -314,6 +314,46 @@ def test_engine_is_chosen_per_thread_through_the_abi():
     assert lib.sagnn_set_engine(0) == 0
 
 
+SELECTION_GOLDEN = os.path.join(ROOT, "tests", "golden", "engine_selection.npz")
+
+
+def engine_selection_sweep(lib):
+    """Every kernel-selection answer the ABI gives without a device, over engine (f16x2, f32, valu) x d in {4, 8, .., 256}
+    x t in 1..32 x heads in {1, 2, 4, .., 32}; byte counts at n = 2. tests/golden/engine_selection.npz holds this sweep of
+    the build before the selection moved into csrc/engine.cpp: np.savez_compressed(SELECTION_GOLDEN, **sweep)."""
+    ds, ts, hs = range(4, 257, 4), range(1, 33), (1, 2, 4, 8, 16, 32)
+    shape = (3, len(ds), len(ts), len(hs))
+    out = {"attn_bwd_front_supported": np.zeros(shape, np.int32), "ln_mhsa_mean_workspace_bytes": np.zeros(shape, np.int32),
+           "interval_fusion_workspace_bytes": np.zeros(shape[:3], np.int32),
+           "attn_bwd_tail_supported": np.zeros(shape[:2], np.int32), "lstm_bwd_supported": np.zeros(shape[:2], np.int32)}
+    prev = lib.sagnn_get_engine()
+    try:
+        for e in range(3):
+            assert lib.sagnn_set_engine(e) == 0
+            for i, d in enumerate(ds):
+                out["attn_bwd_tail_supported"][e, i] = lib.sagnn_attn_bwd_tail_supported(d)
+                out["lstm_bwd_supported"][e, i] = lib.sagnn_lstm_bwd_supported(d)
+                for j, t in enumerate(ts):
+                    out["interval_fusion_workspace_bytes"][e, i, j] = lib.sagnn_interval_fusion_workspace_bytes(2, t, d)
+                    for k, h in enumerate(hs):
+                        out["attn_bwd_front_supported"][e, i, j, k] = lib.sagnn_attn_bwd_front_supported(d, t, h)
+                        out["ln_mhsa_mean_workspace_bytes"][e, i, j, k] = lib.sagnn_ln_mhsa_mean_workspace_bytes(2, t, d, h)
+    finally:
+        lib.sagnn_set_engine(prev)
+    return out
+
+
+def test_engine_selection_answers_match_the_golden_sweep():
+    """The _supported and workspace queries answer from csrc/engine.cpp's selectors: a moved boundary changes a point."""
+    got = engine_selection_sweep(_lib.load())
+    want = np.load(SELECTION_GOLDEN)
+    assert sorted(want.files) == sorted(got)
+    axes = ("engine", "d", "t", "heads")
+    for name in want.files:
+        bad = np.argwhere(want[name] != got[name])
+        assert bad.size == 0, f"{name}: {len(bad)} points differ, first at {dict(zip(axes, bad[0].tolist()))} (indices)"
+
+
 def test_adam_multi_batches_skip_empty_tensors_without_stepping_any_twice():
     """More than 48 tensors (one launch's table) with an empty one among them: host-side argument walk only — the
     launch itself needs a GPU (tests/test_gpu_train.py); here the walk must terminate and reject nothing."""
