@@ -550,6 +550,55 @@ int sagnn_score_topk_f32(const float* Q, int64_t ldq, const float* I, int64_t ld
                          int32_t* topk_items, float* topk_scores, int64_t* target_rank, void* workspace,
                          size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Device sampling of the training batch (sampler.hip): the reference's sampleTrainBatch / negSamp /
+ * sampleSslBatch (model.py:252-339, DataHandler.py:28-41) drawn by HIP kernels, and the head's masked sums
+ * (model.py:161-162) read straight from the sampled sequence segments.
+ * Random numbers: Philox4x32-10, key = seed (low word first), counter = (user id, draw index j, step, stream);
+ *   a uniform integer on [0, n) is the high 64 bits of ((w0 << 32) | w1) * n from the first two output words
+ *   (bias <= n / 2^64). Streams: 0 = the positive's `choose` (j = 0), 1 = negative j, 2 + k = SSL draw j of interval k
+ *   (pair p is draws 2p and 2p + 1). A user's draws are a pure function of (seed, step, user id).
+ * Sequences: seq_ptr [n_users + 1] (int64) into seq_items (every id in [0, n_items)). Banned lists: ban_ptr
+ *   [n_users + 1] (int64) into ban_items, each row sorted and unique (the items a user may not draw as negatives).
+ *
+ * sagnn_sample_train_i32, per batch slot b < n_batch with u = bat_ids[b], n_pos = len(seq[u]) - 1:
+ *   samp = clamp(min(train_sample_num, n_pos), 0), hi = max(min(pred_num + 1, n_pos - 3), 1), choose uniform on [1, hi];
+ *   samp pairs at off = pair_off[b] + j (j < samp, off < n_pairs): uids[off] = uids[n_pairs + off] = u,
+ *   iids[off] = seq[u][n_pos - choose], iids[n_pairs + off] = the r-th item outside the banned row (r uniform on
+ *   [0, n_items - banned count); -1 if the row bans every item), uLocs_seq[off] = uLocs_seq[n_pairs + off] = b.
+ *   Outputs are [2 n_pairs]; the caller sizes pair_off from the per-user samp, so nothing is copied back.
+ *   The head's sequence per slot b < n_slots: seg_begin[b] (index into seq_items), seg_len[b] =
+ *   min(max(n_pos - choose, 0), pos_length), the last seg_len items before the positive; slots >= n_batch get 0, 0.
+ * sagnn_sample_ssl_i32, per interval k < n_intervals, slot b < n_batch: sub_ptr [n_intervals, n_users + 1] (int64)
+ *   into sub_items (the user's distinct items of interval k), npair = min(ssl_num, n_k(u) / 2) pairs, pair p at
+ *   off = ssl_off[k * n_batch + b] + 2p and off + 1 (< n_out): iids two uniform draws with replacement from the row,
+ *   uids = u, uLocs_seq = b at both.
+ * sagnn_seq_sum_f32: seq_tok[b] = sum_{j < seg_len[b]} fi[seq_items[seg_begin[b] + j]] and pos_tok[b] =
+ *   sum_{p = P - seg_len[b]}^{P - 1} pos_embed[p], both summed in ascending j / p from 0.0f (the order the SpMM sums a
+ *   row of at most 16 entries, so equal bit for bit to the per-batch CSR form there); outputs [n_slots, d] at ldo.
+ * sagnn_seq_sum_bwd_f32: d_fi[seq_items[seg_begin[b] + j]] += g_seq[b] (ACCUMULATES; float atomics on whole rows, so
+ *   the last bits may differ from run to run) and d_pos[p] = sum over b in ascending order with seg_len[b] >= P - p
+ *   of g_pos[b] (WRITTEN; deterministic).
+ * Limits: d a multiple of 4 in [4, 256]; feature pointers 16-byte aligned, strides multiples of 4 and >= d;
+ *   pos_length > 0; 0 < n_items < 2^31; 0 <= step < 2^32. Every argument is checked before any device work. One or two
+ *   launches on `stream`, no allocation, no synchronisation.
+ * -------------------------------------------------------------------------------- */
+int sagnn_sample_train_i32(const int32_t* bat_ids, int64_t n_batch, int64_t n_slots, const int64_t* seq_ptr,
+                           const int32_t* seq_items, const int64_t* ban_ptr, const int32_t* ban_items, int64_t n_users,
+                           int64_t n_items, int train_sample_num, int pred_num, int pos_length, const int64_t* pair_off,
+                           int64_t n_pairs, uint64_t seed, int64_t step, int32_t* uids, int32_t* iids,
+                           int32_t* uLocs_seq, int64_t* seg_begin, int32_t* seg_len, void* stream);
+int sagnn_sample_ssl_i32(const int32_t* bat_ids, int64_t n_batch, int n_intervals, const int64_t* sub_ptr,
+                         const int32_t* sub_items, int64_t n_users, int ssl_num, const int64_t* ssl_off, int64_t n_out,
+                         uint64_t seed, int64_t step, int32_t* uids, int32_t* iids, int32_t* uLocs_seq, void* stream);
+int sagnn_seq_sum_f32(const float* fi, int64_t ldf, int64_t n_items, const float* pos_embed, int64_t ldp,
+                      int pos_length, const int32_t* seq_items, int64_t n_flat, const int64_t* seg_begin,
+                      const int32_t* seg_len, int64_t n_slots, int d, float* seq_tok, float* pos_tok, int64_t ldo,
+                      void* stream);
+int sagnn_seq_sum_bwd_f32(const float* g_seq, const float* g_pos, int64_t ldg, const int32_t* seq_items, int64_t n_flat,
+                          const int64_t* seg_begin, const int32_t* seg_len, int64_t n_slots, int pos_length, int d,
+                          float* d_fi, int64_t ld_dfi, int64_t n_items, float* d_pos, int64_t ld_dpos, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

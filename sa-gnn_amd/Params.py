@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import argparse
 
-# name, type, default, help
+# name, type, default, help[, choices]
 _FLAGS = [
     ("lr", float, 1e-3, "learning rate"),
     ("batch", int, 512, "batch size"),
@@ -58,14 +58,16 @@ _FLAGS = [
     ("ssl", bool, True, "unused"),
     ("uid", int, 0, "debug print index"),
     ("full_rank", int, 0, "also report HR / NDCG over the full item catalogue (not in the reference)"),
+    ("sampler", str, "host", "where training batches are drawn: host (numpy) or device (seeded HIP kernels; not in "
+                             "the reference)", ("host", "device")),
 ]
 
 
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="Model Params")
-    for name, typ, default, text in _FLAGS:
+    for name, typ, default, text, *choices in _FLAGS:
         # type=bool keeps the reference's semantics: any non-empty string is True (Params.py:47-49)
-        p.add_argument("--" + name, default=default, type=typ, help=text)
+        p.add_argument("--" + name, default=default, type=typ, help=text, choices=choices[0] if choices else None)
     return p
 
 

@@ -4,7 +4,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
+from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SAGNN_LIB points at an alternative build (diagnostic variants under scratch/); default: in-tree
@@ -152,6 +152,15 @@ SIGNATURES = {
     "sagnn_score_topk_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int, c_int]),
     "sagnn_score_topk_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "sagnn_sample_train_i32": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                                       c_int, c_int, c_int, c_void_p, c_int64, c_uint64, c_int64, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sagnn_sample_ssl_i32": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64,
+                                     c_uint64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sagnn_seq_sum_f32": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p,
+                                  c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
+    "sagnn_seq_sum_bwd_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int,
+                                      c_int, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
 }
 
 _lib = None

@@ -318,6 +318,27 @@ class SpmmFn(torch.autograd.Function):
         return ops.spmm(ctx.plan_t, g.contiguous(), 1.0), None, None
 
 
+class SeqSumFn(torch.autograd.Function):
+    """(fi, posEmbed) -> (seq_tok, pos_tok): the masked sums of model.py:161-162 read from a device-sampled batch's
+    sequence segments (seq_items[seg_begin[b]:][:seg_len[b]], right-aligned) instead of two per-batch CSRs."""
+
+    @staticmethod
+    def forward(ctx, fi, pos_embed, seq_items, seg_begin, seg_len):
+        ctx.save_for_backward(seq_items, seg_begin, seg_len)
+        ctx.shape = (int(fi.shape[0]), int(pos_embed.shape[0]))
+        return ops.seq_sum(fi.detach(), pos_embed.detach(), seq_items, seg_begin, seg_len)
+
+    @staticmethod
+    def backward(ctx, g_seq, g_pos):
+        seq_items, seg_begin, seg_len = ctx.saved_tensors
+        n_items, P = ctx.shape
+        ref = g_seq if g_seq is not None else g_pos
+        g_seq = torch.zeros_like(ref) if g_seq is None else g_seq.contiguous()
+        g_pos = torch.zeros_like(ref) if g_pos is None else g_pos.contiguous()
+        d_fi, d_pos = ops.seq_sum_bwd(g_seq, g_pos, seq_items, seg_begin, seg_len, n_items, P)
+        return d_fi, d_pos, None, None, None
+
+
 class LayerNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta):

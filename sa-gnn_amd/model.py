@@ -12,6 +12,7 @@ prediction head, SSL loss, samplers and optimiser around it are §8(f) "next" ro
 from __future__ import annotations
 
 import numpy as np
+import scipy.sparse as sp
 import torch
 
 from . import autograd as ag
@@ -39,6 +40,73 @@ def random_fusion_params(d: int, device, seed: int = 0) -> dict:
     return {"lstm_W": xavier(2 * d, 4 * d), "lstm_b": small(4 * d), "ln_gamma": small(d, 1.0),
             "ln_beta": small(d), "Wq": xavier(d, d), "bq": small(d), "Wk": xavier(d, d), "bk": small(d),
             "Wv": xavier(d, d), "bv": small(d)}
+
+
+class DeviceSampler:
+    """The per-dataset tables of the device sampler (sagnn_sample_train_i32 / sagnn_sample_ssl_i32), built and
+    checked once on the host and kept on the device:
+      - the flat sequences (seq_ptr int64 [U + 1] into seq_items int32);
+      - the banned CSR (ban_ptr / ban_items): per user the sorted distinct items of its trnMat row (non-zero values),
+        its last item and its test item, i.e. what the reference's negSamp never returns (DataHandler.py:28-41);
+      - the canonical subMat rows (sub_ptr int64 [T, U + 1] into sub_items): distinct items with a non-zero value,
+        the set the reference draws SSL pairs from (model.py:315, `toarray() != 0`);
+      - per user `samp` (pairs of sampleTrainBatch) and per interval `npair` (pairs of sampleSslBatch).
+    Raises ValueError for a sequence id outside [0, n_items) and for a user with pairs to draw but no allowed negative
+    (the reference's rejection loop would never end there)."""
+
+    def __init__(self, handler, device, n_items: int, train_sample_num: int, ssl_num: int):
+        seqs = handler.sequence
+        U, I = len(seqs), int(n_items)
+        lens = np.fromiter((len(q) for q in seqs), dtype=np.int64, count=U)
+        ptr = np.zeros(U + 1, dtype=np.int64)
+        np.cumsum(lens, out=ptr[1:])
+        flat = np.concatenate([np.asarray(q, dtype=np.int64).reshape(-1) for q in seqs]) if U else np.zeros(0, np.int64)
+        bad = np.flatnonzero((flat < 0) | (flat >= I))
+        if bad.size:
+            u = int(np.searchsorted(ptr, bad[0], side="right") - 1)
+            raise ValueError(f"sequence of user {u} holds item {int(flat[bad[0]])}, outside [0, {I})")
+        self.samp = np.clip(np.minimum(train_sample_num, lens - 1), 0, None)
+        # banned (user, item) keys: trnMat's non-zero entries, the last item, the test item
+        trn = sp.csr_matrix(handler.trnMat, copy=True)
+        trn.sum_duplicates()
+        trn.eliminate_zeros()
+        rows = [np.repeat(np.arange(trn.shape[0], dtype=np.int64), np.diff(trn.indptr))]
+        cols = [trn.indices.astype(np.int64)]
+        has = np.flatnonzero(lens > 0)
+        rows.append(has)
+        cols.append(flat[ptr[has + 1] - 1])
+        tst = np.array([-1 if t is None else int(t) for t in handler.tstInt], dtype=np.int64)
+        tu = np.flatnonzero((tst >= 0) & (tst < I))
+        rows.append(tu)
+        cols.append(tst[tu])
+        keys = np.unique(np.concatenate(rows) * I + np.concatenate(cols))
+        ban_ptr = np.zeros(U + 1, dtype=np.int64)
+        np.cumsum(np.bincount(keys // I, minlength=U)[:U], out=ban_ptr[1:])
+        full = np.flatnonzero((self.samp > 0) & (np.diff(ban_ptr) >= I))
+        if full.size:
+            raise ValueError(f"user {int(full[0])} has training pairs to draw but every item is banned for negatives")
+        # canonical interval rows
+        T = len(handler.subMat)
+        sub_ptr = np.zeros((T, U + 1), dtype=np.int64)
+        sub_items, base = [], 0
+        self.npair = np.zeros((T, U), dtype=np.int64)
+        for k, m in enumerate(handler.subMat):
+            c = sp.csr_matrix(m, copy=True)
+            c.sum_duplicates()
+            c.eliminate_zeros()
+            c.sort_indices()
+            if c.shape[0] != U:
+                raise ValueError(f"subMat[{k}] has {c.shape[0]} rows, {U} users")
+            sub_ptr[k] = base + c.indptr.astype(np.int64)
+            sub_items.append(c.indices.astype(np.int32))
+            base += c.nnz
+            self.npair[k] = np.minimum(ssl_num, np.diff(c.indptr) // 2)
+        as_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+        self.n_users, self.n_items, self.train_sample_num, self.ssl_num = U, I, int(train_sample_num), int(ssl_num)
+        self.seq_ptr, self.seq_items = as_dev(ptr), as_dev(flat.astype(np.int32))
+        self.ban_ptr, self.ban_items = as_dev(ban_ptr), as_dev((keys % I).astype(np.int32))
+        self.sub_ptr = as_dev(sub_ptr)
+        self.sub_items = as_dev(np.concatenate(sub_items) if sub_items else np.zeros(0, np.int32))
 
 
 class Recommender:
@@ -420,12 +488,15 @@ class Recommender:
 
     # ------------------------------------------------------------------ training
     def _i32(self, v):
+        if isinstance(v, torch.Tensor):          # a device-sampled batch: int32 on the device already
+            return v.to(self.device, torch.int32)
         return torch.as_tensor(np.asarray(v, dtype=np.int32), device=self.device)
 
     def train_loss(self, batch, keep_rate=None):
         """The reference's loss for one step (model.py:104-205, 241-246) as a torch autograd graph
         whose nodes are HIP operators (sa_gnn_amd.autograd). batch: dict with uids, iids,
-        uLocs_seq, sequence [args.batch, pos_length], mask, suids[k], siids[k]. Returns
+        uLocs_seq, sequence [args.batch, pos_length], mask, suids[k], siids[k]; a device-sampled batch
+        (sample_batch_device) carries seq_seg = (seg_begin, seg_len) instead of sequence / mask. Returns
         (preLoss, sslloss) as 1-element tensors; total loss = preLoss + ssl_reg*sslloss (+ the L2
         term, applied inside the optimiser step)."""
         T, L, d, heads, leaky = args.graphNum, args.gnn_layer, args.latdim, args.num_attention_heads, NNs.leaky
@@ -448,10 +519,14 @@ class Recommender:
             finals.append(ag.interval_fusion(x, p, heads, drop_scale=drop))
         fu, fi = finals
         # ---- head (model.py:156-173)
-        pi, pp = self._masked_sum_plans(batch["sequence"], batch["mask"])
-        pit, ppt = self._masked_sum_plans_t(batch["sequence"], batch["mask"])
-        seq_tok = ag.SpmmFn.apply(fi, pi, pit)
-        pos_tok = ag.SpmmFn.apply(self.posEmbed, pp, ppt)
+        if "seq_seg" in batch:                                            # device-sampled: segments, no CSRs
+            seg_begin, seg_len = batch["seq_seg"]
+            seq_tok, pos_tok = ag.SeqSumFn.apply(fi, self.posEmbed, self._device_sampler().seq_items, seg_begin, seg_len)
+        else:
+            pi, pp = self._masked_sum_plans(batch["sequence"], batch["mask"])
+            pit, ppt = self._masked_sum_plans_t(batch["sequence"], batch["mask"])
+            seq_tok = ag.SpmmFn.apply(fi, pi, pit)
+            pos_tok = ag.SpmmFn.apply(self.posEmbed, pp, ppt)
         B = seq_tok.shape[0]
         ln = lambda x, gb: ag.LayerNormFn.apply(x.view(B, 1, d), gb[0], gb[1]).view(B, d)
         zero = torch.zeros((B, d), dtype=torch.float32, device=self.device)
@@ -598,6 +673,47 @@ class Recommender:
                 uLocs_seq.append(np.repeat(slot, 2).tolist())
         return uLocs, iLocs, uLocs_seq
 
+    TRAIN_SAMPLE_NUM = 40      # the train_sample_num trainEpoch passes (sample_num_list, reference model.py:345-356)
+
+    def _device_sampler(self) -> DeviceSampler:
+        """The device sampler's tables for the current handler and flags, built once."""
+        h = self.handler
+        key = (id(h.sequence), id(h.trnMat), id(h.subMat), id(h.tstInt), args.item, args.sslNum, str(self.device))
+        cached = getattr(self, "_dev_sampler", None)
+        if cached is None or cached[0] != key:
+            cached = self._dev_sampler = (key, DeviceSampler(h, self.device, args.item, self.TRAIN_SAMPLE_NUM, args.sslNum))
+        return cached[1]
+
+    def sample_batch_device(self, batIds, seed: int, step: int) -> dict:
+        """One training batch drawn on the device: sampleTrainBatch's and sampleSslBatch's distributions (with the SSL
+        pairs drawn from each row's distinct items), as a pure function of (seed, step, user id) per user. Returns
+        device int32 tensors uids, iids, uLocs_seq, suids[k], siids[k] and seq_seg = (seg_begin int64, seg_len int32)
+        [args.batch], the head's sequence segments. Every count comes from host tables: nothing is copied back."""
+        S = self._device_sampler()
+        bat = np.asarray(batIds, dtype=np.int64).reshape(-1)
+        B, T = len(bat), len(S.npair)
+        if B > args.batch:
+            raise ValueError(f"{B} users in a batch of {args.batch} slots")
+        if B and (bat.min() < 0 or bat.max() >= S.n_users):
+            raise ValueError(f"batIds outside [0, {S.n_users})")
+        samp = S.samp[bat]
+        npair2 = 2 * S.npair[:, bat]                                      # [T, B] SSL entries per slot
+        offs = np.zeros(B + T * B + 1, dtype=np.int64)                    # pair_off [B] | ssl_off [T, B] | n_out
+        np.cumsum(samp[:-1], out=offs[1:B])
+        np.cumsum(npair2.reshape(-1), out=offs[B + 1:])
+        n_pairs = int(samp.sum())
+        dev = self.device
+        bat_d = torch.from_numpy(bat.astype(np.int32)).to(dev)
+        offs_d = torch.from_numpy(offs).to(dev)
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        uids, iids, locs, seg_begin, seg_len = ops.sample_train(
+            bat_d, args.batch, S.seq_ptr, S.seq_items, S.ban_ptr, S.ban_items, S.n_items, S.train_sample_num,
+            args.pred_num, args.pos_length, offs_d[:B], n_pairs, seed, step)
+        su, si, _ = ops.sample_ssl(bat_d, S.sub_ptr, S.sub_items, S.ssl_num, offs_d[B:B + T * B], int(offs[-1]), seed, step)
+        ends = np.concatenate([[0], np.cumsum(npair2.sum(1))]).astype(np.int64)
+        return {"uids": uids, "iids": iids, "uLocs_seq": locs, "seq_seg": (seg_begin, seg_len),
+                "suids": [su[ends[k]:ends[k + 1]] for k in range(T)], "siids": [si[ends[k]:ends[k + 1]] for k in range(T)]}
+
     def _trainable(self):
         return {k: v for k, v in NNs.params.items() if v.requires_grad}
 
@@ -607,17 +723,23 @@ class Recommender:
             self.optimizer = self._make_optimizer()
         sfIds = np.random.permutation(args.user)[:args.trnNum]
         steps = int(np.ceil(len(sfIds) / args.batch))
+        device = args.sampler == "device"
+        if device:        # one seed per epoch from numpy's global stream: np.random.seed still reproduces a run
+            seed = int(np.random.randint(0, 2 ** 63, dtype=np.int64))
         # losses stay on the device until the epoch ends: a float() per step would make the host wait for the
         # step's kernels before it samples the next batch (host sampling and device work overlap this way)
         loss_sum = torch.zeros(1, dtype=torch.float32, device=self.device)
         pre_sum = torch.zeros(1, dtype=torch.float32, device=self.device)
         for i in range(steps):
             batIds = sfIds[i * args.batch:(i + 1) * args.batch]
-            uLocs, iLocs, sequence, mask, uLocs_seq = self.sampleTrainBatch(batIds, self.handler.trnMat,
-                                                                            self.handler.timeMat, 40, as_arrays=True)
-            suLocs, siLocs, _ = self.sampleSslBatch(batIds, self.handler.subMat, False, as_arrays=True)
-            batch = {"uids": uLocs, "iids": iLocs, "uLocs_seq": uLocs_seq, "sequence": sequence, "mask": mask,
-                     "suids": suLocs, "siids": siLocs}
+            if device:
+                batch = self.sample_batch_device(batIds, seed, i)
+            else:
+                uLocs, iLocs, sequence, mask, uLocs_seq = self.sampleTrainBatch(batIds, self.handler.trnMat,
+                                                                                self.handler.timeMat, 40, as_arrays=True)
+                suLocs, siLocs, _ = self.sampleSslBatch(batIds, self.handler.subMat, False, as_arrays=True)
+                batch = {"uids": uLocs, "iids": iLocs, "uLocs_seq": uLocs_seq, "sequence": sequence, "mask": mask,
+                         "suids": suLocs, "siids": siLocs}
             params = self._trainable()
             for p in params.values():
                 p.grad = None

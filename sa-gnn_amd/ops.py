@@ -767,3 +767,95 @@ def score_topk(Q: torch.Tensor, I: torch.Tensor, k: int, excl=None, target=None)
     check(lib.sagnn_score_topk_f32(Q.data_ptr(), ldq, I.data_ptr(), ldi, B, n_items, d, int(k), _ptr(rp_d), _ptr(it_d),
                                    _ptr(tg_d), items.data_ptr(), scores.data_ptr(), _ptr(rank), _ptr(ws), need, _stream()))
     return items, scores, rank
+
+
+# ---- device sampling of the training batch (sampler.hip) ---------------------------------------------------------
+_empty_ptrs: dict = {}   # device -> a 16-byte buffer standing in for empty tensors (an empty tensor's data_ptr is 0)
+
+
+def _idx_ptr(name: str, t: torch.Tensor, dtype, numel: int | None = None) -> int:
+    """data_ptr of a contiguous index tensor on the device, checked; a valid pointer also for an empty one."""
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_cuda or not t.is_contiguous():
+        raise TypeError(f"{name}: expected a contiguous {dtype} device tensor")
+    if numel is not None and t.numel() != numel:
+        raise ValueError(f"{name}: expected {numel} elements, got {t.numel()}")
+    if t.numel():
+        return t.data_ptr()
+    buf = _empty_ptrs.get(t.device)
+    if buf is None:
+        buf = _empty_ptrs[t.device] = torch.zeros(4, dtype=torch.int32, device=t.device)
+    return buf.data_ptr()
+
+
+def _out(n: int, dtype, device) -> torch.Tensor:
+    return torch.empty(max(int(n), 1), dtype=dtype, device=device)[:int(n)]
+
+
+def sample_train(bat_ids: torch.Tensor, n_slots: int, seq_ptr: torch.Tensor, seq_items: torch.Tensor,
+                 ban_ptr: torch.Tensor, ban_items: torch.Tensor, n_items: int, train_sample_num: int, pred_num: int,
+                 pos_length: int, pair_off: torch.Tensor, n_pairs: int, seed: int, step: int):
+    """One training batch drawn on the device (sagnn_sample_train_i32). bat_ids int32 [B]; seq_ptr / ban_ptr int64
+    [U + 1] into int32 seq_items / ban_items (banned rows sorted, unique); pair_off int64 [B]: where slot b's pairs
+    start, n_pairs their total. Returns uids, iids, uLocs_seq (int32 [2 n_pairs], positives first) and the head's
+    sequence segments seg_begin (int64 [n_slots]), seg_len (int32 [n_slots])."""
+    B, U = int(bat_ids.numel()), int(seq_ptr.numel()) - 1
+    dev = bat_ids.device
+    uids, iids, locs = (_out(2 * n_pairs, torch.int32, dev) for _ in range(3))
+    seg_begin, seg_len = _out(n_slots, torch.int64, dev), _out(n_slots, torch.int32, dev)
+    check(_lib.load().sagnn_sample_train_i32(
+        _idx_ptr("bat_ids", bat_ids, torch.int32), B, int(n_slots), _idx_ptr("seq_ptr", seq_ptr, torch.int64),
+        _idx_ptr("seq_items", seq_items, torch.int32), _idx_ptr("ban_ptr", ban_ptr, torch.int64, U + 1),
+        _idx_ptr("ban_items", ban_items, torch.int32), U, int(n_items), int(train_sample_num), int(pred_num),
+        int(pos_length), _idx_ptr("pair_off", pair_off, torch.int64, B), int(n_pairs), int(seed), int(step),
+        _idx_ptr("uids", uids, torch.int32), _idx_ptr("iids", iids, torch.int32), _idx_ptr("uLocs_seq", locs, torch.int32),
+        _idx_ptr("seg_begin", seg_begin, torch.int64), _idx_ptr("seg_len", seg_len, torch.int32), _stream()))
+    return uids, iids, locs, seg_begin, seg_len
+
+
+def sample_ssl(bat_ids: torch.Tensor, sub_ptr: torch.Tensor, sub_items: torch.Tensor, ssl_num: int,
+               ssl_off: torch.Tensor, n_out: int, seed: int, step: int):
+    """The SSL pairs of every interval in one launch (sagnn_sample_ssl_i32). sub_ptr int64 [T, U + 1] into int32
+    sub_items (distinct items per row); ssl_off int64 [T, B]: where slot b's pairs of interval k start in the
+    concatenated outputs of n_out entries. Returns uids, iids, uLocs_seq (int32 [n_out], pairs interleaved)."""
+    T, B = int(sub_ptr.shape[0]), int(bat_ids.numel())
+    U = int(sub_ptr.shape[1]) - 1
+    dev = bat_ids.device
+    uids, iids, locs = (_out(n_out, torch.int32, dev) for _ in range(3))
+    check(_lib.load().sagnn_sample_ssl_i32(
+        _idx_ptr("bat_ids", bat_ids, torch.int32), B, T, _idx_ptr("sub_ptr", sub_ptr, torch.int64),
+        _idx_ptr("sub_items", sub_items, torch.int32), U, int(ssl_num), _idx_ptr("ssl_off", ssl_off, torch.int64, T * B),
+        int(n_out), int(seed), int(step), _idx_ptr("uids", uids, torch.int32), _idx_ptr("iids", iids, torch.int32),
+        _idx_ptr("uLocs_seq", locs, torch.int32), _stream()))
+    return uids, iids, locs
+
+
+def seq_sum(fi: torch.Tensor, pos_embed: torch.Tensor, seq_items: torch.Tensor, seg_begin: torch.Tensor,
+            seg_len: torch.Tensor):
+    """The head's masked sums over sequence segments (sagnn_seq_sum_f32): seq_tok[b] = sum of fi over the
+    segment's items, pos_tok[b] = sum of the last seg_len[b] rows of pos_embed. Returns two [n_slots, d] tensors."""
+    d, P, n = int(fi.shape[1]), int(pos_embed.shape[0]), int(seg_len.numel())
+    seq_tok = torch.empty((n, d), dtype=torch.float32, device=fi.device)
+    pos_tok = torch.empty((n, d), dtype=torch.float32, device=fi.device)
+    check(_lib.load().sagnn_seq_sum_f32(
+        fi.data_ptr(), _f32_rows("fi", fi, d), int(fi.shape[0]), pos_embed.data_ptr(), _f32_rows("pos_embed", pos_embed, d),
+        P, _idx_ptr("seq_items", seq_items, torch.int32), int(seq_items.numel()),
+        _idx_ptr("seg_begin", seg_begin, torch.int64, n), _idx_ptr("seg_len", seg_len, torch.int32), n, d,
+        seq_tok.data_ptr(), pos_tok.data_ptr(), d, _stream()))
+    return seq_tok, pos_tok
+
+
+def seq_sum_bwd(g_seq: torch.Tensor, g_pos: torch.Tensor, seq_items: torch.Tensor, seg_begin: torch.Tensor,
+                seg_len: torch.Tensor, n_items: int, pos_length: int):
+    """Gradients of seq_sum (sagnn_seq_sum_bwd_f32): d_fi [n_items, d] (a scatter with float atomics) and
+    d_pos [pos_length, d] (deterministic). g_seq / g_pos: contiguous [n_slots, d]."""
+    n, d = int(seg_len.numel()), int(g_seq.shape[1])
+    ld = _f32_rows("g_seq", g_seq, d, n)
+    if _f32_rows("g_pos", g_pos, d, n) != ld:
+        raise ValueError("g_seq and g_pos need the same row stride")
+    d_fi = torch.zeros((int(n_items), d), dtype=torch.float32, device=g_seq.device)
+    d_pos = torch.empty((int(pos_length), d), dtype=torch.float32, device=g_seq.device)
+    check(_lib.load().sagnn_seq_sum_bwd_f32(
+        g_seq.data_ptr(), g_pos.data_ptr(), ld, _idx_ptr("seq_items", seq_items, torch.int32), int(seq_items.numel()),
+        _idx_ptr("seg_begin", seg_begin, torch.int64, n), _idx_ptr("seg_len", seg_len, torch.int32), n, int(pos_length), d,
+        d_fi.data_ptr(), d, int(n_items), d_pos.data_ptr(), d, _stream()))
+    return d_fi, d_pos

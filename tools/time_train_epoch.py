@@ -2,7 +2,9 @@
 """Times Recommender.trainEpoch / testEpoch on a Gowalla-shaped synthetic dataset with the reference's
 gowalla.sh hyper-parameters (U = 48,653, I = 52,619, 3 intervals x 600 k edges, d = 64, batch 512,
 trnNum 10000 -> 20 steps per epoch, keepRate 0.5) and prints where a training step spends its time
-(host sampling / forward + loss / backward / optimiser), wall clock with a device sync after each part."""
+(sampling / forward + loss / backward / optimiser), wall clock with a device sync after each part. Both samplers
+(--sampler host / device) run in the same process, alternated epoch by epoch."""
+import argparse
 import sys
 import time
 
@@ -18,6 +20,9 @@ from sa_gnn_amd.model import Recommender      # noqa: E402
 
 
 def main():
+    ap = argparse.ArgumentParser(description=__doc__)
+    ap.add_argument("--epoch-only", action="store_true", help="one warm-up and one device-sampler epoch (for a profiler)")
+    opt = ap.parse_args()
     Params.parse_args("--data gowalla --lr 2e-3 --reg 1e-2 --ssl_reg 1e-6 --epoch 150 --batch 512 --sslNum 40 --graphNum 3 "
                       "--gnn_layer 2 --att_layer 1 --testSize 1000 --ssldim 48 --keepRate 0.5".split(), namespace=args)
     np.random.seed(100)
@@ -32,38 +37,65 @@ def main():
     h = DataHandler.from_memory(tmt, seq, tst, test_dict)
     rec = Recommender(torch.device("cuda:0"), h)
     rec.prepareModel()
-    for _ in range(2):
-        rec.trainEpoch()
+    if opt.epoch_only:
+        args.sampler = "device"
+        for _ in range(2):
+            rec.trainEpoch()
+        torch.cuda.synchronize()
+        print("two device-sampler epochs done")
+        return
+    samplers = ("host", "device")
+    for name in samplers:          # warm-up: kernels, workspaces, the device sampler's tables
+        args.sampler = name
+        for _ in range(2):
+            rec.trainEpoch()
     torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    n_ep = 5
-    for _ in range(n_ep):
-        rec.trainEpoch()
-    torch.cuda.synchronize()
-    ep = (time.perf_counter() - t0) / n_ep
     steps = int(np.ceil(args.trnNum / args.batch))
-    print(f"train epoch {ep * 1e3:.1f} ms = {steps} steps of {ep / steps * 1e3:.2f} ms")
+    rounds = 3
+    epoch = {name: [] for name in samplers}
+    for _ in range(rounds):        # alternated, so both see the same machine state
+        for name in samplers:
+            args.sampler = name
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            rec.trainEpoch()
+            torch.cuda.synchronize()
+            epoch[name].append(time.perf_counter() - t0)
+    for name in samplers:
+        ep = float(np.median(epoch[name]))
+        print(f"[{name}] train epoch {ep * 1e3:.1f} ms = {steps} steps of {ep / steps * 1e3:.2f} ms "
+              f"(median of {rounds}; all: {[round(1e3 * v, 1) for v in epoch[name]]})")
     # one step, by part
-    parts = {"sample": 0.0, "forward+loss": 0.0, "backward": 0.0, "optimiser": 0.0}
-    sf = np.random.permutation(args.user)[:args.trnNum]
-    for i in range(steps):
-        bat = sf[i * args.batch:(i + 1) * args.batch]
-        torch.cuda.synchronize(); t = time.perf_counter()
-        uL, iL, sq, mk, uLs = rec.sampleTrainBatch(bat, h.trnMat, h.timeMat, 40, as_arrays=True)
-        su, si, _ = rec.sampleSslBatch(bat, h.subMat, False, as_arrays=True)
-        batch = {"uids": uL, "iids": iL, "uLocs_seq": uLs, "sequence": sq, "mask": mk, "suids": su, "siids": si}
-        parts["sample"] += time.perf_counter() - t; t = time.perf_counter()
-        params = rec._trainable()
-        for p in params.values():
-            p.grad = None
-        pre, ssl = rec.train_loss(batch)
-        loss = pre + args.ssl_reg * ssl
-        torch.cuda.synchronize(); parts["forward+loss"] += time.perf_counter() - t; t = time.perf_counter()
-        loss.backward()
-        torch.cuda.synchronize(); parts["backward"] += time.perf_counter() - t; t = time.perf_counter()
-        rec.optimizer.step({k: p.grad for k, p in params.items()})
-        torch.cuda.synchronize(); parts["optimiser"] += time.perf_counter() - t
-    print("per step (ms, synced between parts):", {k: round(v / steps * 1e3, 3) for k, v in parts.items()})
+    parts = {name: {"sample": 0.0, "forward+loss": 0.0, "backward": 0.0, "optimiser": 0.0} for name in samplers}
+    for r in range(rounds):
+        for name in samplers:
+            sf = np.random.permutation(args.user)[:args.trnNum]
+            seed = int(np.random.randint(0, 2 ** 63, dtype=np.int64))
+            part = parts[name]
+            for i in range(steps):
+                bat = sf[i * args.batch:(i + 1) * args.batch]
+                torch.cuda.synchronize(); t = time.perf_counter()
+                if name == "device":
+                    batch = rec.sample_batch_device(bat, seed, i)
+                else:
+                    uL, iL, sq, mk, uLs = rec.sampleTrainBatch(bat, h.trnMat, h.timeMat, 40, as_arrays=True)
+                    su, si, _ = rec.sampleSslBatch(bat, h.subMat, False, as_arrays=True)
+                    batch = {"uids": uL, "iids": iL, "uLocs_seq": uLs, "sequence": sq, "mask": mk, "suids": su, "siids": si}
+                torch.cuda.synchronize(); part["sample"] += time.perf_counter() - t; t = time.perf_counter()
+                params = rec._trainable()
+                for p in params.values():
+                    p.grad = None
+                pre, ssl = rec.train_loss(batch)
+                loss = pre + args.ssl_reg * ssl
+                torch.cuda.synchronize(); part["forward+loss"] += time.perf_counter() - t; t = time.perf_counter()
+                loss.backward()
+                torch.cuda.synchronize(); part["backward"] += time.perf_counter() - t; t = time.perf_counter()
+                rec.optimizer.step({k: p.grad for k, p in params.items()})
+                torch.cuda.synchronize(); part["optimiser"] += time.perf_counter() - t
+    for name in samplers:
+        print(f"[{name}] per step (ms, synced between parts, mean of {rounds} epochs):",
+              {k: round(v / (steps * rounds) * 1e3, 3) for k, v in parts[name].items()})
+    args.sampler = "host"
     t0 = time.perf_counter()
     res = rec.testEpoch()
     torch.cuda.synchronize()
