@@ -551,6 +551,28 @@ int sagnn_score_topk_f32(const float* Q, int64_t ldq, const float* I, int64_t ld
                          size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Sampled-candidate evaluation (evaluate.hip): the reference's test epoch (model.py:430-510) scores testSize
+ * candidates per user with the head and ranks the held-out target among them.
+ *   scores[b, j] = <U[uids[b]], I[c]> + <leaky(S[b]), A[c]>, c = cand[b * ldc + j] (S / A NULL drops the second
+ *   term): bit-identical to sagnn_pair_score_f32 for (uids[b], c, locs = b) — both run the same per-lane arithmetic
+ *   and lane reduction (d / 4 lanes per pair).
+ *   rank[b]: NaN scores count as -inf; with copies = {j : cand[b, j] == target[b]}, p = the highest score over the
+ *   copies and f = the first copy scoring p, rank = #{j : s_j > p} + #{j < f : s_j == p} (the reference's stable
+ *   descending sort, best-ranked copy; at p = -inf every NaN / -inf candidate before f counts). No copy, or
+ *   target[b] < 0, gives -1 (a miss).
+ * uids / target int32 [n_rows]; cand int32 [n_rows, C] at row stride ldc; rank int64 [n_rows]; scores (nullable)
+ *   [n_rows, C] at ld_scores. Candidate and user ids are the caller's responsibility (never checked here).
+ * A row's outputs depend on that row's inputs only (not on n_rows or its position) and are bit-identical between runs.
+ * Limits: d a multiple of 4 in [4, 256] with d / 4 a power of two; 1 <= C <= 8192; ldc >= C; ld_scores >= C;
+ *   strides multiples of 4 and >= d; U, I, S, A 16-byte aligned. Every argument is checked before any device work.
+ *   One launch on `stream`, no allocation, no synchronisation (capturable).
+ * -------------------------------------------------------------------------------- */
+int sagnn_candidate_rank_f32(const float* U, int64_t ldu, const float* I, int64_t ldi, const float* S, int64_t lds,
+                             const float* A, int64_t lda, const int32_t* uids, const int32_t* cand, int64_t ldc,
+                             const int32_t* target, float leaky, int64_t n_rows, int C, int d, int64_t* rank,
+                             float* scores, int64_t ld_scores, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Device sampling of the training batch (sampler.hip): the reference's sampleTrainBatch / negSamp /
  * sampleSslBatch (model.py:252-339, DataHandler.py:28-41) drawn by HIP kernels, and the head's masked sums
  * (model.py:161-162) read straight from the sampled sequence segments.

@@ -60,6 +60,8 @@ _FLAGS = [
     ("full_rank", int, 0, "also report HR / NDCG over the full item catalogue (not in the reference)"),
     ("sampler", str, "host", "where training batches are drawn: host (numpy) or device (seeded HIP kernels; not in "
                              "the reference)", ("host", "device")),
+    ("evaluator", str, "host", "where test epochs score and rank: host (numpy ranking per batch) or device (tables "
+                               "built once, ranks copied back once per epoch; not in the reference)", ("host", "device")),
 ]
 
 

@@ -152,6 +152,9 @@ SIGNATURES = {
     "sagnn_score_topk_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int, c_int]),
     "sagnn_score_topk_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "sagnn_candidate_rank_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                                         c_void_p, c_void_p, c_int64, c_void_p, c_float, c_int64, c_int, c_int, c_void_p,
+                                         c_void_p, c_int64, c_void_p]),
     "sagnn_sample_train_i32": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
                                        c_int, c_int, c_int, c_void_p, c_int64, c_uint64, c_int64, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_void_p, c_void_p]),

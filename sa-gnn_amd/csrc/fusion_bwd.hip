@@ -7,6 +7,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "pair_score.h"
 
 namespace {
 
@@ -442,7 +443,7 @@ __global__ void leaky_add_kernel(const float* __restrict__ a, const float* __res
 }
 
 // preds[e] = <U[uid_e], I[iid_e]> + <leaky(S[loc_e]), A[iid_e]>   (second term optional)
-// One wavefront per pair group: LPR = d/4 lanes per pair, float4 per lane.
+// One wavefront per pair group: LPR = d/4 lanes per pair, float4 per lane (the arithmetic: pair_score.h).
 __global__ void pair_score_kernel(const float* __restrict__ U, int64_t ldu, const float* __restrict__ I, int64_t ldi,
                                   const float* __restrict__ S, int64_t lds_, const float* __restrict__ A, int64_t lda,
                                   const int32_t* __restrict__ uids, const int32_t* __restrict__ iids,
@@ -454,20 +455,18 @@ __global__ void pair_score_kernel(const float* __restrict__ U, int64_t ldu, cons
   const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int64_t e = wave * ppw + lane / lpr;
   const int col = (lane % lpr) * 4;
-  float acc = 0.f;
-  if (e < n_pairs) {
-    const int64_t u = uids[e], it = iids[e];
-    const float4 a = *reinterpret_cast<const float4*>(U + u * ldu + col);
-    const float4 b = *reinterpret_cast<const float4*>(I + it * ldi + col);
-    acc = a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w;
-    if (S) {
-      const float4 s = *reinterpret_cast<const float4*>(S + (int64_t)locs[e] * lds_ + col);
-      const float4 c = *reinterpret_cast<const float4*>(A + it * lda + col);
-      acc += fmaxf(leaky * s.x, s.x) * c.x + fmaxf(leaky * s.y, s.y) * c.y + fmaxf(leaky * s.z, s.z) * c.z +
-             fmaxf(leaky * s.w, s.w) * c.w;
-    }
-  }
-  for (int off = 1; off < lpr; off <<= 1) acc += __shfl_xor(acc, off);
+  const float acc = sagnn::pair_score_lanes(
+      e < n_pairs, S != nullptr,
+      [&](const float*& ur, const float*& ir, const float*& sr, const float*& ar) {
+        const int64_t u = uids[e], it = iids[e];
+        ur = U + u * ldu;
+        ir = I + it * ldi;
+        if (S) {
+          sr = S + (int64_t)locs[e] * lds_;
+          ar = A + it * lda;
+        }
+      },
+      leaky, col, lpr);
   if (e < n_pairs && (lane % lpr) == 0) out[e] = acc;
 }
 

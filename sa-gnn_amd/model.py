@@ -109,6 +109,79 @@ class DeviceSampler:
         self.sub_items = as_dev(np.concatenate(sub_items) if sub_items else np.zeros(0, np.int32))
 
 
+class DeviceEvaluator:
+    """The fixed inputs of a test epoch (testEpoch / testEpochFull) as tables, built once from the host path's own
+    helpers (Recommender._test_candidates, _test_sequences, _masked_sum_csr) and kept on the device:
+      - users int64 / uids int32 [n]: handler.tstUsrs, in order;
+      - cand int32 [n, testSize]: the testSize - 1 negatives of test_dict, then the target LAST (sampleTestBatch);
+      - target int32 [n]: tstInt (args.test) or the sequence's last item (validation);
+      - chunks: per args.batch users (testEpoch's batches, same order) the start row, the user count and the head's
+        masked-sum CSRs over args.batch slots (rowptr, item ids, positions), exactly what _masked_sum_plans uploads
+        for that batch; on the device they become static SpmmPlans (plans);
+      - the full-ranking exclusion CSR (excl_rowptr int64 / excl_items int32: each user's sequence items as the head
+        reads them, sorted), checked once and uploaded once as an ops.ExclusionCSR (excl).
+    Raises ValueError for a test_dict row shorter than testSize - 1 (as the host does), for candidate or target ids
+    outside [0, n_items) (the host would read outside the item table), for a validation user with an empty sequence
+    (the host would read the next user's first item as the target) and for testSize above the kernel's limit.
+    With device=None only the host tables are built."""
+
+    MAX_CANDIDATES = 8192      # sagnn_candidate_rank_f32's limit on C
+
+    def __init__(self, rec, device=None):
+        h = rec.handler
+        I, B = int(args.item), int(args.batch)
+        if not 1 <= args.testSize <= self.MAX_CANDIDATES:
+            raise ValueError(f"testSize = {args.testSize}: the device evaluator takes 1 .. {self.MAX_CANDIDATES}")
+        users = np.asarray(h.tstUsrs, dtype=np.int64).reshape(-1)
+        n = len(users)
+        flat, ptr = rec._flat_sequences()
+        neg_all, row_of = rec._test_candidates()
+        neg = neg_all[row_of[users]] if n else np.zeros((0, args.testSize - 1), np.int32)
+        if args.test:
+            target = np.array([-1 if t is None else int(t) for t in h.tstInt[users]], dtype=np.int64)
+        else:
+            empty = np.flatnonzero(ptr[users + 1] == ptr[users])
+            if empty.size:
+                raise ValueError(f"user {int(users[empty[0]])} has an empty sequence: no validation target")
+            target = flat[ptr[users + 1] - 1]
+        bad = np.flatnonzero((target < 0) | (target >= I))
+        if bad.size:
+            raise ValueError(f"target of test user {int(users[bad[0]])} is {int(target[bad[0]])}, outside [0, {I})")
+        bad = np.argwhere((neg < 0) | (neg >= I))
+        if bad.size:
+            r, j = bad[0]
+            raise ValueError(f"test_dict candidate {int(neg[r, j]) + 1} of user {int(users[r]) + 1} is outside [1, {I}]")
+        self.n, self.n_items, self.batch = n, I, B
+        self.users = users
+        self.target = target.astype(np.int32)
+        self.cand = np.ascontiguousarray(np.concatenate([neg.astype(np.int32), self.target[:, None]], axis=1))
+        self.chunks, lens, excl = [], [], []
+        for st in range(0, n, B):
+            bat = users[st:st + B]
+            sequence, mask, start, seq_end = rec._test_sequences(bat)
+            self.chunks.append((st, len(bat)) + Recommender._masked_sum_csr(sequence, mask))
+            lens.append(seq_end - start)
+            excl.append(np.concatenate([np.sort(flat[a:e]) for a, e in zip(start, seq_end)]))
+        self.excl_rowptr = np.zeros(n + 1, dtype=np.int64)
+        if n:
+            np.cumsum(np.concatenate(lens), out=self.excl_rowptr[1:])
+        self.excl_items = np.concatenate(excl).astype(np.int32) if excl else np.zeros(0, np.int32)
+        self.device = None
+        if device is not None:
+            self._upload(device)
+
+    def _upload(self, device):
+        as_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+        P = int(args.pos_length)
+        self.device = device
+        self.uids_d, self.users_d = as_dev(self.users.astype(np.int32)), as_dev(self.users)
+        self.cand_d, self.target_d = as_dev(self.cand), as_dev(self.target)
+        self.plans = [(ops.SpmmPlan(rp, it, self.batch, self.n_items, device=device, validate=False),
+                       ops.SpmmPlan(rp, pos, self.batch, P, device=device, validate=False))
+                      for _, _, rp, it, pos in self.chunks]
+        self.excl = ops.ExclusionCSR(self.excl_rowptr, self.excl_items, self.n, self.n_items, device)
+
+
 class Recommender:
     def __init__(self, sess, handler):
         self.sess = sess
@@ -276,18 +349,25 @@ class Recommender:
         return replay
 
     # ------------------------------------------------------------------ prediction head
-    def _masked_sum_plans(self, sequence, mask):
-        """Per-batch CSRs for the masked sums of model.py:161-162: row b lists the unmasked
-        entries of the batch slot's sequence (item ids, and their positions)."""
+    @staticmethod
+    def _masked_sum_csr(sequence, mask):
+        """The CSRs of the masked sums of model.py:161-162: row b lists the unmasked entries of the batch slot's
+        sequence. Returns rowptr int32 [B + 1], their item ids and their positions (int32)."""
         sequence = np.asarray(sequence, dtype=np.int64)
         keep = np.asarray(mask) != 0
         B, L = keep.shape
         rowptr = np.zeros(B + 1, dtype=np.int32)
         np.cumsum(keep.sum(1), out=rowptr[1:])
         items = sequence[keep].astype(np.int32)
-        pos = np.broadcast_to(np.arange(L, dtype=np.int32), (B, L))[keep]
+        pos = np.ascontiguousarray(np.broadcast_to(np.arange(L, dtype=np.int32), (B, L))[keep])
+        return rowptr, items, pos
+
+    def _masked_sum_plans(self, sequence, mask):
+        """Per-batch plans for the masked sums of model.py:161-162 (item ids, and positions)."""
+        rowptr, items, pos = self._masked_sum_csr(sequence, mask)
+        B, L = np.asarray(mask).shape
         pi = ops.SpmmPlan(rowptr, items, B, args.item, device=self.device, validate=False)
-        pp = ops.SpmmPlan(rowptr, np.ascontiguousarray(pos), B, L, device=self.device, validate=False)
+        pp = ops.SpmmPlan(rowptr, pos, B, L, device=self.device, validate=False)
         return pi, pp
 
     def predict(self, uids, iids, sequence, mask, uLocs_seq):
@@ -300,9 +380,12 @@ class Recommender:
 
     def _head_att(self, sequence, mask):
         """The head's sequence representation att [args.batch, d] (model.py:158-168) on the cached final vectors."""
+        return self._head_att_plans(*self._masked_sum_plans(sequence, mask))
+
+    def _head_att_plans(self, pi, pp):
+        """_head_att on the masked-sum plans of the batch (item ids pi, positions pp)."""
         heads, leaky = args.num_attention_heads, NNs.leaky
         fi = self.final_item_vector
-        pi, pp = self._masked_sum_plans(sequence, mask)
         seq_tok = ops.spmm(pi, fi, 1.0)                                   # [B, d] masked item sum
         pos_tok = ops.spmm(pp, self.posEmbed.detach(), 1.0)               # [B, d] masked position sum
         B, d = seq_tok.shape
@@ -420,7 +503,10 @@ class Recommender:
 
     def testEpoch(self):
         """reference model.py:430-482. The hot path is evaluated ONCE (parameters are frozen and
-        keepRate = 1 during testing, model.py:458) instead of once per batch."""
+        keepRate = 1 during testing, model.py:458) instead of once per batch. args.evaluator = "device" runs
+        _test_epoch_device (the same dict)."""
+        if args.evaluator == "device":
+            return self._test_epoch_device(full=False)
         self.forward()
         ids = self.handler.tstUsrs
         num = len(ids)
@@ -461,7 +547,9 @@ class Recommender:
         """Full-catalogue HR / NDCG at shoot, 5 and 20: testEpoch()'s users, targets and batches, with the target
         ranked against every item instead of testSize - 1 sampled ones. A user's exclusions are the items of the
         sequence its head reads (the target stays eligible: sagnn_score_topk_f32 never excludes it). Same keys and
-        normalisation as testEpoch(); forward() runs once."""
+        normalisation as testEpoch(); forward() runs once. args.evaluator = "device" runs _test_epoch_device."""
+        if args.evaluator == "device":
+            return self._test_epoch_device(full=True)
         self.forward()
         ids = self.handler.tstUsrs
         num = len(ids)
@@ -483,6 +571,53 @@ class Recommender:
                 hit = (rank >= 0) & (rank < kk)
                 tot[2 * j] += hit.sum()
                 tot[2 * j + 1] += (1.0 / np.log2(rank[hit] + 2)).sum()
+        return {"HR": tot[0] / num, "NDCG": tot[1] / num, "HR5": tot[2] / num, "NDCG5": tot[3] / num,
+                "HR20": tot[4] / num, "NDCG20": tot[5] / num}
+
+    def _device_evaluator(self) -> DeviceEvaluator:
+        """The device evaluator's tables for the current handler and flags, built once."""
+        h = self.handler
+        key = (id(h.sequence), id(h.test_dict), id(h.tstInt), id(h.tstUsrs), bool(args.test), args.testSize,
+               args.pos_length, args.batch, args.item, str(self.device))
+        cached = getattr(self, "_dev_eval", None)
+        if cached is None or cached[0] != key:
+            self._dev_eval = None                         # free the old tables before building the new ones
+            cached = self._dev_eval = (key, DeviceEvaluator(self, self.device))
+        return cached[1]
+
+    def _test_epoch_device(self, full: bool):
+        """testEpoch (full=False) or testEpochFull (full=True) on the device evaluator's tables: forward() once, then
+        per batch of testEpoch the head on the static plans and one ranking launch (sagnn_candidate_rank_f32 on the
+        sampled candidates, or sagnn_score_topk_f32 over the catalogue); the ranks come back in one copy."""
+        E = self._device_evaluator()
+        self.forward()
+        fu, fi, leaky = self.final_user_vector, self.final_item_vector, NNs.leaky
+        ranks = []
+        for (st, nb, _, _, _), (pi, pp) in zip(E.chunks, E.plans):
+            att = self._head_att_plans(pi, pp)[:nb]
+            if full:
+                q = ops.leaky_add(att, fu.index_select(0, E.users_d[st:st + nb]), leaky)
+                _, _, r = ops.score_topk(q, fi, 1, excl=E.excl.rows(st, st + nb), target=E.target_d[st:st + nb])
+            else:
+                r, _ = ops.candidate_rank(fu, fi, E.uids_d[st:st + nb], E.cand_d[st:st + nb], E.target_d[st:st + nb],
+                                          S=att, A=fi, leaky=leaky)
+            ranks.append(r)
+        rank = torch.cat(ranks).cpu().numpy() if ranks else np.zeros(0, np.int64)
+        return self._rank_metrics(rank, E.batch)
+
+    @staticmethod
+    def _rank_metrics(rank, batch):
+        """HR / NDCG at shoot, 5 and 20 from the target ranks of every test user (-1 = a miss), summed per batch of
+        `batch` users in float64 in the order calcRes and testEpochFull sum them, so the dict equals theirs."""
+        num = len(rank)
+        tot = np.zeros(6)
+        for st in range(0, num, batch):
+            r = rank[st:st + batch]
+            res = []
+            for k in (args.shoot, 5, 20):
+                hit = (r >= 0) & (r < k)
+                res += [float(hit.sum()), float((1.0 / np.log2(r[hit] + 2)).sum())]
+            tot += np.array(res)
         return {"HR": tot[0] / num, "NDCG": tot[1] / num, "HR5": tot[2] / num, "NDCG5": tot[3] / num,
                 "HR20": tot[4] / num, "NDCG20": tot[5] / num}
 

@@ -735,23 +735,54 @@ def check_exclusions(rowptr, items, n_rows: int, n_items: int):
     return rp.astype(np.int32), it.astype(np.int32)
 
 
+class ExclusionCSR:
+    """An exclusion CSR for score_topk, checked once on the host (check_exclusions) and uploaded once: rowptr int32
+    [n_rows + 1] into items int32, both on `device`. rows(lo, hi) is the CSR of rows [lo, hi) as a view (rowptr
+    entries index the shared items array directly, so nothing is rebased or copied)."""
+
+    def __init__(self, rowptr, items, n_rows: int, n_items: int, device):
+        rp, it = check_exclusions(rowptr, items, n_rows, n_items)
+        self.n_rows, self.n_items = int(n_rows), int(n_items)
+        self.rowptr = torch.from_numpy(rp).to(device)
+        # an empty items array still needs a valid pointer (never read: every row is empty)
+        self.items = torch.from_numpy(it).to(device) if it.size else torch.zeros(1, dtype=torch.int32, device=device)
+
+    def rows(self, lo: int, hi: int) -> "ExclusionCSR":
+        lo, hi = int(lo), int(hi)
+        if not 0 <= lo <= hi <= self.n_rows:
+            raise ValueError(f"rows [{lo}, {hi}) outside [0, {self.n_rows})")
+        view = ExclusionCSR.__new__(ExclusionCSR)
+        view.n_rows, view.n_items = hi - lo, self.n_items
+        view.rowptr, view.items = self.rowptr[lo:hi + 1], self.items
+        return view
+
+
 def score_topk(Q: torch.Tensor, I: torch.Tensor, k: int, excl=None, target=None):
     """The best k items of every row of Q over the whole item table I (sagnn_score_topk_f32): score <Q[b], I[i]> in
     fp32, higher first, equal scores to the lower id, NaN never returned. excl = (rowptr, items): a CSR of item ids
-    per row left out (checked on the host, then uploaded); target [B]: items whose rank is returned (always eligible).
+    per row left out (checked on the host, then uploaded), or an ExclusionCSR (checked and uploaded already);
+    target [B]: items whose rank is returned (always eligible).
     Returns (items int32 [B, k], scores float32 [B, k], rank int64 [B] or None); empty slots hold -1 / -inf."""
     lib = _lib.load()
     if Q.dim() != 2:
         raise ValueError(f"Q: expected [B, d], got {tuple(Q.shape)}")
     B, d = int(Q.shape[0]), int(Q.shape[1])
     n_items = int(I.shape[0]) if I.dim() == 2 else 0
-    ex = None if excl is None else check_exclusions(excl[0], excl[1], B, n_items)
+    pre = isinstance(excl, ExclusionCSR)
+    if pre and (excl.n_rows != B or excl.n_items != n_items):
+        raise ValueError(f"excl: an ExclusionCSR of {excl.n_rows} rows over {excl.n_items} items, "
+                         f"Q has {B} rows and I {n_items} items")
+    ex = None if (excl is None or pre) else check_exclusions(excl[0], excl[1], B, n_items)
     ldq, ldi = _f32_rows("Q", Q, d), _f32_rows("I", I, d)
     dev = Q.device
     if I.device != dev:
         raise ValueError(f"I on {I.device}, Q on {dev}")
     rp_d = it_d = tg_d = rank = None
-    if ex is not None:
+    if pre:
+        if excl.rowptr.device != dev:
+            raise ValueError(f"excl on {excl.rowptr.device}, Q on {dev}")
+        rp_d, it_d = excl.rowptr, excl.items
+    elif ex is not None:
         rp, it = ex
         rp_d = torch.from_numpy(rp).to(dev)
         it_d = torch.from_numpy(it).to(dev) if it.size else torch.zeros(1, dtype=torch.int32, device=dev)
@@ -767,6 +798,32 @@ def score_topk(Q: torch.Tensor, I: torch.Tensor, k: int, excl=None, target=None)
     check(lib.sagnn_score_topk_f32(Q.data_ptr(), ldq, I.data_ptr(), ldi, B, n_items, d, int(k), _ptr(rp_d), _ptr(it_d),
                                    _ptr(tg_d), items.data_ptr(), scores.data_ptr(), _ptr(rank), _ptr(ws), need, _stream()))
     return items, scores, rank
+
+
+def candidate_rank(U: torch.Tensor, I: torch.Tensor, uids: torch.Tensor, cand: torch.Tensor, target: torch.Tensor,
+                   S: torch.Tensor | None = None, A: torch.Tensor | None = None, leaky: float = 1.0,
+                   want_scores: bool = False):
+    """The target's rank among each row's candidates (sagnn_candidate_rank_f32): scores[b, j] = <U[uids[b]], I[c]> +
+    <leaky(S[b]), A[c]> for c = cand[b, j], bit-identical to pair_score; rank[b] = #(scores above the best target
+    copy) + #(earlier candidates tied with it), NaN read as -inf, -1 when the row holds no copy or target[b] < 0
+    (Recommender.calcRes). uids / target int32 [B], cand int32 [B, C] with unit inner stride; ids are not checked.
+    Returns (rank int64 [B], scores float32 [B, C] or None)."""
+    d = int(U.shape[1])
+    if cand.dim() != 2 or cand.dtype != torch.int32 or not cand.is_cuda or cand.stride(1) != 1:
+        raise ValueError("cand: need an int32 device matrix [B, C] with unit inner stride")
+    B, C = int(cand.shape[0]), int(cand.shape[1])
+    ldc = cand.stride(0) if B > 1 else C
+    cand_ptr = cand.data_ptr() if cand.numel() else _idx_ptr("cand", cand.new_zeros(0), torch.int32)
+    dev = U.device
+    rank = torch.empty(B, dtype=torch.int64, device=dev)
+    scores = torch.empty((B, C), dtype=torch.float32, device=dev) if want_scores else None
+    check(_lib.load().sagnn_candidate_rank_f32(
+        U.data_ptr(), _f32_rows("U", U, d), I.data_ptr(), _f32_rows("I", I, d), _ptr(S),
+        0 if S is None else _f32_rows("S", S, d, B), _ptr(A), 0 if A is None else _f32_rows("A", A, d),
+        _idx_ptr("uids", uids, torch.int32, B), cand_ptr, ldc,
+        _idx_ptr("target", target, torch.int32, B), float(leaky), B, C, d, _idx_ptr("rank", rank, torch.int64),
+        _ptr(scores), C, _stream()))
+    return rank, scores
 
 
 # ---- device sampling of the training batch (sampler.hip) ---------------------------------------------------------
