@@ -42,6 +42,57 @@ def random_fusion_params(d: int, device, seed: int = 0) -> dict:
             "Wv": xavier(d, d), "bv": small(d)}
 
 
+def _flatten_sequences(seqs):
+    """handler.sequence (one array per user) as one flat int64 array + int64 offsets [U + 1]."""
+    lens = np.fromiter((len(q) for q in seqs), dtype=np.int64, count=len(seqs))
+    ptr = np.zeros(len(seqs) + 1, dtype=np.int64)
+    np.cumsum(lens, out=ptr[1:])
+    flat = np.concatenate([np.asarray(q, dtype=np.int64).reshape(-1) for q in seqs]) if len(seqs) else np.zeros(0, np.int64)
+    return flat, ptr
+
+
+def _tst_as_int64(tstInt):
+    """handler.tstInt (an item id or None per user) as int64, -1 for None."""
+    return np.array([-1 if t is None else t for t in tstInt], dtype=np.int64)
+
+
+def _right_aligned(flat, end, n, rows, P):
+    """sequence int64 / mask float32 [rows, P]: row r holds the last min(n[r], P) of the n[r] items that end before
+    flat[end[r]], right-aligned (the head's input layout, reference model.py:284-290 and :399-405)."""
+    k = np.minimum(n, P)
+    sequence = np.zeros((rows, P), dtype=np.int64)
+    mask = np.zeros((rows, P), dtype=np.float32)
+    r = np.repeat(np.arange(len(k), dtype=np.int64), k)
+    within = np.arange(int(k.sum()), dtype=np.int64) - np.repeat(np.cumsum(k) - k, k)
+    sequence[r, P - k[r] + within] = flat[end[r] - k[r] + within]
+    mask[r, P - k[r] + within] = 1
+    return sequence, mask
+
+
+def _exclusions(flat, start, seq_end):
+    """The full-ranking exclusion CSR: row r lists flat[start[r]:seq_end[r]] (the sequence the head reads), sorted.
+    Returns rowptr int64 [n + 1] and the items (int64)."""
+    rowptr = np.zeros(len(start) + 1, dtype=np.int64)
+    np.cumsum(seq_end - start, out=rowptr[1:])
+    items = np.concatenate([np.sort(flat[a:e]) for a, e in zip(start, seq_end)]) if len(start) else np.zeros(0, np.int64)
+    return rowptr, items
+
+
+def _rank_sums(rank, shoot):
+    """One batch's HR / NDCG sums at shoot, 5 and 20 from its target ranks (-1 = a miss), as six floats."""
+    res = []
+    for k in (shoot, 5, 20):
+        hit = (rank >= 0) & (rank < k)
+        res += [float(hit.sum()), float((1.0 / np.log2(rank[hit] + 2)).sum())]
+    return tuple(res)
+
+
+def _metrics(tot, num):
+    """The test epoch's dict from the float64 totals of _rank_sums over its num users."""
+    return {"HR": tot[0] / num, "NDCG": tot[1] / num, "HR5": tot[2] / num, "NDCG5": tot[3] / num,
+            "HR20": tot[4] / num, "NDCG20": tot[5] / num}
+
+
 class DeviceSampler:
     """The per-dataset tables of the device sampler (sagnn_sample_train_i32 / sagnn_sample_ssl_i32), built and
     checked once on the host and kept on the device:
@@ -55,12 +106,9 @@ class DeviceSampler:
     (the reference's rejection loop would never end there)."""
 
     def __init__(self, handler, device, n_items: int, train_sample_num: int, ssl_num: int):
-        seqs = handler.sequence
-        U, I = len(seqs), int(n_items)
-        lens = np.fromiter((len(q) for q in seqs), dtype=np.int64, count=U)
-        ptr = np.zeros(U + 1, dtype=np.int64)
-        np.cumsum(lens, out=ptr[1:])
-        flat = np.concatenate([np.asarray(q, dtype=np.int64).reshape(-1) for q in seqs]) if U else np.zeros(0, np.int64)
+        flat, ptr = _flatten_sequences(handler.sequence)
+        U, I = len(ptr) - 1, int(n_items)
+        lens = np.diff(ptr)
         bad = np.flatnonzero((flat < 0) | (flat >= I))
         if bad.size:
             u = int(np.searchsorted(ptr, bad[0], side="right") - 1)
@@ -75,7 +123,7 @@ class DeviceSampler:
         has = np.flatnonzero(lens > 0)
         rows.append(has)
         cols.append(flat[ptr[has + 1] - 1])
-        tst = np.array([-1 if t is None else int(t) for t in handler.tstInt], dtype=np.int64)
+        tst = _tst_as_int64(handler.tstInt)
         tu = np.flatnonzero((tst >= 0) & (tst < I))
         rows.append(tu)
         cols.append(tst[tu])
@@ -111,7 +159,7 @@ class DeviceSampler:
 
 class DeviceEvaluator:
     """The fixed inputs of a test epoch (testEpoch / testEpochFull) as tables, built once from the host path's own
-    helpers (Recommender._test_candidates, _test_sequences, _masked_sum_csr) and kept on the device:
+    helpers (Recommender._test_batch, _masked_sum_csr, _exclusions) and kept on the device:
       - users int64 / uids int32 [n]: handler.tstUsrs, in order;
       - cand int32 [n, testSize]: the testSize - 1 negatives of test_dict, then the target LAST (sampleTestBatch);
       - target int32 [n]: tstInt (args.test) or the sequence's last item (validation);
@@ -128,44 +176,37 @@ class DeviceEvaluator:
     MAX_CANDIDATES = 8192      # sagnn_candidate_rank_f32's limit on C
 
     def __init__(self, rec, device=None):
-        h = rec.handler
         I, B = int(args.item), int(args.batch)
         if not 1 <= args.testSize <= self.MAX_CANDIDATES:
             raise ValueError(f"testSize = {args.testSize}: the device evaluator takes 1 .. {self.MAX_CANDIDATES}")
-        users = np.asarray(h.tstUsrs, dtype=np.int64).reshape(-1)
+        users = np.asarray(rec.handler.tstUsrs, dtype=np.int64).reshape(-1)
         n = len(users)
         flat, ptr = rec._flat_sequences()
-        neg_all, row_of = rec._test_candidates()
-        neg = neg_all[row_of[users]] if n else np.zeros((0, args.testSize - 1), np.int32)
-        if args.test:
-            target = np.array([-1 if t is None else int(t) for t in h.tstInt[users]], dtype=np.int64)
-        else:
+        rec._test_candidates()                   # a short test_dict row is reported first
+        if not args.test:
             empty = np.flatnonzero(ptr[users + 1] == ptr[users])
             if empty.size:
                 raise ValueError(f"user {int(users[empty[0]])} has an empty sequence: no validation target")
-            target = flat[ptr[users + 1] - 1]
+        self.chunks, parts = [], []
+        for st in range(0, n, B):
+            sequence, mask, start, seq_end, target, cand = rec._test_batch(users[st:st + B])
+            self.chunks.append((st, len(target)) + Recommender._masked_sum_csr(sequence, mask))
+            parts.append((start, seq_end, target, cand.astype(np.int32)))    # the negatives are int32 (test_dict table)
+        start, seq_end, target, cand = ([np.concatenate(c) for c in zip(*parts)] if parts else
+                                        [np.zeros(0, np.int64)] * 3 + [np.zeros((0, args.testSize), np.int32)])
         bad = np.flatnonzero((target < 0) | (target >= I))
         if bad.size:
             raise ValueError(f"target of test user {int(users[bad[0]])} is {int(target[bad[0]])}, outside [0, {I})")
-        bad = np.argwhere((neg < 0) | (neg >= I))
+        bad = np.argwhere((cand[:, :-1] < 0) | (cand[:, :-1] >= I))
         if bad.size:
             r, j = bad[0]
-            raise ValueError(f"test_dict candidate {int(neg[r, j]) + 1} of user {int(users[r]) + 1} is outside [1, {I}]")
+            raise ValueError(f"test_dict candidate {int(cand[r, j]) + 1} of user {int(users[r]) + 1} is outside [1, {I}]")
         self.n, self.n_items, self.batch = n, I, B
         self.users = users
         self.target = target.astype(np.int32)
-        self.cand = np.ascontiguousarray(np.concatenate([neg.astype(np.int32), self.target[:, None]], axis=1))
-        self.chunks, lens, excl = [], [], []
-        for st in range(0, n, B):
-            bat = users[st:st + B]
-            sequence, mask, start, seq_end = rec._test_sequences(bat)
-            self.chunks.append((st, len(bat)) + Recommender._masked_sum_csr(sequence, mask))
-            lens.append(seq_end - start)
-            excl.append(np.concatenate([np.sort(flat[a:e]) for a, e in zip(start, seq_end)]))
-        self.excl_rowptr = np.zeros(n + 1, dtype=np.int64)
-        if n:
-            np.cumsum(np.concatenate(lens), out=self.excl_rowptr[1:])
-        self.excl_items = np.concatenate(excl).astype(np.int32) if excl else np.zeros(0, np.int32)
+        self.cand = cand
+        self.excl_rowptr, excl = _exclusions(flat, start, seq_end)
+        self.excl_items = excl.astype(np.int32)
         self.device = None
         if device is not None:
             self._upload(device)
@@ -375,8 +416,8 @@ class Recommender:
         final_user_vector / final_item_vector. sequence/mask: [args.batch, pos_length]."""
         fu, fi = self.final_user_vector, self.final_item_vector
         att = self._head_att(sequence, mask)
-        as_i32 = lambda v: torch.as_tensor(np.asarray(v, dtype=np.int32), device=self.device)
-        return ops.pair_score(fu, fi, as_i32(uids), as_i32(iids), S=att, A=fi, locs=as_i32(uLocs_seq), leaky=NNs.leaky)
+        return ops.pair_score(fu, fi, self._i32(uids), self._i32(iids), S=att, A=fi, locs=self._i32(uLocs_seq),
+                              leaky=NNs.leaky)
 
     def _head_att(self, sequence, mask):
         """The head's sequence representation att [args.batch, d] (model.py:158-168) on the cached final vectors."""
@@ -409,56 +450,19 @@ class Recommender:
         item (validation), the last min(len, pos_length) items right-aligned. Returns sequence, mask [args.batch,
         pos_length], and per user the flat range [start, seq_end) the sequence was cut from."""
         batIds = np.asarray(batIds, dtype=np.int64)
-        P = args.pos_length
         flat, ptr = self._flat_sequences()
         start, end = ptr[batIds], ptr[batIds + 1]
         seq_end = end if args.test else np.maximum(end - 1, start)
-        k = np.minimum(seq_end - start, P)
-        sequence = np.zeros((args.batch, P), dtype=np.int64)
-        mask = np.zeros((args.batch, P), dtype=np.float32)
-        rws = np.repeat(np.arange(len(batIds), dtype=np.int64), k)
-        within = np.arange(int(k.sum()), dtype=np.int64) - np.repeat(np.cumsum(k) - k, k)
-        sequence[rws, P - k[rws] + within] = flat[seq_end[rws] - k[rws] + within]
-        mask[rws, P - k[rws] + within] = 1
+        sequence, mask = _right_aligned(flat, seq_end, seq_end - start, args.batch, args.pos_length)
         return sequence, mask, start, seq_end
 
-    def _test_candidates(self):
-        """test_dict (1-indexed user -> 1-indexed candidate items, preprocess_to_sequence.ipynb cell 11) as one int32
-        matrix [test users, testSize - 1] of 0-indexed negatives + the row of every user in it; built once (the
-        reference re-reads the dict per user and batch: 25 ms of list -> array conversions per 512-user batch)."""
-        cached = getattr(self, "_tst_cache", None)
-        if cached is None or cached[2] is not self.handler.test_dict or cached[3] != args.testSize:
-            users = np.asarray(self.handler.tstUsrs, dtype=np.int64)
-            row_of = np.full(args.user, -1, dtype=np.int64)
-            row_of[users] = np.arange(len(users))
-            k = args.testSize - 1
-            neg = np.empty((len(users), k), dtype=np.int32)
-            for r, u in enumerate(users):
-                cand = self.handler.test_dict[int(u) + 1][:k]
-                if len(cand) != k:
-                    raise ValueError(f"test_dict[{int(u) + 1}] holds {len(cand)} candidates, testSize - 1 = {k} needed")
-                neg[r] = cand
-            neg -= 1
-            cached = self._tst_cache = (neg, row_of, self.handler.test_dict, args.testSize)
-        return cached[0], cached[1]
-
-    def sampleTestBatch(self, batIds, labelMat=None):
-        """reference model.py:384-428: args.testSize-1 pre-drawn negatives from test_dict
-        (1-indexed user keys and item ids) plus the held-out positive LAST; the user's whole
-        sequence, right-aligned into pos_length slots. Vectorised over the batch (users outside
-        handler.tstUsrs take the reference's per-user path)."""
+    def _test_batch(self, batIds):
+        """The inputs of a test batch for both evaluators: _test_sequences' four arrays, the target int64 [n] (tstInt, -1
+        for None; in validation the held-out item flat[seq_end]) and the candidates int64 [n, testSize]: test_dict's
+        testSize - 1 negatives (users outside tstUsrs read the dict itself), then the target LAST."""
         batIds = np.asarray(batIds, dtype=np.int64)
-        batch = len(batIds)
-        temTst = self.handler.tstInt[batIds]
-        flat, _ = self._flat_sequences()
         sequence, mask, start, seq_end = self._test_sequences(batIds)
-        val_list = [None] * args.batch
-        if args.test:
-            posloc = np.array([(-1 if t is None else t) for t in temTst], dtype=np.int64)
-        else:
-            posloc = flat[seq_end]                                # last item held out for validation
-            for i in range(batch):
-                val_list[i] = int(posloc[i])
+        target = self._tst_ids()[batIds] if args.test else self._flat_sequences()[0][seq_end]
         neg_all, row_of = self._test_candidates()
         rows = row_of[batIds]
         if (rows < 0).any():                                      # not a test user: fall back to the dict
@@ -466,13 +470,63 @@ class Recommender:
                             for u in batIds])
         else:
             neg = neg_all[rows].astype(np.int64)
-        locs = np.concatenate([neg, posloc[:, None]], axis=1)     # [batch, testSize], positive LAST
-        tstLocs = list(locs)
+        return sequence, mask, start, seq_end, target, np.concatenate([neg, target[:, None]], axis=1)
+
+    def _cached(self, name, key, build):
+        """build()'s value, kept in attribute `name` as (signature, value, key) until `key` changes: objects compare by
+        identity (the entry holds them, so ids are not reused), flags by value. The old value goes before build() runs."""
+        sig = tuple(k if isinstance(k, (bool, int, float, str)) else id(k) for k in key)
+        entry = getattr(self, name, None)
+        if entry is None or entry[0] != sig:
+            setattr(self, name, None)
+            entry = (sig, build(), key)
+            setattr(self, name, entry)
+        return entry[1]
+
+    def _flat_sequences(self):
+        """_flatten_sequences(handler.sequence), built once."""
+        return self._cached("_seq_cache", (self.handler.sequence,), lambda: _flatten_sequences(self.handler.sequence))
+
+    def _tst_ids(self):
+        """_tst_as_int64(handler.tstInt), built once."""
+        return self._cached("_tst_ids_cache", (self.handler.tstInt,), lambda: _tst_as_int64(self.handler.tstInt))
+
+    def _test_candidates(self):
+        """test_dict (1-indexed user -> 1-indexed candidate items, preprocess_to_sequence.ipynb cell 11) as one int32
+        matrix [test users, testSize - 1] of 0-indexed negatives + the row of every user in it; built once (the
+        reference re-reads the dict per user and batch: 25 ms of list -> array conversions per 512-user batch)."""
+        h = self.handler
+
+        def build():
+            users = np.asarray(h.tstUsrs, dtype=np.int64)
+            row_of = np.full(args.user, -1, dtype=np.int64)
+            row_of[users] = np.arange(len(users))
+            k = args.testSize - 1
+            neg = np.empty((len(users), k), dtype=np.int32)
+            for r, u in enumerate(users):
+                cand = h.test_dict[int(u) + 1][:k]
+                if len(cand) != k:
+                    raise ValueError(f"test_dict[{int(u) + 1}] holds {len(cand)} candidates, testSize - 1 = {k} needed")
+                neg[r] = cand
+            neg -= 1
+            return neg, row_of
+        return self._cached("_tst_cache", (h.test_dict, h.tstUsrs, args.user, args.testSize), build)
+
+    def sampleTestBatch(self, batIds, labelMat=None):
+        """reference model.py:384-428: args.testSize-1 pre-drawn negatives from test_dict
+        (1-indexed user keys and item ids) plus the held-out positive LAST; the user's whole
+        sequence, right-aligned into pos_length slots (_test_batch)."""
+        batIds = np.asarray(batIds, dtype=np.int64)
+        temTst = self.handler.tstInt[batIds]
+        sequence, mask, _, _, target, locs = self._test_batch(batIds)
+        val_list = [None] * args.batch
+        if not args.test:
+            for i, t in enumerate(target.tolist()):              # last item held out for validation
+                val_list[i] = t
         C = locs.shape[1]
         uLocs = np.repeat(batIds, C)
-        uLocs_seq = np.repeat(np.arange(batch, dtype=np.int64), C)
-        iLocs = locs.reshape(-1)
-        return uLocs, iLocs, temTst, tstLocs, sequence, mask, uLocs_seq, val_list
+        uLocs_seq = np.repeat(np.arange(len(batIds), dtype=np.int64), C)
+        return uLocs, locs.reshape(-1), temTst, list(locs), sequence, mask, uLocs_seq, val_list
 
     @staticmethod
     def calcRes(preds, temTst, tstLocs, shoot=None):
@@ -495,11 +549,7 @@ class Recommender:
         p_best = np.where(copies, preds, -np.inf).max(1)                       # highest score among the copies
         first = (copies & (preds == p_best[:, None])).argmax(1)                 # its first candidate index
         ahead = (preds > p_best[:, None]).sum(1) + ((preds == p_best[:, None]) & (np.arange(C)[None, :] < first[:, None])).sum(1)
-        res = []
-        for k in (shoot, 5, 20):
-            hit = has & (ahead < k)
-            res += [float(hit.sum()), float((1.0 / np.log2(ahead[hit] + 2)).sum())]
-        return tuple(res)
+        return _rank_sums(np.where(has, ahead, -1), shoot)
 
     def testEpoch(self):
         """reference model.py:430-482. The hot path is evaluated ONCE (parameters are frozen and
@@ -517,8 +567,7 @@ class Recommender:
             preds = self.predict(uLocs, iLocs, sequence, mask, uLocs_seq).cpu().numpy()
             target = temTst if args.test else val_list
             tot += np.array(self.calcRes(preds.reshape(len(batIds), -1), target, tstLocs))
-        return {"HR": tot[0] / num, "NDCG": tot[1] / num, "HR5": tot[2] / num, "NDCG5": tot[3] / num,
-                "HR20": tot[4] / num, "NDCG20": tot[5] / num}
+        return _metrics(tot, num)
 
     def recommend(self, uids, k=None, exclude_seen=True):
         """The k best items of the whole catalogue for each user (sagnn_score_topk_f32 on _query_rows), on the cached
@@ -557,33 +606,18 @@ class Recommender:
         tot = np.zeros(6)
         for st in range(0, num, args.batch):
             batIds = np.asarray(ids[st:st + args.batch], dtype=np.int64)
-            _, _, temTst, _, sequence, mask, _, val_list = self.sampleTestBatch(batIds)
-            target = temTst if args.test else val_list
-            tgt = np.asarray([(-1 if t is None else t) for t in target[:len(batIds)]], dtype=np.int32)
-            _, _, start, seq_end = self._test_sequences(batIds)
-            rowptr = np.zeros(len(batIds) + 1, dtype=np.int64)
-            np.cumsum(seq_end - start, out=rowptr[1:])
-            excl = np.concatenate([np.sort(flat[a:e]) for a, e in zip(start, seq_end)]) if len(batIds) else []
+            sequence, mask, start, seq_end, target, _ = self._test_batch(batIds)
             _, _, rank = ops.score_topk(self._query_rows(batIds, sequence, mask), self.final_item_vector, 1,
-                                        excl=(rowptr, excl), target=tgt)
-            rank = rank.cpu().numpy()
-            for j, kk in enumerate((args.shoot, 5, 20)):
-                hit = (rank >= 0) & (rank < kk)
-                tot[2 * j] += hit.sum()
-                tot[2 * j + 1] += (1.0 / np.log2(rank[hit] + 2)).sum()
-        return {"HR": tot[0] / num, "NDCG": tot[1] / num, "HR5": tot[2] / num, "NDCG5": tot[3] / num,
-                "HR20": tot[4] / num, "NDCG20": tot[5] / num}
+                                        excl=_exclusions(flat, start, seq_end), target=target.astype(np.int32))
+            tot += np.array(_rank_sums(rank.cpu().numpy(), args.shoot))
+        return _metrics(tot, num)
 
     def _device_evaluator(self) -> DeviceEvaluator:
         """The device evaluator's tables for the current handler and flags, built once."""
         h = self.handler
-        key = (id(h.sequence), id(h.test_dict), id(h.tstInt), id(h.tstUsrs), bool(args.test), args.testSize,
-               args.pos_length, args.batch, args.item, str(self.device))
-        cached = getattr(self, "_dev_eval", None)
-        if cached is None or cached[0] != key:
-            self._dev_eval = None                         # free the old tables before building the new ones
-            cached = self._dev_eval = (key, DeviceEvaluator(self, self.device))
-        return cached[1]
+        key = (h.sequence, h.test_dict, h.tstInt, h.tstUsrs, bool(args.test), args.testSize, args.pos_length, args.batch,
+               args.item, str(self.device))
+        return self._cached("_dev_eval", key, lambda: DeviceEvaluator(self, self.device))
 
     def _test_epoch_device(self, full: bool):
         """testEpoch (full=False) or testEpochFull (full=True) on the device evaluator's tables: forward() once, then
@@ -608,18 +642,11 @@ class Recommender:
     @staticmethod
     def _rank_metrics(rank, batch):
         """HR / NDCG at shoot, 5 and 20 from the target ranks of every test user (-1 = a miss), summed per batch of
-        `batch` users in float64 in the order calcRes and testEpochFull sum them, so the dict equals theirs."""
-        num = len(rank)
+        `batch` users in float64 with the helpers of testEpoch and testEpochFull, so the dict equals theirs."""
         tot = np.zeros(6)
-        for st in range(0, num, batch):
-            r = rank[st:st + batch]
-            res = []
-            for k in (args.shoot, 5, 20):
-                hit = (r >= 0) & (r < k)
-                res += [float(hit.sum()), float((1.0 / np.log2(r[hit] + 2)).sum())]
-            tot += np.array(res)
-        return {"HR": tot[0] / num, "NDCG": tot[1] / num, "HR5": tot[2] / num, "NDCG5": tot[3] / num,
-                "HR20": tot[4] / num, "NDCG20": tot[5] / num}
+        for st in range(0, len(rank), batch):
+            tot += np.array(_rank_sums(rank[st:st + batch], args.shoot))
+        return _metrics(tot, len(rank))
 
     # ------------------------------------------------------------------ training (SURVEY §8f rank 3)
     def _i32(self, v):
@@ -664,14 +691,12 @@ class Recommender:
             pos_tok = ag.SpmmFn.apply(self.posEmbed, pp, ppt)
         B = seq_tok.shape[0]
         ln = lambda x, gb: ag.LayerNormFn.apply(x.view(B, 1, d), gb[0], gb[1]).view(B, d)
-        zero = torch.zeros((B, d), dtype=torch.float32, device=self.device)
         att = ag.LeakyAddFn.apply(ln(seq_tok, self.head_ln[0]), ln(pos_tok, self.head_ln[1]), 1.0)
         for i, mh in enumerate(self.multihead_self_attention_sequence):
             w = mh.weights()
             a1 = ag.MhsaMeanFn.apply(ln(att, self.head_ln[2 + i]).view(B, 1, d), w["Wq"], w["bq"], w["Wk"], w["bk"],
                                      w["Wv"], w["bv"], heads)
             att = ag.LeakyAddFn.apply(a1, att, leaky)
-        del zero
         preds = ag.PairScoreFn.apply(fu, fi, att, self._i32(batch["uids"]), self._i32(batch["iids"]),
                                      self._i32(batch["uLocs_seq"]), leaky)
         n = preds.shape[0] // 2
@@ -693,22 +718,18 @@ class Recommender:
         """Transposed per-batch CSRs (rows = items / positions, columns = batch slots) for the
         backward of the masked sums. scipy's CSR -> CSC conversion is a counting sort that keeps
         duplicated entries (an item twice in a sequence counts twice), 4x cheaper than an argsort."""
-        import scipy.sparse as sp
-        sequence = np.asarray(sequence, dtype=np.int64)
-        keep = np.asarray(mask) != 0
-        B, L = keep.shape
-        rowptr = np.zeros(B + 1, dtype=np.int32)
-        np.cumsum(keep.sum(1), out=rowptr[1:])
-        nnz = int(rowptr[-1])
+        rowptr, items, pos = self._masked_sum_csr(sequence, mask)
+        B, L = np.asarray(mask).shape
         out = []
-        for cols, n_rows in ((sequence[keep].astype(np.int32), args.item),
-                             (np.broadcast_to(np.arange(L, dtype=np.int32), (B, L))[keep], L)):
-            csc = sp.csr_matrix((np.ones(nnz, dtype=np.int8), cols, rowptr), shape=(B, n_rows)).tocsc()
+        for cols, n_rows in ((items, args.item), (pos, L)):
+            csc = sp.csr_matrix((np.ones(len(cols), dtype=np.int8), cols, rowptr), shape=(B, n_rows)).tocsc()
             out.append(ops.SpmmPlan(csc.indptr.astype(np.int32), csc.indices.astype(np.int32), n_rows, B, device=self.device,
                                     validate=False))
         return out
 
-    def sampleTrainBatch(self, batIds, labelMat, timeMat=None, train_sample_num=40, as_arrays=False):
+    TRAIN_SAMPLE_NUM = 40      # the train_sample_num trainEpoch passes (sample_num_list, reference model.py:345-356)
+
+    def sampleTrainBatch(self, batIds, labelMat, timeMat=None, train_sample_num=TRAIN_SAMPLE_NUM, as_arrays=False):
         """reference model.py:252-302: per user ONE positive (one of the last pred_num+1 items before
         the held-out one, repeated sampNum times) against sampNum uniform negatives the user has
         not interacted with (and != the last item / the test item); the sequence fed to the head
@@ -731,9 +752,8 @@ class Recommender:
         # ---- negatives: bulk rejection against seen items, the last item and the held-out item -----
         lab = labelMat[batIds]                                       # CSR rows, no densification
         slot_seen = np.repeat(np.arange(B, dtype=np.int64), np.diff(lab.indptr))
-        temTst = self.handler.tstInt[batIds]
-        has_tst = np.array([t is not None for t in temTst], dtype=bool)
-        tst_item = np.array([t if t is not None else 0 for t in temTst], dtype=np.int64)
+        tst_item = self._tst_ids()[batIds]
+        has_tst = tst_item >= 0
         last_item = flat[np.maximum(end - 1, start)]
         banned = np.concatenate([slot_seen * I + lab.indices.astype(np.int64),
                                  np.flatnonzero(act) * I + last_item[act],
@@ -751,29 +771,11 @@ class Recommender:
         half_u, half_i, half_l = batIds[slot], pos_item[slot], slot
         # ---- the sequence fed to the head: the items before the chosen positive, right-aligned -------
         m = np.maximum(n_pos - choose, 0)                            # len(posset[:-choose])
-        k = np.minimum(m, P)
-        sequence = np.zeros((args.batch, P), dtype=np.int64)
-        mask = np.zeros((args.batch, P), dtype=np.float32)
-        rows = np.repeat(np.arange(B, dtype=np.int64), k)
-        within = np.arange(int(k.sum()), dtype=np.int64) - np.repeat(np.cumsum(k) - k, k)
-        sequence[rows, P - k[rows] + within] = flat[start[rows] + m[rows] - k[rows] + within]
-        mask[rows, P - k[rows] + within] = 1
+        sequence, mask = _right_aligned(flat, start + m, m, args.batch, P)
         uL, iL, uLs = np.concatenate([half_u, half_u]), np.concatenate([half_i, negs]), np.concatenate([half_l, half_l])
         if as_arrays:      # the epoch loop keeps int32 arrays end to end (the list round trip cost 2 ms per step)
             return uL.astype(np.int32), iL.astype(np.int32), sequence, mask, uLs.astype(np.int32)
         return uL.tolist(), iL.tolist(), sequence, mask, uLs.tolist()       # the reference's feed_dict lists
-
-    def _flat_sequences(self):
-        """handler.sequence (one array per user) as one flat int64 array + offsets, built once."""
-        cached = getattr(self, "_seq_cache", None)
-        if cached is None or cached[2] is not self.handler.sequence:
-            seqs = self.handler.sequence
-            lens = np.fromiter((len(q) for q in seqs), dtype=np.int64, count=len(seqs))
-            ptr = np.zeros(len(seqs) + 1, dtype=np.int64)
-            np.cumsum(lens, out=ptr[1:])
-            flat = np.concatenate([np.asarray(q, dtype=np.int64) for q in seqs]) if len(seqs) else np.zeros(0, np.int64)
-            cached = self._seq_cache = (flat, ptr, seqs)
-        return cached[0], cached[1]
 
     def sampleSslBatch(self, batIds, labelMat, use_epsilon=True, as_arrays=False):
         """reference model.py:304-339: per interval and user up to sslNum (item, item) pairs drawn
@@ -789,35 +791,36 @@ class Recommender:
             npair = np.minimum(args.sslNum, deg // 2)                # pairs per user
             total = int(npair.sum())
             if total == 0:
-                empty = np.zeros(0, np.int32) if as_arrays else []
+                empty = np.zeros(0, np.int32)
                 uLocs.append(empty); iLocs.append(empty); uLocs_seq.append(empty)
                 continue
             slot = np.repeat(np.arange(len(batIds)), npair)          # batch slot of every pair
             base = lab.indptr[:-1][slot]
             first = lab.indices[base + (rng.random_sample(total) * deg[slot]).astype(np.int64)]
             second = lab.indices[base + (rng.random_sample(total) * deg[slot]).astype(np.int64)]
-            its = np.empty(2 * total, dtype=np.int64)
+            its = np.empty(2 * total, dtype=np.int32)
             its[0::2], its[1::2] = first, second
-            if as_arrays:
-                uLocs.append(np.repeat(batIds[slot], 2).astype(np.int32))
-                iLocs.append(its.astype(np.int32))
-                uLocs_seq.append(np.repeat(slot, 2).astype(np.int32))
-            else:
-                uLocs.append(np.repeat(batIds[slot], 2).tolist())
-                iLocs.append(its.tolist())
-                uLocs_seq.append(np.repeat(slot, 2).tolist())
-        return uLocs, iLocs, uLocs_seq
+            uLocs.append(np.repeat(batIds[slot], 2).astype(np.int32))
+            iLocs.append(its)
+            uLocs_seq.append(np.repeat(slot, 2).astype(np.int32))
+        if as_arrays:      # the epoch loop keeps int32 arrays; the reference's feed_dict takes lists
+            return uLocs, iLocs, uLocs_seq
+        return tuple([a.tolist() for a in x] for x in (uLocs, iLocs, uLocs_seq))
 
-    TRAIN_SAMPLE_NUM = 40      # the train_sample_num trainEpoch passes (sample_num_list, reference model.py:345-356)
+    def _host_train_batch(self, batIds) -> dict:
+        """trainEpoch's host-sampled batch for train_loss: sampleTrainBatch and sampleSslBatch as int32 arrays."""
+        h = self.handler
+        uLocs, iLocs, sequence, mask, uLocs_seq = self.sampleTrainBatch(batIds, h.trnMat, h.timeMat, self.TRAIN_SAMPLE_NUM,
+                                                                        as_arrays=True)
+        suLocs, siLocs, _ = self.sampleSslBatch(batIds, h.subMat, False, as_arrays=True)
+        return {"uids": uLocs, "iids": iLocs, "uLocs_seq": uLocs_seq, "sequence": sequence, "mask": mask,
+                "suids": suLocs, "siids": siLocs}
 
     def _device_sampler(self) -> DeviceSampler:
         """The device sampler's tables for the current handler and flags, built once."""
         h = self.handler
-        key = (id(h.sequence), id(h.trnMat), id(h.subMat), id(h.tstInt), args.item, args.sslNum, str(self.device))
-        cached = getattr(self, "_dev_sampler", None)
-        if cached is None or cached[0] != key:
-            cached = self._dev_sampler = (key, DeviceSampler(h, self.device, args.item, self.TRAIN_SAMPLE_NUM, args.sslNum))
-        return cached[1]
+        return self._cached("_dev_sampler", (h.sequence, h.trnMat, h.subMat, h.tstInt, args.item, args.sslNum, str(self.device)),
+                            lambda: DeviceSampler(h, self.device, args.item, self.TRAIN_SAMPLE_NUM, args.sslNum))
 
     def sample_batch_device(self, batIds, seed: int, step: int) -> dict:
         """One training batch drawn on the device: sampleTrainBatch's and sampleSslBatch's distributions (with the SSL
@@ -867,14 +870,7 @@ class Recommender:
         pre_sum = torch.zeros(1, dtype=torch.float32, device=self.device)
         for i in range(steps):
             batIds = sfIds[i * args.batch:(i + 1) * args.batch]
-            if device:
-                batch = self.sample_batch_device(batIds, seed, i)
-            else:
-                uLocs, iLocs, sequence, mask, uLocs_seq = self.sampleTrainBatch(batIds, self.handler.trnMat,
-                                                                                self.handler.timeMat, 40, as_arrays=True)
-                suLocs, siLocs, _ = self.sampleSslBatch(batIds, self.handler.subMat, False, as_arrays=True)
-                batch = {"uids": uLocs, "iids": iLocs, "uLocs_seq": uLocs_seq, "sequence": sequence, "mask": mask,
-                         "suids": suLocs, "siids": siLocs}
+            batch = self.sample_batch_device(batIds, seed, i) if device else self._host_train_batch(batIds)
             params = self._trainable()
             for p in params.values():
                 p.grad = None

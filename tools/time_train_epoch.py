@@ -78,9 +78,7 @@ def main():
                 if name == "device":
                     batch = rec.sample_batch_device(bat, seed, i)
                 else:
-                    uL, iL, sq, mk, uLs = rec.sampleTrainBatch(bat, h.trnMat, h.timeMat, 40, as_arrays=True)
-                    su, si, _ = rec.sampleSslBatch(bat, h.subMat, False, as_arrays=True)
-                    batch = {"uids": uL, "iids": iL, "uLocs_seq": uLs, "sequence": sq, "mask": mk, "suids": su, "siids": si}
+                    batch = rec._host_train_batch(bat)
                 torch.cuda.synchronize(); part["sample"] += time.perf_counter() - t; t = time.perf_counter()
                 params = rec._trainable()
                 for p in params.values():
