@@ -17,12 +17,19 @@ with ~100M unique edges each, embed_dim 64, 2 GNN layers. The SAME total graph r
 
 metric = SpMM edges/s = (edges traversed by all SpMM launches of all ranks per step) / (step time,
 max over ranks). `roofline` prices the dominant kernel (spmm_rows_kernel) with HIP events recorded
-on its launch stream inside the timed region; `cpu_baseline` times the oracle's C port of the
-TF1 CPU op chain on a bounded row sample of the same graph (rank 0, N = 1 only), next to which
-the GPU results of the user-side sample, an item-side slice holding the heaviest hub rows and a
->= 100k-row slice of the fused embeddings are compared with the oracle.
+on its launch stream inside the timed region.
 Prints exactly one JSON line on rank 0. `--dump-outputs DIR` also writes what the last timed step computed
 (DIR/<name>.npy, float32, a fixed seeded row sample where an output exceeds the budget: dump_outputs).
+
+A plain run does only that: set-up, warm-up, the timed steps, the dump, the line. `--full` adds what is
+measured or checked outside the timed steps:
+    fusion_f32_engine   the same step on the exact-fp32 engine (N = 1)
+    breakdown_ms        SpMM / exchange / fusion / gather passes each alone (N > 1)
+    cpu_baseline        the oracle's C port of the TF1 CPU op chain timed on a bounded row sample of the
+                        same graph (rank 0, N = 1), next to which the GPU results of the user-side sample,
+                        an item-side slice holding the heaviest hub rows and a >= 100k-row slice of the
+                        fused embeddings are compared with the oracle
+    roofline.traffic    HBM bytes per SpMM launch recorded by earlier PMC passes (profiles/*hbm_traffic*.json)
 """
 from __future__ import annotations
 
@@ -78,9 +85,12 @@ def parse():
     p.add_argument("--exchange", default="alltoall", choices=["alltoall", "allgather"])
     p.add_argument("--split", default="fractional", choices=["fractional", "groups"],
                    help="T < world: edge-balanced fractional row cuts across all ranks (default) or whole-rank groups per interval")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="after the result's own measurement, also run what a plain run leaves out: the exact-fp32 engine "
+                        "block, the N > 1 breakdown, the CPU baseline with the oracle checks, the recorded roofline traffic")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the oracle checks")
     p.add_argument("--no-breakdown", action="store_true",
-                   help="N > 1: skip the extra untimed-for-the-metric passes (SpMM only / exchange only / fusion only)")
+                   help="with --full, N > 1: skip the extra untimed-for-the-metric passes (SpMM only / exchange only / fusion only)")
     p.add_argument("--cpu-sample-rows", type=int, default=2_000_000)
     p.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU work spent on the cpu_baseline sample")
     p.add_argument("--tuning", default="", help="short,long,chunk override for the SpMM plan")
@@ -94,8 +104,8 @@ def parse():
                         "exchange rounds, pipelined fusion, gathers, their adjoints — through it; a check of the collective calls, "
                         "never a performance run")
     p.add_argument("--engine", default="f16x2", choices=["f16x2", "f32", "valu"],
-                   help="arithmetic engine of the fusion GEMMs for the timed steps (sagnn_set_engine); the default line also "
-                        "carries a short same-run block on the exact-fp32 engine (fusion_f32_engine)")
+                   help="arithmetic engine of the fusion GEMMs for the timed steps (sagnn_set_engine); with --full the default "
+                        "line also carries a short same-run block on the exact-fp32 engine (fusion_f32_engine)")
     p.add_argument("--graph", action="store_true",
                    help="N=1: time a hipGraph replay of the step (launch-bound small workloads); the "
                         "per-kernel event timing then comes from an extra eager pass before it")
@@ -538,7 +548,9 @@ def main():
                 for kk, name in ((0, "spmm_rows"), (1, "spmm_fixup"), (2, "lstm"), (3, "layernorm"), (4, "mhsa_mean"))}
     traffic, traffic_source = None, None
     import glob
-    for tpath in sorted(glob.glob(os.path.join(ROOT, "profiles", "*hbm_traffic*.json"))):
+    # recorded by PMC runs of their own, not measured here: --full only
+    tpaths = sorted(glob.glob(os.path.join(ROOT, "profiles", "*hbm_traffic*.json"))) if a.full else []
+    for tpath in tpaths:
         try:
             tj = json.load(open(tpath))
             if tj.get("workload") == a.workload and tj.get("scale", 1.0) == a.scale and a.zipf == tj.get("zipf", 0.8):
@@ -598,8 +610,8 @@ def main():
         if stage_ms["spmm_rows"] > 0 else None,
     }
 
-    # ---- the same steps on the exact-fp32 engine, same run (N = 1): what the f16 x 2 split buys ---------
-    if not multi and a.stages == "full" and a.engine == "f16x2" and not graph_mode:
+    # ---- --full: the same steps on the exact-fp32 engine, same run (N = 1): what the f16 x 2 split buys --
+    if a.full and not multi and a.stages == "full" and a.engine == "f16x2" and not graph_mode:
         with ops.engine("f32"):
             step()
             sync()
@@ -614,8 +626,8 @@ def main():
         step()                                                # leave the f16x2 results in place for the checks below
         sync()
 
-    # ---- N > 1: where the step time goes (extra passes, outside the timed region) ---------------
-    if multi and a.stages == "full" and not a.no_breakdown:
+    # ---- --full, N > 1: where the step time goes (extra passes, outside the timed region) --------
+    if a.full and multi and a.stages == "full" and not a.no_breakdown:
         bd = {}
 
         def timed(fn, reps=3):
@@ -665,8 +677,8 @@ def main():
             bd["error"] = f"{type(e).__name__}: {e}"
         result["breakdown_ms"] = bd
 
-    # ---- CPU baseline + oracle checks on bounded samples (rank 0, N = 1) ------------------------
-    if rank == 0 and not multi and not a.no_cpu_baseline and t_loc > 0:
+    # ---- --full: CPU baseline + oracle checks on bounded samples (rank 0, N = 1) -----------------
+    if a.full and rank == 0 and not multi and not a.no_cpu_baseline and t_loc > 0:
         import scipy.sparse as sp
         from oracle import selfgnn_oracle as O
         from oracle import tf1_path

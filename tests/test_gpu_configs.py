@@ -33,7 +33,7 @@ def _bench(*args):
 @pytest.mark.parametrize("launch", ["eager", "graph"])
 @pytest.mark.parametrize("workload", sorted(SHAPES))
 def test_dataset_shaped_config_against_the_oracle(workload, launch):
-    r = _bench("--workload", workload, "--steps", "2", "--warmup", "1", "--cpu-seconds", "1",
+    r = _bench("--workload", workload, "--steps", "2", "--warmup", "1", "--full", "--cpu-seconds", "1",
                *(["--graph"] if launch == "graph" else []))
     w, c = SHAPES[workload], r["config"]
     assert (c["users"], c["items"], c["intervals_total"], c["gnn_layers"], c["embed_dim"]) == (w["users"], w["items"], w["T"], w["L"], w["d"])
@@ -48,6 +48,7 @@ def test_dataset_shaped_config_against_the_oracle(workload, launch):
     assert set(fc["by_node_type"]) == {"users", "items"} and fc["intervals"] == w["T"]
     assert fc["worst_over_tolerance"] <= 1.0, fc
     assert fc["by_node_type"]["items"]["rows"] == min(65_536, w["items"])
+    assert ("fusion_f32_engine" in r) == (launch == "eager")      # the same-run exact-fp32 block: eager steps only
 
 
 def test_dump_outputs_hold_the_last_timed_step(tmp_path):
@@ -67,3 +68,13 @@ def test_dump_outputs_hold_the_last_timed_step(tmp_path):
         assert abs(a.mean() - r["final_abs_mean"][j]) <= 1e-6 * r["final_abs_mean"][j]
         pos = float((a.sum(axis=1) * np.arange(1, n + 1)).sum() / (n * (n + 1) / 2.0))
         assert abs(pos - r["final_position_checksum"][j]) <= 1e-6 * r["final_position_checksum"][j]
+
+
+def test_plain_run_leaves_the_full_blocks_out():
+    """Without --full the line holds the timed steps' own figures (headline, in-run roofline, checksums) and nothing that
+    needs work outside them: no exact-fp32 block, CPU baseline or oracle check, no recorded traffic."""
+    r = _bench("--workload", "gowalla-shaped", "--steps", "2", "--warmup", "1")
+    assert r["metric"] == "spmm_edges_per_sec" and r["value"] > 0 and r["ms_per_step"] > 0 and r["steps"] == 2
+    assert r["roofline"]["launches"] > 0 and r["roofline"]["traffic_source"] is None
+    assert len(r["final_abs_mean"]) == 2 and r["dumped_outputs"] is None
+    assert not set(r) & {"fusion_f32_engine", "cpu_baseline", "item_side_check", "fused_check", "breakdown_ms"}

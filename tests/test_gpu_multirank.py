@@ -26,7 +26,7 @@ def _run(cmd):
 def test_two_ranks_match_single_process():
     common = ["--steps", "1", "--warmup", "1", "--scale", "0.004", "--no-cpu-baseline"]
     one = _run([sys.executable, "bench.py", "--intervals", "4"] + common)
-    two = _run([sys.executable, "bench.py", "--gpus", "2",
+    two = _run([sys.executable, "bench.py", "--gpus", "2", "--full",
                 "--dist-backend", "gloo", "--intervals", "4"] + common)
     assert one["config"]["intervals_total"] == two["config"]["intervals_total"] == 4
     assert two["n_gpus"] == 2 and two["config"]["exchange"] == "alltoall"
@@ -54,7 +54,7 @@ def test_interval_count_not_a_multiple_of_the_rank_count(world, T):
     ranks issue in between meets it out of order and the run deadlocks (found by tools/fuzz_ranks.py)."""
     common = ["--steps", "1", "--warmup", "1", "--scale", "0.002", "--no-cpu-baseline", "--intervals", str(T)]
     one = _run([sys.executable, "bench.py"] + common)
-    many = _run([sys.executable, "bench.py", "--gpus", str(world), "--dist-backend", "gloo"] + common)
+    many = _run([sys.executable, "bench.py", "--gpus", str(world), "--dist-backend", "gloo", "--full"] + common)
     assert one["config"]["intervals_total"] == many["config"]["intervals_total"] == T
     assert one["final_abs_mean"] == many["final_abs_mean"]
     assert one["final_position_checksum"] == many["final_position_checksum"]
@@ -104,7 +104,7 @@ def test_rccl_single_rank_runs_the_multi_rank_code_path(stages):
     common = ["--steps", "2" if stages == "train" else "1", "--warmup", "0" if stages == "train" else "1", "--scale", "0.004",
               "--no-cpu-baseline", "--intervals", "4", "--stages", stages]
     one = _run([sys.executable, "bench.py"] + common)
-    rccl = _run([sys.executable, "bench.py", "--dist-single"] + common)
+    rccl = _run([sys.executable, "bench.py", "--dist-single", "--full"] + common)
     assert rccl["n_gpus"] == 1 and rccl["config"]["exchange"] == "alltoall"
     tol = 2e-5 if stages == "train" else 0.0
     for a_, b_ in zip(one["final_abs_mean"] + one["final_position_checksum"], rccl["final_abs_mean"] + rccl["final_position_checksum"]):
