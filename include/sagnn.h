@@ -621,6 +621,39 @@ int sagnn_seq_sum_bwd_f32(const float* g_seq, const float* g_pos, int64_t ldg, c
                           const int64_t* seg_begin, const int32_t* seg_len, int64_t n_slots, int pos_length, int d,
                           float* d_fi, int64_t ld_dfi, int64_t n_items, float* d_pos, int64_t ld_dpos, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Row subsets of the interval fusion for training (fusion_rows.hip). The fusion is independent per node and the loss
+ * reads few rows of its outputs, so a training step may fuse only the rows a batch reads: mark them, compact the
+ * marks into ascending row ids, gather those rows into a dense [cap, t, d] block for the fusion entries above, and
+ * scatter the results back.
+ * sagnn_rows_mark_i32: flags[ids[i]] = 1 for every i < n_ids with 0 <= ids[i] < n_rows (other ids are skipped).
+ * sagnn_rows_mark_seg_i32: the same for seq_items[seg_begin[b] + j], b < n_slots, j < min(seg_len[b], max_len), entries
+ *   outside [0, n_flat) skipped (the device sampler's sequence segments, read as sagnn_seq_sum_f32 reads them).
+ *   Several marks may go into one flag buffer (uint8 [n_rows], zero before the first mark).
+ * sagnn_rows_compact_i32: rows[0 .. count) = the flagged row ids in ascending order, *count (device int32) = how many
+ *   were flagged, slots [count, cap) = 0 (a valid id); ids past cap are dropped (*count still tells the total). Clears
+ *   every flag it read, so the buffer is zero again afterwards. Three launches; the workspace holds
+ *   sagnn_rows_compact_workspace_bytes(n_rows) bytes of tile offsets.
+ * sagnn_rows_gather_f32: out[j, s, :] = x[rows[j], s, :] for j < cap, s < t, x at strides ld_n (row) / ld_t
+ *   (interval), out dense [cap, t, d]. count non-NULL: slots j >= min(*count, cap) are written as zeros.
+ * sagnn_rows_scatter_f32: dst[rows[j], s, :] = src[j, s, :] for j < min(*count, cap), src dense [cap, t, d], dst at
+ *   strides ld_n / ld_t; no other element of dst is written. Rows must be distinct (a compaction's are).
+ * Row ids read on the device outside [0, n_rows) are skipped (gather writes zeros). Limits: 0 <= n_rows < 2^31;
+ *   0 <= cap <= n_rows, cap >= 1 for a compaction over n_rows > 0; d a multiple of 4 in [4, 256]; t >= 1; feature
+ *   pointers and the flag buffer 16-byte aligned, strides multiples of 4, ld_n >= d. Every argument is checked before
+ *   any device work. No allocation, no synchronisation.
+ * -------------------------------------------------------------------------------- */
+int sagnn_rows_mark_i32(const int32_t* ids, int64_t n_ids, int64_t n_rows, uint8_t* flags, void* stream);
+int sagnn_rows_mark_seg_i32(const int32_t* seq_items, int64_t n_flat, const int64_t* seg_begin, const int32_t* seg_len,
+                            int64_t n_slots, int max_len, int64_t n_rows, uint8_t* flags, void* stream);
+size_t sagnn_rows_compact_workspace_bytes(int64_t n_rows);
+int sagnn_rows_compact_i32(uint8_t* flags, int64_t n_rows, int32_t* rows, int64_t cap, int32_t* count, void* workspace,
+                           size_t workspace_bytes, void* stream);
+int sagnn_rows_gather_f32(const float* x, int64_t ld_n, int64_t ld_t, int64_t n_rows, int t, int d, const int32_t* rows,
+                          int64_t cap, const int32_t* count, float* out, void* stream);
+int sagnn_rows_scatter_f32(const float* src, const int32_t* rows, int64_t cap, const int32_t* count, int t, int d,
+                           float* dst, int64_t ld_n, int64_t ld_t, int64_t n_rows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

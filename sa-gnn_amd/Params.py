@@ -62,6 +62,10 @@ _FLAGS = [
                              "the reference)", ("host", "device")),
     ("evaluator", str, "host", "where test epochs score and rank: host (numpy ranking per batch) or device (tables "
                                "built once, ranks copied back once per epoch; not in the reference)", ("host", "device")),
+    ("fusion_rows", str, "all", "rows the training step's interval fusion runs on: all (every user and item) or batch "
+                                "(only the rows the loss reads; the same loss and gradients, but dropout masks are drawn "
+                                "for those rows only, so a seeded run reproduces within a mode, not across modes; not in "
+                                "the reference)", ("all", "batch")),
 ]
 
 

@@ -164,6 +164,14 @@ SIGNATURES = {
                                   c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
     "sagnn_seq_sum_bwd_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int,
                                       c_int, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
+    "sagnn_rows_mark_i32": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "sagnn_rows_mark_seg_i32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p]),
+    "sagnn_rows_compact_workspace_bytes": (c_size_t, [c_int64]),
+    "sagnn_rows_compact_i32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "sagnn_rows_gather_f32": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p,
+                                      c_void_p, c_void_p]),
+    "sagnn_rows_scatter_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_int64, c_int64,
+                                       c_int64, c_void_p]),
 }
 
 _lib = None

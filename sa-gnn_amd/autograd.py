@@ -165,6 +165,97 @@ def lstm_bwd(x, h, gates, cell, dh, drop, W):
     return dx, dW, db
 
 
+def _fusion_forward(x, lstm_W, lstm_b, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, heads, drop_scale):
+    """The training forward of the interval fusion on x [n, t, d] (any node/interval strides): returns
+    (out [n, d], h, gates, cell), the last three as the backward reads them."""
+    lib = ops._lib.load()
+    n, t, d, ld_n, ld_t = ops._ntd("x", x)
+    dev = x.device
+    h = torch.empty((n, t, d), dtype=torch.float32, device=dev)
+    gates = torch.empty((n, t, 4 * d), dtype=torch.float32, device=dev)
+    cell = torch.empty((n, t, d), dtype=torch.float32, device=dev)
+    # h is stored un-dropped (it is also the recurrent operand of the backward pass); the
+    # DropoutWrapper scaling of the emitted output is a separate element-wise pass
+    ops.check(lib.sagnn_lstm_fwd_train_f32(
+        x.data_ptr(), ld_n, ld_t, n, t, d, ops._vec("lstm_W", lstm_W.detach(), 8 * d * d),
+        ops._vec("lstm_b", lstm_b.detach(), 4 * d), 1.0, None, h.data_ptr(), t * d,
+        gates.data_ptr(), cell.data_ptr(), ops._stream()))
+    h_emit = h if drop_scale is None else ops.mul(h, drop_scale.contiguous())
+    out = ops.ln_mhsa_mean(h_emit, ln_gamma.detach(), ln_beta.detach(), Wq.detach(), bq.detach(), Wk.detach(),
+                           bk.detach(), Wv.detach(), bv.detach(), heads)
+    return out, h, gates, cell
+
+
+def _fusion_backward(x, lstm_W, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, h, gates, cell, drop, heads, g_out):
+    """The backward of _fusion_forward for g_out [n, d]: returns (dx [n, t, d], then the gradients of lstm_W, lstm_b,
+    ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv)."""
+    lib = ops._lib.load()
+    n, t, d, ld_n, ld_t = ops._ntd("x", x)
+    dev = x.device
+    st = ops._stream()
+    g_out = g_out.contiguous()
+    # ---- recompute y and Q|K|V, attention backward -> dQ|dK|dV -----------------------------
+    h_emit = h if drop is None else ops.mul(h, drop.contiguous())
+    Wqkv = torch.cat([Wq, Wk, Wv], dim=1).detach().contiguous()                      # [d, 3d]
+    if lib.sagnn_attn_bwd_front_supported(d, t, heads) and FUSED_ATTN_BWD:
+        y2, qkv = _attn_bwd_front(h_emit, ln_gamma.detach(), ln_beta.detach(), Wq, bq, Wk, bk, Wv, bv, heads, g_out)
+    else:
+        y = ops.layernorm_td(h_emit, ln_gamma.detach(), ln_beta.detach())            # [n, t, d]
+        bqkv = torch.cat([bq, bk, bv]).detach().contiguous()
+        y2 = y.view(n * t, d)
+        qkv = ops.dense_nn(y2, Wqkv, bqkv)                                           # [n*t, 3d]
+        ops.check(lib.sagnn_attn_bwd_f32(qkv.data_ptr(), g_out.data_ptr(), d, n, t, d, heads, st))
+    dWqkv = torch.zeros((d, 3 * d), dtype=torch.float32, device=dev)
+    dbqkv = torch.zeros(3 * d, dtype=torch.float32, device=dev)
+    if lib.sagnn_attn_bwd_tail_supported(d) and FUSED_ATTN_BWD:
+        # dW += y^T dQKV, db += colsum dQKV and dy = dQKV W^T (over y) in one pass over dQKV
+        ops.check(lib.sagnn_attn_bwd_tail_f32(y2.data_ptr(), qkv.data_ptr(), n * t, d, Wqkv.data_ptr(),
+                                              dWqkv.data_ptr(), dbqkv.data_ptr(), st))
+        dy = y2
+    else:
+        ops.dense_tn(y2, qkv, dWqkv, dbqkv)
+        dy = ops.dense_nn(qkv, Wqkv.t().contiguous(), None, out=y2)                  # reuses y's storage
+    # ---- layer norm backward (in place on dy) ----------------------------------------------
+    dgamma = torch.zeros(d, dtype=torch.float32, device=dev)
+    dbeta = torch.zeros(d, dtype=torch.float32, device=dev)
+    dh = dy.view(n, t, d)
+    ops.check(lib.sagnn_layernorm_td_bwd_f32(h_emit.data_ptr(), t * d, dh.data_ptr(), t * d, n, t, d,
+                                             ops._vec("gamma", ln_gamma.detach(), d), 1e-12, dh.data_ptr(),
+                                             t * d, dgamma.data_ptr(), dbeta.data_ptr(), st))
+    # ---- BPTT ----------------------------------------------------------------------------------
+    if lib.sagnn_lstm_bwd_supported(d) and FUSED_BPTT:
+        dx, dW, db = lstm_bwd(x, h, gates, cell, dh, drop, lstm_W.detach())
+        return (dx, dW, db, dgamma, dbeta) + _split_qkv_grads(dWqkv, dbqkv, d)
+    # generic BPTT (any d that is a multiple of 32; d = 128 is BASELINE config 3). Per step: the element-wise gate
+    # backward and ONE product d[x_t | h_{t-1}] = dG_t W^T written where the next step reads it. The gate gradients of
+    # all steps stay in HBM ([t, n, 4d]) and the weight gradient is two segmented products after the loop instead of
+    # 2 t small ones (each of those a split-K launch ending in 64 K float atomics per block).
+    WT = lstm_W.detach().t().contiguous()                                            # [4d, 2d]
+    dW = torch.zeros((2 * d, 4 * d), dtype=torch.float32, device=dev)
+    db = torch.zeros(4 * d, dtype=torch.float32, device=dev)
+    defer = n * t * 4 * d * 4 <= DEFERRED_DW_LIMIT
+    dG = torch.empty((t if defer else 1, n, 4 * d), dtype=torch.float32, device=dev)
+    dc = [torch.empty((n, d), dtype=torch.float32, device=dev) for _ in range(2)]
+    dxh = torch.empty((n, t, 2 * d), dtype=torch.float32, device=dev)                # [dx_t | dh_{t-1}] per step
+    for ts in range(t - 1, -1, -1):
+        last = ts == t - 1
+        dgates = dG[ts if defer else 0]
+        ops.check(lib.sagnn_lstm_bwd_step_f32(
+            gates.data_ptr(), cell.data_ptr(), dh.data_ptr(), t * d, ops._ptr(drop),
+            None if last else dxh[:, ts + 1, d:].data_ptr(), t * 2 * d, None if last else dc[(ts + 1) & 1].data_ptr(),
+            dgates.data_ptr(), dc[ts & 1].data_ptr(), n, t, d, ts, st))
+        if not defer:
+            ops.dense_tn(x[:, ts, :], dgates, dW[:d], db)
+            if ts > 0:
+                ops.dense_tn(h[:, ts - 1, :], dgates, dW[d:], None)                  # h un-dropped: the recurrent operand
+        ops.dense_nn(dgates, WT, None, out=dxh[:, ts, :])
+    if defer:
+        ops.dense_tn_seg(x.permute(1, 0, 2), dG, dW[:d], db)
+        if t > 1:
+            ops.dense_tn_seg(h.permute(1, 0, 2)[:t - 1], dG[1:], dW[d:], None)
+    return (dxh[:, :, :d].contiguous(), dW, db, dgamma, dbeta) + _split_qkv_grads(dWqkv, dbqkv, d)
+
+
 class IntervalFusionFn(torch.autograd.Function):
     """x [n, t, d] (any node/interval strides) + fusion parameters -> out [n, d]
     (reference model.py:135-155), differentiable in x and every parameter.
@@ -178,103 +269,95 @@ class IntervalFusionFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, lstm_W, lstm_b, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, heads, drop_scale):
-        lib = ops._lib.load()
-        n, t, d, ld_n, ld_t = ops._ntd("x", x)
-        dev = x.device
-        h = torch.empty((n, t, d), dtype=torch.float32, device=dev)
-        gates = torch.empty((n, t, 4 * d), dtype=torch.float32, device=dev)
-        cell = torch.empty((n, t, d), dtype=torch.float32, device=dev)
-        # h is stored un-dropped (it is also the recurrent operand of the backward pass); the
-        # DropoutWrapper scaling of the emitted output is a separate element-wise pass
-        ops.check(lib.sagnn_lstm_fwd_train_f32(
-            x.data_ptr(), ld_n, ld_t, n, t, d, ops._vec("lstm_W", lstm_W.detach(), 8 * d * d),
-            ops._vec("lstm_b", lstm_b.detach(), 4 * d), 1.0, None, h.data_ptr(), t * d,
-            gates.data_ptr(), cell.data_ptr(), ops._stream()))
-        h_emit = h if drop_scale is None else ops.mul(h, drop_scale.contiguous())
-        out = ops.ln_mhsa_mean(h_emit, ln_gamma.detach(), ln_beta.detach(), Wq.detach(), bq.detach(), Wk.detach(),
-                               bk.detach(), Wv.detach(), bv.detach(), heads)
+        out, h, gates, cell = _fusion_forward(x, lstm_W, lstm_b, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, heads,
+                                              drop_scale)
         ctx.save_for_backward(x, lstm_W, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, h, gates, cell,
-                              drop_scale if drop_scale is not None else torch.empty(0, device=dev))
+                              drop_scale if drop_scale is not None else torch.empty(0, device=x.device))
         ctx.heads = heads
         ctx.has_drop = drop_scale is not None
         return out
 
     @staticmethod
     def backward(ctx, g_out):
-        lib = ops._lib.load()
         (x, lstm_W, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, h, gates, cell, drop) = ctx.saved_tensors
         drop = drop if ctx.has_drop else None
-        heads = ctx.heads
-        n, t, d, ld_n, ld_t = ops._ntd("x", x)
-        dev = x.device
-        st = ops._stream()
-        g_out = g_out.contiguous()
-        # ---- recompute y and Q|K|V, attention backward -> dQ|dK|dV -----------------------------
-        h_emit = h if drop is None else ops.mul(h, drop.contiguous())
-        Wqkv = torch.cat([Wq, Wk, Wv], dim=1).detach().contiguous()                      # [d, 3d]
-        if lib.sagnn_attn_bwd_front_supported(d, t, heads) and FUSED_ATTN_BWD:
-            y2, qkv = _attn_bwd_front(h_emit, ln_gamma.detach(), ln_beta.detach(), Wq, bq, Wk, bk, Wv, bv, heads, g_out)
-        else:
-            y = ops.layernorm_td(h_emit, ln_gamma.detach(), ln_beta.detach())            # [n, t, d]
-            bqkv = torch.cat([bq, bk, bv]).detach().contiguous()
-            y2 = y.view(n * t, d)
-            qkv = ops.dense_nn(y2, Wqkv, bqkv)                                           # [n*t, 3d]
-            ops.check(lib.sagnn_attn_bwd_f32(qkv.data_ptr(), g_out.data_ptr(), d, n, t, d, heads, st))
-        dWqkv = torch.zeros((d, 3 * d), dtype=torch.float32, device=dev)
-        dbqkv = torch.zeros(3 * d, dtype=torch.float32, device=dev)
-        if lib.sagnn_attn_bwd_tail_supported(d) and FUSED_ATTN_BWD:
-            # dW += y^T dQKV, db += colsum dQKV and dy = dQKV W^T (over y) in one pass over dQKV
-            ops.check(lib.sagnn_attn_bwd_tail_f32(y2.data_ptr(), qkv.data_ptr(), n * t, d, Wqkv.data_ptr(),
-                                                  dWqkv.data_ptr(), dbqkv.data_ptr(), st))
-            dy = y2
-        else:
-            ops.dense_tn(y2, qkv, dWqkv, dbqkv)
-            dy = ops.dense_nn(qkv, Wqkv.t().contiguous(), None, out=y2)                  # reuses y's storage
-        # ---- layer norm backward (in place on dy) ----------------------------------------------
-        dgamma = torch.zeros(d, dtype=torch.float32, device=dev)
-        dbeta = torch.zeros(d, dtype=torch.float32, device=dev)
-        dh = dy.view(n, t, d)
-        ops.check(lib.sagnn_layernorm_td_bwd_f32(h_emit.data_ptr(), t * d, dh.data_ptr(), t * d, n, t, d,
-                                                 ops._vec("gamma", ln_gamma.detach(), d), 1e-12, dh.data_ptr(),
-                                                 t * d, dgamma.data_ptr(), dbeta.data_ptr(), st))
-        # ---- BPTT ----------------------------------------------------------------------------------
-        if lib.sagnn_lstm_bwd_supported(d) and FUSED_BPTT:
-            dx, dW, db = lstm_bwd(x, h, gates, cell, dh, drop, lstm_W.detach())
-            return (dx, dW, db, dgamma, dbeta) + _split_qkv_grads(dWqkv, dbqkv, d) + (None, None)
-        # generic BPTT (any d that is a multiple of 32; d = 128 is BASELINE config 3). Per step: the element-wise gate
-        # backward and ONE product d[x_t | h_{t-1}] = dG_t W^T written where the next step reads it. The gate gradients of
-        # all steps stay in HBM ([t, n, 4d]) and the weight gradient is two segmented products after the loop instead of
-        # 2 t small ones (each of those a split-K launch ending in 64 K float atomics per block).
-        WT = lstm_W.detach().t().contiguous()                                            # [4d, 2d]
-        dW = torch.zeros((2 * d, 4 * d), dtype=torch.float32, device=dev)
-        db = torch.zeros(4 * d, dtype=torch.float32, device=dev)
-        defer = n * t * 4 * d * 4 <= DEFERRED_DW_LIMIT
-        dG = torch.empty((t if defer else 1, n, 4 * d), dtype=torch.float32, device=dev)
-        dc = [torch.empty((n, d), dtype=torch.float32, device=dev) for _ in range(2)]
-        dxh = torch.empty((n, t, 2 * d), dtype=torch.float32, device=dev)                # [dx_t | dh_{t-1}] per step
-        for ts in range(t - 1, -1, -1):
-            last = ts == t - 1
-            dgates = dG[ts if defer else 0]
-            ops.check(lib.sagnn_lstm_bwd_step_f32(
-                gates.data_ptr(), cell.data_ptr(), dh.data_ptr(), t * d, ops._ptr(drop),
-                None if last else dxh[:, ts + 1, d:].data_ptr(), t * 2 * d, None if last else dc[(ts + 1) & 1].data_ptr(),
-                dgates.data_ptr(), dc[ts & 1].data_ptr(), n, t, d, ts, st))
-            if not defer:
-                ops.dense_tn(x[:, ts, :], dgates, dW[:d], db)
-                if ts > 0:
-                    ops.dense_tn(h[:, ts - 1, :], dgates, dW[d:], None)                  # h un-dropped: the recurrent operand
-            ops.dense_nn(dgates, WT, None, out=dxh[:, ts, :])
-        if defer:
-            ops.dense_tn_seg(x.permute(1, 0, 2), dG, dW[:d], db)
-            if t > 1:
-                ops.dense_tn_seg(h.permute(1, 0, 2)[:t - 1], dG[1:], dW[d:], None)
-        return (dxh[:, :, :d].contiguous(), dW, db, dgamma, dbeta) + _split_qkv_grads(dWqkv, dbqkv, d) + (None, None)
+        return _fusion_backward(x, lstm_W, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, h, gates, cell, drop, ctx.heads,
+                                g_out) + (None, None)
 
 
 def interval_fusion(x, p: dict, heads: int, drop_scale=None):
     """Differentiable interval fusion; p as in ops.interval_fusion."""
     return IntervalFusionFn.apply(x, p["lstm_W"], p["lstm_b"], p["ln_gamma"], p["ln_beta"], p["Wq"], p["bq"],
                                   p["Wk"], p["bk"], p["Wv"], p["bv"], heads, drop_scale)
+
+
+class IntervalFusionRowsFn(torch.autograd.Function):
+    """The interval fusion of the rows a training step reads: x [N, t, d] (any node/interval strides, the GNN slab's
+    view), rows int32 [cap] ascending and distinct in their first `count` slots (ops.rows_compact), count int32 [1] on
+    the device -> out [N, d], the fusion of x[rows[j]] in row rows[j] for j < count and exact zeros elsewhere.
+    Forward: gather the rows into a dense [cap, t, d] block, _fusion_forward on it, scatter. Backward: gather the
+    upstream gradient's rows (zeros in the padding slots j >= count), _fusion_backward, scatter dx into a zero
+    [N, t, d] gradient. The fusion is independent per node, so an untouched row has no gradient to give.
+    drop_scale: None, a full-size [N, t, d] mask (gathered with the rows) or a [cap, t, d] mask for the slots
+    (cap != N)."""
+
+    @staticmethod
+    def forward(ctx, x, rows, count, lstm_W, lstm_b, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, heads, drop_scale):
+        N, t, d = (int(v) for v in x.shape)
+        cap = int(rows.numel())
+        dev = x.device
+        ctx.heads, ctx.shape, ctx.x_layout = heads, (N, t, d), x.stride(1) == N * d and x.stride(0) == d
+        out = torch.zeros((N, d), dtype=torch.float32, device=dev)
+        ctx.has_drop = drop_scale is not None
+        if cap == 0:
+            ctx.empty = True
+            ctx.save_for_backward(lstm_W, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv)
+            return out
+        ctx.empty = False
+        xs = ops.rows_gather(x.detach(), rows)                                           # [cap, t, d] dense
+        drop = None
+        if drop_scale is not None:
+            if tuple(drop_scale.shape) == (N, t, d):
+                drop = ops.rows_gather(drop_scale, rows)
+            elif tuple(drop_scale.shape) == (cap, t, d):
+                drop = drop_scale.contiguous()
+            else:
+                raise ValueError(f"drop_scale: expected [{N}, {t}, {d}] or [{cap}, {t}, {d}], got {tuple(drop_scale.shape)}")
+        fused, h, gates, cell = _fusion_forward(xs, lstm_W, lstm_b, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, heads, drop)
+        ops.rows_scatter(fused, rows, count, out)
+        ctx.save_for_backward(xs, rows, count, lstm_W, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, h, gates, cell,
+                              drop if drop is not None else torch.empty(0, device=dev))
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        N, t, d = ctx.shape
+        if ctx.empty:
+            params = ctx.saved_tensors
+            lstm_W = params[0]
+            zeros = (torch.zeros_like(lstm_W), torch.zeros(4 * d, dtype=torch.float32, device=lstm_W.device)) + \
+                tuple(torch.zeros_like(p) for p in params[1:])
+            return (torch.zeros((N, t, d), dtype=torch.float32, device=lstm_W.device), None, None) + zeros + (None, None)
+        (xs, rows, count, lstm_W, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, h, gates, cell, drop) = ctx.saved_tensors
+        drop = drop if ctx.has_drop else None
+        g = ops.rows_gather(g_out if g_out.stride(1) == 1 else g_out.contiguous(), rows, count)   # [cap, d]
+        grads = _fusion_backward(xs, lstm_W, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, h, gates, cell, drop, ctx.heads, g)
+        dev = xs.device
+        # in the slab's own layout ([t, N, d] storage seen as [N, t, d]) when x is that view
+        dx = torch.zeros((t, N, d), dtype=torch.float32, device=dev).permute(1, 0, 2) if ctx.x_layout else \
+            torch.zeros((N, t, d), dtype=torch.float32, device=dev)
+        ops.rows_scatter(grads[0].contiguous(), rows, count, dx)
+        return (dx, None, None) + grads[1:] + (None, None)
+
+
+def interval_fusion_rows(x, rows, count, cap: int, p: dict, heads: int, drop_scale=None):
+    """Differentiable interval fusion of rows[:cap] of x (IntervalFusionRowsFn): [N, d] with exact zeros in every row
+    not among the first `count` slots. rows / count as ops.rows_compact returns them (count on the device; cap, the
+    number of slots to run, from the host, at least the count); p as in ops.interval_fusion."""
+    if int(cap) > rows.numel():
+        raise ValueError(f"cap = {int(cap)} > {rows.numel()} row slots")
+    return IntervalFusionRowsFn.apply(x, rows[:int(cap)], count, p["lstm_W"], p["lstm_b"], p["ln_gamma"], p["ln_beta"],
+                                      p["Wq"], p["bq"], p["Wk"], p["bk"], p["Wv"], p["bv"], heads, drop_scale)
 
 
 # ----------------------------------------------------------------------------------------------

@@ -660,9 +660,15 @@ class Recommender:
         uLocs_seq, sequence [args.batch, pos_length], mask, suids[k], siids[k]; a device-sampled batch
         (sample_batch_device) carries seq_seg = (seg_begin, seg_len) instead of sequence / mask. Returns
         (preLoss, sslloss) as 1-element tensors; total loss = preLoss + ssl_reg*sslloss (+ the L2
-        term, applied inside the optimiser step)."""
+        term, applied inside the optimiser step). Under --fusion_rows batch the interval fusion runs on the rows the
+        loss reads only (_touched_rows, autograd.interval_fusion_rows); fu / fi stay full-size with zero rows elsewhere."""
         T, L, d, heads, leaky = args.graphNum, args.gnn_layer, args.latdim, args.num_attention_heads, NNs.leaky
         keep = args.keepRate if keep_rate is None else keep_rate
+        subset = args.fusion_rows == "batch"
+        if subset:        # the rows the loss reads, compacted on the device before the GNN stack is queued
+            batch = dict(batch, uids=self._i32(batch["uids"]), iids=self._i32(batch["iids"]),
+                         suids=[self._i32(v) for v in batch["suids"]], siids=[self._i32(v) for v in batch["siids"]])
+            touched = self._touched_rows(batch)
         # one autograd node for the whole interval loop; uv / iv are [T, N, d] slabs written in place
         batch_ = self._interval_batch()
         if batch_ is not None:
@@ -670,15 +676,28 @@ class Recommender:
         else:
             uv, iv = ag.gnn_stack(self.uEmbed, self.iEmbed, [a.plan for a in self.subAdj], [a.plan for a in self.subTpAdj], L, leaky)
         finals = []
-        for xs, (gamma, beta), att, key in ((uv, self.ln[0], self.multihead_self_attention0, "drop_u"),
-                                            (iv, self.ln[1], self.multihead_self_attention1, "drop_i")):
+        if subset:        # the one read-back of the step: the two counts, copied while the stack's launches queue
+            touched["done"].synchronize()
+            counts = [int(v) for v in touched["host"]]
+            for side, n, c in zip(("users", "items"), counts, touched["caps"]):
+                if n > c:
+                    raise RuntimeError(f"fusion_rows: {n} touched {side} exceed the capacity {c}")
+            self.fusion_rows_counts = tuple(counts)
+        for side, (xs, (gamma, beta), att, key) in enumerate(((uv, self.ln[0], self.multihead_self_attention0, "drop_u"),
+                                                              (iv, self.ln[1], self.multihead_self_attention1, "drop_i"))):
             x = xs.permute(1, 0, 2)                                       # [N, T, d] view of [T, N, d]: no copy
             drop = batch.get(key)
+            # the slots the fusion runs on: at least one, so that an empty set still runs (on padding, to zeros)
+            n_run = max(counts[side], 1) if subset else x.shape[0]
             if drop is None and keep < 1.0:                               # DropoutWrapper(output_keep_prob)
-                drop = (torch.rand((x.shape[0], T, d), device=self.device) < keep).float() / keep
+                drop = (torch.rand((n_run, T, d), device=self.device) < keep).float() / keep
             p = {"lstm_W": self.lstm_kernel, "lstm_b": self.lstm_bias, "ln_gamma": gamma, "ln_beta": beta}
             p.update(att.weights())
-            finals.append(ag.interval_fusion(x, p, heads, drop_scale=drop))
+            if subset:
+                rows, count = touched["rows"][side]
+                finals.append(ag.interval_fusion_rows(x, rows, count, n_run, p, heads, drop_scale=drop))
+            else:
+                finals.append(ag.interval_fusion(x, p, heads, drop_scale=drop))
         fu, fi = finals
         # ---- head (model.py:156-173)
         if "seq_seg" in batch:                                            # device-sampled: segments, no CSRs
@@ -713,6 +732,39 @@ class Recommender:
             p1 = ag.ProdLeakySumFn.apply(uv[k], iv[k], su, si, leaky)
             ssl = ssl + ag.HingeFn.apply(p1[:ns], p1[ns:], w[:ns], w[ns:], s_final[:ns], s_final[ns:], 1.0)
         return pre_loss, ssl
+
+    def _touched_rows(self, batch) -> dict:
+        """--fusion_rows batch: the user rows (uids, suids[k]) and item rows (iids, siids[k], the head's sequence items)
+        the loss reads, marked and compacted on the device (ops.rows_mark / rows_compact) into capacities known on the
+        host, and the two counts copied to pinned host memory without waiting. Returns {"rows": [(rows, count)] * 2,
+        "caps", "host": the pinned counts, "done": the event after their copy}."""
+        U, I, dev = args.user, args.item, self.device
+        flags_u, flags_i, host = self._cached(
+            "_rows_bufs", (U, I, str(dev)), lambda: (torch.zeros(U, dtype=torch.uint8, device=dev),
+                                                     torch.zeros(I, dtype=torch.uint8, device=dev),
+                                                     torch.zeros(2, dtype=torch.int32, pin_memory=True)))
+        for ids in [batch["iids"]] + list(batch["siids"]):
+            ops.rows_mark(ids, flags_i)
+        if "seq_seg" in batch:
+            seg_begin, seg_len = batch["seq_seg"]
+            ops.rows_mark_segments(self._device_sampler().seq_items, seg_begin, seg_len, args.pos_length, flags_i)
+            n_seq = int(seg_len.numel()) * args.pos_length
+        else:
+            _, items, _ = self._masked_sum_csr(batch["sequence"], batch["mask"])
+            n_seq = len(items)
+            ops.rows_mark(torch.from_numpy(items).to(dev), flags_i)
+        for ids in [batch["uids"]] + list(batch["suids"]):
+            ops.rows_mark(ids, flags_u)
+        cap_u = min(U, int(batch["uids"].numel()) + sum(int(v.numel()) for v in batch["suids"]))
+        cap_i = min(I, int(batch["iids"].numel()) + sum(int(v.numel()) for v in batch["siids"]) + n_seq)
+        rows_u, count_u = ops.rows_compact(flags_u, max(cap_u, 1) if U else 0)
+        rows_i, count_i = ops.rows_compact(flags_i, max(cap_i, 1) if I else 0)
+        host[0:1].copy_(count_u, non_blocking=True)
+        host[1:2].copy_(count_i, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record()
+        return {"rows": [(rows_u, count_u), (rows_i, count_i)], "caps": (max(cap_u, 1), max(cap_i, 1)), "host": host,
+                "done": done}
 
     def _masked_sum_plans_t(self, sequence, mask):
         """Transposed per-batch CSRs (rows = items / positions, columns = batch slots) for the

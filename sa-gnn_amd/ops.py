@@ -916,3 +916,77 @@ def seq_sum_bwd(g_seq: torch.Tensor, g_pos: torch.Tensor, seq_items: torch.Tenso
         _idx_ptr("seg_begin", seg_begin, torch.int64, n), _idx_ptr("seg_len", seg_len, torch.int32), n, int(pos_length), d,
         d_fi.data_ptr(), d, int(n_items), d_pos.data_ptr(), d, _stream()))
     return d_fi, d_pos
+
+
+# ---- row subsets of the interval fusion (fusion_rows.hip) ---------------------------------------------------------
+def _flags(name: str, flags: torch.Tensor) -> int:
+    if flags.dtype != torch.uint8 or not flags.is_cuda or not flags.is_contiguous() or flags.dim() != 1:
+        raise TypeError(f"{name}: expected a contiguous uint8 device vector")
+    return flags.data_ptr() if flags.numel() else _idx_ptr(name, flags.new_zeros(0, dtype=torch.int32), torch.int32)
+
+
+def rows_mark(ids: torch.Tensor, flags: torch.Tensor):
+    """flags[ids[i]] = 1 for every id in [0, len(flags)) (sagnn_rows_mark_i32); ids int32 on the device."""
+    check(_lib.load().sagnn_rows_mark_i32(_idx_ptr("ids", ids, torch.int32), int(ids.numel()), int(flags.numel()),
+                                          _flags("flags", flags), _stream()))
+
+
+def rows_mark_segments(seq_items: torch.Tensor, seg_begin: torch.Tensor, seg_len: torch.Tensor, max_len: int,
+                       flags: torch.Tensor):
+    """Marks the items of the device sampler's sequence segments, j < min(seg_len[b], max_len) (sagnn_rows_mark_seg_i32)."""
+    n = int(seg_len.numel())
+    check(_lib.load().sagnn_rows_mark_seg_i32(
+        _idx_ptr("seq_items", seq_items, torch.int32), int(seq_items.numel()), _idx_ptr("seg_begin", seg_begin, torch.int64, n),
+        _idx_ptr("seg_len", seg_len, torch.int32), n, int(max_len), int(flags.numel()), _flags("flags", flags), _stream()))
+
+
+def rows_compact(flags: torch.Tensor, cap: int, rows: torch.Tensor | None = None, count: torch.Tensor | None = None):
+    """The flagged rows in ascending order (sagnn_rows_compact_i32), clearing the flags. Returns rows int32 [cap] (slots
+    past the count hold row 0) and count int32 [1] on the device: the count never goes through the host here."""
+    n, dev = int(flags.numel()), flags.device
+    if rows is None:
+        rows = _out(cap, torch.int32, dev)
+    if count is None:
+        count = torch.empty(1, dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    need = int(lib.sagnn_rows_compact_workspace_bytes(n))
+    ws = torch.empty(max(need // 4, 1), dtype=torch.int32, device=dev)
+    check(lib.sagnn_rows_compact_i32(_flags("flags", flags), n, _idx_ptr("rows", rows, torch.int32, int(cap)), int(cap),
+                                     _idx_ptr("count", count, torch.int32, 1), ws.data_ptr(), ws.numel() * 4, _stream()))
+    return rows, count
+
+
+def rows_gather(x: torch.Tensor, rows: torch.Tensor, count: torch.Tensor | None = None, out: torch.Tensor | None = None):
+    """out[j] = x[rows[j]] for x [N, t, d] (any node / interval strides) or [N, d] (sagnn_rows_gather_f32); out is dense
+    [cap, t, d] / [cap, d] with cap = len(rows). With count (int32 [1] on the device) slots j >= count are zeros."""
+    flat = x.dim() == 2
+    xv = x.unsqueeze(1) if flat else x
+    N, t, d, ld_n, ld_t = _ntd("x", xv)
+    cap = int(rows.numel())
+    if out is None:
+        out = torch.empty((cap, d) if flat else (cap, t, d), dtype=torch.float32, device=x.device)
+    if not out.is_contiguous() or out.numel() != cap * t * d:
+        raise ValueError("out: expected a contiguous tensor of cap * t * d elements")
+    if cap == 0:
+        return out
+    check(_lib.load().sagnn_rows_gather_f32(
+        x.data_ptr(), ld_n, ld_t, N, t, d, _idx_ptr("rows", rows, torch.int32), cap,
+        None if count is None else _idx_ptr("count", count, torch.int32, 1), out.data_ptr(), _stream()))
+    return out
+
+
+def rows_scatter(src: torch.Tensor, rows: torch.Tensor, count: torch.Tensor, out: torch.Tensor):
+    """out[rows[j]] = src[j] for j < count (sagnn_rows_scatter_f32): src dense [cap, t, d] / [cap, d], out [N, t, d]
+    (any node / interval strides) or [N, d]. No other row of out is written."""
+    flat = out.dim() == 2
+    ov = out.unsqueeze(1) if flat else out
+    N, t, d, ld_n, ld_t = _ntd("out", ov)
+    cap = int(rows.numel())
+    if not src.is_contiguous() or src.dtype != torch.float32 or src.numel() != cap * t * d:
+        raise ValueError("src: expected a contiguous float32 tensor of cap * t * d elements")
+    if cap == 0:
+        return out
+    check(_lib.load().sagnn_rows_scatter_f32(
+        src.data_ptr(), _idx_ptr("rows", rows, torch.int32), cap, _idx_ptr("count", count, torch.int32, 1), t, d,
+        out.data_ptr(), ld_n, ld_t, N, _stream()))
+    return out

@@ -3,7 +3,9 @@
 gowalla.sh hyper-parameters (U = 48,653, I = 52,619, 3 intervals x 600 k edges, d = 64, batch 512,
 trnNum 10000 -> 20 steps per epoch, keepRate 0.5) and prints where a training step spends its time
 (sampling / forward + loss / backward / optimiser), wall clock with a device sync after each part. Both samplers
-(--sampler host / device) run in the same process, alternated epoch by epoch."""
+(--sampler host / device) run in the same process, alternated epoch by epoch; --fusion_rows both alternates the two
+fusion modes as well (all rows / the rows the batch reads) and reports the touched rows per step and the f16 x 2
+kernels' fp32 re-evaluations per epoch of each mode."""
 import argparse
 import sys
 import time
@@ -12,7 +14,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, __file__.rsplit("/", 2)[0])
-from sa_gnn_amd import Params, synthetic      # noqa: E402
+from sa_gnn_amd import Params, ops, synthetic      # noqa: E402
 from sa_gnn_amd.DataHandler import DataHandler   # noqa: E402
 from sa_gnn_amd.Params import args            # noqa: E402
 from sa_gnn_amd.Utils import NNLayers as NNs  # noqa: E402
@@ -22,6 +24,8 @@ from sa_gnn_amd.model import Recommender      # noqa: E402
 def main():
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--epoch-only", action="store_true", help="one warm-up and one device-sampler epoch (for a profiler)")
+    ap.add_argument("--fusion_rows", choices=("all", "batch", "both"), default="all",
+                    help="fusion mode(s) to time; both alternates them in one process")
     opt = ap.parse_args()
     Params.parse_args("--data gowalla --lr 2e-3 --reg 1e-2 --ssl_reg 1e-6 --epoch 150 --batch 512 --sslNum 40 --graphNum 3 "
                       "--gnn_layer 2 --att_layer 1 --testSize 1000 --ssldim 48 --keepRate 0.5".split(), namespace=args)
@@ -39,43 +43,56 @@ def main():
     rec.prepareModel()
     if opt.epoch_only:
         args.sampler = "device"
+        args.fusion_rows = "batch" if opt.fusion_rows == "batch" else "all"
         for _ in range(2):
             rec.trainEpoch()
         torch.cuda.synchronize()
-        print("two device-sampler epochs done")
+        print(f"two device-sampler epochs done (--fusion_rows {args.fusion_rows})")
         return
-    samplers = ("host", "device")
-    for name in samplers:          # warm-up: kernels, workspaces, the device sampler's tables
-        args.sampler = name
+    modes = ("all", "batch") if opt.fusion_rows == "both" else (opt.fusion_rows,)
+    configs = [(sampler, mode) for mode in modes for sampler in ("host", "device")]
+    label = lambda c: c[0] if len(modes) == 1 else f"{c[0]}, {c[1]} rows"   # noqa: E731
+
+    def use(c):
+        args.sampler, args.fusion_rows = c
+
+    for c in configs:              # warm-up: kernels, workspaces, the device sampler's tables
+        use(c)
         for _ in range(2):
             rec.trainEpoch()
     torch.cuda.synchronize()
     steps = int(np.ceil(args.trnNum / args.batch))
     rounds = 3
-    epoch = {name: [] for name in samplers}
-    for _ in range(rounds):        # alternated, so both see the same machine state
-        for name in samplers:
-            args.sampler = name
+    epoch = {c: [] for c in configs}
+    redo = {c: [] for c in configs}
+    for _ in range(rounds):        # alternated, so every configuration sees the same machine state
+        for c in configs:
+            use(c)
             torch.cuda.synchronize()
+            ops.range_redo_count(reset=True)
             t0 = time.perf_counter()
             rec.trainEpoch()
             torch.cuda.synchronize()
-            epoch[name].append(time.perf_counter() - t0)
-    for name in samplers:
-        ep = float(np.median(epoch[name]))
-        print(f"[{name}] train epoch {ep * 1e3:.1f} ms = {steps} steps of {ep / steps * 1e3:.2f} ms "
-              f"(median of {rounds}; all: {[round(1e3 * v, 1) for v in epoch[name]]})")
+            epoch[c].append(time.perf_counter() - t0)
+            redo[c].append(ops.range_redo_count())
+    for c in configs:
+        ep = float(np.median(epoch[c]))
+        print(f"[{label(c)}] train epoch {ep * 1e3:.1f} ms = {steps} steps of {ep / steps * 1e3:.2f} ms "
+              f"(median of {rounds}; all: {[round(1e3 * v, 1) for v in epoch[c]]}); "
+              f"range redo count per epoch {redo[c]}")
     # one step, by part
-    parts = {name: {"sample": 0.0, "forward+loss": 0.0, "backward": 0.0, "optimiser": 0.0} for name in samplers}
+    parts = {c: {"sample": 0.0, "forward+loss": 0.0, "backward": 0.0, "optimiser": 0.0} for c in configs}
+    touched = {c: [] for c in configs}
     for r in range(rounds):
-        for name in samplers:
+        for c in configs:
+            use(c)
             sf = np.random.permutation(args.user)[:args.trnNum]
             seed = int(np.random.randint(0, 2 ** 63, dtype=np.int64))
-            part = parts[name]
+            part = parts[c]
             for i in range(steps):
                 bat = sf[i * args.batch:(i + 1) * args.batch]
                 torch.cuda.synchronize(); t = time.perf_counter()
-                if name == "device":
+                if c[0] == "device":
                     batch = rec.sample_batch_device(bat, seed, i)
                 else:
                     batch = rec._host_train_batch(bat)
@@ -86,13 +103,20 @@ def main():
                 pre, ssl = rec.train_loss(batch)
                 loss = pre + args.ssl_reg * ssl
                 torch.cuda.synchronize(); part["forward+loss"] += time.perf_counter() - t; t = time.perf_counter()
+                if c[1] == "batch":
+                    touched[c].append(rec.fusion_rows_counts)
                 loss.backward()
                 torch.cuda.synchronize(); part["backward"] += time.perf_counter() - t; t = time.perf_counter()
                 rec.optimizer.step({k: p.grad for k, p in params.items()})
                 torch.cuda.synchronize(); part["optimiser"] += time.perf_counter() - t
-    for name in samplers:
-        print(f"[{name}] per step (ms, synced between parts, mean of {rounds} epochs):",
-              {k: round(v / (steps * rounds) * 1e3, 3) for k, v in parts[name].items()})
+    for c in configs:
+        print(f"[{label(c)}] per step (ms, synced between parts, mean of {rounds} epochs):",
+              {k: round(v / (steps * rounds) * 1e3, 3) for k, v in parts[c].items()})
+        if touched[c]:
+            tu, ti = np.mean(np.asarray(touched[c], dtype=np.float64), axis=0)
+            print(f"[{label(c)}] touched rows per step (mean of {len(touched[c])}): users {tu:.1f} of {args.user} "
+                  f"({100 * tu / args.user:.2f} %), items {ti:.1f} of {args.item} ({100 * ti / args.item:.2f} %)")
+    args.fusion_rows = "all"
     args.sampler = "host"
     t0 = time.perf_counter()
     res = rec.testEpoch()
