@@ -224,7 +224,7 @@ int sagnn_gnn_interval_ex_f32(const sagnn_spmm_plan* plan_user, const sagnn_spmm
  * For matrices without duplicated stored entries these are the forward plans themselves; with
  * duplicates (forward counts one twice, DataHandler.transpose merges it: DataHandler.py:9-11) the
  * caller passes plans of the exact transposes — the library cannot tell the two cases apart from
- * the handles, so the host side checks it (sa-gnn_amd/graph.py interval_pair, ops.gnn_interval_bwd). */
+ * the handles, so the host side checks it (sa-gnn_amd/graph.py interval_pair, ops._adjoint_pair). */
 int sagnn_gnn_interval_bwd_f32(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item,
                                const float* G_u, int64_t ld_gu, const float* G_i, int64_t ld_gi, int d,
                                int n_layers, float leaky, const uint8_t* mask_u, const uint8_t* mask_i,

@@ -16,45 +16,6 @@ SPLIT_DW = True                # one-launch BPTT (d = 32 / 64): weight gradient 
 SPLIT_DW_MIN_T = 4              # ... from this many steps on (measured: T = 16 -13 %, T = 6 -8 %, T = 2 / 3 nothing: the gate gradients' HBM round trip)
 
 
-class GnnIntervalFn(torch.autograd.Function):
-    """(uEmbed[k], iEmbed[k]) -> (user_k, item_k): L propagation layers with residuals and add_n.
-    Saves one activation mask per layer and direction (d/4 bytes per row) instead of the layer
-    outputs: the backward pass needs only the slopes."""
-
-    @staticmethod
-    def forward(ctx, u0, i0, plan_user, plan_item, n_layers, leaky):
-        U, I, d = plan_user.n_rows, plan_item.n_rows, int(u0.shape[1])
-        dev = u0.device
-        user_out = torch.empty((U, d), dtype=torch.float32, device=dev)
-        item_out = torch.empty((I, d), dtype=torch.float32, device=dev)
-        mask_u = torch.empty((n_layers, U, d // 4), dtype=torch.uint8, device=dev)
-        mask_i = torch.empty((n_layers, I, d // 4), dtype=torch.uint8, device=dev)
-        ops.gnn_interval(plan_user, plan_item, u0.detach().contiguous(), i0.detach().contiguous(), n_layers,
-                         leaky, user_out, item_out, mask_u=mask_u, mask_i=mask_i)
-        ctx.save_for_backward(mask_u, mask_i)
-        ctx.plans = (plan_user, plan_item)
-        ctx.cfg = (n_layers, leaky)
-        return user_out, item_out
-
-    @staticmethod
-    def backward(ctx, g_user, g_item):
-        mask_u, mask_i = ctx.saved_tensors
-        plan_user, plan_item = ctx.plans
-        n_layers, leaky = ctx.cfg
-        U, I, d = plan_user.n_rows, plan_item.n_rows, mask_u.shape[2] * 4
-        if g_user is None:
-            g_user = torch.zeros((U, d), dtype=torch.float32, device=mask_u.device)
-        if g_item is None:
-            g_item = torch.zeros((I, d), dtype=torch.float32, device=mask_u.device)
-        du, di = ops.gnn_interval_bwd(plan_user, plan_item, g_user.contiguous(), g_item.contiguous(), n_layers,
-                                      leaky, mask_u, mask_i)
-        return du, di, None, None, None, None
-
-
-def gnn_interval(u0, i0, plan_user, plan_item, n_layers: int, leaky: float):
-    return GnnIntervalFn.apply(u0, i0, plan_user, plan_item, n_layers, leaky)
-
-
 class GnnStackFn(torch.autograd.Function):
     """(uEmbed [T, U, d], iEmbed [T, I, d]) -> (user slab [T, U, d], item slab [T, I, d]): the whole loop of
     model.py:118-129 as ONE autograd node. Interval outputs are written straight into the slabs the fusion reads
@@ -67,14 +28,13 @@ class GnnStackFn(torch.autograd.Function):
         T, U, d = u_embed.shape
         I = i_embed.shape[1]
         dev = u_embed.device
-        ue, ie = u_embed.detach(), i_embed.detach()
+        ue, ie = (x if x.stride(2) == 1 else x.contiguous() for x in (u_embed.detach(), i_embed.detach()))
         out_u = torch.empty((T, U, d), dtype=torch.float32, device=dev)
         out_i = torch.empty((T, I, d), dtype=torch.float32, device=dev)
         mask_u = torch.empty((T, n_layers, U, d // 4), dtype=torch.uint8, device=dev)
         mask_i = torch.empty((T, n_layers, I, d // 4), dtype=torch.uint8, device=dev)
         if isinstance(plans_user, ops.SpmmBatch):
-            ops.gnn_stack(plans_user, ue if ue.stride(2) == 1 else ue.contiguous(), ie if ie.stride(2) == 1 else ie.contiguous(),
-                          n_layers, leaky, out_u, out_i, mask_u=mask_u, mask_i=mask_i)
+            ops.gnn_stack(plans_user, ue, ie, n_layers, leaky, out_u, out_i, mask_u=mask_u, mask_i=mask_i)
         else:
             scr_u = torch.empty((2, U, d), dtype=torch.float32, device=dev) if n_layers > 1 else None
             scr_i = torch.empty((2, I, d), dtype=torch.float32, device=dev) if n_layers > 1 else None
@@ -117,6 +77,12 @@ class GnnStackFn(torch.autograd.Function):
 def gnn_stack(u_embed, i_embed, plans_user, plans_item, n_layers: int, leaky: float):
     """plans_user: a list of T ops.SpmmPlan (with plans_item the matching list) or an ops.SpmmBatch (plans_item None)."""
     return GnnStackFn.apply(u_embed, i_embed, plans_user, plans_item, n_layers, leaky)
+
+
+def gnn_interval(u0, i0, plan_user, plan_item, n_layers: int, leaky: float):
+    """(uEmbed[k], iEmbed[k]) -> (user_k, item_k): the stack of one interval, on its own plans."""
+    user_out, item_out = gnn_stack(u0.unsqueeze(0), i0.unsqueeze(0), [plan_user], [plan_item], n_layers, leaky)
+    return user_out[0], item_out[0]
 
 
 def _split_qkv_grads(dWqkv, dbqkv, d):

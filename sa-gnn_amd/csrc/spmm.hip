@@ -137,29 +137,11 @@ __device__ __forceinline__ void finish_row(const Epilogue& ep, int64_t row, int 
   }
 }
 
-// gm[r, :] = g[r, :] * (mask bit ? 1 : slope): seeds the backward chain of the GNN stack.
-__global__ void mask_scale_kernel(const float* __restrict__ g, int64_t ldg, const uint8_t* __restrict__ mask,
-                                  int mask_stride, float slope, float* __restrict__ gm, int64_t ldgm,
-                                  int64_t n_rows, int d) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int lpr = d >> 2;
-  if (i >= n_rows * lpr) return;
-  const int64_t row = i / lpr;
-  const int l = (int)(i - row * lpr);
-  const float4 v = ld4(g + row * ldg + 4 * l);
-  const unsigned bits = mask[row * mask_stride + l];
-  float4 z;
-  z.x = (bits & 1u) ? v.x : slope * v.x;
-  z.y = (bits & 2u) ? v.y : slope * v.y;
-  z.z = (bits & 4u) ? v.z : slope * v.z;
-  z.w = (bits & 8u) ? v.w : slope * v.w;
-  st4(gm + row * ldgm + 4 * l, z);
-}
-
-// the same for interval blockIdx.y of a slab
-__global__ void mask_scale_batch_kernel(const float* __restrict__ g, int64_t ldg, int64_t s_g, const uint8_t* __restrict__ mask,
-                                        int64_t s_mask, int mask_stride, float slope, float* __restrict__ gm, int64_t ldgm,
-                                        int64_t s_gm, int64_t n_rows, int d) {
+// gm[r, :] = g[r, :] * (mask bit ? 1 : slope) for interval blockIdx.y of a slab (one matrix: grid.y = 1, the slab
+// strides unused): seeds the backward chain of the GNN stack.
+__global__ void mask_scale_kernel(const float* __restrict__ g, int64_t ldg, int64_t s_g, const uint8_t* __restrict__ mask,
+                                  int64_t s_mask, int mask_stride, float slope, float* __restrict__ gm, int64_t ldgm,
+                                  int64_t s_gm, int64_t n_rows, int d) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int lpr = d >> 2;
   if (i >= n_rows * lpr) return;
@@ -665,26 +647,50 @@ int check_mat(const char* name, const void* ptr, int64_t ld, int d, bool require
   return SAGNN_OK;
 }
 
-}  // namespace
-
-extern "C" int sagnn_spmm_ex_f32(const sagnn_spmm_plan* plan, const float* X, int64_t ldx, int d,
-                                 const sagnn_spmm_epilogue* e, void* workspace, size_t workspace_bytes,
-                                 void* stream) {
-  if (!plan || !e) return sagnn::fail(SAGNN_ERR_NULL, "plan/epilogue is NULL");
-  if (!plan->info.on_device) return sagnn::fail(SAGNN_ERR_ARG, "plan was built host-only (no device CSR)");
+int check_d(int d) {
   if (d < 4 || d > 256 || (d & 3)) return sagnn::fail(SAGNN_ERR_DIM, "d = %d: need a multiple of 4 in [4, 256]", d);
-  if (!e->out && !e->acc_out && !e->out2) return sagnn::fail(SAGNN_ERR_NULL, "no output given");
+  return SAGNN_OK;
+}
+
+struct Slab {           // a [T, N, d]-like operand: interval k's matrix starts at p + k * slab, rows ld apart
+  float* p;
+  int64_t ld, slab;
+};
+
+int check_slab(const char* name, const Slab& x, int d) {
+  if (int rc = check_mat(name, x.p, x.ld, d, true)) return rc;
+  if (x.slab & 3) return sagnn::fail(SAGNN_ERR_ALIGN, "%s: slab stride must be a multiple of 4", name);
+  return SAGNN_OK;
+}
+
+// out = g * (mask bit ? 1 : slope) on the T matrices of a slab; mask slabs s_mask bytes apart, d/4 bytes per row
+int launch_mask_scale(const Slab& g, const uint8_t* mask, int64_t s_mask, float slope, const Slab& out, int64_t n_rows,
+                      int d, int64_t T, hipStream_t stream) {
+  const int64_t n = n_rows * (d / 4);
+  if (n == 0) return SAGNN_OK;
+  hipLaunchKernelGGL(mask_scale_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)T), dim3(256), 0, stream, g.p, g.ld,
+                     g.slab, mask, s_mask, d / 4, slope, out.p, out.ld, out.slab, n_rows, d);
+  SAGNN_HIP_TRY(hipGetLastError());
+  return SAGNN_OK;
+}
+
+// sagnn_spmm_ex_f32 on the kernels' own epilogue: every per-call check, then the launch(es) of one plan
+int spmm_ex(const sagnn_spmm_plan* plan, const float* X, int64_t ldx, int d, const Epilogue& e, void* workspace,
+            size_t workspace_bytes, void* stream) {
+  if (!plan->info.on_device) return sagnn::fail(SAGNN_ERR_ARG, "plan was built host-only (no device CSR)");
+  if (int rc = check_d(d)) return rc;
+  if (!e.out && !e.acc_out && !e.out2) return sagnn::fail(SAGNN_ERR_NULL, "no output given");
   if (int rc = check_mat("X", X, ldx, d, plan->info.nnz > 0)) return rc;
-  if (int rc = check_mat("residual", e->residual, e->ldr, d, false)) return rc;
-  if (int rc = check_mat("out", e->out, e->ldo, d, false)) return rc;
-  if (int rc = check_mat("acc_in", e->acc_in, e->ld_acc_in, d, false)) return rc;
-  if (int rc = check_mat("acc_out", e->acc_out, e->ld_acc_out, d, false)) return rc;
-  if (int rc = check_mat("acc_in2", e->acc_in2, e->ld_acc_in2, d, false)) return rc;
-  if (e->acc_in2 && !e->acc_out) return sagnn::fail(SAGNN_ERR_ARG, "acc_in2 given without acc_out");
-  if (int rc = check_mat("out2", e->out2, e->ldo2, d, false)) return rc;
-  if ((e->out && e->out == X) || (e->acc_out && e->acc_out == X) || (e->out2 && e->out2 == X))
+  if (int rc = check_mat("residual", e.residual, e.ldr, d, false)) return rc;
+  if (int rc = check_mat("out", e.out, e.ldo, d, false)) return rc;
+  if (int rc = check_mat("acc_in", e.acc_in, e.ld_acc_in, d, false)) return rc;
+  if (int rc = check_mat("acc_out", e.acc_out, e.ld_acc_out, d, false)) return rc;
+  if (int rc = check_mat("acc_in2", e.acc_in2, e.ld_acc_in2, d, false)) return rc;
+  if (e.acc_in2 && !e.acc_out) return sagnn::fail(SAGNN_ERR_ARG, "acc_in2 given without acc_out");
+  if (int rc = check_mat("out2", e.out2, e.ldo2, d, false)) return rc;
+  if ((e.out && e.out == X) || (e.acc_out && e.acc_out == X) || (e.out2 && e.out2 == X))
     return sagnn::fail(SAGNN_ERR_ARG, "outputs must not alias X");
-  if (e->mask_in && !e->out2) return sagnn::fail(SAGNN_ERR_ARG, "mask_in given without out2");
+  if (e.mask_in && !e.out2) return sagnn::fail(SAGNN_ERR_ARG, "mask_in given without out2");
   const size_t need = sagnn_spmm_workspace_bytes(plan, d);
   if (need > 0) {
     if (!workspace || workspace_bytes < need)
@@ -694,17 +700,26 @@ extern "C" int sagnn_spmm_ex_f32(const sagnn_spmm_plan* plan, const float* X, in
   }
   if (plan->info.n_rows == 0) return SAGNN_OK;
 
-  Epilogue ep{e->residual, e->ldr,       e->acc_in,  e->ld_acc_in, e->out,   e->ldo,    e->acc_out, e->ld_acc_out,
-              e->leaky,    e->mask_out,  e->mask_in, e->out2,      e->ldo2,  e->slope2, d / 4,
-              e->acc_in2,  e->ld_acc_in2};
   hipStream_t s = static_cast<hipStream_t>(stream);
   float* partial = static_cast<float*>(workspace);
   switch (sagnn::lanes_per_row(d)) {
-    case 8: return launch_spmm<8>(plan, X, ldx, d, ep, partial, s);
-    case 16: return launch_spmm<16>(plan, X, ldx, d, ep, partial, s);
-    case 32: return launch_spmm<32>(plan, X, ldx, d, ep, partial, s);
-    default: return launch_spmm<64>(plan, X, ldx, d, ep, partial, s);
+    case 8: return launch_spmm<8>(plan, X, ldx, d, e, partial, s);
+    case 16: return launch_spmm<16>(plan, X, ldx, d, e, partial, s);
+    case 32: return launch_spmm<32>(plan, X, ldx, d, e, partial, s);
+    default: return launch_spmm<64>(plan, X, ldx, d, e, partial, s);
   }
+}
+
+}  // namespace
+
+extern "C" int sagnn_spmm_ex_f32(const sagnn_spmm_plan* plan, const float* X, int64_t ldx, int d,
+                                 const sagnn_spmm_epilogue* e, void* workspace, size_t workspace_bytes,
+                                 void* stream) {
+  if (!plan || !e) return sagnn::fail(SAGNN_ERR_NULL, "plan/epilogue is NULL");
+  const Epilogue ep{e->residual, e->ldr,       e->acc_in,  e->ld_acc_in, e->out,   e->ldo,    e->acc_out, e->ld_acc_out,
+                    e->leaky,    e->mask_out,  e->mask_in, e->out2,      e->ldo2,  e->slope2, d / 4,
+                    e->acc_in2,  e->ld_acc_in2};
+  return spmm_ex(plan, X, ldx, d, ep, workspace, workspace_bytes, stream);
 }
 
 extern "C" int sagnn_spmm_f32(const sagnn_spmm_plan* plan, const float* X, int64_t ldx, int d,
@@ -725,21 +740,17 @@ extern "C" int sagnn_spmm_f32(const sagnn_spmm_plan* plan, const float* X, int64
   return sagnn_spmm_ex_f32(plan, X, ldx, d, &e, workspace, workspace_bytes, stream);
 }
 
-// out[r, :] = g[r, :] * (mask bit ? 1 : slope): the seed of the backward chain (what sagnn_gnn_interval_bwd_f32 does first),
+// out[r, :] = g[r, :] * (mask bit ? 1 : slope): the seed of the backward chain (what run_backward does first),
 // exposed for hosts that run the chain themselves on row slices (parallel.FractionalRunner.run_backward).
 extern "C" int sagnn_mask_scale_f32(const float* g, int64_t ldg, const uint8_t* mask, float slope, float* out, int64_t ldo,
                                     int64_t n_rows, int d, void* stream) {
   if (!g || !mask || !out) return sagnn::fail(SAGNN_ERR_NULL, "null pointer");
-  if (d < 4 || d > 256 || (d & 3)) return sagnn::fail(SAGNN_ERR_DIM, "d = %d: need a multiple of 4 in [4, 256]", d);
+  if (int rc = check_d(d)) return rc;
   if (n_rows < 0) return sagnn::fail(SAGNN_ERR_ARG, "n_rows = %lld", (long long)n_rows);
   if (int rc = check_mat("g", g, ldg, d, true)) return rc;
   if (int rc = check_mat("out", out, ldo, d, true)) return rc;
-  const int64_t n = n_rows * (d / 4);
-  if (n == 0) return SAGNN_OK;
-  hipLaunchKernelGGL(mask_scale_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), g, ldg,
-                     mask, d / 4, slope, out, ldo, n_rows, d);
-  SAGNN_HIP_TRY(hipGetLastError());
-  return SAGNN_OK;
+  return launch_mask_scale(Slab{const_cast<float*>(g), ldg, 0}, mask, 0, slope, Slab{out, ldo, 0}, n_rows, d, 1,
+                           static_cast<hipStream_t>(stream));
 }
 
 namespace {
@@ -752,165 +763,6 @@ int check_interval_plans(const sagnn_spmm_plan* pu, const sagnn_spmm_plan* pi) {
   return SAGNN_OK;
 }
 }  // namespace
-
-extern "C" int sagnn_gnn_interval_ex_f32(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item,
-                                         const float* u0, int64_t ld_u0, const float* i0, int64_t ld_i0,
-                                         int d, int n_layers, float leaky, float* scratch_u,
-                                         float* scratch_i, float* user_out, int64_t ld_uo, float* item_out,
-                                         int64_t ld_io, uint8_t* mask_u, uint8_t* mask_i, void* workspace,
-                                         size_t workspace_bytes, void* stream) {
-  if (int rc = check_interval_plans(plan_user, plan_item)) return rc;
-  if (!u0 || !i0 || !user_out || !item_out) return sagnn::fail(SAGNN_ERR_NULL, "null embedding pointer");
-  if (n_layers < 1) return sagnn::fail(SAGNN_ERR_ARG, "n_layers = %d: need >= 1", n_layers);
-  if ((mask_u == nullptr) != (mask_i == nullptr)) return sagnn::fail(SAGNN_ERR_NULL, "give both masks or neither");
-  const int64_t U = plan_user->info.n_rows, I = plan_item->info.n_rows;
-  if (n_layers > 1 && (!scratch_u || !scratch_i))
-    return sagnn::fail(SAGNN_ERR_NULL, "scratch buffers required for n_layers > 1");
-  // e^l lives in cur; layer l writes e^{l+1} into the other half of the ping-pong scratch
-  // (skipped for the last layer, whose only consumer is the running sum).
-  const float* cu = u0;
-  int64_t lcu = ld_u0;
-  const float* ci = i0;
-  int64_t lci = ld_i0;
-  const int64_t mrow = d / 4;
-  for (int l = 0; l < n_layers; ++l) {
-    const bool last = (l + 1 == n_layers);
-    sagnn_spmm_epilogue eu{}, ei{};
-    eu.leaky = ei.leaky = leaky;
-    eu.residual = cu;
-    eu.ldr = lcu;
-    ei.residual = ci;
-    ei.ldr = lci;
-    eu.out = last ? nullptr : scratch_u + (int64_t)(l & 1) * U * d;
-    ei.out = last ? nullptr : scratch_i + (int64_t)(l & 1) * I * d;
-    eu.ldo = ei.ldo = d;
-    // Running sum sum_l e^l without a write that is only read back: layer 0 of a deeper stack
-    // writes e^1 alone; layer 1 starts the sum from e^1 (its residual, already in registers);
-    // the LAST layer adds e^0 on the way out (acc_in2). One layer: acc_out = e^0 + e^1 directly.
-    const bool sum_here = last || l >= 1;
-    if (sum_here) {
-      eu.acc_in = (l <= 1) ? cu : user_out;
-      eu.ld_acc_in = (l <= 1) ? lcu : ld_uo;
-      ei.acc_in = (l <= 1) ? ci : item_out;
-      ei.ld_acc_in = (l <= 1) ? lci : ld_io;
-      eu.acc_out = user_out;
-      eu.ld_acc_out = ld_uo;
-      ei.acc_out = item_out;
-      ei.ld_acc_out = ld_io;
-      if (last && l >= 1) {
-        eu.acc_in2 = u0;
-        eu.ld_acc_in2 = ld_u0;
-        ei.acc_in2 = i0;
-        ei.ld_acc_in2 = ld_i0;
-      }
-    }
-    if (mask_u) {
-      eu.mask_out = mask_u + (int64_t)l * U * mrow;
-      ei.mask_out = mask_i + (int64_t)l * I * mrow;
-    }
-    if (int rc = sagnn_spmm_ex_f32(plan_user, ci, lci, d, &eu, workspace, workspace_bytes, stream)) return rc;
-    if (int rc = sagnn_spmm_ex_f32(plan_item, cu, lcu, d, &ei, workspace, workspace_bytes, stream)) return rc;
-    cu = eu.out;
-    lcu = d;
-    ci = ei.out;
-    lci = d;
-  }
-  return SAGNN_OK;
-}
-
-extern "C" int sagnn_gnn_interval_f32(const sagnn_spmm_plan* plan_user,
-                                      const sagnn_spmm_plan* plan_item, const float* u0,
-                                      int64_t ld_u0, const float* i0, int64_t ld_i0, int d,
-                                      int n_layers, float leaky, float* scratch_u, float* scratch_i,
-                                      float* user_out, int64_t ld_uo, float* item_out, int64_t ld_io,
-                                      void* workspace, size_t workspace_bytes, void* stream) {
-  return sagnn_gnn_interval_ex_f32(plan_user, plan_item, u0, ld_u0, i0, ld_i0, d, n_layers, leaky, scratch_u,
-                                   scratch_i, user_out, ld_uo, item_out, ld_io, nullptr, nullptr, workspace,
-                                   workspace_bytes, stream);
-}
-
-// Backward of sagnn_gnn_interval_ex_f32. With g^l = dL/de^l (l = 0..L), G = dL/d(sum_l e^l):
-//   g_u^L = G_u,  g_i^L = G_i
-//   g_u^l = G_u + g_u^{l+1} + A   (g_i^{l+1} * m_i^{l+1})     (plan_user: rows = users)
-//   g_i^l = G_i + g_i^{l+1} + A^T (g_u^{l+1} * m_u^{l+1})     (plan_item: rows = items)
-// m^{l+1} = slope mask of the forward layer that produced e^{l+1} (1 where the activation passed
-// the sum through, leaky elsewhere). Each step is the forward kernel with slope 1, residual =
-// g^{l+1}, acc_in = G, and the masked copy for the next step written by the same epilogue.
-extern "C" int sagnn_gnn_interval_bwd_f32(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item,
-                                          const float* G_u, int64_t ld_gu, const float* G_i, int64_t ld_gi,
-                                          int d, int n_layers, float leaky, const uint8_t* mask_u,
-                                          const uint8_t* mask_i, float* scratch_u, float* scratch_i,
-                                          float* grad_u0, int64_t ld_du, float* grad_i0, int64_t ld_di,
-                                          void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = check_interval_plans(plan_user, plan_item)) return rc;
-  if (!G_u || !G_i || !grad_u0 || !grad_i0 || !mask_u || !mask_i || !scratch_u || !scratch_i)
-    return sagnn::fail(SAGNN_ERR_NULL, "null pointer");
-  if (n_layers < 1) return sagnn::fail(SAGNN_ERR_ARG, "n_layers = %d: need >= 1", n_layers);
-  if (d < 4 || d > 256 || (d & 3)) return sagnn::fail(SAGNN_ERR_DIM, "d = %d: need a multiple of 4 in [4, 256]", d);
-  if (int rc = check_mat("G_u", G_u, ld_gu, d, true)) return rc;
-  if (int rc = check_mat("G_i", G_i, ld_gi, d, true)) return rc;
-  const int64_t U = plan_user->info.n_rows, I = plan_item->info.n_rows;
-  const int64_t mrow = d / 4;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  // scratch_x: [4][N][d]: slots 0/1 ping-pong the full gradients g^l, slots 2/3 the masked copies
-  float* gfull_u[2] = {scratch_u, scratch_u + U * d};
-  float* gmask_u[2] = {scratch_u + 2 * U * d, scratch_u + 3 * U * d};
-  float* gfull_i[2] = {scratch_i, scratch_i + I * d};
-  float* gmask_i[2] = {scratch_i + 2 * I * d, scratch_i + 3 * I * d};
-  // seed: g^L * m^L
-  {
-    const int threads = 256;
-    const int64_t nu = U * mrow, ni = I * mrow;
-    if (nu > 0) {
-      hipLaunchKernelGGL(mask_scale_kernel, dim3((unsigned)((nu + threads - 1) / threads)), dim3(threads), 0, s, G_u,
-                         ld_gu, mask_u + (int64_t)(n_layers - 1) * U * mrow, (int)mrow, leaky, gmask_u[0], (int64_t)d, U, d);
-      SAGNN_HIP_TRY(hipGetLastError());
-    }
-    if (ni > 0) {
-      hipLaunchKernelGGL(mask_scale_kernel, dim3((unsigned)((ni + threads - 1) / threads)), dim3(threads), 0, s, G_i,
-                         ld_gi, mask_i + (int64_t)(n_layers - 1) * I * mrow, (int)mrow, leaky, gmask_i[0], (int64_t)d, I, d);
-      SAGNN_HIP_TRY(hipGetLastError());
-    }
-  }
-  const float* gu_next = G_u;  // g^{l+1}
-  int64_t ld_gun = ld_gu;
-  const float* gi_next = G_i;
-  int64_t ld_gin = ld_gi;
-  int cur = 0;  // index of the masked buffers holding g^{l+1} * m^{l+1}
-  for (int l = n_layers - 1; l >= 0; --l) {
-    const bool final_step = (l == 0);
-    sagnn_spmm_epilogue eu{}, ei{};
-    eu.leaky = ei.leaky = 1.f;
-    eu.residual = gu_next;
-    eu.ldr = ld_gun;
-    ei.residual = gi_next;
-    ei.ldr = ld_gin;
-    eu.acc_in = G_u;
-    eu.ld_acc_in = ld_gu;
-    ei.acc_in = G_i;
-    ei.ld_acc_in = ld_gi;
-    eu.acc_out = final_step ? grad_u0 : gfull_u[l & 1];
-    eu.ld_acc_out = final_step ? ld_du : d;
-    ei.acc_out = final_step ? grad_i0 : gfull_i[l & 1];
-    ei.ld_acc_out = final_step ? ld_di : d;
-    if (!final_step) {
-      eu.mask_in = mask_u + (int64_t)(l - 1) * U * mrow;
-      ei.mask_in = mask_i + (int64_t)(l - 1) * I * mrow;
-      eu.out2 = gmask_u[cur ^ 1];
-      ei.out2 = gmask_i[cur ^ 1];
-      eu.ldo2 = ei.ldo2 = d;
-      eu.slope2 = ei.slope2 = leaky;
-    }
-    if (int rc = sagnn_spmm_ex_f32(plan_user, gmask_i[cur], d, d, &eu, workspace, workspace_bytes, stream)) return rc;
-    if (int rc = sagnn_spmm_ex_f32(plan_item, gmask_u[cur], d, d, &ei, workspace, workspace_bytes, stream)) return rc;
-    gu_next = eu.acc_out;
-    ld_gun = eu.ld_acc_out;
-    gi_next = ei.acc_out;
-    ld_gin = ei.ld_acc_out;
-    cur ^= 1;
-  }
-  return SAGNN_OK;
-}
 
 // ------------------------------------------------------------------------------------------
 // Batch over the T intervals: one launch per LAYER of the stack (+ one fix-up launch)
@@ -1059,16 +911,6 @@ int launch_batch_d(const sagnn_spmm_batch* b, int d, const DirArgs& au, const Di
   }
 }
 
-struct Slab {           // a [T, N, d]-like operand: interval k's matrix starts at p + k * slab, rows ld apart
-  float* p;
-  int64_t ld, slab;
-};
-
-int check_slab(const char* name, const float* p, int64_t ld, int64_t slab, int d) {
-  if (int rc = check_mat(name, p, ld, d, true)) return rc;
-  if (slab & 3) return sagnn::fail(SAGNN_ERR_ALIGN, "%s: slab stride must be a multiple of 4", name);
-  return SAGNN_OK;
-}
 
 int check_batch_ws(const sagnn_spmm_batch* b, int d, const void* workspace, size_t workspace_bytes) {
   const size_t need = sagnn_spmm_batch_workspace_bytes(b, d);
@@ -1079,7 +921,195 @@ int check_batch_ws(const sagnn_spmm_batch* b, int d, const void* workspace, size
   return SAGNN_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// The layer schedule of the GNN stack (model.py:118-129), forward and backward, stated once for one interval
+// (sagnn_gnn_interval_*: T = 1, slab strides unused) and for a batch of T (sagnn_gnn_stack_*)
+// ------------------------------------------------------------------------------------------
+struct Side {           // the operands of one node type
+  Slab in, out;         // forward: e^0 and sum_l e^l; backward: G = dL/d(sum_l e^l) and dL/d e^0
+  float* scratch;       // [2][T][rows][d] forward (unused for one layer), [4][T][rows][d] backward
+  uint8_t* mask;        // [T][n_layers][rows][d/4] activation masks: written forward (optional), read backward
+  int64_t rows;
+};
+struct Stack {
+  Side u, i;
+  int64_t T;
+  int d, n_layers;
+  float leaky;
+};
+
+Slab scratch_slot(const Stack& st, const Side& s, int slot) {
+  return Slab{s.scratch + slot * st.T * s.rows * st.d, (int64_t)st.d, s.rows * st.d};
+}
+
+// Alignment of a stack's operands, ahead of any launch (the scratch only where the schedule uses it)
+int check_stack(const Stack& st, bool scratch_used, const char* in_u, const char* in_i, const char* out_u, const char* out_i) {
+  if (int rc = check_slab(in_u, st.u.in, st.d)) return rc;
+  if (int rc = check_slab(in_i, st.i.in, st.d)) return rc;
+  if (int rc = check_slab(out_u, st.u.out, st.d)) return rc;
+  if (int rc = check_slab(out_i, st.i.out, st.d)) return rc;
+  if (scratch_used && (!sagnn::aligned16(st.u.scratch) || !sagnn::aligned16(st.i.scratch)))
+    return sagnn::fail(SAGNN_ERR_ALIGN, "scratch buffers must be 16-byte aligned");
+  return SAGNN_OK;
+}
+
+// Forward layer l on the rows of `self`, gathering the rows of `other`:  e^{l+1} = leaky(A e_other^l) + e^l.
+DirArgs forward_layer(const Stack& st, const Side& self, const Side& other, int l) {
+  const bool last = (l + 1 == st.n_layers);
+  const int64_t mrow = st.d / 4;
+  // e^0 is the caller's table; layer l writes e^{l+1} into half l & 1 of the ping-pong scratch
+  // (skipped for the last layer, whose only consumer is the running sum).
+  const Slab cur = l == 0 ? self.in : scratch_slot(st, self, (l - 1) & 1);
+  const Slab x = l == 0 ? other.in : scratch_slot(st, other, (l - 1) & 1);
+  DirArgs a{};
+  a.ep.leaky = st.leaky;
+  a.ep.mask_stride = (int)mrow;
+  a.X = x.p, a.ldx = x.ld, a.s_X = x.slab;
+  a.ep.residual = cur.p, a.ep.ldr = cur.ld, a.s_res = cur.slab;
+  if (!last) {
+    const Slab next = scratch_slot(st, self, l & 1);
+    a.ep.out = next.p, a.ep.ldo = next.ld, a.s_out = next.slab;
+  }
+  // Running sum sum_l e^l without a write that is only read back: layer 0 of a deeper stack
+  // writes e^1 alone; layer 1 starts the sum from e^1 (its residual, already in registers);
+  // the LAST layer adds e^0 on the way out (acc_in2). One layer: acc_out = e^0 + e^1 directly.
+  if (last || l >= 1) {
+    const Slab acc = l <= 1 ? cur : self.out;
+    a.ep.acc_in = acc.p, a.ep.ld_acc_in = acc.ld, a.s_acc_in = acc.slab;
+    a.ep.acc_out = self.out.p, a.ep.ld_acc_out = self.out.ld, a.s_acc_out = self.out.slab;
+    if (last && l >= 1) a.ep.acc_in2 = self.in.p, a.ep.ld_acc_in2 = self.in.ld, a.s_acc_in2 = self.in.slab;
+  }
+  if (self.mask) {
+    a.ep.mask_out = self.mask + (int64_t)l * self.rows * mrow;
+    a.s_mask_out = (int64_t)st.n_layers * self.rows * mrow;
+  }
+  return a;
+}
+
+// Backward of the stack. With g^l = dL/de^l (l = 0..L), G = dL/d(sum_l e^l):
+//   g_u^L = G_u,  g_i^L = G_i
+//   g_u^l = G_u + g_u^{l+1} + A   (g_i^{l+1} * m_i^{l+1})     (rows = users)
+//   g_i^l = G_i + g_i^{l+1} + A^T (g_u^{l+1} * m_u^{l+1})     (rows = items)
+// m^{l+1} = slope mask of the forward layer that produced e^{l+1} (1 where the activation passed
+// the sum through, leaky elsewhere). Each step is the forward kernel with slope 1, residual =
+// g^{l+1}, acc_in = G, and the masked copy for the next step written by the same epilogue.
+// Scratch slots 0/1 ping-pong the full gradients g^l, slots 2/3 the masked copies; the seed g^L * m^L is in slot 2.
+DirArgs backward_step(const Stack& st, const Side& self, const Side& other, int l) {
+  const int L = st.n_layers;
+  const int64_t mrow = st.d / 4;
+  const int cur = (L - 1 - l) & 1;   // which masked copy holds g^{l+1} * m^{l+1}
+  const Slab x = scratch_slot(st, other, 2 + cur);
+  const Slab g_next = (l == L - 1) ? self.in : scratch_slot(st, self, (l + 1) & 1);
+  const Slab g = (l == 0) ? self.out : scratch_slot(st, self, l & 1);
+  DirArgs a{};
+  a.ep.leaky = 1.f;
+  a.ep.mask_stride = (int)mrow;
+  a.X = x.p, a.ldx = x.ld, a.s_X = x.slab;
+  a.ep.residual = g_next.p, a.ep.ldr = g_next.ld, a.s_res = g_next.slab;
+  a.ep.acc_in = self.in.p, a.ep.ld_acc_in = self.in.ld, a.s_acc_in = self.in.slab;
+  a.ep.acc_out = g.p, a.ep.ld_acc_out = g.ld, a.s_acc_out = g.slab;
+  if (l > 0) {
+    const Slab gm = scratch_slot(st, self, 2 + (cur ^ 1));
+    a.ep.mask_in = self.mask + (int64_t)(l - 1) * self.rows * mrow;
+    a.s_mask_in = (int64_t)L * self.rows * mrow;
+    a.ep.out2 = gm.p, a.ep.ldo2 = gm.ld, a.s_out2 = gm.slab;
+    a.ep.slope2 = st.leaky;
+  }
+  return a;
+}
+
+// The drivers: `launch(au, ai)` runs one layer, rows = users and rows = items (batched() or per_plan() below).
+template <class Launch>
+int run_forward(const Stack& st, Launch launch) {
+  for (int l = 0; l < st.n_layers; ++l)
+    if (int rc = launch(forward_layer(st, st.u, st.i, l), forward_layer(st, st.i, st.u, l))) return rc;
+  return SAGNN_OK;
+}
+
+template <class Launch>
+int run_backward(const Stack& st, Launch launch, void* stream) {
+  for (const Side* s : {&st.u, &st.i}) {   // seed: g^L * m^L of every interval (one launch per node type)
+    const int64_t mrow = st.d / 4;
+    if (int rc = launch_mask_scale(s->in, s->mask + (int64_t)(st.n_layers - 1) * s->rows * mrow, st.n_layers * s->rows * mrow,
+                                   st.leaky, scratch_slot(st, *s, 2), s->rows, st.d, st.T, static_cast<hipStream_t>(stream)))
+      return rc;
+  }
+  for (int l = st.n_layers - 1; l >= 0; --l)
+    if (int rc = launch(backward_step(st, st.u, st.i, l), backward_step(st, st.i, st.u, l))) return rc;
+  return SAGNN_OK;
+}
+
+// One launch per layer for all T intervals and both directions (+ one fix-up launch when the batch has long rows)
+auto batched(const sagnn_spmm_batch* b, int d, void* workspace, void* stream) {
+  return [=](const DirArgs& au, const DirArgs& ai) {
+    return launch_batch_d(b, d, au, ai, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
+  };
+}
+
+// One interval: the user-side launch, then the item-side launch, each with the per-call checks of sagnn_spmm_ex_f32
+auto per_plan(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item, int d, void* workspace,
+              size_t workspace_bytes, void* stream) {
+  return [=](const DirArgs& au, const DirArgs& ai) {
+    if (int rc = spmm_ex(plan_user, au.X, au.ldx, d, au.ep, workspace, workspace_bytes, stream)) return rc;
+    return spmm_ex(plan_item, ai.X, ai.ldx, d, ai.ep, workspace, workspace_bytes, stream);
+  };
+}
+
+Slab slab(const float* p, int64_t ld, int64_t stride) { return Slab{const_cast<float*>(p), ld, stride}; }
+
 }  // namespace
+
+extern "C" int sagnn_gnn_interval_ex_f32(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item,
+                                         const float* u0, int64_t ld_u0, const float* i0, int64_t ld_i0,
+                                         int d, int n_layers, float leaky, float* scratch_u,
+                                         float* scratch_i, float* user_out, int64_t ld_uo, float* item_out,
+                                         int64_t ld_io, uint8_t* mask_u, uint8_t* mask_i, void* workspace,
+                                         size_t workspace_bytes, void* stream) {
+  if (int rc = check_interval_plans(plan_user, plan_item)) return rc;
+  if (!u0 || !i0 || !user_out || !item_out) return sagnn::fail(SAGNN_ERR_NULL, "null embedding pointer");
+  if (n_layers < 1) return sagnn::fail(SAGNN_ERR_ARG, "n_layers = %d: need >= 1", n_layers);
+  if ((mask_u == nullptr) != (mask_i == nullptr)) return sagnn::fail(SAGNN_ERR_NULL, "give both masks or neither");
+  if (n_layers > 1 && (!scratch_u || !scratch_i))
+    return sagnn::fail(SAGNN_ERR_NULL, "scratch buffers required for n_layers > 1");
+  // the first launch refuses a host-only plan before it looks at d: keep that order
+  if (!plan_user->info.on_device) return sagnn::fail(SAGNN_ERR_ARG, "plan was built host-only (no device CSR)");
+  if (int rc = check_d(d)) return rc;
+  const Stack st{{slab(u0, ld_u0, 0), slab(user_out, ld_uo, 0), scratch_u, mask_u, plan_user->info.n_rows},
+                 {slab(i0, ld_i0, 0), slab(item_out, ld_io, 0), scratch_i, mask_i, plan_item->info.n_rows},
+                 1, d, n_layers, leaky};
+  if (int rc = check_stack(st, n_layers > 1, "u0", "i0", "user_out", "item_out")) return rc;
+  return run_forward(st, per_plan(plan_user, plan_item, d, workspace, workspace_bytes, stream));
+}
+
+extern "C" int sagnn_gnn_interval_f32(const sagnn_spmm_plan* plan_user,
+                                      const sagnn_spmm_plan* plan_item, const float* u0,
+                                      int64_t ld_u0, const float* i0, int64_t ld_i0, int d,
+                                      int n_layers, float leaky, float* scratch_u, float* scratch_i,
+                                      float* user_out, int64_t ld_uo, float* item_out, int64_t ld_io,
+                                      void* workspace, size_t workspace_bytes, void* stream) {
+  return sagnn_gnn_interval_ex_f32(plan_user, plan_item, u0, ld_u0, i0, ld_i0, d, n_layers, leaky, scratch_u,
+                                   scratch_i, user_out, ld_uo, item_out, ld_io, nullptr, nullptr, workspace,
+                                   workspace_bytes, stream);
+}
+
+// Backward of sagnn_gnn_interval_ex_f32 (backward_step above); scratch_x: [4][N][d].
+extern "C" int sagnn_gnn_interval_bwd_f32(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item,
+                                          const float* G_u, int64_t ld_gu, const float* G_i, int64_t ld_gi,
+                                          int d, int n_layers, float leaky, const uint8_t* mask_u,
+                                          const uint8_t* mask_i, float* scratch_u, float* scratch_i,
+                                          float* grad_u0, int64_t ld_du, float* grad_i0, int64_t ld_di,
+                                          void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = check_interval_plans(plan_user, plan_item)) return rc;
+  if (!G_u || !G_i || !grad_u0 || !grad_i0 || !mask_u || !mask_i || !scratch_u || !scratch_i)
+    return sagnn::fail(SAGNN_ERR_NULL, "null pointer");
+  if (n_layers < 1) return sagnn::fail(SAGNN_ERR_ARG, "n_layers = %d: need >= 1", n_layers);
+  if (int rc = check_d(d)) return rc;
+  const Stack st{{slab(G_u, ld_gu, 0), slab(grad_u0, ld_du, 0), scratch_u, const_cast<uint8_t*>(mask_u), plan_user->info.n_rows},
+                 {slab(G_i, ld_gi, 0), slab(grad_i0, ld_di, 0), scratch_i, const_cast<uint8_t*>(mask_i), plan_item->info.n_rows},
+                 1, d, n_layers, leaky};
+  if (int rc = check_stack(st, true, "G_u", "G_i", "grad_u0", "grad_i0")) return rc;
+  return run_backward(st, per_plan(plan_user, plan_item, d, workspace, workspace_bytes, stream), stream);
+}
 
 // The whole GNN loop of model.py:118-129 — every interval, every layer — in L row launches (+ L fix-up launches when
 // the graphs have long rows): sagnn_gnn_interval_ex_f32 for all T intervals at once. Operands are slabs.
@@ -1090,69 +1120,21 @@ extern "C" int sagnn_gnn_stack_f32(const sagnn_spmm_batch* b, const float* u0, i
                                    void* workspace, size_t workspace_bytes, void* stream) {
   if (!b) return sagnn::fail(SAGNN_ERR_NULL, "batch is NULL");
   if (!u0 || !i0 || !user_out || !item_out) return sagnn::fail(SAGNN_ERR_NULL, "null embedding pointer");
-  if (d < 4 || d > 256 || (d & 3)) return sagnn::fail(SAGNN_ERR_DIM, "d = %d: need a multiple of 4 in [4, 256]", d);
+  if (int rc = check_d(d)) return rc;
   if (n_layers < 1) return sagnn::fail(SAGNN_ERR_ARG, "n_layers = %d: need >= 1", n_layers);
   if ((mask_u == nullptr) != (mask_i == nullptr)) return sagnn::fail(SAGNN_ERR_NULL, "give both masks or neither");
   if (n_layers > 1 && (!scratch_u || !scratch_i)) return sagnn::fail(SAGNN_ERR_NULL, "scratch buffers required for n_layers > 1");
-  if (int rc = check_slab("u0", u0, ld_u0, slab_u0, d)) return rc;
-  if (int rc = check_slab("i0", i0, ld_i0, slab_i0, d)) return rc;
-  if (int rc = check_slab("user_out", user_out, ld_uo, slab_uo, d)) return rc;
-  if (int rc = check_slab("item_out", item_out, ld_io, slab_io, d)) return rc;
-  if (n_layers > 1 && (!sagnn::aligned16(scratch_u) || !sagnn::aligned16(scratch_i)))
-    return sagnn::fail(SAGNN_ERR_ALIGN, "scratch buffers must be 16-byte aligned");
+  const Stack st{{slab(u0, ld_u0, slab_u0), slab(user_out, ld_uo, slab_uo), scratch_u, mask_u, b->U},
+                 {slab(i0, ld_i0, slab_i0), slab(item_out, ld_io, slab_io), scratch_i, mask_i, b->I},
+                 b->T, d, n_layers, leaky};
+  if (int rc = check_stack(st, n_layers > 1, "u0", "i0", "user_out", "item_out")) return rc;
   if (int rc = check_batch_ws(b, d, workspace, workspace_bytes)) return rc;
-  const int64_t U = b->U, I = b->I, T = b->T;
-  const int64_t mrow = d / 4;
-  // e^l of interval k: layer 0 reads the callers' tables, layer l >= 1 the ping-pong scratch [2][T][N][d]
-  Slab cu{const_cast<float*>(u0), ld_u0, slab_u0}, ci{const_cast<float*>(i0), ld_i0, slab_i0};
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  for (int l = 0; l < n_layers; ++l) {
-    const bool last = (l + 1 == n_layers);
-    DirArgs au{}, ai{};
-    au.ep.leaky = ai.ep.leaky = leaky;
-    au.ep.mask_stride = ai.ep.mask_stride = (int)mrow;
-    au.X = ci.p, au.ldx = ci.ld, au.s_X = ci.slab;       // rows = users gather item rows
-    ai.X = cu.p, ai.ldx = cu.ld, ai.s_X = cu.slab;
-    au.ep.residual = cu.p, au.ep.ldr = cu.ld, au.s_res = cu.slab;
-    ai.ep.residual = ci.p, ai.ep.ldr = ci.ld, ai.s_res = ci.slab;
-    Slab nu{nullptr, d, U * d}, ni{nullptr, d, I * d};
-    if (!last) {
-      nu.p = scratch_u + (int64_t)(l & 1) * T * U * d;
-      ni.p = scratch_i + (int64_t)(l & 1) * T * I * d;
-      au.ep.out = nu.p, au.ep.ldo = nu.ld, au.s_out = nu.slab;
-      ai.ep.out = ni.p, ai.ep.ldo = ni.ld, ai.s_out = ni.slab;
-    }
-    // running sum as in sagnn_gnn_interval_ex_f32: layer 0 of a deeper stack writes e^1 alone, layer 1 starts the sum
-    // from its residual, the last layer adds e^0 on the way out
-    if (last || l >= 1) {
-      if (l <= 1) {
-        au.ep.acc_in = cu.p, au.ep.ld_acc_in = cu.ld, au.s_acc_in = cu.slab;
-        ai.ep.acc_in = ci.p, ai.ep.ld_acc_in = ci.ld, ai.s_acc_in = ci.slab;
-      } else {
-        au.ep.acc_in = user_out, au.ep.ld_acc_in = ld_uo, au.s_acc_in = slab_uo;
-        ai.ep.acc_in = item_out, ai.ep.ld_acc_in = ld_io, ai.s_acc_in = slab_io;
-      }
-      au.ep.acc_out = user_out, au.ep.ld_acc_out = ld_uo, au.s_acc_out = slab_uo;
-      ai.ep.acc_out = item_out, ai.ep.ld_acc_out = ld_io, ai.s_acc_out = slab_io;
-      if (last && l >= 1) {
-        au.ep.acc_in2 = u0, au.ep.ld_acc_in2 = ld_u0, au.s_acc_in2 = slab_u0;
-        ai.ep.acc_in2 = i0, ai.ep.ld_acc_in2 = ld_i0, ai.s_acc_in2 = slab_i0;
-      }
-    }
-    if (mask_u) {   // [T][L][N][d/4]
-      au.ep.mask_out = mask_u + (int64_t)l * U * mrow, au.s_mask_out = (int64_t)n_layers * U * mrow;
-      ai.ep.mask_out = mask_i + (int64_t)l * I * mrow, ai.s_mask_out = (int64_t)n_layers * I * mrow;
-    }
-    if (int rc = launch_batch_d(b, d, au, ai, static_cast<float*>(workspace), s)) return rc;
-    cu = nu;
-    ci = ni;
-  }
-  return SAGNN_OK;
+  return run_forward(st, batched(b, d, workspace, stream));
 }
 
-// Backward of sagnn_gnn_stack_f32 (see sagnn_gnn_interval_bwd_f32 for the recurrence): G_u / G_i are the gradients at the
-// interval outputs as slabs, masks [T][L][N][d/4] as the forward recorded them; scratch_x: [4][T][N][d]. `b` must be the
-// batch of the ADJOINT patterns (for canonical matrices: the same batch).
+// Backward of sagnn_gnn_stack_f32 (backward_step above): G_u / G_i are the gradients at the interval outputs as slabs,
+// masks [T][L][N][d/4] as the forward recorded them; scratch_x: [4][T][N][d]. `b` must be the batch of the ADJOINT
+// patterns (for canonical matrices: the same batch).
 extern "C" int sagnn_gnn_stack_bwd_f32(const sagnn_spmm_batch* b, const float* G_u, int64_t ld_gu, int64_t slab_gu,
                                        const float* G_i, int64_t ld_gi, int64_t slab_gi, int d, int n_layers, float leaky,
                                        const uint8_t* mask_u, const uint8_t* mask_i, float* scratch_u, float* scratch_i,
@@ -1162,65 +1144,11 @@ extern "C" int sagnn_gnn_stack_bwd_f32(const sagnn_spmm_batch* b, const float* G
   if (!G_u || !G_i || !grad_u0 || !grad_i0 || !mask_u || !mask_i || !scratch_u || !scratch_i)
     return sagnn::fail(SAGNN_ERR_NULL, "null pointer");
   if (n_layers < 1) return sagnn::fail(SAGNN_ERR_ARG, "n_layers = %d: need >= 1", n_layers);
-  if (d < 4 || d > 256 || (d & 3)) return sagnn::fail(SAGNN_ERR_DIM, "d = %d: need a multiple of 4 in [4, 256]", d);
-  if (int rc = check_slab("G_u", G_u, ld_gu, slab_gu, d)) return rc;
-  if (int rc = check_slab("G_i", G_i, ld_gi, slab_gi, d)) return rc;
-  if (int rc = check_slab("grad_u0", grad_u0, ld_du, slab_du, d)) return rc;
-  if (int rc = check_slab("grad_i0", grad_i0, ld_di, slab_di, d)) return rc;
+  if (int rc = check_d(d)) return rc;
+  const Stack st{{slab(G_u, ld_gu, slab_gu), slab(grad_u0, ld_du, slab_du), scratch_u, const_cast<uint8_t*>(mask_u), b->U},
+                 {slab(G_i, ld_gi, slab_gi), slab(grad_i0, ld_di, slab_di), scratch_i, const_cast<uint8_t*>(mask_i), b->I},
+                 b->T, d, n_layers, leaky};
+  if (int rc = check_stack(st, true, "G_u", "G_i", "grad_u0", "grad_i0")) return rc;
   if (int rc = check_batch_ws(b, d, workspace, workspace_bytes)) return rc;
-  const int64_t U = b->U, I = b->I, T = b->T;
-  const int64_t mrow = d / 4;
-  const int64_t s_mask_u = (int64_t)n_layers * U * mrow, s_mask_i = (int64_t)n_layers * I * mrow;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  float* gfull_u[2] = {scratch_u, scratch_u + T * U * d};
-  float* gmask_u[2] = {scratch_u + 2 * T * U * d, scratch_u + 3 * T * U * d};
-  float* gfull_i[2] = {scratch_i, scratch_i + T * I * d};
-  float* gmask_i[2] = {scratch_i + 2 * T * I * d, scratch_i + 3 * T * I * d};
-  // seed: g^L * m^L of every interval (one launch per node type)
-  {
-    const int threads = 256;
-    const int64_t nu = U * mrow, ni = I * mrow;
-    if (nu > 0) {
-      hipLaunchKernelGGL(mask_scale_batch_kernel, dim3((unsigned)((nu + threads - 1) / threads), (unsigned)T), dim3(threads), 0, s,
-                         G_u, ld_gu, slab_gu, mask_u + (int64_t)(n_layers - 1) * U * mrow, s_mask_u, (int)mrow, leaky,
-                         gmask_u[0], (int64_t)d, U * d, U, d);
-      SAGNN_HIP_TRY(hipGetLastError());
-    }
-    if (ni > 0) {
-      hipLaunchKernelGGL(mask_scale_batch_kernel, dim3((unsigned)((ni + threads - 1) / threads), (unsigned)T), dim3(threads), 0, s,
-                         G_i, ld_gi, slab_gi, mask_i + (int64_t)(n_layers - 1) * I * mrow, s_mask_i, (int)mrow, leaky,
-                         gmask_i[0], (int64_t)d, I * d, I, d);
-      SAGNN_HIP_TRY(hipGetLastError());
-    }
-  }
-  Slab gun{const_cast<float*>(G_u), ld_gu, slab_gu}, gin{const_cast<float*>(G_i), ld_gi, slab_gi};   // g^{l+1}
-  int cur = 0;
-  for (int l = n_layers - 1; l >= 0; --l) {
-    const bool final_step = (l == 0);
-    DirArgs au{}, ai{};
-    au.ep.leaky = ai.ep.leaky = 1.f;
-    au.ep.mask_stride = ai.ep.mask_stride = (int)mrow;
-    au.X = gmask_i[cur], au.ldx = d, au.s_X = I * d;
-    ai.X = gmask_u[cur], ai.ldx = d, ai.s_X = U * d;
-    au.ep.residual = gun.p, au.ep.ldr = gun.ld, au.s_res = gun.slab;
-    ai.ep.residual = gin.p, ai.ep.ldr = gin.ld, ai.s_res = gin.slab;
-    au.ep.acc_in = G_u, au.ep.ld_acc_in = ld_gu, au.s_acc_in = slab_gu;
-    ai.ep.acc_in = G_i, ai.ep.ld_acc_in = ld_gi, ai.s_acc_in = slab_gi;
-    Slab ou = final_step ? Slab{grad_u0, ld_du, slab_du} : Slab{gfull_u[l & 1], d, U * d};
-    Slab oi = final_step ? Slab{grad_i0, ld_di, slab_di} : Slab{gfull_i[l & 1], d, I * d};
-    au.ep.acc_out = ou.p, au.ep.ld_acc_out = ou.ld, au.s_acc_out = ou.slab;
-    ai.ep.acc_out = oi.p, ai.ep.ld_acc_out = oi.ld, ai.s_acc_out = oi.slab;
-    if (!final_step) {
-      au.ep.mask_in = mask_u + (int64_t)(l - 1) * U * mrow, au.s_mask_in = s_mask_u;
-      ai.ep.mask_in = mask_i + (int64_t)(l - 1) * I * mrow, ai.s_mask_in = s_mask_i;
-      au.ep.out2 = gmask_u[cur ^ 1], au.ep.ldo2 = d, au.s_out2 = U * d;
-      ai.ep.out2 = gmask_i[cur ^ 1], ai.ep.ldo2 = d, ai.s_out2 = I * d;
-      au.ep.slope2 = ai.ep.slope2 = leaky;
-    }
-    if (int rc = launch_batch_d(b, d, au, ai, static_cast<float*>(workspace), s)) return rc;
-    gun = ou;
-    gin = oi;
-    cur ^= 1;
-  }
-  return SAGNN_OK;
+  return run_backward(st, batched(b, d, workspace, stream), stream);
 }

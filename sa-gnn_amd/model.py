@@ -279,6 +279,14 @@ class Recommender:
                 self._batch = ops.SpmmBatch([a.plan for a in self.subAdj], [a.plan for a in self.subTpAdj])
         return self._batch
 
+    def _stack_plans(self):
+        """The (plans_user, plans_item) that ag.gnn_stack takes for this model: (the ops.SpmmBatch, None), or the two
+        lists of T interval plans when the batch is off (_interval_batch)."""
+        batch = self._interval_batch()
+        if batch is not None:
+            return batch, None
+        return [a.plan for a in self.subAdj], [a.plan for a in self.subTpAdj]
+
     def propagate_intervals(self, intervals=None):
         """reference model.py:118-134: for every interval k the L-layer stack with residuals and
         add_n, written straight into [N, T, d] slabs (no stack/transpose pass). `intervals`
@@ -670,11 +678,7 @@ class Recommender:
                          suids=[self._i32(v) for v in batch["suids"]], siids=[self._i32(v) for v in batch["siids"]])
             touched = self._touched_rows(batch)
         # one autograd node for the whole interval loop; uv / iv are [T, N, d] slabs written in place
-        batch_ = self._interval_batch()
-        if batch_ is not None:
-            uv, iv = ag.gnn_stack(self.uEmbed, self.iEmbed, batch_, None, L, leaky)
-        else:
-            uv, iv = ag.gnn_stack(self.uEmbed, self.iEmbed, [a.plan for a in self.subAdj], [a.plan for a in self.subTpAdj], L, leaky)
+        uv, iv = ag.gnn_stack(self.uEmbed, self.iEmbed, *self._stack_plans(), L, leaky)
         finals = []
         if subset:        # the one read-back of the step: the two counts, copied while the stack's launches queue
             touched["done"].synchronize()

@@ -195,8 +195,8 @@ def spmm_ex(plan: SpmmPlan, x: torch.Tensor | None, leaky: float, residual=None,
     e.acc_in2, e.ld_acc_in2 = _ptr(acc_in2), _f32_rows("acc_in2", acc_in2, d, plan.n_rows)
     e.out2, e.ldo2 = _ptr(out2), _f32_rows("out2", out2, d, plan.n_rows)
     for name, m in (("mask_out", mask_out), ("mask_in", mask_in)):
-        if m is not None and (m.dtype != torch.uint8 or not m.is_contiguous() or m.numel() != plan.n_rows * (d // 4)):
-            raise ValueError(f"{name}: need a contiguous uint8 tensor [{plan.n_rows}, {d // 4}]")
+        if m is not None:
+            _masks(name, m, (plan.n_rows, d // 4))
     e.mask_out, e.mask_in = _ptr(mask_out), _ptr(mask_in)
     ldx = _f32_rows("x", x, d, plan.n_src) if x is not None else d
     ws = plan.workspace(d)
@@ -208,8 +208,7 @@ def spmm_ex(plan: SpmmPlan, x: torch.Tensor | None, leaky: float, residual=None,
 def mask_scale(g: torch.Tensor, mask: torch.Tensor, slope: float, out: torch.Tensor):
     """out = g * (mask bit ? 1 : slope) (sagnn_mask_scale_f32); g / out [rows, d] views, mask [rows, d/4] uint8."""
     rows, d = int(g.shape[0]), int(g.shape[1])
-    if mask.dtype != torch.uint8 or not mask.is_contiguous() or mask.numel() != rows * (d // 4):
-        raise ValueError(f"mask: need a contiguous uint8 tensor [{rows}, {d // 4}]")
+    _masks("mask", mask, (rows, d // 4))
     check(_lib.load().sagnn_mask_scale_f32(_ptr(g), _f32_rows("g", g, d, rows), _ptr(mask), float(slope), _ptr(out),
                                            _f32_rows("out", out, d, rows), rows, d, _stream()))
     return out
@@ -218,6 +217,37 @@ def mask_scale(g: torch.Tensor, mask: torch.Tensor, slope: float, out: torch.Ten
 def _interval_ws(plan_user: SpmmPlan, plan_item: SpmmPlan, d: int):
     wu, wi = plan_user.workspace(d), plan_item.workspace(d)
     return wu if (wi is None or (wu is not None and wu.numel() >= wi.numel())) else wi
+
+
+def _scratch(name: str, s: torch.Tensor | None, k: int, rows: int, d: int, device):
+    """A contiguous float32 scratch of at least k * rows * d elements: `s` checked, or a new one."""
+    if s is None:
+        return torch.empty(k * rows * d, dtype=torch.float32, device=device)
+    if s.dtype != torch.float32 or not s.is_contiguous() or s.numel() < k * rows * d:
+        raise ValueError(f"{name}: need a contiguous float32 buffer of {k}*{rows}*{d} elements")
+    return s
+
+
+def _masks(name: str, m: torch.Tensor, shape: tuple):
+    """The activation masks of a stack: a contiguous uint8 tensor of prod(shape) elements."""
+    if m.dtype != torch.uint8 or not m.is_contiguous() or m.numel() != int(np.prod(shape)):
+        raise ValueError(f"{name}: need a contiguous uint8 tensor {list(shape)}")
+    return m
+
+
+def _adjoint_pair(plan_user: SpmmPlan, plan_item: SpmmPlan):
+    """The (user, item) plans the backward of an interval runs on: rows = users gathers through (item-side forward
+    pattern)^T, rows = items through (user-side)^T. A transposed pair is its own adjoint; a pair with duplicated stored
+    entries carries the exact adjoints (graph.interval_pair); any other pair is refused."""
+    adj_u, adj_i = plan_user.partner_adjoint, plan_item.partner_adjoint
+    if (adj_u is None) != (adj_i is None):
+        raise ValueError("give the exact adjoint of both plans or of neither")
+    if adj_u is not None:
+        return adj_u, adj_i
+    if plan_user.nnz != plan_item.nnz:
+        raise ValueError(f"plans are not a transposed pair (nnz {plan_user.nnz} vs {plan_item.nnz}: duplicated stored "
+                         "entries?) — build them with graph.interval_pair, which adds the exact adjoints")
+    return plan_user, plan_item
 
 
 def gnn_interval(plan_user: SpmmPlan, plan_item: SpmmPlan, u0: torch.Tensor, i0: torch.Tensor,
@@ -235,17 +265,12 @@ def gnn_interval(plan_user: SpmmPlan, plan_item: SpmmPlan, u0: torch.Tensor, i0:
     ld_uo = _f32_rows("user_out", user_out, d, U)
     ld_io = _f32_rows("item_out", item_out, d, I)
     if n_layers > 1:
-        if scratch_u is None:
-            scratch_u = torch.empty((2, U, d), dtype=torch.float32, device=u0.device)
-        if scratch_i is None:
-            scratch_i = torch.empty((2, I, d), dtype=torch.float32, device=u0.device)
-        for name, s, rows in (("scratch_u", scratch_u, U), ("scratch_i", scratch_i, I)):
-            if s.dtype != torch.float32 or not s.is_contiguous() or s.numel() < 2 * rows * d:
-                raise ValueError(f"{name}: need a contiguous float32 buffer of 2*{rows}*{d} elements")
-    for name, m, rows in (("mask_u", mask_u, U), ("mask_i", mask_i, I)):
-        if m is not None and (m.dtype != torch.uint8 or not m.is_contiguous() or
-                              m.numel() != n_layers * rows * (d // 4)):
-            raise ValueError(f"{name}: need a contiguous uint8 tensor [{n_layers}, {rows}, {d // 4}]")
+        scratch_u = _scratch("scratch_u", scratch_u, 2, U, d, u0.device)
+        scratch_i = _scratch("scratch_i", scratch_i, 2, I, d, u0.device)
+    if mask_u is not None:
+        _masks("mask_u", mask_u, (n_layers, U, d // 4))
+    if mask_i is not None:
+        _masks("mask_i", mask_i, (n_layers, I, d // 4))
     ws = _interval_ws(plan_user, plan_item, d)
     check(plan_user._lib.sagnn_gnn_interval_ex_f32(
         plan_user.handle, plan_item.handle, _ptr(u0), ld_u0, _ptr(i0), ld_i0, d, int(n_layers),
@@ -263,15 +288,7 @@ def gnn_interval_bwd(plan_user: SpmmPlan, plan_item: SpmmPlan, grad_user_out: to
     recorded masks -> dL/d u0 [U, d], dL/d i0 [I, d]."""
     d = int(grad_user_out.shape[1])
     U, I = plan_user.n_rows, plan_item.n_rows
-    # rows = users gathers through (item-side forward pattern)^T, rows = items through (user-side)^T
-    adj_u, adj_i = plan_user.partner_adjoint, plan_item.partner_adjoint
-    if (adj_u is None) != (adj_i is None):
-        raise ValueError("give the exact adjoint of both plans or of neither")
-    if adj_u is None and plan_user.nnz != plan_item.nnz:
-        raise ValueError(f"plans are not a transposed pair (nnz {plan_user.nnz} vs {plan_item.nnz}: duplicated stored "
-                         "entries?) — build them with graph.interval_pair, which adds the exact adjoints")
-    if adj_u is not None:
-        plan_user, plan_item = adj_u, adj_i
+    plan_user, plan_item = _adjoint_pair(plan_user, plan_item)
     ld_gu = _f32_rows("grad_user_out", grad_user_out, d, U)
     ld_gi = _f32_rows("grad_item_out", grad_item_out, d, I)
     dev = grad_user_out.device
@@ -281,16 +298,10 @@ def gnn_interval_bwd(plan_user: SpmmPlan, plan_item: SpmmPlan, grad_user_out: to
         grad_i0 = torch.empty((I, d), dtype=torch.float32, device=dev)
     ld_du = _f32_rows("grad_u0", grad_u0, d, U)
     ld_di = _f32_rows("grad_i0", grad_i0, d, I)
-    if scratch_u is None:
-        scratch_u = torch.empty((4, U, d), dtype=torch.float32, device=dev)
-    if scratch_i is None:
-        scratch_i = torch.empty((4, I, d), dtype=torch.float32, device=dev)
-    for name, s_, rows in (("scratch_u", scratch_u, U), ("scratch_i", scratch_i, I)):
-        if s_.dtype != torch.float32 or not s_.is_contiguous() or s_.numel() < 4 * rows * d:
-            raise ValueError(f"{name}: need a contiguous float32 buffer of 4*{rows}*{d} elements")
-    for name, m, rows in (("mask_u", mask_u, U), ("mask_i", mask_i, I)):
-        if m.dtype != torch.uint8 or not m.is_contiguous() or m.numel() != n_layers * rows * (d // 4):
-            raise ValueError(f"{name}: need a contiguous uint8 tensor [{n_layers}, {rows}, {d // 4}]")
+    scratch_u = _scratch("scratch_u", scratch_u, 4, U, d, dev)
+    scratch_i = _scratch("scratch_i", scratch_i, 4, I, d, dev)
+    _masks("mask_u", mask_u, (n_layers, U, d // 4))
+    _masks("mask_i", mask_i, (n_layers, I, d // 4))
     ws = _interval_ws(plan_user, plan_item, d)
     check(plan_user._lib.sagnn_gnn_interval_bwd_f32(
         plan_user.handle, plan_item.handle, _ptr(grad_user_out), ld_gu, _ptr(grad_item_out), ld_gi, d,
@@ -341,17 +352,11 @@ class SpmmBatch:
         return ws
 
     def adjoint(self) -> "SpmmBatch":
-        adj_u = [p.partner_adjoint for p in self.plans_user]
-        adj_i = [p.partner_adjoint for p in self.plans_item]
-        if all(a is None for a in adj_u + adj_i):
-            for pu, pi in zip(self.plans_user, self.plans_item):
-                if pu.nnz != pi.nnz:
-                    raise ValueError("plans are not a transposed pair (duplicated stored entries?) — build them with "
-                                     "graph.interval_pair, which adds the exact adjoints")
+        pairs = [_adjoint_pair(pu, pi) for pu, pi in zip(self.plans_user, self.plans_item)]
+        if all(adj_u is pu for (adj_u, _), pu in zip(pairs, self.plans_user)):
             return self
         if self._adjoint is None:
-            self._adjoint = SpmmBatch([a if a is not None else p for a, p in zip(adj_u, self.plans_user)],
-                                      [a if a is not None else p for a, p in zip(adj_i, self.plans_item)])
+            self._adjoint = SpmmBatch([a for a, _ in pairs], [a for _, a in pairs])
         return self._adjoint
 
 
@@ -379,16 +384,12 @@ def gnn_stack(batch: SpmmBatch, u0: torch.Tensor, i0: torch.Tensor, n_layers: in
     ld_uo, sl_uo = _slab("user_out", user_out, T, U, d)
     ld_io, sl_io = _slab("item_out", item_out, T, I, d)
     if n_layers > 1:
-        if scratch_u is None:
-            scratch_u = torch.empty((2, T, U, d), dtype=torch.float32, device=u0.device)
-        if scratch_i is None:
-            scratch_i = torch.empty((2, T, I, d), dtype=torch.float32, device=u0.device)
-        for name, s_, rows in (("scratch_u", scratch_u, U), ("scratch_i", scratch_i, I)):
-            if s_.dtype != torch.float32 or not s_.is_contiguous() or s_.numel() < 2 * T * rows * d:
-                raise ValueError(f"{name}: need a contiguous float32 buffer of 2*{T}*{rows}*{d} elements")
-    for name, m, rows in (("mask_u", mask_u, U), ("mask_i", mask_i, I)):
-        if m is not None and (m.dtype != torch.uint8 or not m.is_contiguous() or m.numel() != T * n_layers * rows * (d // 4)):
-            raise ValueError(f"{name}: need a contiguous uint8 tensor [{T}, {n_layers}, {rows}, {d // 4}]")
+        scratch_u = _scratch("scratch_u", scratch_u, 2 * T, U, d, u0.device)
+        scratch_i = _scratch("scratch_i", scratch_i, 2 * T, I, d, u0.device)
+    if mask_u is not None:
+        _masks("mask_u", mask_u, (T, n_layers, U, d // 4))
+    if mask_i is not None:
+        _masks("mask_i", mask_i, (T, n_layers, I, d // 4))
     ws = batch.workspace(d)
     check(batch._lib.sagnn_gnn_stack_f32(batch.handle, _ptr(u0), ld_u0, sl_u0, _ptr(i0), ld_i0, sl_i0, d, int(n_layers),
                                          float(leaky), _ptr(scratch_u), _ptr(scratch_i), _ptr(user_out), ld_uo, sl_uo,
@@ -410,13 +411,10 @@ def gnn_stack_bwd(batch: SpmmBatch, grad_user_out: torch.Tensor, grad_item_out: 
     ld_du, sl_du = _slab("grad_u0", grad_u0, T, U, d)
     ld_di, sl_di = _slab("grad_i0", grad_i0, T, I, d)
     dev = grad_user_out.device
-    if scratch_u is None:
-        scratch_u = torch.empty((4, T, U, d), dtype=torch.float32, device=dev)
-    if scratch_i is None:
-        scratch_i = torch.empty((4, T, I, d), dtype=torch.float32, device=dev)
-    for name, m, rows in (("mask_u", mask_u, U), ("mask_i", mask_i, I)):
-        if m.dtype != torch.uint8 or not m.is_contiguous() or m.numel() != T * n_layers * rows * (d // 4):
-            raise ValueError(f"{name}: need a contiguous uint8 tensor [{T}, {n_layers}, {rows}, {d // 4}]")
+    scratch_u = _scratch("scratch_u", scratch_u, 4 * T, U, d, dev)
+    scratch_i = _scratch("scratch_i", scratch_i, 4 * T, I, d, dev)
+    _masks("mask_u", mask_u, (T, n_layers, U, d // 4))
+    _masks("mask_i", mask_i, (T, n_layers, I, d // 4))
     ws = adj.workspace(d)
     check(adj._lib.sagnn_gnn_stack_bwd_f32(adj.handle, _ptr(grad_user_out), ld_gu, sl_gu, _ptr(grad_item_out), ld_gi, sl_gi, d,
                                            int(n_layers), float(leaky), _ptr(mask_u), _ptr(mask_i), _ptr(scratch_u),

@@ -51,7 +51,7 @@ def test_gnn_interval_backward_vs_autograd(dev, d, L, tuning):
 
 
 def test_autograd_function_end_to_end(dev):
-    """GnnIntervalFn inside a torch graph: gradients of a scalar loss w.r.t. the embedding tables."""
+    """ag.gnn_interval inside a torch graph: gradients of a scalar loss w.r.t. the embedding tables."""
     from sa_gnn_amd import autograd as ag
     from sa_gnn_amd import graph
     rng = np.random.default_rng(3)

@@ -325,3 +325,49 @@ def test_gnn_stack_backward_matches_per_interval_backward(dev, d, L, T):
         res.append((ou.detach(), oi.detach(), a.grad, b.grad))
     for x, y in zip(res[0], res[1]):
         assert torch.equal(x, y)
+
+
+def _stack_entry_refusals(dev):
+    """(name, returned code, expected code, refused only since the entries share their checks) for malformed calls of
+    sagnn_gnn_stack_f32 / _bwd_f32 on a real batch; every call returns before a launch."""
+    from sa_gnn_amd import graph, ops
+    rng = np.random.default_rng(3)
+    U, I, T, d = 40, 30, 2, 64
+    pairs = [graph.interval_pair(m, dev) for m in _intervals(rng, U, I, T, (0.1,))]
+    batch = ops.SpmmBatch([p[0].plan for p in pairs], [p[1].plan for p in pairs])
+    lib, b = ops._lib.load(), batch.handle
+    buf = torch.zeros(4 * T * U * d + 8, device=dev)
+    m = torch.zeros(2 * T * U * d // 4, dtype=torch.uint8, device=dev).data_ptr()
+    p, ws = buf.data_ptr(), batch.workspace(d)
+    wsp, wsb = ops._ptr(ws), 0 if ws is None else ws.numel() * 4
+
+    def fwd(u0=p, d=d, L=1, scr_u=None, scr_i=None, mask_u=None, mask_i=None):
+        return lib.sagnn_gnn_stack_f32(b, u0, d, U * d, p, d, I * d, d, L, 0.5, scr_u, scr_i, p, d, U * d, p, d, I * d,
+                                       mask_u, mask_i, wsp, wsb, None)
+
+    def bwd(G_u=p, d=d, L=1, scr_u=p, scr_i=p, mask_u=m, mask_i=m):
+        return lib.sagnn_gnn_stack_bwd_f32(b, G_u, d, U * d, p, d, I * d, d, L, 0.5, mask_u, mask_i, scr_u, scr_i,
+                                           p, d, U * d, p, d, I * d, wsp, wsb, None)
+
+    return [
+        ("forward, NULL embedding", lambda: fwd(u0=None), -1, False),
+        ("forward, n_layers = 0", lambda: fwd(L=0), -5, False),
+        ("forward, d = 62", lambda: fwd(d=62), -2, False),
+        ("forward, one mask without the other", lambda: fwd(mask_i=m), -1, False),
+        ("forward, two layers without scratch", lambda: fwd(L=2), -1, False),
+        ("forward, misaligned embedding", lambda: fwd(u0=p + 4), -3, False),
+        ("forward, misaligned scratch", lambda: fwd(L=2, scr_u=p + 4, scr_i=p), -3, False),
+        ("backward, NULL gradient", lambda: bwd(G_u=None), -1, False),
+        ("backward, n_layers = 0", lambda: bwd(L=0), -5, False),
+        ("backward, d = 62", lambda: bwd(d=62), -2, False),
+        ("backward, one mask without the other", lambda: bwd(mask_u=None), -1, False),
+        ("backward, no scratch", lambda: bwd(scr_i=None), -1, False),
+        ("backward, misaligned gradient", lambda: bwd(G_u=p + 4), -3, False),
+        ("backward, misaligned scratch", lambda: bwd(scr_u=p + 4), -3, True),
+    ], (batch, pairs, buf)
+
+
+def test_gnn_stack_entries_refuse_malformed_calls(dev):
+    """The batched entries' argument checks (the per-interval entries' table is in tests/test_host.py)."""
+    table, keep = _stack_entry_refusals(dev)
+    assert [(name, call()) for name, call, _, _ in table] == [(name, want) for name, _, want, _ in table]

@@ -147,6 +147,57 @@ def test_round3_entries_reject_bad_arguments_without_gpu():
     assert b"null" in msg.value.lower()
 
 
+def test_gnn_stack_entries_reject_malformed_calls_without_gpu():
+    """The four entries of the GNN stack (one interval / a batch, forward / backward) and the code each malformed call
+    returns; every one of them returns before a launch. Plans built with device=None are host-only: a well-formed
+    forward on them is refused as such (-5), and that refusal comes before the forward's look at d. A batch cannot be
+    built without a device, so here the batched entries only see a NULL one (tests/test_gpu_spmm.py has their table)."""
+    lib = _lib.load()
+    buf = (ctypes.c_float * 4096)()
+    p = (ctypes.addressof(buf) + 15) & ~15
+    mbuf = (ctypes.c_uint8 * 4096)()
+    m = ctypes.addressof(mbuf)
+
+    def host_plan(rows, cols):
+        return SpmmPlan(np.arange(rows + 1, dtype=np.int32), np.zeros(rows, np.int32), rows, cols)
+
+    pu, pi, other = host_plan(3, 4), host_plan(4, 3), host_plan(5, 3)
+    U, I = pu.handle, pi.handle
+
+    def fwd(plan_user=U, plan_item=I, u0=p, d=64, L=1, scratch=None, mask_u=None, mask_i=None):
+        return lib.sagnn_gnn_interval_ex_f32(plan_user, plan_item, u0, 64, p, 64, d, L, 0.5, scratch, scratch, p, 64, p, 64,
+                                             mask_u, mask_i, None, 0, None)
+
+    def bwd(plan_user=U, plan_item=I, G_u=p, d=64, L=1, scratch=p, mask_u=m, mask_i=m):
+        return lib.sagnn_gnn_interval_bwd_f32(plan_user, plan_item, G_u, 64, p, 64, d, L, 0.5, mask_u, mask_i, scratch, scratch,
+                                              p, 64, p, 64, None, 0, None)
+
+    table = [
+        ("forward, NULL plan", fwd(plan_user=None), -1),
+        ("forward, NULL embedding", fwd(u0=None), -1),
+        ("forward, n_layers = 0", fwd(L=0), -5),
+        ("forward, d = 62 (host-only plan refused first)", fwd(d=62), -5),
+        ("forward, one mask without the other", fwd(mask_u=m), -1),
+        ("forward, two layers without scratch", fwd(L=2), -1),
+        ("forward, not a transposed pair", fwd(plan_item=other.handle), -5),
+        ("forward, well-formed on host-only plans", fwd(L=2, scratch=p, mask_u=m, mask_i=m), -5),
+        ("backward, NULL plan", bwd(plan_item=None), -1),
+        ("backward, NULL gradient", bwd(G_u=None), -1),
+        ("backward, n_layers = 0", bwd(L=0), -5),
+        ("backward, d = 62", bwd(d=62), -2),
+        ("backward, one mask without the other", bwd(mask_i=None), -1),
+        ("backward, no scratch", bwd(scratch=None), -1),
+        ("backward, not a transposed pair", bwd(plan_item=other.handle), -5),
+        ("batched forward, NULL batch",
+         lib.sagnn_gnn_stack_f32(None, p, 64, 0, p, 64, 0, 64, 1, 0.5, None, None, p, 64, 0, p, 64, 0, None, None, None, 0, None), -1),
+        ("batched backward, NULL batch",
+         lib.sagnn_gnn_stack_bwd_f32(None, p, 64, 0, p, 64, 0, 64, 1, 0.5, m, m, p, p, p, 64, 0, p, 64, 0, None, 0, None), -1),
+    ]
+    assert [(name, rc) for name, rc, _ in table] == [(name, want) for name, _, want in table]
+    # the thin forward without masks goes the same way
+    assert lib.sagnn_gnn_interval_f32(U, I, p, 64, p, 64, 64, 0, 0.5, None, None, p, 64, p, 64, None, 0, None) == -5
+
+
 def test_params_match_reference_flags():
     from sa_gnn_amd import Params
     a = Params.parse_args([])
