@@ -360,9 +360,11 @@ size_t sagnn_interval_fusion_workspace_bytes(int64_t n, int t, int d);
 /* ------------------------------------------------------------------------------------
  * Backward of the interval fusion: the gradients tf.gradients derives for
  * model.py:135-155. The host (sa-gnn_amd/autograd.py) sequences these entries with the dense
- * products below. Any d that is a multiple of 32 trains through the per-step entries and the dense products
- * (d = 128 is checked against the float64 oracle); the fused entries — attention-backward front and tail, the
- * one-launch BPTT — say which d they cover through their *_supported queries. d_k a power of two.
+ * products below. Training needs d in {32, 64, 128, 192, 256}: the dense products take multiples of 32, and
+ * sagnn_attn_bwd_f32 / sagnn_layernorm_td_bwd_f32 need 64 % d == 0 or d % 64 == 0 (SAGNN_ERR_DIM otherwise, so
+ * d = 96, 160 and 224 run the forward only). Each of the five is checked against the float64 oracle; the fused
+ * entries — attention-backward front and tail, the one-launch BPTT — say which shapes they cover through their
+ * *_supported queries. sagnn_attn_bwd_f32 takes any d_k = d / heads (the fused fronts: powers of two).
  *
  * sagnn_lstm_fwd_train_f32 — sagnn_lstm_fwd_f32 that also stores the gate activations
  *   gates [n, t, 4d] = sigmoid(i) | tanh(j) | sigmoid(f + forget_bias) | sigmoid(o) and the cell
@@ -442,7 +444,8 @@ int sagnn_pair_score_f32(const float* U, int64_t ldu, const float* I, int64_t ld
 /* ------------------------------------------------------------------------------------
  * Training-side operators (reference model.py:169-205, 241-250). All scatter
  * outputs (dU, dI, dS, dA, dX, dY, dF, dV, dw3, db3, loss) ACCUMULATE with float atomics: zero
- * them first. Dense gradient rows are [rows, d] contiguous.
+ * them first. Dense gradient rows are [rows, d] contiguous. The slope of max(leaky*x, x) is `leaky` wherever
+ * x <= leaky*x (tf.maximum sends the gradient to its first argument on ties: x = 0, a product of exactly 0).
  *   sagnn_pair_score_bwd_f32      backward of sagnn_pair_score_f32 given g [n_pairs]
  *   sagnn_prod_leaky_sum_f32      s[e] = sum_j leaky(X[uids[e]][j] * Y[iids[e]][j])   (model.py:191,199)
  *   sagnn_prod_leaky_sum_bwd_f32  its backward
@@ -453,7 +456,15 @@ int sagnn_pair_score_f32(const float* U, int64_t ldu, const float* I, int64_t ld
  *   sagnn_rowdot_sigmoid_bwd_f32  dA[e, :k] = dz*w3, dw3 += sum dz*A[e], db3 += sum dz, dz = dw*w*(1-w)
  *   sagnn_hinge_f32               loss += scale * sum max(0, 1 - S*(pos - neg)), S = wp*sp - wn*sn
  *                                 (S = 1 when wp is NULL: model.py:244; weighted: model.py:196,202);
- *                                 writes d(loss)/d pos, neg, wp, wn (each nullable)
+ *                                 writes d(loss)/d pos, neg, wp, wn; a row with 1 - S*(pos - neg) <= 0 has no term
+ *                                 and zero gradients. The gradient outputs are optional IN PAIRS: dpos with dneg,
+ *                                 dwp with dwn (both or neither; dwp / dwn only with wp); wp, wn, sp, sn all or none
+ * Limits: pair entries (pair_score_bwd, prod_leaky_sum*) d = 4 * a power of two, <= 256; meta_features* d a multiple
+ *   of 4 in [4, 256]; U, I, S, A, X, Y, F, V, the meta-feature block (out / dm, [n, 3d] dense) 16-byte aligned with
+ *   strides that are multiples of 4 and >= d; S, A, locs, dS, dA all or none (none drops the second term);
+ *   1 <= k <= 8192, lda >= k, ldda >= k (no alignment: the row-dot reads scalars; dA columns >= k are not written);
+ *   counts >= 0 (0 returns SAGNN_OK at once) and small enough for one launch (SAGNN_ERR_ARG "grid too large").
+ *   Ids are the caller's responsibility (never checked here). Every argument is checked before any device work.
  * -------------------------------------------------------------------------------- */
 int sagnn_pair_score_bwd_f32(const float* U, int64_t ldu, const float* I, int64_t ldi, const float* S, int64_t lds,
                              const float* A, int64_t lda, const int32_t* uids, const int32_t* iids,

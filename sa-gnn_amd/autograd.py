@@ -13,6 +13,9 @@ FUSED_ATTN_BWD = True
 FUSED_BPTT = True
 DEFERRED_DW_LIMIT = 32 << 30   # bytes of gate gradients ([t, n, 4d]) a BPTT may keep for the separate weight-gradient pass
 SPLIT_DW = True                # one-launch BPTT (d = 32 / 64): weight gradient as a second pass on the f16 x 2 engine ...
+# Feature widths the fusion's backward runs at: multiples of 32 (the dense products) with 64 % d == 0 or d % 64 == 0
+# (sagnn_attn_bwd_f32, sagnn_layernorm_td_bwd_f32). The forward alone also runs at d = 96, 160, 224.
+TRAINABLE_D = (32, 64, 128, 192, 256)
 SPLIT_DW_MIN_T = 4              # ... from this many steps on (measured: T = 16 -13 %, T = 6 -8 %, T = 2 / 3 nothing: the gate gradients' HBM round trip)
 
 
@@ -83,6 +86,14 @@ def gnn_interval(u0, i0, plan_user, plan_item, n_layers: int, leaky: float):
     """(uEmbed[k], iEmbed[k]) -> (user_k, item_k): the stack of one interval, on its own plans."""
     user_out, item_out = gnn_stack(u0.unsqueeze(0), i0.unsqueeze(0), [plan_user], [plan_item], n_layers, leaky)
     return user_out[0], item_out[0]
+
+
+def _check_trainable(x):
+    """Refuses a width the backward has no kernels for BEFORE the forward runs (the library would return SAGNN_ERR_DIM
+    halfway through the backward pass, after the LSTM and the attention forward have been paid for)."""
+    d = int(x.shape[-1])
+    if d not in TRAINABLE_D:
+        raise ValueError(f"d = {d}: the interval fusion trains at d in {TRAINABLE_D} (inference: any multiple of 32 up to 256)")
 
 
 def _split_qkv_grads(dWqkv, dbqkv, d):
@@ -192,7 +203,7 @@ def _fusion_backward(x, lstm_W, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, h, ga
     if lib.sagnn_lstm_bwd_supported(d) and FUSED_BPTT:
         dx, dW, db = lstm_bwd(x, h, gates, cell, dh, drop, lstm_W.detach())
         return (dx, dW, db, dgamma, dbeta) + _split_qkv_grads(dWqkv, dbqkv, d)
-    # generic BPTT (any d that is a multiple of 32; d = 128 is BASELINE config 3). Per step: the element-wise gate
+    # generic BPTT (the widths of TRAINABLE_D beyond 32 / 64; d = 128 is BASELINE config 3). Per step: the element-wise gate
     # backward and ONE product d[x_t | h_{t-1}] = dG_t W^T written where the next step reads it. The gate gradients of
     # all steps stay in HBM ([t, n, 4d]) and the weight gradient is two segmented products after the loop instead of
     # 2 t small ones (each of those a split-K launch ending in 64 K float atomics per block).
@@ -252,7 +263,8 @@ class IntervalFusionFn(torch.autograd.Function):
 
 
 def interval_fusion(x, p: dict, heads: int, drop_scale=None):
-    """Differentiable interval fusion; p as in ops.interval_fusion."""
+    """Differentiable interval fusion; p as in ops.interval_fusion. d must be one of TRAINABLE_D."""
+    _check_trainable(x)
     return IntervalFusionFn.apply(x, p["lstm_W"], p["lstm_b"], p["ln_gamma"], p["ln_beta"], p["Wq"], p["bq"],
                                   p["Wk"], p["bk"], p["Wv"], p["bv"], heads, drop_scale)
 
@@ -320,6 +332,7 @@ def interval_fusion_rows(x, rows, count, cap: int, p: dict, heads: int, drop_sca
     """Differentiable interval fusion of rows[:cap] of x (IntervalFusionRowsFn): [N, d] with exact zeros in every row
     not among the first `count` slots. rows / count as ops.rows_compact returns them (count on the device; cap, the
     number of slots to run, from the host, at least the count); p as in ops.interval_fusion."""
+    _check_trainable(x)
     if int(cap) > rows.numel():
         raise ValueError(f"cap = {int(cap)} > {rows.numel()} row slots")
     return IntervalFusionRowsFn.apply(x, rows[:int(cap)], count, p["lstm_W"], p["lstm_b"], p["ln_gamma"], p["ln_beta"],

@@ -19,7 +19,13 @@ constexpr int kBlock = 256;
 // g = dL/dout / t (the same for every query position):
 //   p_s   = sum_{j in head} g_j V[s][j]
 //   dz_qs = a_qs (p_s - sum_s' a_qs' p_s')
+//         evaluated around c = p_0: (p_s - c) - sum_s' a_qs' (p_s' - c) + c (1 - sum_s' a_qs'), with
+//         1 - sum_s' a_qs' = 1e-8 / (R_q + 1e-8) formed directly. fp32 cannot tell sum a from 1, so the plain form loses
+//         what the 1e-8 leaves of dQ / dK where the p_s of a head agree (t = 1: dz = a p 1e-8 / (R + 1e-8) exactly).
 //   dQ[q] = scale * sum_s dz_qs K[s];  dK[s] = scale * sum_q dz_qs Q[q];  dV[s] = g * sum_q a_qs
+// d_k a power of two: p_s is a shuffle sum over the head's adjacent lanes. Any other d_k (d = 192 with 16 heads:
+// d_k = 12, a head may straddle two waves): g goes through LDS (d more floats per slot) and lane c of the head sums
+// p_s for s = c, c + d_k, ...
 __global__ void attn_bwd_kernel(float* __restrict__ qkv, const float* __restrict__ g_out, int64_t ld_g,
                                 int64_t n, int t, int d, int heads) {
   extern __shared__ float sm[];
@@ -29,12 +35,14 @@ __global__ void attn_bwd_kernel(float* __restrict__ qkv, const float* __restrict
   const int dk = d / heads;
   const int h = j / dk, c = j % dk, h0 = h * dk;
   const int td = t * d, tt = t * t;
-  float* qs = sm + (size_t)slot * (3 * td + heads * (tt + 2 * t));
+  const bool pow2 = (dk & (dk - 1)) == 0;
+  float* qs = sm + (size_t)slot * (3 * td + heads * (tt + 2 * t) + (pow2 ? 0 : d));
   float* ks = qs + td;
   float* vs = ks + td;
   float* as = vs + td;            // [heads][t][t]: e, then a
   float* ps = as + heads * tt;    // [heads][t]: p_s
   float* ds = ps + heads * t;     // [heads][t]: sum_s' a_qs' p_s' per query
+  float* gs = ds + heads * t;     // [d]: g, only when d_k is not a power of two
   const float scale = 1.f / sqrtf((float)dk);
   const float inv_t = 1.f / (float)t;
 
@@ -48,6 +56,7 @@ __global__ void attn_bwd_kernel(float* __restrict__ qkv, const float* __restrict
       vs[ts * d + j] = valid ? row[ts * 3 * d + 2 * d + j] : 0.f;
     }
     const float g = valid ? g_out[node * ld_g + j] * inv_t : 0.f;
+    if (!pow2) gs[j] = g;
     __syncthreads();
     // e_qs of this head: its dk lanes split the (q, s) pairs
     for (int pr = c; pr < tt; pr += dk) {
@@ -57,10 +66,18 @@ __global__ void attn_bwd_kernel(float* __restrict__ qkv, const float* __restrict
       as[h * tt + pr] = expf(z * scale);
     }
     // p_s: head sum of g_j V[s][j] (the dk lanes of a head are adjacent lanes of one wave)
-    for (int s = 0; s < t; ++s) {
-      float part = g * vs[s * d + j];
-      for (int off = 1; off < dk; off <<= 1) part += __shfl_xor(part, off);
-      if (c == 0) ps[h * t + s] = part;
+    if (pow2) {
+      for (int s = 0; s < t; ++s) {
+        float part = g * vs[s * d + j];
+        for (int off = 1; off < dk; off <<= 1) part += __shfl_xor(part, off);
+        if (c == 0) ps[h * t + s] = part;
+      }
+    } else {
+      for (int s = c; s < t; s += dk) {
+        float part = 0.f;
+        for (int cc = 0; cc < dk; ++cc) part = fmaf(gs[h0 + cc], vs[s * d + h0 + cc], part);
+        ps[h * t + s] = part;
+      }
     }
     __syncthreads();
     // normalise the rows: lane c takes queries q = c, c + dk, ...
@@ -69,26 +86,28 @@ __global__ void attn_bwd_kernel(float* __restrict__ qkv, const float* __restrict
       float rsum = 0.f;
       for (int s = 0; s < t; ++s) rsum += ar[s];
       const float inv = 1.f / (rsum + 1e-8f);
+      const float c0 = ps[h * t];
       float dot = 0.f;
       for (int s = 0; s < t; ++s) {
         const float a = ar[s] * inv;
         ar[s] = a;
-        dot = fmaf(a, ps[h * t + s], dot);
+        dot = fmaf(a, ps[h * t + s] - c0, dot);
       }
-      ds[h * t + q] = dot;
+      ds[h * t + q] = dot - c0 * (1e-8f * inv);   // sum_s a (p_s - c0) - c0 (1 - sum_s a)
     }
     __syncthreads();
     // per-column outputs, in place
     if (valid) {
+      const float c0 = ps[h * t];
       for (int q = 0; q < t; ++q) {
         const float* ar = as + h * tt + q * t;
         const float dot = ds[h * t + q];
         float dq = 0.f;
-        for (int s = 0; s < t; ++s) dq = fmaf(ar[s] * (ps[h * t + s] - dot), ks[s * d + j], dq);
+        for (int s = 0; s < t; ++s) dq = fmaf(ar[s] * ((ps[h * t + s] - c0) - dot), ks[s * d + j], dq);
         row[q * 3 * d + j] = dq * scale;
       }
       for (int s = 0; s < t; ++s) {
-        const float p = ps[h * t + s];
+        const float p = ps[h * t + s] - c0;
         float dkv = 0.f, asum = 0.f;
         for (int q = 0; q < t; ++q) {
           const float a = as[h * tt + q * t + s];
@@ -575,12 +594,12 @@ extern "C" int sagnn_attn_bwd_f32(float* qkv, const float* g_out, int64_t ld_g, 
   if (n < 0 || t < 1 || t > 64 || d < 4 || d > 256 || (d & 3)) return sagnn::fail(SAGNN_ERR_DIM, "bad n/t/d");
   if (heads < 1 || d % heads) return sagnn::fail(SAGNN_ERR_DIM, "heads = %d does not divide d = %d", heads, d);
   const int dk = d / heads;
-  if (dk & (dk - 1)) return sagnn::fail(SAGNN_ERR_DIM, "d_k = %d must be a power of two", dk);
   if (64 % d != 0 && d % 64 != 0) return sagnn::fail(SAGNN_ERR_DIM, "d = %d: need 64 %% d == 0 or d %% 64 == 0", d);
   if (!qkv || !g_out) return sagnn::fail(SAGNN_ERR_NULL, "null tensor pointer");
   if (n == 0) return SAGNN_OK;
   int slots = kBlock / d > 0 ? kBlock / d : 1;
-  const size_t per_slot = (size_t)(3 * t * d + heads * (t * t + 2 * t)) * sizeof(float);
+  // a d_k that is not a power of two keeps g in LDS as well (d floats per slot)
+  const size_t per_slot = (size_t)(3 * t * d + heads * (t * t + 2 * t) + ((dk & (dk - 1)) ? d : 0)) * sizeof(float);
   while (slots > 1 && slots * per_slot > 64 * 1024) slots >>= 1;
   const size_t lds = slots * per_slot;
   if (lds > 160 * 1024) return sagnn::fail(SAGNN_ERR_DIM, "t*d too large for LDS");

@@ -232,16 +232,51 @@ __global__ void hinge_kernel(const float* __restrict__ pos, const float* __restr
   if ((threadIdx.x & 63) == 0 && term != 0.f) atomicAdd(loss, term);
 }
 
-int64_t pair_blocks(int64_t n_pairs, int d) {
-  const int ppw = 64 / (d / 4);
-  const int64_t waves = (n_pairs + ppw - 1) / ppw;
-  return (waves + 3) / 4;
-}
-
-int check_pair_dims(int d) {
+// ---- host-side argument checks: every entry rejects a bad call before any device work ----------------------------
+int check_pair_dims(const char* who, int d) {
   const int lpr = d / 4;
   if (d < 4 || d > 256 || (d & 3) || (lpr & (lpr - 1)))
-    return sagnn::fail(SAGNN_ERR_DIM, "d = %d: need 4 * a power of two, <= 256", d);
+    return sagnn::fail(SAGNN_ERR_DIM, "%s: d = %d: need 4 * a power of two, <= 256", who, d);
+  return SAGNN_OK;
+}
+
+int check_row_dims(const char* who, int d) {
+  if (d < 4 || d > 256 || (d & 3)) return sagnn::fail(SAGNN_ERR_DIM, "%s: d = %d, need a multiple of 4 in [4, 256]", who, d);
+  return SAGNN_OK;
+}
+
+int check_count(const char* who, const char* name, int64_t n) {
+  if (n < 0) return sagnn::fail(SAGNN_ERR_ARG, "%s: negative count (%s = %lld)", who, name, (long long)n);
+  return SAGNN_OK;
+}
+
+// a matrix whose rows the kernels read or write as float4: 16-byte aligned base, stride a multiple of 4 and >= d
+int check_rows(const char* who, int d, int64_t ld, const void* p, const char* name) {
+  if ((ld & 3) || !sagnn::aligned16(p))
+    return sagnn::fail(SAGNN_ERR_ALIGN, "%s: %s must be 16-byte aligned with a stride that is a multiple of 4", who, name);
+  if (ld < d) return sagnn::fail(SAGNN_ERR_ARG, "%s: stride of %s = %lld < d = %d", who, name, (long long)ld, d);
+  return SAGNN_OK;
+}
+
+// blocks for `items` work items at `per_block` each; rc != 0 when one launch cannot hold them
+int blocks_for(const char* who, int64_t items, int per_block, unsigned* out) {
+  const int64_t n = items / per_block + (items % per_block != 0);
+  if (n > INT32_MAX) return sagnn::fail(SAGNN_ERR_ARG, "%s: grid too large (%lld blocks)", who, (long long)n);
+  *out = (unsigned)n;
+  return SAGNN_OK;
+}
+
+// the pair kernels: one wavefront holds ppw = 64 / (d / 4) pairs, four wavefronts per block
+int pair_blocks(const char* who, int64_t n_pairs, int d, unsigned* out) {
+  return blocks_for(who, n_pairs, (kBlock / 64) * (64 / (d / 4)), out);
+}
+
+constexpr int kRowdotMaxK = 8192;   // the backward keeps k + 1 block partials in LDS
+
+int check_rowdot(const char* who, int64_t n, int k, int64_t lda, const char* lda_name) {
+  if (int rc = check_count(who, "n", n)) return rc;
+  if (k < 1 || k > kRowdotMaxK) return sagnn::fail(SAGNN_ERR_ARG, "%s: k = %d, need 1 <= k <= %d", who, k, kRowdotMaxK);
+  if (lda < k) return sagnn::fail(SAGNN_ERR_ARG, "%s: %s = %lld < k = %d", who, lda_name, (long long)lda, k);
   return SAGNN_OK;
 }
 
@@ -252,13 +287,24 @@ extern "C" int sagnn_pair_score_bwd_f32(const float* U, int64_t ldu, const float
                                         const int32_t* iids, const int32_t* locs, float leaky, const float* g,
                                         float* dU, float* dI, float* dS, float* dA, int64_t n_pairs, int d,
                                         void* stream) {
-  if (int rc = check_pair_dims(d)) return rc;
-  if (!U || !I || !uids || !iids || !g || !dU || !dI) return sagnn::fail(SAGNN_ERR_NULL, "null tensor pointer");
-  if (S && (!A || !locs || !dS || !dA)) return sagnn::fail(SAGNN_ERR_NULL, "S needs A, locs, dS, dA");
-  if (n_pairs <= 0) return SAGNN_OK;
-  hipLaunchKernelGGL(pair_score_bwd_kernel, dim3((unsigned)pair_blocks(n_pairs, d)), dim3(kBlock), 0,
-                     static_cast<hipStream_t>(stream), U, ldu, I, ldi, S, lds, A, lda, uids, iids, locs, leaky, g, dU,
-                     dI, dS, dA, n_pairs, d);
+  const char* who = "pair_score_bwd";
+  if (!U || !I || !uids || !iids || !g || !dU || !dI)
+    return sagnn::fail(SAGNN_ERR_NULL, "%s: null pointer (U, I, uids, iids, g, dU, dI)", who);
+  if (!S != !A || !S != !locs || !S != !dS || !S != !dA)
+    return sagnn::fail(SAGNN_ERR_NULL, "%s: S, A, locs, dS and dA go together (all or none)", who);
+  if (int rc = check_pair_dims(who, d)) return rc;
+  if (int rc = check_count(who, "n_pairs", n_pairs)) return rc;
+  if (int rc = check_rows(who, d, ldu, U, "U")) return rc;
+  if (int rc = check_rows(who, d, ldi, I, "I")) return rc;
+  if (S) {
+    if (int rc = check_rows(who, d, lds, S, "S")) return rc;
+    if (int rc = check_rows(who, d, lda, A, "A")) return rc;
+  }
+  unsigned blocks = 0;
+  if (int rc = pair_blocks(who, n_pairs, d, &blocks)) return rc;
+  if (blocks == 0) return SAGNN_OK;
+  hipLaunchKernelGGL(pair_score_bwd_kernel, dim3(blocks), dim3(kBlock), 0, static_cast<hipStream_t>(stream), U, ldu, I,
+                     ldi, S, lds, A, lda, uids, iids, locs, leaky, g, dU, dI, dS, dA, n_pairs, d);
   SAGNN_HIP_TRY(hipGetLastError());
   return SAGNN_OK;
 }
@@ -266,11 +312,17 @@ extern "C" int sagnn_pair_score_bwd_f32(const float* U, int64_t ldu, const float
 extern "C" int sagnn_prod_leaky_sum_f32(const float* X, int64_t ldx, const float* Y, int64_t ldy,
                                         const int32_t* uids, const int32_t* iids, float leaky, float* out,
                                         int64_t n_pairs, int d, void* stream) {
-  if (int rc = check_pair_dims(d)) return rc;
-  if (!X || !Y || !uids || !iids || !out) return sagnn::fail(SAGNN_ERR_NULL, "null tensor pointer");
-  if (n_pairs <= 0) return SAGNN_OK;
-  hipLaunchKernelGGL(prod_leaky_sum_kernel, dim3((unsigned)pair_blocks(n_pairs, d)), dim3(kBlock), 0,
-                     static_cast<hipStream_t>(stream), X, ldx, Y, ldy, uids, iids, leaky, out, n_pairs, d);
+  const char* who = "prod_leaky_sum";
+  if (!X || !Y || !uids || !iids || !out) return sagnn::fail(SAGNN_ERR_NULL, "%s: null pointer (X, Y, uids, iids, out)", who);
+  if (int rc = check_pair_dims(who, d)) return rc;
+  if (int rc = check_count(who, "n_pairs", n_pairs)) return rc;
+  if (int rc = check_rows(who, d, ldx, X, "X")) return rc;
+  if (int rc = check_rows(who, d, ldy, Y, "Y")) return rc;
+  unsigned blocks = 0;
+  if (int rc = pair_blocks(who, n_pairs, d, &blocks)) return rc;
+  if (blocks == 0) return SAGNN_OK;
+  hipLaunchKernelGGL(prod_leaky_sum_kernel, dim3(blocks), dim3(kBlock), 0, static_cast<hipStream_t>(stream), X, ldx, Y,
+                     ldy, uids, iids, leaky, out, n_pairs, d);
   SAGNN_HIP_TRY(hipGetLastError());
   return SAGNN_OK;
 }
@@ -278,23 +330,36 @@ extern "C" int sagnn_prod_leaky_sum_f32(const float* X, int64_t ldx, const float
 extern "C" int sagnn_prod_leaky_sum_bwd_f32(const float* X, int64_t ldx, const float* Y, int64_t ldy,
                                             const int32_t* uids, const int32_t* iids, float leaky, const float* g,
                                             float* dX, float* dY, int64_t n_pairs, int d, void* stream) {
-  if (int rc = check_pair_dims(d)) return rc;
-  if (!X || !Y || !uids || !iids || !g || !dX || !dY) return sagnn::fail(SAGNN_ERR_NULL, "null tensor pointer");
-  if (n_pairs <= 0) return SAGNN_OK;
-  hipLaunchKernelGGL(prod_leaky_sum_bwd_kernel, dim3((unsigned)pair_blocks(n_pairs, d)), dim3(kBlock), 0,
-                     static_cast<hipStream_t>(stream), X, ldx, Y, ldy, uids, iids, leaky, g, dX, dY, n_pairs, d);
+  const char* who = "prod_leaky_sum_bwd";
+  if (!X || !Y || !uids || !iids || !g || !dX || !dY)
+    return sagnn::fail(SAGNN_ERR_NULL, "%s: null pointer (X, Y, uids, iids, g, dX, dY)", who);
+  if (int rc = check_pair_dims(who, d)) return rc;
+  if (int rc = check_count(who, "n_pairs", n_pairs)) return rc;
+  if (int rc = check_rows(who, d, ldx, X, "X")) return rc;
+  if (int rc = check_rows(who, d, ldy, Y, "Y")) return rc;
+  unsigned blocks = 0;
+  if (int rc = pair_blocks(who, n_pairs, d, &blocks)) return rc;
+  if (blocks == 0) return SAGNN_OK;
+  hipLaunchKernelGGL(prod_leaky_sum_bwd_kernel, dim3(blocks), dim3(kBlock), 0, static_cast<hipStream_t>(stream), X, ldx,
+                     Y, ldy, uids, iids, leaky, g, dX, dY, n_pairs, d);
   SAGNN_HIP_TRY(hipGetLastError());
   return SAGNN_OK;
 }
 
 extern "C" int sagnn_meta_features_f32(const float* F, int64_t ldf, const float* V, int64_t ldv, const int32_t* uids,
                                        float* out, int64_t n, int d, void* stream) {
-  if (d < 4 || (d & 3)) return sagnn::fail(SAGNN_ERR_DIM, "d = %d", d);
-  if (!F || !V || !uids || !out) return sagnn::fail(SAGNN_ERR_NULL, "null tensor pointer");
-  if (n <= 0) return SAGNN_OK;
-  const int64_t total = n * (d / 4);
-  hipLaunchKernelGGL(meta_features_kernel, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                     static_cast<hipStream_t>(stream), F, ldf, V, ldv, uids, out, n, d);
+  const char* who = "meta_features";
+  if (!F || !V || !uids || !out) return sagnn::fail(SAGNN_ERR_NULL, "%s: null pointer (F, V, uids, out)", who);
+  if (int rc = check_row_dims(who, d)) return rc;
+  if (int rc = check_count(who, "n", n)) return rc;
+  if (int rc = check_rows(who, d, ldf, F, "F")) return rc;
+  if (int rc = check_rows(who, d, ldv, V, "V")) return rc;
+  if (int rc = check_rows(who, d, 3 * (int64_t)d, out, "out")) return rc;
+  unsigned blocks = 0;
+  if (int rc = blocks_for(who, n * (d / 4), kBlock, &blocks)) return rc;
+  if (blocks == 0) return SAGNN_OK;
+  hipLaunchKernelGGL(meta_features_kernel, dim3(blocks), dim3(kBlock), 0, static_cast<hipStream_t>(stream), F, ldf, V,
+                     ldv, uids, out, n, d);
   SAGNN_HIP_TRY(hipGetLastError());
   return SAGNN_OK;
 }
@@ -302,32 +367,47 @@ extern "C" int sagnn_meta_features_f32(const float* F, int64_t ldf, const float*
 extern "C" int sagnn_meta_features_bwd_f32(const float* F, int64_t ldf, const float* V, int64_t ldv,
                                            const int32_t* uids, const float* dm, float* dF, float* dV, int64_t n,
                                            int d, void* stream) {
-  if (d < 4 || (d & 3)) return sagnn::fail(SAGNN_ERR_DIM, "d = %d", d);
-  if (!F || !V || !uids || !dm || !dF || !dV) return sagnn::fail(SAGNN_ERR_NULL, "null tensor pointer");
-  if (n <= 0) return SAGNN_OK;
-  const int64_t total = n * (d / 4);
-  hipLaunchKernelGGL(meta_features_bwd_kernel, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                     static_cast<hipStream_t>(stream), F, ldf, V, ldv, uids, dm, dF, dV, n, d);
+  const char* who = "meta_features_bwd";
+  if (!F || !V || !uids || !dm || !dF || !dV)
+    return sagnn::fail(SAGNN_ERR_NULL, "%s: null pointer (F, V, uids, dm, dF, dV)", who);
+  if (int rc = check_row_dims(who, d)) return rc;
+  if (int rc = check_count(who, "n", n)) return rc;
+  if (int rc = check_rows(who, d, ldf, F, "F")) return rc;
+  if (int rc = check_rows(who, d, ldv, V, "V")) return rc;
+  if (int rc = check_rows(who, d, 3 * (int64_t)d, dm, "dm")) return rc;
+  unsigned blocks = 0;
+  if (int rc = blocks_for(who, n * (d / 4), kBlock, &blocks)) return rc;
+  if (blocks == 0) return SAGNN_OK;
+  hipLaunchKernelGGL(meta_features_bwd_kernel, dim3(blocks), dim3(kBlock), 0, static_cast<hipStream_t>(stream), F, ldf,
+                     V, ldv, uids, dm, dF, dV, n, d);
   SAGNN_HIP_TRY(hipGetLastError());
   return SAGNN_OK;
 }
 
 extern "C" int sagnn_leaky_f32(const float* a, const float* g, float* out, float leaky, int64_t count, int backward,
                                void* stream) {
-  if (!a || !out || (backward && !g)) return sagnn::fail(SAGNN_ERR_NULL, "null tensor pointer");
-  if (count <= 0) return SAGNN_OK;
-  hipLaunchKernelGGL(leaky_kernel, dim3((unsigned)((count + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                     static_cast<hipStream_t>(stream), a, g, out, leaky, count, backward ? 1 : 0);
+  const char* who = "leaky";
+  if (!a || !out || (backward && !g)) return sagnn::fail(SAGNN_ERR_NULL, "%s: null pointer (a, out; g when backward)", who);
+  if (int rc = check_count(who, "count", count)) return rc;
+  unsigned blocks = 0;
+  if (int rc = blocks_for(who, count, kBlock, &blocks)) return rc;
+  if (blocks == 0) return SAGNN_OK;
+  hipLaunchKernelGGL(leaky_kernel, dim3(blocks), dim3(kBlock), 0, static_cast<hipStream_t>(stream), a, g, out, leaky,
+                     count, backward ? 1 : 0);
   SAGNN_HIP_TRY(hipGetLastError());
   return SAGNN_OK;
 }
 
 extern "C" int sagnn_rowdot_sigmoid_f32(const float* A, int64_t lda, const float* w3, const float* b3, float* out,
                                         int64_t n, int k, void* stream) {
-  if (!A || !w3 || !b3 || !out) return sagnn::fail(SAGNN_ERR_NULL, "null tensor pointer");
-  if (n <= 0) return SAGNN_OK;
-  hipLaunchKernelGGL(rowdot_sigmoid_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                     static_cast<hipStream_t>(stream), A, lda, w3, b3, out, n, k);
+  const char* who = "rowdot_sigmoid";
+  if (!A || !w3 || !b3 || !out) return sagnn::fail(SAGNN_ERR_NULL, "%s: null pointer (A, w3, b3, out)", who);
+  if (int rc = check_rowdot(who, n, k, lda, "lda")) return rc;
+  unsigned blocks = 0;
+  if (int rc = blocks_for(who, n, kBlock, &blocks)) return rc;
+  if (blocks == 0) return SAGNN_OK;
+  hipLaunchKernelGGL(rowdot_sigmoid_kernel, dim3(blocks), dim3(kBlock), 0, static_cast<hipStream_t>(stream), A, lda, w3,
+                     b3, out, n, k);
   SAGNN_HIP_TRY(hipGetLastError());
   return SAGNN_OK;
 }
@@ -335,11 +415,16 @@ extern "C" int sagnn_rowdot_sigmoid_f32(const float* A, int64_t lda, const float
 extern "C" int sagnn_rowdot_sigmoid_bwd_f32(const float* A, int64_t lda, const float* w3, const float* w,
                                             const float* dw, float* dA, int64_t ldda, float* dw3, float* db3,
                                             int64_t n, int k, void* stream) {
-  if (!A || !w3 || !w || !dw || !dA || !dw3 || !db3) return sagnn::fail(SAGNN_ERR_NULL, "null tensor pointer");
-  if (n <= 0) return SAGNN_OK;
-  hipLaunchKernelGGL(rowdot_sigmoid_bwd_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock),
-                     (size_t)(k + 1) * sizeof(float), static_cast<hipStream_t>(stream), A, lda, w3, w, dw, dA, ldda,
-                     dw3, db3, n, k);
+  const char* who = "rowdot_sigmoid_bwd";
+  if (!A || !w3 || !w || !dw || !dA || !dw3 || !db3)
+    return sagnn::fail(SAGNN_ERR_NULL, "%s: null pointer (A, w3, w, dw, dA, dw3, db3)", who);
+  if (int rc = check_rowdot(who, n, k, lda, "lda")) return rc;
+  if (ldda < k) return sagnn::fail(SAGNN_ERR_ARG, "%s: ldda = %lld < k = %d", who, (long long)ldda, k);
+  unsigned blocks = 0;
+  if (int rc = blocks_for(who, n, kBlock, &blocks)) return rc;
+  if (blocks == 0) return SAGNN_OK;
+  hipLaunchKernelGGL(rowdot_sigmoid_bwd_kernel, dim3(blocks), dim3(kBlock), (size_t)(k + 1) * sizeof(float),
+                     static_cast<hipStream_t>(stream), A, lda, w3, w, dw, dA, ldda, dw3, db3, n, k);
   SAGNN_HIP_TRY(hipGetLastError());
   return SAGNN_OK;
 }
@@ -347,11 +432,19 @@ extern "C" int sagnn_rowdot_sigmoid_bwd_f32(const float* A, int64_t lda, const f
 extern "C" int sagnn_hinge_f32(const float* pos, const float* neg, const float* wp, const float* wn, const float* sp,
                                const float* sn, float scale, float* loss, float* dpos, float* dneg, float* dwp,
                                float* dwn, int64_t n, void* stream) {
-  if (!pos || !neg || !loss) return sagnn::fail(SAGNN_ERR_NULL, "null tensor pointer");
-  if (wp && (!wn || !sp || !sn)) return sagnn::fail(SAGNN_ERR_NULL, "weighted hinge needs wn, sp, sn");
-  if (n <= 0) return SAGNN_OK;
-  hipLaunchKernelGGL(hinge_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                     static_cast<hipStream_t>(stream), pos, neg, wp, wn, sp, sn, scale, loss, dpos, dneg, dwp, dwn, n);
+  const char* who = "hinge";
+  if (!pos || !neg || !loss) return sagnn::fail(SAGNN_ERR_NULL, "%s: null pointer (pos, neg, loss)", who);
+  if (!wp != !wn || !wp != !sp || !wp != !sn)
+    return sagnn::fail(SAGNN_ERR_NULL, "%s: wp, wn, sp and sn go together (all or none)", who);
+  if (!dpos != !dneg) return sagnn::fail(SAGNN_ERR_NULL, "%s: dpos and dneg go together (both or neither)", who);
+  if (!dwp != !dwn) return sagnn::fail(SAGNN_ERR_NULL, "%s: dwp and dwn go together (both or neither)", who);
+  if (dwp && !wp) return sagnn::fail(SAGNN_ERR_ARG, "%s: dwp / dwn given without wp (the plain form has no weights)", who);
+  if (int rc = check_count(who, "n", n)) return rc;
+  unsigned blocks = 0;
+  if (int rc = blocks_for(who, n, kBlock, &blocks)) return rc;
+  if (blocks == 0) return SAGNN_OK;
+  hipLaunchKernelGGL(hinge_kernel, dim3(blocks), dim3(kBlock), 0, static_cast<hipStream_t>(stream), pos, neg, wp, wn, sp,
+                     sn, scale, loss, dpos, dneg, dwp, dwn, n);
   SAGNN_HIP_TRY(hipGetLastError());
   return SAGNN_OK;
 }

@@ -72,13 +72,31 @@ def test_autograd_function_end_to_end(dev):
     np.testing.assert_allclose(pi.grad.cpu().numpy(), ti.grad.numpy(), rtol=2e-4, atol=1e-5 * s)
 
 
+# Shapes whose backward takes the generic entries: no fused attention-backward front (t or d_k outside its table, or
+# d > 128), and beyond d = 64 neither the fused tail nor the one-launch BPTT. d = 192 with 16 heads has d_k = 12.
+GENERIC_ROUTE = {(256, 3, 90, 16), (256, 12, 19, 16), (192, 4, 61, 16), (128, 8, 41, 16), (128, 20, 17, 16), (64, 7, 53, 16),
+                 (64, 10, 37, 16), (64, 20, 23, 16), (32, 7, 45, 8), (64, 3, 300, 8)}
+
+
 @pytest.mark.parametrize("d,t,n,heads", [(64, 3, 300, 16), (32, 2, 130, 16), (64, 1, 70, 16), (64, 5, 97, 4), (128, 3, 90, 16),
                                           (64, 8, 41, 16), (32, 6, 53, 16), (64, 12, 19, 16), (64, 16, 23, 16), (32, 12, 31, 16), (32, 16, 17, 16),
                                           (64, 2, 1000, 16), (64, 4, 77, 16), (64, 5, 61, 16), (64, 6, 37, 16),
-                                          (32, 1, 33, 16), (32, 3, 90, 16), (32, 4, 70, 16), (32, 5, 45, 16), (32, 8, 29, 16)])
+                                          (32, 1, 33, 16), (32, 3, 90, 16), (32, 4, 70, 16), (32, 5, 45, 16), (32, 8, 29, 16)]
+                         + sorted(GENERIC_ROUTE, reverse=True))
 def test_interval_fusion_backward_vs_autograd(dev, d, t, n, heads):
-    """Every gradient of the fusion (x and all ten parameter tensors) against float64 autograd."""
+    """Every gradient of the fusion (x and all ten parameter tensors) against float64 autograd. The shapes of
+    GENERIC_ROUTE must run the generic entries (test ids: "generic" selects the per-kernel tests below, these cases
+    assert their route here)."""
+    from sa_gnn_amd import _lib
     from sa_gnn_amd import autograd as ag
+    if (d, t, n, heads) in GENERIC_ROUTE:
+        lib = _lib.load()
+        # the backward runs on PyTorch's autograd thread, whose engine is the default one, as this thread's is
+        assert ag.FUSED_ATTN_BWD and ag.FUSED_BPTT and lib.sagnn_get_engine() == 0
+        assert not lib.sagnn_attn_bwd_front_supported(d, t, heads), "layernorm_td + dense_nn + sagnn_attn_bwd_f32 must run"
+        if d > 64:
+            assert not lib.sagnn_attn_bwd_tail_supported(d), "dense_tn + dense_nn must run"
+            assert not lib.sagnn_lstm_bwd_supported(d), "the sagnn_lstm_bwd_step_f32 loop must run"
     rng = np.random.default_rng(d + t + n)
     x = rng.standard_normal((n, t, d)).astype(np.float32)
     p = O.init_fusion_params(d, rng)
@@ -109,6 +127,216 @@ def test_interval_fusion_backward_vs_autograd(dev, d, t, n, heads):
     check("dx", xd.grad, tx.grad)
     for k in p:
         check("d" + k, pd[k].grad, tp[k].grad)
+
+
+@pytest.mark.parametrize("d,t,n,heads", [(64, 3, 300, 16), (32, 4, 70, 16)])
+def test_interval_fusion_backward_generic_under_valu(dev, d, t, n, heads):
+    """Under the VALU engine the attention backward has no fused kernels at any shape: layernorm_td + dense_nn +
+    sagnn_attn_bwd_f32, then dense_tn / dense_nn. The engine is per calling thread and torch runs a backward on a
+    thread of its own, so the two halves are called here directly, on the thread that selected the engine."""
+    from sa_gnn_amd import _lib, ops
+    from sa_gnn_amd import autograd as ag
+    rng = np.random.default_rng(d + t + n)
+    x = rng.standard_normal((n, t, d)).astype(np.float32)
+    p = O.init_fusion_params(d, rng)
+    gout = rng.standard_normal((n, d)).astype(np.float32)
+    tx = torch.tensor(x, dtype=torch.float64, requires_grad=True)
+    tp = {k: torch.tensor(v, dtype=torch.float64, requires_grad=True) for k, v in p.items()}
+    out = O.torch_interval_fusion(tx, tp, heads)
+    (out * torch.tensor(gout, dtype=torch.float64)).sum().backward()
+    xd = torch.from_numpy(np.ascontiguousarray(x.transpose(1, 0, 2))).to(dev).permute(1, 0, 2)
+    pd = {k: torch.from_numpy(v).to(dev) for k, v in p.items()}
+    names = ("lstm_W", "lstm_b", "ln_gamma", "ln_beta", "Wq", "bq", "Wk", "bk", "Wv", "bv")
+    with ops.engine("valu"):
+        lib = _lib.load()
+        assert not lib.sagnn_attn_bwd_front_supported(d, t, heads) and not lib.sagnn_attn_bwd_tail_supported(d)
+        got, h, gates, cell = ag._fusion_forward(xd, *(pd[k] for k in names), heads, None)
+        grads = ag._fusion_backward(xd, *(pd[k] for k in names if k != "lstm_b"), h, gates, cell, None, heads,
+                                    torch.from_numpy(gout).to(dev))
+    assert ops.get_engine() == "f16x2"
+    np.testing.assert_allclose(got.cpu().numpy(), out.detach().numpy(), rtol=1e-4, atol=2e-5)
+    for name, a, b in [("dx", grads[0], tx.grad)] + [("d" + k, g, tp[k].grad) for k, g in zip(names, grads[1:])]:
+        a, b = a.cpu().numpy().astype(np.float64), b.numpy()
+        tol = 1e-4 * np.abs(b) + max(2e-5 * np.abs(b).max(), 8e-6 * max(1.0, np.sqrt(n * t / 1000.0)))   # the rule of the test above
+        bad = np.abs(a - b) > tol
+        assert not bad.any(), f"{name}: {bad.sum()}/{bad.size} off, worst {np.abs(a - b)[bad].max():.3e} (scale {np.abs(b).max():.3e})"
+
+
+# ---- the generic backward entries, one kernel at a time ----------------------------------------------------------------
+# Tolerance: |got - want| <= 1e-4 |want| + 2e-5 max |want| (the rule of the composite test without its floor); the
+# atomically accumulated dgamma / dbeta add the eps32 * sqrt(n * t) floor that test documents.
+
+def _close(name, got, want, floor=0.0):
+    a, b = got.detach().double().cpu().numpy().reshape(want.shape), want.detach().numpy()
+    assert np.isfinite(a).all(), f"{name}: non-finite"
+    tol = 1e-4 * np.abs(b) + 2e-5 * np.abs(b).max() + floor
+    bad = np.abs(a - b) > tol
+    assert not bad.any(), f"{name}: {bad.sum()}/{bad.size} off, worst {np.abs(a - b)[bad].max():.3e} (scale {np.abs(b).max():.3e})"
+
+
+# (d, t, extra node stride). Vector kernel: d a power of two, t * d <= 2048, 16-byte rows. Scalar kernel: the rest.
+LN_VECTOR = [(64, 3, 0), (32, 1, 0), (128, 16, 0)]
+LN_SCALAR = [(192, 3, 0), (128, 20, 0), (256, 12, 0), (64, 33, 0), (64, 3, 2)]
+
+
+def _ln_cases():
+    # n = 20011 (more nodes than the persistent grid has waves) where n * t * d stays near 1e7
+    return [(d, t, x, n) for d, t, x in LN_VECTOR + LN_SCALAR for n in (1, 5, 4099, 20011) if n < 20011 or t * d <= 576]
+
+
+@pytest.mark.parametrize("d,t,extra,n", _ln_cases())
+def test_generic_layernorm_td_bwd(dev, d, t, extra, n):
+    """sagnn_layernorm_td_bwd_f32 alone against float64 autograd of O.torch_layer_norm_td, out of place and with dh
+    aliasing dy. A node stride of t * d + 2 is legal for the scalar kernel only."""
+    from sa_gnn_amd import _lib, ops
+    lib = _lib.load()
+    rng = np.random.default_rng(d * t + n)
+    ld = t * d + extra
+    h = (rng.standard_normal((n, t, d)) * 1.5 + 0.3).astype(np.float32)
+    dy = rng.standard_normal((n, t, d)).astype(np.float32)
+    gamma = (1.0 + 0.1 * rng.standard_normal(d)).astype(np.float32)
+    th, tg = (torch.tensor(v, dtype=torch.float64, requires_grad=True) for v in (h, gamma))
+    tb = torch.zeros(d, dtype=torch.float64, requires_grad=True)
+    (O.torch_layer_norm_td(th, tg, tb) * torch.tensor(dy, dtype=torch.float64)).sum().backward()
+
+    def slab(v):
+        buf = torch.full((n, ld), float("nan"), dtype=torch.float32, device=dev)
+        buf[:, :t * d] = torch.from_numpy(v.reshape(n, t * d)).to(dev)
+        return buf
+    hd, dyd, gd = slab(h), slab(dy), torch.from_numpy(gamma).to(dev)
+    floor = float(np.finfo(np.float32).eps) * np.sqrt(n * t)
+    for alias in (False, True):
+        dh = dyd if alias else torch.full((n, ld), float("nan"), dtype=torch.float32, device=dev)
+        dgamma, dbeta = torch.zeros(d, device=dev), torch.zeros(d, device=dev)
+        ops.check(lib.sagnn_layernorm_td_bwd_f32(hd.data_ptr(), ld, dyd.data_ptr(), ld, n, t, d, gd.data_ptr(), 1e-12,
+                                                 dh.data_ptr(), ld, dgamma.data_ptr(), dbeta.data_ptr(), ops._stream()))
+        _close("dh", dh[:, :t * d], th.grad.reshape(n, t * d))
+        _close("dgamma", dgamma, tg.grad, floor)
+        _close("dbeta", dbeta, tb.grad, floor)
+        assert extra == 0 or bool(torch.isnan(dh[:, t * d:]).all())            # the gap between nodes is not written
+
+
+def _attn_slots(d, heads, t):
+    """Nodes per block of sagnn_attn_bwd_f32: 256 / d, halved until their LDS (Q|K|V, the score tiles, g where d_k is
+    not a power of two) fits 64 KiB."""
+    dk = d // heads
+    per_slot = 4 * (3 * t * d + heads * (t * t + 2 * t) + (d if dk & (dk - 1) else 0))
+    slots = max(256 // d, 1)
+    while slots > 1 and slots * per_slot > 64 * 1024:
+        slots >>= 1
+    assert slots * per_slot <= 160 * 1024
+    return slots
+
+
+# (d, heads, t): every d, every d_k of {1, 2, 4, 16} at every d, every t; d = 192 / 16 heads is d_k = 12
+ATTN_SHAPES = [(16, 16, 1), (16, 8, 7), (16, 4, 32), (16, 1, 10), (16, 16, 20), (16, 8, 2),
+               (32, 32, 2), (32, 16, 10), (32, 8, 20), (32, 2, 7), (32, 8, 32), (32, 16, 1),
+               (64, 64, 7), (64, 32, 1), (64, 16, 20), (64, 4, 32), (64, 16, 2), (64, 16, 10),
+               (128, 128, 2), (128, 64, 10), (128, 32, 7), (128, 8, 32), (128, 32, 20), (128, 8, 1),
+               (192, 48, 1), (192, 12, 7), (192, 96, 2), (192, 192, 10), (192, 12, 20), (192, 12, 32), (192, 16, 4),
+               (256, 256, 1), (256, 128, 2), (256, 64, 7), (256, 16, 10), (256, 16, 20), (256, 16, 12)]     # d = 256 at t = 32 is beyond the entry's LDS limit
+
+
+def _attn_cases():
+    out = []
+    for d, heads, t in ATTN_SHAPES:
+        slots = _attn_slots(d, heads, t)
+        ns = {1, slots - 1, slots + 1}
+        if t * d <= 256:               # n * t * 3d near 1e7; at d >= 192 (one node per block) the 16 384-block cap bites
+            ns.add(20011)
+        out += [(d, heads, t, n) for n in sorted(ns) if n > 0]
+    return out
+
+
+def _attn_mean(q, k, v, heads):
+    """O.torch_mhsa_mean from its Q, K, V on (Utils/attention.py:35-45, :74-78, model.py:154-155)."""
+    n, t, d = q.shape
+    dk = d // heads
+    q, k, v = (z.reshape(n, t, heads, dk).permute(0, 2, 1, 3) for z in (q, k, v))
+    scores = torch.exp((q @ k.transpose(-1, -2)) / float(np.sqrt(dk)))
+    attn = scores / (scores.sum(dim=-1, keepdim=True) + 1e-8)
+    return (attn @ v).permute(0, 2, 1, 3).reshape(n, t, d).mean(dim=1)
+
+
+def test_generic_attn_mean_is_the_oracle():
+    """_attn_mean above IS O.torch_mhsa_mean once Q, K, V are formed (a CPU check of the test's own reference)."""
+    rng = np.random.default_rng(4)
+    x = torch.tensor(rng.standard_normal((5, 3, 32)))
+    p = {k: torch.tensor(v, dtype=torch.float64) for k, v in O.init_fusion_params(32, rng).items()}
+    want = O.torch_mhsa_mean(x, p["Wq"], p["bq"], p["Wk"], p["bk"], p["Wv"], p["bv"], 8)
+    got = _attn_mean(x @ p["Wq"] + p["bq"], x @ p["Wk"] + p["bk"], x @ p["Wv"] + p["bv"], 8)
+    assert torch.equal(got, want)
+
+
+@pytest.mark.parametrize("d,heads,t,n", _attn_cases())
+def test_generic_attn_bwd_f32(dev, d, heads, t, n):
+    """sagnn_attn_bwd_f32 alone: Q|K|V [n, t, 3d] -> dQ|dK|dV in place against float64 autograd of the attention +
+    mean on the same Q, K, V; g_out is a row view of a wider slab."""
+    from sa_gnn_amd import _lib, ops
+    lib = _lib.load()
+    rng = np.random.default_rng(d * 100 + t * 7 + heads)
+    qkv = (rng.standard_normal((n, t, 3 * d)) * 0.7).astype(np.float32)
+    g = rng.standard_normal((n, d)).astype(np.float32)
+    tq = torch.tensor(qkv, dtype=torch.float64, requires_grad=True)
+    out = _attn_mean(tq[:, :, :d], tq[:, :, d:2 * d], tq[:, :, 2 * d:], heads)
+    (out * torch.tensor(g, dtype=torch.float64)).sum().backward()
+    qd = torch.from_numpy(qkv).to(dev)
+    gslab = torch.full((n, 2 * d), float("nan"), dtype=torch.float32, device=dev)
+    gslab[:, d:] = torch.from_numpy(g).to(dev)
+    ops.check(lib.sagnn_attn_bwd_f32(qd.data_ptr(), gslab[:, d:].data_ptr(), 2 * d, n, t, d, heads, ops._stream()))
+    for i, name in enumerate(("dQ", "dK", "dV")):
+        _close(name, qd[:, :, i * d:(i + 1) * d].contiguous(), tq.grad[:, :, i * d:(i + 1) * d])
+
+
+@pytest.mark.parametrize("d", (32, 96, 256))
+@pytest.mark.parametrize("ts", (0, 2, 4))
+@pytest.mark.parametrize("drop", (False, True))
+def test_generic_lstm_bwd_step(dev, d, ts, drop):
+    """sagnn_lstm_bwd_step_f32 alone, t = 5: the first step (no previous cell), a middle one, and the last (dh_rec and
+    dc_in NULL), against float64 autograd of one step of O.torch_basic_lstm from its gate pre-activations:
+    c = c_prev sigmoid(f + 1) + sigmoid(i) tanh(j), h = tanh(c) sigmoid(o), loss = <dh, h> + <dc_in, c>."""
+    from sa_gnn_amd import _lib, ops
+    lib = _lib.load()
+    n, t = 257, 5
+    last = ts == t - 1
+    rng = np.random.default_rng(d + ts + 10 * drop)
+    G = torch.tensor(rng.standard_normal((n, 4 * d)), dtype=torch.float64, requires_grad=True)
+    cp = torch.tensor(rng.standard_normal((n, d)) if ts > 0 else np.zeros((n, d)), dtype=torch.float64, requires_grad=True)
+    gi, gj, gf, go = torch.split(G, d, dim=1)
+    acts = (torch.sigmoid(gi), torch.tanh(gj), torch.sigmoid(gf + 1.0), torch.sigmoid(go))
+    c = cp * acts[2] + acts[0] * acts[1]
+    hh = torch.tanh(c) * acts[3]
+    dh_ext = rng.standard_normal((n, t, d)).astype(np.float32)
+    scale = ((rng.random((n, t, d)) < 0.5) * 2.0).astype(np.float32)
+    dh_rec = rng.standard_normal((n, d)).astype(np.float32)
+    dc_in = rng.standard_normal((n, d)).astype(np.float32)
+    dh = torch.tensor(dh_ext[:, ts], dtype=torch.float64)
+    if drop:
+        dh = dh * torch.tensor(scale[:, ts], dtype=torch.float64)
+    if not last:
+        dh = dh + torch.tensor(dh_rec, dtype=torch.float64)
+    loss = (hh * dh).sum()
+    if not last:
+        loss = loss + (c * torch.tensor(dc_in, dtype=torch.float64)).sum()
+    loss.backward()
+    # what the training forward stores: activations [n, t, 4d] and cell states [n, t, d]; the other steps hold noise
+    gates = rng.standard_normal((n, t, 4 * d)).astype(np.float32)
+    cell = rng.standard_normal((n, t, d)).astype(np.float32)
+    gates[:, ts] = torch.cat(acts, dim=1).detach().numpy().astype(np.float32)
+    cell[:, ts] = c.detach().numpy().astype(np.float32)
+    if ts > 0:
+        cell[:, ts - 1] = cp.detach().numpy().astype(np.float32)
+    to = lambda v: torch.from_numpy(np.ascontiguousarray(v)).to(dev)   # noqa: E731
+    gd, cd, dhd, sd, dcd = to(gates), to(cell), to(dh_ext), to(scale), to(dc_in)
+    rec = torch.full((n, 2 * d), float("nan"), dtype=torch.float32, device=dev)      # [dx | dh_rec] rows, as the host keeps them
+    rec[:, d:] = to(dh_rec)
+    dgates = torch.full((n, 4 * d), float("nan"), dtype=torch.float32, device=dev)
+    dc_out = torch.full((n, d), float("nan"), dtype=torch.float32, device=dev)
+    ops.check(lib.sagnn_lstm_bwd_step_f32(gd.data_ptr(), cd.data_ptr(), dhd.data_ptr(), t * d, sd.data_ptr() if drop else None,
+                                          None if last else rec[:, d:].data_ptr(), 2 * d, None if last else dcd.data_ptr(),
+                                          dgates.data_ptr(), dc_out.data_ptr(), n, t, d, ts, ops._stream()))
+    _close("dgates", dgates, G.grad)
+    _close("dc_out", dc_out, cp.grad)
 
 
 def test_interval_fusion_backward_with_output_dropout(dev):
