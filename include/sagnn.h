@@ -343,7 +343,10 @@ int sagnn_mhsa_mean_wide_f32(const float* x, int64_t ld_n, int64_t ld_t, int64_t
 /* layer_norm over (T, d) + attention + mean without the LSTM (model.py:152-155): what the
  * training forward calls after sagnn_lstm_fwd_train_f32. Workspace (bytes from
  * sagnn_ln_mhsa_mean_workspace_bytes, 0 on the fused matrix-core path) holds the normalised
- * tensor where the normalisation cannot ride on the attention kernel's operand. */
+ * tensor where the normalisation cannot ride on the attention kernel's operand. The query assumes
+ * aligned x (base 16-byte aligned, ld_n and ld_t multiples of 4). An unaligned x never runs fused: its caller
+ * reserves n*t*d*4 + sagnn_mhsa_wide_workspace_bytes(n, t, d) bytes, enough for either unfused kernel
+ * (SAGNN_ERR_WORKSPACE with less than the kernel taken needs). */
 size_t sagnn_ln_mhsa_mean_workspace_bytes(int64_t n, int t, int d, int heads);
 int sagnn_ln_mhsa_mean_f32(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int d, int heads,
                            const float* ln_gamma, const float* ln_beta, float ln_eps, const float* Wq,

@@ -1,14 +1,15 @@
 // Kernel selection of the fusion stages (engine.h). Every decision about which kernel a fusion call runs is made here.
 //
 // Rows are tried top to bottom; the first that holds is taken. "vec": x 16-byte aligned, ld_n and ld_t multiples of 4
-// (and h_init likewise where given). Engine "any" includes VALU unless the row says otherwise.
+// (and h_init likewise where given). "h aligned": h 16-byte aligned and ld_h a multiple of 4. Engine "any" includes VALU
+// unless the row says otherwise.
 //
 // stage (entries)                   engine     taken when                                                  runs
 // ---------------------------------------------------------------------------------------------------------------------
 // LSTM fwd (lstm_fwd, _state,       valu       always                                                      Valu
-//   _train, interval_fusion)        f16x2      d in {32, 64}, vec, ld_h < 2^22, t*d < 2^18,                F16x2
+//   _train, interval_fusion)        f16x2      d in {32, 64}, vec, h aligned, ld_h < 2^22, t*d < 2^18,     F16x2
 //                                                not (training and a mask): inference takes the mask
-//                                   f32,f16x2  d in {32, 64}, vec                                          F32Mfma
+//                                   f32,f16x2  d in {32, 64}, vec, h aligned                               F32Mfma
 //                                   f16x2      d = 128, vec, ld_h % 4 = 0, h aligned; inference: no mask;   Split128
 //                                                training: mask absent or aligned
 //                                   any        otherwise                                                   Valu
@@ -28,8 +29,9 @@
 //
 // (*) sagnn_mhsa_mean_f32 has no workspace and runs Valu instead. interval_fusion passes vec = true: its h is workspace.
 // Workspace queries: sagnn_ln_mhsa_mean_workspace_bytes reserves nothing for Split / F32Mfma (vec assumed), y for
-// Valu, y + Q|K|V for Wide. sagnn_interval_fusion_workspace_bytes has no heads: it reserves h, plus Q|K|V wherever Wide
-// is the fall-back of an unaligned call, so also where a fused kernel is taken (d = 128 under f16x2).
+// Valu, y + Q|K|V for Wide; a caller with an unaligned x reserves y + Q|K|V itself (sagnn.h).
+// sagnn_interval_fusion_workspace_bytes has no heads: it reserves h, plus Q|K|V wherever Wide is the fall-back of an
+// unaligned call, so also where a fused kernel is taken (d = 128 under f16x2).
 // VALU has no attention-backward kernels: the two _supported queries answer 0 under it, yet the _f32 entries run
 // the f16x2 choice. The attention backward reads the engine of the thread it runs on (autograd: PyTorch's worker).
 #include "engine.h"
@@ -46,6 +48,7 @@ static bool d32_or_64(int d) { return d == 32 || d == 64; }
 LstmFwd select_lstm_fwd(Engine e, int d, int t, bool vec, int64_t ld_h, bool h_vec, bool train, bool drop, bool drop_vec) {
   if (e == Engine::Valu || !vec) return LstmFwd::Valu;
   if (d32_or_64(d)) {
+    if (!h_vec) return LstmFwd::Valu;  // the f16 kernel stores h as 16-byte rows (raw_buffer_store_b128)
     // the f16 tile's rows are addressed with 32-bit byte offsets from a per-tile base (lstm_fwd_f16)
     if (e == Engine::F16x2 && !(train && drop) && ld_h < (1 << 22) && (int64_t)t * d < (1 << 18)) return LstmFwd::F16x2;
     return LstmFwd::F32Mfma;

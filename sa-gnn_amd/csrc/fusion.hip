@@ -291,6 +291,7 @@ int mhsa_mean_valu(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t,
   while (slots > 1 && (size_t)slots * 4 * t * d * sizeof(float) > 64 * 1024) slots >>= 1;
   const size_t lds = (size_t)slots * 4 * t * d * sizeof(float);
   if (lds > 160 * 1024) return fail(SAGNN_ERR_DIM, "t*d = %d too large for LDS", t * d);
+  if (int rc = sagnn::ensure_dynamic_lds(reinterpret_cast<const void*>(&mhsa_mean_valu_kernel), lds)) return rc;
   int64_t blocks = (n + slots - 1) / slots;
   if (blocks > 8192) blocks = 8192;
   ProfileScope prof(kProfMhsa, s, n, t);

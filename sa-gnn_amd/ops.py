@@ -449,6 +449,11 @@ def _wide(d: int) -> bool:
     return d % 32 == 0 and d not in (32, 64) and _lib.load().sagnn_get_engine() != ENGINES["valu"]
 
 
+def _x_vec(x: torch.Tensor, ld_n: int, ld_t: int) -> bool:
+    """x rows 16-byte aligned: what csrc/engine.cpp calls "vec" and the aligned-only entries require."""
+    return x.data_ptr() % 16 == 0 and ld_n % 4 == 0 and ld_t % 4 == 0
+
+
 def lstm_fwd(x: torch.Tensor, W: torch.Tensor, b: torch.Tensor, forget_bias: float = 1.0,
              drop_scale: torch.Tensor | None = None, out: torch.Tensor | None = None,
              h0: torch.Tensor | None = None, c0: torch.Tensor | None = None, c_out: torch.Tensor | None = None):
@@ -499,7 +504,7 @@ def mhsa_mean(x: torch.Tensor, Wq, bq, Wk, bk, Wv, bv, heads: int, out: torch.Te
         out = torch.empty((n, d), dtype=torch.float32, device=x.device)
     ldo = _f32_rows("out", out, d, n)
     lib = _lib.load()
-    if _wide(d):
+    if _wide(d) and _x_vec(x, ld, ldt):      # the wide entry takes aligned rows only; sagnn_mhsa_mean_f32 takes any
         ws = torch.empty(int(lib.sagnn_mhsa_wide_workspace_bytes(n, t, d)) // 4, dtype=torch.float32, device=x.device)
         check(lib.sagnn_mhsa_mean_wide_f32(
             x.data_ptr(), ld, ldt, n, t, d, int(heads), _vec("Wq", Wq, d * d), _vec("bq", bq, d),
@@ -513,18 +518,24 @@ def mhsa_mean(x: torch.Tensor, Wq, bq, Wk, bk, Wv, bv, heads: int, out: torch.Te
     return out
 
 
-def ln_mhsa_mean(x: torch.Tensor, gamma, beta, Wq, bq, Wk, bk, Wv, bv, heads: int, eps: float = 1e-12):
+def ln_mhsa_mean(x: torch.Tensor, gamma, beta, Wq, bq, Wk, bk, Wv, bv, heads: int, eps: float = 1e-12,
+                 out: torch.Tensor | None = None):
     """layer_norm over (T, d) -> MHSA -> mean (reference model.py:152-155) in one call:
     sagnn_ln_mhsa_mean_f32 (fused on the matrix-core path). x [n, t, d] -> [n, d]."""
     n, t, d, ld, ldt = _ntd("x", x)
-    out = torch.empty((n, d), dtype=torch.float32, device=x.device)
+    if out is None:
+        out = torch.empty((n, d), dtype=torch.float32, device=x.device)
+    ldo = _f32_rows("out", out, d, n)
     lib = _lib.load()
-    need = int(lib.sagnn_ln_mhsa_mean_workspace_bytes(n, t, d, int(heads)))
+    if _x_vec(x, ld, ldt):
+        need = int(lib.sagnn_ln_mhsa_mean_workspace_bytes(n, t, d, int(heads)))
+    else:   # the query assumes aligned x (sagnn.h); an unaligned one runs unfused: y, plus Q|K|V where that is Wide
+        need = n * t * d * 4 + int(lib.sagnn_mhsa_wide_workspace_bytes(n, t, d))
     ws = torch.empty(need // 4, dtype=torch.float32, device=x.device) if need else None
     check(lib.sagnn_ln_mhsa_mean_f32(
         x.data_ptr(), ld, ldt, n, t, d, int(heads), _vec("gamma", gamma, d), _vec("beta", beta, d), float(eps),
         _vec("Wq", Wq, d * d), _vec("bq", bq, d), _vec("Wk", Wk, d * d), _vec("bk", bk, d), _vec("Wv", Wv, d * d),
-        _vec("bv", bv, d), out.data_ptr(), d, _ptr(ws), need, _stream()))
+        _vec("bv", bv, d), out.data_ptr(), ldo, _ptr(ws), need, _stream()))
     return out
 
 

@@ -124,6 +124,23 @@ def test_fusion_argument_errors_without_gpu():
                                       None, 64, None, 0, None) == -1
 
 
+def test_unaligned_attention_calls_are_refused_before_any_launch():
+    """An x off a 16-byte boundary never runs fused (csrc/engine.cpp): sagnn_ln_mhsa_mean_f32 then needs the workspace its
+    query, which assumes aligned x, answers 0 for; the wide entry takes aligned rows only. Both say so before a launch.
+    (The t*d caps of the Valu and wide launchers come after a successful launch set-up: tests/test_gpu_fusion_routes.py.)"""
+    lib = _lib.load()
+    buf = (ctypes.c_float * 4096)()
+    p = (ctypes.addressof(buf) + 15) & ~15
+    assert lib.sagnn_ln_mhsa_mean_workspace_bytes(4, 2, 64, 16) == 0
+    ln = lambda x, ws, nbytes: lib.sagnn_ln_mhsa_mean_f32(x, 128, 64, 4, 2, 64, 16, p, p, 1e-12, p, p, p, p, p, p, p, 64, ws,   # noqa: E731
+                                                          nbytes, None)
+    assert ln(p + 4, None, 0) == -6 and "workspace" in _lib.last_error()
+    assert ln(p + 4, p, 4 * 2 * 64 * 4 - 4) == -6                                     # one float short of y
+    assert lib.sagnn_ln_mhsa_mean_f32(p, 129, 64, 4, 2, 64, 16, p, p, 1e-12, p, p, p, p, p, p, p, 64, None, 0, None) == -6
+    wide = lambda x, ld_n: lib.sagnn_mhsa_mean_wide_f32(x, ld_n, 128, 4, 2, 128, 8, p, p, p, p, p, p, p, 128, p, 4096 * 4, None)   # noqa: E731
+    assert wide(p + 4, 256) == -3 and wide(p, 257) == -3
+
+
 def test_round3_entries_reject_bad_arguments_without_gpu():
     """The entries added in round 3 validate before they touch a device: segmented weight gradient, BPTT with scratch."""
     lib = _lib.load()
