@@ -112,13 +112,29 @@ def _attn_bwd_front(x, gamma, beta, Wq, bq, Wk, bk, Wv, bv, heads, g_out, want_y
     dev = x.device
     dqkv = torch.empty((n * t, 3 * d), dtype=torch.float32, device=dev)
     y = torch.empty((n * t, d), dtype=torch.float32, device=dev) if (want_y and gamma is not None) else None
-    vec = lambda name, v, cnt: ops._vec(name, v.detach(), cnt)   # noqa: E731
     ops.check(lib.sagnn_attn_bwd_front_f32(
-        x.data_ptr(), ld_n, ld_t, n, t, d, int(heads), None if gamma is None else vec("gamma", gamma, d),
-        None if beta is None else vec("beta", beta, d), 1e-12, 0 if gamma is None else 1, vec("Wq", Wq, d * d),
-        vec("bq", bq, d), vec("Wk", Wk, d * d), vec("bk", bk, d), vec("Wv", Wv, d * d), vec("bv", bv, d),
+        x.data_ptr(), ld_n, ld_t, n, t, d, int(heads), None if gamma is None else ops._vec("gamma", gamma.detach(), d),
+        None if beta is None else ops._vec("beta", beta.detach(), d), 1e-12, 0 if gamma is None else 1,
+        *ops._attn_ptrs(d, *(w.detach() for w in (Wq, bq, Wk, bk, Wv, bv))),
         g_out.data_ptr(), int(g_out.stride(0)), dqkv.data_ptr(), ops._ptr(y), ops._stream()))
     return y, dqkv
+
+
+def _attn_bwd_qkv(x, gamma, beta, Wqkv, Wq, bq, Wk, bk, Wv, bv, heads, g_out):
+    """Recompute y = LN(x) (gamma None: y = x) and Q|K|V of x [n, t, d] dense, attention backward for g_out [n, d]
+    contiguous -> (y [n*t, d], dQ|dK|dV [n*t, 3d]): the fused front where it covers the shape and FUSED_ATTN_BWD is
+    set, otherwise [layernorm_td ->] dense_nn -> sagnn_attn_bwd_f32. Wqkv: [Wq | Wk | Wv], detached."""
+    lib = ops._lib.load()
+    n, t, d = x.shape
+    if lib.sagnn_attn_bwd_front_supported(d, t, heads) and FUSED_ATTN_BWD:
+        y, qkv = _attn_bwd_front(x, gamma, beta, Wq, bq, Wk, bk, Wv, bv, heads, g_out)
+        return (x.view(n * t, d) if y is None else y), qkv
+    y = x if gamma is None else ops.layernorm_td(x, gamma, beta)                     # [n, t, d]
+    bqkv = torch.cat([bq, bk, bv]).detach().contiguous()
+    y2 = y.view(n * t, d)
+    qkv = ops.dense_nn(y2, Wqkv, bqkv)                                               # [n*t, 3d]
+    ops.check(lib.sagnn_attn_bwd_f32(qkv.data_ptr(), g_out.data_ptr(), d, n, t, d, heads, ops._stream()))
+    return y2, qkv
 
 
 def lstm_bwd(x, h, gates, cell, dh, drop, W):
@@ -174,14 +190,7 @@ def _fusion_backward(x, lstm_W, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, h, ga
     # ---- recompute y and Q|K|V, attention backward -> dQ|dK|dV -----------------------------
     h_emit = h if drop is None else ops.mul(h, drop.contiguous())
     Wqkv = torch.cat([Wq, Wk, Wv], dim=1).detach().contiguous()                      # [d, 3d]
-    if lib.sagnn_attn_bwd_front_supported(d, t, heads) and FUSED_ATTN_BWD:
-        y2, qkv = _attn_bwd_front(h_emit, ln_gamma.detach(), ln_beta.detach(), Wq, bq, Wk, bk, Wv, bv, heads, g_out)
-    else:
-        y = ops.layernorm_td(h_emit, ln_gamma.detach(), ln_beta.detach())            # [n, t, d]
-        bqkv = torch.cat([bq, bk, bv]).detach().contiguous()
-        y2 = y.view(n * t, d)
-        qkv = ops.dense_nn(y2, Wqkv, bqkv)                                           # [n*t, 3d]
-        ops.check(lib.sagnn_attn_bwd_f32(qkv.data_ptr(), g_out.data_ptr(), d, n, t, d, heads, st))
+    y2, qkv = _attn_bwd_qkv(h_emit, ln_gamma.detach(), ln_beta.detach(), Wqkv, Wq, bq, Wk, bk, Wv, bv, heads, g_out)
     dWqkv = torch.zeros((d, 3 * d), dtype=torch.float32, device=dev)
     dbqkv = torch.zeros(3 * d, dtype=torch.float32, device=dev)
     if lib.sagnn_attn_bwd_tail_supported(d) and FUSED_ATTN_BWD:
@@ -345,25 +354,16 @@ def interval_fusion_rows(x, rows, count, cap: int, p: dict, heads: int, drop_sca
 
 
 def _mhsa_mean_backward(y, Wq, bq, Wk, bk, Wv, bv, heads, g_out):
-    """y [n, t, d] dense, g_out [n, d] -> (dy [n, t, d], dWq, dbq, dWk, dbk, dWv, dbv)."""
-    lib = ops._lib.load()
+    """y [n, t, d] dense, g_out [n, d] -> (dy [n, t, d], dWq, dbq, dWk, dbk, dWv, dbv). y is the saved input of the
+    forward: it is never overwritten, so the in-place tail of _fusion_backward is not taken."""
     n, t, d = y.shape
-    dev = y.device
     Wqkv = torch.cat([Wq, Wk, Wv], dim=1).detach().contiguous()
-    bqkv = torch.cat([bq, bk, bv]).detach().contiguous()
-    y2 = y.reshape(n * t, d)
-    if lib.sagnn_attn_bwd_front_supported(d, t, heads) and FUSED_ATTN_BWD:
-        _, qkv = _attn_bwd_front(y.contiguous(), None, None, Wq, bq, Wk, bk, Wv, bv, heads, g_out.contiguous())
-    else:
-        qkv = ops.dense_nn(y2, Wqkv, bqkv)
-        ops.check(lib.sagnn_attn_bwd_f32(qkv.data_ptr(), g_out.data_ptr(), d, n, t, d, heads, ops._stream()))
-    dWqkv = torch.zeros((d, 3 * d), dtype=torch.float32, device=dev)
-    dbqkv = torch.zeros(3 * d, dtype=torch.float32, device=dev)
+    y2, qkv = _attn_bwd_qkv(y.contiguous(), None, None, Wqkv, Wq, bq, Wk, bk, Wv, bv, heads, g_out.contiguous())
+    dWqkv = torch.zeros((d, 3 * d), dtype=torch.float32, device=y.device)
+    dbqkv = torch.zeros(3 * d, dtype=torch.float32, device=y.device)
     ops.dense_tn(y2, qkv, dWqkv, dbqkv)
     dy = ops.dense_nn(qkv, Wqkv.t().contiguous(), None).view(n, t, d)
-    dWs = [dWqkv[:, i * d:(i + 1) * d].contiguous() for i in range(3)]
-    dbs = [dbqkv[i * d:(i + 1) * d].contiguous() for i in range(3)]
-    return dy, dWs[0], dbs[0], dWs[1], dbs[1], dWs[2], dbs[2]
+    return (dy,) + _split_qkv_grads(dWqkv, dbqkv, d)
 
 
 class SpmmFn(torch.autograd.Function):

@@ -537,11 +537,9 @@ __global__ __launch_bounds__(64 * (D >= 64 ? 4 : D / 16), (D == 128 || (BWD && T
 
 namespace sagnn {
 
-template <int D, int T, bool BWD = false>
-static int launch_split(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, const float* gamma, const float* beta,
-                        float eps, int apply_ln, const float* Wq, const float* bq, const float* Wk, const float* bk,
-                        const float* Wv, const float* bv, float* out, int64_t ld_out, hipStream_t s,
-                        float* dqkv = nullptr, float* y = nullptr) {
+// Forward: writes out [n, d] (row stride ld_out), b is empty. BWD: the front of the attention backward pass, b given.
+template <int D, int T, bool BWD>
+static int launch_split(const SeqView& v, const AttnParams& a, float* out, int64_t ld_out, const AttnBwdOut& b, hipStream_t s) {
   constexpr int NW = D >= 64 ? 4 : D / 16, NB = kRows / T;
   constexpr int LP = (BWD && D == 128) ? 1 : lanes_per_pair(T, D);
   constexpr int GS = kRows * kRec + NB * pad_node(T) + pad_group(T);
@@ -551,38 +549,31 @@ static int launch_split(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, c
   // per CU for each of the two column halves
   const int per_cu = (D == 128 || (BWD && T >= 8)) ? 1 : D == 64 ? 2 : 4;
   constexpr int CB = D == 128 ? 2 : 1;
-  const int64_t n_tiles = (n + NB - 1) / NB;
+  const int64_t n_tiles = (v.n + NB - 1) / NB;
   const int64_t want = (int64_t)cu_count_current() * per_cu / CB;
   const int64_t blocks = n_tiles < want ? n_tiles : (want > 0 ? want : 1);
-  ProfileScope prof(kProfMhsa, s, n, T);
-  hipLaunchKernelGGL((ln_mhsa_split_kernel<D, T, LP, BWD>), dim3((unsigned)blocks, CB), dim3(64 * NW), lds, s, x, ld_n, ld_t, n,
-                     gamma, beta, eps, apply_ln, Wq, bq, Wk, bk, Wv, bv, out, ld_out, n_tiles, dqkv, y, redo_counter());
+  ProfileScope prof(kProfMhsa, s, v.n, T);
+  // the backward front reads the upstream gradient through the kernel's `out` / `ld_out` parameters
+  hipLaunchKernelGGL((ln_mhsa_split_kernel<D, T, LP, BWD>), dim3((unsigned)blocks, CB), dim3(64 * NW), lds, s, v.x, v.ld_n, v.ld_t,
+                     v.n, a.gamma, a.beta, a.eps, a.apply_ln, a.Wq, a.bq, a.Wk, a.bk, a.Wv, a.bv,
+                     BWD ? const_cast<float*>(b.g_out) : out, BWD ? b.ld_g : ld_out, n_tiles, b.dqkv, b.y, redo_counter());
   SAGNN_HIP_TRY(hipGetLastError());
   return SAGNN_OK;
 }
 
 template <int D>
-static int dispatch_t(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, const float* gamma,
-                      const float* beta, float eps, int apply_ln, const float* Wq, const float* bq, const float* Wk,
-                      const float* bk, const float* Wv, const float* bv, float* out, int64_t ld_out, hipStream_t s) {
-#define SAGNN_T_CASE(TT) \
-  case TT: return launch_split<D, TT>(x, ld_n, ld_t, n, gamma, beta, eps, apply_ln, Wq, bq, Wk, bk, Wv, bv, out, ld_out, s);
-  switch (t) {
-    SAGNN_T_CASE(1) SAGNN_T_CASE(2) SAGNN_T_CASE(3) SAGNN_T_CASE(4) SAGNN_T_CASE(5) SAGNN_T_CASE(6)
-    SAGNN_T_CASE(8) SAGNN_T_CASE(12) SAGNN_T_CASE(16)
-    default: return fail(SAGNN_ERR_DIM, "split attention: t = %d has no specialised kernel", t);
-  }
-#undef SAGNN_T_CASE
+static int ln_mhsa_mean_split_d(const SeqView& v, const AttnParams& a, float* out, int64_t ld_out, hipStream_t s) {
+  int rc;
+  const auto launch = [&](auto T) { return launch_split<D, decltype(T)::value, false>(v, a, out, ld_out, AttnBwdOut{}, s); };
+  if (dispatch_t(v.t, SpecialisedT{}, launch, rc)) return rc;
+  return fail(SAGNN_ERR_DIM, "split attention: t = %d has no specialised kernel", v.t);
 }
 
-int ln_mhsa_mean_split(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int d, int heads,
-                       const float* gamma, const float* beta, float eps, int apply_ln, const float* Wq,
-                       const float* bq, const float* Wk, const float* bk, const float* Wv, const float* bv,
-                       float* out, int64_t ld_out, hipStream_t s) {
-  if (!mhsa_split_supported(d, t, heads)) return fail(SAGNN_ERR_DIM, "split attention: unsupported d/t/heads");
-  if (d == 128) return dispatch_t<128>(x, ld_n, ld_t, n, t, gamma, beta, eps, apply_ln, Wq, bq, Wk, bk, Wv, bv, out, ld_out, s);
-  if (d == 64) return dispatch_t<64>(x, ld_n, ld_t, n, t, gamma, beta, eps, apply_ln, Wq, bq, Wk, bk, Wv, bv, out, ld_out, s);
-  return dispatch_t<32>(x, ld_n, ld_t, n, t, gamma, beta, eps, apply_ln, Wq, bq, Wk, bk, Wv, bv, out, ld_out, s);
+int ln_mhsa_mean_split(const SeqView& v, const AttnParams& a, float* out, int64_t ld_out, hipStream_t s) {
+  if (!mhsa_split_supported(v.d, v.t, a.heads)) return fail(SAGNN_ERR_DIM, "split attention: unsupported d/t/heads");
+  if (v.d == 128) return ln_mhsa_mean_split_d<128>(v, a, out, ld_out, s);
+  if (v.d == 64) return ln_mhsa_mean_split_d<64>(v, a, out, ld_out, s);
+  return ln_mhsa_mean_split_d<32>(v, a, out, ld_out, s);
 }
 
 // Front of the attention backward pass on the same kernel (16 heads; d in {32, 64}: every T of the forward — one lane per
@@ -590,38 +581,20 @@ int ln_mhsa_mean_split(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, in
 // t <= 6: d_k = 8, one lane per pair, a pair's k / v / dk vectors take 144 of the 512 registers of a one-workgroup-per-CU wave):
 // y = LN(x) (or x), Q|K|V, attention backward -> dqkv [n*t, 3d] and, when y is not NULL, y [n*t, d].
 template <int D>
-static int dispatch_bwd_t(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, const float* gamma, const float* beta,
-                          float eps, int apply_ln, const float* Wq, const float* bq, const float* Wk, const float* bk,
-                          const float* Wv, const float* bv, const float* g_out, int64_t ld_g, float* dqkv, float* y,
-                          hipStream_t s) {
-#define SAGNN_T_CASE(TT)                                                                                              \
-  case TT:                                                                                                            \
-    return launch_split<D, TT, true>(x, ld_n, ld_t, n, gamma, beta, eps, apply_ln, Wq, bq, Wk, bk, Wv, bv,            \
-                                     const_cast<float*>(g_out), ld_g, s, dqkv, y);
-  switch (t) {
-    SAGNN_T_CASE(1) SAGNN_T_CASE(2) SAGNN_T_CASE(3) SAGNN_T_CASE(4) SAGNN_T_CASE(5) SAGNN_T_CASE(6)
-    case 8: case 12: case 16:
-      if constexpr (D <= 64) {
-        if (t == 8) return launch_split<D, 8, true>(x, ld_n, ld_t, n, gamma, beta, eps, apply_ln, Wq, bq, Wk, bk, Wv, bv, const_cast<float*>(g_out), ld_g, s, dqkv, y);
-        if (t == 12) return launch_split<D, 12, true>(x, ld_n, ld_t, n, gamma, beta, eps, apply_ln, Wq, bq, Wk, bk, Wv, bv, const_cast<float*>(g_out), ld_g, s, dqkv, y);
-        return launch_split<D, 16, true>(x, ld_n, ld_t, n, gamma, beta, eps, apply_ln, Wq, bq, Wk, bk, Wv, bv, const_cast<float*>(g_out), ld_g, s, dqkv, y);
-      }
-      [[fallthrough]];
-    default: return fail(SAGNN_ERR_DIM, "split attention backward front: t = %d has no specialised kernel", t);
-  }
-#undef SAGNN_T_CASE
+static int attn_bwd_front_split_d(const SeqView& v, const AttnParams& a, const AttnBwdOut& b, hipStream_t s) {
+  using Ts = std::conditional_t<D == 128, SplitBwdFrontT128, SpecialisedT>;
+  int rc;
+  const auto launch = [&](auto T) { return launch_split<D, decltype(T)::value, true>(v, a, nullptr, 0, b, s); };
+  if (dispatch_t(v.t, Ts{}, launch, rc)) return rc;
+  return fail(SAGNN_ERR_DIM, "split attention backward front: t = %d has no specialised kernel", v.t);
 }
 
-int attn_bwd_front_split(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int d, int heads, const float* gamma,
-                         const float* beta, float eps, int apply_ln, const float* Wq, const float* bq, const float* Wk,
-                         const float* bk, const float* Wv, const float* bv, const float* g_out, int64_t ld_g, float* dqkv,
-                         float* y, hipStream_t s) {
-  if (!attn_bwd_front_split_supported(d, t, heads)) return fail(SAGNN_ERR_DIM, "split attention backward front: unsupported d/t/heads");
-  if (d == 128)
-    return dispatch_bwd_t<128>(x, ld_n, ld_t, n, t, gamma, beta, eps, apply_ln, Wq, bq, Wk, bk, Wv, bv, g_out, ld_g, dqkv, y, s);
-  if (d == 64)
-    return dispatch_bwd_t<64>(x, ld_n, ld_t, n, t, gamma, beta, eps, apply_ln, Wq, bq, Wk, bk, Wv, bv, g_out, ld_g, dqkv, y, s);
-  return dispatch_bwd_t<32>(x, ld_n, ld_t, n, t, gamma, beta, eps, apply_ln, Wq, bq, Wk, bk, Wv, bv, g_out, ld_g, dqkv, y, s);
+int attn_bwd_front_split(const SeqView& v, const AttnParams& a, const AttnBwdOut& b, hipStream_t s) {
+  if (!attn_bwd_front_split_supported(v.d, v.t, a.heads))
+    return fail(SAGNN_ERR_DIM, "split attention backward front: unsupported d/t/heads");
+  if (v.d == 128) return attn_bwd_front_split_d<128>(v, a, b, s);
+  if (v.d == 64) return attn_bwd_front_split_d<64>(v, a, b, s);
+  return attn_bwd_front_split_d<32>(v, a, b, s);
 }
 
 }  // namespace sagnn

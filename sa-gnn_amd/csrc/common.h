@@ -40,43 +40,62 @@ int cu_count_current();   // compute units of the current device (256 on MI355X)
 // re-evaluate in fp32 because an operand left the split's window (f16_split.h, RANGE): sagnn_range_redo_count reads it.
 unsigned int* redo_counter();
 
+// ---- arguments of the fusion launchers: plain aggregates, passed by const reference ------------
+// A sequence tensor: x[node, ts, :] lives at x + node*ld_n + ts*ld_t (n nodes, t intervals, d features).
+struct SeqView {
+  const float* x;
+  int64_t ld_n, ld_t, n;
+  int t, d;
+  bool vec() const { return aligned16(x) && (ld_n & 3) == 0 && (ld_t & 3) == 0; }   // rows 16-byte aligned
+};
+// Layer norm (gamma / beta / eps; apply_ln = 0: plain attention, gamma / beta ignored) and the three dense layers.
+struct AttnParams {
+  int heads;
+  const float *gamma, *beta;
+  float eps;
+  int apply_ln;
+  const float *Wq, *bq, *Wk, *bk, *Wv, *bv;
+};
+// What the attention-backward front reads and writes besides x: the upstream gradient g_out [n, d] (row stride ld_g),
+// dqkv [n*t, 3d] and, when y is not NULL, the normalised rows y [n*t, d].
+struct AttnBwdOut {
+  const float* g_out;
+  int64_t ld_g;
+  float *dqkv, *y;
+};
+// One LSTM forward: inference (h_init / c_init / c_final optional) or training (gates / cell saved). drop: output mask.
+struct LstmArgs {
+  SeqView x;
+  const float *W, *b;
+  float forget_bias;
+  const float* drop;
+  float* h;
+  int64_t ld_h;
+  float *gates, *cell;
+  const float* h_init;
+  int64_t ld_hi;
+  const float* c_init;
+  float* c_final;
+};
+
 // fusion_mfma.hip: the exact-fp32 MFMA kernels (SAGNN_ENGINE_F32; d = 32 / 64)
-int lstm_fwd_mfma(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int d, const float* W,
-                  const float* b, float forget_bias, const float* drop, float* h, int64_t ld_h,
-                  float* gates_out, float* c_out, const float* h_init, int64_t ld_hi, const float* c_init,
-                  float* c_final, hipStream_t s);
-int ln_mhsa_mean_mfma(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int d, int heads,
-                      const float* gamma, const float* beta, float eps, int apply_ln, const float* Wq,
-                      const float* bq, const float* Wk, const float* bk, const float* Wv,
-                      const float* bv, float* out, int64_t ld_out, hipStream_t s);
-int attn_bwd_front_mfma(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int d, int heads,
-                        const float* gamma, const float* beta, float eps, int apply_ln, const float* Wq,
-                        const float* bq, const float* Wk, const float* bk, const float* Wv, const float* bv,
-                        const float* g_out, int64_t ld_g, float* dqkv, float* y, hipStream_t s);
+int lstm_fwd_mfma(const LstmArgs& a, hipStream_t s);
+int ln_mhsa_mean_mfma(const SeqView& v, const AttnParams& a, float* out, int64_t ld_out, hipStream_t s);
+int attn_bwd_front_mfma(const SeqView& v, const AttnParams& a, const AttnBwdOut& b, hipStream_t s);
 // lstm_f16.hip: the same LSTM on the f16 matrix cores, operands split in two round-to-nearest pieces (default engine)
-int lstm_fwd_f16(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int d, const float* W, const float* b,
-                 float forget_bias, const float* drop, float* h, int64_t ld_h, float* gates_out, float* c_out,
-                 const float* h_init, int64_t ld_hi, const float* c_init, float* c_final, hipStream_t s);
-// attn_split.hip: layer norm + Q|K|V + attention + mean with the products on the f16 matrix cores (split operands)
-int ln_mhsa_mean_split(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int d, int heads,
-                       const float* gamma, const float* beta, float eps, int apply_ln, const float* Wq,
-                       const float* bq, const float* Wk, const float* bk, const float* Wv, const float* bv,
-                       float* out, int64_t ld_out, hipStream_t s);
+int lstm_fwd_f16(const LstmArgs& a, hipStream_t s);
+// attn_split.hip: layer norm + Q|K|V + attention + mean with the products on the f16 matrix cores (split operands),
+// and the attention-backward front on the same kernel
+int ln_mhsa_mean_split(const SeqView& v, const AttnParams& a, float* out, int64_t ld_out, hipStream_t s);
+int attn_bwd_front_split(const SeqView& v, const AttnParams& a, const AttnBwdOut& b, hipStream_t s);
 // lstm_split128.hip: d = 128, one launch per step, hidden slices across workgroups (drop: training form only)
-int lstm_fwd_split128(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, const float* W, const float* b,
-                      float forget_bias, const float* drop, float* h, int64_t ld_h, float* gates_out, float* c_out,
-                      const float* h_init, int64_t ld_hi, const float* c_init, float* c_final, hipStream_t s);
+int lstm_fwd_split128(const LstmArgs& a, hipStream_t s);
 // attn_bwd_tail_f16.hip: dy / dW / db of the three dense layers on the f16 engine (d = 32 / 64)
 int attn_bwd_tail_f16(float* y, const float* dqkv, int64_t rows, int d, const float* Wqkv, float* dWqkv, float* dbqkv,
                       hipStream_t s);
 // same kernel, LSTM form: dW [2d, 4d] += sum_s [x_s | h_{s-1}]^T dG_s from gate gradients stored time-major [t, n, 4d]
 int lstm_dw_f16(const float* x, int64_t ld_n, int64_t ld_t, const float* h, const float* dg, int64_t n, int t, int d, float* dW,
                 hipStream_t s);
-// attn_split.hip: the attention-backward front on the f16 engine
-int attn_bwd_front_split(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int d, int heads, const float* gamma,
-                         const float* beta, float eps, int apply_ln, const float* Wq, const float* bq, const float* Wk,
-                         const float* bk, const float* Wv, const float* bv, const float* g_out, int64_t ld_g, float* dqkv,
-                         float* y, hipStream_t s);
 // dense.hip: products of any size (multiples of 32), cut into LDS-fitting pieces
 int dense_nn_any(const float* X, int64_t ldx, int64_t n, int din, int dout, const float* W, int64_t ldw,
                  const float* bias, float* Y, int64_t ldy, int accumulate, hipStream_t s);

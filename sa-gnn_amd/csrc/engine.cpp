@@ -67,7 +67,7 @@ AttnFwd select_attn_fwd(Engine e, int d, int t, int heads, bool vec) {
 
 AttnBwdFront select_attn_bwd_front(Engine e, int d, int t, int heads) {
   if (e != Engine::F32 && attn_bwd_front_split_supported(d, t, heads)) return AttnBwdFront::Split;
-  if (mhsa_mfma_supported(d, t, heads) && (d / heads == 2 || d / heads == 4) && (t <= 6 || t == 8))
+  if (mhsa_mfma_supported(d, t, heads) && (d / heads == 2 || d / heads == 4) && has_t(t, MfmaBwdFrontT{}))
     return AttnBwdFront::F32Mfma;
   return AttnBwdFront::None;
 }
@@ -82,14 +82,13 @@ LstmBwd select_lstm_bwd(Engine e, int d, bool workspace) {
 
 bool mhsa_split_supported(int d, int t, int heads) {
   if (heads != 16 || !(d == 32 || d == 64 || d == 128)) return false;
-  return (t >= 1 && t <= 6) || t == 8 || t == 12 || t == 16;
+  return has_t(t, SpecialisedT{});
 }
 
-// d = 32 / 64: every t of the forward; d = 128: t <= 6 (a pair's k / v / dk vectors take 144 of the 512 registers)
+// d = 32 / 64: every t of the forward; d = 128: t <= 6
 bool attn_bwd_front_split_supported(int d, int t, int heads) {
   if (heads != 16) return false;
-  if (d == 128) return t >= 1 && t <= 6;
-  return d32_or_64(d) && ((t >= 1 && t <= 6) || t == 8 || t == 12 || t == 16);
+  return d == 128 ? has_t(t, SplitBwdFrontT128{}) : d32_or_64(d) && has_t(t, SpecialisedT{});
 }
 
 bool mhsa_mfma_supported(int d, int t, int heads) {

@@ -4,6 +4,9 @@
 #pragma once
 #include <stdint.h>
 
+#include <type_traits>
+#include <utility>
+
 #include "sagnn.h"
 
 namespace sagnn {
@@ -23,6 +26,25 @@ AttnFwd select_attn_fwd(Engine e, int d, int t, int heads, bool vec);
 AttnBwdFront select_attn_bwd_front(Engine e, int d, int t, int heads);
 AttnBwdTail select_attn_bwd_tail(Engine e, int d);
 LstmBwd select_lstm_bwd(Engine e, int d, bool workspace);
+
+// Interval counts with a specialised attention kernel: the reference's configurations (graphNum 3..12) and the powers
+// of two the weak-scaled benchmark produces. The fp32-MFMA forward takes any other t <= 32 in its run-time form.
+using SpecialisedT = std::integer_sequence<int, 1, 2, 3, 4, 5, 6, 8, 12, 16>;
+// The backward fronts that stop short of it (engine.cpp, "attn bwd front"): the pair form of the fp32-MFMA kernel, and
+// at d = 128 the split kernel, where a pair's k / v / dk vectors take 144 of the 512 registers.
+using MfmaBwdFrontT = std::integer_sequence<int, 1, 2, 3, 4, 5, 6, 8>;
+using SplitBwdFrontT128 = std::integer_sequence<int, 1, 2, 3, 4, 5, 6>;
+
+template <int... Ts>
+constexpr bool has_t(int t, std::integer_sequence<int, Ts...>) {
+  return (... || (t == Ts));
+}
+// Run-time t -> compile-time T: when t is in the sequence, sets rc = f(std::integral_constant<int, T>{}) for the T
+// that equals t and returns true.
+template <int... Ts, class F>
+bool dispatch_t(int t, std::integer_sequence<int, Ts...>, F&& f, int& rc) {
+  return (... || (t == Ts && (rc = f(std::integral_constant<int, Ts>{}), true)));
+}
 
 // shapes the kernel families cover; the launchers check them too
 bool mhsa_split_supported(int d, int t, int heads);             // attn_split.hip, forward

@@ -263,62 +263,81 @@ int check_strides(int64_t ld_n, int64_t ld_t, int64_t n, int t, int d) {
   return SAGNN_OK;
 }
 
+using sagnn::AttnParams;
+using sagnn::LstmArgs;
+using sagnn::SeqView;
+
+int check_heads(int heads, int d) {
+  if (heads < 1 || d % heads) return sagnn::fail(SAGNN_ERR_DIM, "heads = %d does not divide d = %d", heads, d);
+  return SAGNN_OK;
+}
+
+// a weight of the three dense layers is missing, or a layer-norm parameter that apply_ln asks for
+bool missing(const AttnParams& a) {
+  return !a.Wq || !a.bq || !a.Wk || !a.bk || !a.Wv || !a.bv || (a.apply_ln && (!a.gamma || !a.beta));
+}
+
+// The checks of an attention forward entry, in the order its callers rely on: dimensions, heads | d, pointers, strides,
+// ld_out. The entries with an order of their own (interval_fusion: workspace before heads; the backward front: shape
+// before pointers) call the pieces. rows_out = false: the wide entry, which has never looked at ld_out.
+int check_attn_call(const SeqView& v, const AttnParams& a, const float* out, int64_t ld_out, bool rows_out = true) {
+  if (int rc = check_dims(v.n, v.t, v.d)) return rc;
+  if (int rc = check_heads(a.heads, v.d)) return rc;
+  if (!v.x || missing(a) || !out) return sagnn::fail(SAGNN_ERR_NULL, "null tensor pointer");
+  if (int rc = check_strides(v.ld_n, v.ld_t, v.n, v.t, v.d)) return rc;
+  if (rows_out && ld_out < v.d) return sagnn::fail(SAGNN_ERR_ARG, "ld_out smaller than d");
+  return SAGNN_OK;
+}
+
 }  // namespace
 
 namespace sagnn {
 
-int lstm_fwd_valu(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int d, const float* W,
-                  const float* b, float forget_bias, const float* drop, float* h, int64_t ld_h,
-                  float* gates_out, float* c_out, const float* h_init, int64_t ld_hi, const float* c_init,
-                  float* c_final, hipStream_t s) {
+int lstm_fwd_valu(const LstmArgs& a, hipStream_t s) {
+  const SeqView& v = a.x;
+  const int d = v.d;
   const int slots = kBlock / d > 0 ? kBlock / d : 1;
   const int threads = slots * d;
   const int rows_pb = slots * kLstmRowsPerThread;
-  const int64_t blocks = (n + rows_pb - 1) / rows_pb;
+  const int64_t blocks = (v.n + rows_pb - 1) / rows_pb;
   if (blocks > INT32_MAX) return fail(SAGNN_ERR_ARG, "grid too large");
   const size_t lds = (size_t)rows_pb * 2 * d * sizeof(float);
-  ProfileScope prof(kProfLstm, s, n, t);
-  hipLaunchKernelGGL(lstm_fwd_valu_kernel, dim3((unsigned)blocks), dim3(threads), lds, s, x, ld_n, ld_t,
-                     n, t, d, W, b, forget_bias, drop, h, ld_h, gates_out, c_out, h_init, ld_hi, c_init, c_final);
+  ProfileScope prof(kProfLstm, s, v.n, v.t);
+  hipLaunchKernelGGL(lstm_fwd_valu_kernel, dim3((unsigned)blocks), dim3(threads), lds, s, v.x, v.ld_n, v.ld_t, v.n, v.t, d, a.W,
+                     a.b, a.forget_bias, a.drop, a.h, a.ld_h, a.gates, a.cell, a.h_init, a.ld_hi, a.c_init, a.c_final);
   SAGNN_HIP_TRY(hipGetLastError());
   return SAGNN_OK;
 }
 
-int mhsa_mean_valu(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int d, int heads,
-                   const float* Wq, const float* bq, const float* Wk, const float* bk,
-                   const float* Wv, const float* bv, float* out, int64_t ld_out, hipStream_t s) {
+int mhsa_mean_valu(const SeqView& v, const AttnParams& a, float* out, int64_t ld_out, hipStream_t s) {
+  const int t = v.t, d = v.d;
   int slots = kBlock / d > 0 ? kBlock / d : 1;
   while (slots > 1 && (size_t)slots * 4 * t * d * sizeof(float) > 64 * 1024) slots >>= 1;
   const size_t lds = (size_t)slots * 4 * t * d * sizeof(float);
   if (lds > 160 * 1024) return fail(SAGNN_ERR_DIM, "t*d = %d too large for LDS", t * d);
   if (int rc = sagnn::ensure_dynamic_lds(reinterpret_cast<const void*>(&mhsa_mean_valu_kernel), lds)) return rc;
-  int64_t blocks = (n + slots - 1) / slots;
+  int64_t blocks = (v.n + slots - 1) / slots;
   if (blocks > 8192) blocks = 8192;
-  ProfileScope prof(kProfMhsa, s, n, t);
-  hipLaunchKernelGGL(mhsa_mean_valu_kernel, dim3((unsigned)blocks), dim3(slots * d), lds, s, x, ld_n,
-                     ld_t, n, t, d, heads, Wq, bq, Wk, bk, Wv, bv, out, ld_out);
+  ProfileScope prof(kProfMhsa, s, v.n, t);
+  hipLaunchKernelGGL(mhsa_mean_valu_kernel, dim3((unsigned)blocks), dim3(slots * d), lds, s, v.x, v.ld_n, v.ld_t, v.n, t, d,
+                     a.heads, a.Wq, a.bq, a.Wk, a.bk, a.Wv, a.bv, out, ld_out);
   SAGNN_HIP_TRY(hipGetLastError());
   return SAGNN_OK;
 }
 
-}  // namespace sagnn
-
-
-namespace sagnn {
-
 // MHSA + mean for any d % 32 == 0: Q|K|V by three MFMA products per interval into ws [n, t, 3d],
 // then the per-node attention kernel.
-int mhsa_mean_wide(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int d, int heads, const float* Wq,
-                   const float* bq, const float* Wk, const float* bk, const float* Wv, const float* bv, float* out,
-                   int64_t ld_out, float* ws, hipStream_t s) {
+int mhsa_mean_wide(const SeqView& v, const AttnParams& a, float* out, int64_t ld_out, float* ws, hipStream_t s) {
+  const int64_t n = v.n;
+  const int t = v.t, d = v.d;
   ProfileScope prof(kProfMhsa, s, n, t);
   const int64_t ldq = (int64_t)t * 3 * d;
   for (int ts = 0; ts < t; ++ts) {
-    const float* xt = x + (int64_t)ts * ld_t;
+    const float* xt = v.x + (int64_t)ts * v.ld_t;
     float* qt = ws + (int64_t)ts * 3 * d;
-    if (int rc = dense_nn_any(xt, ld_n, n, d, d, Wq, d, bq, qt, ldq, 0, s)) return rc;
-    if (int rc = dense_nn_any(xt, ld_n, n, d, d, Wk, d, bk, qt + d, ldq, 0, s)) return rc;
-    if (int rc = dense_nn_any(xt, ld_n, n, d, d, Wv, d, bv, qt + 2 * d, ldq, 0, s)) return rc;
+    if (int rc = dense_nn_any(xt, v.ld_n, n, d, d, a.Wq, d, a.bq, qt, ldq, 0, s)) return rc;
+    if (int rc = dense_nn_any(xt, v.ld_n, n, d, d, a.Wk, d, a.bk, qt + d, ldq, 0, s)) return rc;
+    if (int rc = dense_nn_any(xt, v.ld_n, n, d, d, a.Wv, d, a.bv, qt + 2 * d, ldq, 0, s)) return rc;
   }
   int slots = kBlock / d > 0 ? kBlock / d : 1;
   while (slots > 1 && (size_t)slots * 3 * t * d * sizeof(float) > 64 * 1024) slots >>= 1;
@@ -327,7 +346,7 @@ int mhsa_mean_wide(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t,
   if (int rc = sagnn::ensure_dynamic_lds(reinterpret_cast<const void*>(&attn_mean_from_qkv_kernel), lds)) return rc;
   int64_t blocks = (n + slots - 1) / slots;
   if (blocks > 16384) blocks = 16384;
-  hipLaunchKernelGGL(attn_mean_from_qkv_kernel, dim3((unsigned)blocks), dim3(slots * d), lds, s, ws, n, t, d, heads,
+  hipLaunchKernelGGL(attn_mean_from_qkv_kernel, dim3((unsigned)blocks), dim3(slots * d), lds, s, ws, n, t, d, a.heads,
                      out, ld_out);
   SAGNN_HIP_TRY(hipGetLastError());
   return SAGNN_OK;
@@ -339,52 +358,46 @@ extern "C" size_t sagnn_mhsa_wide_workspace_bytes(int64_t n, int t, int d) {
   return (n <= 0 || d <= 0 || t <= 0) ? 0 : (size_t)n * (size_t)t * 3 * (size_t)d * sizeof(float);
 }
 
+// sagnn_mhsa_mean_wide_f32 on the structs: interval_fusion and ln_mhsa_mean come here with their normalised rows
+static int mhsa_mean_wide_call(const SeqView& v, const AttnParams& a, float* out, int64_t ld_out, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+  if (int rc = check_dims(v.n, v.t, v.d)) return rc;
+  if (!sagnn::wide_supported(v.d)) return sagnn::fail(SAGNN_ERR_DIM, "d = %d: the wide path needs a multiple of 32", v.d);
+  if (int rc = check_attn_call(v, a, out, ld_out, false)) return rc;
+  if (!v.vec()) return sagnn::fail(SAGNN_ERR_ALIGN, "x rows must be 16-byte aligned");
+  if (v.n == 0) return SAGNN_OK;
+  const size_t need = sagnn_mhsa_wide_workspace_bytes(v.n, v.t, v.d);
+  if (!workspace || workspace_bytes < need) return sagnn::fail(SAGNN_ERR_WORKSPACE, "mhsa wide workspace needs %zu bytes", need);
+  return sagnn::mhsa_mean_wide(v, a, out, ld_out, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
+}
+
 extern "C" int sagnn_mhsa_mean_wide_f32(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int d,
                                         int heads, const float* Wq, const float* bq, const float* Wk,
                                         const float* bk, const float* Wv, const float* bv, float* out,
                                         int64_t ld_out, void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = check_dims(n, t, d)) return rc;
-  if (!sagnn::wide_supported(d)) return sagnn::fail(SAGNN_ERR_DIM, "d = %d: the wide path needs a multiple of 32", d);
-  if (heads < 1 || d % heads) return sagnn::fail(SAGNN_ERR_DIM, "heads = %d does not divide d = %d", heads, d);
-  if (!x || !Wq || !bq || !Wk || !bk || !Wv || !bv || !out) return sagnn::fail(SAGNN_ERR_NULL, "null tensor pointer");
-  if (int rc = check_strides(ld_n, ld_t, n, t, d)) return rc;
-  if ((ld_n & 3) || (ld_t & 3) || !sagnn::aligned16(x)) return sagnn::fail(SAGNN_ERR_ALIGN, "x rows must be 16-byte aligned");
-  if (n == 0) return SAGNN_OK;
-  if (!workspace || workspace_bytes < sagnn_mhsa_wide_workspace_bytes(n, t, d))
-    return sagnn::fail(SAGNN_ERR_WORKSPACE, "mhsa wide workspace needs %zu bytes", sagnn_mhsa_wide_workspace_bytes(n, t, d));
-  return sagnn::mhsa_mean_wide(x, ld_n, ld_t, n, t, d, heads, Wq, bq, Wk, bk, Wv, bv, out, ld_out,
-                               static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
+  return mhsa_mean_wide_call({x, ld_n, ld_t, n, t, d}, {heads, nullptr, nullptr, 0.f, 0, Wq, bq, Wk, bk, Wv, bv}, out, ld_out,
+                             workspace, workspace_bytes, stream);
 }
 
 // The three LSTM forward entries: inference (h_init / c_init / c_final optional) and training (gates / cell saved).
-static int lstm_fwd(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int d, const float* W, const float* b,
-                    float forget_bias, const float* drop, float* h, int64_t ld_h, bool train, float* gates, float* cell,
-                    const float* h_init, int64_t ld_hi, const float* c_init, float* c_final, void* stream) {
-  if (int rc = check_dims(n, t, d)) return rc;
-  if (!x || !W || !b || !h || (train && (!gates || !cell))) return sagnn::fail(SAGNN_ERR_NULL, "null tensor pointer");
-  if ((h_init == nullptr) != (c_init == nullptr)) return sagnn::fail(SAGNN_ERR_NULL, "give both h_init and c_init or neither");
-  if (int rc = check_strides(ld_n, ld_t, n, t, d)) return rc;
-  if (ld_h < (int64_t)t * d) return sagnn::fail(SAGNN_ERR_ARG, "ld_h smaller than t*d");
-  if (h_init && ld_hi < d) return sagnn::fail(SAGNN_ERR_ARG, "ld_hi smaller than d");
-  if (n == 0) return SAGNN_OK;
-  const bool vec = sagnn::aligned16(x) && (ld_n & 3) == 0 && (ld_t & 3) == 0 &&
-                   (!h_init || (sagnn::aligned16(h_init) && (ld_hi & 3) == 0));
-  const bool h_vec = (ld_h & 3) == 0 && sagnn::aligned16(h);
+static int lstm_fwd(const LstmArgs& a, bool train, void* stream) {
+  const SeqView& v = a.x;
+  if (int rc = check_dims(v.n, v.t, v.d)) return rc;
+  if (!v.x || !a.W || !a.b || !a.h || (train && (!a.gates || !a.cell))) return sagnn::fail(SAGNN_ERR_NULL, "null tensor pointer");
+  if ((a.h_init == nullptr) != (a.c_init == nullptr)) return sagnn::fail(SAGNN_ERR_NULL, "give both h_init and c_init or neither");
+  if (int rc = check_strides(v.ld_n, v.ld_t, v.n, v.t, v.d)) return rc;
+  if (a.ld_h < (int64_t)v.t * v.d) return sagnn::fail(SAGNN_ERR_ARG, "ld_h smaller than t*d");
+  if (a.h_init && a.ld_hi < v.d) return sagnn::fail(SAGNN_ERR_ARG, "ld_hi smaller than d");
+  if (v.n == 0) return SAGNN_OK;
+  const bool vec = v.vec() && (!a.h_init || (sagnn::aligned16(a.h_init) && (a.ld_hi & 3) == 0));
+  const bool h_vec = (a.ld_h & 3) == 0 && sagnn::aligned16(a.h);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  switch (sagnn::select_lstm_fwd(sagnn::calling_engine(), d, t, vec, ld_h, h_vec, train, drop != nullptr,
-                                 !drop || sagnn::aligned16(drop))) {
-    case sagnn::LstmFwd::F16x2:
-      return sagnn::lstm_fwd_f16(x, ld_n, ld_t, n, t, d, W, b, forget_bias, drop, h, ld_h, gates, cell, h_init, ld_hi, c_init,
-                                 c_final, s);
-    case sagnn::LstmFwd::F32Mfma:
-      return sagnn::lstm_fwd_mfma(x, ld_n, ld_t, n, t, d, W, b, forget_bias, drop, h, ld_h, gates, cell, h_init, ld_hi, c_init,
-                                  c_final, s);
-    case sagnn::LstmFwd::Split128:
-      return sagnn::lstm_fwd_split128(x, ld_n, ld_t, n, t, W, b, forget_bias, drop, h, ld_h, gates, cell, h_init, ld_hi, c_init,
-                                      c_final, s);
-    default:
-      return sagnn::lstm_fwd_valu(x, ld_n, ld_t, n, t, d, W, b, forget_bias, drop, h, ld_h, gates, cell, h_init, ld_hi, c_init,
-                                  c_final, s);
+  switch (sagnn::select_lstm_fwd(sagnn::calling_engine(), v.d, v.t, vec, a.ld_h, h_vec, train, a.drop != nullptr,
+                                 !a.drop || sagnn::aligned16(a.drop))) {
+    case sagnn::LstmFwd::F16x2: return sagnn::lstm_fwd_f16(a, s);
+    case sagnn::LstmFwd::F32Mfma: return sagnn::lstm_fwd_mfma(a, s);
+    case sagnn::LstmFwd::Split128: return sagnn::lstm_fwd_split128(a, s);
+    default: return sagnn::lstm_fwd_valu(a, s);
   }
 }
 
@@ -392,23 +405,23 @@ extern "C" int sagnn_lstm_fwd_state_f32(const float* x, int64_t ld_n, int64_t ld
                                         const float* W, const float* b, float forget_bias,
                                         const float* drop_scale, const float* h_init, int64_t ld_hi,
                                         const float* c_init, float* h, int64_t ld_h, float* c_final, void* stream) {
-  return lstm_fwd(x, ld_n, ld_t, n, t, d, W, b, forget_bias, drop_scale, h, ld_h, false, nullptr, nullptr, h_init, ld_hi,
-                  c_init, c_final, stream);
+  return lstm_fwd({{x, ld_n, ld_t, n, t, d}, W, b, forget_bias, drop_scale, h, ld_h, nullptr, nullptr, h_init, ld_hi, c_init,
+                   c_final}, false, stream);
 }
 
 extern "C" int sagnn_lstm_fwd_f32(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int d,
                                   const float* W, const float* b, float forget_bias,
                                   const float* drop_scale, float* h, int64_t ld_h, void* stream) {
-  return lstm_fwd(x, ld_n, ld_t, n, t, d, W, b, forget_bias, drop_scale, h, ld_h, false, nullptr, nullptr, nullptr, 0, nullptr,
-                  nullptr, stream);
+  return lstm_fwd({{x, ld_n, ld_t, n, t, d}, W, b, forget_bias, drop_scale, h, ld_h, nullptr, nullptr, nullptr, 0, nullptr,
+                   nullptr}, false, stream);
 }
 
 extern "C" int sagnn_lstm_fwd_train_f32(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int d,
                                         const float* W, const float* b, float forget_bias,
                                         const float* drop_scale, float* h, int64_t ld_h, float* gates,
                                         float* cell, void* stream) {
-  return lstm_fwd(x, ld_n, ld_t, n, t, d, W, b, forget_bias, drop_scale, h, ld_h, true, gates, cell, nullptr, 0, nullptr,
-                  nullptr, stream);
+  return lstm_fwd({{x, ld_n, ld_t, n, t, d}, W, b, forget_bias, drop_scale, h, ld_h, gates, cell, nullptr, 0, nullptr, nullptr},
+                  true, stream);
 }
 
 extern "C" int sagnn_layernorm_td_f32(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int d,
@@ -431,33 +444,36 @@ extern "C" int sagnn_layernorm_td_f32(const float* x, int64_t ld_n, int64_t ld_t
 // layer norm + Q|K|V + attention + mean in ONE kernel: AttnFwd::Split or AttnFwd::F32Mfma
 static bool fused(sagnn::AttnFwd k) { return k == sagnn::AttnFwd::Split || k == sagnn::AttnFwd::F32Mfma; }
 
-static int fused_attention(sagnn::AttnFwd k, const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int d, int heads,
-                           const float* gamma, const float* beta, float eps, int apply_ln, const float* Wq, const float* bq,
-                           const float* Wk, const float* bk, const float* Wv, const float* bv, float* out, int64_t ld_out,
-                           void* stream) {
+static int fused_attention(sagnn::AttnFwd k, const SeqView& v, const AttnParams& a, float* out, int64_t ld_out, void* stream) {
   const auto launch = k == sagnn::AttnFwd::Split ? sagnn::ln_mhsa_mean_split : sagnn::ln_mhsa_mean_mfma;
-  return launch(x, ld_n, ld_t, n, t, d, heads, gamma, beta, eps, apply_ln, Wq, bq, Wk, bk, Wv, bv, out, ld_out,
-                static_cast<hipStream_t>(stream));
+  return launch(v, a, out, ld_out, static_cast<hipStream_t>(stream));
+}
+
+// sagnn_mhsa_mean_f32 on the structs (a.apply_ln = 0)
+static int mhsa_mean_call(const SeqView& v, const AttnParams& a, float* out, int64_t ld_out, void* stream) {
+  if (int rc = check_attn_call(v, a, out, ld_out)) return rc;
+  if (v.n == 0) return SAGNN_OK;
+  const sagnn::AttnFwd k = sagnn::select_attn_fwd(sagnn::calling_engine(), v.d, v.t, a.heads, v.vec());
+  if (fused(k)) return fused_attention(k, v, a, out, ld_out, stream);
+  return sagnn::mhsa_mean_valu(v, a, out, ld_out, static_cast<hipStream_t>(stream));   // Wide too: no workspace
 }
 
 extern "C" int sagnn_mhsa_mean_f32(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int d, int heads,
                                    const float* Wq, const float* bq, const float* Wk,
                                    const float* bk, const float* Wv, const float* bv, float* out,
                                    int64_t ld_out, void* stream) {
-  if (int rc = check_dims(n, t, d)) return rc;
-  if (heads < 1 || d % heads) return sagnn::fail(SAGNN_ERR_DIM, "heads = %d does not divide d = %d", heads, d);
-  if (!x || !Wq || !bq || !Wk || !bk || !Wv || !bv || !out)
-    return sagnn::fail(SAGNN_ERR_NULL, "null tensor pointer");
-  if (int rc = check_strides(ld_n, ld_t, n, t, d)) return rc;
-  if (ld_out < d) return sagnn::fail(SAGNN_ERR_ARG, "ld_out smaller than d");
-  if (n == 0) return SAGNN_OK;
-  const bool vec = sagnn::aligned16(x) && (ld_n & 3) == 0 && (ld_t & 3) == 0;
-  const sagnn::AttnFwd k = sagnn::select_attn_fwd(sagnn::calling_engine(), d, t, heads, vec);
-  if (fused(k))
-    return fused_attention(k, x, ld_n, ld_t, n, t, d, heads, nullptr, nullptr, 0.f, 0, Wq, bq, Wk, bk, Wv, bv, out, ld_out,
-                           stream);
-  return sagnn::mhsa_mean_valu(x, ld_n, ld_t, n, t, d, heads, Wq, bq, Wk, bk, Wv, bv, out, ld_out,   // Wide too: no workspace
-                               static_cast<hipStream_t>(stream));
+  return mhsa_mean_call({x, ld_n, ld_t, n, t, d}, {heads, nullptr, nullptr, 0.f, 0, Wq, bq, Wk, bk, Wv, bv}, out, ld_out, stream);
+}
+
+// Attention over rows y [n, t, d] that a layer-norm launch has normalised in the workspace; `rest` follows them there.
+static int attention_after_layernorm(sagnn::AttnFwd k, float* y, int64_t n, int t, int d, AttnParams a, float* out,
+                                     int64_t ld_out, size_t rest, void* stream) {
+  const int64_t ldw = (int64_t)t * d;
+  const SeqView yv{y, ldw, d, n, t, d};
+  a.gamma = a.beta = nullptr, a.eps = 0.f, a.apply_ln = 0;   // already applied
+  if (k == sagnn::AttnFwd::Wide)   // d = 96, 160, ...: MFMA products + per-node kernel
+    return mhsa_mean_wide_call(yv, a, out, ld_out, y + n * ldw, rest, stream);
+  return mhsa_mean_call(yv, a, out, ld_out, stream);
 }
 
 extern "C" size_t sagnn_interval_fusion_workspace_bytes(int64_t n, int t, int d) {
@@ -477,27 +493,22 @@ extern "C" int sagnn_interval_fusion_f32(const float* x, int64_t ld_n, int64_t l
                                          const float* Wv, const float* bv, float* out,
                                          int64_t ld_out, void* workspace, size_t workspace_bytes,
                                          void* stream) {
+  const AttnParams a{heads, ln_gamma, ln_beta, ln_eps, 1, Wq, bq, Wk, bk, Wv, bv};
   if (int rc = check_dims(n, t, d)) return rc;
   const size_t need = sagnn_interval_fusion_workspace_bytes(n, t, d);
   if (n > 0 && (!workspace || workspace_bytes < need))
     return sagnn::fail(SAGNN_ERR_WORKSPACE, "fusion workspace needs %zu bytes", need);
   float* h = static_cast<float*>(workspace);
   const int64_t ldw = (int64_t)t * d;
-  if (heads < 1 || d % heads) return sagnn::fail(SAGNN_ERR_DIM, "heads = %d does not divide d = %d", heads, d);
-  if (!ln_gamma || !ln_beta || !Wq || !bq || !Wk || !bk || !Wv || !bv || !out)
-    return sagnn::fail(SAGNN_ERR_NULL, "null tensor pointer");
+  if (int rc = check_heads(heads, d)) return rc;
+  if (missing(a) || !out) return sagnn::fail(SAGNN_ERR_NULL, "null tensor pointer");
   if (n == 0) return SAGNN_OK;
   const sagnn::AttnFwd k = sagnn::select_attn_fwd(sagnn::calling_engine(), d, t, heads, true);   // h: workspace rows
   if (int rc = sagnn_lstm_fwd_f32(x, ld_n, ld_t, n, t, d, lstm_W, lstm_b, forget_bias, nullptr, h, ldw, stream)) return rc;
   // layer norm rides on the fused kernel's A operand: h is read once and never rewritten
-  if (fused(k))
-    return fused_attention(k, h, ldw, d, n, t, d, heads, ln_gamma, ln_beta, ln_eps, 1, Wq, bq, Wk, bk, Wv, bv, out, ld_out,
-                           stream);
+  if (fused(k)) return fused_attention(k, {h, ldw, d, n, t, d}, a, out, ld_out, stream);
   if (int rc = sagnn_layernorm_td_f32(h, ldw, d, n, t, d, ln_gamma, ln_beta, ln_eps, h, ldw, stream)) return rc;
-  if (k == sagnn::AttnFwd::Wide)   // d = 96, 160, ...: MFMA products + per-node kernel
-    return sagnn_mhsa_mean_wide_f32(h, ldw, d, n, t, d, heads, Wq, bq, Wk, bk, Wv, bv, out, ld_out, h + n * ldw,
-                                    workspace_bytes - (size_t)n * ldw * sizeof(float), stream);
-  return sagnn_mhsa_mean_f32(h, ldw, d, n, t, d, heads, Wq, bq, Wk, bk, Wv, bv, out, ld_out, stream);
+  return attention_after_layernorm(k, h, n, t, d, a, out, ld_out, workspace_bytes - (size_t)n * ldw * sizeof(float), stream);
 }
 
 
@@ -517,29 +528,19 @@ extern "C" int sagnn_ln_mhsa_mean_f32(const float* x, int64_t ld_n, int64_t ld_t
                                       const float* bq, const float* Wk, const float* bk, const float* Wv,
                                       const float* bv, float* out, int64_t ld_out, void* workspace,
                                       size_t workspace_bytes, void* stream) {
-  if (int rc = check_dims(n, t, d)) return rc;
-  if (heads < 1 || d % heads) return sagnn::fail(SAGNN_ERR_DIM, "heads = %d does not divide d = %d", heads, d);
-  if (!x || !ln_gamma || !ln_beta || !Wq || !bq || !Wk || !bk || !Wv || !bv || !out)
-    return sagnn::fail(SAGNN_ERR_NULL, "null tensor pointer");
-  if (int rc = check_strides(ld_n, ld_t, n, t, d)) return rc;
-  if (ld_out < d) return sagnn::fail(SAGNN_ERR_ARG, "ld_out smaller than d");
+  const SeqView v{x, ld_n, ld_t, n, t, d};
+  const AttnParams a{heads, ln_gamma, ln_beta, ln_eps, 1, Wq, bq, Wk, bk, Wv, bv};
+  if (int rc = check_attn_call(v, a, out, ld_out)) return rc;
   if (n == 0) return SAGNN_OK;
-  const bool vec = sagnn::aligned16(x) && (ld_n & 3) == 0 && (ld_t & 3) == 0;
-  const sagnn::AttnFwd k = sagnn::select_attn_fwd(sagnn::calling_engine(), d, t, heads, vec);
-  if (fused(k))
-    return fused_attention(k, x, ld_n, ld_t, n, t, d, heads, ln_gamma, ln_beta, ln_eps, 1, Wq, bq, Wk, bk, Wv, bv, out, ld_out,
-                           stream);
+  const sagnn::AttnFwd k = sagnn::select_attn_fwd(sagnn::calling_engine(), d, t, heads, v.vec());
+  if (fused(k)) return fused_attention(k, v, a, out, ld_out, stream);
   const size_t ybytes = (size_t)n * t * d * sizeof(float);
   size_t need = ybytes + (k == sagnn::AttnFwd::Wide ? sagnn_mhsa_wide_workspace_bytes(n, t, d) : 0);
   if (!workspace || workspace_bytes < need)
     return sagnn::fail(SAGNN_ERR_WORKSPACE, "ln_mhsa_mean workspace needs %zu bytes", need);
   float* y = static_cast<float*>(workspace);
-  const int64_t ldw = (int64_t)t * d;
-  if (int rc = sagnn_layernorm_td_f32(x, ld_n, ld_t, n, t, d, ln_gamma, ln_beta, ln_eps, y, ldw, stream)) return rc;
-  if (k == sagnn::AttnFwd::Wide)
-    return sagnn_mhsa_mean_wide_f32(y, ldw, d, n, t, d, heads, Wq, bq, Wk, bk, Wv, bv, out, ld_out, y + n * ldw,
-                                    workspace_bytes - ybytes, stream);
-  return sagnn_mhsa_mean_f32(y, ldw, d, n, t, d, heads, Wq, bq, Wk, bk, Wv, bv, out, ld_out, stream);
+  if (int rc = sagnn_layernorm_td_f32(x, ld_n, ld_t, n, t, d, ln_gamma, ln_beta, ln_eps, y, (int64_t)t * d, stream)) return rc;
+  return attention_after_layernorm(k, y, n, t, d, a, out, ld_out, workspace_bytes - ybytes, stream);
 }
 
 // Front of the attention backward pass in one launch (shapes: engine.cpp): y = LN(x) (apply_ln) or x, Q|K|V = y W + b on
@@ -555,19 +556,18 @@ extern "C" int sagnn_attn_bwd_front_f32(const float* x, int64_t ld_n, int64_t ld
                                         const float* Wq, const float* bq, const float* Wk, const float* bk,
                                         const float* Wv, const float* bv, const float* g_out, int64_t ld_g,
                                         float* dqkv, float* y_out, void* stream) {
+  const SeqView v{x, ld_n, ld_t, n, t, d};
+  const AttnParams a{heads, ln_gamma, ln_beta, ln_eps, apply_ln, Wq, bq, Wk, bk, Wv, bv};
   if (int rc = check_dims(n, t, d)) return rc;
   const sagnn::AttnBwdFront k = sagnn::select_attn_bwd_front(sagnn::calling_engine(), d, t, heads);
   if (k == sagnn::AttnBwdFront::None)
     return sagnn::fail(SAGNN_ERR_DIM, "attn_bwd_front: unsupported d = %d, t = %d, heads = %d", d, t, heads);
-  if (!x || !Wq || !bq || !Wk || !bk || !Wv || !bv || !g_out || !dqkv || (apply_ln && (!ln_gamma || !ln_beta)))
-    return sagnn::fail(SAGNN_ERR_NULL, "null tensor pointer");
+  if (!x || missing(a) || !g_out || !dqkv) return sagnn::fail(SAGNN_ERR_NULL, "null tensor pointer");
   if (int rc = check_strides(ld_n, ld_t, n, t, d)) return rc;
   if (ld_g < d) return sagnn::fail(SAGNN_ERR_ARG, "ld_g smaller than d");
-  if (!sagnn::aligned16(x) || (ld_n & 3) || (ld_t & 3) || !sagnn::aligned16(g_out) || (ld_g & 3) ||
-      !sagnn::aligned16(dqkv) || (y_out && !sagnn::aligned16(y_out)))
+  if (!v.vec() || !sagnn::aligned16(g_out) || (ld_g & 3) || !sagnn::aligned16(dqkv) || (y_out && !sagnn::aligned16(y_out)))
     return sagnn::fail(SAGNN_ERR_ALIGN, "attn_bwd_front: need 16-byte aligned rows");
   if (n == 0) return SAGNN_OK;
   const auto launch = k == sagnn::AttnBwdFront::Split ? sagnn::attn_bwd_front_split : sagnn::attn_bwd_front_mfma;
-  return launch(x, ld_n, ld_t, n, t, d, heads, ln_gamma, ln_beta, ln_eps, apply_ln, Wq, bq, Wk, bk, Wv, bv, g_out, ld_g, dqkv,
-                y_out, static_cast<hipStream_t>(stream));
+  return launch(v, a, {g_out, ld_g, dqkv, y_out}, static_cast<hipStream_t>(stream));
 }

@@ -939,113 +939,77 @@ __global__ __launch_bounds__(kBlock, 1) void ln_mhsa_mean_mfma_kernel(
 namespace sagnn {
 
 template <int D, bool SAVE>
-static int launch_lstm_mfma(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t,
-                            const float* W, const float* b, float forget_bias, const float* drop,
-                            float* h, int64_t ld_h, float* gates_out, float* c_out, const float* h_init,
-                            int64_t ld_hi, const float* c_init, float* c_final, hipStream_t s) {
+static int launch_lstm_mfma(const LstmArgs& a, hipStream_t s) {
+  const SeqView& v = a.x;
   const size_t lds = (size_t)(2 * D * 4 * D + 4 * kRowsPerWave * D) * sizeof(float);
   if (int rc = sagnn::ensure_dynamic_lds(reinterpret_cast<const void*>(&lstm_fwd_mfma_kernel<D, SAVE>), lds)) return rc;
   const int cus = cu_count_current();
-  const int64_t n_tiles = (n + kRowsPerBlock - 1) / kRowsPerBlock;
+  const int64_t n_tiles = (v.n + kRowsPerBlock - 1) / kRowsPerBlock;
   const int64_t blocks = n_tiles < cus ? n_tiles : cus;
-  ProfileScope prof(kProfLstm, s, n, t);
-  hipLaunchKernelGGL((lstm_fwd_mfma_kernel<D, SAVE>), dim3((unsigned)blocks), dim3(kBlock), lds, s, x, ld_n, ld_t,
-                     n, t, W, b, forget_bias, drop, h, ld_h, gates_out, c_out, n_tiles, h_init, ld_hi, c_init, c_final);
+  ProfileScope prof(kProfLstm, s, v.n, v.t);
+  hipLaunchKernelGGL((lstm_fwd_mfma_kernel<D, SAVE>), dim3((unsigned)blocks), dim3(kBlock), lds, s, v.x, v.ld_n, v.ld_t, v.n, v.t,
+                     a.W, a.b, a.forget_bias, a.drop, a.h, a.ld_h, a.gates, a.cell, n_tiles, a.h_init, a.ld_hi, a.c_init, a.c_final);
   SAGNN_HIP_TRY(hipGetLastError());
   return SAGNN_OK;
 }
 
-int lstm_fwd_mfma(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int d, const float* W,
-                  const float* b, float forget_bias, const float* drop, float* h, int64_t ld_h,
-                  float* gates_out, float* c_out, const float* h_init, int64_t ld_hi, const float* c_init,
-                  float* c_final, hipStream_t s) {
-  const bool save = gates_out != nullptr;
+int lstm_fwd_mfma(const LstmArgs& a, hipStream_t s) {
+  const bool save = a.gates != nullptr;
+  const int d = a.x.d;
   // 32-row tiles are addressed with 32-bit byte offsets from a per-tile base
-  if (ld_n >= (1 << 24) || ld_h >= (1 << 24) || (int64_t)t * d >= (1 << 20))
+  if (a.x.ld_n >= (1 << 24) || a.ld_h >= (1 << 24) || (int64_t)a.x.t * d >= (1 << 20))
     return fail(SAGNN_ERR_ARG, "MFMA LSTM: row strides must stay below 2^24 floats");
-#define SAGNN_LSTM_GO(DD, SV) \
-  return launch_lstm_mfma<DD, SV>(x, ld_n, ld_t, n, t, W, b, forget_bias, drop, h, ld_h, gates_out, c_out, h_init, ld_hi, c_init, c_final, s)
-  if (d == 64 && save) SAGNN_LSTM_GO(64, true);
-  if (d == 64) SAGNN_LSTM_GO(64, false);
-  if (d == 32 && save) SAGNN_LSTM_GO(32, true);
-  if (d == 32) SAGNN_LSTM_GO(32, false);
-#undef SAGNN_LSTM_GO
+  if (d == 64) return save ? launch_lstm_mfma<64, true>(a, s) : launch_lstm_mfma<64, false>(a, s);
+  if (d == 32) return save ? launch_lstm_mfma<32, true>(a, s) : launch_lstm_mfma<32, false>(a, s);
   return fail(SAGNN_ERR_DIM, "MFMA LSTM supports d = 32 or 64, got %d", d);
 }
 
+// Forward (TT = 0: the run-time-t form): writes out [n, d], b is empty. BWD: the front of the backward pass, out NULL.
 template <int D, int TT, bool BWD>
-static int launch_ln_mhsa_t(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int heads,
-                            const float* gamma, const float* beta, float eps, int apply_ln,
-                            const float* Wq, const float* bq, const float* Wk, const float* bk,
-                            const float* Wv, const float* bv, float* out, int64_t ld_out, const float* g_out,
-                            float* dqkv_out, float* y_out, hipStream_t s) {
+static int launch_ln_mhsa_t(const SeqView& v, const AttnParams& a, float* out, int64_t ld_out, const AttnBwdOut& b, hipStream_t s) {
   const size_t lds = (size_t)(3 * D * D + 4 * kRowsPerWave * (3 * D + 4)) * sizeof(float);
   if (int rc = sagnn::ensure_dynamic_lds(reinterpret_cast<const void*>(&ln_mhsa_mean_mfma_kernel<D, TT, BWD>), lds)) return rc;
   const int cus = cu_count_current();
-  const int64_t nodes_per_tile = 4 * (kRowsPerWave / t);
-  const int64_t n_tiles = (n + nodes_per_tile - 1) / nodes_per_tile;
+  const int64_t nodes_per_tile = 4 * (kRowsPerWave / v.t);
+  const int64_t n_tiles = (v.n + nodes_per_tile - 1) / nodes_per_tile;
   const int64_t blocks = n_tiles < cus ? n_tiles : cus;
-  ProfileScope prof(kProfMhsa, s, n, t);
-  hipLaunchKernelGGL((ln_mhsa_mean_mfma_kernel<D, TT, BWD>), dim3((unsigned)blocks), dim3(kBlock), lds, s, x, ld_n,
-                     ld_t, n, t, heads, gamma, beta, eps, apply_ln, Wq, bq, Wk, bk, Wv, bv, out, ld_out,
-                     n_tiles, g_out, dqkv_out, y_out);
+  ProfileScope prof(kProfMhsa, s, v.n, v.t);
+  // the backward front takes g_out's row stride through the kernel's `ld_out` parameter
+  hipLaunchKernelGGL((ln_mhsa_mean_mfma_kernel<D, TT, BWD>), dim3((unsigned)blocks), dim3(kBlock), lds, s, v.x, v.ld_n, v.ld_t,
+                     v.n, v.t, a.heads, a.gamma, a.beta, a.eps, a.apply_ln, a.Wq, a.bq, a.Wk, a.bk, a.Wv, a.bv, out,
+                     BWD ? b.ld_g : ld_out, n_tiles, b.g_out, b.dqkv, b.y);
   SAGNN_HIP_TRY(hipGetLastError());
   return SAGNN_OK;
 }
 
-// Interval counts with a specialised kernel: the reference's configurations (graphNum 3..12) and
-// the powers of two the weak-scaled benchmark produces; anything else takes the run-time form.
 template <int D>
-static int launch_ln_mhsa(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int heads,
-                          const float* gamma, const float* beta, float eps, int apply_ln,
-                          const float* Wq, const float* bq, const float* Wk, const float* bk,
-                          const float* Wv, const float* bv, float* out, int64_t ld_out, hipStream_t s) {
-#define SAGNN_T_CASE(TT) \
-  case TT: return launch_ln_mhsa_t<D, TT, false>(x, ld_n, ld_t, n, t, heads, gamma, beta, eps, apply_ln, Wq, bq, Wk, bk, Wv, bv, out, ld_out, nullptr, nullptr, nullptr, s);
-  switch (t) {
-    SAGNN_T_CASE(1) SAGNN_T_CASE(2) SAGNN_T_CASE(3) SAGNN_T_CASE(4) SAGNN_T_CASE(5) SAGNN_T_CASE(6)
-    SAGNN_T_CASE(8) SAGNN_T_CASE(12) SAGNN_T_CASE(16)
-    default: return launch_ln_mhsa_t<D, 0, false>(x, ld_n, ld_t, n, t, heads, gamma, beta, eps, apply_ln, Wq, bq, Wk, bk, Wv, bv, out, ld_out, nullptr, nullptr, nullptr, s);
-  }
-#undef SAGNN_T_CASE
+static int ln_mhsa_mean_mfma_d(const SeqView& v, const AttnParams& a, float* out, int64_t ld_out, hipStream_t s) {
+  int rc;
+  const auto launch = [&](auto T) { return launch_ln_mhsa_t<D, decltype(T)::value, false>(v, a, out, ld_out, AttnBwdOut{}, s); };
+  if (dispatch_t(v.t, SpecialisedT{}, launch, rc)) return rc;
+  return launch(std::integral_constant<int, 0>{});   // any other t: the run-time form
 }
 
 // apply_ln = 0: plain MHSA + mean (gamma/beta ignored); 1: layer_norm over (t, d) first.
-int ln_mhsa_mean_mfma(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int d, int heads,
-                      const float* gamma, const float* beta, float eps, int apply_ln, const float* Wq,
-                      const float* bq, const float* Wk, const float* bk, const float* Wv,
-                      const float* bv, float* out, int64_t ld_out, hipStream_t s) {
-  if (d == 64)
-    return launch_ln_mhsa<64>(x, ld_n, ld_t, n, t, heads, gamma, beta, eps, apply_ln, Wq, bq, Wk, bk, Wv, bv, out, ld_out, s);
-  if (d == 32)
-    return launch_ln_mhsa<32>(x, ld_n, ld_t, n, t, heads, gamma, beta, eps, apply_ln, Wq, bq, Wk, bk, Wv, bv, out, ld_out, s);
-  return fail(SAGNN_ERR_DIM, "MFMA attention supports d = 32 or 64, got %d", d);
+int ln_mhsa_mean_mfma(const SeqView& v, const AttnParams& a, float* out, int64_t ld_out, hipStream_t s) {
+  if (v.d == 64) return ln_mhsa_mean_mfma_d<64>(v, a, out, ld_out, s);
+  if (v.d == 32) return ln_mhsa_mean_mfma_d<32>(v, a, out, ld_out, s);
+  return fail(SAGNN_ERR_DIM, "MFMA attention supports d = 32 or 64, got %d", v.d);
 }
 
 template <int D>
-static int launch_attn_bwd_front(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int heads,
-                                 const float* gamma, const float* beta, float eps, int apply_ln, const float* Wq,
-                                 const float* bq, const float* Wk, const float* bk, const float* Wv, const float* bv,
-                                 const float* g_out, int64_t ld_g, float* dqkv, float* y, hipStream_t s) {
-#define SAGNN_T_CASE(TT) \
-  case TT: return launch_ln_mhsa_t<D, TT, true>(x, ld_n, ld_t, n, t, heads, gamma, beta, eps, apply_ln, Wq, bq, Wk, bk, Wv, bv, nullptr, ld_g, g_out, dqkv, y, s);
-  switch (t) {
-    SAGNN_T_CASE(1) SAGNN_T_CASE(2) SAGNN_T_CASE(3) SAGNN_T_CASE(4) SAGNN_T_CASE(5) SAGNN_T_CASE(6) SAGNN_T_CASE(8)
-    default: return fail(SAGNN_ERR_DIM, "attention backward front: t = %d has no specialised kernel", t);
-  }
-#undef SAGNN_T_CASE
+static int attn_bwd_front_mfma_d(const SeqView& v, const AttnParams& a, const AttnBwdOut& b, hipStream_t s) {
+  int rc;
+  const auto launch = [&](auto T) { return launch_ln_mhsa_t<D, decltype(T)::value, true>(v, a, nullptr, 0, b, s); };
+  if (dispatch_t(v.t, MfmaBwdFrontT{}, launch, rc)) return rc;
+  return fail(SAGNN_ERR_DIM, "attention backward front: t = %d has no specialised kernel", v.t);
 }
 
 // Front of the attention backward pass: y = LN(x) (or x), Q|K|V, attention backward -> dqkv [n*t, 3d], y [n*t, d].
-int attn_bwd_front_mfma(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int d, int heads,
-                        const float* gamma, const float* beta, float eps, int apply_ln, const float* Wq,
-                        const float* bq, const float* Wk, const float* bk, const float* Wv, const float* bv,
-                        const float* g_out, int64_t ld_g, float* dqkv, float* y, hipStream_t s) {
-  if (d == 64)
-    return launch_attn_bwd_front<64>(x, ld_n, ld_t, n, t, heads, gamma, beta, eps, apply_ln, Wq, bq, Wk, bk, Wv, bv, g_out, ld_g, dqkv, y, s);
-  if (d == 32)
-    return launch_attn_bwd_front<32>(x, ld_n, ld_t, n, t, heads, gamma, beta, eps, apply_ln, Wq, bq, Wk, bk, Wv, bv, g_out, ld_g, dqkv, y, s);
-  return fail(SAGNN_ERR_DIM, "attention backward front supports d = 32 or 64, got %d", d);
+int attn_bwd_front_mfma(const SeqView& v, const AttnParams& a, const AttnBwdOut& b, hipStream_t s) {
+  if (v.d == 64) return attn_bwd_front_mfma_d<64>(v, a, b, s);
+  if (v.d == 32) return attn_bwd_front_mfma_d<32>(v, a, b, s);
+  return fail(SAGNN_ERR_DIM, "attention backward front supports d = 32 or 64, got %d", v.d);
 }
 
 }  // namespace sagnn

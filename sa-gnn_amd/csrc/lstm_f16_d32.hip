@@ -2,8 +2,8 @@
 #include "lstm_f16_kernel.h"
 
 namespace sagnn {
-int lstm_f16_d32(SAGNN_LSTM_F16_ARGS) {
-  if (drop) return launch_lstm_f16<32, false, true>(SAGNN_LSTM_F16_PASS);
-  return launch_lstm_f16<32, false, false>(SAGNN_LSTM_F16_PASS);
+int lstm_f16_d32(const LstmArgs& a, hipStream_t s) {
+  if (a.drop) return launch_lstm_f16<32, false, true>(a, s);
+  return launch_lstm_f16<32, false, false>(a, s);
 }
 }  // namespace sagnn

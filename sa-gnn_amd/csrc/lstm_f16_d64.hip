@@ -2,8 +2,8 @@
 #include "lstm_f16_kernel.h"
 
 namespace sagnn {
-int lstm_f16_d64(SAGNN_LSTM_F16_ARGS) {
-  if (drop) return launch_lstm_f16<64, false, true>(SAGNN_LSTM_F16_PASS);
-  return launch_lstm_f16<64, false, false>(SAGNN_LSTM_F16_PASS);
+int lstm_f16_d64(const LstmArgs& a, hipStream_t s) {
+  if (a.drop) return launch_lstm_f16<64, false, true>(a, s);
+  return launch_lstm_f16<64, false, false>(a, s);
 }
 }  // namespace sagnn

@@ -2,5 +2,5 @@
 #include "lstm_f16_kernel.h"
 
 namespace sagnn {
-int lstm_f16_d64_save(SAGNN_LSTM_F16_ARGS) { return launch_lstm_f16<64, true, false>(SAGNN_LSTM_F16_PASS); }
+int lstm_f16_d64_save(const LstmArgs& a, hipStream_t s) { return launch_lstm_f16<64, true, false>(a, s); }
 }  // namespace sagnn

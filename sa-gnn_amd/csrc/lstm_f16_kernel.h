@@ -517,32 +517,27 @@ __global__ __launch_bounds__(64 * (D / 16), 1) void lstm_fwd_f16_kernel(
 namespace sagnn {
 
 template <int D, bool SAVE, bool DROP>
-int launch_lstm_f16(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, const float* W, const float* b,
-                    float forget_bias, const float* drop, float* h, int64_t ld_h, float* gates_out, float* c_out,
-                    const float* h_init, int64_t ld_hi, const float* c_init, float* c_final, hipStream_t s) {
+int launch_lstm_f16(const LstmArgs& a, hipStream_t s) {
+  const SeqView& v = a.x;
   // x and h: 2 x 2 images each (96 KB at D = 64) + the flags; the slow pass needs 3 [rows][D] fp32 tiles (72 KB)
   const size_t lds = (size_t)8 * kRows * D * 2 + 16;
   if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&lstm_fwd_f16_kernel<D, SAVE, DROP>), lds)) return rc;
   const int per_cu = D == 64 ? 1 : 2;
-  const int64_t n_tiles = (n + kRows - 1) / kRows;
+  const int64_t n_tiles = (v.n + kRows - 1) / kRows;
   const int64_t want = (int64_t)cu_count_current() * per_cu;
   const int64_t blocks = n_tiles < want ? n_tiles : want;
-  ProfileScope prof(kProfLstm, s, n, t);
-  hipLaunchKernelGGL((lstm_fwd_f16_kernel<D, SAVE, DROP>), dim3((unsigned)blocks), dim3(64 * (D / 16)), lds, s, x, ld_n, ld_t,
-                     n, t, W, b, forget_bias, drop, h, ld_h, gates_out, c_out, n_tiles, h_init, ld_hi, c_init, c_final, redo_counter());
+  ProfileScope prof(kProfLstm, s, v.n, v.t);
+  hipLaunchKernelGGL((lstm_fwd_f16_kernel<D, SAVE, DROP>), dim3((unsigned)blocks), dim3(64 * (D / 16)), lds, s, v.x, v.ld_n, v.ld_t,
+                     v.n, v.t, a.W, a.b, a.forget_bias, a.drop, a.h, a.ld_h, a.gates, a.cell, n_tiles, a.h_init, a.ld_hi, a.c_init,
+                     a.c_final, redo_counter());
   SAGNN_HIP_TRY(hipGetLastError());
   return SAGNN_OK;
 }
 
 // One translation unit per (d, training) pair, as for the bf16 form.
-#define SAGNN_LSTM_F16_ARGS                                                                                       \
-  const float *x, int64_t ld_n, int64_t ld_t, int64_t n, int t, const float *W, const float *b, float forget_bias, \
-      const float *drop, float *h, int64_t ld_h, float *gates_out, float *c_out, const float *h_init, int64_t ld_hi, \
-      const float *c_init, float *c_final, hipStream_t s
-#define SAGNN_LSTM_F16_PASS x, ld_n, ld_t, n, t, W, b, forget_bias, drop, h, ld_h, gates_out, c_out, h_init, ld_hi, c_init, c_final, s
-int lstm_f16_d64(SAGNN_LSTM_F16_ARGS);        // inference (drop optional)
-int lstm_f16_d64_save(SAGNN_LSTM_F16_ARGS);   // training forward (stores gates / cell; no drop)
-int lstm_f16_d32(SAGNN_LSTM_F16_ARGS);
-int lstm_f16_d32_save(SAGNN_LSTM_F16_ARGS);
+int lstm_f16_d64(const LstmArgs& a, hipStream_t s);        // inference (drop optional)
+int lstm_f16_d64_save(const LstmArgs& a, hipStream_t s);   // training forward (stores gates / cell; no drop)
+int lstm_f16_d32(const LstmArgs& a, hipStream_t s);
+int lstm_f16_d32_save(const LstmArgs& a, hipStream_t s);
 
 }  // namespace sagnn

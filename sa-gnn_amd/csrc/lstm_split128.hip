@@ -277,18 +277,19 @@ static int launch_step(const float* x_t, int64_t ld_x, const float* h_prev, int6
 }
 
 // Same contract as lstm_fwd_mfma at d = 128. h [n, t, d] with row stride ld_h >= t*d. drop [n, t, d] (dense) is taken only
-// by the training form (gates_out / c_out given: the un-dropped h_{t-1} is re-made from them).
-int lstm_fwd_split128(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, const float* W, const float* b,
-                      float forget_bias, const float* drop, float* h, int64_t ld_h, float* gates_out, float* c_out,
-                      const float* h_init, int64_t ld_hi, const float* c_init, float* c_final, hipStream_t s) {
-  const bool save = gates_out != nullptr;
-  if (drop && !save) return fail(SAGNN_ERR_ARG, "d = 128 LSTM: an output-dropout mask needs the training form (saved gates / cell)");
+// by the training form (gates / cell given: the un-dropped h_{t-1} is re-made from them).
+int lstm_fwd_split128(const LstmArgs& a, hipStream_t s) {
+  const int64_t n = a.x.n, ld_h = a.ld_h;
+  const int t = a.x.t;
+  float* const h = a.h;
+  const bool save = a.gates != nullptr;
+  if (a.drop && !save) return fail(SAGNN_ERR_ARG, "d = 128 LSTM: an output-dropout mask needs the training form (saved gates / cell)");
   if (n <= 0) return SAGNN_OK;
   ProfileScope prof(kProfLstm, s, n, t);
   for (int ts = 0; ts < t; ++ts) {
-    const bool first = ts == 0 && h_init == nullptr;
-    const float* h_prev = ts == 0 ? h_init : h + (int64_t)(ts - 1) * D;
-    const int64_t ld_hp = ts == 0 ? ld_hi : ld_h;
+    const bool first = ts == 0 && a.h_init == nullptr;
+    const float* h_prev = ts == 0 ? a.h_init : h + (int64_t)(ts - 1) * D;
+    const int64_t ld_hp = ts == 0 ? a.ld_hi : ld_h;
     // cell state: saved states [n, t, d] when training; otherwise parked in h's NEXT slot (free until the next
     // step writes h there), and handed to c_final after the last step
     const float* c_prev;
@@ -296,33 +297,33 @@ int lstm_fwd_split128(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int
     float* c_dst;
     int64_t ld_c;
     if (save) {
-      c_prev = ts == 0 ? c_init : c_out + (int64_t)(ts - 1) * D;
+      c_prev = ts == 0 ? a.c_init : a.cell + (int64_t)(ts - 1) * D;
       ld_cp = ts == 0 ? D : (int64_t)t * D;
-      c_dst = c_out + (int64_t)ts * D;
+      c_dst = a.cell + (int64_t)ts * D;
       ld_c = (int64_t)t * D;
     } else {
-      c_prev = ts == 0 ? c_init : h + (int64_t)ts * D;
+      c_prev = ts == 0 ? a.c_init : h + (int64_t)ts * D;
       ld_cp = ts == 0 ? D : ld_h;
       const bool last = ts + 1 == t;
-      c_dst = last ? c_final : h + (int64_t)(ts + 1) * D;
+      c_dst = last ? a.c_final : h + (int64_t)(ts + 1) * D;
       ld_c = last ? D : ld_h;
     }
-    const float* x_t = x + (int64_t)ts * ld_t;
+    const float* x_t = a.x.x + (int64_t)ts * a.x.ld_t;
     float* h_t = h + (int64_t)ts * D;
-    float* g_t = save ? gates_out + (int64_t)ts * NC : nullptr;
+    float* g_t = save ? a.gates + (int64_t)ts * NC : nullptr;
     int rc;
 #define SAGNN_GO(SV, FI) \
-  rc = launch_step<SV, FI>(x_t, ld_n, h_prev, ld_hp, c_prev, ld_cp, W, b, forget_bias, h_t, ld_h, c_dst, ld_c, g_t, (int64_t)t * NC, n, \
-                           drop ? drop + (int64_t)ts * D : nullptr, (int64_t)t * D,                                                 \
-                           (drop && ts > 0) ? gates_out + (int64_t)(ts - 1) * NC + 3 * D : nullptr, s)
+  rc = launch_step<SV, FI>(x_t, a.x.ld_n, h_prev, ld_hp, c_prev, ld_cp, a.W, a.b, a.forget_bias, h_t, ld_h, c_dst, ld_c, g_t, (int64_t)t * NC, n, \
+                           a.drop ? a.drop + (int64_t)ts * D : nullptr, (int64_t)t * D,                                                 \
+                           (a.drop && ts > 0) ? a.gates + (int64_t)(ts - 1) * NC + 3 * D : nullptr, s)
     if (save && first) SAGNN_GO(true, true);
     else if (save) SAGNN_GO(true, false);
     else if (first) SAGNN_GO(false, true);
     else SAGNN_GO(false, false);
 #undef SAGNN_GO
     if (rc) return rc;
-    if (save && ts + 1 == t && c_final)   // the training entry does not ask for it; keep the contract anyway
-      SAGNN_HIP_TRY(hipMemcpy2DAsync(c_final, D * sizeof(float), c_out + (int64_t)ts * D, (size_t)t * D * sizeof(float),
+    if (save && ts + 1 == t && a.c_final)   // the training entry does not ask for it; keep the contract anyway
+      SAGNN_HIP_TRY(hipMemcpy2DAsync(a.c_final, D * sizeof(float), a.cell + (int64_t)ts * D, (size_t)t * D * sizeof(float),
                                      D * sizeof(float), (size_t)n, hipMemcpyDeviceToDevice, s));
   }
   return SAGNN_OK;

@@ -444,6 +444,12 @@ def _vec(name: str, v: torch.Tensor, numel: int):
     return v.data_ptr()
 
 
+def _attn_ptrs(d: int, Wq, bq, Wk, bk, Wv, bv):
+    """The six checked pointers of the attention's dense layers, in the order every attention entry takes them."""
+    return (_vec("Wq", Wq, d * d), _vec("bq", bq, d), _vec("Wk", Wk, d * d), _vec("bk", bk, d), _vec("Wv", Wv, d * d),
+            _vec("bv", bv, d))
+
+
 def _wide(d: int) -> bool:
     """d handled by the 'wide' MFMA composition (multiples of 32 other than the fused 32 / 64)."""
     return d % 32 == 0 and d not in (32, 64) and _lib.load().sagnn_get_engine() != ENGINES["valu"]
@@ -506,15 +512,11 @@ def mhsa_mean(x: torch.Tensor, Wq, bq, Wk, bk, Wv, bv, heads: int, out: torch.Te
     lib = _lib.load()
     if _wide(d) and _x_vec(x, ld, ldt):      # the wide entry takes aligned rows only; sagnn_mhsa_mean_f32 takes any
         ws = torch.empty(int(lib.sagnn_mhsa_wide_workspace_bytes(n, t, d)) // 4, dtype=torch.float32, device=x.device)
-        check(lib.sagnn_mhsa_mean_wide_f32(
-            x.data_ptr(), ld, ldt, n, t, d, int(heads), _vec("Wq", Wq, d * d), _vec("bq", bq, d),
-            _vec("Wk", Wk, d * d), _vec("bk", bk, d), _vec("Wv", Wv, d * d), _vec("bv", bv, d),
-            out.data_ptr(), ldo, ws.data_ptr(), ws.numel() * 4, _stream()))
+        check(lib.sagnn_mhsa_mean_wide_f32(x.data_ptr(), ld, ldt, n, t, d, int(heads), *_attn_ptrs(d, Wq, bq, Wk, bk, Wv, bv),
+                                           out.data_ptr(), ldo, ws.data_ptr(), ws.numel() * 4, _stream()))
         return out
-    check(lib.sagnn_mhsa_mean_f32(
-        x.data_ptr(), ld, ldt, n, t, d, int(heads), _vec("Wq", Wq, d * d), _vec("bq", bq, d),
-        _vec("Wk", Wk, d * d), _vec("bk", bk, d), _vec("Wv", Wv, d * d), _vec("bv", bv, d),
-        out.data_ptr(), ldo, _stream()))
+    check(lib.sagnn_mhsa_mean_f32(x.data_ptr(), ld, ldt, n, t, d, int(heads), *_attn_ptrs(d, Wq, bq, Wk, bk, Wv, bv),
+                                  out.data_ptr(), ldo, _stream()))
     return out
 
 
@@ -534,8 +536,7 @@ def ln_mhsa_mean(x: torch.Tensor, gamma, beta, Wq, bq, Wk, bk, Wv, bv, heads: in
     ws = torch.empty(need // 4, dtype=torch.float32, device=x.device) if need else None
     check(lib.sagnn_ln_mhsa_mean_f32(
         x.data_ptr(), ld, ldt, n, t, d, int(heads), _vec("gamma", gamma, d), _vec("beta", beta, d), float(eps),
-        _vec("Wq", Wq, d * d), _vec("bq", bq, d), _vec("Wk", Wk, d * d), _vec("bk", bk, d), _vec("Wv", Wv, d * d),
-        _vec("bv", bv, d), out.data_ptr(), ldo, _ptr(ws), need, _stream()))
+        *_attn_ptrs(d, Wq, bq, Wk, bk, Wv, bv), out.data_ptr(), ldo, _ptr(ws), need, _stream()))
     return out
 
 
@@ -554,10 +555,8 @@ def interval_fusion(x: torch.Tensor, p: dict, heads: int, out: torch.Tensor | No
     check(lib.sagnn_interval_fusion_f32(
         x.data_ptr(), ld, ldt, n, t, d, int(heads), _vec("lstm_W", p["lstm_W"], 8 * d * d),
         _vec("lstm_b", p["lstm_b"], 4 * d), 1.0, _vec("ln_gamma", p["ln_gamma"], d),
-        _vec("ln_beta", p["ln_beta"], d), 1e-12, _vec("Wq", p["Wq"], d * d), _vec("bq", p["bq"], d),
-        _vec("Wk", p["Wk"], d * d), _vec("bk", p["bk"], d), _vec("Wv", p["Wv"], d * d),
-        _vec("bv", p["bv"], d), out.data_ptr(), ldo, workspace.data_ptr(),
-        workspace.numel() * workspace.element_size(), _stream()))
+        _vec("ln_beta", p["ln_beta"], d), 1e-12, *_attn_ptrs(d, *(p[k] for k in ("Wq", "bq", "Wk", "bk", "Wv", "bv"))),
+        out.data_ptr(), ldo, workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream()))
     return out
 
 

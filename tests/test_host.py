@@ -141,6 +141,119 @@ def test_unaligned_attention_calls_are_refused_before_any_launch():
     assert wide(p + 4, 256) == -3 and wide(p, 257) == -3
 
 
+def test_fusion_entries_refuse_the_same_calls_with_the_same_codes():
+    """The eight fusion entries and the code each malformed call returns, one literal per (call, entry), recorded from the
+    library before its launchers took argument structs. Every call is one valid host-memory call (n = 4, t = 2, d = 64,
+    16 heads; the wide entry d = 128, 8 heads) with one or two arguments changed; the valid call itself is never made and
+    none of these reaches a launch. `_` marks an entry that does not read the argument or does not check it before its
+    first launch (the wide entry's and interval_fusion's ld_out; an unaligned x where a VALU kernel takes it). Where two
+    faults meet, the code says which check comes first: interval_fusion looks at its workspace before heads and
+    pointers, the backward front at the shape before pointers."""
+    lib = _lib.load()
+    buf = (ctypes.c_float * 8192)()
+    p = (ctypes.addressof(buf) + 15) & ~15
+    seq, qkv = "x ld_n ld_t n t d", "Wq bq Wk bk Wv bv"
+    lstm = f"{seq} W b forget_bias drop"
+    entries = {   # in the column order of `cases`
+        "sagnn_lstm_fwd_f32": f"{lstm} h ld_h stream",
+        "sagnn_lstm_fwd_state_f32": f"{lstm} h_init ld_hi c_init h ld_h c_final stream",
+        "sagnn_lstm_fwd_train_f32": f"{lstm} h ld_h gates cell stream",
+        "sagnn_mhsa_mean_f32": f"{seq} heads {qkv} out ld_out stream",
+        "sagnn_mhsa_mean_wide_f32": f"{seq} heads {qkv} out ld_out ws ws_bytes stream",
+        "sagnn_ln_mhsa_mean_f32": f"{seq} heads gamma beta eps {qkv} out ld_out ws ws_bytes stream",
+        "sagnn_interval_fusion_f32": f"{seq} heads W b forget_bias gamma beta eps {qkv} out ld_out ws ws_bytes stream",
+        "sagnn_attn_bwd_front_f32": f"{seq} heads gamma beta eps apply_ln {qkv} g_out ld_g dqkv y_out stream",
+    }
+    valid = dict(x=p, ld_n=128, ld_t=64, n=4, t=2, d=64, heads=16, W=p, b=p, forget_bias=1.0, drop=None, h=p, ld_h=128,
+                 gates=p, cell=p, h_init=p, ld_hi=64, c_init=p, c_final=p, gamma=p, beta=p, eps=1e-12, apply_ln=1, out=p,
+                 ld_out=64, ws=p, ws_bytes=4 * 2 * 64 * 4, g_out=p, ld_g=64, dqkv=p, y_out=p, stream=None,
+                 **dict.fromkeys(qkv.split(), p))
+    wide = dict(d=128, heads=8, ld_n=256, ld_t=128, ld_out=128, ws_bytes=4 * 2 * 3 * 128 * 4)
+    d128 = dict(d=128, ld_n=256, ld_t=128, ld_g=128)
+    _ = None
+    cases = [
+        # changed arguments                     fwd state train mhsa wide  ln fusion front
+        (dict(x=None),                          (-1, -1, -1, -1, -1, -1, -1, -1)),
+        (dict(W=None),                          (-1, -1, -1,  _,  _,  _, -1,  _)),
+        (dict(b=None),                          (-1, -1, -1,  _,  _,  _, -1,  _)),
+        (dict(h=None),                          (-1, -1, -1,  _,  _,  _,  _,  _)),
+        (dict(gates=None),                      ( _,  _, -1,  _,  _,  _,  _,  _)),
+        (dict(cell=None),                       ( _,  _, -1,  _,  _,  _,  _,  _)),
+        (dict(h_init=None),                     ( _, -1,  _,  _,  _,  _,  _,  _)),   # c_init without h_init
+        (dict(c_init=None),                     ( _, -1,  _,  _,  _,  _,  _,  _)),   # h_init without c_init
+        (dict(gamma=None),                      ( _,  _,  _,  _,  _, -1, -1, -1)),
+        (dict(beta=None),                       ( _,  _,  _,  _,  _, -1, -1, -1)),
+        *[(dict([(w, None)]),                   ( _,  _,  _, -1, -1, -1, -1, -1)) for w in qkv.split()],
+        (dict(out=None),                        ( _,  _,  _, -1, -1, -1, -1,  _)),
+        (dict(g_out=None),                      ( _,  _,  _,  _,  _,  _,  _, -1)),
+        (dict(dqkv=None),                       ( _,  _,  _,  _,  _,  _,  _, -1)),
+        (dict(ws=None),                         ( _,  _,  _,  _, -6,  _, -6,  _)),
+        (dict(d=62),                            (-2, -2, -2, -2, -2, -2, -2, -2)),
+        (dict(d=100, heads=4),                  ( _,  _,  _,  _, -2,  _,  _,  _)),   # a multiple of 4, not of 32
+        (dict(t=0),                             (-2, -2, -2, -2, -2, -2, -2, -2)),
+        (dict(t=65),                            (-2, -2, -2, -2, -2, -2, -2, -2)),
+        (dict(t=7),                             ( _,  _,  _,  _,  _,  _,  _, -2)),   # no backward front for it
+        (dict(d128, t=8),                       ( _,  _,  _,  _,  _,  _,  _, -2)),   # d = 128: the front stops at t = 6
+        (dict(heads=7),                         ( _,  _,  _, -2, -2, -2, -2, -2)),
+        (dict(heads=4),                         ( _,  _,  _,  _,  _,  _,  _, -2)),   # d / heads = 16: no backward front
+        (dict(ld_n=60),                         (-5, -5, -5, -5, -5, -5, -5, -5)),
+        (dict(ld_t=60),                         (-5, -5, -5, -5, -5, -5, -5, -5)),
+        (dict(ld_n=128, ld_t=128),              (-5, -5, -5, -5, -5, -5, -5, -5)),   # neither node- nor time-major
+        (dict(ld_out=60),                       ( _,  _,  _, -5,  _, -5,  _,  _)),
+        (dict(ld_g=60),                         ( _,  _,  _,  _,  _,  _,  _, -5)),
+        (dict(ld_h=124),                        (-5, -5, -5,  _,  _,  _,  _,  _)),
+        (dict(ld_hi=60),                        ( _, -5,  _,  _,  _,  _,  _,  _)),
+        (dict(x=p + 4),                         ( _,  _,  _,  _, -3,  _,  _, -3)),
+        (dict(ld_n=257),                        ( _,  _,  _,  _, -3,  _,  _,  _)),
+        (dict(ld_n=129),                        ( _,  _,  _,  _,  _,  _,  _, -3)),
+        (dict(g_out=p + 4),                     ( _,  _,  _,  _,  _,  _,  _, -3)),
+        (dict(ld_g=66),                         ( _,  _,  _,  _,  _,  _,  _, -3)),
+        (dict(dqkv=p + 4),                      ( _,  _,  _,  _,  _,  _,  _, -3)),
+        (dict(y_out=p + 4),                     ( _,  _,  _,  _,  _,  _,  _, -3)),
+        (dict(ws_bytes=4 * 2 * 3 * 128 * 4 - 4), ( _,  _,  _,  _, -6,  _,  _,  _)),   # one float short
+        (dict(ws_bytes=4 * 2 * 64 * 4 - 4),     ( _,  _,  _,  _,  _,  _, -6,  _)),
+        (dict(x=p + 4, ws_bytes=4 * 2 * 64 * 4 - 4), ( _,  _,  _,  _,  _, -6,  _,  _)),   # unaligned: y needs room
+        (dict(x=p + 4, ws=None),                ( _,  _,  _,  _,  _, -6,  _,  _)),
+        (dict(n=0),                             ( 0,  0,  0,  0,  0,  0,  0,  0)),
+        (dict(n=0, ws=None),                    ( _,  _,  _,  _,  0,  0,  0,  _)),
+        (dict(n=0, x=None),                     (-1, -1, -1, -1, -1, -1,  0, -1)),
+        (dict(n=-1),                            (-5, -5, -5, -5, -5, -5, -5, -5)),
+        # two faults in one call
+        (dict(d=62, x=None),                    (-2, -2, -2, -2, -2, -2, -2, -2)),
+        (dict(t=65, x=None),                    (-2, -2, -2, -2, -2, -2, -2, -2)),
+        (dict(heads=7, Wq=None),                ( _,  _,  _, -2, -2, -2, -2, -2)),
+        (dict(ws_bytes=4 * 2 * 3 * 128 * 4 - 4, out=None), ( _,  _,  _,  _, -1,  _,  _,  _)),
+        (dict(ws_bytes=4 * 2 * 64 * 4 - 4, out=None), ( _,  _,  _,  _,  _,  _, -6,  _)),
+        (dict(ws_bytes=4 * 2 * 64 * 4 - 4, heads=7), ( _,  _,  _,  _,  _,  _, -6,  _)),
+        (dict(x=p + 4, ws_bytes=4 * 2 * 64 * 4 - 4, out=None), ( _,  _,  _,  _,  _, -1,  _,  _)),
+        (dict(t=7, x=None),                     (-1, -1, -1, -1, -1, -1, -6, -2)),   # fusion: t = 7 outgrows the workspace
+        (dict(t=12, x=None),                    ( _,  _,  _,  _,  _,  _,  _, -1)),   # a supported shape: on to the pointers
+        (dict(d128, t=6, x=None),               ( _,  _,  _,  _,  _,  _,  _, -1)),
+        (dict(d128, t=8, x=None),               ( _,  _,  _,  _,  _,  _,  _, -2)),
+        (dict(ld_n=60, ld_out=60),              ( _,  _,  _, -5,  _, -5,  _,  _)),
+        (dict(ld_n=60, x=p + 4),                ( _,  _,  _,  _, -5,  _,  _, -5)),   # strides before alignment
+    ]
+    assert lib.sagnn_get_engine() == 0
+    got = []
+    for changed, codes in cases:
+        for (name, params), want in zip(entries.items(), codes):
+            if want is None:
+                continue
+            params = params.split()
+            assert set(changed) & set(params), (name, changed)     # never the valid call
+            args = {**valid, **(wide if "wide" in name else {}), **changed}
+            rc = getattr(lib, name)(*[args[k] for k in params])
+            got.append((name, changed, rc, want))
+    assert [g for g in got if g[2] != g[3]] == []
+    # under the fp32 engine the backward front has no t = 12 kernel, and says so before it looks at x
+    assert lib.sagnn_set_engine(1) == 0
+    try:
+        front = lambda t: lib.sagnn_attn_bwd_front_f32(None, 128, 64, 4, t, 64, 16, p, p, 1e-12, 1, p, p, p, p, p, p, p, 64, p, p, None)   # noqa: E731
+        assert (front(8), front(12)) == (-1, -2)
+    finally:
+        lib.sagnn_set_engine(0)
+
+
 def test_round3_entries_reject_bad_arguments_without_gpu():
     """The entries added in round 3 validate before they touch a device: segmented weight gradient, BPTT with scratch."""
     lib = _lib.load()
