@@ -266,6 +266,67 @@ int sagnn_gnn_stack_bwd_f32(const sagnn_spmm_batch* batch, const float* G_u, int
                             int64_t slab_di, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Edge dropout of the interval graphs (opt-in, training only; not in the reference, whose edgeDropout rewrites edge
+ * VALUES that messagePropagate never reads: model.py:93-102 vs :84-86). The drop forms below run the same kernels
+ * with one more step: the lane that loads an edge's column index decides whether the edge takes part.
+ *
+ *   keep(edge) = word 0 of Philox4x32-10(key = seed (low word first), counter = (user id, item id, tag, step))
+ *                < keep_threshold
+ *   tag        = (interval k << 8) | (layer l << 1) | dir    dir 0: the user-side product A e_i^l,
+ *                                                            dir 1: the item-side product A^T e_u^l
+ *   s[r,:]     = scale * sum over KEPT edges (r,c) of X[c,:]  then the epilogue of sagnn_spmm_ex_f32
+ *
+ * The decision depends on the edge's (user id, item id) only: not on its position in a CSR, not on the plan that
+ * stores it, not on the degree class that processes it. Duplicated stored entries share one decision. Hence the masked
+ * pattern of a product and the masked pattern of its exact transpose are transposes of each other, and the ADJOINT
+ * CONTRACT above carries over: the backward of layer l's user-side product runs on rows = items with the USER-side
+ * tag, the backward of the item-side product on rows = users with the item-side tag (the stack entries do this).
+ * keep_threshold = min(floor(keep * 2^32), 2^32 - 1) and scale = 1 / keep are computed by the host, once. Draws of
+ * different (k, l, dir, step) are independent. No atomics: a row's result is a deterministic function of its inputs.
+ *
+ * Every drop entry checks the sagnn_edge_drop before anything else: NULL, keep_threshold = 0, scale not finite or
+ * <= 0, n_layers > 127, an interval index >= 2^23 are refused with no device work done.
+ * -------------------------------------------------------------------------------- */
+typedef struct sagnn_edge_drop {
+  uint64_t seed;
+  uint32_t step;
+  uint32_t keep_threshold;
+  float scale;
+} sagnn_edge_drop;
+
+/* sagnn_spmm_ex_f32 as ONE masked product: `tag` as given, rows_are_users != 0 when the plan's rows are users (its
+ * column indices items), 0 when its rows are items. The same tag on the transposed plan with the flag swapped gives
+ * the exact transpose of the mask. */
+int sagnn_spmm_drop_f32(const sagnn_spmm_plan* plan, const float* X, int64_t ldx, int d,
+                        const sagnn_spmm_epilogue* epilogue, const sagnn_edge_drop* drop, uint32_t tag,
+                        int rows_are_users, void* workspace, size_t workspace_bytes, void* stream);
+/* sagnn_gnn_interval_ex_f32 / _bwd_f32 with edge dropout; `interval` is the k of the tags. The backward takes the
+ * sagnn_edge_drop and interval of its forward call, and the adjoint plans as sagnn_gnn_interval_bwd_f32 does. */
+int sagnn_gnn_interval_drop_f32(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item, const float* u0,
+                                int64_t ld_u0, const float* i0, int64_t ld_i0, int d, int n_layers, float leaky,
+                                float* scratch_u, float* scratch_i, float* user_out, int64_t ld_uo, float* item_out,
+                                int64_t ld_io, uint8_t* mask_u, uint8_t* mask_i, const sagnn_edge_drop* drop,
+                                int interval, void* workspace, size_t workspace_bytes, void* stream);
+int sagnn_gnn_interval_drop_bwd_f32(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item,
+                                    const float* G_u, int64_t ld_gu, const float* G_i, int64_t ld_gi, int d,
+                                    int n_layers, float leaky, const uint8_t* mask_u, const uint8_t* mask_i,
+                                    float* scratch_u, float* scratch_i, float* grad_u0, int64_t ld_du, float* grad_i0,
+                                    int64_t ld_di, const sagnn_edge_drop* drop, int interval, void* workspace,
+                                    size_t workspace_bytes, void* stream);
+/* sagnn_gnn_stack_f32 / _bwd_f32 with edge dropout: interval k of the batch drops with tag interval k. */
+int sagnn_gnn_stack_drop_f32(const sagnn_spmm_batch* batch, const float* u0, int64_t ld_u0, int64_t slab_u0,
+                             const float* i0, int64_t ld_i0, int64_t slab_i0, int d, int n_layers, float leaky,
+                             float* scratch_u, float* scratch_i, float* user_out, int64_t ld_uo, int64_t slab_uo,
+                             float* item_out, int64_t ld_io, int64_t slab_io, uint8_t* mask_u, uint8_t* mask_i,
+                             const sagnn_edge_drop* drop, void* workspace, size_t workspace_bytes, void* stream);
+int sagnn_gnn_stack_drop_bwd_f32(const sagnn_spmm_batch* batch, const float* G_u, int64_t ld_gu, int64_t slab_gu,
+                                 const float* G_i, int64_t ld_gi, int64_t slab_gi, int d, int n_layers, float leaky,
+                                 const uint8_t* mask_u, const uint8_t* mask_i, float* scratch_u, float* scratch_i,
+                                 float* grad_u0, int64_t ld_du, int64_t slab_du, float* grad_i0, int64_t ld_di,
+                                 int64_t slab_di, const sagnn_edge_drop* drop, void* workspace, size_t workspace_bytes,
+                                 void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Interval fusion (model.py:135-155). x[node, interval, :] is read at
  * x + node*ld_n + interval*ld_t (elements): [n, t, d] storage is ld_t = d, ld_n >= t*d (what
  * tf.stack + tf.transpose produce, model.py:131-134); [t, n, d] storage is ld_n = d,

@@ -66,6 +66,10 @@ _FLAGS = [
                                 "(only the rows the loss reads; the same loss and gradients, but dropout masks are drawn "
                                 "for those rows only, so a seeded run reproduces within a mode, not across modes; not in "
                                 "the reference)", ("all", "batch")),
+    ("edgeKeepRate", float, 1.0, "keep probability of the edge dropout on the interval graphs in training steps, in "
+                                 "(0, 1]; 1 = off. Not in the reference: its edgeDropout rewrites edge values that "
+                                 "messagePropagate never reads, so the op is dead there and --keepRate only reaches the "
+                                 "LSTM's output dropout"),
 ]
 
 

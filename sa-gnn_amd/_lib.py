@@ -4,7 +4,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_uint64, c_void_p
+from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_uint32, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SAGNN_LIB points at an alternative build (diagnostic variants under scratch/); default: in-tree
@@ -28,6 +28,11 @@ class SpmmEpilogue(ctypes.Structure):
                 ("ld_acc_out", c_int64), ("mask_out", c_void_p), ("mask_in", c_void_p),
                 ("out2", c_void_p), ("ldo2", c_int64), ("slope2", c_float), ("acc_in2", c_void_p),
                 ("ld_acc_in2", c_int64)]
+
+
+class EdgeDropArgs(ctypes.Structure):
+    """sagnn_edge_drop"""
+    _fields_ = [("seed", c_uint64), ("step", c_uint32), ("keep_threshold", c_uint32), ("scale", c_float)]
 
 
 class PlanInfo(ctypes.Structure):
@@ -74,6 +79,22 @@ SIGNATURES = {
     "sagnn_gnn_stack_bwd_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_int,
                                         c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
                                         c_void_p, c_int64, c_int64, c_void_p, c_size_t, c_void_p]),
+    "sagnn_spmm_drop_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int, POINTER(SpmmEpilogue), POINTER(EdgeDropArgs), c_uint32,
+                                    c_int, c_void_p, c_size_t, c_void_p]),
+    "sagnn_gnn_interval_drop_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int,
+                                            c_float, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
+                                            c_void_p, c_void_p, POINTER(EdgeDropArgs), c_int, c_void_p, c_size_t, c_void_p]),
+    "sagnn_gnn_interval_drop_bwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int,
+                                                c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                                c_void_p, c_int64, POINTER(EdgeDropArgs), c_int, c_void_p, c_size_t,
+                                                c_void_p]),
+    "sagnn_gnn_stack_drop_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_int,
+                                         c_float, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64,
+                                         c_void_p, c_void_p, POINTER(EdgeDropArgs), c_void_p, c_size_t, c_void_p]),
+    "sagnn_gnn_stack_drop_bwd_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_int,
+                                             c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                                             c_void_p, c_int64, c_int64, POINTER(EdgeDropArgs), c_void_p, c_size_t,
+                                             c_void_p]),
     "sagnn_gnn_interval_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
                                        c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int64,
                                        c_void_p, c_int64, c_void_p, c_size_t, c_void_p]),

@@ -27,7 +27,7 @@ class GnnStackFn(torch.autograd.Function):
     (sagnn_gnn_interval_ex_f32: graphs whose T-fold scratch would not fit)."""
 
     @staticmethod
-    def forward(ctx, u_embed, i_embed, plans_user, plans_item, n_layers, leaky):
+    def forward(ctx, u_embed, i_embed, plans_user, plans_item, n_layers, leaky, drop=None):
         T, U, d = u_embed.shape
         I = i_embed.shape[1]
         dev = u_embed.device
@@ -37,15 +37,16 @@ class GnnStackFn(torch.autograd.Function):
         mask_u = torch.empty((T, n_layers, U, d // 4), dtype=torch.uint8, device=dev)
         mask_i = torch.empty((T, n_layers, I, d // 4), dtype=torch.uint8, device=dev)
         if isinstance(plans_user, ops.SpmmBatch):
-            ops.gnn_stack(plans_user, ue, ie, n_layers, leaky, out_u, out_i, mask_u=mask_u, mask_i=mask_i)
+            ops.gnn_stack(plans_user, ue, ie, n_layers, leaky, out_u, out_i, mask_u=mask_u, mask_i=mask_i, drop=drop)
         else:
             scr_u = torch.empty((2, U, d), dtype=torch.float32, device=dev) if n_layers > 1 else None
             scr_i = torch.empty((2, I, d), dtype=torch.float32, device=dev) if n_layers > 1 else None
             for k in range(T):
                 ops.gnn_interval(plans_user[k], plans_item[k], ue[k], ie[k], n_layers, leaky, out_u[k], out_i[k], scr_u, scr_i,
-                                 mask_u=mask_u[k], mask_i=mask_i[k])
+                                 mask_u=mask_u[k], mask_i=mask_i[k], drop=drop, interval=k)
         ctx.save_for_backward(mask_u, mask_i)
         ctx.plans = (plans_user, plans_item)
+        ctx.drop = drop       # the backward drops the edges the forward dropped: the same ops.EdgeDrop
         ctx.cfg = (n_layers, leaky)
         return out_u, out_i
 
@@ -67,19 +68,20 @@ class GnnStackFn(torch.autograd.Function):
         du = torch.empty((T, U, d), dtype=torch.float32, device=dev)
         di = torch.empty((T, I, d), dtype=torch.float32, device=dev)
         if isinstance(plans_user, ops.SpmmBatch):
-            ops.gnn_stack_bwd(plans_user, g_user, g_item, n_layers, leaky, mask_u, mask_i, du, di)
-            return du, di, None, None, None, None
+            ops.gnn_stack_bwd(plans_user, g_user, g_item, n_layers, leaky, mask_u, mask_i, du, di, drop=ctx.drop)
+            return du, di, None, None, None, None, None
         scr_u = torch.empty((4, U, d), dtype=torch.float32, device=dev)
         scr_i = torch.empty((4, I, d), dtype=torch.float32, device=dev)
         for k in range(T):
             ops.gnn_interval_bwd(plans_user[k], plans_item[k], g_user[k], g_item[k], n_layers, leaky, mask_u[k], mask_i[k],
-                                 grad_u0=du[k], grad_i0=di[k], scratch_u=scr_u, scratch_i=scr_i)
-        return du, di, None, None, None, None
+                                 grad_u0=du[k], grad_i0=di[k], scratch_u=scr_u, scratch_i=scr_i, drop=ctx.drop, interval=k)
+        return du, di, None, None, None, None, None
 
 
-def gnn_stack(u_embed, i_embed, plans_user, plans_item, n_layers: int, leaky: float):
-    """plans_user: a list of T ops.SpmmPlan (with plans_item the matching list) or an ops.SpmmBatch (plans_item None)."""
-    return GnnStackFn.apply(u_embed, i_embed, plans_user, plans_item, n_layers, leaky)
+def gnn_stack(u_embed, i_embed, plans_user, plans_item, n_layers: int, leaky: float, drop=None):
+    """plans_user: a list of T ops.SpmmPlan (with plans_item the matching list) or an ops.SpmmBatch (plans_item None).
+    drop: an ops.EdgeDrop for edge dropout in the forward and, identically, in the backward; None = no dropout."""
+    return GnnStackFn.apply(u_embed, i_embed, plans_user, plans_item, n_layers, leaky, drop)
 
 
 def gnn_interval(u0, i0, plan_user, plan_item, n_layers: int, leaky: float):

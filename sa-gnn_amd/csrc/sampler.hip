@@ -8,6 +8,7 @@
 //
 // These kernels move a few kilobytes per batch (512 slots x at most 40 draws): one thread per draw, no LDS.
 #include "common.h"
+#include "philox.h"
 
 #include <limits.h>
 
@@ -15,23 +16,8 @@ namespace {
 
 constexpr int kBlock = 256;
 
-struct Word4 {
-  uint32_t x, y, z, w;
-};
-
-__device__ __forceinline__ Word4 philox4x32_10(Word4 c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    if (r) {
-      k0 += 0x9E3779B9u;
-      k1 += 0xBB67AE85u;
-    }
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c.x;
-    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c.z;
-    c = Word4{(uint32_t)(p1 >> 32) ^ c.y ^ k0, (uint32_t)p1, (uint32_t)(p0 >> 32) ^ c.w ^ k1, (uint32_t)p0};
-  }
-  return c;
-}
+using sagnn::Word4;
+using sagnn::philox4x32_10;
 
 // uniform on [0, n), n >= 1; bias at most n / 2^64
 __device__ __forceinline__ uint32_t draw(uint64_t seed, uint32_t user, uint32_t j, uint32_t step, uint32_t stream,

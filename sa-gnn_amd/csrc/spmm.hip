@@ -15,11 +15,19 @@
 //   long   (> long_thresh)       pre-cut into chunks (plan), one wave per chunk writing a raw
 //          partial sum, then a fix-up wave per row adds the partials in chunk order.
 // Column indices are fetched coalesced (one per lane) and broadcast with ds_bpermute.
+//
+// Edge dropout (the *_drop_* entries): the lane that loaded an edge's column index decides whether the
+// edge is kept — one Philox block per edge, a pure function of (seed, step, tag, user id, item id) — and replaces a
+// dropped index by -1 before the broadcast, so a dropped edge is a gather that is never issued. The drop kernels are
+// instantiations of their own (DROP = true); the default kernels compile to what they were without it.
+#include <float.h>
+
 #include <algorithm>
 #include <new>
 #include <vector>
 
 #include "common.h"
+#include "philox.h"
 
 namespace {
 
@@ -94,6 +102,46 @@ __device__ __forceinline__ void add4(float4& a, const float4& b) {
   a.w += b.w;
 }
 
+// Edge dropout of one product: the decision of edge (user, item) is word 0 of Philox4x32-10(key = seed, counter =
+// (user, item, tag, step)) < thresh. rows_users says which of (row, column index) is the user.
+struct RowDrop {
+  uint32_t k0, k1, step, thresh, tag;
+  int rows_users;
+  float scale;             // 1 / keep: multiplies the finished row sum
+};
+// Both directions of a batched launch: r.tag is the tag of the segments whose rows are users, tag_i that of the
+// item-row segments, both without the interval (seg_drop adds k << 8).
+struct BatchDrop {
+  RowDrop r;
+  uint32_t tag_i;
+};
+
+__device__ __forceinline__ RowDrop seg_drop(const BatchDrop& b, int dir, int k) {
+  RowDrop r = b.r;
+  r.tag = (dir ? b.tag_i : r.tag) | ((uint32_t)k << 8);
+  r.rows_users = !dir;
+  return r;
+}
+
+// The loading lane's filter: idx if edge (row, idx) is kept, else -1 (an index of -1 stays -1).
+template <bool DROP>
+__device__ __forceinline__ int keep_edge(const RowDrop& dr, int row, int idx) {
+  if constexpr (DROP) {
+    const uint32_t u = dr.rows_users ? (uint32_t)row : (uint32_t)idx;
+    const uint32_t i = dr.rows_users ? (uint32_t)idx : (uint32_t)row;
+    const sagnn::Word4 w = sagnn::philox4x32_10(sagnn::Word4{u, i, dr.tag, dr.step}, dr.k0, dr.k1);
+    return w.x < dr.thresh ? idx : -1;
+  } else {
+    return idx;
+  }
+}
+
+template <bool DROP>
+__device__ __forceinline__ float4 drop_scale(const RowDrop& dr, float4 s) {
+  if constexpr (DROP) return make_float4(dr.scale * s.x, dr.scale * s.y, dr.scale * s.z, dr.scale * s.w);
+  else return s;
+}
+
 // y = max(leaky*s, s) + residual ; out = y ; acc_out = acc_in + y (+ acc_in2) ; training extras as above.
 __device__ __forceinline__ void finish_row(const Epilogue& ep, int64_t row, int col, float4 s) {
   float4 y;
@@ -161,17 +209,20 @@ __global__ void mask_scale_kernel(const float* __restrict__ g, int64_t ldg, int6
 // Whole wave sums X[idx[e], :] for e in [e0, e1): G neighbour rows per load instruction.
 // IDENT: the "index" of edge e is e itself (fix-up pass over the partial-sum workspace).
 // Returns the total in every lane-group (cross-group xor reduction).
-template <int LPR, bool IDENT>
+// DROP: the edges belong to row `row`; each lane filters the 64-edge slice it loaded when the slice is taken up, so
+// the load of the next slice still overlaps this slice's gathers.
+template <int LPR, bool IDENT, bool DROP = false>
 __device__ __forceinline__ float4 wave_row_sum(const int32_t* __restrict__ colidx, int e0, int e1,
                                                const float* __restrict__ X, int64_t ldx,
-                                               int lane, int grp, int col, bool lane_on) {
+                                               int lane, int grp, int col, bool lane_on, const RowDrop& dr = RowDrop{},
+                                               int row = 0) {
   constexpr int G = kWave / LPR;
   constexpr int STEP = G * kUnroll;  // divides 64 for every LPR in {8,16,32,64}
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
   int idx_next = -1;
   if (e0 + lane < e1) idx_next = IDENT ? (e0 + lane) : ldi_s(colidx + e0 + lane);
   for (int e = e0; e < e1; e += kWave) {
-    const int idx = idx_next;
+    const int idx = keep_edge<DROP>(dr, row, idx_next);
     const int en = e + kWave;
     idx_next = -1;
     if (en + lane < e1) idx_next = IDENT ? (en + lane) : ldi_s(colidx + en + lane);
@@ -202,10 +253,11 @@ __device__ __forceinline__ float4 wave_row_sum(const int32_t* __restrict__ colid
 
 // A wave's share of the row blocks: RPW consecutive rows starting at row0 (short rows by lane groups, medium rows by
 // the whole wave; long rows belong to the chunk waves + fix-up).
-template <int LPR, int RPW>
+template <int LPR, int RPW, bool DROP = false>
 __device__ __forceinline__ void rows_wave(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
                                           const float* __restrict__ X, int64_t ldx, int d, int64_t n_rows, int64_t row0,
-                                          int short_t, int long_t, const Epilogue& ep, int lane) {
+                                          int short_t, int long_t, const Epilogue& ep, int lane,
+                                          const RowDrop& dr = RowDrop{}) {
   constexpr int G = kWave / LPR;
   const int grp = lane / LPR;
   const int sub = lane % LPR;
@@ -232,7 +284,8 @@ __device__ __forceinline__ void rows_wave(const int32_t* __restrict__ rowptr, co
     const int lr = it * G + grp;
     const int e0 = e0_n;
     const int dg = dg_n;
-    int idx = idx_n;
+    // DROP: the prefetched slice is filtered here, not where it was requested, so its load stays in flight
+    int idx = keep_edge<DROP>(dr, (int)row0 + lr, idx_n);
     const bool mine = (lr < nr) && (dg <= short_t);
     const int my_deg = mine ? dg : 0;
     if (it + 1 < RPW / G) {
@@ -251,7 +304,7 @@ __device__ __forceinline__ void rows_wave(const int32_t* __restrict__ rowptr, co
     for (int eo = 0; eo < maxdeg; eo += LPR) {
       if (eo > 0) {
         const int k = eo + sub;
-        idx = (k < my_deg) ? ldi_s(colidx + e0 + k) : -1;
+        idx = (k < my_deg) ? keep_edge<DROP>(dr, (int)row0 + lr, ldi_s(colidx + e0 + k)) : -1;
       }
       const int lim = min(LPR, maxdeg - eo);
       for (int j = 0; j < lim; j += kUnroll) {
@@ -268,7 +321,7 @@ __device__ __forceinline__ void rows_wave(const int32_t* __restrict__ rowptr, co
         for (int u = 0; u < kUnroll; ++u) add4(acc, v[u]);
       }
     }
-    if (mine && lane_on) finish_row(ep, row0 + lr, col, acc);
+    if (mine && lane_on) finish_row(ep, row0 + lr, col, drop_scale<DROP>(dr, acc));
   }
 
   // ---- medium rows: the whole wave per row ----------------------------------------------
@@ -277,8 +330,9 @@ __device__ __forceinline__ void rows_wave(const int32_t* __restrict__ rowptr, co
     medium &= medium - 1;
     const int e0 = __builtin_amdgcn_readlane(rp, lr);
     const int dg = __builtin_amdgcn_readlane(deg_l, lr);
-    const float4 s = wave_row_sum<LPR, false>(colidx, e0, e0 + dg, X, ldx, lane, grp, col, lane_on);
-    if (grp == 0 && lane_on) finish_row(ep, row0 + lr, col, s);
+    const float4 s =
+        wave_row_sum<LPR, false, DROP>(colidx, e0, e0 + dg, X, ldx, lane, grp, col, lane_on, dr, (int)row0 + lr);
+    if (grp == 0 && lane_on) finish_row(ep, row0 + lr, col, drop_scale<DROP>(dr, s));
   }
 }
 
@@ -327,6 +381,53 @@ __global__ __launch_bounds__(kBlock) void spmm_fixup_kernel(const int32_t* __res
   const float4 s = wave_row_sum<LPR, true>(nullptr, long_slot[li], long_slot[li + 1], partial, d,
                                            lane, grp, col, lane_on);
   if (grp == 0 && lane_on) finish_row(ep, long_row[li], col, s);
+}
+
+// The drop forms of the two kernels above. chunk_row[ci] is the row chunk ci belongs to (the default kernels never
+// need it); the partial sums stay unscaled and the fix-up scales the finished row once.
+template <int LPR, int RPW>
+__global__ __launch_bounds__(kBlock) void spmm_rows_drop_kernel(
+    const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
+    const float* __restrict__ X, int64_t ldx, int d, int64_t n_rows, int short_t, int long_t,
+    const int32_t* __restrict__ chunk_e0, const int32_t* __restrict__ chunk_e1,
+    const int32_t* __restrict__ chunk_row, int64_t n_chunks, int chunk_blocks, float* __restrict__ partial, Epilogue ep,
+    RowDrop dr) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wave = threadIdx.x / kWave;
+
+  if ((int)blockIdx.x < chunk_blocks) {
+    const int grp = lane / LPR;
+    const int col = 4 * (lane % LPR);
+    const bool lane_on = col < d;
+    const int64_t ci = (int64_t)blockIdx.x * kWavesPerBlock + wave;
+    if (ci >= n_chunks) return;
+    const float4 s = wave_row_sum<LPR, false, true>(colidx, chunk_e0[ci], chunk_e1[ci], X, ldx, lane, grp, col, lane_on,
+                                                    dr, chunk_row[ci]);
+    if (grp == 0 && lane_on) st4(partial + ci * (int64_t)d + col, s);
+    return;
+  }
+
+  const int64_t row0 = ((int64_t)(blockIdx.x - chunk_blocks) * kWavesPerBlock + wave) * RPW;
+  if (row0 >= n_rows) return;
+  rows_wave<LPR, RPW, true>(rowptr, colidx, X, ldx, d, n_rows, row0, short_t, long_t, ep, lane, dr);
+}
+
+template <int LPR>
+__global__ __launch_bounds__(kBlock) void spmm_fixup_drop_kernel(const int32_t* __restrict__ long_row,
+                                                                const int32_t* __restrict__ long_slot,
+                                                                int64_t n_long, const float* __restrict__ partial,
+                                                                int d, Epilogue ep, float scale) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wave = threadIdx.x / kWave;
+  const int grp = lane / LPR;
+  const int col = 4 * (lane % LPR);
+  const bool lane_on = col < d;
+  const int64_t li = (int64_t)blockIdx.x * kWavesPerBlock + wave;
+  if (li >= n_long) return;
+  const float4 s = wave_row_sum<LPR, true>(nullptr, long_slot[li], long_slot[li + 1], partial, d,
+                                           lane, grp, col, lane_on);
+  if (grp == 0 && lane_on)
+    finish_row(ep, long_row[li], col, make_float4(scale * s.x, scale * s.y, scale * s.z, scale * s.w));
 }
 
 
@@ -424,6 +525,68 @@ __global__ __launch_bounds__(kBlock) void spmm_fixup_batch_kernel(const int32_t*
   if (grp == 0 && lane_on) finish_row(ep, long_row[li], col, s);
 }
 
+// The drop forms of the two batched kernels: a segment's tag and orientation come from its (direction, interval).
+template <int LPR, int RPW>
+__global__ __launch_bounds__(kBlock) void spmm_rows_batch_drop_kernel(const SegMeta* __restrict__ meta, BatchGeom g,
+                                                                     const int32_t* __restrict__ chunk_e0,
+                                                                     const int32_t* __restrict__ chunk_e1,
+                                                                     const int32_t* __restrict__ chunk_seg,
+                                                                     const int32_t* __restrict__ chunk_row, int64_t n_chunks,
+                                                                     float* __restrict__ partial, int d, DirArgs au,
+                                                                     DirArgs ai, BatchDrop bd) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wave = threadIdx.x / kWave;
+  if ((int)blockIdx.x < g.chunk_blocks) {
+    const int grp = lane / LPR;
+    const int col = 4 * (lane % LPR);
+    const bool lane_on = col < d;
+    const int64_t ci = (int64_t)blockIdx.x * kWavesPerBlock + wave;
+    if (ci >= n_chunks) return;
+    const int seg = __builtin_amdgcn_readfirstlane(chunk_seg[ci]);
+    const int dir = seg >= g.T, k = seg - dir * g.T;
+    const DirArgs& a = dir ? ai : au;
+    const RowDrop dr = seg_drop(bd, dir, k);
+    const float4 s = wave_row_sum<LPR, false, true>(meta[seg].colidx, chunk_e0[ci], chunk_e1[ci], a.X + (int64_t)k * a.s_X,
+                                                    a.ldx, lane, grp, col, lane_on, dr, chunk_row[ci]);
+    if (grp == 0 && lane_on) st4(partial + ci * (int64_t)d + col, s);
+    return;
+  }
+  int rb = (int)blockIdx.x - g.chunk_blocks;
+  const int dir = rb >= g.T * g.blocks_u;
+  if (dir) rb -= g.T * g.blocks_u;
+  const int per = dir ? g.blocks_i : g.blocks_u;
+  const int k = rb / per;
+  const int64_t n_rows = dir ? g.rows_i : g.rows_u;
+  const int64_t row0 = ((int64_t)(rb - k * per) * kWavesPerBlock + wave) * RPW;
+  if (row0 >= n_rows) return;
+  const SegMeta m = meta[dir * g.T + k];
+  const DirArgs& a = dir ? ai : au;
+  const Epilogue ep = seg_epilogue(a, k);
+  rows_wave<LPR, RPW, true>(m.rowptr, m.colidx, a.X + (int64_t)k * a.s_X, a.ldx, d, n_rows, row0, m.short_t, m.long_t, ep,
+                            lane, seg_drop(bd, dir, k));
+}
+
+template <int LPR>
+__global__ __launch_bounds__(kBlock) void spmm_fixup_batch_drop_kernel(const int32_t* __restrict__ long_row,
+                                                                      const int32_t* __restrict__ long_slot,
+                                                                      const int32_t* __restrict__ long_seg, int64_t n_long,
+                                                                      const float* __restrict__ partial, int d, int T,
+                                                                      DirArgs au, DirArgs ai, float scale) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wave = threadIdx.x / kWave;
+  const int grp = lane / LPR;
+  const int col = 4 * (lane % LPR);
+  const bool lane_on = col < d;
+  const int64_t li = (int64_t)blockIdx.x * kWavesPerBlock + wave;
+  if (li >= n_long) return;
+  const int seg = __builtin_amdgcn_readfirstlane(long_seg[li]);
+  const int dir = seg >= T, k = seg - dir * T;
+  const Epilogue ep = seg_epilogue(dir ? ai : au, k);
+  const float4 s = wave_row_sum<LPR, true>(nullptr, long_slot[li], long_slot[li + 1], partial, d, lane, grp, col, lane_on);
+  if (grp == 0 && lane_on)
+    finish_row(ep, long_row[li], col, make_float4(scale * s.x, scale * s.y, scale * s.z, scale * s.w));
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------
@@ -436,10 +599,10 @@ struct sagnn_spmm_plan {
   // host copies of the chunk metadata (kept for tests / introspection)
   std::vector<int32_t> chunk_row, chunk_e0, chunk_e1;
   std::vector<int32_t> long_row, long_slot;  // long_slot has n_long+1 entries
-  // device copies: one allocation [chunk_e0 | chunk_e1 | long_row | long_slot]
+  // device copies: one allocation [chunk_e0 | chunk_e1 | long_row | long_slot | chunk_row]
   int32_t* d_meta = nullptr;
   const int32_t *d_chunk_e0 = nullptr, *d_chunk_e1 = nullptr, *d_long_row = nullptr,
-                *d_long_slot = nullptr;
+                *d_long_slot = nullptr, *d_chunk_row = nullptr;   // chunk_row: read by the drop kernels only
 };
 
 namespace {
@@ -538,7 +701,7 @@ extern "C" int sagnn_spmm_plan_create(const int32_t* h_rowptr, const int32_t* d_
   if (d_rowptr) {
     const size_t nck = p->chunk_row.size(), nl = p->long_row.size();
     if (nck > 0) {
-      const size_t words = 2 * nck + nl + (nl + 1);
+      const size_t words = 3 * nck + nl + (nl + 1);
       hipError_t e = hipMalloc((void**)&p->d_meta, words * sizeof(int32_t));
       if (e != hipSuccess) {
         delete p;
@@ -549,6 +712,7 @@ extern "C" int sagnn_spmm_plan_create(const int32_t* h_rowptr, const int32_t* d_
       std::copy(p->chunk_e1.begin(), p->chunk_e1.end(), host.begin() + nck);
       std::copy(p->long_row.begin(), p->long_row.end(), host.begin() + 2 * nck);
       std::copy(p->long_slot.begin(), p->long_slot.end(), host.begin() + 2 * nck + nl);
+      std::copy(p->chunk_row.begin(), p->chunk_row.end(), host.begin() + 2 * nck + 2 * nl + 1);
       e = hipMemcpy(p->d_meta, host.data(), words * sizeof(int32_t), hipMemcpyHostToDevice);
       if (e != hipSuccess) {
         (void)hipFree(p->d_meta);
@@ -559,6 +723,7 @@ extern "C" int sagnn_spmm_plan_create(const int32_t* h_rowptr, const int32_t* d_
       p->d_chunk_e1 = p->d_meta + nck;
       p->d_long_row = p->d_meta + 2 * nck;
       p->d_long_slot = p->d_meta + 2 * nck + nl;
+      p->d_chunk_row = p->d_meta + 2 * nck + 2 * nl + 1;
     }
     p->info.on_device = 1;
   }
@@ -601,9 +766,10 @@ extern "C" size_t sagnn_spmm_workspace_bytes(const sagnn_spmm_plan* plan, int d)
 // ------------------------------------------------------------------------------------------
 namespace {
 
+// drop = nullptr: the default kernels, launched as before the drop forms existed
 template <int LPR>
 int launch_spmm(const sagnn_spmm_plan* p, const float* X, int64_t ldx, int d, const Epilogue& ep,
-                float* partial, hipStream_t stream) {
+                float* partial, hipStream_t stream, const RowDrop* drop = nullptr) {
   const int64_t n_rows = p->info.n_rows;
   const int64_t n_chunks = p->info.n_chunks;
   const int64_t chunk_blocks = (n_chunks + kWavesPerBlock - 1) / kWavesPerBlock;
@@ -616,7 +782,17 @@ int launch_spmm(const sagnn_spmm_plan* p, const float* X, int64_t ldx, int d, co
   if (blocks > INT32_MAX) return sagnn::fail(SAGNN_ERR_ARG, "grid too large");
   if (blocks > 0) {
     sagnn::ProfileScope prof(sagnn::kProfSpmmRows, stream, p->info.nnz, n_rows);
-    if (small)
+    if (drop && small)
+      hipLaunchKernelGGL((spmm_rows_drop_kernel<LPR, RPW_SMALL>), dim3((unsigned)blocks), dim3(kBlock), 0, stream,
+                         p->d_rowptr, p->d_colidx, X, ldx, d, n_rows, p->info.short_thresh,
+                         p->info.long_thresh, p->d_chunk_e0, p->d_chunk_e1, p->d_chunk_row, n_chunks,
+                         (int)chunk_blocks, partial, ep, *drop);
+    else if (drop)
+      hipLaunchKernelGGL((spmm_rows_drop_kernel<LPR, kRowsPerWave>), dim3((unsigned)blocks), dim3(kBlock), 0, stream,
+                         p->d_rowptr, p->d_colidx, X, ldx, d, n_rows, p->info.short_thresh,
+                         p->info.long_thresh, p->d_chunk_e0, p->d_chunk_e1, p->d_chunk_row, n_chunks,
+                         (int)chunk_blocks, partial, ep, *drop);
+    else if (small)
       hipLaunchKernelGGL((spmm_rows_kernel<LPR, RPW_SMALL>), dim3((unsigned)blocks), dim3(kBlock), 0, stream,
                          p->d_rowptr, p->d_colidx, X, ldx, d, n_rows, p->info.short_thresh,
                          p->info.long_thresh, p->d_chunk_e0, p->d_chunk_e1, n_chunks,
@@ -632,8 +808,12 @@ int launch_spmm(const sagnn_spmm_plan* p, const float* X, int64_t ldx, int d, co
   if (n_long > 0) {
     sagnn::ProfileScope prof(sagnn::kProfSpmmFixup, stream, n_chunks, n_long);
     const int64_t fb = (n_long + kWavesPerBlock - 1) / kWavesPerBlock;
-    hipLaunchKernelGGL(spmm_fixup_kernel<LPR>, dim3((unsigned)fb), dim3(kBlock), 0, stream,
-                       p->d_long_row, p->d_long_slot, n_long, partial, d, ep);
+    if (drop)
+      hipLaunchKernelGGL(spmm_fixup_drop_kernel<LPR>, dim3((unsigned)fb), dim3(kBlock), 0, stream,
+                         p->d_long_row, p->d_long_slot, n_long, partial, d, ep, drop->scale);
+    else
+      hipLaunchKernelGGL(spmm_fixup_kernel<LPR>, dim3((unsigned)fb), dim3(kBlock), 0, stream,
+                         p->d_long_row, p->d_long_slot, n_long, partial, d, ep);
     SAGNN_HIP_TRY(hipGetLastError());
   }
   return SAGNN_OK;
@@ -676,7 +856,7 @@ int launch_mask_scale(const Slab& g, const uint8_t* mask, int64_t s_mask, float 
 
 // sagnn_spmm_ex_f32 on the kernels' own epilogue: every per-call check, then the launch(es) of one plan
 int spmm_ex(const sagnn_spmm_plan* plan, const float* X, int64_t ldx, int d, const Epilogue& e, void* workspace,
-            size_t workspace_bytes, void* stream) {
+            size_t workspace_bytes, void* stream, const RowDrop* drop = nullptr) {
   if (!plan->info.on_device) return sagnn::fail(SAGNN_ERR_ARG, "plan was built host-only (no device CSR)");
   if (int rc = check_d(d)) return rc;
   if (!e.out && !e.acc_out && !e.out2) return sagnn::fail(SAGNN_ERR_NULL, "no output given");
@@ -703,10 +883,10 @@ int spmm_ex(const sagnn_spmm_plan* plan, const float* X, int64_t ldx, int d, con
   hipStream_t s = static_cast<hipStream_t>(stream);
   float* partial = static_cast<float*>(workspace);
   switch (sagnn::lanes_per_row(d)) {
-    case 8: return launch_spmm<8>(plan, X, ldx, d, e, partial, s);
-    case 16: return launch_spmm<16>(plan, X, ldx, d, e, partial, s);
-    case 32: return launch_spmm<32>(plan, X, ldx, d, e, partial, s);
-    default: return launch_spmm<64>(plan, X, ldx, d, e, partial, s);
+    case 8: return launch_spmm<8>(plan, X, ldx, d, e, partial, s, drop);
+    case 16: return launch_spmm<16>(plan, X, ldx, d, e, partial, s, drop);
+    case 32: return launch_spmm<32>(plan, X, ldx, d, e, partial, s, drop);
+    default: return launch_spmm<64>(plan, X, ldx, d, e, partial, s, drop);
   }
 }
 
@@ -720,6 +900,40 @@ extern "C" int sagnn_spmm_ex_f32(const sagnn_spmm_plan* plan, const float* X, in
                     e->leaky,    e->mask_out,  e->mask_in, e->out2,      e->ldo2,  e->slope2, d / 4,
                     e->acc_in2,  e->ld_acc_in2};
   return spmm_ex(plan, X, ldx, d, ep, workspace, workspace_bytes, stream);
+}
+
+namespace {
+constexpr int kDropMaxLayers = 127;          // tag = (k << 8) | (l << 1) | dir: seven bits of layer
+constexpr int64_t kDropMaxIntervals = 1 << 23;
+
+// The caller's sagnn_edge_drop, checked ahead of everything else of a drop entry (no device work before it passes)
+int check_drop(const sagnn_edge_drop* drop, int n_layers, int64_t last_interval) {
+  if (!drop) return sagnn::fail(SAGNN_ERR_NULL, "edge drop: the sagnn_edge_drop is NULL");
+  if (drop->keep_threshold == 0) return sagnn::fail(SAGNN_ERR_ARG, "edge drop: keep_threshold = 0 keeps no edge");
+  if (!(drop->scale > 0.f) || !(drop->scale <= FLT_MAX))
+    return sagnn::fail(SAGNN_ERR_ARG, "edge drop: scale = %g, need a finite value > 0", (double)drop->scale);
+  if (n_layers > kDropMaxLayers)
+    return sagnn::fail(SAGNN_ERR_ARG, "edge drop: n_layers = %d, the tag holds %d", n_layers, kDropMaxLayers);
+  if (last_interval < 0 || last_interval >= kDropMaxIntervals)
+    return sagnn::fail(SAGNN_ERR_ARG, "edge drop: interval %lld outside [0, 2^23)", (long long)last_interval);
+  return SAGNN_OK;
+}
+
+RowDrop row_drop(const sagnn_edge_drop& e, uint32_t tag, bool rows_users) {
+  return RowDrop{(uint32_t)e.seed, (uint32_t)(e.seed >> 32), e.step, e.keep_threshold, tag, rows_users ? 1 : 0, e.scale};
+}
+}  // namespace
+
+extern "C" int sagnn_spmm_drop_f32(const sagnn_spmm_plan* plan, const float* X, int64_t ldx, int d,
+                                   const sagnn_spmm_epilogue* e, const sagnn_edge_drop* drop, uint32_t tag,
+                                   int rows_are_users, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = check_drop(drop, 0, 0)) return rc;
+  if (!plan || !e) return sagnn::fail(SAGNN_ERR_NULL, "plan/epilogue is NULL");
+  const Epilogue ep{e->residual, e->ldr,       e->acc_in,  e->ld_acc_in, e->out,   e->ldo,    e->acc_out, e->ld_acc_out,
+                    e->leaky,    e->mask_out,  e->mask_in, e->out2,      e->ldo2,  e->slope2, d / 4,
+                    e->acc_in2,  e->ld_acc_in2};
+  const RowDrop dr = row_drop(*drop, tag, rows_are_users != 0);
+  return spmm_ex(plan, X, ldx, d, ep, workspace, workspace_bytes, stream, &dr);
 }
 
 extern "C" int sagnn_spmm_f32(const sagnn_spmm_plan* plan, const float* X, int64_t ldx, int d,
@@ -771,11 +985,11 @@ struct sagnn_spmm_batch {
   int T = 0;
   int64_t U = 0, I = 0;
   int64_t n_chunks = 0, n_long = 0, nnz = 0;
-  // device: [SegMeta x 2T] and [chunk_e0 | chunk_e1 | chunk_seg | long_row | long_seg | long_slot (+1)]
+  // device: [SegMeta x 2T] and [chunk_e0 | chunk_e1 | chunk_seg | long_row | long_seg | long_slot (+1) | chunk_row]
   SegMeta* d_meta = nullptr;
   int32_t* d_ints = nullptr;
   const int32_t *d_chunk_e0 = nullptr, *d_chunk_e1 = nullptr, *d_chunk_seg = nullptr, *d_long_row = nullptr,
-                *d_long_seg = nullptr, *d_long_slot = nullptr;
+                *d_long_seg = nullptr, *d_long_slot = nullptr, *d_chunk_row = nullptr;
 };
 
 extern "C" int sagnn_spmm_batch_create(const sagnn_spmm_plan* const* plans_user, const sagnn_spmm_plan* const* plans_item,
@@ -798,7 +1012,7 @@ extern "C" int sagnn_spmm_batch_create(const sagnn_spmm_plan* const* plans_user,
   b->U = plans_user[0]->info.n_rows;
   b->I = plans_item[0]->info.n_rows;
   std::vector<SegMeta> meta(2 * (size_t)T);
-  std::vector<int32_t> ce0, ce1, cseg, lrow, lseg, lslot;
+  std::vector<int32_t> ce0, ce1, cseg, crow, lrow, lseg, lslot;
   try {
     for (int s = 0; s < 2 * T; ++s) {
       const sagnn_spmm_plan* p = s < T ? plans_user[s] : plans_item[s - T];
@@ -807,6 +1021,7 @@ extern "C" int sagnn_spmm_batch_create(const sagnn_spmm_plan* const* plans_user,
       ce0.insert(ce0.end(), p->chunk_e0.begin(), p->chunk_e0.end());
       ce1.insert(ce1.end(), p->chunk_e1.begin(), p->chunk_e1.end());
       cseg.insert(cseg.end(), p->chunk_e0.size(), (int32_t)s);
+      crow.insert(crow.end(), p->chunk_row.begin(), p->chunk_row.end());
       for (size_t j = 0; j < p->long_row.size(); ++j) {
         lrow.push_back(p->long_row[j]);
         lseg.push_back((int32_t)s);
@@ -830,13 +1045,14 @@ extern "C" int sagnn_spmm_batch_create(const sagnn_spmm_plan* const* plans_user,
   if (e == hipSuccess && b->n_chunks > 0) {
     const size_t nck = ce0.size(), nl = lrow.size();
     std::vector<int32_t> host;
-    host.reserve(3 * nck + 3 * nl + 1);
+    host.reserve(4 * nck + 3 * nl + 1);
     host.insert(host.end(), ce0.begin(), ce0.end());
     host.insert(host.end(), ce1.begin(), ce1.end());
     host.insert(host.end(), cseg.begin(), cseg.end());
     host.insert(host.end(), lrow.begin(), lrow.end());
     host.insert(host.end(), lseg.begin(), lseg.end());
     host.insert(host.end(), lslot.begin(), lslot.end());
+    host.insert(host.end(), crow.begin(), crow.end());
     e = hipMalloc((void**)&b->d_ints, host.size() * sizeof(int32_t));
     if (e == hipSuccess) e = hipMemcpy(b->d_ints, host.data(), host.size() * sizeof(int32_t), hipMemcpyHostToDevice);
     b->d_chunk_e0 = b->d_ints;
@@ -845,6 +1061,7 @@ extern "C" int sagnn_spmm_batch_create(const sagnn_spmm_plan* const* plans_user,
     b->d_long_row = b->d_ints + 3 * nck;
     b->d_long_seg = b->d_ints + 3 * nck + nl;
     b->d_long_slot = b->d_ints + 3 * nck + 2 * nl;
+    b->d_chunk_row = b->d_ints + 3 * nck + 3 * nl + 1;
   }
   if (e != hipSuccess) {
     if (b->d_meta) (void)hipFree(b->d_meta);
@@ -872,7 +1089,8 @@ extern "C" size_t sagnn_spmm_batch_workspace_bytes(const sagnn_spmm_batch* b, in
 namespace {
 
 template <int LPR>
-int launch_batch(const sagnn_spmm_batch* b, int d, const DirArgs& au, const DirArgs& ai, float* partial, hipStream_t stream) {
+int launch_batch(const sagnn_spmm_batch* b, int d, const DirArgs& au, const DirArgs& ai, float* partial, hipStream_t stream,
+                 const BatchDrop* drop) {
   constexpr int G = kWave / LPR;
   constexpr int RPW_SMALL = G > 4 ? G : 4;
   const bool small = (b->U > b->I ? b->U : b->I) < kSmallRows;
@@ -884,7 +1102,15 @@ int launch_batch(const sagnn_spmm_batch* b, int d, const DirArgs& au, const DirA
   const BatchGeom g{b->T, (int32_t)chunk_blocks, (int32_t)bu, (int32_t)bi, (int32_t)b->U, (int32_t)b->I};
   if (blocks > 0) {
     sagnn::ProfileScope prof(sagnn::kProfSpmmRows, stream, b->nnz, (int64_t)b->T * (b->U + b->I));
-    if (small)
+    if (drop && small)
+      hipLaunchKernelGGL((spmm_rows_batch_drop_kernel<LPR, RPW_SMALL>), dim3((unsigned)blocks), dim3(kBlock), 0, stream,
+                         b->d_meta, g, b->d_chunk_e0, b->d_chunk_e1, b->d_chunk_seg, b->d_chunk_row, b->n_chunks, partial, d,
+                         au, ai, *drop);
+    else if (drop)
+      hipLaunchKernelGGL((spmm_rows_batch_drop_kernel<LPR, kRowsPerWave>), dim3((unsigned)blocks), dim3(kBlock), 0, stream,
+                         b->d_meta, g, b->d_chunk_e0, b->d_chunk_e1, b->d_chunk_seg, b->d_chunk_row, b->n_chunks, partial, d,
+                         au, ai, *drop);
+    else if (small)
       hipLaunchKernelGGL((spmm_rows_batch_kernel<LPR, RPW_SMALL>), dim3((unsigned)blocks), dim3(kBlock), 0, stream, b->d_meta,
                          g, b->d_chunk_e0, b->d_chunk_e1, b->d_chunk_seg, b->n_chunks, partial, d, au, ai);
     else
@@ -895,19 +1121,24 @@ int launch_batch(const sagnn_spmm_batch* b, int d, const DirArgs& au, const DirA
   if (b->n_long > 0) {
     sagnn::ProfileScope prof(sagnn::kProfSpmmFixup, stream, b->n_chunks, b->n_long);
     const int64_t fb = (b->n_long + kWavesPerBlock - 1) / kWavesPerBlock;
-    hipLaunchKernelGGL(spmm_fixup_batch_kernel<LPR>, dim3((unsigned)fb), dim3(kBlock), 0, stream, b->d_long_row,
-                       b->d_long_slot, b->d_long_seg, b->n_long, partial, d, b->T, au, ai);
+    if (drop)
+      hipLaunchKernelGGL(spmm_fixup_batch_drop_kernel<LPR>, dim3((unsigned)fb), dim3(kBlock), 0, stream, b->d_long_row,
+                         b->d_long_slot, b->d_long_seg, b->n_long, partial, d, b->T, au, ai, drop->r.scale);
+    else
+      hipLaunchKernelGGL(spmm_fixup_batch_kernel<LPR>, dim3((unsigned)fb), dim3(kBlock), 0, stream, b->d_long_row,
+                         b->d_long_slot, b->d_long_seg, b->n_long, partial, d, b->T, au, ai);
     SAGNN_HIP_TRY(hipGetLastError());
   }
   return SAGNN_OK;
 }
 
-int launch_batch_d(const sagnn_spmm_batch* b, int d, const DirArgs& au, const DirArgs& ai, float* partial, hipStream_t s) {
+int launch_batch_d(const sagnn_spmm_batch* b, int d, const DirArgs& au, const DirArgs& ai, float* partial, hipStream_t s,
+                   const BatchDrop* drop = nullptr) {
   switch (sagnn::lanes_per_row(d)) {
-    case 8: return launch_batch<8>(b, d, au, ai, partial, s);
-    case 16: return launch_batch<16>(b, d, au, ai, partial, s);
-    case 32: return launch_batch<32>(b, d, au, ai, partial, s);
-    default: return launch_batch<64>(b, d, au, ai, partial, s);
+    case 8: return launch_batch<8>(b, d, au, ai, partial, s, drop);
+    case 16: return launch_batch<16>(b, d, au, ai, partial, s, drop);
+    case 32: return launch_batch<32>(b, d, au, ai, partial, s, drop);
+    default: return launch_batch<64>(b, d, au, ai, partial, s, drop);
   }
 }
 
@@ -1018,11 +1249,20 @@ DirArgs backward_step(const Stack& st, const Side& self, const Side& other, int 
   return a;
 }
 
-// The drivers: `launch(au, ai)` runs one layer, rows = users and rows = items (batched() or per_plan() below).
+// The edge-dropout tags of one launch pair (without the interval): tag_u for the launch whose rows are users, tag_i for
+// the one whose rows are items. dir 0 = the forward's user-side product A e_i, dir 1 = its item-side product A^T e_u.
+struct LayerTags {
+  uint32_t tag_u, tag_i;
+};
+
+// The drivers: `launch(au, ai, tags)` runs one layer, rows = users and rows = items (batched() or per_plan() below;
+// only the drop forms read the tags).
 template <class Launch>
 int run_forward(const Stack& st, Launch launch) {
   for (int l = 0; l < st.n_layers; ++l)
-    if (int rc = launch(forward_layer(st, st.u, st.i, l), forward_layer(st, st.i, st.u, l))) return rc;
+    if (int rc = launch(forward_layer(st, st.u, st.i, l), forward_layer(st, st.i, st.u, l),
+                        LayerTags{(uint32_t)l << 1, (uint32_t)l << 1 | 1u}))
+      return rc;
   return SAGNN_OK;
 }
 
@@ -1034,24 +1274,47 @@ int run_backward(const Stack& st, Launch launch, void* stream) {
                                    st.leaky, scratch_slot(st, *s, 2), s->rows, st.d, st.T, static_cast<hipStream_t>(stream)))
       return rc;
   }
+  // Step l's rows = users launch is the adjoint of layer l's ITEM-side product (it carries g_i^{l+1} back to the users
+  // through the transpose of the pattern that product gathered through), so it drops with that product's tag (dir 1)
+  // on rows that are users; the rows = items launch mirrors it with the user-side tag (dir 0).
   for (int l = st.n_layers - 1; l >= 0; --l)
-    if (int rc = launch(backward_step(st, st.u, st.i, l), backward_step(st, st.i, st.u, l))) return rc;
+    if (int rc = launch(backward_step(st, st.u, st.i, l), backward_step(st, st.i, st.u, l),
+                        LayerTags{(uint32_t)l << 1 | 1u, (uint32_t)l << 1}))
+      return rc;
   return SAGNN_OK;
 }
 
 // One launch per layer for all T intervals and both directions (+ one fix-up launch when the batch has long rows)
 auto batched(const sagnn_spmm_batch* b, int d, void* workspace, void* stream) {
-  return [=](const DirArgs& au, const DirArgs& ai) {
+  return [=](const DirArgs& au, const DirArgs& ai, const LayerTags&) {
     return launch_batch_d(b, d, au, ai, static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
+  };
+}
+
+auto batched_drop(const sagnn_spmm_batch* b, int d, void* workspace, void* stream, const sagnn_edge_drop& drop) {
+  return [=](const DirArgs& au, const DirArgs& ai, const LayerTags& t) {
+    const BatchDrop bd{row_drop(drop, t.tag_u, true), t.tag_i};
+    return launch_batch_d(b, d, au, ai, static_cast<float*>(workspace), static_cast<hipStream_t>(stream), &bd);
   };
 }
 
 // One interval: the user-side launch, then the item-side launch, each with the per-call checks of sagnn_spmm_ex_f32
 auto per_plan(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item, int d, void* workspace,
               size_t workspace_bytes, void* stream) {
-  return [=](const DirArgs& au, const DirArgs& ai) {
+  return [=](const DirArgs& au, const DirArgs& ai, const LayerTags&) {
     if (int rc = spmm_ex(plan_user, au.X, au.ldx, d, au.ep, workspace, workspace_bytes, stream)) return rc;
     return spmm_ex(plan_item, ai.X, ai.ldx, d, ai.ep, workspace, workspace_bytes, stream);
+  };
+}
+
+// per_plan with edge dropout; `interval` is the k of the tags
+auto per_plan_drop(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item, int d, void* workspace,
+                   size_t workspace_bytes, void* stream, const sagnn_edge_drop& drop, int interval) {
+  return [=](const DirArgs& au, const DirArgs& ai, const LayerTags& t) {
+    const uint32_t k = (uint32_t)interval << 8;
+    const RowDrop du = row_drop(drop, t.tag_u | k, true), di = row_drop(drop, t.tag_i | k, false);
+    if (int rc = spmm_ex(plan_user, au.X, au.ldx, d, au.ep, workspace, workspace_bytes, stream, &du)) return rc;
+    return spmm_ex(plan_item, ai.X, ai.ldx, d, ai.ep, workspace, workspace_bytes, stream, &di);
   };
 }
 
@@ -1059,12 +1322,12 @@ Slab slab(const float* p, int64_t ld, int64_t stride) { return Slab{const_cast<f
 
 }  // namespace
 
-extern "C" int sagnn_gnn_interval_ex_f32(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item,
-                                         const float* u0, int64_t ld_u0, const float* i0, int64_t ld_i0,
-                                         int d, int n_layers, float leaky, float* scratch_u,
-                                         float* scratch_i, float* user_out, int64_t ld_uo, float* item_out,
-                                         int64_t ld_io, uint8_t* mask_u, uint8_t* mask_i, void* workspace,
-                                         size_t workspace_bytes, void* stream) {
+// The four stack entries and their drop forms share these bodies: drop = nullptr is the entry without dropout.
+namespace {
+int interval_forward(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item, const float* u0, int64_t ld_u0,
+                     const float* i0, int64_t ld_i0, int d, int n_layers, float leaky, float* scratch_u, float* scratch_i,
+                     float* user_out, int64_t ld_uo, float* item_out, int64_t ld_io, uint8_t* mask_u, uint8_t* mask_i,
+                     const sagnn_edge_drop* drop, int interval, void* workspace, size_t workspace_bytes, void* stream) {
   if (int rc = check_interval_plans(plan_user, plan_item)) return rc;
   if (!u0 || !i0 || !user_out || !item_out) return sagnn::fail(SAGNN_ERR_NULL, "null embedding pointer");
   if (n_layers < 1) return sagnn::fail(SAGNN_ERR_ARG, "n_layers = %d: need >= 1", n_layers);
@@ -1078,7 +1341,90 @@ extern "C" int sagnn_gnn_interval_ex_f32(const sagnn_spmm_plan* plan_user, const
                  {slab(i0, ld_i0, 0), slab(item_out, ld_io, 0), scratch_i, mask_i, plan_item->info.n_rows},
                  1, d, n_layers, leaky};
   if (int rc = check_stack(st, n_layers > 1, "u0", "i0", "user_out", "item_out")) return rc;
+  if (drop)
+    return run_forward(st, per_plan_drop(plan_user, plan_item, d, workspace, workspace_bytes, stream, *drop, interval));
   return run_forward(st, per_plan(plan_user, plan_item, d, workspace, workspace_bytes, stream));
+}
+
+int interval_backward(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item, const float* G_u, int64_t ld_gu,
+                      const float* G_i, int64_t ld_gi, int d, int n_layers, float leaky, const uint8_t* mask_u,
+                      const uint8_t* mask_i, float* scratch_u, float* scratch_i, float* grad_u0, int64_t ld_du,
+                      float* grad_i0, int64_t ld_di, const sagnn_edge_drop* drop, int interval, void* workspace,
+                      size_t workspace_bytes, void* stream) {
+  if (int rc = check_interval_plans(plan_user, plan_item)) return rc;
+  if (!G_u || !G_i || !grad_u0 || !grad_i0 || !mask_u || !mask_i || !scratch_u || !scratch_i)
+    return sagnn::fail(SAGNN_ERR_NULL, "null pointer");
+  if (n_layers < 1) return sagnn::fail(SAGNN_ERR_ARG, "n_layers = %d: need >= 1", n_layers);
+  if (int rc = check_d(d)) return rc;
+  const Stack st{{slab(G_u, ld_gu, 0), slab(grad_u0, ld_du, 0), scratch_u, const_cast<uint8_t*>(mask_u), plan_user->info.n_rows},
+                 {slab(G_i, ld_gi, 0), slab(grad_i0, ld_di, 0), scratch_i, const_cast<uint8_t*>(mask_i), plan_item->info.n_rows},
+                 1, d, n_layers, leaky};
+  if (int rc = check_stack(st, true, "G_u", "G_i", "grad_u0", "grad_i0")) return rc;
+  if (drop)
+    return run_backward(st, per_plan_drop(plan_user, plan_item, d, workspace, workspace_bytes, stream, *drop, interval),
+                        stream);
+  return run_backward(st, per_plan(plan_user, plan_item, d, workspace, workspace_bytes, stream), stream);
+}
+
+int stack_forward(const sagnn_spmm_batch* b, const float* u0, int64_t ld_u0, int64_t slab_u0, const float* i0, int64_t ld_i0,
+                  int64_t slab_i0, int d, int n_layers, float leaky, float* scratch_u, float* scratch_i, float* user_out,
+                  int64_t ld_uo, int64_t slab_uo, float* item_out, int64_t ld_io, int64_t slab_io, uint8_t* mask_u,
+                  uint8_t* mask_i, const sagnn_edge_drop* drop, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!b) return sagnn::fail(SAGNN_ERR_NULL, "batch is NULL");
+  if (!u0 || !i0 || !user_out || !item_out) return sagnn::fail(SAGNN_ERR_NULL, "null embedding pointer");
+  if (int rc = check_d(d)) return rc;
+  if (n_layers < 1) return sagnn::fail(SAGNN_ERR_ARG, "n_layers = %d: need >= 1", n_layers);
+  if ((mask_u == nullptr) != (mask_i == nullptr)) return sagnn::fail(SAGNN_ERR_NULL, "give both masks or neither");
+  if (n_layers > 1 && (!scratch_u || !scratch_i)) return sagnn::fail(SAGNN_ERR_NULL, "scratch buffers required for n_layers > 1");
+  const Stack st{{slab(u0, ld_u0, slab_u0), slab(user_out, ld_uo, slab_uo), scratch_u, mask_u, b->U},
+                 {slab(i0, ld_i0, slab_i0), slab(item_out, ld_io, slab_io), scratch_i, mask_i, b->I},
+                 b->T, d, n_layers, leaky};
+  if (int rc = check_stack(st, n_layers > 1, "u0", "i0", "user_out", "item_out")) return rc;
+  if (int rc = check_batch_ws(b, d, workspace, workspace_bytes)) return rc;
+  if (drop) return run_forward(st, batched_drop(b, d, workspace, stream, *drop));
+  return run_forward(st, batched(b, d, workspace, stream));
+}
+
+int stack_backward(const sagnn_spmm_batch* b, const float* G_u, int64_t ld_gu, int64_t slab_gu, const float* G_i,
+                   int64_t ld_gi, int64_t slab_gi, int d, int n_layers, float leaky, const uint8_t* mask_u,
+                   const uint8_t* mask_i, float* scratch_u, float* scratch_i, float* grad_u0, int64_t ld_du, int64_t slab_du,
+                   float* grad_i0, int64_t ld_di, int64_t slab_di, const sagnn_edge_drop* drop, void* workspace,
+                   size_t workspace_bytes, void* stream) {
+  if (!b) return sagnn::fail(SAGNN_ERR_NULL, "batch is NULL");
+  if (!G_u || !G_i || !grad_u0 || !grad_i0 || !mask_u || !mask_i || !scratch_u || !scratch_i)
+    return sagnn::fail(SAGNN_ERR_NULL, "null pointer");
+  if (n_layers < 1) return sagnn::fail(SAGNN_ERR_ARG, "n_layers = %d: need >= 1", n_layers);
+  if (int rc = check_d(d)) return rc;
+  const Stack st{{slab(G_u, ld_gu, slab_gu), slab(grad_u0, ld_du, slab_du), scratch_u, const_cast<uint8_t*>(mask_u), b->U},
+                 {slab(G_i, ld_gi, slab_gi), slab(grad_i0, ld_di, slab_di), scratch_i, const_cast<uint8_t*>(mask_i), b->I},
+                 b->T, d, n_layers, leaky};
+  if (int rc = check_stack(st, true, "G_u", "G_i", "grad_u0", "grad_i0")) return rc;
+  if (int rc = check_batch_ws(b, d, workspace, workspace_bytes)) return rc;
+  if (drop) return run_backward(st, batched_drop(b, d, workspace, stream, *drop), stream);
+  return run_backward(st, batched(b, d, workspace, stream), stream);
+}
+}  // namespace
+
+extern "C" int sagnn_gnn_interval_ex_f32(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item,
+                                         const float* u0, int64_t ld_u0, const float* i0, int64_t ld_i0,
+                                         int d, int n_layers, float leaky, float* scratch_u,
+                                         float* scratch_i, float* user_out, int64_t ld_uo, float* item_out,
+                                         int64_t ld_io, uint8_t* mask_u, uint8_t* mask_i, void* workspace,
+                                         size_t workspace_bytes, void* stream) {
+  return interval_forward(plan_user, plan_item, u0, ld_u0, i0, ld_i0, d, n_layers, leaky, scratch_u, scratch_i, user_out,
+                          ld_uo, item_out, ld_io, mask_u, mask_i, nullptr, 0, workspace, workspace_bytes, stream);
+}
+
+// sagnn_gnn_interval_ex_f32 with edge dropout; `interval` is the k of the tags (this interval's index in the model)
+extern "C" int sagnn_gnn_interval_drop_f32(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item,
+                                           const float* u0, int64_t ld_u0, const float* i0, int64_t ld_i0, int d,
+                                           int n_layers, float leaky, float* scratch_u, float* scratch_i, float* user_out,
+                                           int64_t ld_uo, float* item_out, int64_t ld_io, uint8_t* mask_u, uint8_t* mask_i,
+                                           const sagnn_edge_drop* drop, int interval, void* workspace,
+                                           size_t workspace_bytes, void* stream) {
+  if (int rc = check_drop(drop, n_layers, interval)) return rc;
+  return interval_forward(plan_user, plan_item, u0, ld_u0, i0, ld_i0, d, n_layers, leaky, scratch_u, scratch_i, user_out,
+                          ld_uo, item_out, ld_io, mask_u, mask_i, drop, interval, workspace, workspace_bytes, stream);
 }
 
 extern "C" int sagnn_gnn_interval_f32(const sagnn_spmm_plan* plan_user,
@@ -1099,16 +1445,20 @@ extern "C" int sagnn_gnn_interval_bwd_f32(const sagnn_spmm_plan* plan_user, cons
                                           const uint8_t* mask_i, float* scratch_u, float* scratch_i,
                                           float* grad_u0, int64_t ld_du, float* grad_i0, int64_t ld_di,
                                           void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = check_interval_plans(plan_user, plan_item)) return rc;
-  if (!G_u || !G_i || !grad_u0 || !grad_i0 || !mask_u || !mask_i || !scratch_u || !scratch_i)
-    return sagnn::fail(SAGNN_ERR_NULL, "null pointer");
-  if (n_layers < 1) return sagnn::fail(SAGNN_ERR_ARG, "n_layers = %d: need >= 1", n_layers);
-  if (int rc = check_d(d)) return rc;
-  const Stack st{{slab(G_u, ld_gu, 0), slab(grad_u0, ld_du, 0), scratch_u, const_cast<uint8_t*>(mask_u), plan_user->info.n_rows},
-                 {slab(G_i, ld_gi, 0), slab(grad_i0, ld_di, 0), scratch_i, const_cast<uint8_t*>(mask_i), plan_item->info.n_rows},
-                 1, d, n_layers, leaky};
-  if (int rc = check_stack(st, true, "G_u", "G_i", "grad_u0", "grad_i0")) return rc;
-  return run_backward(st, per_plan(plan_user, plan_item, d, workspace, workspace_bytes, stream), stream);
+  return interval_backward(plan_user, plan_item, G_u, ld_gu, G_i, ld_gi, d, n_layers, leaky, mask_u, mask_i, scratch_u,
+                           scratch_i, grad_u0, ld_du, grad_i0, ld_di, nullptr, 0, workspace, workspace_bytes, stream);
+}
+
+// Backward of sagnn_gnn_interval_drop_f32: the same sagnn_edge_drop and interval as the forward call.
+extern "C" int sagnn_gnn_interval_drop_bwd_f32(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item,
+                                               const float* G_u, int64_t ld_gu, const float* G_i, int64_t ld_gi, int d,
+                                               int n_layers, float leaky, const uint8_t* mask_u, const uint8_t* mask_i,
+                                               float* scratch_u, float* scratch_i, float* grad_u0, int64_t ld_du,
+                                               float* grad_i0, int64_t ld_di, const sagnn_edge_drop* drop, int interval,
+                                               void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = check_drop(drop, n_layers, interval)) return rc;
+  return interval_backward(plan_user, plan_item, G_u, ld_gu, G_i, ld_gi, d, n_layers, leaky, mask_u, mask_i, scratch_u,
+                           scratch_i, grad_u0, ld_du, grad_i0, ld_di, drop, interval, workspace, workspace_bytes, stream);
 }
 
 // The whole GNN loop of model.py:118-129 — every interval, every layer — in L row launches (+ L fix-up launches when
@@ -1118,18 +1468,19 @@ extern "C" int sagnn_gnn_stack_f32(const sagnn_spmm_batch* b, const float* u0, i
                                    float* scratch_u, float* scratch_i, float* user_out, int64_t ld_uo, int64_t slab_uo,
                                    float* item_out, int64_t ld_io, int64_t slab_io, uint8_t* mask_u, uint8_t* mask_i,
                                    void* workspace, size_t workspace_bytes, void* stream) {
-  if (!b) return sagnn::fail(SAGNN_ERR_NULL, "batch is NULL");
-  if (!u0 || !i0 || !user_out || !item_out) return sagnn::fail(SAGNN_ERR_NULL, "null embedding pointer");
-  if (int rc = check_d(d)) return rc;
-  if (n_layers < 1) return sagnn::fail(SAGNN_ERR_ARG, "n_layers = %d: need >= 1", n_layers);
-  if ((mask_u == nullptr) != (mask_i == nullptr)) return sagnn::fail(SAGNN_ERR_NULL, "give both masks or neither");
-  if (n_layers > 1 && (!scratch_u || !scratch_i)) return sagnn::fail(SAGNN_ERR_NULL, "scratch buffers required for n_layers > 1");
-  const Stack st{{slab(u0, ld_u0, slab_u0), slab(user_out, ld_uo, slab_uo), scratch_u, mask_u, b->U},
-                 {slab(i0, ld_i0, slab_i0), slab(item_out, ld_io, slab_io), scratch_i, mask_i, b->I},
-                 b->T, d, n_layers, leaky};
-  if (int rc = check_stack(st, n_layers > 1, "u0", "i0", "user_out", "item_out")) return rc;
-  if (int rc = check_batch_ws(b, d, workspace, workspace_bytes)) return rc;
-  return run_forward(st, batched(b, d, workspace, stream));
+  return stack_forward(b, u0, ld_u0, slab_u0, i0, ld_i0, slab_i0, d, n_layers, leaky, scratch_u, scratch_i, user_out, ld_uo,
+                       slab_uo, item_out, ld_io, slab_io, mask_u, mask_i, nullptr, workspace, workspace_bytes, stream);
+}
+
+// sagnn_gnn_stack_f32 with edge dropout: interval k of the batch drops with tag interval k.
+extern "C" int sagnn_gnn_stack_drop_f32(const sagnn_spmm_batch* b, const float* u0, int64_t ld_u0, int64_t slab_u0,
+                                        const float* i0, int64_t ld_i0, int64_t slab_i0, int d, int n_layers, float leaky,
+                                        float* scratch_u, float* scratch_i, float* user_out, int64_t ld_uo, int64_t slab_uo,
+                                        float* item_out, int64_t ld_io, int64_t slab_io, uint8_t* mask_u, uint8_t* mask_i,
+                                        const sagnn_edge_drop* drop, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = check_drop(drop, n_layers, b ? b->T - 1 : 0)) return rc;
+  return stack_forward(b, u0, ld_u0, slab_u0, i0, ld_i0, slab_i0, d, n_layers, leaky, scratch_u, scratch_i, user_out, ld_uo,
+                       slab_uo, item_out, ld_io, slab_io, mask_u, mask_i, drop, workspace, workspace_bytes, stream);
 }
 
 // Backward of sagnn_gnn_stack_f32 (backward_step above): G_u / G_i are the gradients at the interval outputs as slabs,
@@ -1140,15 +1491,18 @@ extern "C" int sagnn_gnn_stack_bwd_f32(const sagnn_spmm_batch* b, const float* G
                                        const uint8_t* mask_u, const uint8_t* mask_i, float* scratch_u, float* scratch_i,
                                        float* grad_u0, int64_t ld_du, int64_t slab_du, float* grad_i0, int64_t ld_di,
                                        int64_t slab_di, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!b) return sagnn::fail(SAGNN_ERR_NULL, "batch is NULL");
-  if (!G_u || !G_i || !grad_u0 || !grad_i0 || !mask_u || !mask_i || !scratch_u || !scratch_i)
-    return sagnn::fail(SAGNN_ERR_NULL, "null pointer");
-  if (n_layers < 1) return sagnn::fail(SAGNN_ERR_ARG, "n_layers = %d: need >= 1", n_layers);
-  if (int rc = check_d(d)) return rc;
-  const Stack st{{slab(G_u, ld_gu, slab_gu), slab(grad_u0, ld_du, slab_du), scratch_u, const_cast<uint8_t*>(mask_u), b->U},
-                 {slab(G_i, ld_gi, slab_gi), slab(grad_i0, ld_di, slab_di), scratch_i, const_cast<uint8_t*>(mask_i), b->I},
-                 b->T, d, n_layers, leaky};
-  if (int rc = check_stack(st, true, "G_u", "G_i", "grad_u0", "grad_i0")) return rc;
-  if (int rc = check_batch_ws(b, d, workspace, workspace_bytes)) return rc;
-  return run_backward(st, batched(b, d, workspace, stream), stream);
+  return stack_backward(b, G_u, ld_gu, slab_gu, G_i, ld_gi, slab_gi, d, n_layers, leaky, mask_u, mask_i, scratch_u, scratch_i,
+                        grad_u0, ld_du, slab_du, grad_i0, ld_di, slab_di, nullptr, workspace, workspace_bytes, stream);
+}
+
+// Backward of sagnn_gnn_stack_drop_f32 on the adjoint batch: the same sagnn_edge_drop as the forward call.
+extern "C" int sagnn_gnn_stack_drop_bwd_f32(const sagnn_spmm_batch* b, const float* G_u, int64_t ld_gu, int64_t slab_gu,
+                                            const float* G_i, int64_t ld_gi, int64_t slab_gi, int d, int n_layers,
+                                            float leaky, const uint8_t* mask_u, const uint8_t* mask_i, float* scratch_u,
+                                            float* scratch_i, float* grad_u0, int64_t ld_du, int64_t slab_du,
+                                            float* grad_i0, int64_t ld_di, int64_t slab_di, const sagnn_edge_drop* drop,
+                                            void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = check_drop(drop, n_layers, b ? b->T - 1 : 0)) return rc;
+  return stack_backward(b, G_u, ld_gu, slab_gu, G_i, ld_gi, slab_gi, d, n_layers, leaky, mask_u, mask_i, scratch_u, scratch_i,
+                        grad_u0, ld_du, slab_du, grad_i0, ld_di, slab_di, drop, workspace, workspace_bytes, stream);
 }

@@ -249,7 +249,9 @@ class Recommender:
     def edgeDropout(self, mat):
         """reference model.py:93-102 rewrites edge VALUES only; messagePropagate never reads them
         (model.py:84-86), so the forward result is independent of keepRate and TF prunes the op.
-        Identity here."""
+        Identity here. Dropout that does reach the graph is opt-in and lives inside the SpMM kernels:
+        --edgeKeepRate below 1 makes train_loss drop edges (ops.EdgeDrop); this method
+        stays what the reference computes."""
         return mat
 
     def _define_fusion_params(self):
@@ -662,14 +664,17 @@ class Recommender:
             return v.to(self.device, torch.int32)
         return torch.as_tensor(np.asarray(v, dtype=np.int32), device=self.device)
 
-    def train_loss(self, batch, keep_rate=None):
+    def train_loss(self, batch, keep_rate=None, edge_keep=None):
         """The reference's loss for one step (model.py:104-205, 241-246) as a torch autograd graph
         whose nodes are HIP operators (sa_gnn_amd.autograd). batch: dict with uids, iids,
         uLocs_seq, sequence [args.batch, pos_length], mask, suids[k], siids[k]; a device-sampled batch
         (sample_batch_device) carries seq_seg = (seg_begin, seg_len) instead of sequence / mask. Returns
         (preLoss, sslloss) as 1-element tensors; total loss = preLoss + ssl_reg*sslloss (+ the L2
         term, applied inside the optimiser step). Under --fusion_rows batch the interval fusion runs on the rows the
-        loss reads only (_touched_rows, autograd.interval_fusion_rows); fu / fi stay full-size with zero rows elsewhere."""
+        loss reads only (_touched_rows, autograd.interval_fusion_rows); fu / fi stay full-size with zero rows elsewhere.
+        With an edge keep rate below 1 (edge_keep, default args.edgeKeepRate) the GNN stack drops edges, forward and
+        backward alike, keyed by batch["edge_seed"] = (seed, step) (default (0, 0)); every other entry point of the
+        model (forward, evaluators, recommend, parallel) never drops."""
         T, L, d, heads, leaky = args.graphNum, args.gnn_layer, args.latdim, args.num_attention_heads, NNs.leaky
         keep = args.keepRate if keep_rate is None else keep_rate
         subset = args.fusion_rows == "batch"
@@ -678,7 +683,9 @@ class Recommender:
                          suids=[self._i32(v) for v in batch["suids"]], siids=[self._i32(v) for v in batch["siids"]])
             touched = self._touched_rows(batch)
         # one autograd node for the whole interval loop; uv / iv are [T, N, d] slabs written in place
-        uv, iv = ag.gnn_stack(self.uEmbed, self.iEmbed, *self._stack_plans(), L, leaky)
+        edge_keep = args.edgeKeepRate if edge_keep is None else edge_keep
+        edge_drop = ops.EdgeDrop(*batch.get("edge_seed", (0, 0)), edge_keep) if edge_keep < 1.0 else None
+        uv, iv = ag.gnn_stack(self.uEmbed, self.iEmbed, *self._stack_plans(), L, leaky, drop=edge_drop)
         finals = []
         if subset:        # the one read-back of the step: the two counts, copied while the stack's launches queue
             touched["done"].synchronize()
@@ -920,6 +927,9 @@ class Recommender:
         device = args.sampler == "device"
         if device:        # one seed per epoch from numpy's global stream: np.random.seed still reproduces a run
             seed = int(np.random.randint(0, 2 ** 63, dtype=np.int64))
+        edge_drop = args.edgeKeepRate < 1.0
+        if edge_drop:     # its own seed per epoch, drawn only when the flag is on: a seeded run without it sees the
+            edge_seed = int(np.random.randint(0, 2 ** 63, dtype=np.int64))      # np.random stream it always saw
         # losses stay on the device until the epoch ends: a float() per step would make the host wait for the
         # step's kernels before it samples the next batch (host sampling and device work overlap this way)
         loss_sum = torch.zeros(1, dtype=torch.float32, device=self.device)
@@ -927,6 +937,8 @@ class Recommender:
         for i in range(steps):
             batIds = sfIds[i * args.batch:(i + 1) * args.batch]
             batch = self.sample_batch_device(batIds, seed, i) if device else self._host_train_batch(batIds)
+            if edge_drop:
+                batch["edge_seed"] = (edge_seed, i)
             params = self._trainable()
             for p in params.values():
                 p.grad = None
@@ -987,6 +999,8 @@ class Recommender:
     def prepareModel(self):
         """reference model.py:207-240 up to the call of ours(): adjacency constants for every
         interval and both directions, leaky slope, then the hot path."""
+        if not 0.0 < args.edgeKeepRate <= 1.0:
+            raise ValueError(f"--edgeKeepRate {args.edgeKeepRate}: need a rate in (0, 1]")
         NNs.reset(self.device)
         NNs.leaky = args.leaky
         self.actFunc = "leakyRelu"

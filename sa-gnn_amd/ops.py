@@ -3,6 +3,7 @@ out. torch is used for device memory and streams only — no arithmetic happens 
 from __future__ import annotations
 
 import ctypes
+import math
 
 import numpy as np
 import torch
@@ -179,7 +180,8 @@ def spmm(plan: SpmmPlan, x: torch.Tensor, leaky: float, residual: torch.Tensor |
 
 
 def spmm_ex(plan: SpmmPlan, x: torch.Tensor | None, leaky: float, residual=None, out=None, acc_in=None, acc_out=None,
-            acc_in2=None, mask_out=None, mask_in=None, out2=None, slope2: float = 1.0, want_out: bool = False):
+            acc_in2=None, mask_out=None, mask_in=None, out2=None, slope2: float = 1.0, want_out: bool = False,
+            _drop=None):
     """sagnn_spmm_ex_f32: spmm plus the training epilogue — mask_out [rows, d/4] uint8 records the activation slopes,
     out2 = v * (mask_in bit ? 1 : slope2) with v the accumulated value if acc_out is given, acc_in2 a second addend."""
     ref = next(t_ for t_ in (x, residual, out, acc_out, out2) if t_ is not None)
@@ -200,9 +202,59 @@ def spmm_ex(plan: SpmmPlan, x: torch.Tensor | None, leaky: float, residual=None,
     e.mask_out, e.mask_in = _ptr(mask_out), _ptr(mask_in)
     ldx = _f32_rows("x", x, d, plan.n_src) if x is not None else d
     ws = plan.workspace(d)
+    if _drop is not None:       # spmm_drop
+        drop, tag, rows_are_users = _drop
+        check(plan._lib.sagnn_spmm_drop_f32(plan.handle, _ptr(x), ldx, d, ctypes.byref(e), ctypes.byref(drop.struct()), tag,
+                                            int(rows_are_users), _ptr(ws), 0 if ws is None else ws.numel() * 4, _stream()))
+        return out
     check(plan._lib.sagnn_spmm_ex_f32(plan.handle, _ptr(x), ldx, d, ctypes.byref(e), _ptr(ws), 0 if ws is None else ws.numel() * 4,
                                       _stream()))
     return out
+
+
+class EdgeDrop:
+    """Edge dropout of the interval graphs for one training step (sagnn_edge_drop, include/sagnn.h): every edge of
+    every (interval, layer, direction) product is kept with probability `keep`, by a Philox draw keyed on
+    (seed, step, interval, layer, direction, user id, item id), and the row sums are scaled by 1 / keep. The threshold
+    and the scale are fixed here, once, so that host and device never disagree about a rounding. Not in the reference:
+    its edgeDropout rewrites edge values that messagePropagate never reads (model.py:93-102, :84-86)."""
+
+    def __init__(self, seed: int, step: int, keep: float):
+        keep = float(keep)
+        if not 0.0 < keep <= 1.0:
+            raise ValueError(f"EdgeDrop: keep = {keep}, need 0 < keep <= 1")
+        if not 0 <= int(seed) < 2 ** 64 or not 0 <= int(step) < 2 ** 32:
+            raise ValueError(f"EdgeDrop: seed = {seed}, step = {step}: need 0 <= seed < 2^64, 0 <= step < 2^32")
+        self.seed, self.step, self.keep = int(seed), int(step), keep
+        self.threshold = min(int(math.floor(keep * 2.0 ** 32)), 2 ** 32 - 1)
+        self.scale = float(np.float32(1.0) / np.float32(keep))
+        if self.threshold == 0:
+            raise ValueError(f"EdgeDrop: keep = {keep} is below 2^-32: no edge would be kept")
+
+    @classmethod
+    def raw(cls, seed: int, step: int, threshold: int, scale: float) -> "EdgeDrop":
+        """An EdgeDrop with the threshold and the scale given directly (tests and benchmarks: threshold 2^32 - 1 with
+        scale 1 keeps every edge, which leaves the cost of the draw alone)."""
+        self = cls(seed, step, 1.0)
+        self.threshold, self.scale, self.keep = int(threshold), float(scale), int(threshold) / 2.0 ** 32
+        return self
+
+    def struct(self) -> "_lib.EdgeDropArgs":
+        return _lib.EdgeDropArgs(self.seed, self.step, self.threshold, self.scale)
+
+
+def edge_tag(interval: int, layer: int, direction: int) -> int:
+    """The tag of one product of the stack: direction 0 = user-side (A e_i), 1 = item-side (A^T e_u)."""
+    return (int(interval) << 8) | (int(layer) << 1) | int(direction)
+
+
+def spmm_drop(plan: SpmmPlan, x: torch.Tensor | None, leaky: float, drop: EdgeDrop, tag: int, rows_are_users: bool,
+              residual=None, out=None, acc_in=None, acc_out=None, acc_in2=None, mask_out=None, mask_in=None, out2=None,
+              slope2: float = 1.0, want_out: bool = False):
+    """sagnn_spmm_drop_f32: spmm_ex as one masked product — edge (user, item) takes part iff `drop` keeps it under `tag`;
+    rows_are_users says whether the plan's rows are users (its column indices items) or the other way round."""
+    return spmm_ex(plan, x, leaky, residual, out, acc_in, acc_out, acc_in2, mask_out, mask_in, out2, slope2, want_out,
+                   _drop=(drop, int(tag), bool(rows_are_users)))
 
 
 def mask_scale(g: torch.Tensor, mask: torch.Tensor, slope: float, out: torch.Tensor):
@@ -253,8 +305,10 @@ def _adjoint_pair(plan_user: SpmmPlan, plan_item: SpmmPlan):
 def gnn_interval(plan_user: SpmmPlan, plan_item: SpmmPlan, u0: torch.Tensor, i0: torch.Tensor,
                  n_layers: int, leaky: float, user_out: torch.Tensor, item_out: torch.Tensor,
                  scratch_u: torch.Tensor | None = None, scratch_i: torch.Tensor | None = None,
-                 mask_u: torch.Tensor | None = None, mask_i: torch.Tensor | None = None):
-    """One interval of the GNN loop (reference model.py:118-129): sagnn_gnn_interval_[ex_]f32.
+                 mask_u: torch.Tensor | None = None, mask_i: torch.Tensor | None = None,
+                 drop: EdgeDrop | None = None, interval: int = 0):
+    """One interval of the GNN loop (reference model.py:118-129): sagnn_gnn_interval_[ex_]f32; with `drop`, edge
+    dropout under the tags of interval `interval` (sagnn_gnn_interval_drop_f32).
     user_out / item_out are [rows, d] views (any row stride, e.g. a column of an [N, T, d] slab).
     mask_u [L, U, d/4] / mask_i [L, I, d/4] uint8 (both or neither) record the activation masks
     the backward pass needs."""
@@ -272,6 +326,13 @@ def gnn_interval(plan_user: SpmmPlan, plan_item: SpmmPlan, u0: torch.Tensor, i0:
     if mask_i is not None:
         _masks("mask_i", mask_i, (n_layers, I, d // 4))
     ws = _interval_ws(plan_user, plan_item, d)
+    if drop is not None:
+        check(plan_user._lib.sagnn_gnn_interval_drop_f32(
+            plan_user.handle, plan_item.handle, _ptr(u0), ld_u0, _ptr(i0), ld_i0, d, int(n_layers),
+            float(leaky), _ptr(scratch_u), _ptr(scratch_i), _ptr(user_out), ld_uo, _ptr(item_out), ld_io,
+            _ptr(mask_u), _ptr(mask_i), ctypes.byref(drop.struct()), int(interval), _ptr(ws),
+            0 if ws is None else ws.numel() * 4, _stream()))
+        return user_out, item_out
     check(plan_user._lib.sagnn_gnn_interval_ex_f32(
         plan_user.handle, plan_item.handle, _ptr(u0), ld_u0, _ptr(i0), ld_i0, d, int(n_layers),
         float(leaky), _ptr(scratch_u), _ptr(scratch_i), _ptr(user_out), ld_uo, _ptr(item_out), ld_io,
@@ -283,9 +344,10 @@ def gnn_interval_bwd(plan_user: SpmmPlan, plan_item: SpmmPlan, grad_user_out: to
                      grad_item_out: torch.Tensor, n_layers: int, leaky: float, mask_u: torch.Tensor,
                      mask_i: torch.Tensor, grad_u0: torch.Tensor | None = None,
                      grad_i0: torch.Tensor | None = None, scratch_u: torch.Tensor | None = None,
-                     scratch_i: torch.Tensor | None = None):
+                     scratch_i: torch.Tensor | None = None, drop: EdgeDrop | None = None, interval: int = 0):
     """Backward of gnn_interval (sagnn_gnn_interval_bwd_f32): dL/d(user_out), dL/d(item_out) and the
-    recorded masks -> dL/d u0 [U, d], dL/d i0 [I, d]."""
+    recorded masks -> dL/d u0 [U, d], dL/d i0 [I, d]. `drop` / `interval`: those of the forward call
+    (sagnn_gnn_interval_drop_bwd_f32)."""
     d = int(grad_user_out.shape[1])
     U, I = plan_user.n_rows, plan_item.n_rows
     plan_user, plan_item = _adjoint_pair(plan_user, plan_item)
@@ -303,6 +365,13 @@ def gnn_interval_bwd(plan_user: SpmmPlan, plan_item: SpmmPlan, grad_user_out: to
     _masks("mask_u", mask_u, (n_layers, U, d // 4))
     _masks("mask_i", mask_i, (n_layers, I, d // 4))
     ws = _interval_ws(plan_user, plan_item, d)
+    if drop is not None:
+        check(plan_user._lib.sagnn_gnn_interval_drop_bwd_f32(
+            plan_user.handle, plan_item.handle, _ptr(grad_user_out), ld_gu, _ptr(grad_item_out), ld_gi, d,
+            int(n_layers), float(leaky), _ptr(mask_u), _ptr(mask_i), _ptr(scratch_u), _ptr(scratch_i),
+            _ptr(grad_u0), ld_du, _ptr(grad_i0), ld_di, ctypes.byref(drop.struct()), int(interval), _ptr(ws),
+            0 if ws is None else ws.numel() * 4, _stream()))
+        return grad_u0, grad_i0
     check(plan_user._lib.sagnn_gnn_interval_bwd_f32(
         plan_user.handle, plan_item.handle, _ptr(grad_user_out), ld_gu, _ptr(grad_item_out), ld_gi, d,
         int(n_layers), float(leaky), _ptr(mask_u), _ptr(mask_i), _ptr(scratch_u), _ptr(scratch_i),
@@ -373,8 +442,10 @@ def _slab(name: str, x: torch.Tensor, T: int, rows: int, d: int):
 
 def gnn_stack(batch: SpmmBatch, u0: torch.Tensor, i0: torch.Tensor, n_layers: int, leaky: float,
               user_out: torch.Tensor, item_out: torch.Tensor, scratch_u: torch.Tensor | None = None,
-              scratch_i: torch.Tensor | None = None, mask_u: torch.Tensor | None = None, mask_i: torch.Tensor | None = None):
-    """Every interval of the GNN loop (reference model.py:118-129) in one launch per layer: sagnn_gnn_stack_f32.
+              scratch_i: torch.Tensor | None = None, mask_u: torch.Tensor | None = None, mask_i: torch.Tensor | None = None,
+              drop: EdgeDrop | None = None):
+    """Every interval of the GNN loop (reference model.py:118-129) in one launch per layer: sagnn_gnn_stack_f32; with
+    `drop`, edge dropout (sagnn_gnn_stack_drop_f32).
     u0 [T, U, d], i0 [T, I, d]; user_out / item_out indexed [T, N, d] (e.g. `x.permute(1, 0, 2)` of the [N, T, d]
     tensor the fusion reads); mask_u [T, L, U, d/4] / mask_i [T, L, I, d/4] uint8 for training."""
     T, U, I = batch.T, batch.U, batch.I
@@ -391,6 +462,13 @@ def gnn_stack(batch: SpmmBatch, u0: torch.Tensor, i0: torch.Tensor, n_layers: in
     if mask_i is not None:
         _masks("mask_i", mask_i, (T, n_layers, I, d // 4))
     ws = batch.workspace(d)
+    if drop is not None:
+        check(batch._lib.sagnn_gnn_stack_drop_f32(batch.handle, _ptr(u0), ld_u0, sl_u0, _ptr(i0), ld_i0, sl_i0, d,
+                                                  int(n_layers), float(leaky), _ptr(scratch_u), _ptr(scratch_i),
+                                                  _ptr(user_out), ld_uo, sl_uo, _ptr(item_out), ld_io, sl_io, _ptr(mask_u),
+                                                  _ptr(mask_i), ctypes.byref(drop.struct()), _ptr(ws),
+                                                  0 if ws is None else ws.numel() * 4, _stream()))
+        return user_out, item_out
     check(batch._lib.sagnn_gnn_stack_f32(batch.handle, _ptr(u0), ld_u0, sl_u0, _ptr(i0), ld_i0, sl_i0, d, int(n_layers),
                                          float(leaky), _ptr(scratch_u), _ptr(scratch_i), _ptr(user_out), ld_uo, sl_uo,
                                          _ptr(item_out), ld_io, sl_io, _ptr(mask_u), _ptr(mask_i), _ptr(ws),
@@ -400,9 +478,11 @@ def gnn_stack(batch: SpmmBatch, u0: torch.Tensor, i0: torch.Tensor, n_layers: in
 
 def gnn_stack_bwd(batch: SpmmBatch, grad_user_out: torch.Tensor, grad_item_out: torch.Tensor, n_layers: int, leaky: float,
                   mask_u: torch.Tensor, mask_i: torch.Tensor, grad_u0: torch.Tensor, grad_i0: torch.Tensor,
-                  scratch_u: torch.Tensor | None = None, scratch_i: torch.Tensor | None = None):
+                  scratch_u: torch.Tensor | None = None, scratch_i: torch.Tensor | None = None,
+                  drop: EdgeDrop | None = None):
     """Backward of gnn_stack (sagnn_gnn_stack_bwd_f32) on the batch's adjoint patterns: gradients at the interval
-    outputs [T, N, d] (any strides) -> dL/d u0 [T, U, d], dL/d i0 [T, I, d]."""
+    outputs [T, N, d] (any strides) -> dL/d u0 [T, U, d], dL/d i0 [T, I, d]. `drop`: that of the forward call
+    (sagnn_gnn_stack_drop_bwd_f32)."""
     adj = batch.adjoint()
     T, U, I = batch.T, batch.U, batch.I
     d = int(grad_user_out.shape[2])
@@ -416,6 +496,13 @@ def gnn_stack_bwd(batch: SpmmBatch, grad_user_out: torch.Tensor, grad_item_out: 
     _masks("mask_u", mask_u, (T, n_layers, U, d // 4))
     _masks("mask_i", mask_i, (T, n_layers, I, d // 4))
     ws = adj.workspace(d)
+    if drop is not None:
+        check(adj._lib.sagnn_gnn_stack_drop_bwd_f32(adj.handle, _ptr(grad_user_out), ld_gu, sl_gu, _ptr(grad_item_out), ld_gi,
+                                                    sl_gi, d, int(n_layers), float(leaky), _ptr(mask_u), _ptr(mask_i),
+                                                    _ptr(scratch_u), _ptr(scratch_i), _ptr(grad_u0), ld_du, sl_du,
+                                                    _ptr(grad_i0), ld_di, sl_di, ctypes.byref(drop.struct()), _ptr(ws),
+                                                    0 if ws is None else ws.numel() * 4, _stream()))
+        return grad_u0, grad_i0
     check(adj._lib.sagnn_gnn_stack_bwd_f32(adj.handle, _ptr(grad_user_out), ld_gu, sl_gu, _ptr(grad_item_out), ld_gi, sl_gi, d,
                                            int(n_layers), float(leaky), _ptr(mask_u), _ptr(mask_i), _ptr(scratch_u),
                                            _ptr(scratch_i), _ptr(grad_u0), ld_du, sl_du, _ptr(grad_i0), ld_di, sl_di, _ptr(ws),

@@ -26,9 +26,12 @@ def main():
     ap.add_argument("--epoch-only", action="store_true", help="one warm-up and one device-sampler epoch (for a profiler)")
     ap.add_argument("--fusion_rows", choices=("all", "batch", "both"), default="all",
                     help="fusion mode(s) to time; both alternates them in one process")
+    ap.add_argument("--edge_keep", type=float, default=1.0,
+                    help="--edgeKeepRate of the run: below 1 the training steps drop edges of the interval graphs")
     opt = ap.parse_args()
     Params.parse_args("--data gowalla --lr 2e-3 --reg 1e-2 --ssl_reg 1e-6 --epoch 150 --batch 512 --sslNum 40 --graphNum 3 "
                       "--gnn_layer 2 --att_layer 1 --testSize 1000 --ssldim 48 --keepRate 0.5".split(), namespace=args)
+    args.edgeKeepRate = opt.edge_keep
     np.random.seed(100)
     U, I = 48653, 52619
     tmt = synthetic.make_trn_mat_time(U, I, [600000] * 3)
@@ -47,7 +50,7 @@ def main():
         for _ in range(2):
             rec.trainEpoch()
         torch.cuda.synchronize()
-        print(f"two device-sampler epochs done (--fusion_rows {args.fusion_rows})")
+        print(f"two device-sampler epochs done (--fusion_rows {args.fusion_rows}, --edge_keep {args.edgeKeepRate})")
         return
     modes = ("all", "batch") if opt.fusion_rows == "both" else (opt.fusion_rows,)
     configs = [(sampler, mode) for mode in modes for sampler in ("host", "device")]
