@@ -79,22 +79,6 @@ SIGNATURES = {
     "sagnn_gnn_stack_bwd_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_int,
                                         c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
                                         c_void_p, c_int64, c_int64, c_void_p, c_size_t, c_void_p]),
-    "sagnn_spmm_drop_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int, POINTER(SpmmEpilogue), POINTER(EdgeDropArgs), c_uint32,
-                                    c_int, c_void_p, c_size_t, c_void_p]),
-    "sagnn_gnn_interval_drop_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int,
-                                            c_float, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
-                                            c_void_p, c_void_p, POINTER(EdgeDropArgs), c_int, c_void_p, c_size_t, c_void_p]),
-    "sagnn_gnn_interval_drop_bwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int,
-                                                c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
-                                                c_void_p, c_int64, POINTER(EdgeDropArgs), c_int, c_void_p, c_size_t,
-                                                c_void_p]),
-    "sagnn_gnn_stack_drop_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_int,
-                                         c_float, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64,
-                                         c_void_p, c_void_p, POINTER(EdgeDropArgs), c_void_p, c_size_t, c_void_p]),
-    "sagnn_gnn_stack_drop_bwd_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_int,
-                                             c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
-                                             c_void_p, c_int64, c_int64, POINTER(EdgeDropArgs), c_void_p, c_size_t,
-                                             c_void_p]),
     "sagnn_gnn_interval_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
                                        c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int64,
                                        c_void_p, c_int64, c_void_p, c_size_t, c_void_p]),
@@ -194,6 +178,22 @@ SIGNATURES = {
     "sagnn_rows_scatter_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_int64, c_int64,
                                        c_int64, c_void_p]),
 }
+
+
+def _drop_form(base: str, *selectors):
+    """A drop entry: its base entry's arguments with the sagnn_edge_drop, then what selects its tags, ahead of the
+    trailing (workspace, workspace_bytes, stream)."""
+    res, args = SIGNATURES[base]
+    return res, args[:-3] + [POINTER(EdgeDropArgs), *selectors] + args[-3:]
+
+
+SIGNATURES.update({
+    "sagnn_spmm_drop_f32": _drop_form("sagnn_spmm_ex_f32", c_uint32, c_int),              # tag, rows_are_users
+    "sagnn_gnn_interval_drop_f32": _drop_form("sagnn_gnn_interval_ex_f32", c_int),        # interval
+    "sagnn_gnn_interval_drop_bwd_f32": _drop_form("sagnn_gnn_interval_bwd_f32", c_int),
+    "sagnn_gnn_stack_drop_f32": _drop_form("sagnn_gnn_stack_f32"),
+    "sagnn_gnn_stack_drop_bwd_f32": _drop_form("sagnn_gnn_stack_bwd_f32"),
+})
 
 _lib = None
 

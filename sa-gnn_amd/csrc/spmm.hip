@@ -18,8 +18,8 @@
 //
 // Edge dropout (the *_drop_* entries): the lane that loaded an edge's column index decides whether the
 // edge is kept — one Philox block per edge, a pure function of (seed, step, tag, user id, item id) — and replaces a
-// dropped index by -1 before the broadcast, so a dropped edge is a gather that is never issued. The drop kernels are
-// instantiations of their own (DROP = true); the default kernels compile to what they were without it.
+// dropped index by -1 before the broadcast, so a dropped edge is a gather that is never issued. Every kernel is one
+// template whose drop-only arguments are a pack: with the pack empty it compiles to what it was without dropout.
 #include <float.h>
 
 #include <algorithm>
@@ -142,6 +142,26 @@ __device__ __forceinline__ float4 drop_scale(const RowDrop& dr, float4 s) {
   else return s;
 }
 
+// What only a drop kernel is passed comes after the arguments every kernel has, as a pack that is empty for the default
+// kernels (their argument list stays what it was): the row of each long-row chunk and the launch's RowDrop / BatchDrop
+// for the rows and chunks, the scale for the fix-ups, whose partial sums arrive unscaled. A pointer among them is
+// __restrict__ like the pointers ahead of it (KernelArg).
+template <class T>
+struct KernelArg { using type = T; };
+template <class T>
+struct KernelArg<T*> { using type = T* __restrict__; };
+template <class Drop>
+__device__ __forceinline__ Drop drop_of() { return Drop{}; }
+template <class Drop>
+__device__ __forceinline__ const Drop& drop_of(const int32_t*, const Drop& drop) { return drop; }
+__device__ __forceinline__ int chunk_row_of(int64_t) { return 0; }
+template <class Drop>
+__device__ __forceinline__ int chunk_row_of(int64_t ci, const int32_t* chunk_row, const Drop&) { return chunk_row[ci]; }
+__device__ __forceinline__ float4 scaled(float4 s) { return s; }
+__device__ __forceinline__ float4 scaled(float4 s, float scale) {
+  return make_float4(scale * s.x, scale * s.y, scale * s.z, scale * s.w);
+}
+
 // y = max(leaky*s, s) + residual ; out = y ; acc_out = acc_in + y (+ acc_in2) ; training extras as above.
 __device__ __forceinline__ void finish_row(const Epilogue& ep, int64_t row, int col, float4 s) {
   float4 y;
@@ -253,11 +273,11 @@ __device__ __forceinline__ float4 wave_row_sum(const int32_t* __restrict__ colid
 
 // A wave's share of the row blocks: RPW consecutive rows starting at row0 (short rows by lane groups, medium rows by
 // the whole wave; long rows belong to the chunk waves + fix-up).
-template <int LPR, int RPW, bool DROP = false>
+template <int LPR, int RPW, bool DROP>
 __device__ __forceinline__ void rows_wave(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
                                           const float* __restrict__ X, int64_t ldx, int d, int64_t n_rows, int64_t row0,
                                           int short_t, int long_t, const Epilogue& ep, int lane,
-                                          const RowDrop& dr = RowDrop{}) {
+                                          const RowDrop& dr) {
   constexpr int G = kWave / LPR;
   const int grp = lane / LPR;
   const int sub = lane % LPR;
@@ -338,12 +358,14 @@ __device__ __forceinline__ void rows_wave(const int32_t* __restrict__ rowptr, co
 
 // One launch covers the long-row chunks (first `chunk_blocks` blocks, heaviest work first)
 // and the row blocks (remaining blocks).
-template <int LPR, int RPW>
+template <int LPR, int RPW, class... DropArgs>   // none, or (chunk_row, RowDrop)
 __global__ __launch_bounds__(kBlock) void spmm_rows_kernel(
     const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
     const float* __restrict__ X, int64_t ldx, int d, int64_t n_rows, int short_t, int long_t,
     const int32_t* __restrict__ chunk_e0, const int32_t* __restrict__ chunk_e1, int64_t n_chunks,
-    int chunk_blocks, float* __restrict__ partial, Epilogue ep) {
+    int chunk_blocks, float* __restrict__ partial, Epilogue ep, typename KernelArg<DropArgs>::type... da) {
+  static_assert(sizeof...(DropArgs) == 0 || sizeof...(DropArgs) == 2, "drop-only arguments: none, or chunk_row and the drop");
+  constexpr bool DROP = sizeof...(DropArgs) != 0;
   const int lane = threadIdx.x & (kWave - 1);
   const int wave = threadIdx.x / kWave;
 
@@ -353,24 +375,26 @@ __global__ __launch_bounds__(kBlock) void spmm_rows_kernel(
     const bool lane_on = col < d;
     const int64_t ci = (int64_t)blockIdx.x * kWavesPerBlock + wave;
     if (ci >= n_chunks) return;
-    const float4 s =
-        wave_row_sum<LPR, false>(colidx, chunk_e0[ci], chunk_e1[ci], X, ldx, lane, grp, col, lane_on);
+    const float4 s = wave_row_sum<LPR, false, DROP>(colidx, chunk_e0[ci], chunk_e1[ci], X, ldx, lane, grp, col, lane_on,
+                                                    drop_of<RowDrop>(da...), chunk_row_of(ci, da...));
     if (grp == 0 && lane_on) st4(partial + ci * (int64_t)d + col, s);
     return;
   }
 
   const int64_t row0 = ((int64_t)(blockIdx.x - chunk_blocks) * kWavesPerBlock + wave) * RPW;
   if (row0 >= n_rows) return;
-  rows_wave<LPR, RPW>(rowptr, colidx, X, ldx, d, n_rows, row0, short_t, long_t, ep, lane);
+  rows_wave<LPR, RPW, DROP>(rowptr, colidx, X, ldx, d, n_rows, row0, short_t, long_t, ep, lane, drop_of<RowDrop>(da...));
 }
 
-// Fix-up for long rows: add the partial sums of a row in chunk order, then the epilogue.
-template <int LPR>
+// Fix-up for long rows: add the partial sums of a row in chunk order (a drop launch: and scale the finished sum once),
+// then the epilogue.
+template <int LPR, class... Scale>   // none, or (float)
 __global__ __launch_bounds__(kBlock) void spmm_fixup_kernel(const int32_t* __restrict__ long_row,
                                                            const int32_t* __restrict__ long_slot,
                                                            int64_t n_long,
                                                            const float* __restrict__ partial, int d,
-                                                           Epilogue ep) {
+                                                           Epilogue ep, Scale... scale) {
+  static_assert(sizeof...(Scale) <= 1, "drop-only argument: none, or the scale");
   const int lane = threadIdx.x & (kWave - 1);
   const int wave = threadIdx.x / kWave;
   const int grp = lane / LPR;
@@ -380,56 +404,8 @@ __global__ __launch_bounds__(kBlock) void spmm_fixup_kernel(const int32_t* __res
   if (li >= n_long) return;
   const float4 s = wave_row_sum<LPR, true>(nullptr, long_slot[li], long_slot[li + 1], partial, d,
                                            lane, grp, col, lane_on);
-  if (grp == 0 && lane_on) finish_row(ep, long_row[li], col, s);
+  if (grp == 0 && lane_on) finish_row(ep, long_row[li], col, scaled(s, scale...));
 }
-
-// The drop forms of the two kernels above. chunk_row[ci] is the row chunk ci belongs to (the default kernels never
-// need it); the partial sums stay unscaled and the fix-up scales the finished row once.
-template <int LPR, int RPW>
-__global__ __launch_bounds__(kBlock) void spmm_rows_drop_kernel(
-    const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
-    const float* __restrict__ X, int64_t ldx, int d, int64_t n_rows, int short_t, int long_t,
-    const int32_t* __restrict__ chunk_e0, const int32_t* __restrict__ chunk_e1,
-    const int32_t* __restrict__ chunk_row, int64_t n_chunks, int chunk_blocks, float* __restrict__ partial, Epilogue ep,
-    RowDrop dr) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wave = threadIdx.x / kWave;
-
-  if ((int)blockIdx.x < chunk_blocks) {
-    const int grp = lane / LPR;
-    const int col = 4 * (lane % LPR);
-    const bool lane_on = col < d;
-    const int64_t ci = (int64_t)blockIdx.x * kWavesPerBlock + wave;
-    if (ci >= n_chunks) return;
-    const float4 s = wave_row_sum<LPR, false, true>(colidx, chunk_e0[ci], chunk_e1[ci], X, ldx, lane, grp, col, lane_on,
-                                                    dr, chunk_row[ci]);
-    if (grp == 0 && lane_on) st4(partial + ci * (int64_t)d + col, s);
-    return;
-  }
-
-  const int64_t row0 = ((int64_t)(blockIdx.x - chunk_blocks) * kWavesPerBlock + wave) * RPW;
-  if (row0 >= n_rows) return;
-  rows_wave<LPR, RPW, true>(rowptr, colidx, X, ldx, d, n_rows, row0, short_t, long_t, ep, lane, dr);
-}
-
-template <int LPR>
-__global__ __launch_bounds__(kBlock) void spmm_fixup_drop_kernel(const int32_t* __restrict__ long_row,
-                                                                const int32_t* __restrict__ long_slot,
-                                                                int64_t n_long, const float* __restrict__ partial,
-                                                                int d, Epilogue ep, float scale) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wave = threadIdx.x / kWave;
-  const int grp = lane / LPR;
-  const int col = 4 * (lane % LPR);
-  const bool lane_on = col < d;
-  const int64_t li = (int64_t)blockIdx.x * kWavesPerBlock + wave;
-  if (li >= n_long) return;
-  const float4 s = wave_row_sum<LPR, true>(nullptr, long_slot[li], long_slot[li + 1], partial, d,
-                                           lane, grp, col, lane_on);
-  if (grp == 0 && lane_on)
-    finish_row(ep, long_row[li], col, make_float4(scale * s.x, scale * s.y, scale * s.z, scale * s.w));
-}
-
 
 // ---- all T intervals of a layer, both directions, in ONE launch (dataset-sized graphs) ----------------------------
 // The reference's loop over k (model.py:118-129) is independent per interval, so a layer of the stack is 2 T
@@ -469,12 +445,16 @@ __device__ __forceinline__ Epilogue seg_epilogue(const DirArgs& a, int k) {
   return e;
 }
 
-template <int LPR, int RPW>
+// A drop launch: a segment's tag and orientation come from its (direction, interval).
+template <int LPR, int RPW, class... DropArgs>   // none, or (chunk_row, BatchDrop)
 __global__ __launch_bounds__(kBlock) void spmm_rows_batch_kernel(const SegMeta* __restrict__ meta, BatchGeom g,
                                                                 const int32_t* __restrict__ chunk_e0,
                                                                 const int32_t* __restrict__ chunk_e1,
                                                                 const int32_t* __restrict__ chunk_seg, int64_t n_chunks,
-                                                                float* __restrict__ partial, int d, DirArgs au, DirArgs ai) {
+                                                                float* __restrict__ partial, int d, DirArgs au, DirArgs ai,
+                                                                typename KernelArg<DropArgs>::type... da) {
+  static_assert(sizeof...(DropArgs) == 0 || sizeof...(DropArgs) == 2, "drop-only arguments: none, or chunk_row and the drop");
+  constexpr bool DROP = sizeof...(DropArgs) != 0;
   const int lane = threadIdx.x & (kWave - 1);
   const int wave = threadIdx.x / kWave;
   if ((int)blockIdx.x < g.chunk_blocks) {
@@ -486,8 +466,9 @@ __global__ __launch_bounds__(kBlock) void spmm_rows_batch_kernel(const SegMeta* 
     const int seg = __builtin_amdgcn_readfirstlane(chunk_seg[ci]);
     const int dir = seg >= g.T, k = seg - dir * g.T;
     const DirArgs& a = dir ? ai : au;
-    const float4 s = wave_row_sum<LPR, false>(meta[seg].colidx, chunk_e0[ci], chunk_e1[ci], a.X + (int64_t)k * a.s_X, a.ldx,
-                                              lane, grp, col, lane_on);
+    const float4 s = wave_row_sum<LPR, false, DROP>(meta[seg].colidx, chunk_e0[ci], chunk_e1[ci], a.X + (int64_t)k * a.s_X,
+                                                    a.ldx, lane, grp, col, lane_on,
+                                                    seg_drop(drop_of<BatchDrop>(da...), dir, k), chunk_row_of(ci, da...));
     if (grp == 0 && lane_on) st4(partial + ci * (int64_t)d + col, s);
     return;
   }
@@ -502,15 +483,17 @@ __global__ __launch_bounds__(kBlock) void spmm_rows_batch_kernel(const SegMeta* 
   const SegMeta m = meta[dir * g.T + k];
   const DirArgs& a = dir ? ai : au;
   const Epilogue ep = seg_epilogue(a, k);
-  rows_wave<LPR, RPW>(m.rowptr, m.colidx, a.X + (int64_t)k * a.s_X, a.ldx, d, n_rows, row0, m.short_t, m.long_t, ep, lane);
+  rows_wave<LPR, RPW, DROP>(m.rowptr, m.colidx, a.X + (int64_t)k * a.s_X, a.ldx, d, n_rows, row0, m.short_t, m.long_t, ep,
+                            lane, seg_drop(drop_of<BatchDrop>(da...), dir, k));
 }
 
-template <int LPR>
+template <int LPR, class... Scale>
 __global__ __launch_bounds__(kBlock) void spmm_fixup_batch_kernel(const int32_t* __restrict__ long_row,
                                                                  const int32_t* __restrict__ long_slot,
                                                                  const int32_t* __restrict__ long_seg, int64_t n_long,
                                                                  const float* __restrict__ partial, int d, int T,
-                                                                 DirArgs au, DirArgs ai) {
+                                                                 DirArgs au, DirArgs ai, Scale... scale) {
+  static_assert(sizeof...(Scale) <= 1, "drop-only argument: none, or the scale");
   const int lane = threadIdx.x & (kWave - 1);
   const int wave = threadIdx.x / kWave;
   const int grp = lane / LPR;
@@ -522,69 +505,7 @@ __global__ __launch_bounds__(kBlock) void spmm_fixup_batch_kernel(const int32_t*
   const int dir = seg >= T, k = seg - dir * T;
   const Epilogue ep = seg_epilogue(dir ? ai : au, k);
   const float4 s = wave_row_sum<LPR, true>(nullptr, long_slot[li], long_slot[li + 1], partial, d, lane, grp, col, lane_on);
-  if (grp == 0 && lane_on) finish_row(ep, long_row[li], col, s);
-}
-
-// The drop forms of the two batched kernels: a segment's tag and orientation come from its (direction, interval).
-template <int LPR, int RPW>
-__global__ __launch_bounds__(kBlock) void spmm_rows_batch_drop_kernel(const SegMeta* __restrict__ meta, BatchGeom g,
-                                                                     const int32_t* __restrict__ chunk_e0,
-                                                                     const int32_t* __restrict__ chunk_e1,
-                                                                     const int32_t* __restrict__ chunk_seg,
-                                                                     const int32_t* __restrict__ chunk_row, int64_t n_chunks,
-                                                                     float* __restrict__ partial, int d, DirArgs au,
-                                                                     DirArgs ai, BatchDrop bd) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wave = threadIdx.x / kWave;
-  if ((int)blockIdx.x < g.chunk_blocks) {
-    const int grp = lane / LPR;
-    const int col = 4 * (lane % LPR);
-    const bool lane_on = col < d;
-    const int64_t ci = (int64_t)blockIdx.x * kWavesPerBlock + wave;
-    if (ci >= n_chunks) return;
-    const int seg = __builtin_amdgcn_readfirstlane(chunk_seg[ci]);
-    const int dir = seg >= g.T, k = seg - dir * g.T;
-    const DirArgs& a = dir ? ai : au;
-    const RowDrop dr = seg_drop(bd, dir, k);
-    const float4 s = wave_row_sum<LPR, false, true>(meta[seg].colidx, chunk_e0[ci], chunk_e1[ci], a.X + (int64_t)k * a.s_X,
-                                                    a.ldx, lane, grp, col, lane_on, dr, chunk_row[ci]);
-    if (grp == 0 && lane_on) st4(partial + ci * (int64_t)d + col, s);
-    return;
-  }
-  int rb = (int)blockIdx.x - g.chunk_blocks;
-  const int dir = rb >= g.T * g.blocks_u;
-  if (dir) rb -= g.T * g.blocks_u;
-  const int per = dir ? g.blocks_i : g.blocks_u;
-  const int k = rb / per;
-  const int64_t n_rows = dir ? g.rows_i : g.rows_u;
-  const int64_t row0 = ((int64_t)(rb - k * per) * kWavesPerBlock + wave) * RPW;
-  if (row0 >= n_rows) return;
-  const SegMeta m = meta[dir * g.T + k];
-  const DirArgs& a = dir ? ai : au;
-  const Epilogue ep = seg_epilogue(a, k);
-  rows_wave<LPR, RPW, true>(m.rowptr, m.colidx, a.X + (int64_t)k * a.s_X, a.ldx, d, n_rows, row0, m.short_t, m.long_t, ep,
-                            lane, seg_drop(bd, dir, k));
-}
-
-template <int LPR>
-__global__ __launch_bounds__(kBlock) void spmm_fixup_batch_drop_kernel(const int32_t* __restrict__ long_row,
-                                                                      const int32_t* __restrict__ long_slot,
-                                                                      const int32_t* __restrict__ long_seg, int64_t n_long,
-                                                                      const float* __restrict__ partial, int d, int T,
-                                                                      DirArgs au, DirArgs ai, float scale) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wave = threadIdx.x / kWave;
-  const int grp = lane / LPR;
-  const int col = 4 * (lane % LPR);
-  const bool lane_on = col < d;
-  const int64_t li = (int64_t)blockIdx.x * kWavesPerBlock + wave;
-  if (li >= n_long) return;
-  const int seg = __builtin_amdgcn_readfirstlane(long_seg[li]);
-  const int dir = seg >= T, k = seg - dir * T;
-  const Epilogue ep = seg_epilogue(dir ? ai : au, k);
-  const float4 s = wave_row_sum<LPR, true>(nullptr, long_slot[li], long_slot[li + 1], partial, d, lane, grp, col, lane_on);
-  if (grp == 0 && lane_on)
-    finish_row(ep, long_row[li], col, make_float4(scale * s.x, scale * s.y, scale * s.z, scale * s.w));
+  if (grp == 0 && lane_on) finish_row(ep, long_row[li], col, scaled(s, scale...));
 }
 
 }  // namespace
@@ -766,7 +687,8 @@ extern "C" size_t sagnn_spmm_workspace_bytes(const sagnn_spmm_plan* plan, int d)
 // ------------------------------------------------------------------------------------------
 namespace {
 
-// drop = nullptr: the default kernels, launched as before the drop forms existed
+// drop = nullptr: the default kernels. The row block of a wave (small) and the drop-only arguments, none or all, name
+// the instantiation of a kernel; its launch is stated once.
 template <int LPR>
 int launch_spmm(const sagnn_spmm_plan* p, const float* X, int64_t ldx, int d, const Epilogue& ep,
                 float* partial, hipStream_t stream, const RowDrop* drop = nullptr) {
@@ -782,38 +704,28 @@ int launch_spmm(const sagnn_spmm_plan* p, const float* X, int64_t ldx, int d, co
   if (blocks > INT32_MAX) return sagnn::fail(SAGNN_ERR_ARG, "grid too large");
   if (blocks > 0) {
     sagnn::ProfileScope prof(sagnn::kProfSpmmRows, stream, p->info.nnz, n_rows);
-    if (drop && small)
-      hipLaunchKernelGGL((spmm_rows_drop_kernel<LPR, RPW_SMALL>), dim3((unsigned)blocks), dim3(kBlock), 0, stream,
-                         p->d_rowptr, p->d_colidx, X, ldx, d, n_rows, p->info.short_thresh,
-                         p->info.long_thresh, p->d_chunk_e0, p->d_chunk_e1, p->d_chunk_row, n_chunks,
-                         (int)chunk_blocks, partial, ep, *drop);
-    else if (drop)
-      hipLaunchKernelGGL((spmm_rows_drop_kernel<LPR, kRowsPerWave>), dim3((unsigned)blocks), dim3(kBlock), 0, stream,
-                         p->d_rowptr, p->d_colidx, X, ldx, d, n_rows, p->info.short_thresh,
-                         p->info.long_thresh, p->d_chunk_e0, p->d_chunk_e1, p->d_chunk_row, n_chunks,
-                         (int)chunk_blocks, partial, ep, *drop);
-    else if (small)
-      hipLaunchKernelGGL((spmm_rows_kernel<LPR, RPW_SMALL>), dim3((unsigned)blocks), dim3(kBlock), 0, stream,
-                         p->d_rowptr, p->d_colidx, X, ldx, d, n_rows, p->info.short_thresh,
-                         p->info.long_thresh, p->d_chunk_e0, p->d_chunk_e1, n_chunks,
-                         (int)chunk_blocks, partial, ep);
+    const auto rows = [&](auto kernel, auto... da) {
+      hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kBlock), 0, stream, p->d_rowptr, p->d_colidx, X, ldx, d, n_rows,
+                         p->info.short_thresh, p->info.long_thresh, p->d_chunk_e0, p->d_chunk_e1, n_chunks,
+                         (int)chunk_blocks, partial, ep, da...);
+    };
+    if (drop)
+      rows(small ? spmm_rows_kernel<LPR, RPW_SMALL, const int32_t*, RowDrop> : spmm_rows_kernel<LPR, kRowsPerWave, const int32_t*, RowDrop>,
+           p->d_chunk_row, *drop);
     else
-      hipLaunchKernelGGL((spmm_rows_kernel<LPR, kRowsPerWave>), dim3((unsigned)blocks), dim3(kBlock), 0, stream,
-                         p->d_rowptr, p->d_colidx, X, ldx, d, n_rows, p->info.short_thresh,
-                         p->info.long_thresh, p->d_chunk_e0, p->d_chunk_e1, n_chunks,
-                         (int)chunk_blocks, partial, ep);
+      rows(small ? spmm_rows_kernel<LPR, RPW_SMALL> : spmm_rows_kernel<LPR, kRowsPerWave>);
     SAGNN_HIP_TRY(hipGetLastError());
   }
   const int64_t n_long = p->info.n_long_rows;
   if (n_long > 0) {
     sagnn::ProfileScope prof(sagnn::kProfSpmmFixup, stream, n_chunks, n_long);
     const int64_t fb = (n_long + kWavesPerBlock - 1) / kWavesPerBlock;
-    if (drop)
-      hipLaunchKernelGGL(spmm_fixup_drop_kernel<LPR>, dim3((unsigned)fb), dim3(kBlock), 0, stream,
-                         p->d_long_row, p->d_long_slot, n_long, partial, d, ep, drop->scale);
-    else
-      hipLaunchKernelGGL(spmm_fixup_kernel<LPR>, dim3((unsigned)fb), dim3(kBlock), 0, stream,
-                         p->d_long_row, p->d_long_slot, n_long, partial, d, ep);
+    const auto fixup = [&](auto kernel, auto... scale) {
+      hipLaunchKernelGGL(kernel, dim3((unsigned)fb), dim3(kBlock), 0, stream,
+                         p->d_long_row, p->d_long_slot, n_long, partial, d, ep, scale...);
+    };
+    if (drop) fixup(spmm_fixup_kernel<LPR, float>, drop->scale);
+    else fixup(spmm_fixup_kernel<LPR>);
     SAGNN_HIP_TRY(hipGetLastError());
   }
   return SAGNN_OK;
@@ -852,6 +764,13 @@ int launch_mask_scale(const Slab& g, const uint8_t* mask, int64_t s_mask, float 
                      g.slab, mask, s_mask, d / 4, slope, out.p, out.ld, out.slab, n_rows, d);
   SAGNN_HIP_TRY(hipGetLastError());
   return SAGNN_OK;
+}
+
+// The kernels' epilogue of the caller's (masks: d / 4 bytes per row)
+Epilogue kernel_epilogue(const sagnn_spmm_epilogue& e, int d) {
+  return Epilogue{e.residual, e.ldr,      e.acc_in,  e.ld_acc_in, e.out,  e.ldo,    e.acc_out, e.ld_acc_out,
+                  e.leaky,    e.mask_out, e.mask_in, e.out2,      e.ldo2, e.slope2, d / 4,     e.acc_in2,
+                  e.ld_acc_in2};
 }
 
 // sagnn_spmm_ex_f32 on the kernels' own epilogue: every per-call check, then the launch(es) of one plan
@@ -896,10 +815,7 @@ extern "C" int sagnn_spmm_ex_f32(const sagnn_spmm_plan* plan, const float* X, in
                                  const sagnn_spmm_epilogue* e, void* workspace, size_t workspace_bytes,
                                  void* stream) {
   if (!plan || !e) return sagnn::fail(SAGNN_ERR_NULL, "plan/epilogue is NULL");
-  const Epilogue ep{e->residual, e->ldr,       e->acc_in,  e->ld_acc_in, e->out,   e->ldo,    e->acc_out, e->ld_acc_out,
-                    e->leaky,    e->mask_out,  e->mask_in, e->out2,      e->ldo2,  e->slope2, d / 4,
-                    e->acc_in2,  e->ld_acc_in2};
-  return spmm_ex(plan, X, ldx, d, ep, workspace, workspace_bytes, stream);
+  return spmm_ex(plan, X, ldx, d, kernel_epilogue(*e, d), workspace, workspace_bytes, stream);
 }
 
 namespace {
@@ -929,11 +845,8 @@ extern "C" int sagnn_spmm_drop_f32(const sagnn_spmm_plan* plan, const float* X, 
                                    int rows_are_users, void* workspace, size_t workspace_bytes, void* stream) {
   if (int rc = check_drop(drop, 0, 0)) return rc;
   if (!plan || !e) return sagnn::fail(SAGNN_ERR_NULL, "plan/epilogue is NULL");
-  const Epilogue ep{e->residual, e->ldr,       e->acc_in,  e->ld_acc_in, e->out,   e->ldo,    e->acc_out, e->ld_acc_out,
-                    e->leaky,    e->mask_out,  e->mask_in, e->out2,      e->ldo2,  e->slope2, d / 4,
-                    e->acc_in2,  e->ld_acc_in2};
   const RowDrop dr = row_drop(*drop, tag, rows_are_users != 0);
-  return spmm_ex(plan, X, ldx, d, ep, workspace, workspace_bytes, stream, &dr);
+  return spmm_ex(plan, X, ldx, d, kernel_epilogue(*e, d), workspace, workspace_bytes, stream, &dr);
 }
 
 extern "C" int sagnn_spmm_f32(const sagnn_spmm_plan* plan, const float* X, int64_t ldx, int d,
@@ -1102,31 +1015,27 @@ int launch_batch(const sagnn_spmm_batch* b, int d, const DirArgs& au, const DirA
   const BatchGeom g{b->T, (int32_t)chunk_blocks, (int32_t)bu, (int32_t)bi, (int32_t)b->U, (int32_t)b->I};
   if (blocks > 0) {
     sagnn::ProfileScope prof(sagnn::kProfSpmmRows, stream, b->nnz, (int64_t)b->T * (b->U + b->I));
-    if (drop && small)
-      hipLaunchKernelGGL((spmm_rows_batch_drop_kernel<LPR, RPW_SMALL>), dim3((unsigned)blocks), dim3(kBlock), 0, stream,
-                         b->d_meta, g, b->d_chunk_e0, b->d_chunk_e1, b->d_chunk_seg, b->d_chunk_row, b->n_chunks, partial, d,
-                         au, ai, *drop);
-    else if (drop)
-      hipLaunchKernelGGL((spmm_rows_batch_drop_kernel<LPR, kRowsPerWave>), dim3((unsigned)blocks), dim3(kBlock), 0, stream,
-                         b->d_meta, g, b->d_chunk_e0, b->d_chunk_e1, b->d_chunk_seg, b->d_chunk_row, b->n_chunks, partial, d,
-                         au, ai, *drop);
-    else if (small)
-      hipLaunchKernelGGL((spmm_rows_batch_kernel<LPR, RPW_SMALL>), dim3((unsigned)blocks), dim3(kBlock), 0, stream, b->d_meta,
-                         g, b->d_chunk_e0, b->d_chunk_e1, b->d_chunk_seg, b->n_chunks, partial, d, au, ai);
+    const auto rows = [&](auto kernel, auto... da) {
+      hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kBlock), 0, stream, b->d_meta, g, b->d_chunk_e0, b->d_chunk_e1,
+                         b->d_chunk_seg, b->n_chunks, partial, d, au, ai, da...);
+    };
+    if (drop)
+      rows(small ? spmm_rows_batch_kernel<LPR, RPW_SMALL, const int32_t*, BatchDrop>
+                 : spmm_rows_batch_kernel<LPR, kRowsPerWave, const int32_t*, BatchDrop>,
+           b->d_chunk_row, *drop);
     else
-      hipLaunchKernelGGL((spmm_rows_batch_kernel<LPR, kRowsPerWave>), dim3((unsigned)blocks), dim3(kBlock), 0, stream,
-                         b->d_meta, g, b->d_chunk_e0, b->d_chunk_e1, b->d_chunk_seg, b->n_chunks, partial, d, au, ai);
+      rows(small ? spmm_rows_batch_kernel<LPR, RPW_SMALL> : spmm_rows_batch_kernel<LPR, kRowsPerWave>);
     SAGNN_HIP_TRY(hipGetLastError());
   }
   if (b->n_long > 0) {
     sagnn::ProfileScope prof(sagnn::kProfSpmmFixup, stream, b->n_chunks, b->n_long);
     const int64_t fb = (b->n_long + kWavesPerBlock - 1) / kWavesPerBlock;
-    if (drop)
-      hipLaunchKernelGGL(spmm_fixup_batch_drop_kernel<LPR>, dim3((unsigned)fb), dim3(kBlock), 0, stream, b->d_long_row,
-                         b->d_long_slot, b->d_long_seg, b->n_long, partial, d, b->T, au, ai, drop->r.scale);
-    else
-      hipLaunchKernelGGL(spmm_fixup_batch_kernel<LPR>, dim3((unsigned)fb), dim3(kBlock), 0, stream, b->d_long_row,
-                         b->d_long_slot, b->d_long_seg, b->n_long, partial, d, b->T, au, ai);
+    const auto fixup = [&](auto kernel, auto... scale) {
+      hipLaunchKernelGGL(kernel, dim3((unsigned)fb), dim3(kBlock), 0, stream,
+                         b->d_long_row, b->d_long_slot, b->d_long_seg, b->n_long, partial, d, b->T, au, ai, scale...);
+    };
+    if (drop) fixup(spmm_fixup_batch_kernel<LPR, float>, drop->r.scale);
+    else fixup(spmm_fixup_batch_kernel<LPR>);
     SAGNN_HIP_TRY(hipGetLastError());
   }
   return SAGNN_OK;

@@ -179,6 +179,13 @@ def spmm(plan: SpmmPlan, x: torch.Tensor, leaky: float, residual: torch.Tensor |
     return out
 
 
+def _call(lib, entry: str, args: tuple, drop_args: tuple, ws):
+    """lib.<entry>(*args, *drop_args, workspace, workspace_bytes, stream): every SpMM / GNN entry ends with these three,
+    and a drop entry takes its base entry's arguments with the sagnn_edge_drop (and what selects its tags) just ahead of
+    them."""
+    check(getattr(lib, entry)(*args, *drop_args, _ptr(ws), 0 if ws is None else ws.numel() * 4, _stream()))
+
+
 def spmm_ex(plan: SpmmPlan, x: torch.Tensor | None, leaky: float, residual=None, out=None, acc_in=None, acc_out=None,
             acc_in2=None, mask_out=None, mask_in=None, out2=None, slope2: float = 1.0, want_out: bool = False,
             _drop=None):
@@ -202,13 +209,12 @@ def spmm_ex(plan: SpmmPlan, x: torch.Tensor | None, leaky: float, residual=None,
     e.mask_out, e.mask_in = _ptr(mask_out), _ptr(mask_in)
     ldx = _f32_rows("x", x, d, plan.n_src) if x is not None else d
     ws = plan.workspace(d)
+    drop_args = ()
     if _drop is not None:       # spmm_drop
         drop, tag, rows_are_users = _drop
-        check(plan._lib.sagnn_spmm_drop_f32(plan.handle, _ptr(x), ldx, d, ctypes.byref(e), ctypes.byref(drop.struct()), tag,
-                                            int(rows_are_users), _ptr(ws), 0 if ws is None else ws.numel() * 4, _stream()))
-        return out
-    check(plan._lib.sagnn_spmm_ex_f32(plan.handle, _ptr(x), ldx, d, ctypes.byref(e), _ptr(ws), 0 if ws is None else ws.numel() * 4,
-                                      _stream()))
+        drop_args = (ctypes.byref(drop.struct()), tag, int(rows_are_users))
+    _call(plan._lib, "sagnn_spmm_ex_f32" if _drop is None else "sagnn_spmm_drop_f32",
+          (plan.handle, _ptr(x), ldx, d, ctypes.byref(e)), drop_args, ws)
     return out
 
 
@@ -326,17 +332,10 @@ def gnn_interval(plan_user: SpmmPlan, plan_item: SpmmPlan, u0: torch.Tensor, i0:
     if mask_i is not None:
         _masks("mask_i", mask_i, (n_layers, I, d // 4))
     ws = _interval_ws(plan_user, plan_item, d)
-    if drop is not None:
-        check(plan_user._lib.sagnn_gnn_interval_drop_f32(
-            plan_user.handle, plan_item.handle, _ptr(u0), ld_u0, _ptr(i0), ld_i0, d, int(n_layers),
-            float(leaky), _ptr(scratch_u), _ptr(scratch_i), _ptr(user_out), ld_uo, _ptr(item_out), ld_io,
-            _ptr(mask_u), _ptr(mask_i), ctypes.byref(drop.struct()), int(interval), _ptr(ws),
-            0 if ws is None else ws.numel() * 4, _stream()))
-        return user_out, item_out
-    check(plan_user._lib.sagnn_gnn_interval_ex_f32(
-        plan_user.handle, plan_item.handle, _ptr(u0), ld_u0, _ptr(i0), ld_i0, d, int(n_layers),
-        float(leaky), _ptr(scratch_u), _ptr(scratch_i), _ptr(user_out), ld_uo, _ptr(item_out), ld_io,
-        _ptr(mask_u), _ptr(mask_i), _ptr(ws), 0 if ws is None else ws.numel() * 4, _stream()))
+    _call(plan_user._lib, "sagnn_gnn_interval_ex_f32" if drop is None else "sagnn_gnn_interval_drop_f32",
+          (plan_user.handle, plan_item.handle, _ptr(u0), ld_u0, _ptr(i0), ld_i0, d, int(n_layers), float(leaky),
+           _ptr(scratch_u), _ptr(scratch_i), _ptr(user_out), ld_uo, _ptr(item_out), ld_io, _ptr(mask_u), _ptr(mask_i)),
+          () if drop is None else (ctypes.byref(drop.struct()), int(interval)), ws)
     return user_out, item_out
 
 
@@ -365,17 +364,11 @@ def gnn_interval_bwd(plan_user: SpmmPlan, plan_item: SpmmPlan, grad_user_out: to
     _masks("mask_u", mask_u, (n_layers, U, d // 4))
     _masks("mask_i", mask_i, (n_layers, I, d // 4))
     ws = _interval_ws(plan_user, plan_item, d)
-    if drop is not None:
-        check(plan_user._lib.sagnn_gnn_interval_drop_bwd_f32(
-            plan_user.handle, plan_item.handle, _ptr(grad_user_out), ld_gu, _ptr(grad_item_out), ld_gi, d,
-            int(n_layers), float(leaky), _ptr(mask_u), _ptr(mask_i), _ptr(scratch_u), _ptr(scratch_i),
-            _ptr(grad_u0), ld_du, _ptr(grad_i0), ld_di, ctypes.byref(drop.struct()), int(interval), _ptr(ws),
-            0 if ws is None else ws.numel() * 4, _stream()))
-        return grad_u0, grad_i0
-    check(plan_user._lib.sagnn_gnn_interval_bwd_f32(
-        plan_user.handle, plan_item.handle, _ptr(grad_user_out), ld_gu, _ptr(grad_item_out), ld_gi, d,
-        int(n_layers), float(leaky), _ptr(mask_u), _ptr(mask_i), _ptr(scratch_u), _ptr(scratch_i),
-        _ptr(grad_u0), ld_du, _ptr(grad_i0), ld_di, _ptr(ws), 0 if ws is None else ws.numel() * 4, _stream()))
+    _call(plan_user._lib, "sagnn_gnn_interval_bwd_f32" if drop is None else "sagnn_gnn_interval_drop_bwd_f32",
+          (plan_user.handle, plan_item.handle, _ptr(grad_user_out), ld_gu, _ptr(grad_item_out), ld_gi, d, int(n_layers),
+           float(leaky), _ptr(mask_u), _ptr(mask_i), _ptr(scratch_u), _ptr(scratch_i), _ptr(grad_u0), ld_du, _ptr(grad_i0),
+           ld_di),
+          () if drop is None else (ctypes.byref(drop.struct()), int(interval)), ws)
     return grad_u0, grad_i0
 
 
@@ -462,17 +455,10 @@ def gnn_stack(batch: SpmmBatch, u0: torch.Tensor, i0: torch.Tensor, n_layers: in
     if mask_i is not None:
         _masks("mask_i", mask_i, (T, n_layers, I, d // 4))
     ws = batch.workspace(d)
-    if drop is not None:
-        check(batch._lib.sagnn_gnn_stack_drop_f32(batch.handle, _ptr(u0), ld_u0, sl_u0, _ptr(i0), ld_i0, sl_i0, d,
-                                                  int(n_layers), float(leaky), _ptr(scratch_u), _ptr(scratch_i),
-                                                  _ptr(user_out), ld_uo, sl_uo, _ptr(item_out), ld_io, sl_io, _ptr(mask_u),
-                                                  _ptr(mask_i), ctypes.byref(drop.struct()), _ptr(ws),
-                                                  0 if ws is None else ws.numel() * 4, _stream()))
-        return user_out, item_out
-    check(batch._lib.sagnn_gnn_stack_f32(batch.handle, _ptr(u0), ld_u0, sl_u0, _ptr(i0), ld_i0, sl_i0, d, int(n_layers),
-                                         float(leaky), _ptr(scratch_u), _ptr(scratch_i), _ptr(user_out), ld_uo, sl_uo,
-                                         _ptr(item_out), ld_io, sl_io, _ptr(mask_u), _ptr(mask_i), _ptr(ws),
-                                         0 if ws is None else ws.numel() * 4, _stream()))
+    _call(batch._lib, "sagnn_gnn_stack_f32" if drop is None else "sagnn_gnn_stack_drop_f32",
+          (batch.handle, _ptr(u0), ld_u0, sl_u0, _ptr(i0), ld_i0, sl_i0, d, int(n_layers), float(leaky), _ptr(scratch_u),
+           _ptr(scratch_i), _ptr(user_out), ld_uo, sl_uo, _ptr(item_out), ld_io, sl_io, _ptr(mask_u), _ptr(mask_i)),
+          () if drop is None else (ctypes.byref(drop.struct()),), ws)
     return user_out, item_out
 
 
@@ -496,17 +482,11 @@ def gnn_stack_bwd(batch: SpmmBatch, grad_user_out: torch.Tensor, grad_item_out: 
     _masks("mask_u", mask_u, (T, n_layers, U, d // 4))
     _masks("mask_i", mask_i, (T, n_layers, I, d // 4))
     ws = adj.workspace(d)
-    if drop is not None:
-        check(adj._lib.sagnn_gnn_stack_drop_bwd_f32(adj.handle, _ptr(grad_user_out), ld_gu, sl_gu, _ptr(grad_item_out), ld_gi,
-                                                    sl_gi, d, int(n_layers), float(leaky), _ptr(mask_u), _ptr(mask_i),
-                                                    _ptr(scratch_u), _ptr(scratch_i), _ptr(grad_u0), ld_du, sl_du,
-                                                    _ptr(grad_i0), ld_di, sl_di, ctypes.byref(drop.struct()), _ptr(ws),
-                                                    0 if ws is None else ws.numel() * 4, _stream()))
-        return grad_u0, grad_i0
-    check(adj._lib.sagnn_gnn_stack_bwd_f32(adj.handle, _ptr(grad_user_out), ld_gu, sl_gu, _ptr(grad_item_out), ld_gi, sl_gi, d,
-                                           int(n_layers), float(leaky), _ptr(mask_u), _ptr(mask_i), _ptr(scratch_u),
-                                           _ptr(scratch_i), _ptr(grad_u0), ld_du, sl_du, _ptr(grad_i0), ld_di, sl_di, _ptr(ws),
-                                           0 if ws is None else ws.numel() * 4, _stream()))
+    _call(adj._lib, "sagnn_gnn_stack_bwd_f32" if drop is None else "sagnn_gnn_stack_drop_bwd_f32",
+          (adj.handle, _ptr(grad_user_out), ld_gu, sl_gu, _ptr(grad_item_out), ld_gi, sl_gi, d, int(n_layers), float(leaky),
+           _ptr(mask_u), _ptr(mask_i), _ptr(scratch_u), _ptr(scratch_i), _ptr(grad_u0), ld_du, sl_du, _ptr(grad_i0), ld_di,
+           sl_di),
+          () if drop is None else (ctypes.byref(drop.struct()),), ws)
     return grad_u0, grad_i0
 
 

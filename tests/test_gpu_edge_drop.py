@@ -2,7 +2,8 @@
 the numpy restatement (edge_drop_ref), for every row class and lane-group width; the values and the training epilogue
 against float64; the stack and its adjoint against torch float64 autograd over explicitly masked dense matrices; and the
 Recommender's training loss with --edgeKeepRate. Graphs are tiny, with plan tuning (4, 16, 64) so that 40 rows hold
-short, medium and chunked long rows."""
+short, medium and chunked long rows; one test runs 262,144 rows, the smallest count that takes the large-row-block
+instantiations of the kernels."""
 import numpy as np
 import pytest
 import scipy.sparse as sp
@@ -241,6 +242,118 @@ def test_stack_and_adjoint_vs_float64_autograd(dev, L):
     oi = torch.empty((T, I, d), device=dev)
     ops.gnn_stack(batch, torch.from_numpy(u0).to(dev), torch.from_numpy(i0).to(dev), L, leaky, ou, oi)
     assert torch.equal(plain[0], ou) and torch.equal(plain[1], oi) and not torch.equal(plain[0], got[0])
+
+
+# ---- the large-row-block variant (RPW = kRowsPerWave) ---------------------------------------------------------------------
+BIG_U, BIG_I, BIG_D = 262144, 4096, 32      # kSmallRows users exactly: the launchers test n_rows < kSmallRows
+
+
+def _big_matrix(rng, row1):
+    """[BIG_U, BIG_I] stored pattern, about 660 k entries: user 0 empty, user 1 the items `row1`, user 2 a duplicated
+    entry, user 3 300 items (five chunks of 64), user 4 ten items (medium), the others min of two draws from 0 .. 8
+    unsorted random items (mean 2.5, so an item row of the transpose holds about 160; uniform degrees 0 .. 8 would store
+    1.05 M entries, 256 per item row, and only cost host time)."""
+    deg = np.minimum(rng.integers(0, 9, BIG_U), rng.integers(0, 9, BIG_U))
+    deg[:5] = [0, len(row1), 4, 300, 10]
+    rowptr = np.concatenate([[0], np.cumsum(deg)]).astype(np.int32)
+    colidx = rng.integers(0, BIG_I, rowptr[-1]).astype(np.int32)
+    colidx[rowptr[1]:rowptr[2]] = row1
+    colidx[rowptr[2]:rowptr[3]] = [3, 7, 7, BIG_I - 1]
+    colidx[rowptr[3]:rowptr[4]] = rng.choice(BIG_I, 300, replace=False)
+    return sp.csr_matrix((np.ones(colidx.size, np.intc), colidx, rowptr), shape=(BIG_U, BIG_I))
+
+
+def _sparse_counts(rowptr, colidx, shape):
+    """float64 CSR of the multiplicities of a stored pattern (the COO -> CSR conversion sums duplicates)."""
+    rows = np.repeat(np.arange(shape[0]), np.diff(rowptr))
+    return sp.coo_matrix((np.ones(colidx.size), (rows, colidx)), shape=shape).tocsr()
+
+
+def _sparse_masked(counts, rows_are_users, drop, k, l, direction):
+    """scale * counts with the entries edge_drop_ref drops removed; drop = None: counts."""
+    if drop is None:
+        return counts
+    c = counts.tocoo()
+    users, items = (c.row, c.col) if rows_are_users else (c.col, c.row)
+    kept = R.keep_mask(drop.seed, drop.step, k, l, direction, users, items, thresh=drop.threshold)
+    return sp.csr_matrix((float(np.float32(drop.scale)) * c.data * kept, (c.row, c.col)), shape=counts.shape)
+
+
+def _sparse_stack_reference(cu, ci, u0, i0, L, leaky, drop):
+    """The layer recurrence of _stack_reference in float64 on sparse matrices, forward only: cu[k] / ci[k] the user-side
+    and item-side multiplicities of interval k. Returns the outputs and, for assert_sum_close, their abs_terms: with
+    t^0 = 0, t^{l+1} = A (|e_other^l| + t_other^l) + |e^l| + t^l bounds what the roundings of layer l + 1 and the
+    errors its inputs carry can sum to, in units of 3 eps32; the output sum_l e^l collects sum_l (|e^l| + t^l)."""
+    lk = lambda x: np.maximum(leaky * x, x)
+    outs, terms = ([], []), ([], [])
+    for k in range(len(cu)):
+        e, t = (u0[k].astype(np.float64), i0[k].astype(np.float64)), (np.zeros(u0[k].shape), np.zeros(i0[k].shape))
+        out, term = list(e), [np.abs(e[0]), np.abs(e[1])]
+        for l in range(L):
+            au = _sparse_masked(cu[k], True, drop, k, l, 0)
+            ai = _sparse_masked(ci[k], False, drop, k, l, 1)
+            t = (au @ (np.abs(e[1]) + t[1]) + np.abs(e[0]) + t[0], ai @ (np.abs(e[0]) + t[0]) + np.abs(e[1]) + t[1])
+            e = (lk(au @ e[1]) + e[0], lk(ai @ e[0]) + e[1])
+            for side in (0, 1):
+                out[side] = out[side] + e[side]
+                term[side] = term[side] + np.abs(e[side]) + t[side]
+        for side in (0, 1):
+            outs[side].append(out[side])
+            terms[side].append(term[side])
+    return np.stack(outs[0]), np.stack(outs[1]), np.stack(terms[0]), np.stack(terms[1])
+
+
+def test_large_row_block_variant_with_and_without_drop(dev):
+    """262,144 users: every launch takes the RPW = kRowsPerWave instantiation of its kernel, per plan and batched,
+    default and DROP, on rows of every class (the 4,096 item rows are all long, several chunks each)."""
+    from sa_gnn_amd import graph, ops
+    U, I, d, leaky, keep, T, L = BIG_U, BIG_I, BIG_D, 0.5, 0.5, 2, 2
+    rng = np.random.default_rng(262144)
+    drop = ops.EdgeDrop(SEED, STEP, keep)
+    tag = ops.edge_tag(0, 1, 0)
+    row1 = np.flatnonzero(~R.keep_mask(SEED, STEP, 0, 1, 0, np.full(I, 1), np.arange(I), keep=keep))[:3]
+    mats = [_big_matrix(rng, row1), sp.csr_matrix((U, I), dtype=np.intc)]                # the second: the phantom edge alone
+    pairs = [graph.interval_pair(m, dev, tuning=TUNING) for m in mats]
+    plans_u, plans_i = [a.plan for a, _ in pairs], [t.plan for _, t in pairs]
+    pu, pi = plans_u[0], plans_i[0]
+    deg = np.diff(graph.csr_arrays(mats[0])[0])
+    assert (deg == 0).any() and ((deg > 0) & (deg <= 4)).any() and ((deg > 4) & (deg <= 16)).any()
+    assert pu.info.n_long_rows >= 1 and pu.info.n_chunks > pu.info.n_long_rows
+    assert pi.info.n_long_rows == I and pi.info.n_chunks >= 2 * I
+    assert plans_u[1].nnz == 1 and plans_i[1].nnz == 1
+    cu = [_sparse_counts(*graph.csr_arrays(m), (U, I)) for m in mats]
+    ci = [_sparse_counts(*graph.csr_arrays(graph.transpose(m)), (I, U)) for m in mats]
+    assert cu[0][2, 7] == 2 and ci[0][7, 2] == 1 and pu.nnz > pi.nnz                     # the duplicated stored entry
+    u0 = rng.standard_normal((T, U, d)).astype(np.float32)
+    i0 = rng.standard_normal((T, I, d)).astype(np.float32)
+    u0_d, i0_d = torch.from_numpy(u0).to(dev), torch.from_numpy(i0).to(dev)
+
+    # (a), (b): one product on each orientation, default and dropped, with a residual
+    for dr in (None, drop):
+        for plan, counts, rows_are_users, x, x_d, res, res_d in ((pu, cu[0], True, i0[0], i0_d[0], u0[1], u0_d[1]),
+                                                                   (pi, ci[0], False, u0[0], u0_d[0], i0[1], i0_d[1])):
+            if dr is None:
+                got = ops.spmm_ex(plan, x_d, leaky, residual=res_d, want_out=True)
+            else:
+                got = ops.spmm_drop(plan, x_d, leaky, dr, tag, rows_are_users, residual=res_d, want_out=True)
+            a = _sparse_masked(counts, rows_are_users, dr, 0, 1, 0)
+            s = a @ x.astype(np.float64)
+            assert_sum_close(got.cpu().numpy(), np.maximum(leaky * s, s) + res, a @ np.abs(x).astype(np.float64) + np.abs(res))
+            if dr is not None and rows_are_users:                                         # user 1: every edge dropped
+                assert torch.equal(got[1], res_d[1]) and not torch.equal(got[2], res_d[2])
+
+    # (c): the batched stack, and each interval of it through the per-plan entry, bit for bit
+    batch = ops.SpmmBatch(plans_u, plans_i)
+    for dr in (None, drop):
+        ou, oi = torch.empty((T, U, d), device=dev), torch.empty((T, I, d), device=dev)
+        ops.gnn_stack(batch, u0_d, i0_d, L, leaky, ou, oi, drop=dr)
+        want_u, want_i, terms_u, terms_i = _sparse_stack_reference(cu, ci, u0, i0, L, leaky, dr)
+        assert_sum_close(ou.cpu().numpy(), want_u, terms_u)
+        assert_sum_close(oi.cpu().numpy(), want_i, terms_i)
+        for k in range(T):
+            ku, ki = torch.empty((U, d), device=dev), torch.empty((I, d), device=dev)
+            ops.gnn_interval(plans_u[k], plans_i[k], u0_d[k], i0_d[k], L, leaky, ku, ki, drop=dr, interval=k)
+            assert torch.equal(ku, ou[k]) and torch.equal(ki, oi[k])
 
 
 # ---- Recommender ------------------------------------------------------------------------------------------------------
