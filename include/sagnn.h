@@ -119,7 +119,7 @@ typedef struct sagnn_spmm_plan_info {
   int32_t short_thresh, long_thresh, chunk_edges;
   int32_t max_degree;
   int32_t on_device;     /* 1 if chunk metadata was uploaded (d_rowptr given) */
-  int32_t reserved;
+  int32_t weighted;      /* 1 if edge weights are set (sagnn_spmm_plan_set_weights); was `reserved`, always 0 before */
 } sagnn_spmm_plan_info;
 
 /* h_rowptr: host copy of rowptr [n_rows+1] (read during the call only).
@@ -136,6 +136,26 @@ int sagnn_spmm_plan_get_info(const sagnn_spmm_plan* plan, sagnn_spmm_plan_info* 
  * consecutive and in edge order. */
 int sagnn_spmm_plan_copy_chunks(const sagnn_spmm_plan* plan, int32_t* rows, int32_t* e_begin,
                                 int32_t* e_end, int64_t cap);
+/* Edge weights (opt-in; not in the reference, whose normalised edge values are cast to int32 and never read:
+ * DataHandler.py:53-59, model.py:84-86). d_weights: device array of nnz floats in colidx order, BORROWED: it must
+ * outlive the plan or be cleared first; NULL clears the weights. Refused for a NULL plan and for a host-only plan.
+ *
+ * With weights set, every entry that takes the plan computes
+ *     s[r,:] = sum over the row's stored edges e, in order, of w[e] * X[colidx[e],:]
+ * accumulated as acc = fmaf(w[e], x, acc) (one rounding per edge and element), and everything after s (activation,
+ * mask_out, residual, running sums, out2) is unchanged: sagnn_spmm_f32, _ex_f32, _drop_f32, sagnn_gnn_interval_* and
+ * their backwards. Under edge dropout a dropped edge is still a gather that is never issued, its weight is ignored, and
+ * scale = 1/keep multiplies the finished weighted sum. The weights are not checked on the device: NaN or Inf values are
+ * the caller's to keep out. A plan without weights runs exactly the kernels it ran before this entry existed.
+ *
+ * sagnn_spmm_batch_create reads the weight pointers of its 2 T plans at creation (later changes to a plan do not reach
+ * the batch) and fails when some plans have weights and others do not; sagnn_gnn_stack_* and their backwards follow
+ * the batch.
+ *
+ * ADJOINT CONTRACT with weights: the backward entries run the same kernels on the adjoint plans (below). For a correct
+ * gradient the adjoint plan must carry the SAME weight for the same (user, item) edge as the forward plan it
+ * transposes. The library does not check this; the Python layer guarantees it (graph.interval_pair(norm="sym")). */
+int sagnn_spmm_plan_set_weights(sagnn_spmm_plan* plan, const float* d_weights);
 /* Bytes of device workspace sagnn_spmm_f32 needs for feature width d (0 if no long rows). */
 size_t sagnn_spmm_workspace_bytes(const sagnn_spmm_plan* plan, int d);
 
@@ -150,7 +170,8 @@ size_t sagnn_spmm_workspace_bytes(const sagnn_spmm_plan* plan, int d);
  *     out[r,:]     = y            (if out     != NULL)
  *     acc_out[r,:] = acc_in + y   (if acc_out != NULL; acc_in NULL means 0)
  *
- * Edge values are ignored, as in the reference (model.py:84, :86). residual may be NULL.
+ * Edge values are ignored, as in the reference (model.py:84, :86), unless the plan carries weights
+ * (sagnn_spmm_plan_set_weights above: s[r,:] = sum of w[e] * X[c,:]). residual may be NULL.
  * acc_in may alias residual and may alias acc_out (in-place running sum). out/acc_out
  * must not alias X. At least one of out/acc_out is required.
  * -------------------------------------------------------------------------------- */

@@ -70,6 +70,11 @@ _FLAGS = [
                                  "(0, 1]; 1 = off. Not in the reference: its edgeDropout rewrites edge values that "
                                  "messagePropagate never reads, so the op is dead there and --keepRate only reaches the "
                                  "LSTM's output dropout"),
+    ("adjNorm", str, "none", "normalisation of the interval adjacencies: none (the unweighted sum the reference's graph "
+                             "computes) or sym (edge (u, i) weighs 1 / sqrt(deg_u * deg_i), on every entry point, "
+                             "training and inference). Not in the reference's graph: transToLsts(norm=True) computes "
+                             "these values (DataHandler.py:53-59) but they are cast to int32 and never read",
+     ("none", "sym")),
 ]
 
 

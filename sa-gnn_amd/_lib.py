@@ -39,7 +39,7 @@ class PlanInfo(ctypes.Structure):
     _fields_ = [("n_rows", c_int64), ("n_src", c_int64), ("nnz", c_int64),
                 ("n_long_rows", c_int64), ("n_chunks", c_int64), ("short_thresh", c_int32),
                 ("long_thresh", c_int32), ("chunk_edges", c_int32), ("max_degree", c_int32),
-                ("on_device", c_int32), ("reserved", c_int32)]
+                ("on_device", c_int32), ("weighted", c_int32)]
 
 
 # name -> (restype, argtypes); must list every symbol include/sagnn.h declares
@@ -56,6 +56,7 @@ SIGNATURES = {
                                        POINTER(Tuning), POINTER(c_void_p)]),
     "sagnn_spmm_plan_destroy": (c_int, [c_void_p]),
     "sagnn_spmm_plan_get_info": (c_int, [c_void_p, POINTER(PlanInfo)]),
+    "sagnn_spmm_plan_set_weights": (c_int, [c_void_p, c_void_p]),
     "sagnn_spmm_plan_copy_chunks": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64]),
     "sagnn_spmm_workspace_bytes": (c_size_t, [c_void_p, c_int]),
     "sagnn_spmm_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_float,

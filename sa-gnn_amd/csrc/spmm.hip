@@ -20,6 +20,13 @@
 // edge is kept — one Philox block per edge, a pure function of (seed, step, tag, user id, item id) — and replaces a
 // dropped index by -1 before the broadcast, so a dropped edge is a gather that is never issued. Every kernel is one
 // template whose drop-only arguments are a pack: with the pack empty it compiles to what it was without dropout.
+//
+// Edge weights (sagnn_spmm_plan_set_weights): s[r] = sum_e w[e] * X[col[e], :]. The lane that loads
+// colidx[e] loads w[e] from the same coalesced non-temporal stream and both are broadcast together; the gather
+// accumulates acc = fmaf(w, x, acc), one rounding per edge and element, in edge order. A dropped or absent edge has
+// index -1, gathers nothing and adds fmaf(w, 0, acc) = acc. The weights travel in the same trailing pack (none; drop;
+// weights; drop + weights): WEIGHTED is a compile-time property of an instantiation. The fix-ups add raw partial sums,
+// which the chunk waves have weighted already, so a weighted launch runs the fix-up kernels it would run unweighted.
 #include <float.h>
 
 #include <algorithm>
@@ -95,6 +102,13 @@ __device__ __forceinline__ int ldi_s(const int32_t* p) {
   return *p;
 #endif
 }
+__device__ __forceinline__ float ldf_s(const float* p) {
+#ifndef SAGNN_PLAIN_STREAMS
+  return __builtin_nontemporal_load(p);
+#else
+  return *p;
+#endif
+}
 __device__ __forceinline__ void add4(float4& a, const float4& b) {
   a.x += b.x;
   a.y += b.y;
@@ -121,6 +135,19 @@ __device__ __forceinline__ RowDrop seg_drop(const BatchDrop& b, int dir, int k) 
   r.tag = (dir ? b.tag_i : r.tag) | ((uint32_t)k << 8);
   r.rows_users = !dir;
   return r;
+}
+
+// acc += w * v (WEIGHTED: one fused multiply-add per element) or acc += v
+template <bool WEIGHTED>
+__device__ __forceinline__ void acc4(float4& a, float w, const float4& v) {
+  if constexpr (WEIGHTED) {
+    a.x = fmaf(w, v.x, a.x);
+    a.y = fmaf(w, v.y, a.y);
+    a.z = fmaf(w, v.z, a.z);
+    a.w = fmaf(w, v.w, a.w);
+  } else {
+    add4(a, v);
+  }
 }
 
 // The loading lane's filter: idx if edge (row, idx) is kept, else -1 (an index of -1 stays -1).
@@ -150,13 +177,42 @@ template <class T>
 struct KernelArg { using type = T; };
 template <class T>
 struct KernelArg<T*> { using type = T* __restrict__; };
+// A weighted launch appends its weights to either form of the pack: the edge weights of the plan (const float*), or for
+// the batched kernels a device table of the 2T segments' weight pointers, parallel to SegMeta (const float* const*).
+// The pack is then: none; (chunk_row, drop); (weights); (chunk_row, drop, weights).
+template <class... A>
+struct Pack {
+  static_assert(sizeof...(A) <= 3, "trailing arguments: none; chunk_row and the drop; the weights; all three");
+  static constexpr bool DROP = sizeof...(A) >= 2;
+  static constexpr bool WEIGHTED = sizeof...(A) == 1 || sizeof...(A) == 3;
+};
 template <class Drop>
 __device__ __forceinline__ Drop drop_of() { return Drop{}; }
+template <class Drop, class W>
+__device__ __forceinline__ Drop drop_of(W) { return Drop{}; }
 template <class Drop>
 __device__ __forceinline__ const Drop& drop_of(const int32_t*, const Drop& drop) { return drop; }
+template <class Drop, class W>
+__device__ __forceinline__ const Drop& drop_of(const int32_t*, const Drop& drop, W) { return drop; }
 __device__ __forceinline__ int chunk_row_of(int64_t) { return 0; }
+template <class W>
+__device__ __forceinline__ int chunk_row_of(int64_t, W) { return 0; }
 template <class Drop>
 __device__ __forceinline__ int chunk_row_of(int64_t ci, const int32_t* chunk_row, const Drop&) { return chunk_row[ci]; }
+template <class Drop, class W>
+__device__ __forceinline__ int chunk_row_of(int64_t ci, const int32_t* chunk_row, const Drop&, W) { return chunk_row[ci]; }
+// the weights of the launch's plan, or of segment `seg` of a batch
+__device__ __forceinline__ const float* weights_of(int) { return nullptr; }
+template <class Drop>
+__device__ __forceinline__ const float* weights_of(int, const int32_t*, const Drop&) { return nullptr; }
+__device__ __forceinline__ const float* weights_of(int, const float* w) { return w; }
+__device__ __forceinline__ const float* weights_of(int seg, const float* const* table) { return table[seg]; }
+template <class Drop>
+__device__ __forceinline__ const float* weights_of(int, const int32_t*, const Drop&, const float* w) { return w; }
+template <class Drop>
+__device__ __forceinline__ const float* weights_of(int seg, const int32_t*, const Drop&, const float* const* table) {
+  return table[seg];
+}
 __device__ __forceinline__ float4 scaled(float4 s) { return s; }
 __device__ __forceinline__ float4 scaled(float4 s, float scale) {
   return make_float4(scale * s.x, scale * s.y, scale * s.z, scale * s.w);
@@ -231,34 +287,50 @@ __global__ void mask_scale_kernel(const float* __restrict__ g, int64_t ldg, int6
 // Returns the total in every lane-group (cross-group xor reduction).
 // DROP: the edges belong to row `row`; each lane filters the 64-edge slice it loaded when the slice is taken up, so
 // the load of the next slice still overlaps this slice's gathers.
-template <int LPR, bool IDENT, bool DROP = false>
+// WEIGHTED: edge e counts w[e] times; a slice's weights are requested with its indices and broadcast with them.
+template <int LPR, bool IDENT, bool DROP = false, bool WEIGHTED = false>
 __device__ __forceinline__ float4 wave_row_sum(const int32_t* __restrict__ colidx, int e0, int e1,
                                                const float* __restrict__ X, int64_t ldx,
                                                int lane, int grp, int col, bool lane_on, const RowDrop& dr = RowDrop{},
-                                               int row = 0) {
+                                               int row = 0, const float* __restrict__ w = nullptr) {
+  static_assert(!(IDENT && WEIGHTED), "the fix-up pass adds partial sums that are weighted already");
   constexpr int G = kWave / LPR;
   constexpr int STEP = G * kUnroll;  // divides 64 for every LPR in {8,16,32,64}
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
   int idx_next = -1;
-  if (e0 + lane < e1) idx_next = IDENT ? (e0 + lane) : ldi_s(colidx + e0 + lane);
+  float w_next = 0.f;
+  if (e0 + lane < e1) {
+    idx_next = IDENT ? (e0 + lane) : ldi_s(colidx + e0 + lane);
+    if constexpr (WEIGHTED) w_next = ldf_s(w + e0 + lane);
+  }
   for (int e = e0; e < e1; e += kWave) {
     const int idx = keep_edge<DROP>(dr, row, idx_next);
+    const float wt = w_next;
     const int en = e + kWave;
     idx_next = -1;
-    if (en + lane < e1) idx_next = IDENT ? (en + lane) : ldi_s(colidx + en + lane);
+    if constexpr (WEIGHTED) w_next = 0.f;
+    if (en + lane < e1) {
+      idx_next = IDENT ? (en + lane) : ldi_s(colidx + en + lane);
+      if constexpr (WEIGHTED) w_next = ldf_s(w + en + lane);
+    }
     const int cnt = min(kWave, e1 - e);
     for (int j = 0; j < cnt; j += STEP) {
       float4 v[kUnroll];
       int c[kUnroll];
+      float cw[kUnroll];
 #pragma unroll
-      for (int u = 0; u < kUnroll; ++u) c[u] = __shfl(idx, j + u * G + grp);
+      for (int u = 0; u < kUnroll; ++u) {
+        c[u] = __shfl(idx, j + u * G + grp);
+        if constexpr (WEIGHTED) cw[u] = __shfl(wt, j + u * G + grp);
+        else cw[u] = 1.f;
+      }
 #pragma unroll
       for (int u = 0; u < kUnroll; ++u) {
         v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (c[u] >= 0 && lane_on) v[u] = ld4(X + (int64_t)c[u] * ldx + col);
       }
 #pragma unroll
-      for (int u = 0; u < kUnroll; ++u) add4(acc, v[u]);
+      for (int u = 0; u < kUnroll; ++u) acc4<WEIGHTED>(acc, cw[u], v[u]);
     }
   }
 #pragma unroll
@@ -273,11 +345,11 @@ __device__ __forceinline__ float4 wave_row_sum(const int32_t* __restrict__ colid
 
 // A wave's share of the row blocks: RPW consecutive rows starting at row0 (short rows by lane groups, medium rows by
 // the whole wave; long rows belong to the chunk waves + fix-up).
-template <int LPR, int RPW, bool DROP>
+template <int LPR, int RPW, bool DROP, bool WEIGHTED>
 __device__ __forceinline__ void rows_wave(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
                                           const float* __restrict__ X, int64_t ldx, int d, int64_t n_rows, int64_t row0,
                                           int short_t, int long_t, const Epilogue& ep, int lane,
-                                          const RowDrop& dr) {
+                                          const RowDrop& dr, const float* __restrict__ w) {
   constexpr int G = kWave / LPR;
   const int grp = lane / LPR;
   const int sub = lane % LPR;
@@ -298,7 +370,11 @@ __device__ __forceinline__ void rows_wave(const int32_t* __restrict__ rowptr, co
   int e0_n = __shfl(rp, grp);
   int dg_n = __shfl(deg_l, grp);
   int idx_n = -1;
-  if (dg_n <= short_t && sub < dg_n) idx_n = ldi_s(colidx + e0_n + sub);
+  float w_n = 0.f;           // WEIGHTED: the weight travels with its index, from the same lane
+  if (dg_n <= short_t && sub < dg_n) {
+    idx_n = ldi_s(colidx + e0_n + sub);
+    if constexpr (WEIGHTED) w_n = ldf_s(w + e0_n + sub);
+  }
 #pragma unroll 1
   for (int it = 0; it < RPW / G; ++it) {
     const int lr = it * G + grp;
@@ -306,13 +382,18 @@ __device__ __forceinline__ void rows_wave(const int32_t* __restrict__ rowptr, co
     const int dg = dg_n;
     // DROP: the prefetched slice is filtered here, not where it was requested, so its load stays in flight
     int idx = keep_edge<DROP>(dr, (int)row0 + lr, idx_n);
+    float wt = w_n;
     const bool mine = (lr < nr) && (dg <= short_t);
     const int my_deg = mine ? dg : 0;
     if (it + 1 < RPW / G) {
       e0_n = __shfl(rp, lr + G);
       dg_n = __shfl(deg_l, lr + G);
       idx_n = -1;
-      if (dg_n <= short_t && sub < dg_n) idx_n = ldi_s(colidx + e0_n + sub);
+      if constexpr (WEIGHTED) w_n = 0.f;
+      if (dg_n <= short_t && sub < dg_n) {
+        idx_n = ldi_s(colidx + e0_n + sub);
+        if constexpr (WEIGHTED) w_n = ldf_s(w + e0_n + sub);
+      }
     }
     int maxdeg = 0;
 #pragma unroll
@@ -325,20 +406,26 @@ __device__ __forceinline__ void rows_wave(const int32_t* __restrict__ rowptr, co
       if (eo > 0) {
         const int k = eo + sub;
         idx = (k < my_deg) ? keep_edge<DROP>(dr, (int)row0 + lr, ldi_s(colidx + e0 + k)) : -1;
+        if constexpr (WEIGHTED) wt = (k < my_deg) ? ldf_s(w + e0 + k) : 0.f;
       }
       const int lim = min(LPR, maxdeg - eo);
       for (int j = 0; j < lim; j += kUnroll) {
         float4 v[kUnroll];
         int c[kUnroll];
+        float cw[kUnroll];
 #pragma unroll
-        for (int u = 0; u < kUnroll; ++u) c[u] = __shfl(idx, grp * LPR + j + u);
+        for (int u = 0; u < kUnroll; ++u) {
+          c[u] = __shfl(idx, grp * LPR + j + u);
+          if constexpr (WEIGHTED) cw[u] = __shfl(wt, grp * LPR + j + u);
+          else cw[u] = 1.f;
+        }
 #pragma unroll
         for (int u = 0; u < kUnroll; ++u) {
           v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
           if (c[u] >= 0 && lane_on) v[u] = ld4(X + (int64_t)c[u] * ldx + col);
         }
 #pragma unroll
-        for (int u = 0; u < kUnroll; ++u) add4(acc, v[u]);
+        for (int u = 0; u < kUnroll; ++u) acc4<WEIGHTED>(acc, cw[u], v[u]);
       }
     }
     if (mine && lane_on) finish_row(ep, row0 + lr, col, drop_scale<DROP>(dr, acc));
@@ -351,21 +438,20 @@ __device__ __forceinline__ void rows_wave(const int32_t* __restrict__ rowptr, co
     const int e0 = __builtin_amdgcn_readlane(rp, lr);
     const int dg = __builtin_amdgcn_readlane(deg_l, lr);
     const float4 s =
-        wave_row_sum<LPR, false, DROP>(colidx, e0, e0 + dg, X, ldx, lane, grp, col, lane_on, dr, (int)row0 + lr);
+        wave_row_sum<LPR, false, DROP, WEIGHTED>(colidx, e0, e0 + dg, X, ldx, lane, grp, col, lane_on, dr, (int)row0 + lr, w);
     if (grp == 0 && lane_on) finish_row(ep, row0 + lr, col, drop_scale<DROP>(dr, s));
   }
 }
 
 // One launch covers the long-row chunks (first `chunk_blocks` blocks, heaviest work first)
 // and the row blocks (remaining blocks).
-template <int LPR, int RPW, class... DropArgs>   // none, or (chunk_row, RowDrop)
+template <int LPR, int RPW, class... DropArgs>   // none; (chunk_row, RowDrop); (weights); (chunk_row, RowDrop, weights)
 __global__ __launch_bounds__(kBlock) void spmm_rows_kernel(
     const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
     const float* __restrict__ X, int64_t ldx, int d, int64_t n_rows, int short_t, int long_t,
     const int32_t* __restrict__ chunk_e0, const int32_t* __restrict__ chunk_e1, int64_t n_chunks,
     int chunk_blocks, float* __restrict__ partial, Epilogue ep, typename KernelArg<DropArgs>::type... da) {
-  static_assert(sizeof...(DropArgs) == 0 || sizeof...(DropArgs) == 2, "drop-only arguments: none, or chunk_row and the drop");
-  constexpr bool DROP = sizeof...(DropArgs) != 0;
+  constexpr bool DROP = Pack<DropArgs...>::DROP, WEIGHTED = Pack<DropArgs...>::WEIGHTED;
   const int lane = threadIdx.x & (kWave - 1);
   const int wave = threadIdx.x / kWave;
 
@@ -375,15 +461,17 @@ __global__ __launch_bounds__(kBlock) void spmm_rows_kernel(
     const bool lane_on = col < d;
     const int64_t ci = (int64_t)blockIdx.x * kWavesPerBlock + wave;
     if (ci >= n_chunks) return;
-    const float4 s = wave_row_sum<LPR, false, DROP>(colidx, chunk_e0[ci], chunk_e1[ci], X, ldx, lane, grp, col, lane_on,
-                                                    drop_of<RowDrop>(da...), chunk_row_of(ci, da...));
+    const float4 s = wave_row_sum<LPR, false, DROP, WEIGHTED>(colidx, chunk_e0[ci], chunk_e1[ci], X, ldx, lane, grp, col,
+                                                              lane_on, drop_of<RowDrop>(da...), chunk_row_of(ci, da...),
+                                                              weights_of(0, da...));
     if (grp == 0 && lane_on) st4(partial + ci * (int64_t)d + col, s);
     return;
   }
 
   const int64_t row0 = ((int64_t)(blockIdx.x - chunk_blocks) * kWavesPerBlock + wave) * RPW;
   if (row0 >= n_rows) return;
-  rows_wave<LPR, RPW, DROP>(rowptr, colidx, X, ldx, d, n_rows, row0, short_t, long_t, ep, lane, drop_of<RowDrop>(da...));
+  rows_wave<LPR, RPW, DROP, WEIGHTED>(rowptr, colidx, X, ldx, d, n_rows, row0, short_t, long_t, ep, lane,
+                                      drop_of<RowDrop>(da...), weights_of(0, da...));
 }
 
 // Fix-up for long rows: add the partial sums of a row in chunk order (a drop launch: and scale the finished sum once),
@@ -445,16 +533,16 @@ __device__ __forceinline__ Epilogue seg_epilogue(const DirArgs& a, int k) {
   return e;
 }
 
-// A drop launch: a segment's tag and orientation come from its (direction, interval).
-template <int LPR, int RPW, class... DropArgs>   // none, or (chunk_row, BatchDrop)
+// A drop launch: a segment's tag and orientation come from its (direction, interval). A weighted launch: a segment's
+// weights come from the table of 2T pointers, indexed like SegMeta.
+template <int LPR, int RPW, class... DropArgs>   // none; (chunk_row, BatchDrop); (weight table); all three
 __global__ __launch_bounds__(kBlock) void spmm_rows_batch_kernel(const SegMeta* __restrict__ meta, BatchGeom g,
                                                                 const int32_t* __restrict__ chunk_e0,
                                                                 const int32_t* __restrict__ chunk_e1,
                                                                 const int32_t* __restrict__ chunk_seg, int64_t n_chunks,
                                                                 float* __restrict__ partial, int d, DirArgs au, DirArgs ai,
                                                                 typename KernelArg<DropArgs>::type... da) {
-  static_assert(sizeof...(DropArgs) == 0 || sizeof...(DropArgs) == 2, "drop-only arguments: none, or chunk_row and the drop");
-  constexpr bool DROP = sizeof...(DropArgs) != 0;
+  constexpr bool DROP = Pack<DropArgs...>::DROP, WEIGHTED = Pack<DropArgs...>::WEIGHTED;
   const int lane = threadIdx.x & (kWave - 1);
   const int wave = threadIdx.x / kWave;
   if ((int)blockIdx.x < g.chunk_blocks) {
@@ -466,9 +554,10 @@ __global__ __launch_bounds__(kBlock) void spmm_rows_batch_kernel(const SegMeta* 
     const int seg = __builtin_amdgcn_readfirstlane(chunk_seg[ci]);
     const int dir = seg >= g.T, k = seg - dir * g.T;
     const DirArgs& a = dir ? ai : au;
-    const float4 s = wave_row_sum<LPR, false, DROP>(meta[seg].colidx, chunk_e0[ci], chunk_e1[ci], a.X + (int64_t)k * a.s_X,
-                                                    a.ldx, lane, grp, col, lane_on,
-                                                    seg_drop(drop_of<BatchDrop>(da...), dir, k), chunk_row_of(ci, da...));
+    const float4 s = wave_row_sum<LPR, false, DROP, WEIGHTED>(meta[seg].colidx, chunk_e0[ci], chunk_e1[ci],
+                                                              a.X + (int64_t)k * a.s_X, a.ldx, lane, grp, col, lane_on,
+                                                              seg_drop(drop_of<BatchDrop>(da...), dir, k),
+                                                              chunk_row_of(ci, da...), weights_of(seg, da...));
     if (grp == 0 && lane_on) st4(partial + ci * (int64_t)d + col, s);
     return;
   }
@@ -483,8 +572,9 @@ __global__ __launch_bounds__(kBlock) void spmm_rows_batch_kernel(const SegMeta* 
   const SegMeta m = meta[dir * g.T + k];
   const DirArgs& a = dir ? ai : au;
   const Epilogue ep = seg_epilogue(a, k);
-  rows_wave<LPR, RPW, DROP>(m.rowptr, m.colidx, a.X + (int64_t)k * a.s_X, a.ldx, d, n_rows, row0, m.short_t, m.long_t, ep,
-                            lane, seg_drop(drop_of<BatchDrop>(da...), dir, k));
+  rows_wave<LPR, RPW, DROP, WEIGHTED>(m.rowptr, m.colidx, a.X + (int64_t)k * a.s_X, a.ldx, d, n_rows, row0, m.short_t,
+                                      m.long_t, ep, lane, seg_drop(drop_of<BatchDrop>(da...), dir, k),
+                                      weights_of(dir * g.T + k, da...));
 }
 
 template <int LPR, class... Scale>
@@ -524,6 +614,7 @@ struct sagnn_spmm_plan {
   int32_t* d_meta = nullptr;
   const int32_t *d_chunk_e0 = nullptr, *d_chunk_e1 = nullptr, *d_long_row = nullptr,
                 *d_long_slot = nullptr, *d_chunk_row = nullptr;   // chunk_row: read by the drop kernels only
+  const float* d_weights = nullptr;   // borrowed, [nnz] in colidx order (sagnn_spmm_plan_set_weights); NULL = unweighted
 };
 
 namespace {
@@ -659,6 +750,16 @@ extern "C" int sagnn_spmm_plan_destroy(sagnn_spmm_plan* plan) {
   return SAGNN_OK;
 }
 
+extern "C" int sagnn_spmm_plan_set_weights(sagnn_spmm_plan* plan, const float* d_weights) {
+  if (!plan) return sagnn::fail(SAGNN_ERR_NULL, "plan is NULL");
+  if (!plan->info.on_device) return sagnn::fail(SAGNN_ERR_ARG, "plan was built host-only (no device CSR): it takes no weights");
+  if (d_weights && (reinterpret_cast<uintptr_t>(d_weights) & 3))
+    return sagnn::fail(SAGNN_ERR_ALIGN, "weights: pointer must be 4-byte aligned");
+  plan->d_weights = d_weights;
+  plan->info.weighted = d_weights ? 1 : 0;
+  return SAGNN_OK;
+}
+
 extern "C" int sagnn_spmm_plan_get_info(const sagnn_spmm_plan* plan, sagnn_spmm_plan_info* info) {
   if (!plan || !info) return sagnn::fail(SAGNN_ERR_NULL, "plan/info is NULL");
   *info = plan->info;
@@ -687,8 +788,8 @@ extern "C" size_t sagnn_spmm_workspace_bytes(const sagnn_spmm_plan* plan, int d)
 // ------------------------------------------------------------------------------------------
 namespace {
 
-// drop = nullptr: the default kernels. The row block of a wave (small) and the drop-only arguments, none or all, name
-// the instantiation of a kernel; its launch is stated once.
+// drop = nullptr and a plan without weights: the default kernels. The row block of a wave (small) and the trailing
+// arguments (the drop's, the plan's weights, both or neither) name the instantiation of a kernel; its launch is stated once.
 template <int LPR>
 int launch_spmm(const sagnn_spmm_plan* p, const float* X, int64_t ldx, int d, const Epilogue& ep,
                 float* partial, hipStream_t stream, const RowDrop* drop = nullptr) {
@@ -709,9 +810,16 @@ int launch_spmm(const sagnn_spmm_plan* p, const float* X, int64_t ldx, int d, co
                          p->info.short_thresh, p->info.long_thresh, p->d_chunk_e0, p->d_chunk_e1, n_chunks,
                          (int)chunk_blocks, partial, ep, da...);
     };
-    if (drop)
+    const float* w = p->d_weights;
+    if (drop && w)
+      rows(small ? spmm_rows_kernel<LPR, RPW_SMALL, const int32_t*, RowDrop, const float*>
+                 : spmm_rows_kernel<LPR, kRowsPerWave, const int32_t*, RowDrop, const float*>,
+           p->d_chunk_row, *drop, w);
+    else if (drop)
       rows(small ? spmm_rows_kernel<LPR, RPW_SMALL, const int32_t*, RowDrop> : spmm_rows_kernel<LPR, kRowsPerWave, const int32_t*, RowDrop>,
            p->d_chunk_row, *drop);
+    else if (w)
+      rows(small ? spmm_rows_kernel<LPR, RPW_SMALL, const float*> : spmm_rows_kernel<LPR, kRowsPerWave, const float*>, w);
     else
       rows(small ? spmm_rows_kernel<LPR, RPW_SMALL> : spmm_rows_kernel<LPR, kRowsPerWave>);
     SAGNN_HIP_TRY(hipGetLastError());
@@ -900,6 +1008,7 @@ struct sagnn_spmm_batch {
   int64_t n_chunks = 0, n_long = 0, nnz = 0;
   // device: [SegMeta x 2T] and [chunk_e0 | chunk_e1 | chunk_seg | long_row | long_seg | long_slot (+1) | chunk_row]
   SegMeta* d_meta = nullptr;
+  const float** d_weights = nullptr;   // [2T] the segments' weight pointers as the plans held them at creation; NULL = unweighted
   int32_t* d_ints = nullptr;
   const int32_t *d_chunk_e0 = nullptr, *d_chunk_e1 = nullptr, *d_chunk_seg = nullptr, *d_long_row = nullptr,
                 *d_long_seg = nullptr, *d_long_slot = nullptr, *d_chunk_row = nullptr;
@@ -919,17 +1028,25 @@ extern "C" int sagnn_spmm_batch_create(const sagnn_spmm_plan* const* plans_user,
     if (plans_user[k]->info.n_rows != plans_user[0]->info.n_rows || plans_item[k]->info.n_rows != plans_item[0]->info.n_rows)
       return sagnn::fail(SAGNN_ERR_ARG, "interval %d: every interval must have the same user / item counts", k);
   }
+  const bool weighted = plans_user[0]->d_weights != nullptr;
+  for (int k = 0; k < T; ++k)
+    for (const sagnn_spmm_plan* p : {plans_user[k], plans_item[k]})
+      if ((p->d_weights != nullptr) != weighted)
+        return sagnn::fail(SAGNN_ERR_ARG, "interval %d: some plans of the batch carry edge weights and others do not "
+                           "(sagnn_spmm_plan_set_weights): give all 2 T plans weights or none", k);
   sagnn_spmm_batch* b = new (std::nothrow) sagnn_spmm_batch();
   if (!b) return sagnn::fail(SAGNN_ERR_NOMEM, "out of host memory");
   b->T = T;
   b->U = plans_user[0]->info.n_rows;
   b->I = plans_item[0]->info.n_rows;
   std::vector<SegMeta> meta(2 * (size_t)T);
+  std::vector<const float*> wtab(2 * (size_t)T);
   std::vector<int32_t> ce0, ce1, cseg, crow, lrow, lseg, lslot;
   try {
     for (int s = 0; s < 2 * T; ++s) {
       const sagnn_spmm_plan* p = s < T ? plans_user[s] : plans_item[s - T];
       meta[s] = SegMeta{p->d_rowptr, p->d_colidx, p->info.short_thresh, p->info.long_thresh};
+      wtab[s] = p->d_weights;
       const int32_t coff = (int32_t)ce0.size();
       ce0.insert(ce0.end(), p->chunk_e0.begin(), p->chunk_e0.end());
       ce1.insert(ce1.end(), p->chunk_e1.begin(), p->chunk_e1.end());
@@ -955,6 +1072,10 @@ extern "C" int sagnn_spmm_batch_create(const sagnn_spmm_plan* const* plans_user,
   b->n_long = (int64_t)lrow.size();
   hipError_t e = hipMalloc((void**)&b->d_meta, meta.size() * sizeof(SegMeta));
   if (e == hipSuccess) e = hipMemcpy(b->d_meta, meta.data(), meta.size() * sizeof(SegMeta), hipMemcpyHostToDevice);
+  if (e == hipSuccess && weighted) {
+    e = hipMalloc((void**)&b->d_weights, wtab.size() * sizeof(const float*));
+    if (e == hipSuccess) e = hipMemcpy(b->d_weights, wtab.data(), wtab.size() * sizeof(const float*), hipMemcpyHostToDevice);
+  }
   if (e == hipSuccess && b->n_chunks > 0) {
     const size_t nck = ce0.size(), nl = lrow.size();
     std::vector<int32_t> host;
@@ -978,6 +1099,7 @@ extern "C" int sagnn_spmm_batch_create(const sagnn_spmm_plan* const* plans_user,
   }
   if (e != hipSuccess) {
     if (b->d_meta) (void)hipFree(b->d_meta);
+    if (b->d_weights) (void)hipFree(b->d_weights);
     if (b->d_ints) (void)hipFree(b->d_ints);
     delete b;
     return sagnn::hip_fail(e, "batch tables (hipMalloc / hipMemcpy)");
@@ -989,6 +1111,7 @@ extern "C" int sagnn_spmm_batch_create(const sagnn_spmm_plan* const* plans_user,
 extern "C" int sagnn_spmm_batch_destroy(sagnn_spmm_batch* b) {
   if (!b) return SAGNN_OK;
   if (b->d_meta) (void)hipFree(b->d_meta);
+  if (b->d_weights) (void)hipFree(b->d_weights);
   if (b->d_ints) (void)hipFree(b->d_ints);
   delete b;
   return SAGNN_OK;
@@ -1019,10 +1142,18 @@ int launch_batch(const sagnn_spmm_batch* b, int d, const DirArgs& au, const DirA
       hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kBlock), 0, stream, b->d_meta, g, b->d_chunk_e0, b->d_chunk_e1,
                          b->d_chunk_seg, b->n_chunks, partial, d, au, ai, da...);
     };
-    if (drop)
+    const float* const* w = b->d_weights;
+    if (drop && w)
+      rows(small ? spmm_rows_batch_kernel<LPR, RPW_SMALL, const int32_t*, BatchDrop, const float* const*>
+                 : spmm_rows_batch_kernel<LPR, kRowsPerWave, const int32_t*, BatchDrop, const float* const*>,
+           b->d_chunk_row, *drop, w);
+    else if (drop)
       rows(small ? spmm_rows_batch_kernel<LPR, RPW_SMALL, const int32_t*, BatchDrop>
                  : spmm_rows_batch_kernel<LPR, kRowsPerWave, const int32_t*, BatchDrop>,
            b->d_chunk_row, *drop);
+    else if (w)
+      rows(small ? spmm_rows_batch_kernel<LPR, RPW_SMALL, const float* const*>
+                 : spmm_rows_batch_kernel<LPR, kRowsPerWave, const float* const*>, w);
     else
       rows(small ? spmm_rows_batch_kernel<LPR, RPW_SMALL> : spmm_rows_batch_kernel<LPR, kRowsPerWave>);
     SAGNN_HIP_TRY(hipGetLastError());

@@ -43,14 +43,30 @@ def csr_arrays(mat, phantom_edge: bool = True):
     return rowptr.astype(np.int32), np.ascontiguousarray(col)
 
 
+def sym_norm_weights(rowptr, colidx, n_rows: int, n_src: int):
+    """float32 w[e] = 1 / sqrt(deg_row[r(e)] * deg_col[colidx[e]]) for the stored pattern (rowptr, colidx): the values of
+    D_r^-1/2 A D_c^-1/2 that the reference's transToLsts(norm=True) computes and then drops (DataHandler.py:53-59,
+    model.py:84-86). deg_row / deg_col count the pattern's stored edges per row / per column, duplicates included;
+    computed in float64 and rounded once."""
+    rowptr = np.asarray(rowptr, dtype=np.int64)
+    colidx = np.asarray(colidx, dtype=np.int64)
+    if rowptr.size != n_rows + 1 or (colidx.size and (colidx.min() < 0 or colidx.max() >= n_src)):
+        raise ValueError("sym_norm_weights: rowptr / colidx do not describe an n_rows x n_src pattern")
+    deg_row = np.diff(rowptr)
+    deg_col = np.bincount(colidx, minlength=n_src)
+    rows = np.repeat(np.arange(n_rows, dtype=np.int64), deg_row)
+    prod = deg_row[rows].astype(np.float64) * deg_col[colidx].astype(np.float64)
+    return (1.0 / np.sqrt(prod)).astype(np.float32)
+
+
 class IntervalAdj:
     """One direction of one interval graph: what the reference holds as a tf SparseTensor
     (model.py:234 / :236). `.indices`-style access is not offered: the kernels use CSR."""
 
-    def __init__(self, rowptr, colidx, shape, device, tuning=None, validate=True):
+    def __init__(self, rowptr, colidx, shape, device, tuning=None, validate=True, weights=None):
         self.dense_shape = (int(shape[0]), int(shape[1]))
         self.plan = SpmmPlan(rowptr, colidx, self.dense_shape[0], self.dense_shape[1], device=device,
-                             tuning=tuning, validate=validate)
+                             tuning=tuning, validate=validate, weights=weights)
         self.nnz = self.plan.nnz
 
     @classmethod
@@ -70,8 +86,45 @@ def exact_transpose_arrays(mat):
     return rowptr.astype(np.int32), np.ascontiguousarray(np.asarray(coo.row, dtype=np.int32)[order])
 
 
-def interval_pair(sub_mat, device, tuning=None):
+NORMS = ("none", "sym")
+
+
+def merged_arrays(mat):
+    """csr_arrays(mat) with duplicated stored entries merged: each (row, column) once, columns ascending within a row.
+    Explicit zeros stay edges and an empty matrix keeps its phantom edge (0, 0)."""
+    rowptr, colidx = csr_arrays(mat)
+    n_rows, n_cols = int(mat.shape[0]), int(mat.shape[1])
+    rows = np.repeat(np.arange(n_rows, dtype=np.int64), np.diff(rowptr))
+    key = np.unique(rows * max(n_cols, 1) + colidx)
+    rows, cols = key // max(n_cols, 1), key % max(n_cols, 1)
+    rp = np.zeros(n_rows + 1, dtype=np.int64)
+    np.cumsum(np.bincount(rows, minlength=n_rows), out=rp[1:])
+    return rp.astype(np.int32), np.ascontiguousarray(cols.astype(np.int32))
+
+
+def _sym_pair(sub_mat, device, tuning):
+    """The sym-normalised pair: the merged pattern and its exact transpose, the same weight on both for one
+    (user, item), so each direction is the other's adjoint, weights included."""
+    U, I = int(sub_mat.shape[0]), int(sub_mat.shape[1])
+    rp, ci = merged_arrays(sub_mat)
+    w = sym_norm_weights(rp, ci, U, I)
+    users = np.repeat(np.arange(U, dtype=np.int32), np.diff(rp))
+    order = np.argsort(ci, kind="stable")                           # by item, users ascending within an item
+    rp_t = np.zeros(I + 1, dtype=np.int64)
+    np.cumsum(np.bincount(ci, minlength=I), out=rp_t[1:])
+    fwd = IntervalAdj(rp, ci, (U, I), device, tuning=tuning, weights=w)
+    tp = IntervalAdj(rp_t.astype(np.int32), np.ascontiguousarray(users[order]), (I, U), device, tuning=tuning,
+                     weights=np.ascontiguousarray(w[order]))
+    return fwd, tp
+
+
+def interval_pair(sub_mat, device, tuning=None, norm="none"):
     """(subAdj[k], subTpAdj[k]) for one interval matrix (reference model.py:230-237).
+
+    norm="sym" (not in the reference's graph): the pattern is what csr_arrays emits with duplicated
+    stored entries MERGED, edge (u, i) weighs 1 / sqrt(deg_u * deg_i) with the degrees counted on that pattern
+    (sym_norm_weights), the item-side plan is the exact transpose with the same weights, and no partner_adjoint is
+    built: the pair is its own adjoint. norm="none" is everything below, unchanged.
 
     With duplicated stored entries the two patterns are NOT transposes of each other (forward
     counts a duplicate twice, DataHandler.transpose merges it — DataHandler.py:9-11), so the
@@ -80,6 +133,10 @@ def interval_pair(sub_mat, device, tuning=None):
     d/d e_i of the user-side sum gathers through the forward pattern's true transpose (the
     duplicate counts twice, as TF's gather gradient does), d/d e_u of the item-side sum through
     the merged forward pattern."""
+    if norm not in NORMS:
+        raise ValueError(f"norm = {norm!r}: one of {NORMS}")
+    if norm == "sym":
+        return _sym_pair(sub_mat, device, tuning)
     fwd = IntervalAdj.from_scipy(sub_mat, device, tuning)
     tp_mat = transpose(sub_mat)
     tp = IntervalAdj.from_scipy(tp_mat, device, tuning)

@@ -20,7 +20,7 @@ from . import ops
 from .Params import args
 from .Utils import NNLayers as NNs
 from .Utils.attention import MultiHeadSelfAttention
-from .graph import interval_pair
+from .graph import NORMS, interval_pair
 
 
 def random_fusion_params(d: int, device, seed: int = 0) -> dict:
@@ -967,7 +967,7 @@ class Recommender:
         os.makedirs(os.path.join(directory, "Models"), exist_ok=True)
         with open(os.path.join(directory, "History", args.save_path + ".his"), "wb") as fs:
             pickle.dump(self.metrics, fs)
-        state = {"params": {k: v.detach().cpu() for k, v in NNs.params.items()}}
+        state = {"params": {k: v.detach().cpu() for k, v in NNs.params.items()}, "adjNorm": args.adjNorm}
         if getattr(self, "optimizer", None) is not None:
             state["optimizer"] = self.optimizer.state_dict()
         torch.save(state, os.path.join(directory, "Models", args.save_path))
@@ -978,6 +978,10 @@ class Recommender:
         import os
         import pickle
         state = torch.load(os.path.join(directory, "Models", args.load_model), weights_only=True)
+        stored_norm = state.get("adjNorm", "none")       # a checkpoint from before --adjNorm is an unnormalised model
+        if stored_norm != args.adjNorm:
+            raise ValueError(f"checkpoint was trained with --adjNorm {stored_norm}, this run has --adjNorm {args.adjNorm}: "
+                             "the normalisation is part of the model")
         saved = state["params"]
         if set(saved) != set(NNs.params):
             raise KeyError(f"checkpoint variables differ from the model's: missing {sorted(set(NNs.params) - set(saved))[:4]}, "
@@ -1001,12 +1005,14 @@ class Recommender:
         interval and both directions, leaky slope, then the hot path."""
         if not 0.0 < args.edgeKeepRate <= 1.0:
             raise ValueError(f"--edgeKeepRate {args.edgeKeepRate}: need a rate in (0, 1]")
+        if args.adjNorm not in NORMS:
+            raise ValueError(f"--adjNorm {args.adjNorm}: one of {NORMS}")
         NNs.reset(self.device)
         NNs.leaky = args.leaky
         self.actFunc = "leakyRelu"
         self.subAdj, self.subTpAdj = [], []
         for i in range(args.graphNum):
-            adj, tp = interval_pair(self.handler.subMat[i], self.device)
+            adj, tp = interval_pair(self.handler.subMat[i], self.device, norm=args.adjNorm)
             self.subAdj.append(adj)
             self.subTpAdj.append(tp)
         self.maxTime = self.handler.maxTime

@@ -73,14 +73,33 @@ def _f32_rows(name: str, t: torch.Tensor | None, d: int, rows: int | None = None
     return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), d)
 
 
+def _check_weights(weights, nnz: int) -> torch.Tensor:
+    """The edge weights of a plan as a host float32 tensor: nnz finite values (TypeError / ValueError otherwise)."""
+    w = torch.as_tensor(weights)
+    if w.dtype != torch.float32:
+        raise TypeError(f"weights must be float32, got {w.dtype}")
+    if w.dim() != 1 or w.numel() != nnz:
+        raise ValueError(f"weights: expected {nnz} values (one per stored edge, in colidx order), got shape {tuple(w.shape)}")
+    w = w.detach().cpu()
+    if not bool(torch.isfinite(w).all()):
+        raise ValueError("weights: NaN or Inf among the edge weights")
+    return w
+
+
 class SpmmPlan:
     """Degree-class plan for one CSR adjacency (sagnn_spmm_plan_*). Owns the device CSR copies.
 
     rowptr / colidx: int32, numpy or torch (host or device). With device=None a host-only plan
-    is built (no GPU touched) for inspecting the chunking."""
+    is built (no GPU touched) for inspecting the chunking.
+
+    weights: None (the unweighted sum, the kernels of a plan without weights), or nnz finite float32 values in colidx
+    order, numpy or torch: every product on this plan then sums w[e] * X[colidx[e]] (sagnn_spmm_plan_set_weights,
+    DESIGN.md §17). They are checked on the host; the plan keeps the device copy alive. For a correct backward pass
+    the adjoint plan must carry the same weight for the same (user, item): graph.interval_pair(norm="sym") builds
+    such pairs."""
 
     def __init__(self, rowptr, colidx, n_rows: int, n_src: int, device=None,
-                 tuning: tuple[int, int, int] | None = None, validate: bool = True):
+                 tuning: tuple[int, int, int] | None = None, validate: bool = True, weights=None):
         lib = _lib.load()
         self._lib = lib
         self._h = ctypes.c_void_p()
@@ -92,6 +111,9 @@ class SpmmPlan:
         if rp_t.numel() != self.n_rows + 1:
             raise ValueError(f"rowptr has {rp_t.numel()} entries, expected n_rows+1 = {self.n_rows + 1}")
         self.nnz = int(ci_t.numel())
+        w_t = None if weights is None else _check_weights(weights, self.nnz)
+        if w_t is not None and device is None:
+            raise ValueError("weights: a host-only plan (device=None) takes no weights")
         rp_h = rp_t.cpu().contiguous()
         self._rowptr_host = rp_h.numpy()
         if validate:
@@ -121,6 +143,17 @@ class SpmmPlan:
         # plan of the partner's exact transpose when the (user, item) pair of an interval is not a
         # transposed pair (duplicated stored entries, graph.interval_pair); None = the pair is exact
         self.partner_adjoint: SpmmPlan | None = None
+        self.weights = None
+        if w_t is not None:
+            self.weights = w_t.to(device).contiguous()
+            if self.weights.numel() == 0:  # a valid pointer: the plan counts as weighted
+                self.weights = torch.zeros(1, dtype=torch.float32, device=device)
+            check(lib.sagnn_spmm_plan_set_weights(self._h, self.weights.data_ptr()))
+            check(lib.sagnn_spmm_plan_get_info(self._h, ctypes.byref(info)))
+
+    @property
+    def weighted(self) -> bool:
+        return self.weights is not None
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -382,6 +415,9 @@ class SpmmBatch:
         if len(plans_user) != len(plans_item) or not plans_user:
             raise ValueError("one user-side and one item-side plan per interval")
         self.plans_user, self.plans_item = list(plans_user), list(plans_item)
+        self.weighted = self.plans_user[0].weighted
+        if any(p.weighted != self.weighted for p in self.plans_user + self.plans_item):
+            raise ValueError("SpmmBatch: some plans carry edge weights and others do not; give all 2 T plans weights or none")
         self.T, self.U, self.I = len(plans_user), plans_user[0].n_rows, plans_item[0].n_rows
         self.device = plans_user[0].device
         self._lib = _lib.load()

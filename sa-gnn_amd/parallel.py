@@ -35,6 +35,7 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
+from .Params import args
 
 
 # bench.py --dist-single sets this: the one-rank shortcuts below are skipped and every collective is issued through a
@@ -52,6 +53,9 @@ class IntervalSharding:
     def __init__(self, n_intervals: int, world: int, rank: int):
         if not (0 <= rank < world):
             raise ValueError(f"rank {rank} outside world {world}")
+        if getattr(args, "adjNorm", "none") != "none":
+            # the runners build row slices of unweighted plans (csr_row_slice): they would run unnormalised
+            raise ValueError(f"--adjNorm {args.adjNorm} is not supported by the interval-parallel path")
         self.T, self.world, self.rank = int(n_intervals), int(world), int(rank)
         self.rounds = -(-self.T // self.world)            # all-to-all calls every rank takes part in
 
