@@ -76,7 +76,9 @@ size_t sagnn_last_error(char* buf, size_t cap);
  * issues then takes one slot until they run out. sagnn_profile_read synchronises on the
  * recorded events, returns up to `cap` records in issue order and clears the log.
  * kind: 0 = SpMM row/chunk kernel (units_a = nnz, units_b = n_rows), 1 = SpMM fix-up,
- *       2 = LSTM, 3 = layer-norm, 4 = MHSA+mean (units_a = n, units_b = t).
+ *       2 = LSTM, 3 = layer-norm, 4 = MHSA+mean (units_a = n, units_b = t),
+ *       5 = an entry of the sequence attention (seq_attn.hip: gather, attention, pool and their
+ *       backwards; units_a = n_slots, units_b = pos_length).
  * -------------------------------------------------------------------------------- */
 int sagnn_profile_enable(int capacity);
 int sagnn_profile_read(float* ms, int32_t* kind, int64_t* units_a, int64_t* units_b, int cap,
@@ -749,6 +751,63 @@ int sagnn_rows_gather_f32(const float* x, int64_t ld_n, int64_t ld_t, int64_t n_
                           int64_t cap, const int32_t* count, float* out, void* stream);
 int sagnn_rows_scatter_f32(const float* src, const int32_t* rows, int64_t cap, const int32_t* count, int t, int d,
                            float* dst, int64_t ld_n, int64_t ld_t, int64_t n_rows, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Self-attention over the user's item sequence (seq_attn.hip; --seqAtt full, not in the reference's graph: the
+ * reference multiplies the mask into the tokens before its attention layers, model.py:161-162, so they run on
+ * length-1 sequences and the attn_mask of Utils/attention.py:35-45 is never passed).
+ * Layout: a padded slab [n_slots * P, d], P = pos_length; token j of slot b is row b * P + j, j < n_b =
+ *   clamp(seg_len[b], 0, P) (seg_len int32 [n_slots] on the device). Padding rule: rows j >= n_b hold finite values in
+ *   every activation and exact zeros in every gradient these entries write, so the row-wise entries
+ *   (sagnn_layernorm_td_f32 with t = 1, sagnn_dense_nn_f32, sagnn_dense_tn_f32, sagnn_leaky_add_f32) run over all
+ *   n_slots * P rows and dW = y^T dQKV stays correct. sagnn_attn_bwd_tail_f32 is not among them: a workgroup of it whose
+ *   first chunk of 32 gradient rows is all zero, which is what such padding produces, returns NaN bias gradients.
+ * Tokens: slot b's token j is item seq_items[seg_begin[b] + j] (seg_begin int64 [n_slots], seq_items int32 [n_flat])
+ *   at position seq_pos[seg_begin[b] + j], or, with seq_pos NULL, right-aligned at P - n_b + j. An explicit seq_pos
+ *   ascends strictly within a slot (a mask's positions do). Entries outside [0, n_flat), items outside [0, n_items)
+ *   and positions outside [0, P) read as zero rows and receive no gradient.
+ * sagnn_seq_gather_f32: seq_slab[b * P + j] = fi[item], pos_slab[b * P + j] = pos_embed[position]; zeros in the padding.
+ * sagnn_seq_gather_bwd_f32: d_fi[item] += g_seq[b * P + j] (ACCUMULATES; float atomics on whole rows, an item twice
+ *   in a sequence counts twice; the last bits may differ from run to run) and d_pos[p] = the sum over slots in
+ *   ascending b of the g_pos row of the token at position p (WRITTEN; deterministic).
+ * sagnn_seq_attn_f32: qkv [n_slots * P, 3d] dense (q | k | v per row, head h in columns h * d_k .. of each third,
+ *   d_k = d / heads) -> ctx [n_slots * P, d] dense: over slot b's n_b tokens only,
+ *   e[j, s] = exp(<q_j, k_s> / sqrt(d_k)) with no max subtraction, a = e / (sum_s e + 1e-8), ctx_j = sum_s a[j, s] v_s
+ *   (s ascending). Padded rows of ctx are zero. The quotient is evaluated with numerator and denominator scaled by
+ *   exp(-max_s score) per row, which leaves it what it is and keeps scores beyond fp32's exp range (88) from
+ *   overflowing into inf / inf (forward and backward alike); results are finite for any finite q|k|v.
+ * sagnn_seq_attn_bwd_f32: (qkv, g_ctx [n_slots * P, d]) -> dqkv [n_slots * P, 3d], every row WRITTEN, padded rows zero.
+ *   e is recomputed from qkv (nothing else is saved by the forward); no atomics, bit-identical between runs. Padded
+ *   rows of g_ctx are not read.
+ * sagnn_seq_pool_f32: out[b] = sum_{j < n_b} x[b * P + j] (j ascending from 0.0f; an empty slot gives a zero row).
+ * sagnn_seq_pool_bwd_f32: dx[b * P + j] = g[b] for j < n_b, zeros in the padding (every row WRITTEN).
+ * sagnn_seq_attn_supported(d, heads, pos_length): SAGNN_OK when the two attention entries take the shape,
+ *   SAGNN_ERR_DIM otherwise (the reason in sagnn_last_error): d a multiple of 4, d % heads == 0, d / heads in
+ *   {2, 4, 8}, 1 <= pos_length <= 256 (one workgroup per (slot, head) with a thread per token; K, V and, backward, q
+ *   and g of the head in LDS). Never touches the device.
+ * fp32 VALU under every engine (sagnn_set_engine does not change these kernels). Profile kind 5.
+ * Limits: gather / pool: d a multiple of 4 in [4, 256], 1 <= pos_length <= 256 (SAGNN_ERR_DIM otherwise); feature
+ *   pointers 16-byte aligned, strides multiples of 4 and >= d; n_items > 0; counts >= 0 (n_slots = 0 returns SAGNN_OK
+ *   at once, except that sagnn_seq_gather_bwd_f32 still writes its zero d_pos). Every argument is checked before any device work. One launch each (two for sagnn_seq_gather_bwd_f32)
+ *   on `stream`, no allocation, no synchronisation (capturable).
+ * -------------------------------------------------------------------------------- */
+int sagnn_seq_attn_supported(int d, int heads, int pos_length);
+int sagnn_seq_gather_f32(const float* fi, int64_t ldf, int64_t n_items, const float* pos_embed, int64_t ldp,
+                         int pos_length, const int32_t* seq_items, int64_t n_flat, const int32_t* seq_pos,
+                         const int64_t* seg_begin, const int32_t* seg_len, int64_t n_slots, int d, float* seq_slab,
+                         float* pos_slab, int64_t ldo, void* stream);
+int sagnn_seq_gather_bwd_f32(const float* g_seq, const float* g_pos, int64_t ldg, const int32_t* seq_items,
+                             int64_t n_flat, const int32_t* seq_pos, const int64_t* seg_begin, const int32_t* seg_len,
+                             int64_t n_slots, int pos_length, int d, float* d_fi, int64_t ld_dfi, int64_t n_items,
+                             float* d_pos, int64_t ld_dpos, void* stream);
+int sagnn_seq_attn_f32(const float* qkv, const int32_t* seg_len, int64_t n_slots, int pos_length, int d, int heads,
+                       float* ctx, void* stream);
+int sagnn_seq_attn_bwd_f32(const float* qkv, const float* g_ctx, const int32_t* seg_len, int64_t n_slots,
+                           int pos_length, int d, int heads, float* dqkv, void* stream);
+int sagnn_seq_pool_f32(const float* x, int64_t ldx, const int32_t* seg_len, int64_t n_slots, int pos_length, int d,
+                       float* out, int64_t ldo, void* stream);
+int sagnn_seq_pool_bwd_f32(const float* g, int64_t ldg, const int32_t* seg_len, int64_t n_slots, int pos_length, int d,
+                           float* dx, int64_t ldx, void* stream);
 
 #ifdef __cplusplus
 }

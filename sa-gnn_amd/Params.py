@@ -75,6 +75,13 @@ _FLAGS = [
                              "training and inference). Not in the reference's graph: transToLsts(norm=True) computes "
                              "these values (DataHandler.py:53-59) but they are cast to int32 and never read",
      ("none", "sym")),
+    ("seqAtt", str, "sum", "what the head's attention layers see of the user's item sequence: sum (the masked sum "
+                           "collapses the sequence into one token, as the reference's graph computes) or full (every "
+                           "item of the sequence is a token and the layers attend over the real items, padding masked; "
+                           "same variables; needs latdim / num_attention_heads in {2, 4, 8} and pos_length <= 256). Not "
+                           "in the reference's graph: it multiplies the mask in before the attention layers "
+                           "(model.py:161-162) and never passes attn_mask (Utils/attention.py:35-45)",
+     ("sum", "full")),
 ]
 
 

@@ -178,6 +178,15 @@ SIGNATURES = {
                                       c_void_p, c_void_p]),
     "sagnn_rows_scatter_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_void_p, c_int64, c_int64,
                                        c_int64, c_void_p]),
+    "sagnn_seq_attn_supported": (c_int, [c_int, c_int, c_int]),
+    "sagnn_seq_gather_f32": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p,
+                                     c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
+    "sagnn_seq_gather_bwd_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                         c_int64, c_int, c_int, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_void_p]),
+    "sagnn_seq_attn_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "sagnn_seq_attn_bwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "sagnn_seq_pool_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p]),
+    "sagnn_seq_pool_bwd_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p]),
 }
 
 

@@ -601,3 +601,94 @@ class HingeFn(torch.autograd.Function):
         if ctx.weighted:
             return dpos, dneg, saved[2] * g, saved[3] * g, None, None, None
         return dpos, dneg, None, None, None, None, None
+
+
+# ----------------------------------------------------------------------------------------------
+# Self-attention over the item sequence (--seqAtt full; seq_attn.hip). Activations
+# are padded slabs [n_slots * P, d]; seg_len (int32 [n_slots], on the device) holds the lengths.
+# ----------------------------------------------------------------------------------------------
+
+
+class SeqGatherFn(torch.autograd.Function):
+    """(fi, posEmbed) -> (item token slab, position token slab), both [n_slots * P, d] with zeros in the padding
+    (sagnn_seq_gather_f32). Slot b's token j is item seq_items[seg_begin[b] + j] at position seq_pos[seg_begin[b] + j],
+    or right-aligned (P - n_b + j) with seq_pos None."""
+
+    @staticmethod
+    def forward(ctx, fi, pos_embed, seq_items, seq_pos, seg_begin, seg_len):
+        ctx.tokens = (seq_items, seq_pos, seg_begin, seg_len)
+        ctx.shape = (int(fi.shape[0]), int(pos_embed.shape[0]))
+        return ops.seq_gather(fi.detach(), pos_embed.detach(), seq_items, seq_pos, seg_begin, seg_len)
+
+    @staticmethod
+    def backward(ctx, g_seq, g_pos):
+        n_items, P = ctx.shape
+        ref = g_seq if g_seq is not None else g_pos
+        g_seq = torch.zeros_like(ref) if g_seq is None else g_seq.contiguous()
+        g_pos = torch.zeros_like(ref) if g_pos is None else g_pos.contiguous()
+        d_fi, d_pos = ops.seq_gather_bwd(g_seq, g_pos, *ctx.tokens, n_items, P)
+        return d_fi, d_pos, None, None, None, None
+
+
+class SeqAttnFn(torch.autograd.Function):
+    """One sequence-attention layer on a slab: x [n_slots * P, d] -> leaky(ctx) + x with y = LN(x) per token,
+    q|k|v = y [Wq|Wk|Wv] + b and ctx the ragged attention over each slot's real tokens (sagnn_seq_attn_f32).
+    Saved for the backward: x and q|k|v. The backward recomputes ctx (for the slope of leaky) and y, then
+    sagnn_seq_attn_bwd_f32 -> dW, db (dense_tn) and dy (dense_nn) -> layer-norm backward. Padded rows of the incoming gradient must be zero (SeqPoolFn's and this class's are); the returned
+    gradient's are."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, Wq, bq, Wk, bk, Wv, bv, seg_len, P, heads, leaky):
+        x = x.detach().contiguous()
+        R, d = x.shape
+        y = ops.layernorm_td(x.view(R, 1, d), gamma.detach(), beta.detach()).view(R, d)
+        Wqkv = torch.cat([Wq, Wk, Wv], dim=1).detach().contiguous()
+        bqkv = torch.cat([bq, bk, bv]).detach().contiguous()
+        qkv = ops.dense_nn(y, Wqkv, bqkv)
+        att = ops.seq_attn(qkv, seg_len, P, heads)
+        ctx.save_for_backward(x, qkv, gamma, beta, Wqkv, seg_len)
+        ctx.cfg = (int(P), int(heads), float(leaky))
+        return ops.leaky_add(att, x, leaky)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, qkv, gamma, beta, Wqkv, seg_len = ctx.saved_tensors
+        P, heads, leaky = ctx.cfg
+        lib = ops._lib.load()
+        R, d = x.shape
+        dev, st = x.device, ops._stream()
+        g = g.contiguous()
+        att = ops.seq_attn(qkv, seg_len, P, heads)
+        g_att = torch.empty_like(att)
+        ops.check(lib.sagnn_leaky_f32(att.data_ptr(), g.data_ptr(), g_att.data_ptr(), leaky, att.numel(), 1, st))
+        dqkv = ops.seq_attn_bwd(qkv, g_att, seg_len, P, heads)
+        y = ops.layernorm_td(x.view(R, 1, d), gamma.detach(), beta.detach()).view(R, d)     # not saved: recomputed
+        dWqkv = torch.zeros((d, 3 * d), dtype=torch.float32, device=dev)
+        dbqkv = torch.zeros(3 * d, dtype=torch.float32, device=dev)
+        # dW, db and dy as two products, not sagnn_attn_bwd_tail_f32: the fused tail scales its chunks of 32 rows against
+        # the gradient rows it has met, and a workgroup whose FIRST chunk holds only zero rows (a slab's padding: any
+        # slot shorter than P - 32) returns NaN bias gradients (measured on the Gowalla-shaped set, DESIGN.md §18)
+        ops.dense_tn(y, dqkv, dWqkv, dbqkv)
+        dy = ops.dense_nn(dqkv, Wqkv.t().contiguous(), None, out=y)
+        dgamma = torch.zeros(d, dtype=torch.float32, device=dev)
+        dbeta = torch.zeros(d, dtype=torch.float32, device=dev)
+        ops.check(lib.sagnn_layernorm_td_bwd_f32(x.data_ptr(), d, dy.data_ptr(), d, R, 1, d, ops._vec("gamma", gamma.detach(), d),
+                                                 1e-12, dy.data_ptr(), d, dgamma.data_ptr(), dbeta.data_ptr(), st))
+        dx = ops.leaky_add(dy, g, 1.0)                                     # slope 1: dy + g, the residual's share
+        return (dx, dgamma, dbeta) + _split_qkv_grads(dWqkv, dbqkv, d) + (None, None, None, None)
+
+
+class SeqPoolFn(torch.autograd.Function):
+    """x [n_slots * P, d] -> [n_slots, d]: the sum over each slot's real tokens (sagnn_seq_pool_f32); the backward
+    broadcasts, with zeros into the padding."""
+
+    @staticmethod
+    def forward(ctx, x, seg_len, P):
+        ctx.save_for_backward(seg_len)
+        ctx.P = int(P)
+        return ops.seq_pool(x.detach().contiguous(), seg_len, P)
+
+    @staticmethod
+    def backward(ctx, g):
+        (seg_len,) = ctx.saved_tensors
+        return ops.seq_pool_bwd(g.contiguous(), seg_len, ctx.P), None, None

@@ -23,6 +23,9 @@ from .Utils.attention import MultiHeadSelfAttention
 from .graph import NORMS, interval_pair
 
 
+SEQ_ATT = ("sum", "full")      # --seqAtt: the reference's collapsed head, or attention over every sequence item
+
+
 def random_fusion_params(d: int, device, seed: int = 0) -> dict:
     """Random-init fusion parameters with the shapes TF creates (BasicLSTMCell kernel [2d, 4d] and
     bias [4d]; layer_norm gamma/beta [d]; three dense kernels [d, d] with bias [d]). Kernels are
@@ -165,7 +168,8 @@ class DeviceEvaluator:
       - target int32 [n]: tstInt (args.test) or the sequence's last item (validation);
       - chunks: per args.batch users (testEpoch's batches, same order) the start row, the user count and the head's
         masked-sum CSRs over args.batch slots (rowptr, item ids, positions), exactly what _masked_sum_plans uploads
-        for that batch; on the device they become static SpmmPlans (plans);
+        for that batch; on the device they become static SpmmPlans (plans) or, under --seqAtt full, the token arrays
+        of the sequence attention (tokens, Recommender._csr_tokens);
       - the full-ranking exclusion CSR (excl_rowptr int64 / excl_items int32: each user's sequence items as the head
         reads them, sorted), checked once and uploaded once as an ops.ExclusionCSR (excl).
     Raises ValueError for a test_dict row shorter than testSize - 1 (as the host does), for candidate or target ids
@@ -217,9 +221,13 @@ class DeviceEvaluator:
         self.device = device
         self.uids_d, self.users_d = as_dev(self.users.astype(np.int32)), as_dev(self.users)
         self.cand_d, self.target_d = as_dev(self.cand), as_dev(self.target)
-        self.plans = [(ops.SpmmPlan(rp, it, self.batch, self.n_items, device=device, validate=False),
-                       ops.SpmmPlan(rp, pos, self.batch, P, device=device, validate=False))
-                      for _, _, rp, it, pos in self.chunks]
+        self.plans = self.tokens = None
+        if args.seqAtt == "full":
+            self.tokens = [Recommender._csr_tokens(rp, it, pos, device) for _, _, rp, it, pos in self.chunks]
+        else:
+            self.plans = [(ops.SpmmPlan(rp, it, self.batch, self.n_items, device=device, validate=False),
+                           ops.SpmmPlan(rp, pos, self.batch, P, device=device, validate=False))
+                          for _, _, rp, it, pos in self.chunks]
         self.excl = ops.ExclusionCSR(self.excl_rowptr, self.excl_items, self.n, self.n_items, device)
 
 
@@ -431,7 +439,39 @@ class Recommender:
 
     def _head_att(self, sequence, mask):
         """The head's sequence representation att [args.batch, d] (model.py:158-168) on the cached final vectors."""
+        if args.seqAtt == "full":
+            return self._head_att_tokens(*self._csr_tokens(*self._masked_sum_csr(sequence, mask), self.device))
         return self._head_att_plans(*self._masked_sum_plans(sequence, mask))
+
+    @staticmethod
+    def _csr_tokens(rowptr, items, pos, device):
+        """_masked_sum_csr's arrays as the token description of the sequence attention, on the device: (item ids
+        int32, positions int32, seg_begin int64 [B] = rowptr[:-1], seg_len int32 [B] = diff(rowptr))."""
+        as_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+        return (as_dev(items), as_dev(pos), as_dev(rowptr[:-1].astype(np.int64)), as_dev(np.diff(rowptr).astype(np.int32)))
+
+    def _seq_att_full(self, fi, seq_items, seq_pos, seg_begin, seg_len):
+        """--seqAtt full (not in the reference's graph): att [args.batch, d] with every item of a slot's
+        sequence a token and the att_layer attention layers run over the slot's real tokens, as the attn_mask of
+        Utils/attention.py:35-45 would have it. Token j of slot b is item seq_items[seg_begin[b] + j] at position
+        seq_pos[...] (None: right-aligned); activations are padded slabs [args.batch * pos_length, d]. The one place
+        that builds it: differentiable in fi and the head's parameters (train_loss), and called without a graph by the
+        inference paths. Same variables as the collapsed head."""
+        heads, leaky, P = args.num_attention_heads, NNs.leaky, args.pos_length
+        seq, pos = ag.SeqGatherFn.apply(fi, self.posEmbed, seq_items, seq_pos, seg_begin, seg_len)
+        R, d = seq.shape
+        ln = lambda x, gb: ag.LayerNormFn.apply(x.view(R, 1, d), gb[0], gb[1]).view(R, d)
+        x = ag.LeakyAddFn.apply(ln(seq, self.head_ln[0]), ln(pos, self.head_ln[1]), 1.0)
+        for i, mh in enumerate(self.multihead_self_attention_sequence):
+            w = mh.weights()
+            x = ag.SeqAttnFn.apply(x, *self.head_ln[2 + i], w["Wq"], w["bq"], w["Wk"], w["bk"], w["Wv"], w["bv"], seg_len, P,
+                                   heads, leaky)
+        return ag.SeqPoolFn.apply(x, seg_len, P)
+
+    def _head_att_tokens(self, seq_items, seq_pos, seg_begin, seg_len):
+        """_head_att under --seqAtt full, on the batch's token arrays (_csr_tokens): _seq_att_full without a graph."""
+        with torch.no_grad():
+            return self._seq_att_full(self.final_item_vector, seq_items, seq_pos, seg_begin, seg_len)
 
     def _head_att_plans(self, pi, pp):
         """_head_att on the masked-sum plans of the batch (item ids pi, positions pp)."""
@@ -626,7 +666,7 @@ class Recommender:
         """The device evaluator's tables for the current handler and flags, built once."""
         h = self.handler
         key = (h.sequence, h.test_dict, h.tstInt, h.tstUsrs, bool(args.test), args.testSize, args.pos_length, args.batch,
-               args.item, str(self.device))
+               args.item, str(self.device), args.seqAtt)
         return self._cached("_dev_eval", key, lambda: DeviceEvaluator(self, self.device))
 
     def _test_epoch_device(self, full: bool):
@@ -637,8 +677,8 @@ class Recommender:
         self.forward()
         fu, fi, leaky = self.final_user_vector, self.final_item_vector, NNs.leaky
         ranks = []
-        for (st, nb, _, _, _), (pi, pp) in zip(E.chunks, E.plans):
-            att = self._head_att_plans(pi, pp)[:nb]
+        for c, (st, nb, _, _, _) in enumerate(E.chunks):
+            att = (self._head_att_tokens(*E.tokens[c]) if E.tokens is not None else self._head_att_plans(*E.plans[c]))[:nb]
             if full:
                 q = ops.leaky_add(att, fu.index_select(0, E.users_d[st:st + nb]), leaky)
                 _, _, r = ops.score_topk(q, fi, 1, excl=E.excl.rows(st, st + nb), target=E.target_d[st:st + nb])
@@ -711,22 +751,14 @@ class Recommender:
                 finals.append(ag.interval_fusion(x, p, heads, drop_scale=drop))
         fu, fi = finals
         # ---- head (model.py:156-173)
-        if "seq_seg" in batch:                                            # device-sampled: segments, no CSRs
-            seg_begin, seg_len = batch["seq_seg"]
-            seq_tok, pos_tok = ag.SeqSumFn.apply(fi, self.posEmbed, self._device_sampler().seq_items, seg_begin, seg_len)
+        if args.seqAtt == "full":                                         # every sequence item a token (_seq_att_full)
+            if "seq_seg" in batch:
+                tokens = (self._device_sampler().seq_items, None) + tuple(batch["seq_seg"])
+            else:
+                tokens = self._csr_tokens(*self._masked_sum_csr(batch["sequence"], batch["mask"]), self.device)
+            att = self._seq_att_full(fi, *tokens)
         else:
-            pi, pp = self._masked_sum_plans(batch["sequence"], batch["mask"])
-            pit, ppt = self._masked_sum_plans_t(batch["sequence"], batch["mask"])
-            seq_tok = ag.SpmmFn.apply(fi, pi, pit)
-            pos_tok = ag.SpmmFn.apply(self.posEmbed, pp, ppt)
-        B = seq_tok.shape[0]
-        ln = lambda x, gb: ag.LayerNormFn.apply(x.view(B, 1, d), gb[0], gb[1]).view(B, d)
-        att = ag.LeakyAddFn.apply(ln(seq_tok, self.head_ln[0]), ln(pos_tok, self.head_ln[1]), 1.0)
-        for i, mh in enumerate(self.multihead_self_attention_sequence):
-            w = mh.weights()
-            a1 = ag.MhsaMeanFn.apply(ln(att, self.head_ln[2 + i]).view(B, 1, d), w["Wq"], w["bq"], w["Wk"], w["bk"],
-                                     w["Wv"], w["bv"], heads)
-            att = ag.LeakyAddFn.apply(a1, att, leaky)
+            att = self._head_att_sum_train(fi, batch)
         preds = ag.PairScoreFn.apply(fu, fi, att, self._i32(batch["uids"]), self._i32(batch["iids"]),
                                      self._i32(batch["uLocs_seq"]), leaky)
         n = preds.shape[0] // 2
@@ -743,6 +775,28 @@ class Recommender:
             p1 = ag.ProdLeakySumFn.apply(uv[k], iv[k], su, si, leaky)
             ssl = ssl + ag.HingeFn.apply(p1[:ns], p1[ns:], w[:ns], w[ns:], s_final[:ns], s_final[ns:], 1.0)
         return pre_loss, ssl
+
+    def _head_att_sum_train(self, fi, batch):
+        """The reference's collapsed head (--seqAtt sum) as autograd nodes: the masked sums make ONE token per slot and
+        the attention layers run on length-1 sequences (model.py:158-168)."""
+        d, heads, leaky = args.latdim, args.num_attention_heads, NNs.leaky
+        if "seq_seg" in batch:                                            # device-sampled: segments, no CSRs
+            seg_begin, seg_len = batch["seq_seg"]
+            seq_tok, pos_tok = ag.SeqSumFn.apply(fi, self.posEmbed, self._device_sampler().seq_items, seg_begin, seg_len)
+        else:
+            pi, pp = self._masked_sum_plans(batch["sequence"], batch["mask"])
+            pit, ppt = self._masked_sum_plans_t(batch["sequence"], batch["mask"])
+            seq_tok = ag.SpmmFn.apply(fi, pi, pit)
+            pos_tok = ag.SpmmFn.apply(self.posEmbed, pp, ppt)
+        B = seq_tok.shape[0]
+        ln = lambda x, gb: ag.LayerNormFn.apply(x.view(B, 1, d), gb[0], gb[1]).view(B, d)
+        att = ag.LeakyAddFn.apply(ln(seq_tok, self.head_ln[0]), ln(pos_tok, self.head_ln[1]), 1.0)
+        for i, mh in enumerate(self.multihead_self_attention_sequence):
+            w = mh.weights()
+            a1 = ag.MhsaMeanFn.apply(ln(att, self.head_ln[2 + i]).view(B, 1, d), w["Wq"], w["bq"], w["Wk"], w["bk"],
+                                     w["Wv"], w["bv"], heads)
+            att = ag.LeakyAddFn.apply(a1, att, leaky)
+        return att
 
     def _touched_rows(self, batch) -> dict:
         """--fusion_rows batch: the user rows (uids, suids[k]) and item rows (iids, siids[k], the head's sequence items)
@@ -967,7 +1021,8 @@ class Recommender:
         os.makedirs(os.path.join(directory, "Models"), exist_ok=True)
         with open(os.path.join(directory, "History", args.save_path + ".his"), "wb") as fs:
             pickle.dump(self.metrics, fs)
-        state = {"params": {k: v.detach().cpu() for k, v in NNs.params.items()}, "adjNorm": args.adjNorm}
+        state = {"params": {k: v.detach().cpu() for k, v in NNs.params.items()}, "adjNorm": args.adjNorm,
+                 "seqAtt": args.seqAtt}
         if getattr(self, "optimizer", None) is not None:
             state["optimizer"] = self.optimizer.state_dict()
         torch.save(state, os.path.join(directory, "Models", args.save_path))
@@ -982,6 +1037,10 @@ class Recommender:
         if stored_norm != args.adjNorm:
             raise ValueError(f"checkpoint was trained with --adjNorm {stored_norm}, this run has --adjNorm {args.adjNorm}: "
                              "the normalisation is part of the model")
+        stored_att = state.get("seqAtt", "sum")          # a checkpoint from before --seqAtt is a collapsed-head model
+        if stored_att != args.seqAtt:
+            raise ValueError(f"checkpoint was trained with --seqAtt {stored_att}, this run has --seqAtt {args.seqAtt}: "
+                             "the head's attention is part of the model")
         saved = state["params"]
         if set(saved) != set(NNs.params):
             raise KeyError(f"checkpoint variables differ from the model's: missing {sorted(set(NNs.params) - set(saved))[:4]}, "
@@ -1007,6 +1066,12 @@ class Recommender:
             raise ValueError(f"--edgeKeepRate {args.edgeKeepRate}: need a rate in (0, 1]")
         if args.adjNorm not in NORMS:
             raise ValueError(f"--adjNorm {args.adjNorm}: one of {NORMS}")
+        if args.seqAtt not in SEQ_ATT:
+            raise ValueError(f"--seqAtt {args.seqAtt}: one of {SEQ_ATT}")
+        if args.seqAtt == "full":          # refused before any forward: the attention kernels take these shapes only
+            why = ops.seq_attn_supported(args.latdim, args.num_attention_heads, args.pos_length)
+            if why is not None:
+                raise ValueError(f"--seqAtt full is not available for this configuration: {why}")
         NNs.reset(self.device)
         NNs.leaky = args.leaky
         self.actFunc = "leakyRelu"

@@ -1101,3 +1101,94 @@ def rows_scatter(src: torch.Tensor, rows: torch.Tensor, count: torch.Tensor, out
         src.data_ptr(), _idx_ptr("rows", rows, torch.int32), cap, _idx_ptr("count", count, torch.int32, 1), t, d,
         out.data_ptr(), ld_n, ld_t, N, _stream()))
     return out
+
+
+# ---- self-attention over the item sequence (seq_attn.hip; --seqAtt full) ------------------------------------------
+def seq_attn_supported(d: int, heads: int, pos_length: int) -> str | None:
+    """None when sagnn_seq_attn_f32 / _bwd_f32 take the shape (sagnn_seq_attn_supported), else the library's reason."""
+    return None if _lib.load().sagnn_seq_attn_supported(int(d), int(heads), int(pos_length)) == 0 else _lib.last_error()
+
+
+def _seq_tokens(seq_items, seq_pos, seg_begin, seg_len):
+    """The checked pointers of a slab's token description: (items, n_flat, positions or None, seg_begin, seg_len, n_slots)."""
+    n = int(seg_len.numel())
+    n_flat = int(seq_items.numel())
+    return (_idx_ptr("seq_items", seq_items, torch.int32), n_flat,
+            None if seq_pos is None else _idx_ptr("seq_pos", seq_pos, torch.int32, n_flat),
+            _idx_ptr("seg_begin", seg_begin, torch.int64, n), _idx_ptr("seg_len", seg_len, torch.int32), n)
+
+
+def seq_gather(fi: torch.Tensor, pos_embed: torch.Tensor, seq_items: torch.Tensor, seq_pos: torch.Tensor | None,
+               seg_begin: torch.Tensor, seg_len: torch.Tensor):
+    """The token slabs of the sequence attention (sagnn_seq_gather_f32): two [n_slots * P, d] tensors, P =
+    len(pos_embed); row b * P + j holds fi[item] / pos_embed[position] of slot b's token j, zeros in the padding.
+    seq_pos None: right-aligned positions P - n_b + j."""
+    d, P = int(fi.shape[1]), int(pos_embed.shape[0])
+    items, n_flat, pos, beg, ln, n = _seq_tokens(seq_items, seq_pos, seg_begin, seg_len)
+    seq_slab = torch.empty((n * P, d), dtype=torch.float32, device=fi.device)
+    pos_slab = torch.empty((n * P, d), dtype=torch.float32, device=fi.device)
+    check(_lib.load().sagnn_seq_gather_f32(
+        fi.data_ptr(), _f32_rows("fi", fi, d), int(fi.shape[0]), pos_embed.data_ptr(), _f32_rows("pos_embed", pos_embed, d),
+        P, items, n_flat, pos, beg, ln, n, d, seq_slab.data_ptr(), pos_slab.data_ptr(), d, _stream()))
+    return seq_slab, pos_slab
+
+
+def seq_gather_bwd(g_seq: torch.Tensor, g_pos: torch.Tensor, seq_items: torch.Tensor, seq_pos: torch.Tensor | None,
+                   seg_begin: torch.Tensor, seg_len: torch.Tensor, n_items: int, pos_length: int):
+    """Gradients of seq_gather (sagnn_seq_gather_bwd_f32): d_fi [n_items, d] (a scatter with float atomics) and d_pos
+    [pos_length, d] (deterministic). g_seq / g_pos: [n_slots * pos_length, d] with one row stride."""
+    items, n_flat, pos, beg, ln, n = _seq_tokens(seq_items, seq_pos, seg_begin, seg_len)
+    P, d = int(pos_length), int(g_seq.shape[1])
+    ld = _f32_rows("g_seq", g_seq, d, n * P)
+    if _f32_rows("g_pos", g_pos, d, n * P) != ld:
+        raise ValueError("g_seq and g_pos need the same row stride")
+    d_fi = torch.zeros((int(n_items), d), dtype=torch.float32, device=g_seq.device)
+    d_pos = torch.empty((P, d), dtype=torch.float32, device=g_seq.device)
+    check(_lib.load().sagnn_seq_gather_bwd_f32(g_seq.data_ptr(), g_pos.data_ptr(), ld, items, n_flat, pos, beg, ln, n, P, d,
+                                               d_fi.data_ptr(), d, int(n_items), d_pos.data_ptr(), d, _stream()))
+    return d_fi, d_pos
+
+
+def _slab_rows(name: str, t: torch.Tensor, cols: int, rows: int) -> int:
+    if _f32_rows(name, t, cols, rows) != cols:
+        raise ValueError(f"{name}: expected a contiguous [{rows}, {cols}] tensor")
+    return t.data_ptr()
+
+
+def seq_attn(qkv: torch.Tensor, seg_len: torch.Tensor, pos_length: int, heads: int):
+    """The ragged attention over each slot's real tokens (sagnn_seq_attn_f32): qkv [n_slots * P, 3d] contiguous ->
+    ctx [n_slots * P, d], zero rows in the padding."""
+    n, P, d = int(seg_len.numel()), int(pos_length), int(qkv.shape[1]) // 3
+    ctx = torch.empty((n * P, d), dtype=torch.float32, device=qkv.device)
+    check(_lib.load().sagnn_seq_attn_f32(_slab_rows("qkv", qkv, 3 * d, n * P), _idx_ptr("seg_len", seg_len, torch.int32), n, P,
+                                         d, int(heads), ctx.data_ptr(), _stream()))
+    return ctx
+
+
+def seq_attn_bwd(qkv: torch.Tensor, g_ctx: torch.Tensor, seg_len: torch.Tensor, pos_length: int, heads: int):
+    """(qkv, g_ctx [n_slots * P, d]) -> dqkv [n_slots * P, 3d] (sagnn_seq_attn_bwd_f32): zero rows in the padding,
+    bit-identical between runs."""
+    n, P, d = int(seg_len.numel()), int(pos_length), int(qkv.shape[1]) // 3
+    dqkv = torch.empty((n * P, 3 * d), dtype=torch.float32, device=qkv.device)
+    check(_lib.load().sagnn_seq_attn_bwd_f32(_slab_rows("qkv", qkv, 3 * d, n * P), _slab_rows("g_ctx", g_ctx, d, n * P),
+                                             _idx_ptr("seg_len", seg_len, torch.int32), n, P, d, int(heads), dqkv.data_ptr(),
+                                             _stream()))
+    return dqkv
+
+
+def seq_pool(x: torch.Tensor, seg_len: torch.Tensor, pos_length: int):
+    """out[b] = the sum of slot b's real token rows of x [n_slots * P, d] (sagnn_seq_pool_f32) -> [n_slots, d]."""
+    n, P, d = int(seg_len.numel()), int(pos_length), int(x.shape[1])
+    out = torch.empty((n, d), dtype=torch.float32, device=x.device)
+    check(_lib.load().sagnn_seq_pool_f32(x.data_ptr(), _f32_rows("x", x, d, n * P), _idx_ptr("seg_len", seg_len, torch.int32),
+                                         n, P, d, out.data_ptr(), d, _stream()))
+    return out
+
+
+def seq_pool_bwd(g: torch.Tensor, seg_len: torch.Tensor, pos_length: int):
+    """dx[b * P + j] = g[b] for slot b's real tokens, zeros in the padding (sagnn_seq_pool_bwd_f32) -> [n_slots * P, d]."""
+    n, P, d = int(seg_len.numel()), int(pos_length), int(g.shape[1])
+    dx = torch.empty((n * P, d), dtype=torch.float32, device=g.device)
+    check(_lib.load().sagnn_seq_pool_bwd_f32(g.data_ptr(), _f32_rows("g", g, d, n), _idx_ptr("seg_len", seg_len, torch.int32),
+                                             n, P, d, dx.data_ptr(), d, _stream()))
+    return dx

@@ -2,7 +2,9 @@
 """Times Recommender.testEpoch / testEpochFull under both evaluators (--evaluator host / device) on the Gowalla-shaped
 synthetic dataset and hyper-parameters of tools/time_train_epoch.py (U = 48,653, I = 52,619, 3 intervals x 600 k edges,
 d = 64, batch 512, 10,000 test users, testSize 1000). The evaluators run in the same process, alternated epoch by
-epoch after warm-up; every device result is checked equal (==) to the host result of the same parameters."""
+epoch after warm-up; every device result is checked equal (==) to the host result of the same parameters. --seqAtt
+both times the head's two forms (the collapsed sum / attention over every sequence item) one after the other in the
+same process."""
 import argparse
 import sys
 import time
@@ -21,6 +23,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--epoch-only", action="store_true", help="one warm-up and one device test epoch (for a profiler)")
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--seqAtt", choices=("sum", "full", "both"), default="sum", help="the head's form(s) to time")
     opt = ap.parse_args()
     Params.parse_args("--data gowalla --lr 2e-3 --reg 1e-2 --ssl_reg 1e-6 --epoch 150 --batch 512 --sslNum 40 --graphNum 3 "
                       "--gnn_layer 2 --att_layer 1 --testSize 1000 --ssldim 48 --keepRate 0.5".split(), namespace=args)
@@ -38,11 +41,21 @@ def main():
     rec.prepareModel()
     if opt.epoch_only:
         args.evaluator = "device"
+        args.seqAtt = "full" if opt.seqAtt == "full" else "sum"
         for _ in range(2):
             rec.testEpoch()
         torch.cuda.synchronize()
         print("two device test epochs done")
         return
+    for att in (("sum", "full") if opt.seqAtt == "both" else (opt.seqAtt,)):
+        args.seqAtt = att
+        if opt.seqAtt != "sum":
+            print(f"---- --seqAtt {att}")
+        time_evaluators(rec, h, opt)
+    args.seqAtt = "sum"
+
+
+def time_evaluators(rec, h, opt):
     names = ("host", "device")
     kinds = {"testEpoch": rec.testEpoch, "testEpochFull": rec.testEpochFull}
     # first calls: the host path builds its candidate / sequence caches on its first test epoch, the device path its

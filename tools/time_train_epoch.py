@@ -5,8 +5,11 @@ trnNum 10000 -> 20 steps per epoch, keepRate 0.5) and prints where a training st
 (sampling / forward + loss / backward / optimiser), wall clock with a device sync after each part. Both samplers
 (--sampler host / device) run in the same process, alternated epoch by epoch; --fusion_rows both alternates the two
 fusion modes as well (all rows / the rows the batch reads) and reports the touched rows per step and the f16 x 2
-kernels' fp32 re-evaluations per epoch of each mode."""
+kernels' fp32 re-evaluations per epoch of each mode. --seqAtt both alternates the head's two forms (the collapsed sum /
+attention over every sequence item) and reports the device time of the sequence-attention entries per step
+(sagnn_profile_read, kind 5)."""
 import argparse
+import ctypes
 import sys
 import time
 
@@ -28,6 +31,8 @@ def main():
                     help="fusion mode(s) to time; both alternates them in one process")
     ap.add_argument("--edge_keep", type=float, default=1.0,
                     help="--edgeKeepRate of the run: below 1 the training steps drop edges of the interval graphs")
+    ap.add_argument("--seqAtt", choices=("sum", "full", "both"), default="sum",
+                    help="the head's form(s) to time; both alternates them in one process")
     opt = ap.parse_args()
     Params.parse_args("--data gowalla --lr 2e-3 --reg 1e-2 --ssl_reg 1e-6 --epoch 150 --batch 512 --sslNum 40 --graphNum 3 "
                       "--gnn_layer 2 --att_layer 1 --testSize 1000 --ssldim 48 --keepRate 0.5".split(), namespace=args)
@@ -47,20 +52,42 @@ def main():
     if opt.epoch_only:
         args.sampler = "device"
         args.fusion_rows = "batch" if opt.fusion_rows == "batch" else "all"
+        args.seqAtt = "full" if opt.seqAtt == "full" else "sum"
         for _ in range(2):
             rec.trainEpoch()
         torch.cuda.synchronize()
-        print(f"two device-sampler epochs done (--fusion_rows {args.fusion_rows}, --edge_keep {args.edgeKeepRate})")
+        print(f"two device-sampler epochs done (--fusion_rows {args.fusion_rows}, --edge_keep {args.edgeKeepRate}, "
+              f"--seqAtt {args.seqAtt}); every parameter finite:",
+              all(bool(torch.isfinite(p).all()) for p in NNs.params.values()))
         return
     modes = ("all", "batch") if opt.fusion_rows == "both" else (opt.fusion_rows,)
-    configs = [(sampler, mode) for mode in modes for sampler in ("host", "device")]
-    label = lambda c: c[0] if len(modes) == 1 else f"{c[0]}, {c[1]} rows"   # noqa: E731
+    atts = ("sum", "full") if opt.seqAtt == "both" else (opt.seqAtt,)
+    configs = [(sampler, mode, att) for att in atts for mode in modes for sampler in ("host", "device")]
+    label = lambda c: ", ".join([c[0]] + ([f"{c[1]} rows"] if len(modes) > 1 else []) +   # noqa: E731
+                                ([f"seqAtt {c[2]}"] if atts != ("sum",) else []))
 
-    def use(c):
-        args.sampler, args.fusion_rows = c
+    initial = {k: p.detach().clone() for k, p in NNs.params.items()}
+    finite = {}
+
+    def use(c, fresh=False):
+        # fresh: the initial parameters and a new optimiser. Step times depend on the parameters (the f16 x 2 kernels'
+        # fp32 re-evaluations), and at gowalla.sh's learning rate this synthetic set's training goes non-finite after a
+        # few hundred steps, with or without --seqAtt full (non-finite epochs run at half the time): with several head
+        # forms every timed epoch is therefore the first epoch of its own training (profiles/seq_att_epoch.txt holds a
+        # parent-commit run that shows the default path's divergence). A run without --seqAtt both keeps training its
+        # parameters as before, so its lines, not a `both` run's sum lines, are what compares with an earlier commit.
+        args.sampler, args.fusion_rows, args.seqAtt = c
+        if fresh and len(atts) > 1:
+            with torch.no_grad():
+                for k, p in NNs.params.items():
+                    p.copy_(initial[k])
+            rec.optimizer = None
+
+    def note_finite(c):
+        finite[c] = finite.get(c, True) and all(bool(torch.isfinite(p).all()) for p in NNs.params.values())
 
     for c in configs:              # warm-up: kernels, workspaces, the device sampler's tables
-        use(c)
+        use(c, fresh=True)
         for _ in range(2):
             rec.trainEpoch()
     torch.cuda.synchronize()
@@ -68,9 +95,9 @@ def main():
     rounds = 3
     epoch = {c: [] for c in configs}
     redo = {c: [] for c in configs}
-    for _ in range(rounds):        # alternated, so every configuration sees the same machine state
+    for r in range(rounds):        # alternated, so every configuration sees the same machine state
         for c in configs:
-            use(c)
+            use(c, fresh=True)
             torch.cuda.synchronize()
             ops.range_redo_count(reset=True)
             t0 = time.perf_counter()
@@ -78,20 +105,23 @@ def main():
             torch.cuda.synchronize()
             epoch[c].append(time.perf_counter() - t0)
             redo[c].append(ops.range_redo_count())
+            note_finite(c)
     for c in configs:
         ep = float(np.median(epoch[c]))
         print(f"[{label(c)}] train epoch {ep * 1e3:.1f} ms = {steps} steps of {ep / steps * 1e3:.2f} ms "
               f"(median of {rounds}; all: {[round(1e3 * v, 1) for v in epoch[c]]}); "
-              f"range redo count per epoch {redo[c]}")
+              f"range redo count per epoch {redo[c]}; every parameter finite after each: {finite[c]}")
     # one step, by part
     parts = {c: {"sample": 0.0, "forward+loss": 0.0, "backward": 0.0, "optimiser": 0.0} for c in configs}
     touched = {c: [] for c in configs}
     for r in range(rounds):
         for c in configs:
-            use(c)
+            use(c, fresh=True)
             sf = np.random.permutation(args.user)[:args.trnNum]
             seed = int(np.random.randint(0, 2 ** 63, dtype=np.int64))
             part = parts[c]
+            if getattr(rec, "optimizer", None) is None:
+                rec.optimizer = rec._make_optimizer()
             for i in range(steps):
                 bat = sf[i * args.batch:(i + 1) * args.batch]
                 torch.cuda.synchronize(); t = time.perf_counter()
@@ -112,6 +142,7 @@ def main():
                 torch.cuda.synchronize(); part["backward"] += time.perf_counter() - t; t = time.perf_counter()
                 rec.optimizer.step({k: p.grad for k, p in params.items()})
                 torch.cuda.synchronize(); part["optimiser"] += time.perf_counter() - t
+            note_finite(c)
     for c in configs:
         print(f"[{label(c)}] per step (ms, synced between parts, mean of {rounds} epochs):",
               {k: round(v / (steps * rounds) * 1e3, 3) for k, v in parts[c].items()})
@@ -119,8 +150,24 @@ def main():
             tu, ti = np.mean(np.asarray(touched[c], dtype=np.float64), axis=0)
             print(f"[{label(c)}] touched rows per step (mean of {len(touched[c])}): users {tu:.1f} of {args.user} "
                   f"({100 * tu / args.user:.2f} %), items {ti:.1f} of {args.item} ({100 * ti / args.item:.2f} %)")
+    if "full" in atts:        # device time of the sequence-attention entries (profile kind 5), one device-sampler epoch
+        lib = ops._lib.load()
+        use(("device", modes[0], "full"), fresh=True)
+        cap = 4096 * steps
+        lib.sagnn_profile_enable(cap)
+        rec.trainEpoch()
+        ms, kind, n = np.zeros(cap, np.float32), np.zeros(cap, np.int32), ctypes.c_int(0)
+        ops.check(lib.sagnn_profile_read(ms.ctypes.data, kind.ctypes.data, None, None, cap, ctypes.byref(n)))
+        lib.sagnn_profile_enable(0)
+        sel = kind[:n.value] == 5
+        print(f"[device, seqAtt full] sequence-attention entries (gather, attention, pool and their backwards): "
+              f"{int(sel.sum()) / steps:.0f} calls and {float(ms[:n.value][sel].sum()) / steps:.3f} ms of device time per step; "
+              f"layer-norm entries (profile kind 3): {float(ms[:n.value][kind[:n.value] == 3].sum()) / steps:.3f} ms per step")
+        print("every parameter finite after that epoch:", all(bool(torch.isfinite(p).all()) for p in NNs.params.values()))
+    print("every parameter finite after every timed epoch above:", finite)
     args.fusion_rows = "all"
     args.sampler = "host"
+    args.seqAtt = "sum"
     t0 = time.perf_counter()
     res = rec.testEpoch()
     torch.cuda.synchronize()
