@@ -78,7 +78,8 @@ size_t sagnn_last_error(char* buf, size_t cap);
  * kind: 0 = SpMM row/chunk kernel (units_a = nnz, units_b = n_rows), 1 = SpMM fix-up,
  *       2 = LSTM, 3 = layer-norm, 4 = MHSA+mean (units_a = n, units_b = t),
  *       5 = an entry of the sequence attention (seq_attn.hip: gather, attention, pool and their
- *       backwards; units_a = n_slots, units_b = pos_length).
+ *       backwards; units_a = n_slots, units_b = pos_length),
+ *       6 = sagnn_softmax_loss_f32 or its backward (units_a = n_queries, units_b = n_items).
  * -------------------------------------------------------------------------------- */
 int sagnn_profile_enable(int capacity);
 int sagnn_profile_read(float* ms, int32_t* kind, int64_t* units_a, int64_t* units_b, int cap,
@@ -808,6 +809,45 @@ int sagnn_seq_pool_f32(const float* x, int64_t ldx, const int32_t* seg_len, int6
                        float* out, int64_t ldo, void* stream);
 int sagnn_seq_pool_bwd_f32(const float* g, int64_t ldg, const int32_t* seg_len, int64_t n_slots, int pos_length, int d,
                            float* dx, int64_t ldx, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Full-catalogue softmax cross-entropy (softmax_loss.hip; --predLoss softmax, not in the reference, which trains the
+ * head with a sampled hinge loss only: model.py:241-246).
+ *   z(b, i) = <Q[b], I[i]> * inv_temp, the product in fp32 on the exact-fp32 matrix cores (v_mfma_f32_16x16x4_f32): a
+ *   fixed fmaf chain over k, a function of the query row and the item row alone. sagnn_set_engine does NOT apply.
+ *   loss[0] = scale * sum over rows b with a target of ( lse[b] - z(b, target[b]) ),
+ *   lse[b]  = ln sum_{i eligible for b} exp(z(b, i)),  tscore[b] = <Q[b], I[target[b]]> (the product, before inv_temp).
+ * Eligible items: every item of [0, n_items) except row b's exclusion list; target[b] is always eligible, even when
+ *   the list holds it. Row b uses list excl_row[b] (int32 [n_queries]) of the CSR (excl_ptr int64 [n_lists + 1] into
+ *   excl_items int32), or list b when excl_row is NULL (then n_lists >= n_queries): a per-user table plus the batch's
+ *   user ids serve as they are. Lists are ascending, duplicates allowed; the ids are only compared, never used as
+ *   addresses. An excl_row value outside [0, n_lists) means an empty list. All three pointers NULL: no exclusions
+ *   (excl_ptr and excl_items go together, excl_row needs them).
+ * A target outside [0, n_items) (the model passes -1) skips the row: its loss term, lse[b] and tscore[b] are 0, its dQ
+ *   row is 0 and it adds nothing to dI.
+ * sagnn_softmax_loss_bwd_f32: given lse as the forward wrote it and the upstream scalar g (DEVICE float [1]), with
+ *   g(b, i) = g * scale * inv_temp * (p(b, i) - [i == target[b]]), p = exp(z - lse[b]) on eligible items and 0 elsewhere,
+ *   dQ[b] = sum_i g(b, i) I[i] and dI[i] = sum_b g(b, i) Q[b]. The logits are recomputed, never stored. Every row of
+ *   dQ [n_queries, d] and dI [n_items, d] is WRITTEN (zeros where nothing contributes); nothing is accumulated.
+ * lse[b], tscore[b] and dQ[b] depend on row b's inputs only: not on n_queries, the row's position or the strides. All
+ *   outputs are bit-identical between runs (no atomics: chunk partials are merged in a fixed order).
+ * Logits beyond fp32's exp range are fine (running maximum); a side without eligible items merges as empty.
+ * Limits: d in {32, 64, 128}; n_queries >= 0; 1 <= n_items < 2^31; ldq, ldi, lddq, lddi multiples of 4 and >= d; Q, I, dQ,
+ *   dI and workspace 16-byte aligned; inv_temp > 0 and finite, scale finite; workspace_bytes >=
+ *   sagnn_softmax_loss_workspace_bytes(n_queries, n_items, d) (one size serves both entries; it grows with each
+ *   argument). Every argument is checked before any device work. Three launches each on `stream`, no allocation, no
+ *   synchronisation (capturable). Profile kind 6.
+ * -------------------------------------------------------------------------------- */
+size_t sagnn_softmax_loss_workspace_bytes(int64_t n_queries, int64_t n_items, int d);
+int sagnn_softmax_loss_f32(const float* Q, int64_t ldq, const float* I, int64_t ldi, int64_t n_queries, int64_t n_items,
+                           int d, const int32_t* target, float inv_temp, float scale, const int64_t* excl_ptr,
+                           const int32_t* excl_items, const int32_t* excl_row, int64_t n_lists, float* loss, float* lse,
+                           float* tscore, void* workspace, size_t workspace_bytes, void* stream);
+int sagnn_softmax_loss_bwd_f32(const float* Q, int64_t ldq, const float* I, int64_t ldi, int64_t n_queries,
+                               int64_t n_items, int d, const int32_t* target, float inv_temp, float scale,
+                               const int64_t* excl_ptr, const int32_t* excl_items, const int32_t* excl_row,
+                               int64_t n_lists, const float* lse, const float* g, float* dQ, int64_t lddq, float* dI,
+                               int64_t lddi, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

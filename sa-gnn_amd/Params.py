@@ -82,6 +82,14 @@ _FLAGS = [
                            "in the reference's graph: it multiplies the mask in before the attention layers "
                            "(model.py:161-162) and never passes attn_mask (Utils/attention.py:35-45)",
      ("sum", "full")),
+    ("predLoss", str, "hinge", "the training loss of the prediction head: hinge (one positive against 40 sampled "
+                               "negatives, the reference's loss) or softmax (cross-entropy of the user's next item "
+                               "against every item the sampler may draw as its negative, over the whole catalogue; the "
+                               "same variables, so checkpoints carry over; needs --fusion_rows all and latdim in "
+                               "{32, 64, 128}). Not in the reference, which has the sampled hinge loss only "
+                               "(model.py:241-246)", ("hinge", "softmax")),
+    ("softmaxTemp", float, 1.0, "temperature of --predLoss softmax: the logits are <q, item> / softmaxTemp, > 0 (not in "
+                                "the reference)"),
 ]
 
 

@@ -481,6 +481,25 @@ class PairScoreFn(torch.autograd.Function):
         return dU, dI, dS, None, None, None, None
 
 
+class SoftmaxLossFn(torch.autograd.Function):
+    """Full-catalogue softmax cross-entropy of ops.softmax_loss as a 1-element loss (--predLoss softmax). Saves lse;
+    the backward recomputes the logits in two kernels (dQ by item chunk, dI by item tile) and never stores them."""
+
+    @staticmethod
+    def forward(ctx, Q, I, target, inv_temp, scale, excl, excl_row):
+        Q, I = Q.detach().contiguous(), I.detach().contiguous()
+        loss, lse, _ = ops.softmax_loss(Q, I, target, inv_temp, scale, excl, excl_row)
+        ctx.save_for_backward(Q, I, target, lse)
+        ctx.args = (inv_temp, scale, excl, excl_row)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        Q, I, target, lse = ctx.saved_tensors
+        dQ, dI = ops.softmax_loss_bwd(Q, I, target, lse, g.detach().reshape(1).float().contiguous(), *ctx.args)
+        return dQ, dI, None, None, None, None, None
+
+
 class ProdLeakySumFn(torch.autograd.Function):
     """s[e] = sum_j leaky(X[u][j] * Y[i][j]) (model.py:191, :199)."""
 

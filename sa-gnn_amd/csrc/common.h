@@ -108,7 +108,8 @@ int gemm_tn(const float* X, int64_t ldx, int64_t xseg, const float* G, int64_t l
             int din, int dout, float* dW, int64_t lddw, float* db, hipStream_t s);
 
 // ---- optional per-launch timing (sagnn_profile_*) -------------------------------------------
-enum ProfileKind { kProfSpmmRows = 0, kProfSpmmFixup = 1, kProfLstm = 2, kProfLayerNorm = 3, kProfMhsa = 4, kProfSeqAtt = 5 };
+enum ProfileKind { kProfSpmmRows = 0, kProfSpmmFixup = 1, kProfLstm = 2, kProfLayerNorm = 3, kProfMhsa = 4, kProfSeqAtt = 5,
+                   kProfSoftmaxLoss = 6 };
 
 // Records a hipEvent pair around the launches issued during its lifetime, on the launch stream,
 // when profiling is enabled; otherwise does nothing.

@@ -24,6 +24,7 @@ from .graph import NORMS, interval_pair
 
 
 SEQ_ATT = ("sum", "full")      # --seqAtt: the reference's collapsed head, or attention over every sequence item
+PRED_LOSS = ("hinge", "softmax")   # --predLoss: the reference's sampled hinge loss, or softmax over the whole catalogue
 
 
 def random_fusion_params(d: int, device, seed: int = 0) -> dict:
@@ -96,6 +97,44 @@ def _metrics(tot, num):
             "HR20": tot[4] / num, "NDCG20": tot[5] / num}
 
 
+def _check_sequence_ids(flat, ptr, n_items: int):
+    """ValueError for the first sequence id outside [0, n_items)."""
+    bad = np.flatnonzero((flat < 0) | (flat >= n_items))
+    if bad.size:
+        u = int(np.searchsorted(ptr, bad[0], side="right") - 1)
+        raise ValueError(f"sequence of user {u} holds item {int(flat[bad[0]])}, outside [0, {n_items})")
+
+
+def banned_table(handler, n_items: int, flat=None, ptr=None):
+    """The banned CSR of every user as host arrays (ban_ptr int64 [U + 1], ban_items int32): per user the sorted
+    distinct items of its trnMat row (non-zero values), its last item and its test item, i.e. what the reference's
+    negSamp never returns (DataHandler.py:28-41). The device sampler draws its negatives outside these lists and the
+    full-catalogue softmax loss leaves them out of its sum. flat / ptr: _flatten_sequences(handler.sequence) when the
+    caller holds it already."""
+    if flat is None:
+        flat, ptr = _flatten_sequences(handler.sequence)
+    U, I = len(ptr) - 1, int(n_items)
+    _check_sequence_ids(flat, ptr, I)
+    lens = np.diff(ptr)
+    # banned (user, item) keys: trnMat's non-zero entries, the last item, the test item
+    trn = sp.csr_matrix(handler.trnMat, copy=True)
+    trn.sum_duplicates()
+    trn.eliminate_zeros()
+    rows = [np.repeat(np.arange(trn.shape[0], dtype=np.int64), np.diff(trn.indptr))]
+    cols = [trn.indices.astype(np.int64)]
+    has = np.flatnonzero(lens > 0)
+    rows.append(has)
+    cols.append(flat[ptr[has + 1] - 1])
+    tst = _tst_as_int64(handler.tstInt)
+    tu = np.flatnonzero((tst >= 0) & (tst < I))
+    rows.append(tu)
+    cols.append(tst[tu])
+    keys = np.unique(np.concatenate(rows) * I + np.concatenate(cols))
+    ban_ptr = np.zeros(U + 1, dtype=np.int64)
+    np.cumsum(np.bincount(keys // I, minlength=U)[:U], out=ban_ptr[1:])
+    return ban_ptr, (keys % I).astype(np.int32)
+
+
 class DeviceSampler:
     """The per-dataset tables of the device sampler (sagnn_sample_train_i32 / sagnn_sample_ssl_i32), built and
     checked once on the host and kept on the device:
@@ -112,27 +151,9 @@ class DeviceSampler:
         flat, ptr = _flatten_sequences(handler.sequence)
         U, I = len(ptr) - 1, int(n_items)
         lens = np.diff(ptr)
-        bad = np.flatnonzero((flat < 0) | (flat >= I))
-        if bad.size:
-            u = int(np.searchsorted(ptr, bad[0], side="right") - 1)
-            raise ValueError(f"sequence of user {u} holds item {int(flat[bad[0]])}, outside [0, {I})")
+        _check_sequence_ids(flat, ptr, I)
         self.samp = np.clip(np.minimum(train_sample_num, lens - 1), 0, None)
-        # banned (user, item) keys: trnMat's non-zero entries, the last item, the test item
-        trn = sp.csr_matrix(handler.trnMat, copy=True)
-        trn.sum_duplicates()
-        trn.eliminate_zeros()
-        rows = [np.repeat(np.arange(trn.shape[0], dtype=np.int64), np.diff(trn.indptr))]
-        cols = [trn.indices.astype(np.int64)]
-        has = np.flatnonzero(lens > 0)
-        rows.append(has)
-        cols.append(flat[ptr[has + 1] - 1])
-        tst = _tst_as_int64(handler.tstInt)
-        tu = np.flatnonzero((tst >= 0) & (tst < I))
-        rows.append(tu)
-        cols.append(tst[tu])
-        keys = np.unique(np.concatenate(rows) * I + np.concatenate(cols))
-        ban_ptr = np.zeros(U + 1, dtype=np.int64)
-        np.cumsum(np.bincount(keys // I, minlength=U)[:U], out=ban_ptr[1:])
+        ban_ptr, ban_items = banned_table(handler, I, flat, ptr)
         full = np.flatnonzero((self.samp > 0) & (np.diff(ban_ptr) >= I))
         if full.size:
             raise ValueError(f"user {int(full[0])} has training pairs to draw but every item is banned for negatives")
@@ -155,7 +176,7 @@ class DeviceSampler:
         as_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
         self.n_users, self.n_items, self.train_sample_num, self.ssl_num = U, I, int(train_sample_num), int(ssl_num)
         self.seq_ptr, self.seq_items = as_dev(ptr), as_dev(flat.astype(np.int32))
-        self.ban_ptr, self.ban_items = as_dev(ban_ptr), as_dev((keys % I).astype(np.int32))
+        self.ban_ptr, self.ban_items = as_dev(ban_ptr), as_dev(ban_items)
         self.sub_ptr = as_dev(sub_ptr)
         self.sub_items = as_dev(np.concatenate(sub_items) if sub_items else np.zeros(0, np.int32))
 
@@ -714,7 +735,10 @@ class Recommender:
         loss reads only (_touched_rows, autograd.interval_fusion_rows); fu / fi stay full-size with zero rows elsewhere.
         With an edge keep rate below 1 (edge_keep, default args.edgeKeepRate) the GNN stack drops edges, forward and
         backward alike, keyed by batch["edge_seed"] = (seed, step) (default (0, 0)); every other entry point of the
-        model (forward, evaluators, recommend, parallel) never drops."""
+        model (forward, evaluators, recommend, parallel) never drops.
+        Under --predLoss softmax preLoss is the full-catalogue softmax cross-entropy of every active slot's positive
+        (_softmax_pre_loss) and the batch's sampled negatives are not read. The flag is not part of the model: the
+        variables are the same, and checkpoints neither store nor check it."""
         T, L, d, heads, leaky = args.graphNum, args.gnn_layer, args.latdim, args.num_attention_heads, NNs.leaky
         keep = args.keepRate if keep_rate is None else keep_rate
         subset = args.fusion_rows == "batch"
@@ -759,10 +783,13 @@ class Recommender:
             att = self._seq_att_full(fi, *tokens)
         else:
             att = self._head_att_sum_train(fi, batch)
-        preds = ag.PairScoreFn.apply(fu, fi, att, self._i32(batch["uids"]), self._i32(batch["iids"]),
-                                     self._i32(batch["uLocs_seq"]), leaky)
-        n = preds.shape[0] // 2
-        pre_loss = ag.HingeFn.apply(preds[:n], preds[n:], None, None, None, None, 1.0 / max(n, 1))
+        if args.predLoss == "softmax":
+            pre_loss = self._softmax_pre_loss(fu, fi, att, batch)
+        else:
+            preds = ag.PairScoreFn.apply(fu, fi, att, self._i32(batch["uids"]), self._i32(batch["iids"]),
+                                         self._i32(batch["uLocs_seq"]), leaky)
+            n = preds.shape[0] // 2
+            pre_loss = ag.HingeFn.apply(preds[:n], preds[n:], None, None, None, None, 1.0 / max(n, 1))
         # ---- SSL (model.py:174-205)
         ssl = torch.zeros(1, dtype=torch.float32, device=self.device)
         for k in range(T):
@@ -775,6 +802,39 @@ class Recommender:
             p1 = ag.ProdLeakySumFn.apply(uv[k], iv[k], su, si, leaky)
             ssl = ssl + ag.HingeFn.apply(p1[:ns], p1[ns:], w[:ns], w[ns:], s_final[:ns], s_final[ns:], 1.0)
         return pre_loss, ssl
+
+    def _banned_device(self):
+        """banned_table of the current handler as device tensors (ptr int64, items int32), built once."""
+        h = self.handler
+
+        def build():
+            ptr, items = banned_table(h, args.item)
+            items = items if items.size else np.zeros(1, np.int32)       # an empty table still needs a valid pointer
+            return torch.from_numpy(ptr).to(self.device), torch.from_numpy(items).to(self.device)
+        return self._cached("_banned_dev", (h.sequence, h.trnMat, h.tstInt, args.item, str(self.device)), build)
+
+    def _softmax_pre_loss(self, fu, fi, att, batch):
+        """--predLoss softmax: (1 / max(n_active, 1)) * sum over the active slots b of ln sum_{i in E_b} exp(z_bi) - z_{b,t_b}
+        with z_bi = <leaky(att[b]) + fu[u_b], fi[i]> / softmaxTemp and E_b = every item outside user u_b's banned list
+        (the items negSamp never draws), plus the target t_b. One (slot, user, target) triple per active slot, from the
+        positive half of the batch without a read-back: the first pair of each slot (host batch) or the pair at the
+        slot's pair offset (device batch: batch["active"] = (slots, offsets), host tables of sample_batch_device)."""
+        dev = self.device
+        if "active" in batch:
+            slots, first = batch["active"]
+        else:
+            locs = batch["uLocs_seq"]
+            locs = locs.cpu().numpy() if isinstance(locs, torch.Tensor) else np.asarray(locs)
+            slots, first = np.unique(locs[:len(locs) // 2], return_index=True)
+        if len(slots) == 0:
+            return att.sum().reshape(1) * 0.0
+        first = torch.as_tensor(np.asarray(first, dtype=np.int64), device=dev)
+        slots = torch.as_tensor(np.asarray(slots, dtype=np.int64), device=dev)
+        u = self._i32(batch["uids"]).index_select(0, first)
+        t = self._i32(batch["iids"]).index_select(0, first)
+        q = ag.LeakyAddFn.apply(att.index_select(0, slots), fu.index_select(0, u.long()), NNs.leaky)
+        return ag.SoftmaxLossFn.apply(q, fi, t, 1.0 / args.softmaxTemp, 1.0 / max(int(slots.numel()), 1),
+                                      self._banned_device(), u)
 
     def _head_att_sum_train(self, fi, batch):
         """The reference's collapsed head (--seqAtt sum) as autograd nodes: the masked sums make ONE token per slot and
@@ -942,8 +1002,9 @@ class Recommender:
     def sample_batch_device(self, batIds, seed: int, step: int) -> dict:
         """One training batch drawn on the device: sampleTrainBatch's and sampleSslBatch's distributions (with the SSL
         pairs drawn from each row's distinct items), as a pure function of (seed, step, user id) per user. Returns
-        device int32 tensors uids, iids, uLocs_seq, suids[k], siids[k] and seq_seg = (seg_begin int64, seg_len int32)
-        [args.batch], the head's sequence segments. Every count comes from host tables: nothing is copied back."""
+        device int32 tensors uids, iids, uLocs_seq, suids[k], siids[k], seq_seg = (seg_begin int64, seg_len int32)
+        [args.batch], the head's sequence segments, and active = (slots, offsets): the slots that hold pairs and the
+        index of each one's first pair (host int64 arrays). Every count comes from host tables: nothing is copied back."""
         S = self._device_sampler()
         bat = np.asarray(batIds, dtype=np.int64).reshape(-1)
         B, T = len(bat), len(S.npair)
@@ -966,7 +1027,9 @@ class Recommender:
             args.pred_num, args.pos_length, offs_d[:B], n_pairs, seed, step)
         su, si, _ = ops.sample_ssl(bat_d, S.sub_ptr, S.sub_items, S.ssl_num, offs_d[B:B + T * B], int(offs[-1]), seed, step)
         ends = np.concatenate([[0], np.cumsum(npair2.sum(1))]).astype(np.int64)
+        act = np.flatnonzero(samp > 0)                                    # the slots that hold pairs, and their first pair
         return {"uids": uids, "iids": iids, "uLocs_seq": locs, "seq_seg": (seg_begin, seg_len),
+                "active": (act.astype(np.int64), offs[:B][act]),
                 "suids": [su[ends[k]:ends[k + 1]] for k in range(T)], "siids": [si[ends[k]:ends[k + 1]] for k in range(T)]}
 
     def _trainable(self):
@@ -1068,6 +1131,16 @@ class Recommender:
             raise ValueError(f"--adjNorm {args.adjNorm}: one of {NORMS}")
         if args.seqAtt not in SEQ_ATT:
             raise ValueError(f"--seqAtt {args.seqAtt}: one of {SEQ_ATT}")
+        if args.predLoss not in PRED_LOSS:
+            raise ValueError(f"--predLoss {args.predLoss}: one of {PRED_LOSS}")
+        if not args.softmaxTemp > 0.0 or not np.isfinite(args.softmaxTemp):
+            raise ValueError(f"--softmaxTemp {args.softmaxTemp}: need a finite temperature > 0")
+        if args.predLoss == "softmax":
+            if args.fusion_rows == "batch":
+                raise ValueError("--predLoss softmax does not combine with --fusion_rows batch: the loss reads every item "
+                                 "row of the fused table, so there is no row subset to fuse")
+            if args.latdim not in (32, 64, 128):
+                raise ValueError(f"--predLoss softmax needs latdim in (32, 64, 128), got {args.latdim}")
         if args.seqAtt == "full":          # refused before any forward: the attention kernels take these shapes only
             why = ops.seq_attn_supported(args.latdim, args.num_attention_heads, args.pos_length)
             if why is not None:

@@ -911,6 +911,105 @@ def score_topk(Q: torch.Tensor, I: torch.Tensor, k: int, excl=None, target=None)
     return items, scores, rank
 
 
+_softmax_ws: dict = {}   # (device, n_queries, n_items, d) -> workspace of sagnn_softmax_loss_f32 and its backward
+
+
+def _softmax_workspace(device: torch.device, B: int, n_items: int, d: int):
+    key = (device, B, n_items, d)
+    ws = _softmax_ws.get(key)
+    if ws is None:
+        need = int(_lib.load().sagnn_softmax_loss_workspace_bytes(B, n_items, d))
+        if len(_softmax_ws) >= 8:      # a training run has one or two sizes (the last batch of an epoch is shorter)
+            _softmax_ws.clear()
+        ws = _softmax_ws[key] = (torch.empty(max(need, 256), dtype=torch.uint8, device=device), need)
+    return ws
+
+
+def _softmax_args(Q, I, target, inv_temp, scale, excl, excl_row):
+    """Host checks shared by softmax_loss and softmax_loss_bwd, before any device call. Returns the leading arguments
+    of both entries, (B, n_items, d) and the tensors that must stay alive over the call."""
+    if not isinstance(Q, torch.Tensor) or Q.dim() != 2:
+        raise ValueError(f"Q: expected [B, d], got {tuple(Q.shape) if isinstance(Q, torch.Tensor) else type(Q)}")
+    B, d = int(Q.shape[0]), int(Q.shape[1])
+    if d not in (32, 64, 128):
+        raise ValueError(f"softmax_loss: d = {d}, need 32, 64 or 128")
+    n_items = int(I.shape[0]) if isinstance(I, torch.Tensor) and I.dim() == 2 else 0
+    if n_items < 1 or n_items >= 2 ** 31:
+        raise ValueError(f"I: expected [n_items, {d}] with 1 <= n_items < 2^31")
+    inv_temp = float(inv_temp)
+    if not (inv_temp > 0.0 and np.isfinite(inv_temp)):
+        raise ValueError(f"inv_temp = {inv_temp}: need a finite value > 0")
+    scale = 1.0 / max(B, 1) if scale is None else float(scale)
+    if not np.isfinite(scale):
+        raise ValueError(f"scale = {scale} is not finite")
+    ldq, ldi = _f32_rows("Q", Q, d), _f32_rows("I", I, d)
+    dev = Q.device
+    if I.device != dev:
+        raise ValueError(f"I on {I.device}, Q on {dev}")
+    tgt = _idx_ptr("target", target, torch.int32, B)
+    if target.device != dev:
+        raise ValueError(f"target on {target.device}, Q on {dev}")
+    ptr_p = items_p = row_p = None
+    n_lists = 0
+    if excl is None:
+        if excl_row is not None:
+            raise ValueError("excl_row without excl")
+    else:
+        ex_ptr, ex_items = excl
+        if not isinstance(ex_ptr, torch.Tensor) or ex_ptr.dim() != 1 or ex_ptr.numel() < 1:
+            raise ValueError("excl: expected (ptr int64 [n_lists + 1], items int32) device tensors")
+        n_lists = int(ex_ptr.numel()) - 1
+        ptr_p = _idx_ptr("excl ptr", ex_ptr, torch.int64)
+        items_p = _idx_ptr("excl items", ex_items, torch.int32)
+        if ex_ptr.device != dev or ex_items.device != dev:
+            raise ValueError(f"excl on {ex_ptr.device} / {ex_items.device}, Q on {dev}")
+        if excl_row is not None:
+            row_p = _idx_ptr("excl_row", excl_row, torch.int32, B)
+            if excl_row.device != dev:
+                raise ValueError(f"excl_row on {excl_row.device}, Q on {dev}")
+        elif n_lists < B:
+            raise ValueError(f"excl: {n_lists} lists for {B} rows and no excl_row")
+    lead = (Q.data_ptr(), ldq, I.data_ptr(), ldi, B, n_items, d, tgt, inv_temp, scale, ptr_p, items_p, row_p, n_lists)
+    return lead, (B, n_items, d)
+
+
+def softmax_loss(Q: torch.Tensor, I: torch.Tensor, target: torch.Tensor, inv_temp: float = 1.0, scale: float | None = None,
+                 excl=None, excl_row: torch.Tensor | None = None):
+    """Full-catalogue softmax cross-entropy (sagnn_softmax_loss_f32): z[b, i] = <Q[b], I[i]> * inv_temp,
+    loss = scale * sum_b (lse[b] - z[b, target[b]]), lse[b] = ln sum exp z[b, i] over row b's eligible items: all of
+    [0, n_items) except its exclusion list, the target always eligible. target int32 [B], rows with a target outside
+    [0, n_items) are skipped. excl = (ptr int64 [n_lists + 1], items int32) device tensors, lists ascending; row b uses
+    list excl_row[b] (int32 [B]) or list b. scale defaults to 1 / max(B, 1).
+    Returns (loss [1], lse [B], tscore [B] = <Q[b], I[target[b]]>); the logits are never stored."""
+    lead, (B, n_items, d) = _softmax_args(Q, I, target, inv_temp, scale, excl, excl_row)
+    dev = Q.device
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    lse, tscore = _out(B, torch.float32, dev), _out(B, torch.float32, dev)
+    ws, need = _softmax_workspace(dev, B, n_items, d)
+    check(_lib.load().sagnn_softmax_loss_f32(*lead, loss.data_ptr(), lse.data_ptr(), tscore.data_ptr(), ws.data_ptr(), need,
+                                             _stream()))
+    return loss, lse, tscore
+
+
+def softmax_loss_bwd(Q: torch.Tensor, I: torch.Tensor, target: torch.Tensor, lse: torch.Tensor, g: torch.Tensor,
+                     inv_temp: float = 1.0, scale: float | None = None, excl=None, excl_row: torch.Tensor | None = None):
+    """Gradients of softmax_loss (sagnn_softmax_loss_bwd_f32) given the forward's lse [B] and the upstream scalar g (a
+    1-element float32 device tensor): returns (dQ [B, d], dI [n_items, d]), every row written, the logits recomputed."""
+    lead, (B, n_items, d) = _softmax_args(Q, I, target, inv_temp, scale, excl, excl_row)
+    dev = Q.device
+    for name, t, n in (("lse", lse, B), ("g", g, 1)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous() \
+                or t.numel() != n:
+            raise ValueError(f"{name}: need a contiguous float32 tensor of {n} elements on {dev}")
+    dQ = torch.empty((max(B, 1), d), dtype=torch.float32, device=dev)[:B]
+    dI = torch.empty((n_items, d), dtype=torch.float32, device=dev)
+    ws, need = _softmax_workspace(dev, B, n_items, d)
+    lse_p = lse.data_ptr() if B else dQ.data_ptr()
+    check(_lib.load().sagnn_softmax_loss_bwd_f32(*lead, lse_p, g.data_ptr(), dQ.data_ptr(), d, dI.data_ptr(), d,
+                                                 ws.data_ptr(), need, _stream()))
+    return dQ, dI
+
+
 def candidate_rank(U: torch.Tensor, I: torch.Tensor, uids: torch.Tensor, cand: torch.Tensor, target: torch.Tensor,
                    S: torch.Tensor | None = None, A: torch.Tensor | None = None, leaky: float = 1.0,
                    want_scores: bool = False):

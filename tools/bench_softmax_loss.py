@@ -1,0 +1,114 @@
+"""Times the full-catalogue softmax loss (ops.softmax_loss / softmax_loss_bwd -> sagnn_softmax_loss_f32 and its
+backward) at 512 queries, forward and forward + backward, beside the materialised torch form
+cross_entropy(Q @ I.T / temp + mask) in the same process, and prints one JSON line per case. Needs a GPU.
+
+  python tools/bench_softmax_loss.py [--iters 20] [--warmup 3] [--rounds 5] [--cases gowalla,movielens,synthetic]
+
+Cases: Gowalla-shaped (52,619 items, d 32), MovieLens-shaped (3,706 items, d 128), synthetic (5 M items, d 64). Every
+user excludes 100 random items. The two forms alternate round by round; the figures are medians over the rounds. The
+torch form runs where its [512, n_items] logits, mask and softmax fit (not at 5 M items). The per-kernel split comes
+from sagnn_profile_read (kind 6: one record per entry) and, kernel by kernel, from a profiler's kernel trace.
+Rates count 2 * queries * items * d flops per product: one product forward, four backward (the scores twice, dQ, dI)."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from sa_gnn_amd import ops  # noqa: E402
+
+PEAK_TF = 155.0     # measured fp32-MFMA rate of the MI355X (v_mfma_f32_16x16x4_f32)
+CASES = {"gowalla": (52_619, 32, 512), "movielens": (3_706, 128, 512), "synthetic": (5_000_000, 64, 512)}
+N_EXCL = 100
+
+
+def timed(fn, iters, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--cases", default=",".join(CASES))
+    ap.add_argument("--temp", type=float, default=1.0)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("bench_softmax_loss: no GPU visible")
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(0)
+    rng = np.random.default_rng(0)
+    inv_temp = 1.0 / a.temp
+    for name in a.cases.split(","):
+        n_items, d, B = CASES[name]
+        I = torch.randn((n_items, d), generator=g, device=dev) * 0.3
+        Q = torch.randn((B, d), generator=g, device=dev) * 0.3
+        tgt = torch.randint(0, n_items, (B,), generator=g, device=dev, dtype=torch.int32)
+        lists = np.sort(rng.integers(0, n_items, (B, N_EXCL)), axis=1)
+        ptr = torch.arange(0, (B + 1) * N_EXCL, N_EXCL, dtype=torch.int64, device=dev)
+        items = torch.from_numpy(lists.reshape(-1).astype(np.int32)).to(dev)
+        one = torch.ones(1, device=dev)
+        excl = (ptr, items)
+
+        def fwd():
+            return ops.softmax_loss(Q, I, tgt, inv_temp, None, excl)
+
+        def fwd_bwd():
+            _, lse, _ = fwd()
+            return ops.softmax_loss_bwd(Q, I, tgt, lse, one, inv_temp, None, excl)
+
+        torch_fits = B * n_items * 4 * 6 < (8 << 30)
+        if torch_fits:
+            mask = torch.zeros((B, n_items), device=dev)
+            mask[torch.arange(B, device=dev).repeat_interleave(N_EXCL), items.long()] = float("-inf")
+            mask[torch.arange(B, device=dev), tgt.long()] = 0.0
+            Qt, It = Q.clone().requires_grad_(True), I.clone().requires_grad_(True)
+
+            def t_fwd():
+                with torch.no_grad():
+                    return torch.nn.functional.cross_entropy(Q @ I.T * inv_temp + mask, tgt.long())
+
+            def t_fwd_bwd():
+                Qt.grad = It.grad = None
+                torch.nn.functional.cross_entropy(Qt @ It.T * inv_temp + mask, tgt.long()).backward()
+
+        res = {k: [] for k in ("fwd", "fwd_bwd", "torch_fwd", "torch_fwd_bwd")}
+        for _ in range(a.rounds):          # alternated: both forms see the same machine state
+            res["fwd"].append(timed(fwd, a.iters, a.warmup))
+            res["fwd_bwd"].append(timed(fwd_bwd, a.iters, a.warmup))
+            if torch_fits:
+                res["torch_fwd"].append(timed(t_fwd, a.iters, a.warmup))
+                res["torch_fwd_bwd"].append(timed(t_fwd_bwd, a.iters, a.warmup))
+        med = {k: float(np.median(v)) for k, v in res.items() if v}
+        flop = 2.0 * B * n_items * d
+        bwd_ms = med["fwd_bwd"] - med["fwd"]
+        rec = {"case": name, "n_items": n_items, "d": d, "queries": B, "fwd_ms": round(med["fwd"], 4),
+               "fwd_bwd_ms": round(med["fwd_bwd"], 4), "fwd_tflops": round(flop / med["fwd"] / 1e9, 2),
+               "fwd_frac_of_155": round(flop / med["fwd"] / 1e9 / PEAK_TF, 4),
+               "bwd_tflops": round(4 * flop / bwd_ms / 1e9, 2), "bwd_frac_of_155": round(4 * flop / bwd_ms / 1e9 / PEAK_TF, 4)}
+        if torch_fits:
+            loss = float(fwd()[0])
+            rec.update({"torch_fwd_ms": round(med["torch_fwd"], 4), "torch_fwd_bwd_ms": round(med["torch_fwd_bwd"], 4),
+                        "fwd_speedup": round(med["torch_fwd"] / med["fwd"], 2),
+                        "fwd_bwd_speedup": round(med["torch_fwd_bwd"] / med["fwd_bwd"], 2),
+                        "loss": loss, "torch_loss": float(t_fwd())})
+            del mask, Qt, It
+        print(json.dumps(rec), flush=True)
+        del I, Q
+
+
+if __name__ == "__main__":
+    main()

@@ -7,7 +7,8 @@ trnNum 10000 -> 20 steps per epoch, keepRate 0.5) and prints where a training st
 fusion modes as well (all rows / the rows the batch reads) and reports the touched rows per step and the f16 x 2
 kernels' fp32 re-evaluations per epoch of each mode. --seqAtt both alternates the head's two forms (the collapsed sum /
 attention over every sequence item) and reports the device time of the sequence-attention entries per step
-(sagnn_profile_read, kind 5)."""
+(sagnn_profile_read, kind 5). --predLoss both alternates the head's two training losses (the sampled hinge loss / the
+full-catalogue softmax) and reports the device time of the softmax entries per step (kind 6)."""
 import argparse
 import ctypes
 import sys
@@ -33,6 +34,8 @@ def main():
                     help="--edgeKeepRate of the run: below 1 the training steps drop edges of the interval graphs")
     ap.add_argument("--seqAtt", choices=("sum", "full", "both"), default="sum",
                     help="the head's form(s) to time; both alternates them in one process")
+    ap.add_argument("--predLoss", choices=("hinge", "softmax", "both"), default="hinge",
+                    help="the head's training loss(es) to time; both alternates them in one process")
     opt = ap.parse_args()
     Params.parse_args("--data gowalla --lr 2e-3 --reg 1e-2 --ssl_reg 1e-6 --epoch 150 --batch 512 --sslNum 40 --graphNum 3 "
                       "--gnn_layer 2 --att_layer 1 --testSize 1000 --ssldim 48 --keepRate 0.5".split(), namespace=args)
@@ -53,18 +56,23 @@ def main():
         args.sampler = "device"
         args.fusion_rows = "batch" if opt.fusion_rows == "batch" else "all"
         args.seqAtt = "full" if opt.seqAtt == "full" else "sum"
+        args.predLoss = "softmax" if opt.predLoss == "softmax" else "hinge"
         for _ in range(2):
             rec.trainEpoch()
         torch.cuda.synchronize()
         print(f"two device-sampler epochs done (--fusion_rows {args.fusion_rows}, --edge_keep {args.edgeKeepRate}, "
-              f"--seqAtt {args.seqAtt}); every parameter finite:",
+              f"--seqAtt {args.seqAtt}, --predLoss {args.predLoss}); every parameter finite:",
               all(bool(torch.isfinite(p).all()) for p in NNs.params.values()))
         return
     modes = ("all", "batch") if opt.fusion_rows == "both" else (opt.fusion_rows,)
     atts = ("sum", "full") if opt.seqAtt == "both" else (opt.seqAtt,)
-    configs = [(sampler, mode, att) for att in atts for mode in modes for sampler in ("host", "device")]
+    losses = ("hinge", "softmax") if opt.predLoss == "both" else (opt.predLoss,)
+    if "softmax" in losses and "batch" in modes:
+        sys.exit("--predLoss softmax does not combine with --fusion_rows batch")
+    configs = [(sampler, mode, att, loss) for loss in losses for att in atts for mode in modes for sampler in ("host", "device")]
     label = lambda c: ", ".join([c[0]] + ([f"{c[1]} rows"] if len(modes) > 1 else []) +   # noqa: E731
-                                ([f"seqAtt {c[2]}"] if atts != ("sum",) else []))
+                                ([f"seqAtt {c[2]}"] if atts != ("sum",) else []) +
+                                ([f"predLoss {c[3]}"] if losses != ("hinge",) else []))
 
     initial = {k: p.detach().clone() for k, p in NNs.params.items()}
     finite = {}
@@ -76,8 +84,8 @@ def main():
         # forms every timed epoch is therefore the first epoch of its own training (profiles/seq_att_epoch.txt holds a
         # parent-commit run that shows the default path's divergence). A run without --seqAtt both keeps training its
         # parameters as before, so its lines, not a `both` run's sum lines, are what compares with an earlier commit.
-        args.sampler, args.fusion_rows, args.seqAtt = c
-        if fresh and len(atts) > 1:
+        args.sampler, args.fusion_rows, args.seqAtt, args.predLoss = c
+        if fresh and len(atts) * len(losses) > 1:
             with torch.no_grad():
                 for k, p in NNs.params.items():
                     p.copy_(initial[k])
@@ -152,7 +160,7 @@ def main():
                   f"({100 * tu / args.user:.2f} %), items {ti:.1f} of {args.item} ({100 * ti / args.item:.2f} %)")
     if "full" in atts:        # device time of the sequence-attention entries (profile kind 5), one device-sampler epoch
         lib = ops._lib.load()
-        use(("device", modes[0], "full"), fresh=True)
+        use(("device", modes[0], "full", losses[0]), fresh=True)
         cap = 4096 * steps
         lib.sagnn_profile_enable(cap)
         rec.trainEpoch()
@@ -164,8 +172,22 @@ def main():
               f"{int(sel.sum()) / steps:.0f} calls and {float(ms[:n.value][sel].sum()) / steps:.3f} ms of device time per step; "
               f"layer-norm entries (profile kind 3): {float(ms[:n.value][kind[:n.value] == 3].sum()) / steps:.3f} ms per step")
         print("every parameter finite after that epoch:", all(bool(torch.isfinite(p).all()) for p in NNs.params.values()))
+    if "softmax" in losses:   # device time of the softmax-loss entries (profile kind 6), one device-sampler epoch
+        lib = ops._lib.load()
+        use(("device", modes[0], atts[0], "softmax"), fresh=True)
+        cap = 4096 * steps
+        lib.sagnn_profile_enable(cap)
+        rec.trainEpoch()
+        ms, kind, n = np.zeros(cap, np.float32), np.zeros(cap, np.int32), ctypes.c_int(0)
+        ops.check(lib.sagnn_profile_read(ms.ctypes.data, kind.ctypes.data, None, None, cap, ctypes.byref(n)))
+        lib.sagnn_profile_enable(0)
+        sel = np.flatnonzero(kind[:n.value] == 6)
+        print(f"[device, predLoss softmax] softmax-loss entries: {len(sel) / steps:.0f} calls per step; forward "
+              f"{float(ms[sel[0::2]].sum()) / steps:.3f} ms and backward {float(ms[sel[1::2]].sum()) / steps:.3f} ms of device "
+              f"time per step")
     print("every parameter finite after every timed epoch above:", finite)
     args.fusion_rows = "all"
+    args.predLoss = "hinge"
     args.sampler = "host"
     args.seqAtt = "sum"
     t0 = time.perf_counter()
