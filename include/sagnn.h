@@ -350,6 +350,80 @@ int sagnn_gnn_stack_drop_bwd_f32(const sagnn_spmm_batch* batch, const float* G_u
                                  int64_t slab_di, const sagnn_edge_drop* drop, void* workspace, size_t workspace_bytes,
                                  void* stream);
 
+/* --------------------------------------------------------------------------------
+ * Time-aware messages (the term the reference comments out at model.py:86). Every stored edge of a plan
+ * carries a bucket id (sagnn_spmm_plan_set_buckets) and every product of the stack (interval k, layer l, direction dir;
+ * dir 0: rows are users, 1: rows are items) has a table TE[k,l,dir] of n_buckets rows of d floats:
+ *
+ *   s[r,:] = sum over the edges e of row r of  w[e] * ( X[col[e],:] + TE[k,l,dir][bucket[e],:] )     (w = 1: unweighted)
+ *
+ * then the epilogue of sagnn_spmm_ex_f32. X + TE is rounded once, then accumulated as the plan's kernels accumulate.
+ * The gradient into X is that of the entry without time; the backward entries add
+ *
+ *   dTE[k,l,dir][b,:] = sum over the edges e with bucket[e] = b of  w[e] * gm[row[e],:]
+ *
+ * with gm the masked gradient at that product's rows: an SpMM whose rows are buckets, run on the "time adjoint" plans
+ * the caller builds (n_rows = n_buckets, n_src = the product's row count, colidx = the row of each edge in stable
+ * bucket order, the weights permuted alongside). No atomics: dTE is a deterministic function of its inputs.
+ *
+ * A time entry refuses (SAGNN_ERR_ARG, before any launch) a plan or batch without buckets, a bucket count that differs
+ * from time->n_buckets, and a non-NULL `drop`: edge dropout and time do not combine.
+ * -------------------------------------------------------------------------------- */
+/* d_buckets: [nnz] uint16 in colidx order, every value < n_buckets <= 65535 (checked by the caller), borrowed like the
+ * weights. NULL clears them. Set before sagnn_spmm_batch_create, which copies the pointer. */
+int sagnn_spmm_plan_set_buckets(sagnn_spmm_plan* plan, const uint16_t* d_buckets, int32_t n_buckets);
+
+typedef struct sagnn_edge_time {
+  const float* te;          /* TE[0,0,0]; a table is [n_buckets, d], rows d apart, 16-byte aligned */
+  int64_t stride_interval;  /* elements from TE[k,l,dir] to TE[k+1,l,dir] */
+  int64_t stride_layer;     /*                          to TE[k,l+1,dir] */
+  int64_t stride_dir;       /*                          to TE[k,l,1] from TE[k,l,0] */
+  int32_t n_buckets;
+  /* the backward entries only */
+  float* dte;                         /* written: dTE, laid out like te */
+  const sagnn_spmm_plan* adj_user;    /* interval entries: the time-adjoint plans of the user-side (dir 0) product */
+  const sagnn_spmm_plan* adj_item;    /*                   and of the item-side (dir 1) product */
+  const sagnn_spmm_batch* adj_batch;  /* stack entries: sagnn_spmm_time_batch_create of the 2 T time-adjoint plans */
+  void* adj_workspace;                /* sagnn_spmm[_batch]_workspace_bytes of the adjoint plans (the larger) / batch */
+  size_t adj_workspace_bytes;
+} sagnn_edge_time;
+
+/* The 2 T time-adjoint plans of a model as one batch: every plan has n_buckets rows; the user-side ones gather from U
+ * rows, the item-side ones from I rows. (sagnn_spmm_batch_create insists on transposed pairs; these are not.) */
+int sagnn_spmm_time_batch_create(const sagnn_spmm_plan* const* adj_user, const sagnn_spmm_plan* const* adj_item,
+                                 int n_intervals, sagnn_spmm_batch** batch_out);
+
+/* One product with the table time->te (the strides are not read). `drop` must be NULL. */
+int sagnn_spmm_time_f32(const sagnn_spmm_plan* plan, const float* X, int64_t ldx, int d,
+                        const sagnn_spmm_epilogue* epilogue, const sagnn_edge_drop* drop, const sagnn_edge_time* time,
+                        void* workspace, size_t workspace_bytes, void* stream);
+/* The interval / stack entries with time: the argument lists of the drop entries (`drop` must be NULL) and the
+ * sagnn_edge_time. An interval entry works on TE[interval,:,:]; the stack entries on all of it. */
+int sagnn_gnn_interval_time_f32(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item, const float* u0,
+                                int64_t ld_u0, const float* i0, int64_t ld_i0, int d, int n_layers, float leaky,
+                                float* scratch_u, float* scratch_i, float* user_out, int64_t ld_uo, float* item_out,
+                                int64_t ld_io, uint8_t* mask_u, uint8_t* mask_i, const sagnn_edge_drop* drop,
+                                int interval, const sagnn_edge_time* time, void* workspace, size_t workspace_bytes,
+                                void* stream);
+int sagnn_gnn_interval_time_bwd_f32(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item,
+                                    const float* G_u, int64_t ld_gu, const float* G_i, int64_t ld_gi, int d,
+                                    int n_layers, float leaky, const uint8_t* mask_u, const uint8_t* mask_i,
+                                    float* scratch_u, float* scratch_i, float* grad_u0, int64_t ld_du, float* grad_i0,
+                                    int64_t ld_di, const sagnn_edge_drop* drop, int interval,
+                                    const sagnn_edge_time* time, void* workspace, size_t workspace_bytes, void* stream);
+int sagnn_gnn_stack_time_f32(const sagnn_spmm_batch* batch, const float* u0, int64_t ld_u0, int64_t slab_u0,
+                             const float* i0, int64_t ld_i0, int64_t slab_i0, int d, int n_layers, float leaky,
+                             float* scratch_u, float* scratch_i, float* user_out, int64_t ld_uo, int64_t slab_uo,
+                             float* item_out, int64_t ld_io, int64_t slab_io, uint8_t* mask_u, uint8_t* mask_i,
+                             const sagnn_edge_drop* drop, const sagnn_edge_time* time, void* workspace,
+                             size_t workspace_bytes, void* stream);
+int sagnn_gnn_stack_time_bwd_f32(const sagnn_spmm_batch* batch, const float* G_u, int64_t ld_gu, int64_t slab_gu,
+                                 const float* G_i, int64_t ld_gi, int64_t slab_gi, int d, int n_layers, float leaky,
+                                 const uint8_t* mask_u, const uint8_t* mask_i, float* scratch_u, float* scratch_i,
+                                 float* grad_u0, int64_t ld_du, int64_t slab_du, float* grad_i0, int64_t ld_di,
+                                 int64_t slab_di, const sagnn_edge_drop* drop, const sagnn_edge_time* time,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Interval fusion (model.py:135-155). x[node, interval, :] is read at
  * x + node*ld_n + interval*ld_t (elements): [n, t, d] storage is ld_t = d, ld_n >= t*d (what

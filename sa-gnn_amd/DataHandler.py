@@ -103,6 +103,21 @@ class DataHandler:
         self.tstUsrs = np.flatnonzero(np.array([t is not None for t in tst_int]))
         self.prepareGlobalData()
 
+    def timeProcess(self, trnMats):
+        """reference DataHandler.timeProcess (DataHandler.py:136-150), restated on int64: mi = the smallest stored
+        timestamp over all interval matrices, bucket = (t - mi) // (86400 * slot), returns (mi, largest bucket + 1).
+        The reference rewrites the matrices' data to the buckets; here they keep their timestamps and graph.pair_buckets
+        derives every edge's bucket from (mi, slot). Empty matrices (np.min raises on them there) are passed over."""
+        from .graph import edge_buckets
+        stamps = [np.asarray(m.data).astype(np.int64) for m in trnMats if m.nnz]
+        if not stamps:
+            return 0, 1
+        mi = int(min(int(t.min()) for t in stamps))
+        return mi, int(max(int(edge_buckets(t, mi, args.slot).max()) for t in stamps)) + 1
+
     def prepareGlobalData(self):
         self.maxTime = 1                                                   # DataHandler.py:164
+        self.timeMin = 0
+        if getattr(args, "edgeTime", "none") == "slot":                    # the call DataHandler.py:165 comments out
+            self.timeMin, self.maxTime = self.timeProcess(self.subMat)
         self.item_with_pop = []

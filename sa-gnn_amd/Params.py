@@ -38,7 +38,9 @@ _FLAGS = [
     ("deep_layer", int, 0, "unused"),
     ("mult", float, 100, "unused"),
     ("keepRate", float, 0.5, "dropout keep probability"),
-    ("slot", float, 1, "dead code only"),
+    ("slot", float, 1, "days per time bucket of --edgeTime slot: an interaction at time t falls in bucket "
+                       "(t - earliest) // (86400 * slot); unread under --edgeTime none, as in the reference, whose "
+                       "timeProcess call is commented out"),
     ("graphSampleN", int, 15000, "dead code only"),
     ("divSize", int, 10000, "unused"),
     ("tstEpoch", int, 3, "test every N epochs"),
@@ -88,6 +90,12 @@ _FLAGS = [
                                "same variables, so checkpoints carry over; needs --fusion_rows all and latdim in "
                                "{32, 64, 128}). Not in the reference, which has the sampled hinge loss only "
                                "(model.py:241-246)", ("hinge", "softmax")),
+    ("edgeTime", str, "none", "time inside the interval graphs: none (an edge's timestamp only decides which interval graph "
+                              "holds it, as the reference's graph computes) or slot (every message adds the row of "
+                              "timeEmbed @ W its edge's --slot-day bucket selects, W the [d, d] weight of that "
+                              "messagePropagate call, on every entry point, training and inference; part of the model; "
+                              "needs --edgeKeepRate 1). Not in the reference's graph: it defines timeEmbed and the "
+                              "weights (model.py:81, :117) and comments the term out (model.py:86)", ("none", "slot")),
     ("softmaxTemp", float, 1.0, "temperature of --predLoss softmax: the logits are <q, item> / softmaxTemp, > 0 (not in "
                                 "the reference)"),
 ]

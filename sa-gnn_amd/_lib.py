@@ -35,6 +35,13 @@ class EdgeDropArgs(ctypes.Structure):
     _fields_ = [("seed", c_uint64), ("step", c_uint32), ("keep_threshold", c_uint32), ("scale", c_float)]
 
 
+class EdgeTimeArgs(ctypes.Structure):
+    """sagnn_edge_time"""
+    _fields_ = [("te", c_void_p), ("stride_interval", c_int64), ("stride_layer", c_int64), ("stride_dir", c_int64),
+                ("n_buckets", c_int32), ("dte", c_void_p), ("adj_user", c_void_p), ("adj_item", c_void_p),
+                ("adj_batch", c_void_p), ("adj_workspace", c_void_p), ("adj_workspace_bytes", c_size_t)]
+
+
 class PlanInfo(ctypes.Structure):
     _fields_ = [("n_rows", c_int64), ("n_src", c_int64), ("nnz", c_int64),
                 ("n_long_rows", c_int64), ("n_chunks", c_int64), ("short_thresh", c_int32),
@@ -210,6 +217,26 @@ SIGNATURES.update({
     "sagnn_gnn_interval_drop_bwd_f32": _drop_form("sagnn_gnn_interval_bwd_f32", c_int),
     "sagnn_gnn_stack_drop_f32": _drop_form("sagnn_gnn_stack_f32"),
     "sagnn_gnn_stack_drop_bwd_f32": _drop_form("sagnn_gnn_stack_bwd_f32"),
+})
+
+
+
+def _time_form(entry: str, *ahead):
+    """A time entry: its drop entry's arguments (the sagnn_edge_drop must be NULL) with the sagnn_edge_time ahead of the
+    trailing (workspace, workspace_bytes, stream). The one-product entry has no tag arguments: its base entry's
+    arguments, the sagnn_edge_drop, the sagnn_edge_time."""
+    res, args = SIGNATURES[entry]
+    return res, args[:-3] + [*ahead, POINTER(EdgeTimeArgs)] + args[-3:]
+
+
+SIGNATURES.update({
+    "sagnn_spmm_plan_set_buckets": (c_int, [c_void_p, c_void_p, c_int32]),
+    "sagnn_spmm_time_batch_create": (c_int, [c_void_p, c_void_p, c_int, POINTER(c_void_p)]),
+    "sagnn_spmm_time_f32": _time_form("sagnn_spmm_ex_f32", POINTER(EdgeDropArgs)),
+    "sagnn_gnn_interval_time_f32": _time_form("sagnn_gnn_interval_drop_f32"),
+    "sagnn_gnn_interval_time_bwd_f32": _time_form("sagnn_gnn_interval_drop_bwd_f32"),
+    "sagnn_gnn_stack_time_f32": _time_form("sagnn_gnn_stack_drop_f32"),
+    "sagnn_gnn_stack_time_bwd_f32": _time_form("sagnn_gnn_stack_drop_bwd_f32"),
 })
 
 _lib = None

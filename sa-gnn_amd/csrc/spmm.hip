@@ -31,6 +31,7 @@
 
 #include <algorithm>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "common.h"
@@ -109,6 +110,13 @@ __device__ __forceinline__ float ldf_s(const float* p) {
   return *p;
 #endif
 }
+__device__ __forceinline__ int ldb_s(const uint16_t* p) {
+#ifndef SAGNN_PLAIN_STREAMS
+  return __builtin_nontemporal_load(p);
+#else
+  return *p;
+#endif
+}
 __device__ __forceinline__ void add4(float4& a, const float4& b) {
   a.x += b.x;
   a.y += b.y;
@@ -169,49 +177,66 @@ __device__ __forceinline__ float4 drop_scale(const RowDrop& dr, float4 s) {
   else return s;
 }
 
-// What only a drop kernel is passed comes after the arguments every kernel has, as a pack that is empty for the default
-// kernels (their argument list stays what it was): the row of each long-row chunk and the launch's RowDrop / BatchDrop
-// for the rows and chunks, the scale for the fix-ups, whose partial sums arrive unscaled. A pointer among them is
-// __restrict__ like the pointers ahead of it (KernelArg).
+// Time-aware messages (sagnn_spmm_plan_set_buckets): edge e adds TE[bucket[e], :] to the row it gathers,
+// v = X[col[e]] + TE[bucket[e]], before the accumulation. RowTime is one product's bucket stream and table (rows d
+// apart); BatchTime the 2T segments' bucket pointers, parallel to SegMeta, and the layer's TE base with the element
+// strides of interval and direction.
+struct RowTime {
+  const uint16_t* bucket;
+  const float* te;
+};
+struct BatchTime {
+  const uint16_t* const* buckets;
+  const float* te;
+  int64_t s_k, s_dir;
+};
+__device__ __forceinline__ RowTime seg_time(const BatchTime& t, int seg, int dir, int k) {
+  return RowTime{t.buckets[seg], t.te + (int64_t)k * t.s_k + (int64_t)dir * t.s_dir};
+}
+__device__ __forceinline__ RowTime seg_time(const RowTime& t, int, int, int) { return t; }
+
+// What only some kernels are passed comes after the arguments every kernel has, as a pack that is empty for the default
+// kernels (their argument list stays what it was). The forms are told apart by the TYPES in the pack:
+//   const int32_t*, RowDrop / BatchDrop   the row of each long-row chunk and the launch's drop (the fix-ups take the
+//                                         scale alone: their partial sums arrive unscaled);
+//   const float* / const float* const*    the edge weights of the plan, or for the batched kernels a device table of the
+//                                         2T segments' weight pointers, parallel to SegMeta;
+//   RowTime / BatchTime                   the time term, above.
+// Instantiated: none; (chunk_row, drop); (weights); (chunk_row, drop, weights); (time); (time, weights). A pointer among
+// them is __restrict__ like the pointers ahead of it (KernelArg).
 template <class T>
 struct KernelArg { using type = T; };
 template <class T>
 struct KernelArg<T*> { using type = T* __restrict__; };
-// A weighted launch appends its weights to either form of the pack: the edge weights of the plan (const float*), or for
-// the batched kernels a device table of the 2T segments' weight pointers, parallel to SegMeta (const float* const*).
-// The pack is then: none; (chunk_row, drop); (weights); (chunk_row, drop, weights).
+template <class Want, class... A>
+constexpr bool kHas = (std::is_same_v<Want, A> || ...);
 template <class... A>
 struct Pack {
-  static_assert(sizeof...(A) <= 3, "trailing arguments: none; chunk_row and the drop; the weights; all three");
-  static constexpr bool DROP = sizeof...(A) >= 2;
-  static constexpr bool WEIGHTED = sizeof...(A) == 1 || sizeof...(A) == 3;
+  static constexpr bool DROP = kHas<RowDrop, A...> || kHas<BatchDrop, A...>;
+  static constexpr bool WEIGHTED = kHas<const float*, A...> || kHas<const float* const*, A...>;
+  static constexpr bool TIME = kHas<RowTime, A...> || kHas<BatchTime, A...>;
+  static_assert(DROP == kHas<const int32_t*, A...>, "a drop comes with the rows of the chunks");
+  static_assert(!(DROP && TIME), "there are no drop + time kernels");
+  static_assert(sizeof...(A) == 2 * DROP + WEIGHTED + TIME, "trailing arguments: a drop, weights, a time term");
 };
-template <class Drop>
-__device__ __forceinline__ Drop drop_of() { return Drop{}; }
-template <class Drop, class W>
-__device__ __forceinline__ Drop drop_of(W) { return Drop{}; }
-template <class Drop>
-__device__ __forceinline__ const Drop& drop_of(const int32_t*, const Drop& drop) { return drop; }
-template <class Drop, class W>
-__device__ __forceinline__ const Drop& drop_of(const int32_t*, const Drop& drop, W) { return drop; }
-__device__ __forceinline__ int chunk_row_of(int64_t) { return 0; }
-template <class W>
-__device__ __forceinline__ int chunk_row_of(int64_t, W) { return 0; }
-template <class Drop>
-__device__ __forceinline__ int chunk_row_of(int64_t ci, const int32_t* chunk_row, const Drop&) { return chunk_row[ci]; }
-template <class Drop, class W>
-__device__ __forceinline__ int chunk_row_of(int64_t ci, const int32_t* chunk_row, const Drop&, W) { return chunk_row[ci]; }
+// the pack's argument of type Want, or Want{} when the pack has none
+template <class Want>
+__device__ __forceinline__ Want arg_of() { return Want{}; }
+template <class Want, class A0, class... A>
+__device__ __forceinline__ Want arg_of(A0 a0, A... rest) {
+  if constexpr (std::is_same_v<Want, A0>) return a0;
+  else return arg_of<Want, A...>(rest...);
+}
+template <class... A>
+__device__ __forceinline__ int chunk_row_of(int64_t ci, A... da) {
+  if constexpr (Pack<A...>::DROP) return arg_of<const int32_t*, A...>(da...)[ci];
+  else return 0;
+}
 // the weights of the launch's plan, or of segment `seg` of a batch
-__device__ __forceinline__ const float* weights_of(int) { return nullptr; }
-template <class Drop>
-__device__ __forceinline__ const float* weights_of(int, const int32_t*, const Drop&) { return nullptr; }
-__device__ __forceinline__ const float* weights_of(int, const float* w) { return w; }
-__device__ __forceinline__ const float* weights_of(int seg, const float* const* table) { return table[seg]; }
-template <class Drop>
-__device__ __forceinline__ const float* weights_of(int, const int32_t*, const Drop&, const float* w) { return w; }
-template <class Drop>
-__device__ __forceinline__ const float* weights_of(int seg, const int32_t*, const Drop&, const float* const* table) {
-  return table[seg];
+template <class... A>
+__device__ __forceinline__ const float* weights_of(int seg, A... da) {
+  if constexpr (kHas<const float* const*, A...>) return arg_of<const float* const*, A...>(da...)[seg];
+  else return arg_of<const float*, A...>(da...);
 }
 __device__ __forceinline__ float4 scaled(float4 s) { return s; }
 __device__ __forceinline__ float4 scaled(float4 s, float scale) {
@@ -288,46 +313,62 @@ __global__ void mask_scale_kernel(const float* __restrict__ g, int64_t ldg, int6
 // DROP: the edges belong to row `row`; each lane filters the 64-edge slice it loaded when the slice is taken up, so
 // the load of the next slice still overlaps this slice's gathers.
 // WEIGHTED: edge e counts w[e] times; a slice's weights are requested with its indices and broadcast with them.
-template <int LPR, bool IDENT, bool DROP = false, bool WEIGHTED = false>
+// TIME: edge e gathers TE[bucket[e], :] (rows ldte apart) next to X[idx[e], :]; a slice's buckets travel like its weights, the
+// table row is a plain cached load by the lanes that gather X, and it is added into its X row before the accumulation.
+template <int LPR, bool IDENT, bool DROP = false, bool WEIGHTED = false, bool TIME = false>
 __device__ __forceinline__ float4 wave_row_sum(const int32_t* __restrict__ colidx, int e0, int e1,
                                                const float* __restrict__ X, int64_t ldx,
                                                int lane, int grp, int col, bool lane_on, const RowDrop& dr = RowDrop{},
-                                               int row = 0, const float* __restrict__ w = nullptr) {
-  static_assert(!(IDENT && WEIGHTED), "the fix-up pass adds partial sums that are weighted already");
+                                               int row = 0, const float* __restrict__ w = nullptr,
+                                               const RowTime& tm = RowTime{}, int ldte = 0) {
+  static_assert(!(IDENT && (WEIGHTED || TIME)), "the fix-up pass adds partial sums that carry the weights and the time term already");
   constexpr int G = kWave / LPR;
   constexpr int STEP = G * kUnroll;  // divides 64 for every LPR in {8,16,32,64}
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
   int idx_next = -1;
   float w_next = 0.f;
+  int b_next = 0;
   if (e0 + lane < e1) {
     idx_next = IDENT ? (e0 + lane) : ldi_s(colidx + e0 + lane);
     if constexpr (WEIGHTED) w_next = ldf_s(w + e0 + lane);
+    if constexpr (TIME) b_next = ldb_s(tm.bucket + e0 + lane);
   }
   for (int e = e0; e < e1; e += kWave) {
     const int idx = keep_edge<DROP>(dr, row, idx_next);
     const float wt = w_next;
+    const int bk = b_next;
     const int en = e + kWave;
     idx_next = -1;
     if constexpr (WEIGHTED) w_next = 0.f;
+    if constexpr (TIME) b_next = 0;
     if (en + lane < e1) {
       idx_next = IDENT ? (en + lane) : ldi_s(colidx + en + lane);
       if constexpr (WEIGHTED) w_next = ldf_s(w + en + lane);
+      if constexpr (TIME) b_next = ldb_s(tm.bucket + en + lane);
     }
     const int cnt = min(kWave, e1 - e);
     for (int j = 0; j < cnt; j += STEP) {
       float4 v[kUnroll];
       int c[kUnroll];
       float cw[kUnroll];
+      int cb[kUnroll];
 #pragma unroll
       for (int u = 0; u < kUnroll; ++u) {
         c[u] = __shfl(idx, j + u * G + grp);
         if constexpr (WEIGHTED) cw[u] = __shfl(wt, j + u * G + grp);
         else cw[u] = 1.f;
+        if constexpr (TIME) cb[u] = __shfl(bk, j + u * G + grp);
+        else cb[u] = 0;
       }
 #pragma unroll
       for (int u = 0; u < kUnroll; ++u) {
         v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (c[u] >= 0 && lane_on) v[u] = ld4(X + (int64_t)c[u] * ldx + col);
+      }
+      if constexpr (TIME) {
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u)
+          if (c[u] >= 0 && lane_on) add4(v[u], ld4(tm.te + cb[u] * ldte + col));
       }
 #pragma unroll
       for (int u = 0; u < kUnroll; ++u) acc4<WEIGHTED>(acc, cw[u], v[u]);
@@ -345,11 +386,12 @@ __device__ __forceinline__ float4 wave_row_sum(const int32_t* __restrict__ colid
 
 // A wave's share of the row blocks: RPW consecutive rows starting at row0 (short rows by lane groups, medium rows by
 // the whole wave; long rows belong to the chunk waves + fix-up).
-template <int LPR, int RPW, bool DROP, bool WEIGHTED>
+template <int LPR, int RPW, bool DROP, bool WEIGHTED, bool TIME = false>
 __device__ __forceinline__ void rows_wave(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
                                           const float* __restrict__ X, int64_t ldx, int d, int64_t n_rows, int64_t row0,
                                           int short_t, int long_t, const Epilogue& ep, int lane,
-                                          const RowDrop& dr, const float* __restrict__ w) {
+                                          const RowDrop& dr, const float* __restrict__ w,
+                                          const RowTime& tm = RowTime{}) {
   constexpr int G = kWave / LPR;
   const int grp = lane / LPR;
   const int sub = lane % LPR;
@@ -371,9 +413,11 @@ __device__ __forceinline__ void rows_wave(const int32_t* __restrict__ rowptr, co
   int dg_n = __shfl(deg_l, grp);
   int idx_n = -1;
   float w_n = 0.f;           // WEIGHTED: the weight travels with its index, from the same lane
+  int b_n = 0;               // TIME: so does the bucket
   if (dg_n <= short_t && sub < dg_n) {
     idx_n = ldi_s(colidx + e0_n + sub);
     if constexpr (WEIGHTED) w_n = ldf_s(w + e0_n + sub);
+    if constexpr (TIME) b_n = ldb_s(tm.bucket + e0_n + sub);
   }
 #pragma unroll 1
   for (int it = 0; it < RPW / G; ++it) {
@@ -383,6 +427,7 @@ __device__ __forceinline__ void rows_wave(const int32_t* __restrict__ rowptr, co
     // DROP: the prefetched slice is filtered here, not where it was requested, so its load stays in flight
     int idx = keep_edge<DROP>(dr, (int)row0 + lr, idx_n);
     float wt = w_n;
+    int bk = b_n;
     const bool mine = (lr < nr) && (dg <= short_t);
     const int my_deg = mine ? dg : 0;
     if (it + 1 < RPW / G) {
@@ -390,9 +435,11 @@ __device__ __forceinline__ void rows_wave(const int32_t* __restrict__ rowptr, co
       dg_n = __shfl(deg_l, lr + G);
       idx_n = -1;
       if constexpr (WEIGHTED) w_n = 0.f;
+      if constexpr (TIME) b_n = 0;
       if (dg_n <= short_t && sub < dg_n) {
         idx_n = ldi_s(colidx + e0_n + sub);
         if constexpr (WEIGHTED) w_n = ldf_s(w + e0_n + sub);
+        if constexpr (TIME) b_n = ldb_s(tm.bucket + e0_n + sub);
       }
     }
     int maxdeg = 0;
@@ -407,22 +454,31 @@ __device__ __forceinline__ void rows_wave(const int32_t* __restrict__ rowptr, co
         const int k = eo + sub;
         idx = (k < my_deg) ? keep_edge<DROP>(dr, (int)row0 + lr, ldi_s(colidx + e0 + k)) : -1;
         if constexpr (WEIGHTED) wt = (k < my_deg) ? ldf_s(w + e0 + k) : 0.f;
+        if constexpr (TIME) bk = (k < my_deg) ? ldb_s(tm.bucket + e0 + k) : 0;
       }
       const int lim = min(LPR, maxdeg - eo);
       for (int j = 0; j < lim; j += kUnroll) {
         float4 v[kUnroll];
         int c[kUnroll];
         float cw[kUnroll];
+        int cb[kUnroll];
 #pragma unroll
         for (int u = 0; u < kUnroll; ++u) {
           c[u] = __shfl(idx, grp * LPR + j + u);
           if constexpr (WEIGHTED) cw[u] = __shfl(wt, grp * LPR + j + u);
           else cw[u] = 1.f;
+          if constexpr (TIME) cb[u] = __shfl(bk, grp * LPR + j + u);
+          else cb[u] = 0;
         }
 #pragma unroll
         for (int u = 0; u < kUnroll; ++u) {
           v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
           if (c[u] >= 0 && lane_on) v[u] = ld4(X + (int64_t)c[u] * ldx + col);
+        }
+        if constexpr (TIME) {
+#pragma unroll
+          for (int u = 0; u < kUnroll; ++u)
+            if (c[u] >= 0 && lane_on) add4(v[u], ld4(tm.te + cb[u] * d + col));
         }
 #pragma unroll
         for (int u = 0; u < kUnroll; ++u) acc4<WEIGHTED>(acc, cw[u], v[u]);
@@ -438,20 +494,21 @@ __device__ __forceinline__ void rows_wave(const int32_t* __restrict__ rowptr, co
     const int e0 = __builtin_amdgcn_readlane(rp, lr);
     const int dg = __builtin_amdgcn_readlane(deg_l, lr);
     const float4 s =
-        wave_row_sum<LPR, false, DROP, WEIGHTED>(colidx, e0, e0 + dg, X, ldx, lane, grp, col, lane_on, dr, (int)row0 + lr, w);
+        wave_row_sum<LPR, false, DROP, WEIGHTED, TIME>(colidx, e0, e0 + dg, X, ldx, lane, grp, col, lane_on, dr, (int)row0 + lr, w,
+                                                       tm, d);
     if (grp == 0 && lane_on) finish_row(ep, row0 + lr, col, drop_scale<DROP>(dr, s));
   }
 }
 
 // One launch covers the long-row chunks (first `chunk_blocks` blocks, heaviest work first)
 // and the row blocks (remaining blocks).
-template <int LPR, int RPW, class... DropArgs>   // none; (chunk_row, RowDrop); (weights); (chunk_row, RowDrop, weights)
+template <int LPR, int RPW, class... DropArgs>   // none; (chunk_row, RowDrop); (weights); (chunk_row, RowDrop, weights); (RowTime); (RowTime, weights)
 __global__ __launch_bounds__(kBlock) void spmm_rows_kernel(
     const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
     const float* __restrict__ X, int64_t ldx, int d, int64_t n_rows, int short_t, int long_t,
     const int32_t* __restrict__ chunk_e0, const int32_t* __restrict__ chunk_e1, int64_t n_chunks,
     int chunk_blocks, float* __restrict__ partial, Epilogue ep, typename KernelArg<DropArgs>::type... da) {
-  constexpr bool DROP = Pack<DropArgs...>::DROP, WEIGHTED = Pack<DropArgs...>::WEIGHTED;
+  constexpr bool DROP = Pack<DropArgs...>::DROP, WEIGHTED = Pack<DropArgs...>::WEIGHTED, TIME = Pack<DropArgs...>::TIME;
   const int lane = threadIdx.x & (kWave - 1);
   const int wave = threadIdx.x / kWave;
 
@@ -461,17 +518,18 @@ __global__ __launch_bounds__(kBlock) void spmm_rows_kernel(
     const bool lane_on = col < d;
     const int64_t ci = (int64_t)blockIdx.x * kWavesPerBlock + wave;
     if (ci >= n_chunks) return;
-    const float4 s = wave_row_sum<LPR, false, DROP, WEIGHTED>(colidx, chunk_e0[ci], chunk_e1[ci], X, ldx, lane, grp, col,
-                                                              lane_on, drop_of<RowDrop>(da...), chunk_row_of(ci, da...),
-                                                              weights_of(0, da...));
+    const float4 s = wave_row_sum<LPR, false, DROP, WEIGHTED, TIME>(
+        colidx, chunk_e0[ci], chunk_e1[ci], X, ldx, lane, grp, col, lane_on, arg_of<RowDrop, DropArgs...>(da...),
+        chunk_row_of<DropArgs...>(ci, da...), weights_of<DropArgs...>(0, da...), arg_of<RowTime, DropArgs...>(da...), d);
     if (grp == 0 && lane_on) st4(partial + ci * (int64_t)d + col, s);
     return;
   }
 
   const int64_t row0 = ((int64_t)(blockIdx.x - chunk_blocks) * kWavesPerBlock + wave) * RPW;
   if (row0 >= n_rows) return;
-  rows_wave<LPR, RPW, DROP, WEIGHTED>(rowptr, colidx, X, ldx, d, n_rows, row0, short_t, long_t, ep, lane,
-                                      drop_of<RowDrop>(da...), weights_of(0, da...));
+  rows_wave<LPR, RPW, DROP, WEIGHTED, TIME>(rowptr, colidx, X, ldx, d, n_rows, row0, short_t, long_t, ep, lane,
+                                            arg_of<RowDrop, DropArgs...>(da...), weights_of<DropArgs...>(0, da...),
+                                            arg_of<RowTime, DropArgs...>(da...));
 }
 
 // Fix-up for long rows: add the partial sums of a row in chunk order (a drop launch: and scale the finished sum once),
@@ -535,14 +593,14 @@ __device__ __forceinline__ Epilogue seg_epilogue(const DirArgs& a, int k) {
 
 // A drop launch: a segment's tag and orientation come from its (direction, interval). A weighted launch: a segment's
 // weights come from the table of 2T pointers, indexed like SegMeta.
-template <int LPR, int RPW, class... DropArgs>   // none; (chunk_row, BatchDrop); (weight table); all three
+template <int LPR, int RPW, class... DropArgs>   // none; (chunk_row, BatchDrop); (weight table); all three; (BatchTime); (BatchTime, weight table)
 __global__ __launch_bounds__(kBlock) void spmm_rows_batch_kernel(const SegMeta* __restrict__ meta, BatchGeom g,
                                                                 const int32_t* __restrict__ chunk_e0,
                                                                 const int32_t* __restrict__ chunk_e1,
                                                                 const int32_t* __restrict__ chunk_seg, int64_t n_chunks,
                                                                 float* __restrict__ partial, int d, DirArgs au, DirArgs ai,
                                                                 typename KernelArg<DropArgs>::type... da) {
-  constexpr bool DROP = Pack<DropArgs...>::DROP, WEIGHTED = Pack<DropArgs...>::WEIGHTED;
+  constexpr bool DROP = Pack<DropArgs...>::DROP, WEIGHTED = Pack<DropArgs...>::WEIGHTED, TIME = Pack<DropArgs...>::TIME;
   const int lane = threadIdx.x & (kWave - 1);
   const int wave = threadIdx.x / kWave;
   if ((int)blockIdx.x < g.chunk_blocks) {
@@ -554,10 +612,12 @@ __global__ __launch_bounds__(kBlock) void spmm_rows_batch_kernel(const SegMeta* 
     const int seg = __builtin_amdgcn_readfirstlane(chunk_seg[ci]);
     const int dir = seg >= g.T, k = seg - dir * g.T;
     const DirArgs& a = dir ? ai : au;
-    const float4 s = wave_row_sum<LPR, false, DROP, WEIGHTED>(meta[seg].colidx, chunk_e0[ci], chunk_e1[ci],
-                                                              a.X + (int64_t)k * a.s_X, a.ldx, lane, grp, col, lane_on,
-                                                              seg_drop(drop_of<BatchDrop>(da...), dir, k),
-                                                              chunk_row_of(ci, da...), weights_of(seg, da...));
+    RowTime tm{};
+    if constexpr (TIME) tm = seg_time(arg_of<BatchTime, DropArgs...>(da...), seg, dir, k);
+    const float4 s = wave_row_sum<LPR, false, DROP, WEIGHTED, TIME>(
+        meta[seg].colidx, chunk_e0[ci], chunk_e1[ci], a.X + (int64_t)k * a.s_X, a.ldx, lane, grp, col, lane_on,
+        seg_drop(arg_of<BatchDrop, DropArgs...>(da...), dir, k), chunk_row_of<DropArgs...>(ci, da...),
+        weights_of<DropArgs...>(seg, da...), tm, d);
     if (grp == 0 && lane_on) st4(partial + ci * (int64_t)d + col, s);
     return;
   }
@@ -572,9 +632,11 @@ __global__ __launch_bounds__(kBlock) void spmm_rows_batch_kernel(const SegMeta* 
   const SegMeta m = meta[dir * g.T + k];
   const DirArgs& a = dir ? ai : au;
   const Epilogue ep = seg_epilogue(a, k);
-  rows_wave<LPR, RPW, DROP, WEIGHTED>(m.rowptr, m.colidx, a.X + (int64_t)k * a.s_X, a.ldx, d, n_rows, row0, m.short_t,
-                                      m.long_t, ep, lane, seg_drop(drop_of<BatchDrop>(da...), dir, k),
-                                      weights_of(dir * g.T + k, da...));
+  RowTime tm{};
+  if constexpr (TIME) tm = seg_time(arg_of<BatchTime, DropArgs...>(da...), dir * g.T + k, dir, k);
+  rows_wave<LPR, RPW, DROP, WEIGHTED, TIME>(m.rowptr, m.colidx, a.X + (int64_t)k * a.s_X, a.ldx, d, n_rows, row0, m.short_t,
+                                            m.long_t, ep, lane, seg_drop(arg_of<BatchDrop, DropArgs...>(da...), dir, k),
+                                            weights_of<DropArgs...>(dir * g.T + k, da...), tm);
 }
 
 template <int LPR, class... Scale>
@@ -615,6 +677,8 @@ struct sagnn_spmm_plan {
   const int32_t *d_chunk_e0 = nullptr, *d_chunk_e1 = nullptr, *d_long_row = nullptr,
                 *d_long_slot = nullptr, *d_chunk_row = nullptr;   // chunk_row: read by the drop kernels only
   const float* d_weights = nullptr;   // borrowed, [nnz] in colidx order (sagnn_spmm_plan_set_weights); NULL = unweighted
+  const uint16_t* d_buckets = nullptr;   // borrowed, [nnz] in colidx order (sagnn_spmm_plan_set_buckets); NULL = no time term
+  int32_t n_buckets = 0;
 };
 
 namespace {
@@ -760,6 +824,18 @@ extern "C" int sagnn_spmm_plan_set_weights(sagnn_spmm_plan* plan, const float* d
   return SAGNN_OK;
 }
 
+extern "C" int sagnn_spmm_plan_set_buckets(sagnn_spmm_plan* plan, const uint16_t* d_buckets, int32_t n_buckets) {
+  if (!plan) return sagnn::fail(SAGNN_ERR_NULL, "plan is NULL");
+  if (!plan->info.on_device) return sagnn::fail(SAGNN_ERR_ARG, "plan was built host-only (no device CSR): it takes no buckets");
+  if (d_buckets && (n_buckets < 1 || n_buckets > 65535))
+    return sagnn::fail(SAGNN_ERR_ARG, "buckets: n_buckets = %d, need 1 <= n_buckets <= 65535 (uint16 ids)", n_buckets);
+  if (d_buckets && (reinterpret_cast<uintptr_t>(d_buckets) & 1))
+    return sagnn::fail(SAGNN_ERR_ALIGN, "buckets: pointer must be 2-byte aligned");
+  plan->d_buckets = d_buckets;
+  plan->n_buckets = d_buckets ? n_buckets : 0;
+  return SAGNN_OK;
+}
+
 extern "C" int sagnn_spmm_plan_get_info(const sagnn_spmm_plan* plan, sagnn_spmm_plan_info* info) {
   if (!plan || !info) return sagnn::fail(SAGNN_ERR_NULL, "plan/info is NULL");
   *info = plan->info;
@@ -788,11 +864,12 @@ extern "C" size_t sagnn_spmm_workspace_bytes(const sagnn_spmm_plan* plan, int d)
 // ------------------------------------------------------------------------------------------
 namespace {
 
-// drop = nullptr and a plan without weights: the default kernels. The row block of a wave (small) and the trailing
-// arguments (the drop's, the plan's weights, both or neither) name the instantiation of a kernel; its launch is stated once.
+// drop = nullptr, te = nullptr and a plan without weights: the default kernels. The row block of a wave (small) and the
+// trailing arguments (the drop's, the plan's weights, the time term's) name the instantiation of a kernel; its launch is
+// stated once. te: the product's TE table (the plan's buckets index it); never with a drop.
 template <int LPR>
 int launch_spmm(const sagnn_spmm_plan* p, const float* X, int64_t ldx, int d, const Epilogue& ep,
-                float* partial, hipStream_t stream, const RowDrop* drop = nullptr) {
+                float* partial, hipStream_t stream, const RowDrop* drop = nullptr, const float* te = nullptr) {
   const int64_t n_rows = p->info.n_rows;
   const int64_t n_chunks = p->info.n_chunks;
   const int64_t chunk_blocks = (n_chunks + kWavesPerBlock - 1) / kWavesPerBlock;
@@ -811,7 +888,13 @@ int launch_spmm(const sagnn_spmm_plan* p, const float* X, int64_t ldx, int d, co
                          (int)chunk_blocks, partial, ep, da...);
     };
     const float* w = p->d_weights;
-    if (drop && w)
+    const RowTime tm{p->d_buckets, te};
+    if (te && w)
+      rows(small ? spmm_rows_kernel<LPR, RPW_SMALL, RowTime, const float*> : spmm_rows_kernel<LPR, kRowsPerWave, RowTime, const float*>,
+           tm, w);
+    else if (te)
+      rows(small ? spmm_rows_kernel<LPR, RPW_SMALL, RowTime> : spmm_rows_kernel<LPR, kRowsPerWave, RowTime>, tm);
+    else if (drop && w)
       rows(small ? spmm_rows_kernel<LPR, RPW_SMALL, const int32_t*, RowDrop, const float*>
                  : spmm_rows_kernel<LPR, kRowsPerWave, const int32_t*, RowDrop, const float*>,
            p->d_chunk_row, *drop, w);
@@ -883,9 +966,14 @@ Epilogue kernel_epilogue(const sagnn_spmm_epilogue& e, int d) {
 
 // sagnn_spmm_ex_f32 on the kernels' own epilogue: every per-call check, then the launch(es) of one plan
 int spmm_ex(const sagnn_spmm_plan* plan, const float* X, int64_t ldx, int d, const Epilogue& e, void* workspace,
-            size_t workspace_bytes, void* stream, const RowDrop* drop = nullptr) {
+            size_t workspace_bytes, void* stream, const RowDrop* drop = nullptr, const float* te = nullptr) {
   if (!plan->info.on_device) return sagnn::fail(SAGNN_ERR_ARG, "plan was built host-only (no device CSR)");
   if (int rc = check_d(d)) return rc;
+  if (te) {
+    if (drop) return sagnn::fail(SAGNN_ERR_ARG, "edge time: no product takes a drop and a time term");
+    if (!plan->d_buckets) return sagnn::fail(SAGNN_ERR_ARG, "edge time: the plan has no buckets (sagnn_spmm_plan_set_buckets)");
+    if (!sagnn::aligned16(te)) return sagnn::fail(SAGNN_ERR_ALIGN, "edge time: TE must be 16-byte aligned");
+  }
   if (!e.out && !e.acc_out && !e.out2) return sagnn::fail(SAGNN_ERR_NULL, "no output given");
   if (int rc = check_mat("X", X, ldx, d, plan->info.nnz > 0)) return rc;
   if (int rc = check_mat("residual", e.residual, e.ldr, d, false)) return rc;
@@ -910,10 +998,10 @@ int spmm_ex(const sagnn_spmm_plan* plan, const float* X, int64_t ldx, int d, con
   hipStream_t s = static_cast<hipStream_t>(stream);
   float* partial = static_cast<float*>(workspace);
   switch (sagnn::lanes_per_row(d)) {
-    case 8: return launch_spmm<8>(plan, X, ldx, d, e, partial, s, drop);
-    case 16: return launch_spmm<16>(plan, X, ldx, d, e, partial, s, drop);
-    case 32: return launch_spmm<32>(plan, X, ldx, d, e, partial, s, drop);
-    default: return launch_spmm<64>(plan, X, ldx, d, e, partial, s, drop);
+    case 8: return launch_spmm<8>(plan, X, ldx, d, e, partial, s, drop, te);
+    case 16: return launch_spmm<16>(plan, X, ldx, d, e, partial, s, drop, te);
+    case 32: return launch_spmm<32>(plan, X, ldx, d, e, partial, s, drop, te);
+    default: return launch_spmm<64>(plan, X, ldx, d, e, partial, s, drop, te);
   }
 }
 
@@ -1009,31 +1097,48 @@ struct sagnn_spmm_batch {
   // device: [SegMeta x 2T] and [chunk_e0 | chunk_e1 | chunk_seg | long_row | long_seg | long_slot (+1) | chunk_row]
   SegMeta* d_meta = nullptr;
   const float** d_weights = nullptr;   // [2T] the segments' weight pointers as the plans held them at creation; NULL = unweighted
+  const uint16_t** d_buckets = nullptr;   // [2T] likewise the bucket pointers; NULL = the plans have none
+  int32_t n_buckets = 0;
   int32_t* d_ints = nullptr;
   const int32_t *d_chunk_e0 = nullptr, *d_chunk_e1 = nullptr, *d_chunk_seg = nullptr, *d_long_row = nullptr,
                 *d_long_seg = nullptr, *d_long_slot = nullptr, *d_chunk_row = nullptr;
 };
 
-extern "C" int sagnn_spmm_batch_create(const sagnn_spmm_plan* const* plans_user, const sagnn_spmm_plan* const* plans_item,
-                                       int n_intervals, sagnn_spmm_batch** batch_out) {
+namespace {
+// The tables of a batch; `paired`: the plans of an interval must be a transposed pair (sagnn_spmm_batch_create). The time
+// batch (sagnn_spmm_time_batch_create) gathers from U rows on one side and I rows on the other into n_buckets rows each.
+int batch_create(const sagnn_spmm_plan* const* plans_user, const sagnn_spmm_plan* const* plans_item, int n_intervals,
+                 bool paired, sagnn_spmm_batch** batch_out) {
   if (!batch_out) return sagnn::fail(SAGNN_ERR_NULL, "batch_out is NULL");
   *batch_out = nullptr;
   if (!plans_user || !plans_item) return sagnn::fail(SAGNN_ERR_NULL, "plan table is NULL");
   if (n_intervals < 1 || n_intervals > 4096) return sagnn::fail(SAGNN_ERR_ARG, "n_intervals = %d", n_intervals);
   const int T = n_intervals;
   for (int k = 0; k < T; ++k) {
-    if (int rc = check_interval_plans(plans_user[k], plans_item[k])) return rc;
+    if (paired) {
+      if (int rc = check_interval_plans(plans_user[k], plans_item[k])) return rc;
+    } else {
+      if (!plans_user[k] || !plans_item[k]) return sagnn::fail(SAGNN_ERR_NULL, "plan is NULL");
+      if (plans_user[k]->info.n_rows != plans_item[k]->info.n_rows || plans_user[k]->info.n_src != plans_user[0]->info.n_src ||
+          plans_item[k]->info.n_src != plans_item[0]->info.n_src)
+        return sagnn::fail(SAGNN_ERR_ARG, "interval %d: time-adjoint plans need one bucket count and one source row count per side", k);
+    }
     if (!plans_user[k]->info.on_device || !plans_item[k]->info.on_device)
       return sagnn::fail(SAGNN_ERR_ARG, "interval %d: plan was built host-only", k);
     if (plans_user[k]->info.n_rows != plans_user[0]->info.n_rows || plans_item[k]->info.n_rows != plans_item[0]->info.n_rows)
       return sagnn::fail(SAGNN_ERR_ARG, "interval %d: every interval must have the same user / item counts", k);
   }
   const bool weighted = plans_user[0]->d_weights != nullptr;
+  // a batch carries buckets when all its plans do, with one bucket count; otherwise it has none and the time entries
+  // refuse it (the adjoint batch of a model mixes forward plans with exact adjoints that need no buckets)
+  int32_t n_buckets = plans_user[0]->n_buckets;
   for (int k = 0; k < T; ++k)
-    for (const sagnn_spmm_plan* p : {plans_user[k], plans_item[k]})
+    for (const sagnn_spmm_plan* p : {plans_user[k], plans_item[k]}) {
       if ((p->d_weights != nullptr) != weighted)
         return sagnn::fail(SAGNN_ERR_ARG, "interval %d: some plans of the batch carry edge weights and others do not "
                            "(sagnn_spmm_plan_set_weights): give all 2 T plans weights or none", k);
+      if (p->n_buckets != n_buckets) n_buckets = 0;
+    }
   sagnn_spmm_batch* b = new (std::nothrow) sagnn_spmm_batch();
   if (!b) return sagnn::fail(SAGNN_ERR_NOMEM, "out of host memory");
   b->T = T;
@@ -1041,12 +1146,15 @@ extern "C" int sagnn_spmm_batch_create(const sagnn_spmm_plan* const* plans_user,
   b->I = plans_item[0]->info.n_rows;
   std::vector<SegMeta> meta(2 * (size_t)T);
   std::vector<const float*> wtab(2 * (size_t)T);
+  std::vector<const uint16_t*> btab(2 * (size_t)T);
+  b->n_buckets = n_buckets;
   std::vector<int32_t> ce0, ce1, cseg, crow, lrow, lseg, lslot;
   try {
     for (int s = 0; s < 2 * T; ++s) {
       const sagnn_spmm_plan* p = s < T ? plans_user[s] : plans_item[s - T];
       meta[s] = SegMeta{p->d_rowptr, p->d_colidx, p->info.short_thresh, p->info.long_thresh};
       wtab[s] = p->d_weights;
+      btab[s] = p->d_buckets;
       const int32_t coff = (int32_t)ce0.size();
       ce0.insert(ce0.end(), p->chunk_e0.begin(), p->chunk_e0.end());
       ce1.insert(ce1.end(), p->chunk_e1.begin(), p->chunk_e1.end());
@@ -1076,6 +1184,10 @@ extern "C" int sagnn_spmm_batch_create(const sagnn_spmm_plan* const* plans_user,
     e = hipMalloc((void**)&b->d_weights, wtab.size() * sizeof(const float*));
     if (e == hipSuccess) e = hipMemcpy(b->d_weights, wtab.data(), wtab.size() * sizeof(const float*), hipMemcpyHostToDevice);
   }
+  if (e == hipSuccess && n_buckets > 0) {
+    e = hipMalloc((void**)&b->d_buckets, btab.size() * sizeof(const uint16_t*));
+    if (e == hipSuccess) e = hipMemcpy(b->d_buckets, btab.data(), btab.size() * sizeof(const uint16_t*), hipMemcpyHostToDevice);
+  }
   if (e == hipSuccess && b->n_chunks > 0) {
     const size_t nck = ce0.size(), nl = lrow.size();
     std::vector<int32_t> host;
@@ -1100,6 +1212,7 @@ extern "C" int sagnn_spmm_batch_create(const sagnn_spmm_plan* const* plans_user,
   if (e != hipSuccess) {
     if (b->d_meta) (void)hipFree(b->d_meta);
     if (b->d_weights) (void)hipFree(b->d_weights);
+    if (b->d_buckets) (void)hipFree(b->d_buckets);
     if (b->d_ints) (void)hipFree(b->d_ints);
     delete b;
     return sagnn::hip_fail(e, "batch tables (hipMalloc / hipMemcpy)");
@@ -1107,11 +1220,23 @@ extern "C" int sagnn_spmm_batch_create(const sagnn_spmm_plan* const* plans_user,
   *batch_out = b;
   return SAGNN_OK;
 }
+}  // namespace
+
+extern "C" int sagnn_spmm_batch_create(const sagnn_spmm_plan* const* plans_user, const sagnn_spmm_plan* const* plans_item,
+                                       int n_intervals, sagnn_spmm_batch** batch_out) {
+  return batch_create(plans_user, plans_item, n_intervals, true, batch_out);
+}
+
+extern "C" int sagnn_spmm_time_batch_create(const sagnn_spmm_plan* const* adj_user, const sagnn_spmm_plan* const* adj_item,
+                                            int n_intervals, sagnn_spmm_batch** batch_out) {
+  return batch_create(adj_user, adj_item, n_intervals, false, batch_out);
+}
 
 extern "C" int sagnn_spmm_batch_destroy(sagnn_spmm_batch* b) {
   if (!b) return SAGNN_OK;
   if (b->d_meta) (void)hipFree(b->d_meta);
   if (b->d_weights) (void)hipFree(b->d_weights);
+  if (b->d_buckets) (void)hipFree(b->d_buckets);
   if (b->d_ints) (void)hipFree(b->d_ints);
   delete b;
   return SAGNN_OK;
@@ -1126,7 +1251,7 @@ namespace {
 
 template <int LPR>
 int launch_batch(const sagnn_spmm_batch* b, int d, const DirArgs& au, const DirArgs& ai, float* partial, hipStream_t stream,
-                 const BatchDrop* drop) {
+                 const BatchDrop* drop, const BatchTime* time) {
   constexpr int G = kWave / LPR;
   constexpr int RPW_SMALL = G > 4 ? G : 4;
   const bool small = (b->U > b->I ? b->U : b->I) < kSmallRows;
@@ -1143,7 +1268,12 @@ int launch_batch(const sagnn_spmm_batch* b, int d, const DirArgs& au, const DirA
                          b->d_chunk_seg, b->n_chunks, partial, d, au, ai, da...);
     };
     const float* const* w = b->d_weights;
-    if (drop && w)
+    if (time && w)
+      rows(small ? spmm_rows_batch_kernel<LPR, RPW_SMALL, BatchTime, const float* const*>
+                 : spmm_rows_batch_kernel<LPR, kRowsPerWave, BatchTime, const float* const*>, *time, w);
+    else if (time)
+      rows(small ? spmm_rows_batch_kernel<LPR, RPW_SMALL, BatchTime> : spmm_rows_batch_kernel<LPR, kRowsPerWave, BatchTime>, *time);
+    else if (drop && w)
       rows(small ? spmm_rows_batch_kernel<LPR, RPW_SMALL, const int32_t*, BatchDrop, const float* const*>
                  : spmm_rows_batch_kernel<LPR, kRowsPerWave, const int32_t*, BatchDrop, const float* const*>,
            b->d_chunk_row, *drop, w);
@@ -1173,12 +1303,12 @@ int launch_batch(const sagnn_spmm_batch* b, int d, const DirArgs& au, const DirA
 }
 
 int launch_batch_d(const sagnn_spmm_batch* b, int d, const DirArgs& au, const DirArgs& ai, float* partial, hipStream_t s,
-                   const BatchDrop* drop = nullptr) {
+                   const BatchDrop* drop = nullptr, const BatchTime* time = nullptr) {
   switch (sagnn::lanes_per_row(d)) {
-    case 8: return launch_batch<8>(b, d, au, ai, partial, s, drop);
-    case 16: return launch_batch<16>(b, d, au, ai, partial, s, drop);
-    case 32: return launch_batch<32>(b, d, au, ai, partial, s, drop);
-    default: return launch_batch<64>(b, d, au, ai, partial, s, drop);
+    case 8: return launch_batch<8>(b, d, au, ai, partial, s, drop, time);
+    case 16: return launch_batch<16>(b, d, au, ai, partial, s, drop, time);
+    case 32: return launch_batch<32>(b, d, au, ai, partial, s, drop, time);
+    default: return launch_batch<64>(b, d, au, ai, partial, s, drop, time);
   }
 }
 
@@ -1293,6 +1423,7 @@ DirArgs backward_step(const Stack& st, const Side& self, const Side& other, int 
 // the one whose rows are items. dir 0 = the forward's user-side product A e_i, dir 1 = its item-side product A^T e_u.
 struct LayerTags {
   uint32_t tag_u, tag_i;
+  int layer;              // read by the time forms: which TE[:, l, :] the launch pair adds
 };
 
 // The drivers: `launch(au, ai, tags)` runs one layer, rows = users and rows = items (batched() or per_plan() below;
@@ -1301,13 +1432,18 @@ template <class Launch>
 int run_forward(const Stack& st, Launch launch) {
   for (int l = 0; l < st.n_layers; ++l)
     if (int rc = launch(forward_layer(st, st.u, st.i, l), forward_layer(st, st.i, st.u, l),
-                        LayerTags{(uint32_t)l << 1, (uint32_t)l << 1 | 1u}))
+                        LayerTags{(uint32_t)l << 1, (uint32_t)l << 1 | 1u, l}))
       return rc;
   return SAGNN_OK;
 }
 
-template <class Launch>
-int run_backward(const Stack& st, Launch launch, void* stream) {
+// before_step(l, gm_u, gm_i) runs ahead of step l with the masked gradients g^{l+1} * m^{l+1} of both sides, which are
+// the gradients at the row sums of layer l's two products (the time forms reduce them into dTE[:, l, :]).
+struct NoBeforeStep {
+  int operator()(int, const Slab&, const Slab&) const { return SAGNN_OK; }
+};
+template <class Launch, class BeforeStep = NoBeforeStep>
+int run_backward(const Stack& st, Launch launch, void* stream, BeforeStep before_step = BeforeStep{}) {
   for (const Side* s : {&st.u, &st.i}) {   // seed: g^L * m^L of every interval (one launch per node type)
     const int64_t mrow = st.d / 4;
     if (int rc = launch_mask_scale(s->in, s->mask + (int64_t)(st.n_layers - 1) * s->rows * mrow, st.n_layers * s->rows * mrow,
@@ -1317,10 +1453,13 @@ int run_backward(const Stack& st, Launch launch, void* stream) {
   // Step l's rows = users launch is the adjoint of layer l's ITEM-side product (it carries g_i^{l+1} back to the users
   // through the transpose of the pattern that product gathered through), so it drops with that product's tag (dir 1)
   // on rows that are users; the rows = items launch mirrors it with the user-side tag (dir 0).
-  for (int l = st.n_layers - 1; l >= 0; --l)
+  for (int l = st.n_layers - 1; l >= 0; --l) {
+    const int cur = (st.n_layers - 1 - l) & 1;
+    if (int rc = before_step(l, scratch_slot(st, st.u, 2 + cur), scratch_slot(st, st.i, 2 + cur))) return rc;
     if (int rc = launch(backward_step(st, st.u, st.i, l), backward_step(st, st.i, st.u, l),
-                        LayerTags{(uint32_t)l << 1 | 1u, (uint32_t)l << 1}))
+                        LayerTags{(uint32_t)l << 1 | 1u, (uint32_t)l << 1, l}))
       return rc;
+  }
   return SAGNN_OK;
 }
 
@@ -1358,6 +1497,85 @@ auto per_plan_drop(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan
   };
 }
 
+// ---- the time forms (sagnn_edge_time) ----
+// The caller's sagnn_edge_time, checked ahead of every launch of a time entry; n_buckets: that of the plans / the batch
+int check_time(const sagnn_edge_time* t, const sagnn_edge_drop* drop, int32_t n_buckets, int d) {
+  if (drop) return sagnn::fail(SAGNN_ERR_ARG, "edge time: edge dropout and time do not combine (drop must be NULL)");
+  if (!t || !t->te) return sagnn::fail(SAGNN_ERR_NULL, "edge time: the sagnn_edge_time or its te is NULL");
+  if (n_buckets == 0) return sagnn::fail(SAGNN_ERR_ARG, "edge time: the plans carry no buckets (sagnn_spmm_plan_set_buckets)");
+  if (t->n_buckets != n_buckets)
+    return sagnn::fail(SAGNN_ERR_ARG, "edge time: n_buckets = %d but the plans were given %d", t->n_buckets, n_buckets);
+  if (!sagnn::aligned16(t->te) || ((t->stride_interval | t->stride_layer | t->stride_dir) & 3) || (d & 3))
+    return sagnn::fail(SAGNN_ERR_ALIGN, "edge time: te must be 16-byte aligned and its strides multiples of 4");
+  return SAGNN_OK;
+}
+
+// what the backward entries need on top: where dTE goes and the time-adjoint plans (interval) or batch (stack)
+int check_time_bwd(const sagnn_edge_time* t, bool stack, int64_t U, int64_t I, int T) {
+  if (!t->dte) return sagnn::fail(SAGNN_ERR_NULL, "edge time: dte is NULL");
+  if (!sagnn::aligned16(t->dte)) return sagnn::fail(SAGNN_ERR_ALIGN, "edge time: dte must be 16-byte aligned");
+  if (stack) {
+    const sagnn_spmm_batch* b = t->adj_batch;
+    if (!b) return sagnn::fail(SAGNN_ERR_NULL, "edge time: adj_batch is NULL");
+    if (b->T != T || b->U != t->n_buckets || b->I != t->n_buckets)
+      return sagnn::fail(SAGNN_ERR_ARG, "edge time: adj_batch is not the time batch of %d intervals and %d buckets", T, t->n_buckets);
+    return SAGNN_OK;
+  }
+  if (!t->adj_user || !t->adj_item) return sagnn::fail(SAGNN_ERR_NULL, "edge time: adj_user / adj_item is NULL");
+  if (t->adj_user->info.n_rows != t->n_buckets || t->adj_item->info.n_rows != t->n_buckets || t->adj_user->info.n_src != U ||
+      t->adj_item->info.n_src != I)
+    return sagnn::fail(SAGNN_ERR_ARG, "edge time: adj_user / adj_item are not %d x %lld and %d x %lld", t->n_buckets,
+                       (long long)U, t->n_buckets, (long long)I);
+  return SAGNN_OK;
+}
+
+// per_plan / batched with the time term of layer t.layer; `interval`: the k of a per-plan pair
+auto per_plan_time(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item, int d, void* workspace,
+                   size_t workspace_bytes, void* stream, const sagnn_edge_time& tm, int interval) {
+  return [=](const DirArgs& au, const DirArgs& ai, const LayerTags& t) {
+    const float* te = tm.te + interval * tm.stride_interval + t.layer * tm.stride_layer;
+    if (int rc = spmm_ex(plan_user, au.X, au.ldx, d, au.ep, workspace, workspace_bytes, stream, nullptr, te)) return rc;
+    return spmm_ex(plan_item, ai.X, ai.ldx, d, ai.ep, workspace, workspace_bytes, stream, nullptr, te + tm.stride_dir);
+  };
+}
+
+auto batched_time(const sagnn_spmm_batch* b, int d, void* workspace, void* stream, const sagnn_edge_time& tm) {
+  return [=](const DirArgs& au, const DirArgs& ai, const LayerTags& t) {
+    const BatchTime bt{b->d_buckets, tm.te + t.layer * tm.stride_layer, tm.stride_interval, tm.stride_dir};
+    return launch_batch_d(b, d, au, ai, static_cast<float*>(workspace), static_cast<hipStream_t>(stream), nullptr, &bt);
+  };
+}
+
+// dTE[:, l, dir] = (time adjoint of that product) . gm: a plain product (slope 1, no residual) whose rows are buckets
+DirArgs dte_args(const Slab& gm, float* out, int d, int64_t s_out) {
+  DirArgs a{};
+  a.ep.leaky = 1.f;
+  a.ep.mask_stride = d / 4;
+  a.X = gm.p, a.ldx = gm.ld, a.s_X = gm.slab;
+  a.ep.out = out, a.ep.ldo = d, a.s_out = s_out;
+  return a;
+}
+
+auto dte_per_plan(const sagnn_edge_time& tm, int d, int interval, void* stream) {
+  return [=](int l, const Slab& gm_u, const Slab& gm_i) {
+    float* dte = tm.dte + interval * tm.stride_interval + l * tm.stride_layer;
+    if (int rc = spmm_ex(tm.adj_user, gm_u.p, gm_u.ld, d, dte_args(gm_u, dte, d, 0).ep, tm.adj_workspace,
+                         tm.adj_workspace_bytes, stream))
+      return rc;
+    return spmm_ex(tm.adj_item, gm_i.p, gm_i.ld, d, dte_args(gm_i, dte + tm.stride_dir, d, 0).ep, tm.adj_workspace,
+                   tm.adj_workspace_bytes, stream);
+  };
+}
+
+auto dte_batched(const sagnn_edge_time& tm, int d, void* stream) {
+  return [=](int l, const Slab& gm_u, const Slab& gm_i) {
+    float* dte = tm.dte + l * tm.stride_layer;
+    return launch_batch_d(tm.adj_batch, d, dte_args(gm_u, dte, d, tm.stride_interval),
+                          dte_args(gm_i, dte + tm.stride_dir, d, tm.stride_interval), static_cast<float*>(tm.adj_workspace),
+                          static_cast<hipStream_t>(stream));
+  };
+}
+
 Slab slab(const float* p, int64_t ld, int64_t stride) { return Slab{const_cast<float*>(p), ld, stride}; }
 
 }  // namespace
@@ -1367,7 +1585,8 @@ namespace {
 int interval_forward(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item, const float* u0, int64_t ld_u0,
                      const float* i0, int64_t ld_i0, int d, int n_layers, float leaky, float* scratch_u, float* scratch_i,
                      float* user_out, int64_t ld_uo, float* item_out, int64_t ld_io, uint8_t* mask_u, uint8_t* mask_i,
-                     const sagnn_edge_drop* drop, int interval, void* workspace, size_t workspace_bytes, void* stream) {
+                     const sagnn_edge_drop* drop, int interval, const sagnn_edge_time* time, void* workspace,
+                     size_t workspace_bytes, void* stream) {
   if (int rc = check_interval_plans(plan_user, plan_item)) return rc;
   if (!u0 || !i0 || !user_out || !item_out) return sagnn::fail(SAGNN_ERR_NULL, "null embedding pointer");
   if (n_layers < 1) return sagnn::fail(SAGNN_ERR_ARG, "n_layers = %d: need >= 1", n_layers);
@@ -1381,6 +1600,7 @@ int interval_forward(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* pl
                  {slab(i0, ld_i0, 0), slab(item_out, ld_io, 0), scratch_i, mask_i, plan_item->info.n_rows},
                  1, d, n_layers, leaky};
   if (int rc = check_stack(st, n_layers > 1, "u0", "i0", "user_out", "item_out")) return rc;
+  if (time) return run_forward(st, per_plan_time(plan_user, plan_item, d, workspace, workspace_bytes, stream, *time, interval));
   if (drop)
     return run_forward(st, per_plan_drop(plan_user, plan_item, d, workspace, workspace_bytes, stream, *drop, interval));
   return run_forward(st, per_plan(plan_user, plan_item, d, workspace, workspace_bytes, stream));
@@ -1389,8 +1609,8 @@ int interval_forward(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* pl
 int interval_backward(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item, const float* G_u, int64_t ld_gu,
                       const float* G_i, int64_t ld_gi, int d, int n_layers, float leaky, const uint8_t* mask_u,
                       const uint8_t* mask_i, float* scratch_u, float* scratch_i, float* grad_u0, int64_t ld_du,
-                      float* grad_i0, int64_t ld_di, const sagnn_edge_drop* drop, int interval, void* workspace,
-                      size_t workspace_bytes, void* stream) {
+                      float* grad_i0, int64_t ld_di, const sagnn_edge_drop* drop, int interval, const sagnn_edge_time* time,
+                      void* workspace, size_t workspace_bytes, void* stream) {
   if (int rc = check_interval_plans(plan_user, plan_item)) return rc;
   if (!G_u || !G_i || !grad_u0 || !grad_i0 || !mask_u || !mask_i || !scratch_u || !scratch_i)
     return sagnn::fail(SAGNN_ERR_NULL, "null pointer");
@@ -1400,6 +1620,9 @@ int interval_backward(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* p
                  {slab(G_i, ld_gi, 0), slab(grad_i0, ld_di, 0), scratch_i, const_cast<uint8_t*>(mask_i), plan_item->info.n_rows},
                  1, d, n_layers, leaky};
   if (int rc = check_stack(st, true, "G_u", "G_i", "grad_u0", "grad_i0")) return rc;
+  if (time)   // the adjoint chain does not see the time term: the plain launches, and dTE ahead of each step
+    return run_backward(st, per_plan(plan_user, plan_item, d, workspace, workspace_bytes, stream), stream,
+                        dte_per_plan(*time, d, interval, stream));
   if (drop)
     return run_backward(st, per_plan_drop(plan_user, plan_item, d, workspace, workspace_bytes, stream, *drop, interval),
                         stream);
@@ -1409,7 +1632,8 @@ int interval_backward(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* p
 int stack_forward(const sagnn_spmm_batch* b, const float* u0, int64_t ld_u0, int64_t slab_u0, const float* i0, int64_t ld_i0,
                   int64_t slab_i0, int d, int n_layers, float leaky, float* scratch_u, float* scratch_i, float* user_out,
                   int64_t ld_uo, int64_t slab_uo, float* item_out, int64_t ld_io, int64_t slab_io, uint8_t* mask_u,
-                  uint8_t* mask_i, const sagnn_edge_drop* drop, void* workspace, size_t workspace_bytes, void* stream) {
+                  uint8_t* mask_i, const sagnn_edge_drop* drop, const sagnn_edge_time* time, void* workspace,
+                  size_t workspace_bytes, void* stream) {
   if (!b) return sagnn::fail(SAGNN_ERR_NULL, "batch is NULL");
   if (!u0 || !i0 || !user_out || !item_out) return sagnn::fail(SAGNN_ERR_NULL, "null embedding pointer");
   if (int rc = check_d(d)) return rc;
@@ -1421,6 +1645,7 @@ int stack_forward(const sagnn_spmm_batch* b, const float* u0, int64_t ld_u0, int
                  b->T, d, n_layers, leaky};
   if (int rc = check_stack(st, n_layers > 1, "u0", "i0", "user_out", "item_out")) return rc;
   if (int rc = check_batch_ws(b, d, workspace, workspace_bytes)) return rc;
+  if (time) return run_forward(st, batched_time(b, d, workspace, stream, *time));
   if (drop) return run_forward(st, batched_drop(b, d, workspace, stream, *drop));
   return run_forward(st, batched(b, d, workspace, stream));
 }
@@ -1428,8 +1653,8 @@ int stack_forward(const sagnn_spmm_batch* b, const float* u0, int64_t ld_u0, int
 int stack_backward(const sagnn_spmm_batch* b, const float* G_u, int64_t ld_gu, int64_t slab_gu, const float* G_i,
                    int64_t ld_gi, int64_t slab_gi, int d, int n_layers, float leaky, const uint8_t* mask_u,
                    const uint8_t* mask_i, float* scratch_u, float* scratch_i, float* grad_u0, int64_t ld_du, int64_t slab_du,
-                   float* grad_i0, int64_t ld_di, int64_t slab_di, const sagnn_edge_drop* drop, void* workspace,
-                   size_t workspace_bytes, void* stream) {
+                   float* grad_i0, int64_t ld_di, int64_t slab_di, const sagnn_edge_drop* drop, const sagnn_edge_time* time,
+                   void* workspace, size_t workspace_bytes, void* stream) {
   if (!b) return sagnn::fail(SAGNN_ERR_NULL, "batch is NULL");
   if (!G_u || !G_i || !grad_u0 || !grad_i0 || !mask_u || !mask_i || !scratch_u || !scratch_i)
     return sagnn::fail(SAGNN_ERR_NULL, "null pointer");
@@ -1440,6 +1665,10 @@ int stack_backward(const sagnn_spmm_batch* b, const float* G_u, int64_t ld_gu, i
                  b->T, d, n_layers, leaky};
   if (int rc = check_stack(st, true, "G_u", "G_i", "grad_u0", "grad_i0")) return rc;
   if (int rc = check_batch_ws(b, d, workspace, workspace_bytes)) return rc;
+  if (time) {
+    if (int rc = check_batch_ws(time->adj_batch, d, time->adj_workspace, time->adj_workspace_bytes)) return rc;
+    return run_backward(st, batched(b, d, workspace, stream), stream, dte_batched(*time, d, stream));
+  }
   if (drop) return run_backward(st, batched_drop(b, d, workspace, stream, *drop), stream);
   return run_backward(st, batched(b, d, workspace, stream), stream);
 }
@@ -1452,7 +1681,7 @@ extern "C" int sagnn_gnn_interval_ex_f32(const sagnn_spmm_plan* plan_user, const
                                          int64_t ld_io, uint8_t* mask_u, uint8_t* mask_i, void* workspace,
                                          size_t workspace_bytes, void* stream) {
   return interval_forward(plan_user, plan_item, u0, ld_u0, i0, ld_i0, d, n_layers, leaky, scratch_u, scratch_i, user_out,
-                          ld_uo, item_out, ld_io, mask_u, mask_i, nullptr, 0, workspace, workspace_bytes, stream);
+                          ld_uo, item_out, ld_io, mask_u, mask_i, nullptr, 0, nullptr, workspace, workspace_bytes, stream);
 }
 
 // sagnn_gnn_interval_ex_f32 with edge dropout; `interval` is the k of the tags (this interval's index in the model)
@@ -1464,7 +1693,7 @@ extern "C" int sagnn_gnn_interval_drop_f32(const sagnn_spmm_plan* plan_user, con
                                            size_t workspace_bytes, void* stream) {
   if (int rc = check_drop(drop, n_layers, interval)) return rc;
   return interval_forward(plan_user, plan_item, u0, ld_u0, i0, ld_i0, d, n_layers, leaky, scratch_u, scratch_i, user_out,
-                          ld_uo, item_out, ld_io, mask_u, mask_i, drop, interval, workspace, workspace_bytes, stream);
+                          ld_uo, item_out, ld_io, mask_u, mask_i, drop, interval, nullptr, workspace, workspace_bytes, stream);
 }
 
 extern "C" int sagnn_gnn_interval_f32(const sagnn_spmm_plan* plan_user,
@@ -1486,7 +1715,7 @@ extern "C" int sagnn_gnn_interval_bwd_f32(const sagnn_spmm_plan* plan_user, cons
                                           float* grad_u0, int64_t ld_du, float* grad_i0, int64_t ld_di,
                                           void* workspace, size_t workspace_bytes, void* stream) {
   return interval_backward(plan_user, plan_item, G_u, ld_gu, G_i, ld_gi, d, n_layers, leaky, mask_u, mask_i, scratch_u,
-                           scratch_i, grad_u0, ld_du, grad_i0, ld_di, nullptr, 0, workspace, workspace_bytes, stream);
+                           scratch_i, grad_u0, ld_du, grad_i0, ld_di, nullptr, 0, nullptr, workspace, workspace_bytes, stream);
 }
 
 // Backward of sagnn_gnn_interval_drop_f32: the same sagnn_edge_drop and interval as the forward call.
@@ -1498,7 +1727,7 @@ extern "C" int sagnn_gnn_interval_drop_bwd_f32(const sagnn_spmm_plan* plan_user,
                                                void* workspace, size_t workspace_bytes, void* stream) {
   if (int rc = check_drop(drop, n_layers, interval)) return rc;
   return interval_backward(plan_user, plan_item, G_u, ld_gu, G_i, ld_gi, d, n_layers, leaky, mask_u, mask_i, scratch_u,
-                           scratch_i, grad_u0, ld_du, grad_i0, ld_di, drop, interval, workspace, workspace_bytes, stream);
+                           scratch_i, grad_u0, ld_du, grad_i0, ld_di, drop, interval, nullptr, workspace, workspace_bytes, stream);
 }
 
 // The whole GNN loop of model.py:118-129 — every interval, every layer — in L row launches (+ L fix-up launches when
@@ -1509,7 +1738,7 @@ extern "C" int sagnn_gnn_stack_f32(const sagnn_spmm_batch* b, const float* u0, i
                                    float* item_out, int64_t ld_io, int64_t slab_io, uint8_t* mask_u, uint8_t* mask_i,
                                    void* workspace, size_t workspace_bytes, void* stream) {
   return stack_forward(b, u0, ld_u0, slab_u0, i0, ld_i0, slab_i0, d, n_layers, leaky, scratch_u, scratch_i, user_out, ld_uo,
-                       slab_uo, item_out, ld_io, slab_io, mask_u, mask_i, nullptr, workspace, workspace_bytes, stream);
+                       slab_uo, item_out, ld_io, slab_io, mask_u, mask_i, nullptr, nullptr, workspace, workspace_bytes, stream);
 }
 
 // sagnn_gnn_stack_f32 with edge dropout: interval k of the batch drops with tag interval k.
@@ -1520,7 +1749,7 @@ extern "C" int sagnn_gnn_stack_drop_f32(const sagnn_spmm_batch* b, const float* 
                                         const sagnn_edge_drop* drop, void* workspace, size_t workspace_bytes, void* stream) {
   if (int rc = check_drop(drop, n_layers, b ? b->T - 1 : 0)) return rc;
   return stack_forward(b, u0, ld_u0, slab_u0, i0, ld_i0, slab_i0, d, n_layers, leaky, scratch_u, scratch_i, user_out, ld_uo,
-                       slab_uo, item_out, ld_io, slab_io, mask_u, mask_i, drop, workspace, workspace_bytes, stream);
+                       slab_uo, item_out, ld_io, slab_io, mask_u, mask_i, drop, nullptr, workspace, workspace_bytes, stream);
 }
 
 // Backward of sagnn_gnn_stack_f32 (backward_step above): G_u / G_i are the gradients at the interval outputs as slabs,
@@ -1532,7 +1761,7 @@ extern "C" int sagnn_gnn_stack_bwd_f32(const sagnn_spmm_batch* b, const float* G
                                        float* grad_u0, int64_t ld_du, int64_t slab_du, float* grad_i0, int64_t ld_di,
                                        int64_t slab_di, void* workspace, size_t workspace_bytes, void* stream) {
   return stack_backward(b, G_u, ld_gu, slab_gu, G_i, ld_gi, slab_gi, d, n_layers, leaky, mask_u, mask_i, scratch_u, scratch_i,
-                        grad_u0, ld_du, slab_du, grad_i0, ld_di, slab_di, nullptr, workspace, workspace_bytes, stream);
+                        grad_u0, ld_du, slab_du, grad_i0, ld_di, slab_di, nullptr, nullptr, workspace, workspace_bytes, stream);
 }
 
 // Backward of sagnn_gnn_stack_drop_f32 on the adjoint batch: the same sagnn_edge_drop as the forward call.
@@ -1544,5 +1773,74 @@ extern "C" int sagnn_gnn_stack_drop_bwd_f32(const sagnn_spmm_batch* b, const flo
                                             void* workspace, size_t workspace_bytes, void* stream) {
   if (int rc = check_drop(drop, n_layers, b ? b->T - 1 : 0)) return rc;
   return stack_backward(b, G_u, ld_gu, slab_gu, G_i, ld_gi, slab_gi, d, n_layers, leaky, mask_u, mask_i, scratch_u, scratch_i,
-                        grad_u0, ld_du, slab_du, grad_i0, ld_di, slab_di, drop, workspace, workspace_bytes, stream);
+                        grad_u0, ld_du, slab_du, grad_i0, ld_di, slab_di, drop, nullptr, workspace, workspace_bytes, stream);
+}
+
+// ---- the time entries (include/sagnn.h, "Time-aware messages"): the same bodies with a sagnn_edge_time ----
+extern "C" int sagnn_spmm_time_f32(const sagnn_spmm_plan* plan, const float* X, int64_t ldx, int d,
+                                   const sagnn_spmm_epilogue* e, const sagnn_edge_drop* drop, const sagnn_edge_time* time,
+                                   void* workspace, size_t workspace_bytes, void* stream) {
+  if (!plan || !e) return sagnn::fail(SAGNN_ERR_NULL, "plan/epilogue is NULL");
+  if (int rc = check_time(time, drop, plan->n_buckets, d)) return rc;
+  return spmm_ex(plan, X, ldx, d, kernel_epilogue(*e, d), workspace, workspace_bytes, stream, nullptr, time->te);
+}
+
+extern "C" int sagnn_gnn_interval_time_f32(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item,
+                                           const float* u0, int64_t ld_u0, const float* i0, int64_t ld_i0, int d,
+                                           int n_layers, float leaky, float* scratch_u, float* scratch_i, float* user_out,
+                                           int64_t ld_uo, float* item_out, int64_t ld_io, uint8_t* mask_u, uint8_t* mask_i,
+                                           const sagnn_edge_drop* drop, int interval, const sagnn_edge_time* time,
+                                           void* workspace, size_t workspace_bytes, void* stream) {
+  if (!plan_user || !plan_item) return sagnn::fail(SAGNN_ERR_NULL, "plan is NULL");
+  if (plan_user->n_buckets != plan_item->n_buckets)
+    return sagnn::fail(SAGNN_ERR_ARG, "edge time: the two plans carry different bucket counts (or only one carries buckets)");
+  if (int rc = check_time(time, drop, plan_user->n_buckets, d)) return rc;
+  if (interval < 0) return sagnn::fail(SAGNN_ERR_ARG, "edge time: interval = %d", interval);
+  return interval_forward(plan_user, plan_item, u0, ld_u0, i0, ld_i0, d, n_layers, leaky, scratch_u, scratch_i, user_out,
+                          ld_uo, item_out, ld_io, mask_u, mask_i, nullptr, interval, time, workspace, workspace_bytes, stream);
+}
+
+// plan_user / plan_item: the adjoint plans, as sagnn_gnn_interval_bwd_f32 takes them (they need no buckets: the chain
+// does not see the time term); the buckets are in time->adj_user / adj_item.
+extern "C" int sagnn_gnn_interval_time_bwd_f32(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item,
+                                               const float* G_u, int64_t ld_gu, const float* G_i, int64_t ld_gi, int d,
+                                               int n_layers, float leaky, const uint8_t* mask_u, const uint8_t* mask_i,
+                                               float* scratch_u, float* scratch_i, float* grad_u0, int64_t ld_du,
+                                               float* grad_i0, int64_t ld_di, const sagnn_edge_drop* drop, int interval,
+                                               const sagnn_edge_time* time, void* workspace, size_t workspace_bytes,
+                                               void* stream) {
+  if (!plan_user || !plan_item) return sagnn::fail(SAGNN_ERR_NULL, "plan is NULL");
+  if (int rc = check_time(time, drop, time ? time->n_buckets : 0, d)) return rc;
+  if (interval < 0) return sagnn::fail(SAGNN_ERR_ARG, "edge time: interval = %d", interval);
+  if (int rc = check_time_bwd(time, false, plan_user->info.n_rows, plan_item->info.n_rows, 1)) return rc;
+  return interval_backward(plan_user, plan_item, G_u, ld_gu, G_i, ld_gi, d, n_layers, leaky, mask_u, mask_i, scratch_u,
+                           scratch_i, grad_u0, ld_du, grad_i0, ld_di, nullptr, interval, time, workspace, workspace_bytes,
+                           stream);
+}
+
+extern "C" int sagnn_gnn_stack_time_f32(const sagnn_spmm_batch* b, const float* u0, int64_t ld_u0, int64_t slab_u0,
+                                        const float* i0, int64_t ld_i0, int64_t slab_i0, int d, int n_layers, float leaky,
+                                        float* scratch_u, float* scratch_i, float* user_out, int64_t ld_uo, int64_t slab_uo,
+                                        float* item_out, int64_t ld_io, int64_t slab_io, uint8_t* mask_u, uint8_t* mask_i,
+                                        const sagnn_edge_drop* drop, const sagnn_edge_time* time, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
+  if (!b) return sagnn::fail(SAGNN_ERR_NULL, "batch is NULL");
+  if (int rc = check_time(time, drop, b->n_buckets, d)) return rc;
+  return stack_forward(b, u0, ld_u0, slab_u0, i0, ld_i0, slab_i0, d, n_layers, leaky, scratch_u, scratch_i, user_out, ld_uo,
+                       slab_uo, item_out, ld_io, slab_io, mask_u, mask_i, nullptr, time, workspace, workspace_bytes, stream);
+}
+
+// b: the batch of the adjoint patterns, as sagnn_gnn_stack_bwd_f32 takes it; the buckets are in time->adj_batch.
+extern "C" int sagnn_gnn_stack_time_bwd_f32(const sagnn_spmm_batch* b, const float* G_u, int64_t ld_gu, int64_t slab_gu,
+                                            const float* G_i, int64_t ld_gi, int64_t slab_gi, int d, int n_layers,
+                                            float leaky, const uint8_t* mask_u, const uint8_t* mask_i, float* scratch_u,
+                                            float* scratch_i, float* grad_u0, int64_t ld_du, int64_t slab_du,
+                                            float* grad_i0, int64_t ld_di, int64_t slab_di, const sagnn_edge_drop* drop,
+                                            const sagnn_edge_time* time, void* workspace, size_t workspace_bytes,
+                                            void* stream) {
+  if (!b) return sagnn::fail(SAGNN_ERR_NULL, "batch is NULL");
+  if (int rc = check_time(time, drop, time ? time->n_buckets : 0, d)) return rc;
+  if (int rc = check_time_bwd(time, true, b->U, b->I, b->T)) return rc;
+  return stack_backward(b, G_u, ld_gu, slab_gu, G_i, ld_gi, slab_gi, d, n_layers, leaky, mask_u, mask_i, scratch_u, scratch_i,
+                        grad_u0, ld_du, slab_du, grad_i0, ld_di, slab_di, nullptr, time, workspace, workspace_bytes, stream);
 }

@@ -24,6 +24,7 @@ from .graph import NORMS, interval_pair
 
 
 SEQ_ATT = ("sum", "full")      # --seqAtt: the reference's collapsed head, or attention over every sequence item
+EDGE_TIME = ("none", "slot")   # --edgeTime: the reference's graph, or messages that add their edge's time-bucket row
 PRED_LOSS = ("hinge", "softmax")   # --predLoss: the reference's sampled hinge loss, or softmax over the whole catalogue
 
 
@@ -318,6 +319,15 @@ class Recommender:
             return batch, None
         return [a.plan for a in self.subAdj], [a.plan for a in self.subTpAdj]
 
+    def time_tables(self):
+        """TE [T, L, 2, M, d] = timeEmbed @ W of every messagePropagate call, in the registration order of the weights
+        (interval, layer, user call, item call), as ONE batched matmul; None under --edgeTime none or
+        without GNN layers. Differentiable: dTE reaches timeEmbed and the 2 T L weights through torch."""
+        T, L, d = args.graphNum, args.gnn_layer, args.latdim
+        if args.edgeTime != "slot" or L == 0:
+            return None
+        return torch.matmul(self.timeEmbed, torch.stack(self.time_weights).view(T, L, 2, d, d))
+
     def propagate_intervals(self, intervals=None):
         """reference model.py:118-134: for every interval k the L-layer stack with residuals and
         add_n, written straight into [N, T, d] slabs (no stack/transpose pass). `intervals`
@@ -327,6 +337,8 @@ class Recommender:
             self.user_vector_tensor = torch.empty((args.user, T, d), dtype=torch.float32, device=self.device)
             self.item_vector_tensor = torch.empty((args.item, T, d), dtype=torch.float32, device=self.device)
         batch = self._interval_batch() if (intervals is None and L > 0) else None
+        te = self.time_tables()
+        te = None if te is None else te.detach()
         if batch is not None:
             # every interval in one launch per layer (sagnn_gnn_stack_f32): the reference's loop over k is independent
             # per interval, and on dataset-sized graphs its 2 T L SpMMs are bound by their launches
@@ -335,7 +347,7 @@ class Recommender:
                 self._scratch_bi = torch.empty((2, T, args.item, d), dtype=torch.float32, device=self.device)
             ops.gnn_stack(batch, self.uEmbed.detach(), self.iEmbed.detach(), L, NNs.leaky,
                           self.user_vector_tensor.permute(1, 0, 2), self.item_vector_tensor.permute(1, 0, 2),
-                          self._scratch_bu, self._scratch_bi)
+                          self._scratch_bu, self._scratch_bi, time=te)
             return self.user_vector_tensor, self.item_vector_tensor
         if L > 1 and self._scratch_u is None:
             self._scratch_u = torch.empty((2, args.user, d), dtype=torch.float32, device=self.device)
@@ -348,7 +360,7 @@ class Recommender:
             ops.gnn_interval(self.subAdj[k].plan, self.subTpAdj[k].plan, self.uEmbed[k].detach(),
                              self.iEmbed[k].detach(), L, NNs.leaky,
                              self.user_vector_tensor[:, k, :], self.item_vector_tensor[:, k, :],
-                             self._scratch_u, self._scratch_i)
+                             self._scratch_u, self._scratch_i, time=None if te is None else te[k])
         return self.user_vector_tensor, self.item_vector_tensor
 
     def fuse_intervals(self, user_vector_tensor, item_vector_tensor):
@@ -372,9 +384,9 @@ class Recommender:
         self.iEmbed = NNs.defineParam("iEmbed", [T, args.item, d], reg=True)
         self.posEmbed = NNs.defineParam("posEmbed", [args.pos_length, d], reg=True)
         self.timeEmbed = NNs.defineParam("timeEmbed", [self.maxTime + 1, d], reg=True)
-        # one dead [d, d] weight per messagePropagate call: 2*T*L of them (model.py:81, :122-123)
-        for _ in range(2 * T * args.gnn_layer):
-            NNs.defineRandomNameParam([d, d], reg=True)
+        # one [d, d] weight per messagePropagate call: 2*T*L of them (model.py:81, :122-123), in the order (interval,
+        # layer, user call, item call). Dead in the reference and under --edgeTime none; --edgeTime slot reads them
+        self.time_weights = [NNs.defineRandomNameParam([d, d], reg=True) for _ in range(2 * T * args.gnn_layer)]
         self._define_fusion_params()
         self._define_head_params()
         self._define_ssl_params()
@@ -749,7 +761,9 @@ class Recommender:
         # one autograd node for the whole interval loop; uv / iv are [T, N, d] slabs written in place
         edge_keep = args.edgeKeepRate if edge_keep is None else edge_keep
         edge_drop = ops.EdgeDrop(*batch.get("edge_seed", (0, 0)), edge_keep) if edge_keep < 1.0 else None
-        uv, iv = ag.gnn_stack(self.uEmbed, self.iEmbed, *self._stack_plans(), L, leaky, drop=edge_drop)
+        if edge_drop is not None and args.edgeTime != "none":
+            raise ValueError("an edge keep rate below 1 does not combine with --edgeTime slot")
+        uv, iv = ag.gnn_stack(self.uEmbed, self.iEmbed, *self._stack_plans(), L, leaky, drop=edge_drop, TE=self.time_tables())
         finals = []
         if subset:        # the one read-back of the step: the two counts, copied while the stack's launches queue
             touched["done"].synchronize()
@@ -1085,10 +1099,16 @@ class Recommender:
         with open(os.path.join(directory, "History", args.save_path + ".his"), "wb") as fs:
             pickle.dump(self.metrics, fs)
         state = {"params": {k: v.detach().cpu() for k, v in NNs.params.items()}, "adjNorm": args.adjNorm,
-                 "seqAtt": args.seqAtt}
+                 "seqAtt": args.seqAtt, "edgeTime": self._edge_time_state()}
         if getattr(self, "optimizer", None) is not None:
             state["optimizer"] = self.optimizer.state_dict()
         torch.save(state, os.path.join(directory, "Models", args.save_path))
+
+    def _edge_time_state(self) -> dict:
+        """What a checkpoint records of --edgeTime: the flag and, under slot, what fixes every edge's bucket."""
+        if args.edgeTime == "none":
+            return {"mode": "none"}
+        return {"mode": args.edgeTime, "slot": float(args.slot), "mi": int(self.handler.timeMin), "M": int(self.maxTime) + 1}
 
     def loadModel(self, directory="."):
         """reference model.py:522-526. The variable set and every shape must match the model that
@@ -1104,6 +1124,10 @@ class Recommender:
         if stored_att != args.seqAtt:
             raise ValueError(f"checkpoint was trained with --seqAtt {stored_att}, this run has --seqAtt {args.seqAtt}: "
                              "the head's attention is part of the model")
+        stored_time = state.get("edgeTime", {"mode": "none"})      # a checkpoint from before --edgeTime has no time term
+        if stored_time != self._edge_time_state():
+            raise ValueError(f"checkpoint was trained with --edgeTime {stored_time}, this run has {self._edge_time_state()}: "
+                             "the time term, --slot, the earliest timestamp and the table size are part of the model")
         saved = state["params"]
         if set(saved) != set(NNs.params):
             raise KeyError(f"checkpoint variables differ from the model's: missing {sorted(set(NNs.params) - set(saved))[:4]}, "
@@ -1133,6 +1157,16 @@ class Recommender:
             raise ValueError(f"--seqAtt {args.seqAtt}: one of {SEQ_ATT}")
         if args.predLoss not in PRED_LOSS:
             raise ValueError(f"--predLoss {args.predLoss}: one of {PRED_LOSS}")
+        if args.edgeTime not in EDGE_TIME:
+            raise ValueError(f"--edgeTime {args.edgeTime}: one of {EDGE_TIME}")
+        time = None
+        if args.edgeTime == "slot":
+            if args.edgeKeepRate < 1.0:
+                raise ValueError("--edgeTime slot does not combine with --edgeKeepRate < 1: the bucket-sorted reduction of "
+                                 "the time tables' gradient cannot evaluate the (user, item)-keyed drop")
+            # (a handler prepared before the flag was set has not run it yet)
+            self.handler.timeMin, self.handler.maxTime = self.handler.timeProcess(self.handler.subMat)
+            time = (self.handler.timeMin, args.slot, ops.check_n_buckets(self.handler.maxTime + 1))
         if not args.softmaxTemp > 0.0 or not np.isfinite(args.softmaxTemp):
             raise ValueError(f"--softmaxTemp {args.softmaxTemp}: need a finite temperature > 0")
         if args.predLoss == "softmax":
@@ -1150,7 +1184,7 @@ class Recommender:
         self.actFunc = "leakyRelu"
         self.subAdj, self.subTpAdj = [], []
         for i in range(args.graphNum):
-            adj, tp = interval_pair(self.handler.subMat[i], self.device, norm=args.adjNorm)
+            adj, tp = interval_pair(self.handler.subMat[i], self.device, norm=args.adjNorm, time=time)
             self.subAdj.append(adj)
             self.subTpAdj.append(tp)
         self.maxTime = self.handler.maxTime

@@ -86,6 +86,45 @@ def _check_weights(weights, nnz: int) -> torch.Tensor:
     return w
 
 
+MAX_BUCKETS = 65535      # bucket ids travel as uint16
+
+
+def check_n_buckets(n_buckets: int) -> int:
+    """The size M of a time table: 1 <= M <= 65535, refused otherwise with the flag that shrinks it."""
+    n_buckets = int(n_buckets)
+    if not 1 <= n_buckets <= MAX_BUCKETS:
+        raise ValueError(f"edge time: {n_buckets} time buckets, the bucket ids are uint16 and the table holds at most "
+                         f"{MAX_BUCKETS} rows: choose a larger --slot (days per bucket)")
+    return n_buckets
+
+
+def _check_buckets(buckets, n_buckets: int, nnz: int) -> torch.Tensor:
+    """The bucket ids of a plan as a host uint16 tensor: nnz values < n_buckets (TypeError / ValueError otherwise)."""
+    n_buckets = check_n_buckets(n_buckets)
+    b = np.asarray(buckets.detach().cpu().numpy() if isinstance(buckets, torch.Tensor) else buckets)
+    if b.dtype != np.uint16:
+        raise TypeError(f"buckets must be uint16, got {b.dtype}")
+    if b.ndim != 1 or b.size != nnz:
+        raise ValueError(f"buckets: expected {nnz} values (one per stored edge, in colidx order), got shape {b.shape}")
+    if b.size and int(b.max()) >= n_buckets:
+        raise ValueError(f"buckets: id {int(b.max())} outside [0, {n_buckets})")
+    return torch.from_numpy(np.ascontiguousarray(b))
+
+
+def time_adjoint_arrays(rowptr, buckets, n_buckets: int, weights=None):
+    """The "time adjoint" of a pattern with bucket ids: the CSR whose rows are buckets and whose column indices are the
+    ROW of each edge, in stable bucket order (edge order kept within a bucket), the weights permuted alongside.
+    dTE = (this pattern) . gm. Returns (rowptr int32 [n_buckets + 1], colidx int32 [nnz], weights or None)."""
+    rowptr = np.asarray(rowptr, dtype=np.int64)
+    b = np.asarray(buckets, dtype=np.int64)
+    rows = np.repeat(np.arange(rowptr.size - 1, dtype=np.int32), np.diff(rowptr))
+    order = np.argsort(b, kind="stable")
+    rp = np.zeros(int(n_buckets) + 1, dtype=np.int64)
+    np.cumsum(np.bincount(b, minlength=int(n_buckets)), out=rp[1:])
+    w = None if weights is None else np.ascontiguousarray(np.asarray(weights, dtype=np.float32)[order])
+    return rp.astype(np.int32), np.ascontiguousarray(rows[order]), w
+
+
 class SpmmPlan:
     """Degree-class plan for one CSR adjacency (sagnn_spmm_plan_*). Owns the device CSR copies.
 
@@ -96,10 +135,16 @@ class SpmmPlan:
     order, numpy or torch: every product on this plan then sums w[e] * X[colidx[e]] (sagnn_spmm_plan_set_weights,
     DESIGN.md §17). They are checked on the host; the plan keeps the device copy alive. For a correct backward pass
     the adjoint plan must carry the same weight for the same (user, item): graph.interval_pair(norm="sym") builds
-    such pairs."""
+    such pairs.
+
+    buckets / n_buckets: None, or nnz uint16 bucket ids in colidx order, each < n_buckets <= 65535 (checked on the host):
+    the time entries (spmm_time, gnn_interval / gnn_stack with time=) then add TE[bucket[e]] to what edge e gathers
+    (sagnn_spmm_plan_set_buckets). The entries without time ignore them. `time_adjoint` is the plan of
+    the dTE reduction, built on first use."""
 
     def __init__(self, rowptr, colidx, n_rows: int, n_src: int, device=None,
-                 tuning: tuple[int, int, int] | None = None, validate: bool = True, weights=None):
+                 tuning: tuple[int, int, int] | None = None, validate: bool = True, weights=None, buckets=None,
+                 n_buckets: int | None = None):
         lib = _lib.load()
         self._lib = lib
         self._h = ctypes.c_void_p()
@@ -114,6 +159,11 @@ class SpmmPlan:
         w_t = None if weights is None else _check_weights(weights, self.nnz)
         if w_t is not None and device is None:
             raise ValueError("weights: a host-only plan (device=None) takes no weights")
+        if (buckets is None) != (n_buckets is None):
+            raise ValueError("buckets: give buckets and n_buckets together")
+        b_t = None if buckets is None else _check_buckets(buckets, n_buckets, self.nnz)
+        if b_t is not None and device is None:
+            raise ValueError("buckets: a host-only plan (device=None) takes no buckets")
         rp_h = rp_t.cpu().contiguous()
         self._rowptr_host = rp_h.numpy()
         if validate:
@@ -150,6 +200,28 @@ class SpmmPlan:
                 self.weights = torch.zeros(1, dtype=torch.float32, device=device)
             check(lib.sagnn_spmm_plan_set_weights(self._h, self.weights.data_ptr()))
             check(lib.sagnn_spmm_plan_get_info(self._h, ctypes.byref(info)))
+        self.buckets, self.n_buckets = None, 0
+        self._tuning = tuning
+        self._time_adjoint: SpmmPlan | None = None
+        if b_t is not None:
+            self._buckets_host = b_t.numpy()
+            self._weights_host = None if w_t is None else w_t.numpy()
+            self.n_buckets = int(n_buckets)
+            self.buckets = b_t.to(device).contiguous()
+            if self.buckets.numel() == 0:
+                self.buckets = torch.zeros(1, dtype=torch.uint16, device=device)
+            check(lib.sagnn_spmm_plan_set_buckets(self._h, self.buckets.data_ptr(), self.n_buckets))
+
+    @property
+    def time_adjoint(self) -> "SpmmPlan":
+        """The plan of this product's dTE reduction (time_adjoint_arrays), built on the first backward."""
+        if self.buckets is None:
+            raise ValueError("time_adjoint: the plan has no buckets")
+        if self._time_adjoint is None:
+            rp, ci, w = time_adjoint_arrays(self._rowptr_host, self._buckets_host, self.n_buckets, self._weights_host)
+            self._time_adjoint = SpmmPlan(rp, ci, self.n_buckets, self.n_rows, device=self.device, tuning=self._tuning,
+                                          validate=False, weights=w)
+        return self._time_adjoint
 
     @property
     def weighted(self) -> bool:
@@ -221,7 +293,7 @@ def _call(lib, entry: str, args: tuple, drop_args: tuple, ws):
 
 def spmm_ex(plan: SpmmPlan, x: torch.Tensor | None, leaky: float, residual=None, out=None, acc_in=None, acc_out=None,
             acc_in2=None, mask_out=None, mask_in=None, out2=None, slope2: float = 1.0, want_out: bool = False,
-            _drop=None):
+            _drop=None, _time=None):
     """sagnn_spmm_ex_f32: spmm plus the training epilogue — mask_out [rows, d/4] uint8 records the activation slopes,
     out2 = v * (mask_in bit ? 1 : slope2) with v the accumulated value if acc_out is given, acc_in2 a second addend."""
     ref = next(t_ for t_ in (x, residual, out, acc_out, out2) if t_ is not None)
@@ -246,8 +318,12 @@ def spmm_ex(plan: SpmmPlan, x: torch.Tensor | None, leaky: float, residual=None,
     if _drop is not None:       # spmm_drop
         drop, tag, rows_are_users = _drop
         drop_args = (ctypes.byref(drop.struct()), tag, int(rows_are_users))
-    _call(plan._lib, "sagnn_spmm_ex_f32" if _drop is None else "sagnn_spmm_drop_f32",
-          (plan.handle, _ptr(x), ldx, d, ctypes.byref(e)), drop_args, ws)
+    entry = "sagnn_spmm_ex_f32" if _drop is None else "sagnn_spmm_drop_f32"
+    if _time is not None:       # spmm_time
+        et = _EdgeTime(_te_table("te", _time.view(1, 1, *_time.shape) if _time.dim() == 2 else _time, (1, 1),
+                                 plan.n_buckets, d), plan.n_buckets, stack=False)
+        entry, drop_args = "sagnn_spmm_time_f32", et.tail()
+    _call(plan._lib, entry, (plan.handle, _ptr(x), ldx, d, ctypes.byref(e)), drop_args, ws)
     return out
 
 
@@ -296,6 +372,59 @@ def spmm_drop(plan: SpmmPlan, x: torch.Tensor | None, leaky: float, drop: EdgeDr
                    _drop=(drop, int(tag), bool(rows_are_users)))
 
 
+def _te_table(name: str, te: torch.Tensor, lead: tuple, n_buckets: int, d: int) -> torch.Tensor:
+    if te.dtype != torch.float32 or not te.is_cuda or tuple(te.shape) != (*lead, n_buckets, d) or not te.is_contiguous():
+        raise ValueError(f"{name}: expected a contiguous float32 device tensor {[*lead, n_buckets, d]}, got "
+                         f"{tuple(te.shape)} {te.dtype} on {te.device}")
+    return te
+
+
+def _need_buckets(what: str, n_buckets: int) -> int:
+    if not n_buckets:
+        raise ValueError(f"{what}: a time table was given but the plans carry no buckets (SpmmPlan(..., buckets=, n_buckets=))")
+    return n_buckets
+
+
+class _EdgeTime:
+    """The sagnn_edge_time of one call: TE [..., L, 2, M, d] (an interval entry: [L, 2, M, d] of its interval, `interval`
+    0) and, for a backward entry, dTE with the time-adjoint plans or batch. Keeps what it points to alive."""
+
+    def __init__(self, te: torch.Tensor, n_buckets: int, stack: bool, dte: torch.Tensor | None = None, adj=None, d: int = 0):
+        a = _lib.EdgeTimeArgs()
+        a.te, a.n_buckets = te.data_ptr(), int(n_buckets)
+        a.stride_dir = te.stride(-3)
+        a.stride_layer = te.stride(-4)
+        a.stride_interval = te.stride(0) if stack else 0
+        self.keep = [te, dte, adj]
+        if dte is not None:
+            a.dte = dte.data_ptr()
+            if stack:
+                a.adj_batch = adj.handle
+                ws = adj.workspace(d)
+            else:
+                a.adj_user, a.adj_item = adj[0].handle, adj[1].handle
+                ws = _interval_ws(adj[0], adj[1], d)
+            self.keep.append(ws)
+            a.adj_workspace, a.adj_workspace_bytes = _ptr(ws), 0 if ws is None else ws.numel() * 4
+        self.args = a
+
+    def tail(self, *selectors):
+        """What a time entry takes after its base entry's arguments: a NULL sagnn_edge_drop, the drop form's selectors,
+        the sagnn_edge_time."""
+        return (None, *selectors, ctypes.byref(self.args))
+
+
+def spmm_time(plan: SpmmPlan, x: torch.Tensor | None, leaky: float, te: torch.Tensor, residual=None, out=None, acc_in=None,
+              acc_out=None, acc_in2=None, mask_out=None, mask_in=None, out2=None, slope2: float = 1.0,
+              want_out: bool = False):
+    """sagnn_spmm_time_f32: spmm_ex with the time term — edge e gathers x[colidx[e]] + te[bucket[e]]; te [n_buckets, d]
+    float32, the plan built with buckets."""
+    if plan.buckets is None:
+        raise ValueError("spmm_time: the plan has no buckets (SpmmPlan(..., buckets=, n_buckets=))")
+    return spmm_ex(plan, x, leaky, residual, out, acc_in, acc_out, acc_in2, mask_out, mask_in, out2, slope2, want_out,
+                   _time=te)
+
+
 def mask_scale(g: torch.Tensor, mask: torch.Tensor, slope: float, out: torch.Tensor):
     """out = g * (mask bit ? 1 : slope) (sagnn_mask_scale_f32); g / out [rows, d] views, mask [rows, d/4] uint8."""
     rows, d = int(g.shape[0]), int(g.shape[1])
@@ -341,16 +470,32 @@ def _adjoint_pair(plan_user: SpmmPlan, plan_item: SpmmPlan):
     return plan_user, plan_item
 
 
+def _time_or_drop(stem: str, base: str, drop, selectors: tuple, et):
+    """(entry name, what follows the base entry's arguments) of a stack call: the base entry, its drop form (`drop`), or
+    its time form (`et`, an _EdgeTime or False). A time form takes its selectors with interval 0: the TE it is given is
+    that of its own interval."""
+    bwd = "bwd_" if "bwd" in base else ""
+    if et:
+        if drop is not None:
+            raise ValueError("edge dropout and time do not combine: give `drop` or `time`, not both")
+        return f"{stem}_time_{bwd}f32", et.tail(*(0 for _ in selectors))
+    if drop is None:
+        return f"{stem}_{base}", ()
+    return f"{stem}_drop_{bwd}f32", (ctypes.byref(drop.struct()), *selectors)
+
+
 def gnn_interval(plan_user: SpmmPlan, plan_item: SpmmPlan, u0: torch.Tensor, i0: torch.Tensor,
                  n_layers: int, leaky: float, user_out: torch.Tensor, item_out: torch.Tensor,
                  scratch_u: torch.Tensor | None = None, scratch_i: torch.Tensor | None = None,
                  mask_u: torch.Tensor | None = None, mask_i: torch.Tensor | None = None,
-                 drop: EdgeDrop | None = None, interval: int = 0):
+                 drop: EdgeDrop | None = None, interval: int = 0, time: torch.Tensor | None = None):
     """One interval of the GNN loop (reference model.py:118-129): sagnn_gnn_interval_[ex_]f32; with `drop`, edge
     dropout under the tags of interval `interval` (sagnn_gnn_interval_drop_f32).
     user_out / item_out are [rows, d] views (any row stride, e.g. a column of an [N, T, d] slab).
     mask_u [L, U, d/4] / mask_i [L, I, d/4] uint8 (both or neither) record the activation masks
-    the backward pass needs."""
+    the backward pass needs.
+    time: TE [L, 2, M, d] of this interval (layer, direction: 0 = the user-side product, 1 = the item-side one), the
+    plans built with buckets (sagnn_gnn_interval_time_f32); not with `drop`."""
     d = int(u0.shape[1])
     U, I = plan_user.n_rows, plan_item.n_rows
     ld_u0 = _f32_rows("u0", u0, d, U)
@@ -365,10 +510,13 @@ def gnn_interval(plan_user: SpmmPlan, plan_item: SpmmPlan, u0: torch.Tensor, i0:
     if mask_i is not None:
         _masks("mask_i", mask_i, (n_layers, I, d // 4))
     ws = _interval_ws(plan_user, plan_item, d)
-    _call(plan_user._lib, "sagnn_gnn_interval_ex_f32" if drop is None else "sagnn_gnn_interval_drop_f32",
+    entry, tail = _time_or_drop("sagnn_gnn_interval", "ex_f32", drop, (int(interval),), time is not None and _EdgeTime(
+        _te_table("time", time, (n_layers, 2), _need_buckets("gnn_interval", plan_user.n_buckets), d), plan_user.n_buckets,
+        stack=False))
+    _call(plan_user._lib, entry,
           (plan_user.handle, plan_item.handle, _ptr(u0), ld_u0, _ptr(i0), ld_i0, d, int(n_layers), float(leaky),
            _ptr(scratch_u), _ptr(scratch_i), _ptr(user_out), ld_uo, _ptr(item_out), ld_io, _ptr(mask_u), _ptr(mask_i)),
-          () if drop is None else (ctypes.byref(drop.struct()), int(interval)), ws)
+          tail, ws)
     return user_out, item_out
 
 
@@ -376,12 +524,20 @@ def gnn_interval_bwd(plan_user: SpmmPlan, plan_item: SpmmPlan, grad_user_out: to
                      grad_item_out: torch.Tensor, n_layers: int, leaky: float, mask_u: torch.Tensor,
                      mask_i: torch.Tensor, grad_u0: torch.Tensor | None = None,
                      grad_i0: torch.Tensor | None = None, scratch_u: torch.Tensor | None = None,
-                     scratch_i: torch.Tensor | None = None, drop: EdgeDrop | None = None, interval: int = 0):
+                     scratch_i: torch.Tensor | None = None, drop: EdgeDrop | None = None, interval: int = 0,
+                     time: torch.Tensor | None = None, grad_time: torch.Tensor | None = None):
     """Backward of gnn_interval (sagnn_gnn_interval_bwd_f32): dL/d(user_out), dL/d(item_out) and the
     recorded masks -> dL/d u0 [U, d], dL/d i0 [I, d]. `drop` / `interval`: those of the forward call
-    (sagnn_gnn_interval_drop_bwd_f32)."""
+    (sagnn_gnn_interval_drop_bwd_f32). `time`: the TE [L, 2, M, d] of the forward call; dTE is written to grad_time (same
+    shape) through the forward plans' time adjoints (sagnn_gnn_interval_time_bwd_f32)."""
     d = int(grad_user_out.shape[1])
     U, I = plan_user.n_rows, plan_item.n_rows
+    et = False
+    if time is not None:
+        M = _need_buckets("gnn_interval_bwd", plan_user.n_buckets)
+        et = _EdgeTime(_te_table("time", time, (n_layers, 2), M, d), M, stack=False,
+                       dte=_te_table("grad_time", grad_time, (n_layers, 2), M, d),
+                       adj=(plan_user.time_adjoint, plan_item.time_adjoint), d=d)
     plan_user, plan_item = _adjoint_pair(plan_user, plan_item)
     ld_gu = _f32_rows("grad_user_out", grad_user_out, d, U)
     ld_gi = _f32_rows("grad_item_out", grad_item_out, d, I)
@@ -397,11 +553,11 @@ def gnn_interval_bwd(plan_user: SpmmPlan, plan_item: SpmmPlan, grad_user_out: to
     _masks("mask_u", mask_u, (n_layers, U, d // 4))
     _masks("mask_i", mask_i, (n_layers, I, d // 4))
     ws = _interval_ws(plan_user, plan_item, d)
-    _call(plan_user._lib, "sagnn_gnn_interval_bwd_f32" if drop is None else "sagnn_gnn_interval_drop_bwd_f32",
+    entry, tail = _time_or_drop("sagnn_gnn_interval", "bwd_f32", drop, (int(interval),), et)
+    _call(plan_user._lib, entry,
           (plan_user.handle, plan_item.handle, _ptr(grad_user_out), ld_gu, _ptr(grad_item_out), ld_gi, d, int(n_layers),
            float(leaky), _ptr(mask_u), _ptr(mask_i), _ptr(scratch_u), _ptr(scratch_i), _ptr(grad_u0), ld_du, _ptr(grad_i0),
-           ld_di),
-          () if drop is None else (ctypes.byref(drop.struct()), int(interval)), ws)
+           ld_di), tail, ws)
     return grad_u0, grad_i0
 
 
@@ -411,20 +567,25 @@ class SpmmBatch:
     plans alive. `adjoint()` is the batch the backward pass runs on (the same one unless a matrix holds duplicated
     stored entries, graph.interval_pair)."""
 
-    def __init__(self, plans_user, plans_item):
+    def __init__(self, plans_user, plans_item, _time_batch: bool = False):
         if len(plans_user) != len(plans_item) or not plans_user:
             raise ValueError("one user-side and one item-side plan per interval")
         self.plans_user, self.plans_item = list(plans_user), list(plans_item)
         self.weighted = self.plans_user[0].weighted
         if any(p.weighted != self.weighted for p in self.plans_user + self.plans_item):
             raise ValueError("SpmmBatch: some plans carry edge weights and others do not; give all 2 T plans weights or none")
+        # buckets: all 2 T plans with one bucket count, or the batch has none (the time entries then refuse it)
+        counts = {p.n_buckets for p in self.plans_user + self.plans_item}
+        self.n_buckets = counts.pop() if len(counts) == 1 else 0
         self.T, self.U, self.I = len(plans_user), plans_user[0].n_rows, plans_item[0].n_rows
         self.device = plans_user[0].device
         self._lib = _lib.load()
         self._h = ctypes.c_void_p()
         PU = (ctypes.c_void_p * self.T)(*[p.handle for p in self.plans_user])
         PI = (ctypes.c_void_p * self.T)(*[p.handle for p in self.plans_item])
-        check(self._lib.sagnn_spmm_batch_create(PU, PI, self.T, ctypes.byref(self._h)))
+        create = self._lib.sagnn_spmm_time_batch_create if _time_batch else self._lib.sagnn_spmm_batch_create
+        check(create(PU, PI, self.T, ctypes.byref(self._h)))
+        self._time_adjoint: SpmmBatch | None = None
         self.nnz = sum(p.nnz for p in self.plans_user) + sum(p.nnz for p in self.plans_item)
         self._ws: dict[int, torch.Tensor] = {}
         self._adjoint: SpmmBatch | None = None
@@ -449,6 +610,17 @@ class SpmmBatch:
             self._ws[d] = ws
         return ws
 
+    @property
+    def time_adjoint(self) -> "SpmmBatch":
+        """The 2 T time-adjoint plans as one batch (sagnn_spmm_time_batch_create): the dTE reduction of a layer is one
+        launch. Built on the first backward."""
+        if not self.n_buckets:
+            raise ValueError("time_adjoint: the batch's plans have no buckets")
+        if self._time_adjoint is None:
+            self._time_adjoint = SpmmBatch([p.time_adjoint for p in self.plans_user],
+                                           [p.time_adjoint for p in self.plans_item], _time_batch=True)
+        return self._time_adjoint
+
     def adjoint(self) -> "SpmmBatch":
         pairs = [_adjoint_pair(pu, pi) for pu, pi in zip(self.plans_user, self.plans_item)]
         if all(adj_u is pu for (adj_u, _), pu in zip(pairs, self.plans_user)):
@@ -472,11 +644,12 @@ def _slab(name: str, x: torch.Tensor, T: int, rows: int, d: int):
 def gnn_stack(batch: SpmmBatch, u0: torch.Tensor, i0: torch.Tensor, n_layers: int, leaky: float,
               user_out: torch.Tensor, item_out: torch.Tensor, scratch_u: torch.Tensor | None = None,
               scratch_i: torch.Tensor | None = None, mask_u: torch.Tensor | None = None, mask_i: torch.Tensor | None = None,
-              drop: EdgeDrop | None = None):
+              drop: EdgeDrop | None = None, time: torch.Tensor | None = None):
     """Every interval of the GNN loop (reference model.py:118-129) in one launch per layer: sagnn_gnn_stack_f32; with
     `drop`, edge dropout (sagnn_gnn_stack_drop_f32).
     u0 [T, U, d], i0 [T, I, d]; user_out / item_out indexed [T, N, d] (e.g. `x.permute(1, 0, 2)` of the [N, T, d]
-    tensor the fusion reads); mask_u [T, L, U, d/4] / mask_i [T, L, I, d/4] uint8 for training."""
+    tensor the fusion reads); mask_u [T, L, U, d/4] / mask_i [T, L, I, d/4] uint8 for training.
+    time: TE [T, L, 2, M, d], the batch's plans built with buckets (sagnn_gnn_stack_time_f32); not with `drop`."""
     T, U, I = batch.T, batch.U, batch.I
     d = int(u0.shape[2])
     ld_u0, sl_u0 = _slab("u0", u0, T, U, d)
@@ -491,23 +664,32 @@ def gnn_stack(batch: SpmmBatch, u0: torch.Tensor, i0: torch.Tensor, n_layers: in
     if mask_i is not None:
         _masks("mask_i", mask_i, (T, n_layers, I, d // 4))
     ws = batch.workspace(d)
-    _call(batch._lib, "sagnn_gnn_stack_f32" if drop is None else "sagnn_gnn_stack_drop_f32",
+    entry, tail = _time_or_drop("sagnn_gnn_stack", "f32", drop, (), time is not None and _EdgeTime(
+        _te_table("time", time, (T, n_layers, 2), _need_buckets("gnn_stack", batch.n_buckets), d), batch.n_buckets,
+        stack=True))
+    _call(batch._lib, entry,
           (batch.handle, _ptr(u0), ld_u0, sl_u0, _ptr(i0), ld_i0, sl_i0, d, int(n_layers), float(leaky), _ptr(scratch_u),
            _ptr(scratch_i), _ptr(user_out), ld_uo, sl_uo, _ptr(item_out), ld_io, sl_io, _ptr(mask_u), _ptr(mask_i)),
-          () if drop is None else (ctypes.byref(drop.struct()),), ws)
+          tail, ws)
     return user_out, item_out
 
 
 def gnn_stack_bwd(batch: SpmmBatch, grad_user_out: torch.Tensor, grad_item_out: torch.Tensor, n_layers: int, leaky: float,
                   mask_u: torch.Tensor, mask_i: torch.Tensor, grad_u0: torch.Tensor, grad_i0: torch.Tensor,
                   scratch_u: torch.Tensor | None = None, scratch_i: torch.Tensor | None = None,
-                  drop: EdgeDrop | None = None):
+                  drop: EdgeDrop | None = None, time: torch.Tensor | None = None, grad_time: torch.Tensor | None = None):
     """Backward of gnn_stack (sagnn_gnn_stack_bwd_f32) on the batch's adjoint patterns: gradients at the interval
     outputs [T, N, d] (any strides) -> dL/d u0 [T, U, d], dL/d i0 [T, I, d]. `drop`: that of the forward call
-    (sagnn_gnn_stack_drop_bwd_f32)."""
+    (sagnn_gnn_stack_drop_bwd_f32). `time`: the TE [T, L, 2, M, d] of the forward call; dTE is written to grad_time (same
+    shape) through the batch's time adjoint, one launch per layer (sagnn_gnn_stack_time_bwd_f32)."""
     adj = batch.adjoint()
     T, U, I = batch.T, batch.U, batch.I
     d = int(grad_user_out.shape[2])
+    et = False
+    if time is not None:
+        M = _need_buckets("gnn_stack_bwd", batch.n_buckets)
+        et = _EdgeTime(_te_table("time", time, (T, n_layers, 2), M, d), M, stack=True,
+                       dte=_te_table("grad_time", grad_time, (T, n_layers, 2), M, d), adj=batch.time_adjoint, d=d)
     ld_gu, sl_gu = _slab("grad_user_out", grad_user_out, T, U, d)
     ld_gi, sl_gi = _slab("grad_item_out", grad_item_out, T, I, d)
     ld_du, sl_du = _slab("grad_u0", grad_u0, T, U, d)
@@ -518,11 +700,11 @@ def gnn_stack_bwd(batch: SpmmBatch, grad_user_out: torch.Tensor, grad_item_out: 
     _masks("mask_u", mask_u, (T, n_layers, U, d // 4))
     _masks("mask_i", mask_i, (T, n_layers, I, d // 4))
     ws = adj.workspace(d)
-    _call(adj._lib, "sagnn_gnn_stack_bwd_f32" if drop is None else "sagnn_gnn_stack_drop_bwd_f32",
+    entry, tail = _time_or_drop("sagnn_gnn_stack", "bwd_f32", drop, (), et)
+    _call(adj._lib, entry,
           (adj.handle, _ptr(grad_user_out), ld_gu, sl_gu, _ptr(grad_item_out), ld_gi, sl_gi, d, int(n_layers), float(leaky),
            _ptr(mask_u), _ptr(mask_i), _ptr(scratch_u), _ptr(scratch_i), _ptr(grad_u0), ld_du, sl_du, _ptr(grad_i0), ld_di,
-           sl_di),
-          () if drop is None else (ctypes.byref(drop.struct()),), ws)
+           sl_di), tail, ws)
     return grad_u0, grad_i0
 
 

@@ -56,6 +56,9 @@ class IntervalSharding:
         if getattr(args, "adjNorm", "none") != "none":
             # the runners build row slices of unweighted plans (csr_row_slice): they would run unnormalised
             raise ValueError(f"--adjNorm {args.adjNorm} is not supported by the interval-parallel path")
+        if getattr(args, "edgeTime", "none") != "none":
+            # the runners' row slices carry no buckets: they would run without the time term
+            raise ValueError(f"--edgeTime {args.edgeTime} is not supported by the interval-parallel path")
         self.T, self.world, self.rank = int(n_intervals), int(world), int(rank)
         self.rounds = -(-self.T // self.world)            # all-to-all calls every rank takes part in
 
