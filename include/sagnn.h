@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define SAGNN_VERSION 10302 /* 1.3.0 */
+#define SAGNN_VERSION 10400 /* 1.4.0 */
 
 enum {
   SAGNN_OK = 0,
@@ -211,88 +211,28 @@ int sagnn_mask_scale_f32(const float* g, int64_t ldg, const uint8_t* mask, float
                          int64_t n_rows, int d, void* stream);
 
 /* ------------------------------------------------------------------------------------
- * sagnn_gnn_interval_f32 — one iteration k of the loop model.py:118-129 (L layers, both
- * directions, simultaneous update, residuals, add_n), 2*L SpMM launches issued from C.
- *
- *   e_u^0 = u0, e_i^0 = i0
- *   e_u^{l+1} = leaky(A   e_i^l) + e_u^l        plan_user: rows = users, cols = items
- *   e_i^{l+1} = leaky(A^T e_u^l) + e_i^l        plan_item: rows = items, cols = users
- *   user_out = sum_{l=0..L} e_u^l ;  item_out = sum_{l=0..L} e_i^l
- *
- * scratch_u: [2, U, d] floats, scratch_i: [2, I, d] floats (ping-pong layer outputs; may be
- * NULL when n_layers <= 1). user_out/item_out are written with row strides ld_uo/ld_io so
- * the caller can target row k of an [N, T, d] slab directly (replaces tf.stack +
- * tf.transpose, model.py:131-134).
- * -------------------------------------------------------------------------------- */
-int sagnn_gnn_interval_f32(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item,
-                           const float* u0, int64_t ld_u0, const float* i0, int64_t ld_i0,
-                           int d, int n_layers, float leaky, float* scratch_u, float* scratch_i,
-                           float* user_out, int64_t ld_uo, float* item_out, int64_t ld_io,
-                           void* workspace, size_t workspace_bytes, void* stream);
-
-/* Training form of sagnn_gnn_interval_f32: additionally records the activation masks of every
- * layer, mask_u [n_layers, U, d/4] and mask_i [n_layers, I, d/4] bytes (both or neither). */
-int sagnn_gnn_interval_ex_f32(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item,
-                              const float* u0, int64_t ld_u0, const float* i0, int64_t ld_i0, int d,
-                              int n_layers, float leaky, float* scratch_u, float* scratch_i,
-                              float* user_out, int64_t ld_uo, float* item_out, int64_t ld_io,
-                              uint8_t* mask_u, uint8_t* mask_i, void* workspace,
-                              size_t workspace_bytes, void* stream);
-
-/* Backward of the interval stack (what tf.gradients builds for model.py:118-129): given
- * G_u = dL/d user_out, G_i = dL/d item_out and the recorded masks, writes dL/d u0 and dL/d i0.
- * Same SpMM kernel with the roles of the two adjacencies swapped (the reference already holds
- * both, model.py:234-236). scratch_u: [4, U, d] floats, scratch_i: [4, I, d] floats.
- * ADJOINT CONTRACT: plan_user (rows = users) must be the exact transpose, multiplicities included,
- * of the item-side pattern the forward pass used, and plan_item that of the user-side pattern.
- * For matrices without duplicated stored entries these are the forward plans themselves; with
- * duplicates (forward counts one twice, DataHandler.transpose merges it: DataHandler.py:9-11) the
- * caller passes plans of the exact transposes — the library cannot tell the two cases apart from
- * the handles, so the host side checks it (sa-gnn_amd/graph.py interval_pair, ops._adjoint_pair). */
-int sagnn_gnn_interval_bwd_f32(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item,
-                               const float* G_u, int64_t ld_gu, const float* G_i, int64_t ld_gi, int d,
-                               int n_layers, float leaky, const uint8_t* mask_u, const uint8_t* mask_i,
-                               float* scratch_u, float* scratch_i, float* grad_u0, int64_t ld_du,
-                               float* grad_i0, int64_t ld_di, void* workspace, size_t workspace_bytes,
-                               void* stream);
-
-/* ------------------------------------------------------------------------------------
- * The WHOLE loop over k of model.py:118-129 in one launch per layer. The reference's loop body is independent per
- * interval, so a layer of the stack is 2 T independent SpMMs (T with rows = users, T with rows = items); on
- * dataset-sized graphs (tens of thousands of rows) each is a launch of a few microseconds and the stack is bound by
- * its 2 T L launches (+ as many fix-ups). A batch object ties the T interval plans together: a block of the batched
- * kernel finds (direction, interval, row block) by division, every per-interval operand is a SLAB — interval k's
- * [N, d] matrix starts `slab` elements after interval k-1's, rows `ld` apart — so u0 [T, U, d] is (ld = d,
- * slab = U d) and a column of the [N, T, d] tensor the fusion reads is (ld = T d, slab = d). One row launch and (if
- * any interval has long rows) ONE fix-up launch per layer: Amazon-shaped T = 5, L = 3: 60 launches -> 6.
+ * Batch over the T intervals. The loop body of model.py:118-129 is independent per interval, so a layer of the stack
+ * is 2 T independent SpMMs (T with rows = users, T with rows = items); on dataset-sized graphs (tens of thousands of
+ * rows) each is a launch of a few microseconds and the stack is bound by its 2 T L launches (+ as many fix-ups). A
+ * batch object ties the T interval plans together: a block of the batched kernel finds (direction, interval, row block)
+ * by division, every per-interval operand is a SLAB — interval k's [N, d] matrix starts `slab` elements after interval
+ * k-1's, rows `ld` apart — so u0 [T, U, d] is (ld = d, slab = U d) and a column of the [N, T, d] tensor the fusion reads
+ * is (ld = T d, slab = d). One row launch and (if any interval has long rows) ONE fix-up launch per layer:
+ * Amazon-shaped T = 5, L = 3: 60 launches -> 6.
  *
  * sagnn_spmm_batch_create keeps the plans' device CSR pointers: the plans must outlive the batch. Every interval must
  * have the same user / item counts. Workspace: sagnn_spmm_batch_workspace_bytes (partial sums of all long-row chunks).
- * sagnn_gnn_stack_f32: sagnn_gnn_interval_ex_f32 for all intervals; scratch_u [2, T, U, d], scratch_i [2, T, I, d]
- *   (NULL when n_layers <= 1); mask_u [T, n_layers, U, d/4] / mask_i [T, n_layers, I, d/4] bytes (both or neither).
- * sagnn_gnn_stack_bwd_f32: sagnn_gnn_interval_bwd_f32 for all intervals; scratch_u [4, T, U, d], scratch_i [4, T, I, d];
- *   `batch` must tie the ADJOINT plans (the adjoint contract above, per interval).
  * -------------------------------------------------------------------------------- */
 typedef struct sagnn_spmm_batch sagnn_spmm_batch;
 int sagnn_spmm_batch_create(const sagnn_spmm_plan* const* plans_user, const sagnn_spmm_plan* const* plans_item,
                             int n_intervals, sagnn_spmm_batch** batch_out);
 int sagnn_spmm_batch_destroy(sagnn_spmm_batch* batch);
 size_t sagnn_spmm_batch_workspace_bytes(const sagnn_spmm_batch* batch, int d);
-int sagnn_gnn_stack_f32(const sagnn_spmm_batch* batch, const float* u0, int64_t ld_u0, int64_t slab_u0,
-                        const float* i0, int64_t ld_i0, int64_t slab_i0, int d, int n_layers, float leaky,
-                        float* scratch_u, float* scratch_i, float* user_out, int64_t ld_uo, int64_t slab_uo,
-                        float* item_out, int64_t ld_io, int64_t slab_io, uint8_t* mask_u, uint8_t* mask_i,
-                        void* workspace, size_t workspace_bytes, void* stream);
-int sagnn_gnn_stack_bwd_f32(const sagnn_spmm_batch* batch, const float* G_u, int64_t ld_gu, int64_t slab_gu,
-                            const float* G_i, int64_t ld_gi, int64_t slab_gi, int d, int n_layers, float leaky,
-                            const uint8_t* mask_u, const uint8_t* mask_i, float* scratch_u, float* scratch_i,
-                            float* grad_u0, int64_t ld_du, int64_t slab_du, float* grad_i0, int64_t ld_di,
-                            int64_t slab_di, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Edge dropout of the interval graphs (opt-in, training only; not in the reference, whose edgeDropout rewrites edge
- * VALUES that messagePropagate never reads: model.py:93-102 vs :84-86). The drop forms below run the same kernels
- * with one more step: the lane that loads an edge's column index decides whether the edge takes part.
+ * VALUES that messagePropagate never reads: model.py:93-102 vs :84-86). The same kernels with one more step: the lane
+ * that loads an edge's column index decides whether the edge takes part.
  *
  *   keep(edge) = word 0 of Philox4x32-10(key = seed (low word first), counter = (user id, item id, tag, step))
  *                < keep_threshold
@@ -303,12 +243,12 @@ int sagnn_gnn_stack_bwd_f32(const sagnn_spmm_batch* batch, const float* G_u, int
  * The decision depends on the edge's (user id, item id) only: not on its position in a CSR, not on the plan that
  * stores it, not on the degree class that processes it. Duplicated stored entries share one decision. Hence the masked
  * pattern of a product and the masked pattern of its exact transpose are transposes of each other, and the ADJOINT
- * CONTRACT above carries over: the backward of layer l's user-side product runs on rows = items with the USER-side
+ * CONTRACT (below) carries over: the backward of layer l's user-side product runs on rows = items with the USER-side
  * tag, the backward of the item-side product on rows = users with the item-side tag (the stack entries do this).
  * keep_threshold = min(floor(keep * 2^32), 2^32 - 1) and scale = 1 / keep are computed by the host, once. Draws of
  * different (k, l, dir, step) are independent. No atomics: a row's result is a deterministic function of its inputs.
  *
- * Every drop entry checks the sagnn_edge_drop before anything else: NULL, keep_threshold = 0, scale not finite or
+ * An entry that drops checks the sagnn_edge_drop before anything else: NULL, keep_threshold = 0, scale not finite or
  * <= 0, n_layers > 127, an interval index >= 2^23 are refused with no device work done.
  * -------------------------------------------------------------------------------- */
 typedef struct sagnn_edge_drop {
@@ -324,31 +264,6 @@ typedef struct sagnn_edge_drop {
 int sagnn_spmm_drop_f32(const sagnn_spmm_plan* plan, const float* X, int64_t ldx, int d,
                         const sagnn_spmm_epilogue* epilogue, const sagnn_edge_drop* drop, uint32_t tag,
                         int rows_are_users, void* workspace, size_t workspace_bytes, void* stream);
-/* sagnn_gnn_interval_ex_f32 / _bwd_f32 with edge dropout; `interval` is the k of the tags. The backward takes the
- * sagnn_edge_drop and interval of its forward call, and the adjoint plans as sagnn_gnn_interval_bwd_f32 does. */
-int sagnn_gnn_interval_drop_f32(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item, const float* u0,
-                                int64_t ld_u0, const float* i0, int64_t ld_i0, int d, int n_layers, float leaky,
-                                float* scratch_u, float* scratch_i, float* user_out, int64_t ld_uo, float* item_out,
-                                int64_t ld_io, uint8_t* mask_u, uint8_t* mask_i, const sagnn_edge_drop* drop,
-                                int interval, void* workspace, size_t workspace_bytes, void* stream);
-int sagnn_gnn_interval_drop_bwd_f32(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item,
-                                    const float* G_u, int64_t ld_gu, const float* G_i, int64_t ld_gi, int d,
-                                    int n_layers, float leaky, const uint8_t* mask_u, const uint8_t* mask_i,
-                                    float* scratch_u, float* scratch_i, float* grad_u0, int64_t ld_du, float* grad_i0,
-                                    int64_t ld_di, const sagnn_edge_drop* drop, int interval, void* workspace,
-                                    size_t workspace_bytes, void* stream);
-/* sagnn_gnn_stack_f32 / _bwd_f32 with edge dropout: interval k of the batch drops with tag interval k. */
-int sagnn_gnn_stack_drop_f32(const sagnn_spmm_batch* batch, const float* u0, int64_t ld_u0, int64_t slab_u0,
-                             const float* i0, int64_t ld_i0, int64_t slab_i0, int d, int n_layers, float leaky,
-                             float* scratch_u, float* scratch_i, float* user_out, int64_t ld_uo, int64_t slab_uo,
-                             float* item_out, int64_t ld_io, int64_t slab_io, uint8_t* mask_u, uint8_t* mask_i,
-                             const sagnn_edge_drop* drop, void* workspace, size_t workspace_bytes, void* stream);
-int sagnn_gnn_stack_drop_bwd_f32(const sagnn_spmm_batch* batch, const float* G_u, int64_t ld_gu, int64_t slab_gu,
-                                 const float* G_i, int64_t ld_gi, int64_t slab_gi, int d, int n_layers, float leaky,
-                                 const uint8_t* mask_u, const uint8_t* mask_i, float* scratch_u, float* scratch_i,
-                                 float* grad_u0, int64_t ld_du, int64_t slab_du, float* grad_i0, int64_t ld_di,
-                                 int64_t slab_di, const sagnn_edge_drop* drop, void* workspace, size_t workspace_bytes,
-                                 void* stream);
 
 /* --------------------------------------------------------------------------------
  * Time-aware messages (the term the reference comments out at model.py:86). Every stored edge of a plan
@@ -358,7 +273,7 @@ int sagnn_gnn_stack_drop_bwd_f32(const sagnn_spmm_batch* batch, const float* G_u
  *   s[r,:] = sum over the edges e of row r of  w[e] * ( X[col[e],:] + TE[k,l,dir][bucket[e],:] )     (w = 1: unweighted)
  *
  * then the epilogue of sagnn_spmm_ex_f32. X + TE is rounded once, then accumulated as the plan's kernels accumulate.
- * The gradient into X is that of the entry without time; the backward entries add
+ * The gradient into X is that of the product without time; the backward entries add
  *
  *   dTE[k,l,dir][b,:] = sum over the edges e with bucket[e] = b of  w[e] * gm[row[e],:]
  *
@@ -366,8 +281,8 @@ int sagnn_gnn_stack_drop_bwd_f32(const sagnn_spmm_batch* batch, const float* G_u
  * the caller builds (n_rows = n_buckets, n_src = the product's row count, colidx = the row of each edge in stable
  * bucket order, the weights permuted alongside). No atomics: dTE is a deterministic function of its inputs.
  *
- * A time entry refuses (SAGNN_ERR_ARG, before any launch) a plan or batch without buckets, a bucket count that differs
- * from time->n_buckets, and a non-NULL `drop`: edge dropout and time do not combine.
+ * An entry with time refuses (SAGNN_ERR_ARG, before any launch) a plan or batch without buckets, a bucket count that
+ * differs from time->n_buckets, and a non-NULL `drop`: edge dropout and time do not combine.
  * -------------------------------------------------------------------------------- */
 /* d_buckets: [nnz] uint16 in colidx order, every value < n_buckets <= 65535 (checked by the caller), borrowed like the
  * weights. NULL clears them. Set before sagnn_spmm_batch_create, which copies the pointer. */
@@ -397,32 +312,66 @@ int sagnn_spmm_time_batch_create(const sagnn_spmm_plan* const* adj_user, const s
 int sagnn_spmm_time_f32(const sagnn_spmm_plan* plan, const float* X, int64_t ldx, int d,
                         const sagnn_spmm_epilogue* epilogue, const sagnn_edge_drop* drop, const sagnn_edge_time* time,
                         void* workspace, size_t workspace_bytes, void* stream);
-/* The interval / stack entries with time: the argument lists of the drop entries (`drop` must be NULL) and the
- * sagnn_edge_time. An interval entry works on TE[interval,:,:]; the stack entries on all of it. */
-int sagnn_gnn_interval_time_f32(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item, const float* u0,
-                                int64_t ld_u0, const float* i0, int64_t ld_i0, int d, int n_layers, float leaky,
-                                float* scratch_u, float* scratch_i, float* user_out, int64_t ld_uo, float* item_out,
-                                int64_t ld_io, uint8_t* mask_u, uint8_t* mask_i, const sagnn_edge_drop* drop,
-                                int interval, const sagnn_edge_time* time, void* workspace, size_t workspace_bytes,
-                                void* stream);
-int sagnn_gnn_interval_time_bwd_f32(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item,
-                                    const float* G_u, int64_t ld_gu, const float* G_i, int64_t ld_gi, int d,
-                                    int n_layers, float leaky, const uint8_t* mask_u, const uint8_t* mask_i,
-                                    float* scratch_u, float* scratch_i, float* grad_u0, int64_t ld_du, float* grad_i0,
-                                    int64_t ld_di, const sagnn_edge_drop* drop, int interval,
-                                    const sagnn_edge_time* time, void* workspace, size_t workspace_bytes, void* stream);
-int sagnn_gnn_stack_time_f32(const sagnn_spmm_batch* batch, const float* u0, int64_t ld_u0, int64_t slab_u0,
-                             const float* i0, int64_t ld_i0, int64_t slab_i0, int d, int n_layers, float leaky,
-                             float* scratch_u, float* scratch_i, float* user_out, int64_t ld_uo, int64_t slab_uo,
-                             float* item_out, int64_t ld_io, int64_t slab_io, uint8_t* mask_u, uint8_t* mask_i,
-                             const sagnn_edge_drop* drop, const sagnn_edge_time* time, void* workspace,
-                             size_t workspace_bytes, void* stream);
-int sagnn_gnn_stack_time_bwd_f32(const sagnn_spmm_batch* batch, const float* G_u, int64_t ld_gu, int64_t slab_gu,
-                                 const float* G_i, int64_t ld_gi, int64_t slab_gi, int d, int n_layers, float leaky,
-                                 const uint8_t* mask_u, const uint8_t* mask_i, float* scratch_u, float* scratch_i,
-                                 float* grad_u0, int64_t ld_du, int64_t slab_du, float* grad_i0, int64_t ld_di,
-                                 int64_t slab_di, const sagnn_edge_drop* drop, const sagnn_edge_time* time,
-                                 void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * The GNN stack — the loop model.py:118-129 (L layers, both directions, simultaneous update, residuals, add_n), issued
+ * from C. Four entries: forward or backward, of ONE interval k (2 L SpMM launches on its plan pair) or of a BATCH of T
+ * intervals (one launch per layer, above). Per interval:
+ *
+ *   e_u^0 = u0, e_i^0 = i0
+ *   e_u^{l+1} = leaky(A   e_i^l) + e_u^l        plan_user: rows = users, cols = items
+ *   e_i^{l+1} = leaky(A^T e_u^l) + e_i^l        plan_item: rows = items, cols = users
+ *   user_out = sum_{l=0..L} e_u^l ;  item_out = sum_{l=0..L} e_i^l
+ *
+ * The outputs are written with row strides ld_out, so an interval entry can target row k of an [N, T, d] slab directly
+ * (replaces tf.stack + tf.transpose, model.py:131-134). The backward (what tf.gradients builds for the loop): given
+ * G_u = dL/d user_out, G_i = dL/d item_out and the masks the forward recorded, writes dL/d u0 and dL/d i0 — the same
+ * SpMM kernel with the roles of the two adjacencies swapped (the reference already holds both, model.py:234-236).
+ *
+ * ADJOINT CONTRACT: the backward's plan_user (rows = users) must be the exact transpose, multiplicities included,
+ * of the item-side pattern the forward pass used, and plan_item that of the user-side pattern; the backward's `batch`
+ * must tie such plans, per interval. For matrices without duplicated stored entries these are the forward plans
+ * themselves; with duplicates (forward counts one twice, DataHandler.transpose merges it: DataHandler.py:9-11) the
+ * caller passes plans of the exact transposes — the library cannot tell the two cases apart from the handles, so the
+ * host side checks it (sa-gnn_amd/graph.py interval_pair, ops._adjoint_pair).
+ *
+ * `edges` names the form of every product; it is not inferred from which pointer is set:
+ *   SAGNN_EDGES_PLAIN  drop and time must be NULL.
+ *   SAGNN_EDGES_DROP   edge dropout (above) under `drop`. An interval entry drops with the tags of interval
+ *                      `interval`, interval k of a batch with those of k. The backward takes the sagnn_edge_drop (and
+ *                      interval) of its forward call.
+ *   SAGNN_EDGES_TIME   time-aware messages (above) under `time`; drop must be NULL. An interval entry works on
+ *                      TE[interval,:,:], a stack entry on all of it. The forward's plans / batch carry the buckets; the
+ *                      backward's need none, it reduces dTE through time->adj_*.
+ * A NULL args, an `edges` outside these three and PLAIN with a drop or time set are refused before any launch.
+ * -------------------------------------------------------------------------------- */
+typedef struct sagnn_gnn_side {     /* the operands of one node type (users or items), N rows */
+  const float* in;   int64_t ld_in,  slab_in;    /* forward: e^0 (u0 / i0); backward: G = dL/d out */
+  float*       out;  int64_t ld_out, slab_out;   /* forward: sum of the layers; backward: dL/d e^0 */
+  float*       scratch;                          /* forward [2,T,N,d] (NULL if n_layers <= 1); backward [4,T,N,d] */
+  uint8_t*     mask;                             /* [T, n_layers, N, d/4]; forward writes (both sides or neither), backward reads */
+} sagnn_gnn_side;
+
+enum { SAGNN_EDGES_PLAIN = 0, SAGNN_EDGES_DROP = 1, SAGNN_EDGES_TIME = 2 };
+
+typedef struct sagnn_gnn_args {
+  sagnn_gnn_side user, item;
+  int d, n_layers;
+  float leaky;
+  int edges;                       /* SAGNN_EDGES_* */
+  const sagnn_edge_drop* drop;     /* SAGNN_EDGES_DROP */
+  const sagnn_edge_time* time;     /* SAGNN_EDGES_TIME */
+  int interval;                    /* interval entries: the k of the drop tags / of TE[k]; stack entries do not read it */
+  void* workspace; size_t workspace_bytes;   /* sagnn_spmm_workspace_bytes (the larger of the two plans) / _batch_ */
+} sagnn_gnn_args;
+
+/* The interval entries take T = 1 and do not read slab_in / slab_out. */
+int sagnn_gnn_interval_f32(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item, const sagnn_gnn_args* args,
+                           void* stream);
+int sagnn_gnn_interval_bwd_f32(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item,
+                               const sagnn_gnn_args* args, void* stream);
+int sagnn_gnn_stack_f32(const sagnn_spmm_batch* batch, const sagnn_gnn_args* args, void* stream);
+int sagnn_gnn_stack_bwd_f32(const sagnn_spmm_batch* batch, const sagnn_gnn_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Interval fusion (model.py:135-155). x[node, interval, :] is read at

@@ -42,6 +42,22 @@ class EdgeTimeArgs(ctypes.Structure):
                 ("adj_batch", c_void_p), ("adj_workspace", c_void_p), ("adj_workspace_bytes", c_size_t)]
 
 
+class GnnSide(ctypes.Structure):
+    """sagnn_gnn_side"""
+    _fields_ = [("in_", c_void_p), ("ld_in", c_int64), ("slab_in", c_int64), ("out", c_void_p), ("ld_out", c_int64),
+                ("slab_out", c_int64), ("scratch", c_void_p), ("mask", c_void_p)]
+
+
+EDGES_PLAIN, EDGES_DROP, EDGES_TIME = 0, 1, 2       # SAGNN_EDGES_*
+
+
+class GnnArgs(ctypes.Structure):
+    """sagnn_gnn_args"""
+    _fields_ = [("user", GnnSide), ("item", GnnSide), ("d", c_int), ("n_layers", c_int), ("leaky", c_float),
+                ("edges", c_int), ("drop", POINTER(EdgeDropArgs)), ("time", POINTER(EdgeTimeArgs)), ("interval", c_int),
+                ("workspace", c_void_p), ("workspace_bytes", c_size_t)]
+
+
 class PlanInfo(ctypes.Structure):
     _fields_ = [("n_rows", c_int64), ("n_src", c_int64), ("nnz", c_int64),
                 ("n_long_rows", c_int64), ("n_chunks", c_int64), ("short_thresh", c_int32),
@@ -72,24 +88,19 @@ SIGNATURES = {
     "sagnn_spmm_ex_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int, POINTER(SpmmEpilogue), c_void_p, c_size_t,
                                   c_void_p]),
     "sagnn_mask_scale_f32": (c_int, [c_void_p, c_int64, c_void_p, c_float, c_void_p, c_int64, c_int64, c_int, c_void_p]),
-    "sagnn_gnn_interval_ex_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int,
-                                          c_float, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
-                                          c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "sagnn_gnn_interval_bwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int,
-                                           c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
-                                           c_void_p, c_int64, c_void_p, c_size_t, c_void_p]),
     "sagnn_spmm_batch_create": (c_int, [c_void_p, c_void_p, c_int, POINTER(c_void_p)]),
     "sagnn_spmm_batch_destroy": (c_int, [c_void_p]),
     "sagnn_spmm_batch_workspace_bytes": (c_size_t, [c_void_p, c_int]),
-    "sagnn_gnn_stack_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_float,
-                                    c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p,
-                                    c_void_p, c_void_p, c_size_t, c_void_p]),
-    "sagnn_gnn_stack_bwd_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_int,
-                                        c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
-                                        c_void_p, c_int64, c_int64, c_void_p, c_size_t, c_void_p]),
-    "sagnn_gnn_interval_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
-                                       c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int64,
-                                       c_void_p, c_int64, c_void_p, c_size_t, c_void_p]),
+    "sagnn_gnn_interval_f32": (c_int, [c_void_p, c_void_p, POINTER(GnnArgs), c_void_p]),
+    "sagnn_gnn_interval_bwd_f32": (c_int, [c_void_p, c_void_p, POINTER(GnnArgs), c_void_p]),
+    "sagnn_gnn_stack_f32": (c_int, [c_void_p, POINTER(GnnArgs), c_void_p]),
+    "sagnn_gnn_stack_bwd_f32": (c_int, [c_void_p, POINTER(GnnArgs), c_void_p]),
+    "sagnn_spmm_drop_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int, POINTER(SpmmEpilogue), POINTER(EdgeDropArgs),
+                                    c_uint32, c_int, c_void_p, c_size_t, c_void_p]),
+    "sagnn_spmm_plan_set_buckets": (c_int, [c_void_p, c_void_p, c_int32]),
+    "sagnn_spmm_time_batch_create": (c_int, [c_void_p, c_void_p, c_int, POINTER(c_void_p)]),
+    "sagnn_spmm_time_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int, POINTER(SpmmEpilogue), POINTER(EdgeDropArgs),
+                                    POINTER(EdgeTimeArgs), c_void_p, c_size_t, c_void_p]),
     "sagnn_lstm_fwd_train_f32": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_float,
                                          c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "sagnn_mhsa_wide_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
@@ -204,41 +215,6 @@ SIGNATURES = {
 }
 
 
-def _drop_form(base: str, *selectors):
-    """A drop entry: its base entry's arguments with the sagnn_edge_drop, then what selects its tags, ahead of the
-    trailing (workspace, workspace_bytes, stream)."""
-    res, args = SIGNATURES[base]
-    return res, args[:-3] + [POINTER(EdgeDropArgs), *selectors] + args[-3:]
-
-
-SIGNATURES.update({
-    "sagnn_spmm_drop_f32": _drop_form("sagnn_spmm_ex_f32", c_uint32, c_int),              # tag, rows_are_users
-    "sagnn_gnn_interval_drop_f32": _drop_form("sagnn_gnn_interval_ex_f32", c_int),        # interval
-    "sagnn_gnn_interval_drop_bwd_f32": _drop_form("sagnn_gnn_interval_bwd_f32", c_int),
-    "sagnn_gnn_stack_drop_f32": _drop_form("sagnn_gnn_stack_f32"),
-    "sagnn_gnn_stack_drop_bwd_f32": _drop_form("sagnn_gnn_stack_bwd_f32"),
-})
-
-
-
-def _time_form(entry: str, *ahead):
-    """A time entry: its drop entry's arguments (the sagnn_edge_drop must be NULL) with the sagnn_edge_time ahead of the
-    trailing (workspace, workspace_bytes, stream). The one-product entry has no tag arguments: its base entry's
-    arguments, the sagnn_edge_drop, the sagnn_edge_time."""
-    res, args = SIGNATURES[entry]
-    return res, args[:-3] + [*ahead, POINTER(EdgeTimeArgs)] + args[-3:]
-
-
-SIGNATURES.update({
-    "sagnn_spmm_plan_set_buckets": (c_int, [c_void_p, c_void_p, c_int32]),
-    "sagnn_spmm_time_batch_create": (c_int, [c_void_p, c_void_p, c_int, POINTER(c_void_p)]),
-    "sagnn_spmm_time_f32": _time_form("sagnn_spmm_ex_f32", POINTER(EdgeDropArgs)),
-    "sagnn_gnn_interval_time_f32": _time_form("sagnn_gnn_interval_drop_f32"),
-    "sagnn_gnn_interval_time_bwd_f32": _time_form("sagnn_gnn_interval_drop_bwd_f32"),
-    "sagnn_gnn_stack_time_f32": _time_form("sagnn_gnn_stack_drop_f32"),
-    "sagnn_gnn_stack_time_bwd_f32": _time_form("sagnn_gnn_stack_drop_bwd_f32"),
-})
-
 _lib = None
 
 
@@ -251,6 +227,9 @@ def load() -> ctypes.CDLL:
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; "
             "g.build()'` (or `make -C sa-gnn_amd/csrc`). There is no fallback path.")
     lib = ctypes.CDLL(LIB_PATH)
+    lib.sagnn_version.restype = c_int
+    if lib.sagnn_version() < 10400:     # before 1.4.0 the GNN stack entries took positional arguments under the same names
+        raise ImportError(f"{LIB_PATH} is libsagnn {lib.sagnn_version()}: this binding needs >= 10400 (sagnn_gnn_args)")
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.restype = res

@@ -24,27 +24,32 @@ class GnnStackFn(torch.autograd.Function):
     model.py:118-129 as ONE autograd node. Interval outputs are written straight into the slabs the fusion reads
     as [N, T, d] views (no torch.stack copy). With an ops.SpmmBatch the loop over k happens INSIDE the launches
     (one per layer, sagnn_gnn_stack_f32 / _bwd_f32); with plan lists every interval takes its own 2 L launches
-    (sagnn_gnn_interval_ex_f32: graphs whose T-fold scratch would not fit)."""
+    (sagnn_gnn_interval_f32: graphs whose T-fold scratch would not fit).
+    TE: None, or the time-aware messages of DESIGN.md §20 as one more input [T, L, 2, M, d] — TE[k, l, dir] is added, row
+    bucket[e], to what edge e of product (interval k, layer l, direction dir) gathers — with its gradient dTE. The
+    gradients into the embeddings are the same either way: the adjoint chain does not see the time term. The plans carry
+    the buckets (ops.SpmmPlan(buckets=)); not with `drop`."""
 
     @staticmethod
-    def forward(ctx, u_embed, i_embed, plans_user, plans_item, n_layers, leaky, drop=None):
+    def forward(ctx, u_embed, i_embed, plans_user, plans_item, n_layers, leaky, drop=None, TE=None):
         T, U, d = u_embed.shape
         I = i_embed.shape[1]
         dev = u_embed.device
         ue, ie = (x if x.stride(2) == 1 else x.contiguous() for x in (u_embed.detach(), i_embed.detach()))
+        te = None if TE is None else TE.detach().contiguous()
         out_u = torch.empty((T, U, d), dtype=torch.float32, device=dev)
         out_i = torch.empty((T, I, d), dtype=torch.float32, device=dev)
         mask_u = torch.empty((T, n_layers, U, d // 4), dtype=torch.uint8, device=dev)
         mask_i = torch.empty((T, n_layers, I, d // 4), dtype=torch.uint8, device=dev)
         if isinstance(plans_user, ops.SpmmBatch):
-            ops.gnn_stack(plans_user, ue, ie, n_layers, leaky, out_u, out_i, mask_u=mask_u, mask_i=mask_i, drop=drop)
+            ops.gnn_stack(plans_user, ue, ie, n_layers, leaky, out_u, out_i, mask_u=mask_u, mask_i=mask_i, drop=drop, time=te)
         else:
             scr_u = torch.empty((2, U, d), dtype=torch.float32, device=dev) if n_layers > 1 else None
             scr_i = torch.empty((2, I, d), dtype=torch.float32, device=dev) if n_layers > 1 else None
             for k in range(T):
                 ops.gnn_interval(plans_user[k], plans_item[k], ue[k], ie[k], n_layers, leaky, out_u[k], out_i[k], scr_u, scr_i,
-                                 mask_u=mask_u[k], mask_i=mask_i[k], drop=drop, interval=k)
-        ctx.save_for_backward(mask_u, mask_i)
+                                 mask_u=mask_u[k], mask_i=mask_i[k], drop=drop, interval=k, time=None if te is None else te[k])
+        ctx.save_for_backward(mask_u, mask_i, *(() if te is None else (te,)))
         ctx.plans = (plans_user, plans_item)
         ctx.drop = drop       # the backward drops the edges the forward dropped: the same ops.EdgeDrop
         ctx.cfg = (n_layers, leaky)
@@ -52,7 +57,8 @@ class GnnStackFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_user, g_item):
-        mask_u, mask_i = ctx.saved_tensors
+        mask_u, mask_i, *te = ctx.saved_tensors
+        te = te[0] if te else None
         plans_user, plans_item = ctx.plans
         n_layers, leaky = ctx.cfg
         T, _, U, dq = mask_u.shape
@@ -67,86 +73,28 @@ class GnnStackFn(torch.autograd.Function):
             g_item = g_item.contiguous()
         du = torch.empty((T, U, d), dtype=torch.float32, device=dev)
         di = torch.empty((T, I, d), dtype=torch.float32, device=dev)
+        dte = None if te is None else torch.empty_like(te)
         if isinstance(plans_user, ops.SpmmBatch):
-            ops.gnn_stack_bwd(plans_user, g_user, g_item, n_layers, leaky, mask_u, mask_i, du, di, drop=ctx.drop)
-            return du, di, None, None, None, None, None
+            ops.gnn_stack_bwd(plans_user, g_user, g_item, n_layers, leaky, mask_u, mask_i, du, di, drop=ctx.drop, time=te,
+                              grad_time=dte)
+            return du, di, None, None, None, None, None, dte
         scr_u = torch.empty((4, U, d), dtype=torch.float32, device=dev)
         scr_i = torch.empty((4, I, d), dtype=torch.float32, device=dev)
         for k in range(T):
             ops.gnn_interval_bwd(plans_user[k], plans_item[k], g_user[k], g_item[k], n_layers, leaky, mask_u[k], mask_i[k],
-                                 grad_u0=du[k], grad_i0=di[k], scratch_u=scr_u, scratch_i=scr_i, drop=ctx.drop, interval=k)
-        return du, di, None, None, None, None, None
-
-
-class GnnStackTimeFn(torch.autograd.Function):
-    """GnnStackFn with time-aware messages: a third input TE [T, L, 2, M, d] — TE[k, l, dir] is added,
-    row bucket[e], to what edge e of product (interval k, layer l, direction dir) gathers — and its gradient dTE. The
-    gradients into the embeddings are those of GnnStackFn: the adjoint chain does not see the time term. The plans
-    carry the buckets (ops.SpmmPlan(buckets=)); there is no edge dropout on this node."""
-
-    @staticmethod
-    def forward(ctx, u_embed, i_embed, TE, plans_user, plans_item, n_layers, leaky):
-        T, U, d = u_embed.shape
-        I = i_embed.shape[1]
-        dev = u_embed.device
-        ue, ie = (x if x.stride(2) == 1 else x.contiguous() for x in (u_embed.detach(), i_embed.detach()))
-        te = TE.detach().contiguous()
-        out_u = torch.empty((T, U, d), dtype=torch.float32, device=dev)
-        out_i = torch.empty((T, I, d), dtype=torch.float32, device=dev)
-        mask_u = torch.empty((T, n_layers, U, d // 4), dtype=torch.uint8, device=dev)
-        mask_i = torch.empty((T, n_layers, I, d // 4), dtype=torch.uint8, device=dev)
-        if isinstance(plans_user, ops.SpmmBatch):
-            ops.gnn_stack(plans_user, ue, ie, n_layers, leaky, out_u, out_i, mask_u=mask_u, mask_i=mask_i, time=te)
-        else:
-            scr_u = torch.empty((2, U, d), dtype=torch.float32, device=dev) if n_layers > 1 else None
-            scr_i = torch.empty((2, I, d), dtype=torch.float32, device=dev) if n_layers > 1 else None
-            for k in range(T):
-                ops.gnn_interval(plans_user[k], plans_item[k], ue[k], ie[k], n_layers, leaky, out_u[k], out_i[k], scr_u, scr_i,
-                                 mask_u=mask_u[k], mask_i=mask_i[k], time=te[k])
-        ctx.save_for_backward(mask_u, mask_i, te)
-        ctx.plans = (plans_user, plans_item)
-        ctx.cfg = (n_layers, leaky)
-        return out_u, out_i
-
-    @staticmethod
-    def backward(ctx, g_user, g_item):
-        mask_u, mask_i, te = ctx.saved_tensors
-        plans_user, plans_item = ctx.plans
-        n_layers, leaky = ctx.cfg
-        T, _, U, dq = mask_u.shape
-        I, d, dev = mask_i.shape[2], dq * 4, mask_u.device
-        if g_user is None:
-            g_user = torch.zeros((T, U, d), dtype=torch.float32, device=dev)
-        if g_item is None:
-            g_item = torch.zeros((T, I, d), dtype=torch.float32, device=dev)
-        if g_user.stride(2) != 1:
-            g_user = g_user.contiguous()
-        if g_item.stride(2) != 1:
-            g_item = g_item.contiguous()
-        du = torch.empty((T, U, d), dtype=torch.float32, device=dev)
-        di = torch.empty((T, I, d), dtype=torch.float32, device=dev)
-        dte = torch.empty_like(te)
-        if isinstance(plans_user, ops.SpmmBatch):
-            ops.gnn_stack_bwd(plans_user, g_user, g_item, n_layers, leaky, mask_u, mask_i, du, di, time=te, grad_time=dte)
-            return du, di, dte, None, None, None, None
-        scr_u = torch.empty((4, U, d), dtype=torch.float32, device=dev)
-        scr_i = torch.empty((4, I, d), dtype=torch.float32, device=dev)
-        for k in range(T):
-            ops.gnn_interval_bwd(plans_user[k], plans_item[k], g_user[k], g_item[k], n_layers, leaky, mask_u[k], mask_i[k],
-                                 grad_u0=du[k], grad_i0=di[k], scratch_u=scr_u, scratch_i=scr_i, time=te[k], grad_time=dte[k])
-        return du, di, dte, None, None, None, None
+                                 grad_u0=du[k], grad_i0=di[k], scratch_u=scr_u, scratch_i=scr_i, drop=ctx.drop, interval=k,
+                                 time=None if te is None else te[k], grad_time=None if te is None else dte[k])
+        return du, di, None, None, None, None, None, dte
 
 
 def gnn_stack(u_embed, i_embed, plans_user, plans_item, n_layers: int, leaky: float, drop=None, TE=None):
     """plans_user: a list of T ops.SpmmPlan (with plans_item the matching list) or an ops.SpmmBatch (plans_item None).
     drop: an ops.EdgeDrop for edge dropout in the forward and, identically, in the backward; None = no dropout.
-    TE: None (the node without time, unchanged), or the time tables [T, L, 2, M, d] in the registration order of their
-    weights (k, l, user call, item call): GnnStackTimeFn, which also returns dTE. Not with `drop`."""
-    if TE is not None:
-        if drop is not None:
-            raise ValueError("edge dropout and time-aware messages do not combine (--edgeKeepRate < 1 with --edgeTime slot)")
-        return GnnStackTimeFn.apply(u_embed, i_embed, TE, plans_user, plans_item, n_layers, leaky)
-    return GnnStackFn.apply(u_embed, i_embed, plans_user, plans_item, n_layers, leaky, drop)
+    TE: None (the node without time), or the time tables [T, L, 2, M, d] in the registration order of their weights
+    (k, l, user call, item call); the node then also returns dTE. Not with `drop`."""
+    if TE is not None and drop is not None:
+        raise ValueError("edge dropout and time-aware messages do not combine (--edgeKeepRate < 1 with --edgeTime slot)")
+    return GnnStackFn.apply(u_embed, i_embed, plans_user, plans_item, n_layers, leaky, drop, TE)
 
 
 def gnn_interval(u0, i0, plan_user, plan_item, n_layers: int, leaky: float):

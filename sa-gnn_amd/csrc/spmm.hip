@@ -1578,269 +1578,151 @@ auto dte_batched(const sagnn_edge_time& tm, int d, void* stream) {
 
 Slab slab(const float* p, int64_t ld, int64_t stride) { return Slab{const_cast<float*>(p), ld, stride}; }
 
-}  // namespace
+// ---- the four entries (include/sagnn.h, "The GNN stack") ----
+// What an entry runs on: the plan pair of one interval (T = 1, slab strides unused) or a batch of T intervals. Apart from
+// this geometry and the launcher it selects, the interval and the stack entries are the same code.
+struct Graphs {
+  const sagnn_spmm_plan *plan_user, *plan_item;   // the interval entries
+  const sagnn_spmm_batch* batch;                  // the stack entries
+  bool stack;
+  bool given() const { return stack ? batch != nullptr : plan_user && plan_item; }
+  int64_t T() const { return stack ? batch->T : 1; }
+  int64_t U() const { return stack ? batch->U : plan_user->info.n_rows; }
+  int64_t I() const { return stack ? batch->I : plan_item->info.n_rows; }
+};
 
-// The four stack entries and their drop forms share these bodies: drop = nullptr is the entry without dropout.
-namespace {
-int interval_forward(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item, const float* u0, int64_t ld_u0,
-                     const float* i0, int64_t ld_i0, int d, int n_layers, float leaky, float* scratch_u, float* scratch_i,
-                     float* user_out, int64_t ld_uo, float* item_out, int64_t ld_io, uint8_t* mask_u, uint8_t* mask_i,
-                     const sagnn_edge_drop* drop, int interval, const sagnn_edge_time* time, void* workspace,
-                     size_t workspace_bytes, void* stream) {
-  if (int rc = check_interval_plans(plan_user, plan_item)) return rc;
-  if (!u0 || !i0 || !user_out || !item_out) return sagnn::fail(SAGNN_ERR_NULL, "null embedding pointer");
-  if (n_layers < 1) return sagnn::fail(SAGNN_ERR_ARG, "n_layers = %d: need >= 1", n_layers);
-  if ((mask_u == nullptr) != (mask_i == nullptr)) return sagnn::fail(SAGNN_ERR_NULL, "give both masks or neither");
-  if (n_layers > 1 && (!scratch_u || !scratch_i))
-    return sagnn::fail(SAGNN_ERR_NULL, "scratch buffers required for n_layers > 1");
-  // the first launch refuses a host-only plan before it looks at d: keep that order
-  if (!plan_user->info.on_device) return sagnn::fail(SAGNN_ERR_ARG, "plan was built host-only (no device CSR)");
-  if (int rc = check_d(d)) return rc;
-  const Stack st{{slab(u0, ld_u0, 0), slab(user_out, ld_uo, 0), scratch_u, mask_u, plan_user->info.n_rows},
-                 {slab(i0, ld_i0, 0), slab(item_out, ld_io, 0), scratch_i, mask_i, plan_item->info.n_rows},
-                 1, d, n_layers, leaky};
-  if (int rc = check_stack(st, n_layers > 1, "u0", "i0", "user_out", "item_out")) return rc;
-  if (time) return run_forward(st, per_plan_time(plan_user, plan_item, d, workspace, workspace_bytes, stream, *time, interval));
-  if (drop)
-    return run_forward(st, per_plan_drop(plan_user, plan_item, d, workspace, workspace_bytes, stream, *drop, interval));
-  return run_forward(st, per_plan(plan_user, plan_item, d, workspace, workspace_bytes, stream));
+int check_graphs(const Graphs& g) {
+  if (g.stack) return g.batch ? SAGNN_OK : sagnn::fail(SAGNN_ERR_NULL, "batch is NULL");
+  return check_interval_plans(g.plan_user, g.plan_item);
 }
 
-int interval_backward(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item, const float* G_u, int64_t ld_gu,
-                      const float* G_i, int64_t ld_gi, int d, int n_layers, float leaky, const uint8_t* mask_u,
-                      const uint8_t* mask_i, float* scratch_u, float* scratch_i, float* grad_u0, int64_t ld_du,
-                      float* grad_i0, int64_t ld_di, const sagnn_edge_drop* drop, int interval, const sagnn_edge_time* time,
-                      void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = check_interval_plans(plan_user, plan_item)) return rc;
-  if (!G_u || !G_i || !grad_u0 || !grad_i0 || !mask_u || !mask_i || !scratch_u || !scratch_i)
-    return sagnn::fail(SAGNN_ERR_NULL, "null pointer");
-  if (n_layers < 1) return sagnn::fail(SAGNN_ERR_ARG, "n_layers = %d: need >= 1", n_layers);
-  if (int rc = check_d(d)) return rc;
-  const Stack st{{slab(G_u, ld_gu, 0), slab(grad_u0, ld_du, 0), scratch_u, const_cast<uint8_t*>(mask_u), plan_user->info.n_rows},
-                 {slab(G_i, ld_gi, 0), slab(grad_i0, ld_di, 0), scratch_i, const_cast<uint8_t*>(mask_i), plan_item->info.n_rows},
-                 1, d, n_layers, leaky};
-  if (int rc = check_stack(st, true, "G_u", "G_i", "grad_u0", "grad_i0")) return rc;
-  if (time)   // the adjoint chain does not see the time term: the plain launches, and dTE ahead of each step
-    return run_backward(st, per_plan(plan_user, plan_item, d, workspace, workspace_bytes, stream), stream,
-                        dte_per_plan(*time, d, interval, stream));
-  if (drop)
-    return run_backward(st, per_plan_drop(plan_user, plan_item, d, workspace, workspace_bytes, stream, *drop, interval),
-                        stream);
-  return run_backward(st, per_plan(plan_user, plan_item, d, workspace, workspace_bytes, stream), stream);
-}
-
-int stack_forward(const sagnn_spmm_batch* b, const float* u0, int64_t ld_u0, int64_t slab_u0, const float* i0, int64_t ld_i0,
-                  int64_t slab_i0, int d, int n_layers, float leaky, float* scratch_u, float* scratch_i, float* user_out,
-                  int64_t ld_uo, int64_t slab_uo, float* item_out, int64_t ld_io, int64_t slab_io, uint8_t* mask_u,
-                  uint8_t* mask_i, const sagnn_edge_drop* drop, const sagnn_edge_time* time, void* workspace,
-                  size_t workspace_bytes, void* stream) {
-  if (!b) return sagnn::fail(SAGNN_ERR_NULL, "batch is NULL");
-  if (!u0 || !i0 || !user_out || !item_out) return sagnn::fail(SAGNN_ERR_NULL, "null embedding pointer");
-  if (int rc = check_d(d)) return rc;
-  if (n_layers < 1) return sagnn::fail(SAGNN_ERR_ARG, "n_layers = %d: need >= 1", n_layers);
-  if ((mask_u == nullptr) != (mask_i == nullptr)) return sagnn::fail(SAGNN_ERR_NULL, "give both masks or neither");
-  if (n_layers > 1 && (!scratch_u || !scratch_i)) return sagnn::fail(SAGNN_ERR_NULL, "scratch buffers required for n_layers > 1");
-  const Stack st{{slab(u0, ld_u0, slab_u0), slab(user_out, ld_uo, slab_uo), scratch_u, mask_u, b->U},
-                 {slab(i0, ld_i0, slab_i0), slab(item_out, ld_io, slab_io), scratch_i, mask_i, b->I},
-                 b->T, d, n_layers, leaky};
-  if (int rc = check_stack(st, n_layers > 1, "u0", "i0", "user_out", "item_out")) return rc;
-  if (int rc = check_batch_ws(b, d, workspace, workspace_bytes)) return rc;
-  if (time) return run_forward(st, batched_time(b, d, workspace, stream, *time));
-  if (drop) return run_forward(st, batched_drop(b, d, workspace, stream, *drop));
-  return run_forward(st, batched(b, d, workspace, stream));
-}
-
-int stack_backward(const sagnn_spmm_batch* b, const float* G_u, int64_t ld_gu, int64_t slab_gu, const float* G_i,
-                   int64_t ld_gi, int64_t slab_gi, int d, int n_layers, float leaky, const uint8_t* mask_u,
-                   const uint8_t* mask_i, float* scratch_u, float* scratch_i, float* grad_u0, int64_t ld_du, int64_t slab_du,
-                   float* grad_i0, int64_t ld_di, int64_t slab_di, const sagnn_edge_drop* drop, const sagnn_edge_time* time,
-                   void* workspace, size_t workspace_bytes, void* stream) {
-  if (!b) return sagnn::fail(SAGNN_ERR_NULL, "batch is NULL");
-  if (!G_u || !G_i || !grad_u0 || !grad_i0 || !mask_u || !mask_i || !scratch_u || !scratch_i)
-    return sagnn::fail(SAGNN_ERR_NULL, "null pointer");
-  if (n_layers < 1) return sagnn::fail(SAGNN_ERR_ARG, "n_layers = %d: need >= 1", n_layers);
-  if (int rc = check_d(d)) return rc;
-  const Stack st{{slab(G_u, ld_gu, slab_gu), slab(grad_u0, ld_du, slab_du), scratch_u, const_cast<uint8_t*>(mask_u), b->U},
-                 {slab(G_i, ld_gi, slab_gi), slab(grad_i0, ld_di, slab_di), scratch_i, const_cast<uint8_t*>(mask_i), b->I},
-                 b->T, d, n_layers, leaky};
-  if (int rc = check_stack(st, true, "G_u", "G_i", "grad_u0", "grad_i0")) return rc;
-  if (int rc = check_batch_ws(b, d, workspace, workspace_bytes)) return rc;
-  if (time) {
-    if (int rc = check_batch_ws(time->adj_batch, d, time->adj_workspace, time->adj_workspace_bytes)) return rc;
-    return run_backward(st, batched(b, d, workspace, stream), stream, dte_batched(*time, d, stream));
+// What the form named by args->edges checks ahead of the shared body. DROP looks at its struct before anything else,
+// the graphs included; TIME at the graphs first, because it compares their bucket count with the struct's.
+int check_form(const Graphs& g, const sagnn_gnn_args* a, bool backward) {
+  if (!a) return sagnn::fail(SAGNN_ERR_NULL, "the sagnn_gnn_args is NULL");
+  switch (a->edges) {
+    case SAGNN_EDGES_PLAIN:
+      if (a->drop || a->time) return sagnn::fail(SAGNN_ERR_ARG, "edges = SAGNN_EDGES_PLAIN with a drop or time struct");
+      return SAGNN_OK;
+    case SAGNN_EDGES_DROP:
+      return check_drop(a->drop, a->n_layers, !g.stack ? a->interval : g.batch ? g.batch->T - 1 : 0);
+    case SAGNN_EDGES_TIME: {
+      if (!g.given()) return sagnn::fail(SAGNN_ERR_NULL, g.stack ? "batch is NULL" : "plan is NULL");
+      // The forward's graphs carry the buckets. The backward's are the adjoint patterns, which need none (the chain
+      // does not see the time term): there the buckets are in time->adj_user / adj_item / adj_batch.
+      int32_t n_buckets = a->time ? a->time->n_buckets : 0;
+      if (!backward) {
+        if (!g.stack && g.plan_user->n_buckets != g.plan_item->n_buckets)
+          return sagnn::fail(SAGNN_ERR_ARG, "edge time: the two plans carry different bucket counts (or only one carries buckets)");
+        n_buckets = g.stack ? g.batch->n_buckets : g.plan_user->n_buckets;
+      }
+      if (int rc = check_time(a->time, a->drop, n_buckets, a->d)) return rc;
+      if (!g.stack && a->interval < 0) return sagnn::fail(SAGNN_ERR_ARG, "edge time: interval = %d", a->interval);
+      return backward ? check_time_bwd(a->time, g.stack, g.U(), g.I(), (int)g.T()) : SAGNN_OK;
+    }
   }
-  if (drop) return run_backward(st, batched_drop(b, d, workspace, stream, *drop), stream);
-  return run_backward(st, batched(b, d, workspace, stream), stream);
+  return sagnn::fail(SAGNN_ERR_ARG, "edges = %d: not a SAGNN_EDGES_* value", a->edges);
+}
+
+Stack make_stack(const Graphs& g, const sagnn_gnn_args& a) {
+  const auto side = [&](const sagnn_gnn_side& s, int64_t rows) {
+    return Side{slab(s.in, s.ld_in, g.stack ? s.slab_in : 0), slab(s.out, s.ld_out, g.stack ? s.slab_out : 0), s.scratch,
+                s.mask, rows};
+  };
+  return Stack{side(a.user, g.U()), side(a.item, g.I()), g.T(), a.d, a.n_layers, a.leaky};
+}
+
+// run(launcher): the launcher of one layer for these graphs and edge form
+template <class Run>
+int with_launcher(const Graphs& g, const sagnn_gnn_args& a, void* stream, Run run) {
+  void* const ws = a.workspace;
+  const size_t n = a.workspace_bytes;
+  switch (a.edges) {
+    case SAGNN_EDGES_DROP:
+      return g.stack ? run(batched_drop(g.batch, a.d, ws, stream, *a.drop))
+                     : run(per_plan_drop(g.plan_user, g.plan_item, a.d, ws, n, stream, *a.drop, a.interval));
+    case SAGNN_EDGES_TIME:
+      return g.stack ? run(batched_time(g.batch, a.d, ws, stream, *a.time))
+                     : run(per_plan_time(g.plan_user, g.plan_item, a.d, ws, n, stream, *a.time, a.interval));
+    default:
+      return g.stack ? run(batched(g.batch, a.d, ws, stream)) : run(per_plan(g.plan_user, g.plan_item, a.d, ws, n, stream));
+  }
+}
+
+int gnn_forward(const Graphs& g, const sagnn_gnn_args* a, void* stream) {
+  if (int rc = check_form(g, a, false)) return rc;
+  if (int rc = check_graphs(g)) return rc;
+  const sagnn_gnn_side &u = a->user, &i = a->item;
+  if (!u.in || !i.in || !u.out || !i.out) return sagnn::fail(SAGNN_ERR_NULL, "null embedding pointer");
+  if (g.stack)   // a batch is on the device, so d comes first; an interval looks at d after its plan (below)
+    if (int rc = check_d(a->d)) return rc;
+  if (a->n_layers < 1) return sagnn::fail(SAGNN_ERR_ARG, "n_layers = %d: need >= 1", a->n_layers);
+  if ((u.mask == nullptr) != (i.mask == nullptr)) return sagnn::fail(SAGNN_ERR_NULL, "give both masks or neither");
+  if (a->n_layers > 1 && (!u.scratch || !i.scratch))
+    return sagnn::fail(SAGNN_ERR_NULL, "scratch buffers required for n_layers > 1");
+  if (!g.stack) {
+    // the first launch refuses a host-only plan before it looks at d: keep that order
+    if (!g.plan_user->info.on_device) return sagnn::fail(SAGNN_ERR_ARG, "plan was built host-only (no device CSR)");
+    if (int rc = check_d(a->d)) return rc;
+  }
+  const Stack st = make_stack(g, *a);
+  if (int rc = check_stack(st, a->n_layers > 1, "u0", "i0", "user_out", "item_out")) return rc;
+  if (g.stack)   // (the per-plan launches check the workspace themselves, as sagnn_spmm_ex_f32 does)
+    if (int rc = check_batch_ws(g.batch, a->d, a->workspace, a->workspace_bytes)) return rc;
+  return with_launcher(g, *a, stream, [&](auto launch) { return run_forward(st, launch); });
+}
+
+int gnn_backward(const Graphs& g, const sagnn_gnn_args* a, void* stream) {
+  if (int rc = check_form(g, a, true)) return rc;
+  if (int rc = check_graphs(g)) return rc;
+  const sagnn_gnn_side &u = a->user, &i = a->item;
+  if (!u.in || !i.in || !u.out || !i.out || !u.mask || !i.mask || !u.scratch || !i.scratch)
+    return sagnn::fail(SAGNN_ERR_NULL, "null pointer");
+  if (a->n_layers < 1) return sagnn::fail(SAGNN_ERR_ARG, "n_layers = %d: need >= 1", a->n_layers);
+  if (int rc = check_d(a->d)) return rc;
+  const Stack st = make_stack(g, *a);
+  if (int rc = check_stack(st, true, "G_u", "G_i", "grad_u0", "grad_i0")) return rc;
+  if (g.stack)
+    if (int rc = check_batch_ws(g.batch, a->d, a->workspace, a->workspace_bytes)) return rc;
+  if (a->edges != SAGNN_EDGES_TIME)
+    return with_launcher(g, *a, stream, [&](auto launch) { return run_backward(st, launch, stream); });
+  // the adjoint chain does not see the time term: the plain launches, and dTE ahead of each step
+  const sagnn_edge_time& tm = *a->time;
+  if (!g.stack)
+    return run_backward(st, per_plan(g.plan_user, g.plan_item, a->d, a->workspace, a->workspace_bytes, stream), stream,
+                        dte_per_plan(tm, a->d, a->interval, stream));
+  if (int rc = check_batch_ws(tm.adj_batch, a->d, tm.adj_workspace, tm.adj_workspace_bytes)) return rc;
+  return run_backward(st, batched(g.batch, a->d, a->workspace, stream), stream, dte_batched(tm, a->d, stream));
 }
 }  // namespace
 
-extern "C" int sagnn_gnn_interval_ex_f32(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item,
-                                         const float* u0, int64_t ld_u0, const float* i0, int64_t ld_i0,
-                                         int d, int n_layers, float leaky, float* scratch_u,
-                                         float* scratch_i, float* user_out, int64_t ld_uo, float* item_out,
-                                         int64_t ld_io, uint8_t* mask_u, uint8_t* mask_i, void* workspace,
-                                         size_t workspace_bytes, void* stream) {
-  return interval_forward(plan_user, plan_item, u0, ld_u0, i0, ld_i0, d, n_layers, leaky, scratch_u, scratch_i, user_out,
-                          ld_uo, item_out, ld_io, mask_u, mask_i, nullptr, 0, nullptr, workspace, workspace_bytes, stream);
+// One interval k of the loop of model.py:118-129: 2 L launches through the per-call checks of sagnn_spmm_ex_f32.
+extern "C" int sagnn_gnn_interval_f32(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item,
+                                      const sagnn_gnn_args* args, void* stream) {
+  return gnn_forward(Graphs{plan_user, plan_item, nullptr, false}, args, stream);
 }
 
-// sagnn_gnn_interval_ex_f32 with edge dropout; `interval` is the k of the tags (this interval's index in the model)
-extern "C" int sagnn_gnn_interval_drop_f32(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item,
-                                           const float* u0, int64_t ld_u0, const float* i0, int64_t ld_i0, int d,
-                                           int n_layers, float leaky, float* scratch_u, float* scratch_i, float* user_out,
-                                           int64_t ld_uo, float* item_out, int64_t ld_io, uint8_t* mask_u, uint8_t* mask_i,
-                                           const sagnn_edge_drop* drop, int interval, void* workspace,
-                                           size_t workspace_bytes, void* stream) {
-  if (int rc = check_drop(drop, n_layers, interval)) return rc;
-  return interval_forward(plan_user, plan_item, u0, ld_u0, i0, ld_i0, d, n_layers, leaky, scratch_u, scratch_i, user_out,
-                          ld_uo, item_out, ld_io, mask_u, mask_i, drop, interval, nullptr, workspace, workspace_bytes, stream);
-}
-
-extern "C" int sagnn_gnn_interval_f32(const sagnn_spmm_plan* plan_user,
-                                      const sagnn_spmm_plan* plan_item, const float* u0,
-                                      int64_t ld_u0, const float* i0, int64_t ld_i0, int d,
-                                      int n_layers, float leaky, float* scratch_u, float* scratch_i,
-                                      float* user_out, int64_t ld_uo, float* item_out, int64_t ld_io,
-                                      void* workspace, size_t workspace_bytes, void* stream) {
-  return sagnn_gnn_interval_ex_f32(plan_user, plan_item, u0, ld_u0, i0, ld_i0, d, n_layers, leaky, scratch_u,
-                                   scratch_i, user_out, ld_uo, item_out, ld_io, nullptr, nullptr, workspace,
-                                   workspace_bytes, stream);
-}
-
-// Backward of sagnn_gnn_interval_ex_f32 (backward_step above); scratch_x: [4][N][d].
+// plan_user / plan_item: the ADJOINT plans (for canonical matrices the forward plans themselves).
 extern "C" int sagnn_gnn_interval_bwd_f32(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item,
-                                          const float* G_u, int64_t ld_gu, const float* G_i, int64_t ld_gi,
-                                          int d, int n_layers, float leaky, const uint8_t* mask_u,
-                                          const uint8_t* mask_i, float* scratch_u, float* scratch_i,
-                                          float* grad_u0, int64_t ld_du, float* grad_i0, int64_t ld_di,
-                                          void* workspace, size_t workspace_bytes, void* stream) {
-  return interval_backward(plan_user, plan_item, G_u, ld_gu, G_i, ld_gi, d, n_layers, leaky, mask_u, mask_i, scratch_u,
-                           scratch_i, grad_u0, ld_du, grad_i0, ld_di, nullptr, 0, nullptr, workspace, workspace_bytes, stream);
+                                          const sagnn_gnn_args* args, void* stream) {
+  return gnn_backward(Graphs{plan_user, plan_item, nullptr, false}, args, stream);
 }
 
-// Backward of sagnn_gnn_interval_drop_f32: the same sagnn_edge_drop and interval as the forward call.
-extern "C" int sagnn_gnn_interval_drop_bwd_f32(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item,
-                                               const float* G_u, int64_t ld_gu, const float* G_i, int64_t ld_gi, int d,
-                                               int n_layers, float leaky, const uint8_t* mask_u, const uint8_t* mask_i,
-                                               float* scratch_u, float* scratch_i, float* grad_u0, int64_t ld_du,
-                                               float* grad_i0, int64_t ld_di, const sagnn_edge_drop* drop, int interval,
-                                               void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = check_drop(drop, n_layers, interval)) return rc;
-  return interval_backward(plan_user, plan_item, G_u, ld_gu, G_i, ld_gi, d, n_layers, leaky, mask_u, mask_i, scratch_u,
-                           scratch_i, grad_u0, ld_du, grad_i0, ld_di, drop, interval, nullptr, workspace, workspace_bytes, stream);
+// The whole loop — every interval, every layer — in L row launches (+ L fix-up launches when the graphs have long rows).
+extern "C" int sagnn_gnn_stack_f32(const sagnn_spmm_batch* batch, const sagnn_gnn_args* args, void* stream) {
+  return gnn_forward(Graphs{nullptr, nullptr, batch, true}, args, stream);
 }
 
-// The whole GNN loop of model.py:118-129 — every interval, every layer — in L row launches (+ L fix-up launches when
-// the graphs have long rows): sagnn_gnn_interval_ex_f32 for all T intervals at once. Operands are slabs.
-extern "C" int sagnn_gnn_stack_f32(const sagnn_spmm_batch* b, const float* u0, int64_t ld_u0, int64_t slab_u0,
-                                   const float* i0, int64_t ld_i0, int64_t slab_i0, int d, int n_layers, float leaky,
-                                   float* scratch_u, float* scratch_i, float* user_out, int64_t ld_uo, int64_t slab_uo,
-                                   float* item_out, int64_t ld_io, int64_t slab_io, uint8_t* mask_u, uint8_t* mask_i,
-                                   void* workspace, size_t workspace_bytes, void* stream) {
-  return stack_forward(b, u0, ld_u0, slab_u0, i0, ld_i0, slab_i0, d, n_layers, leaky, scratch_u, scratch_i, user_out, ld_uo,
-                       slab_uo, item_out, ld_io, slab_io, mask_u, mask_i, nullptr, nullptr, workspace, workspace_bytes, stream);
+// batch: the batch of the ADJOINT patterns (for canonical matrices the same batch).
+extern "C" int sagnn_gnn_stack_bwd_f32(const sagnn_spmm_batch* batch, const sagnn_gnn_args* args, void* stream) {
+  return gnn_backward(Graphs{nullptr, nullptr, batch, true}, args, stream);
 }
 
-// sagnn_gnn_stack_f32 with edge dropout: interval k of the batch drops with tag interval k.
-extern "C" int sagnn_gnn_stack_drop_f32(const sagnn_spmm_batch* b, const float* u0, int64_t ld_u0, int64_t slab_u0,
-                                        const float* i0, int64_t ld_i0, int64_t slab_i0, int d, int n_layers, float leaky,
-                                        float* scratch_u, float* scratch_i, float* user_out, int64_t ld_uo, int64_t slab_uo,
-                                        float* item_out, int64_t ld_io, int64_t slab_io, uint8_t* mask_u, uint8_t* mask_i,
-                                        const sagnn_edge_drop* drop, void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = check_drop(drop, n_layers, b ? b->T - 1 : 0)) return rc;
-  return stack_forward(b, u0, ld_u0, slab_u0, i0, ld_i0, slab_i0, d, n_layers, leaky, scratch_u, scratch_i, user_out, ld_uo,
-                       slab_uo, item_out, ld_io, slab_io, mask_u, mask_i, drop, nullptr, workspace, workspace_bytes, stream);
-}
-
-// Backward of sagnn_gnn_stack_f32 (backward_step above): G_u / G_i are the gradients at the interval outputs as slabs,
-// masks [T][L][N][d/4] as the forward recorded them; scratch_x: [4][T][N][d]. `b` must be the batch of the ADJOINT
-// patterns (for canonical matrices: the same batch).
-extern "C" int sagnn_gnn_stack_bwd_f32(const sagnn_spmm_batch* b, const float* G_u, int64_t ld_gu, int64_t slab_gu,
-                                       const float* G_i, int64_t ld_gi, int64_t slab_gi, int d, int n_layers, float leaky,
-                                       const uint8_t* mask_u, const uint8_t* mask_i, float* scratch_u, float* scratch_i,
-                                       float* grad_u0, int64_t ld_du, int64_t slab_du, float* grad_i0, int64_t ld_di,
-                                       int64_t slab_di, void* workspace, size_t workspace_bytes, void* stream) {
-  return stack_backward(b, G_u, ld_gu, slab_gu, G_i, ld_gi, slab_gi, d, n_layers, leaky, mask_u, mask_i, scratch_u, scratch_i,
-                        grad_u0, ld_du, slab_du, grad_i0, ld_di, slab_di, nullptr, nullptr, workspace, workspace_bytes, stream);
-}
-
-// Backward of sagnn_gnn_stack_drop_f32 on the adjoint batch: the same sagnn_edge_drop as the forward call.
-extern "C" int sagnn_gnn_stack_drop_bwd_f32(const sagnn_spmm_batch* b, const float* G_u, int64_t ld_gu, int64_t slab_gu,
-                                            const float* G_i, int64_t ld_gi, int64_t slab_gi, int d, int n_layers,
-                                            float leaky, const uint8_t* mask_u, const uint8_t* mask_i, float* scratch_u,
-                                            float* scratch_i, float* grad_u0, int64_t ld_du, int64_t slab_du,
-                                            float* grad_i0, int64_t ld_di, int64_t slab_di, const sagnn_edge_drop* drop,
-                                            void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = check_drop(drop, n_layers, b ? b->T - 1 : 0)) return rc;
-  return stack_backward(b, G_u, ld_gu, slab_gu, G_i, ld_gi, slab_gi, d, n_layers, leaky, mask_u, mask_i, scratch_u, scratch_i,
-                        grad_u0, ld_du, slab_du, grad_i0, ld_di, slab_di, drop, nullptr, workspace, workspace_bytes, stream);
-}
-
-// ---- the time entries (include/sagnn.h, "Time-aware messages"): the same bodies with a sagnn_edge_time ----
+// One product with a time table (include/sagnn.h, "Time-aware messages")
 extern "C" int sagnn_spmm_time_f32(const sagnn_spmm_plan* plan, const float* X, int64_t ldx, int d,
                                    const sagnn_spmm_epilogue* e, const sagnn_edge_drop* drop, const sagnn_edge_time* time,
                                    void* workspace, size_t workspace_bytes, void* stream) {
   if (!plan || !e) return sagnn::fail(SAGNN_ERR_NULL, "plan/epilogue is NULL");
   if (int rc = check_time(time, drop, plan->n_buckets, d)) return rc;
   return spmm_ex(plan, X, ldx, d, kernel_epilogue(*e, d), workspace, workspace_bytes, stream, nullptr, time->te);
-}
-
-extern "C" int sagnn_gnn_interval_time_f32(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item,
-                                           const float* u0, int64_t ld_u0, const float* i0, int64_t ld_i0, int d,
-                                           int n_layers, float leaky, float* scratch_u, float* scratch_i, float* user_out,
-                                           int64_t ld_uo, float* item_out, int64_t ld_io, uint8_t* mask_u, uint8_t* mask_i,
-                                           const sagnn_edge_drop* drop, int interval, const sagnn_edge_time* time,
-                                           void* workspace, size_t workspace_bytes, void* stream) {
-  if (!plan_user || !plan_item) return sagnn::fail(SAGNN_ERR_NULL, "plan is NULL");
-  if (plan_user->n_buckets != plan_item->n_buckets)
-    return sagnn::fail(SAGNN_ERR_ARG, "edge time: the two plans carry different bucket counts (or only one carries buckets)");
-  if (int rc = check_time(time, drop, plan_user->n_buckets, d)) return rc;
-  if (interval < 0) return sagnn::fail(SAGNN_ERR_ARG, "edge time: interval = %d", interval);
-  return interval_forward(plan_user, plan_item, u0, ld_u0, i0, ld_i0, d, n_layers, leaky, scratch_u, scratch_i, user_out,
-                          ld_uo, item_out, ld_io, mask_u, mask_i, nullptr, interval, time, workspace, workspace_bytes, stream);
-}
-
-// plan_user / plan_item: the adjoint plans, as sagnn_gnn_interval_bwd_f32 takes them (they need no buckets: the chain
-// does not see the time term); the buckets are in time->adj_user / adj_item.
-extern "C" int sagnn_gnn_interval_time_bwd_f32(const sagnn_spmm_plan* plan_user, const sagnn_spmm_plan* plan_item,
-                                               const float* G_u, int64_t ld_gu, const float* G_i, int64_t ld_gi, int d,
-                                               int n_layers, float leaky, const uint8_t* mask_u, const uint8_t* mask_i,
-                                               float* scratch_u, float* scratch_i, float* grad_u0, int64_t ld_du,
-                                               float* grad_i0, int64_t ld_di, const sagnn_edge_drop* drop, int interval,
-                                               const sagnn_edge_time* time, void* workspace, size_t workspace_bytes,
-                                               void* stream) {
-  if (!plan_user || !plan_item) return sagnn::fail(SAGNN_ERR_NULL, "plan is NULL");
-  if (int rc = check_time(time, drop, time ? time->n_buckets : 0, d)) return rc;
-  if (interval < 0) return sagnn::fail(SAGNN_ERR_ARG, "edge time: interval = %d", interval);
-  if (int rc = check_time_bwd(time, false, plan_user->info.n_rows, plan_item->info.n_rows, 1)) return rc;
-  return interval_backward(plan_user, plan_item, G_u, ld_gu, G_i, ld_gi, d, n_layers, leaky, mask_u, mask_i, scratch_u,
-                           scratch_i, grad_u0, ld_du, grad_i0, ld_di, nullptr, interval, time, workspace, workspace_bytes,
-                           stream);
-}
-
-extern "C" int sagnn_gnn_stack_time_f32(const sagnn_spmm_batch* b, const float* u0, int64_t ld_u0, int64_t slab_u0,
-                                        const float* i0, int64_t ld_i0, int64_t slab_i0, int d, int n_layers, float leaky,
-                                        float* scratch_u, float* scratch_i, float* user_out, int64_t ld_uo, int64_t slab_uo,
-                                        float* item_out, int64_t ld_io, int64_t slab_io, uint8_t* mask_u, uint8_t* mask_i,
-                                        const sagnn_edge_drop* drop, const sagnn_edge_time* time, void* workspace,
-                                        size_t workspace_bytes, void* stream) {
-  if (!b) return sagnn::fail(SAGNN_ERR_NULL, "batch is NULL");
-  if (int rc = check_time(time, drop, b->n_buckets, d)) return rc;
-  return stack_forward(b, u0, ld_u0, slab_u0, i0, ld_i0, slab_i0, d, n_layers, leaky, scratch_u, scratch_i, user_out, ld_uo,
-                       slab_uo, item_out, ld_io, slab_io, mask_u, mask_i, nullptr, time, workspace, workspace_bytes, stream);
-}
-
-// b: the batch of the adjoint patterns, as sagnn_gnn_stack_bwd_f32 takes it; the buckets are in time->adj_batch.
-extern "C" int sagnn_gnn_stack_time_bwd_f32(const sagnn_spmm_batch* b, const float* G_u, int64_t ld_gu, int64_t slab_gu,
-                                            const float* G_i, int64_t ld_gi, int64_t slab_gi, int d, int n_layers,
-                                            float leaky, const uint8_t* mask_u, const uint8_t* mask_i, float* scratch_u,
-                                            float* scratch_i, float* grad_u0, int64_t ld_du, int64_t slab_du,
-                                            float* grad_i0, int64_t ld_di, int64_t slab_di, const sagnn_edge_drop* drop,
-                                            const sagnn_edge_time* time, void* workspace, size_t workspace_bytes,
-                                            void* stream) {
-  if (!b) return sagnn::fail(SAGNN_ERR_NULL, "batch is NULL");
-  if (int rc = check_time(time, drop, time ? time->n_buckets : 0, d)) return rc;
-  if (int rc = check_time_bwd(time, true, b->U, b->I, b->T)) return rc;
-  return stack_backward(b, G_u, ld_gu, slab_gu, G_i, ld_gi, slab_gi, d, n_layers, leaky, mask_u, mask_i, scratch_u, scratch_i,
-                        grad_u0, ld_du, slab_du, grad_i0, ld_di, slab_di, nullptr, time, workspace, workspace_bytes, stream);
 }

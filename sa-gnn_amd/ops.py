@@ -284,11 +284,10 @@ def spmm(plan: SpmmPlan, x: torch.Tensor, leaky: float, residual: torch.Tensor |
     return out
 
 
-def _call(lib, entry: str, args: tuple, drop_args: tuple, ws):
-    """lib.<entry>(*args, *drop_args, workspace, workspace_bytes, stream): every SpMM / GNN entry ends with these three,
-    and a drop entry takes its base entry's arguments with the sagnn_edge_drop (and what selects its tags) just ahead of
-    them."""
-    check(getattr(lib, entry)(*args, *drop_args, _ptr(ws), 0 if ws is None else ws.numel() * 4, _stream()))
+def _call(entry, args: tuple, form_args: tuple, ws):
+    """entry(*args, *form_args, workspace, workspace_bytes, stream): the one-product entries end with these three, and
+    the drop and time forms take sagnn_spmm_ex_f32's arguments with their own just ahead of them."""
+    check(entry(*args, *form_args, _ptr(ws), 0 if ws is None else ws.numel() * 4, _stream()))
 
 
 def spmm_ex(plan: SpmmPlan, x: torch.Tensor | None, leaky: float, residual=None, out=None, acc_in=None, acc_out=None,
@@ -314,16 +313,15 @@ def spmm_ex(plan: SpmmPlan, x: torch.Tensor | None, leaky: float, residual=None,
     e.mask_out, e.mask_in = _ptr(mask_out), _ptr(mask_in)
     ldx = _f32_rows("x", x, d, plan.n_src) if x is not None else d
     ws = plan.workspace(d)
-    drop_args = ()
+    entry, form_args = plan._lib.sagnn_spmm_ex_f32, ()
     if _drop is not None:       # spmm_drop
         drop, tag, rows_are_users = _drop
-        drop_args = (ctypes.byref(drop.struct()), tag, int(rows_are_users))
-    entry = "sagnn_spmm_ex_f32" if _drop is None else "sagnn_spmm_drop_f32"
-    if _time is not None:       # spmm_time
+        entry, form_args = plan._lib.sagnn_spmm_drop_f32, (ctypes.byref(drop.struct()), tag, int(rows_are_users))
+    if _time is not None:       # spmm_time: its `drop` must be NULL
         et = _EdgeTime(_te_table("te", _time.view(1, 1, *_time.shape) if _time.dim() == 2 else _time, (1, 1),
                                  plan.n_buckets, d), plan.n_buckets, stack=False)
-        entry, drop_args = "sagnn_spmm_time_f32", et.tail()
-    _call(plan._lib, entry, (plan.handle, _ptr(x), ldx, d, ctypes.byref(e)), drop_args, ws)
+        entry, form_args = plan._lib.sagnn_spmm_time_f32, (None, ctypes.byref(et.args))
+    _call(entry, (plan.handle, _ptr(x), ldx, d, ctypes.byref(e)), form_args, ws)
     return out
 
 
@@ -408,11 +406,6 @@ class _EdgeTime:
             a.adj_workspace, a.adj_workspace_bytes = _ptr(ws), 0 if ws is None else ws.numel() * 4
         self.args = a
 
-    def tail(self, *selectors):
-        """What a time entry takes after its base entry's arguments: a NULL sagnn_edge_drop, the drop form's selectors,
-        the sagnn_edge_time."""
-        return (None, *selectors, ctypes.byref(self.args))
-
 
 def spmm_time(plan: SpmmPlan, x: torch.Tensor | None, leaky: float, te: torch.Tensor, residual=None, out=None, acc_in=None,
               acc_out=None, acc_in2=None, mask_out=None, mask_in=None, out2=None, slope2: float = 1.0,
@@ -470,18 +463,26 @@ def _adjoint_pair(plan_user: SpmmPlan, plan_item: SpmmPlan):
     return plan_user, plan_item
 
 
-def _time_or_drop(stem: str, base: str, drop, selectors: tuple, et):
-    """(entry name, what follows the base entry's arguments) of a stack call: the base entry, its drop form (`drop`), or
-    its time form (`et`, an _EdgeTime or False). A time form takes its selectors with interval 0: the TE it is given is
-    that of its own interval."""
-    bwd = "bwd_" if "bwd" in base else ""
-    if et:
-        if drop is not None:
-            raise ValueError("edge dropout and time do not combine: give `drop` or `time`, not both")
-        return f"{stem}_time_{bwd}f32", et.tail(*(0 for _ in selectors))
-    if drop is None:
-        return f"{stem}_{base}", ()
-    return f"{stem}_drop_{bwd}f32", (ctypes.byref(drop.struct()), *selectors)
+def _gnn_args(user: tuple, item: tuple, d: int, n_layers: int, leaky: float, drop, interval: int, et, ws):
+    """The sagnn_gnn_args of one stack call. user / item: (in, ld_in, slab_in, out, ld_out, slab_out, scratch, mask) of
+    that node type; drop: an EdgeDrop or None; et: an _EdgeTime or None (a time call of one interval is given the TE of
+    its own interval, so its `interval` is 0). The struct holds its sagnn_edge_drop / sagnn_edge_time (ctypes keeps
+    the target of a pointer field); the caller holds `et`, and with it the tables and the adjoint workspace, until the
+    call is over."""
+    if et is not None and drop is not None:
+        raise ValueError("edge dropout and time do not combine: give `drop` or `time`, not both")
+    a = _lib.GnnArgs()
+    for side, (x, ld_in, slab_in, out, ld_out, slab_out, scratch, mask) in ((a.user, user), (a.item, item)):
+        side.in_, side.ld_in, side.slab_in = _ptr(x), ld_in, slab_in
+        side.out, side.ld_out, side.slab_out = _ptr(out), ld_out, slab_out
+        side.scratch, side.mask = _ptr(scratch), _ptr(mask)
+    a.d, a.n_layers, a.leaky = d, int(n_layers), float(leaky)
+    a.workspace, a.workspace_bytes = _ptr(ws), 0 if ws is None else ws.numel() * 4
+    if et is not None:
+        a.edges, a.time = _lib.EDGES_TIME, ctypes.pointer(et.args)
+    elif drop is not None:
+        a.edges, a.drop, a.interval = _lib.EDGES_DROP, ctypes.pointer(drop.struct()), int(interval)
+    return a
 
 
 def gnn_interval(plan_user: SpmmPlan, plan_item: SpmmPlan, u0: torch.Tensor, i0: torch.Tensor,
@@ -489,13 +490,13 @@ def gnn_interval(plan_user: SpmmPlan, plan_item: SpmmPlan, u0: torch.Tensor, i0:
                  scratch_u: torch.Tensor | None = None, scratch_i: torch.Tensor | None = None,
                  mask_u: torch.Tensor | None = None, mask_i: torch.Tensor | None = None,
                  drop: EdgeDrop | None = None, interval: int = 0, time: torch.Tensor | None = None):
-    """One interval of the GNN loop (reference model.py:118-129): sagnn_gnn_interval_[ex_]f32; with `drop`, edge
-    dropout under the tags of interval `interval` (sagnn_gnn_interval_drop_f32).
+    """One interval of the GNN loop (reference model.py:118-129): sagnn_gnn_interval_f32; with `drop`, edge
+    dropout under the tags of interval `interval` (SAGNN_EDGES_DROP).
     user_out / item_out are [rows, d] views (any row stride, e.g. a column of an [N, T, d] slab).
     mask_u [L, U, d/4] / mask_i [L, I, d/4] uint8 (both or neither) record the activation masks
     the backward pass needs.
     time: TE [L, 2, M, d] of this interval (layer, direction: 0 = the user-side product, 1 = the item-side one), the
-    plans built with buckets (sagnn_gnn_interval_time_f32); not with `drop`."""
+    plans built with buckets (SAGNN_EDGES_TIME); not with `drop`."""
     d = int(u0.shape[1])
     U, I = plan_user.n_rows, plan_item.n_rows
     ld_u0 = _f32_rows("u0", u0, d, U)
@@ -510,13 +511,12 @@ def gnn_interval(plan_user: SpmmPlan, plan_item: SpmmPlan, u0: torch.Tensor, i0:
     if mask_i is not None:
         _masks("mask_i", mask_i, (n_layers, I, d // 4))
     ws = _interval_ws(plan_user, plan_item, d)
-    entry, tail = _time_or_drop("sagnn_gnn_interval", "ex_f32", drop, (int(interval),), time is not None and _EdgeTime(
+    et = None if time is None else _EdgeTime(
         _te_table("time", time, (n_layers, 2), _need_buckets("gnn_interval", plan_user.n_buckets), d), plan_user.n_buckets,
-        stack=False))
-    _call(plan_user._lib, entry,
-          (plan_user.handle, plan_item.handle, _ptr(u0), ld_u0, _ptr(i0), ld_i0, d, int(n_layers), float(leaky),
-           _ptr(scratch_u), _ptr(scratch_i), _ptr(user_out), ld_uo, _ptr(item_out), ld_io, _ptr(mask_u), _ptr(mask_i)),
-          tail, ws)
+        stack=False)
+    args = _gnn_args((u0, ld_u0, 0, user_out, ld_uo, 0, scratch_u, mask_u),
+                     (i0, ld_i0, 0, item_out, ld_io, 0, scratch_i, mask_i), d, n_layers, leaky, drop, interval, et, ws)
+    check(plan_user._lib.sagnn_gnn_interval_f32(plan_user.handle, plan_item.handle, ctypes.byref(args), _stream()))
     return user_out, item_out
 
 
@@ -527,12 +527,12 @@ def gnn_interval_bwd(plan_user: SpmmPlan, plan_item: SpmmPlan, grad_user_out: to
                      scratch_i: torch.Tensor | None = None, drop: EdgeDrop | None = None, interval: int = 0,
                      time: torch.Tensor | None = None, grad_time: torch.Tensor | None = None):
     """Backward of gnn_interval (sagnn_gnn_interval_bwd_f32): dL/d(user_out), dL/d(item_out) and the
-    recorded masks -> dL/d u0 [U, d], dL/d i0 [I, d]. `drop` / `interval`: those of the forward call
-    (sagnn_gnn_interval_drop_bwd_f32). `time`: the TE [L, 2, M, d] of the forward call; dTE is written to grad_time (same
-    shape) through the forward plans' time adjoints (sagnn_gnn_interval_time_bwd_f32)."""
+    recorded masks -> dL/d u0 [U, d], dL/d i0 [I, d]. `drop` / `interval`: those of the forward call.
+    `time`: the TE [L, 2, M, d] of the forward call; dTE is written to grad_time (same
+    shape) through the forward plans' time adjoints."""
     d = int(grad_user_out.shape[1])
     U, I = plan_user.n_rows, plan_item.n_rows
-    et = False
+    et = None
     if time is not None:
         M = _need_buckets("gnn_interval_bwd", plan_user.n_buckets)
         et = _EdgeTime(_te_table("time", time, (n_layers, 2), M, d), M, stack=False,
@@ -553,11 +553,9 @@ def gnn_interval_bwd(plan_user: SpmmPlan, plan_item: SpmmPlan, grad_user_out: to
     _masks("mask_u", mask_u, (n_layers, U, d // 4))
     _masks("mask_i", mask_i, (n_layers, I, d // 4))
     ws = _interval_ws(plan_user, plan_item, d)
-    entry, tail = _time_or_drop("sagnn_gnn_interval", "bwd_f32", drop, (int(interval),), et)
-    _call(plan_user._lib, entry,
-          (plan_user.handle, plan_item.handle, _ptr(grad_user_out), ld_gu, _ptr(grad_item_out), ld_gi, d, int(n_layers),
-           float(leaky), _ptr(mask_u), _ptr(mask_i), _ptr(scratch_u), _ptr(scratch_i), _ptr(grad_u0), ld_du, _ptr(grad_i0),
-           ld_di), tail, ws)
+    args = _gnn_args((grad_user_out, ld_gu, 0, grad_u0, ld_du, 0, scratch_u, mask_u),
+                     (grad_item_out, ld_gi, 0, grad_i0, ld_di, 0, scratch_i, mask_i), d, n_layers, leaky, drop, interval, et, ws)
+    check(plan_user._lib.sagnn_gnn_interval_bwd_f32(plan_user.handle, plan_item.handle, ctypes.byref(args), _stream()))
     return grad_u0, grad_i0
 
 
@@ -646,10 +644,10 @@ def gnn_stack(batch: SpmmBatch, u0: torch.Tensor, i0: torch.Tensor, n_layers: in
               scratch_i: torch.Tensor | None = None, mask_u: torch.Tensor | None = None, mask_i: torch.Tensor | None = None,
               drop: EdgeDrop | None = None, time: torch.Tensor | None = None):
     """Every interval of the GNN loop (reference model.py:118-129) in one launch per layer: sagnn_gnn_stack_f32; with
-    `drop`, edge dropout (sagnn_gnn_stack_drop_f32).
+    `drop`, edge dropout (SAGNN_EDGES_DROP).
     u0 [T, U, d], i0 [T, I, d]; user_out / item_out indexed [T, N, d] (e.g. `x.permute(1, 0, 2)` of the [N, T, d]
     tensor the fusion reads); mask_u [T, L, U, d/4] / mask_i [T, L, I, d/4] uint8 for training.
-    time: TE [T, L, 2, M, d], the batch's plans built with buckets (sagnn_gnn_stack_time_f32); not with `drop`."""
+    time: TE [T, L, 2, M, d], the batch's plans built with buckets (SAGNN_EDGES_TIME); not with `drop`."""
     T, U, I = batch.T, batch.U, batch.I
     d = int(u0.shape[2])
     ld_u0, sl_u0 = _slab("u0", u0, T, U, d)
@@ -664,13 +662,12 @@ def gnn_stack(batch: SpmmBatch, u0: torch.Tensor, i0: torch.Tensor, n_layers: in
     if mask_i is not None:
         _masks("mask_i", mask_i, (T, n_layers, I, d // 4))
     ws = batch.workspace(d)
-    entry, tail = _time_or_drop("sagnn_gnn_stack", "f32", drop, (), time is not None and _EdgeTime(
+    et = None if time is None else _EdgeTime(
         _te_table("time", time, (T, n_layers, 2), _need_buckets("gnn_stack", batch.n_buckets), d), batch.n_buckets,
-        stack=True))
-    _call(batch._lib, entry,
-          (batch.handle, _ptr(u0), ld_u0, sl_u0, _ptr(i0), ld_i0, sl_i0, d, int(n_layers), float(leaky), _ptr(scratch_u),
-           _ptr(scratch_i), _ptr(user_out), ld_uo, sl_uo, _ptr(item_out), ld_io, sl_io, _ptr(mask_u), _ptr(mask_i)),
-          tail, ws)
+        stack=True)
+    args = _gnn_args((u0, ld_u0, sl_u0, user_out, ld_uo, sl_uo, scratch_u, mask_u),
+                     (i0, ld_i0, sl_i0, item_out, ld_io, sl_io, scratch_i, mask_i), d, n_layers, leaky, drop, 0, et, ws)
+    check(batch._lib.sagnn_gnn_stack_f32(batch.handle, ctypes.byref(args), _stream()))
     return user_out, item_out
 
 
@@ -679,13 +676,13 @@ def gnn_stack_bwd(batch: SpmmBatch, grad_user_out: torch.Tensor, grad_item_out: 
                   scratch_u: torch.Tensor | None = None, scratch_i: torch.Tensor | None = None,
                   drop: EdgeDrop | None = None, time: torch.Tensor | None = None, grad_time: torch.Tensor | None = None):
     """Backward of gnn_stack (sagnn_gnn_stack_bwd_f32) on the batch's adjoint patterns: gradients at the interval
-    outputs [T, N, d] (any strides) -> dL/d u0 [T, U, d], dL/d i0 [T, I, d]. `drop`: that of the forward call
-    (sagnn_gnn_stack_drop_bwd_f32). `time`: the TE [T, L, 2, M, d] of the forward call; dTE is written to grad_time (same
-    shape) through the batch's time adjoint, one launch per layer (sagnn_gnn_stack_time_bwd_f32)."""
+    outputs [T, N, d] (any strides) -> dL/d u0 [T, U, d], dL/d i0 [T, I, d]. `drop`: that of the forward call.
+    `time`: the TE [T, L, 2, M, d] of the forward call; dTE is written to grad_time (same
+    shape) through the batch's time adjoint, one launch per layer."""
     adj = batch.adjoint()
     T, U, I = batch.T, batch.U, batch.I
     d = int(grad_user_out.shape[2])
-    et = False
+    et = None
     if time is not None:
         M = _need_buckets("gnn_stack_bwd", batch.n_buckets)
         et = _EdgeTime(_te_table("time", time, (T, n_layers, 2), M, d), M, stack=True,
@@ -700,11 +697,9 @@ def gnn_stack_bwd(batch: SpmmBatch, grad_user_out: torch.Tensor, grad_item_out: 
     _masks("mask_u", mask_u, (T, n_layers, U, d // 4))
     _masks("mask_i", mask_i, (T, n_layers, I, d // 4))
     ws = adj.workspace(d)
-    entry, tail = _time_or_drop("sagnn_gnn_stack", "bwd_f32", drop, (), et)
-    _call(adj._lib, entry,
-          (adj.handle, _ptr(grad_user_out), ld_gu, sl_gu, _ptr(grad_item_out), ld_gi, sl_gi, d, int(n_layers), float(leaky),
-           _ptr(mask_u), _ptr(mask_i), _ptr(scratch_u), _ptr(scratch_i), _ptr(grad_u0), ld_du, sl_du, _ptr(grad_i0), ld_di,
-           sl_di), tail, ws)
+    args = _gnn_args((grad_user_out, ld_gu, sl_gu, grad_u0, ld_du, sl_du, scratch_u, mask_u),
+                     (grad_item_out, ld_gi, sl_gi, grad_i0, ld_di, sl_di, scratch_i, mask_i), d, n_layers, leaky, drop, 0, et, ws)
+    check(adj._lib.sagnn_gnn_stack_bwd_f32(adj.handle, ctypes.byref(args), _stream()))
     return grad_u0, grad_i0
 
 

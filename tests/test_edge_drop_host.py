@@ -1,6 +1,6 @@
-"""CPU suite of the edge dropout of the interval graphs (--edgeKeepRate, ops.EdgeDrop, the sagnn_*_drop_* entries): the
-threshold and the mask restated in numpy (edge_drop_ref), the entries' argument checks (all refused before any device
-work, so no GPU is needed), the flag's range check and what trainEpoch draws from np.random."""
+"""CPU suite of the edge dropout of the interval graphs (--edgeKeepRate, ops.EdgeDrop, sagnn_spmm_drop_f32 and the GNN stack
+entries under SAGNN_EDGES_DROP): the threshold and the mask restated in numpy (edge_drop_ref), the entries' argument checks
+(all refused before any device work, so no GPU is needed), the flag's range check and what trainEpoch draws from np.random."""
 import ctypes
 
 import numpy as np
@@ -73,16 +73,22 @@ def _spmm(lib, p, drop, plan=None):
     return lib.sagnn_spmm_drop_f32(plan, p, 64, 64, ctypes.byref(e), drop, 5, 1, None, 0, None)
 
 
-def _interval(lib, p, drop, fn="sagnn_gnn_interval_drop_f32", L=2, k=0):
-    if fn.endswith("bwd_f32"):
-        return getattr(lib, fn)(None, None, p, 64, p, 64, 64, L, 0.5, p, p, p, p, p, 64, p, 64, drop, k, None, 0, None)
-    return getattr(lib, fn)(None, None, p, 64, p, 64, 64, L, 0.5, p, p, p, 64, p, 64, p, p, drop, k, None, 0, None)
+def _gnn_args(p, drop, L, k=0):
+    """A sagnn_gnn_args with edges = DROP and every operand given; drop: None or a ctypes.byref of the struct."""
+    a = _lib.GnnArgs(d=64, n_layers=L, leaky=0.5, edges=_lib.EDGES_DROP, interval=k)
+    if drop is not None:
+        a.drop = ctypes.pointer(drop._obj)
+    for side in (a.user, a.item):
+        side.in_, side.ld_in, side.out, side.ld_out, side.scratch, side.mask = p, 64, p, 64, p, p
+    return ctypes.byref(a)
 
 
-def _stack(lib, p, drop, fn="sagnn_gnn_stack_drop_f32", L=2):
-    if fn.endswith("bwd_f32"):
-        return getattr(lib, fn)(None, p, 64, 0, p, 64, 0, 64, L, 0.5, p, p, p, p, p, 64, 0, p, 64, 0, drop, None, 0, None)
-    return getattr(lib, fn)(None, p, 64, 0, p, 64, 0, 64, L, 0.5, p, p, p, 64, 0, p, 64, 0, p, p, drop, None, 0, None)
+def _interval(lib, p, drop, fn="sagnn_gnn_interval_f32", L=2, k=0):
+    return getattr(lib, fn)(None, None, _gnn_args(p, drop, L, k), None)
+
+
+def _stack(lib, p, drop, fn="sagnn_gnn_stack_f32", L=2):
+    return getattr(lib, fn)(None, _gnn_args(p, drop, L), None)
 
 
 BAD = [(dict(keep_threshold=0), "keep_threshold = 0"), (dict(scale=0.0), "scale"), (dict(scale=-2.0), "scale"),
@@ -94,8 +100,8 @@ def test_drop_entries_exist_and_reject_bad_arguments():
     buf = (ctypes.c_float * 4096)()
     p = ctypes.addressof(buf)
     calls = [lambda d: _spmm(lib, p, d),
-             lambda d: _interval(lib, p, d), lambda d: _interval(lib, p, d, "sagnn_gnn_interval_drop_bwd_f32"),
-             lambda d: _stack(lib, p, d), lambda d: _stack(lib, p, d, "sagnn_gnn_stack_drop_bwd_f32")]
+             lambda d: _interval(lib, p, d), lambda d: _interval(lib, p, d, "sagnn_gnn_interval_bwd_f32"),
+             lambda d: _stack(lib, p, d), lambda d: _stack(lib, p, d, "sagnn_gnn_stack_bwd_f32")]
     for call in calls:
         assert call(None) == -1 and "sagnn_edge_drop is null" in _lib.last_error().lower()
         for over, text in BAD:
@@ -104,13 +110,13 @@ def test_drop_entries_exist_and_reject_bad_arguments():
         # a good struct gets as far as the next check: the NULL plan / batch
         assert call(ctypes.byref(_drop())) == -1 and "edge drop" not in _lib.last_error().lower()
     good = ctypes.byref(_drop())
-    for fn in ("sagnn_gnn_interval_drop_f32", "sagnn_gnn_interval_drop_bwd_f32"):
+    for fn in ("sagnn_gnn_interval_f32", "sagnn_gnn_interval_bwd_f32"):
         assert _interval(lib, p, good, fn, L=128) == -5 and "n_layers = 128" in _lib.last_error()
         assert _interval(lib, p, good, fn, L=127) == -1
         assert _interval(lib, p, good, fn, k=1 << 23) == -5 and "interval" in _lib.last_error()
         assert _interval(lib, p, good, fn, k=-1) == -5 and "interval" in _lib.last_error()
         assert _interval(lib, p, good, fn, k=(1 << 23) - 1) == -1
-    for fn in ("sagnn_gnn_stack_drop_f32", "sagnn_gnn_stack_drop_bwd_f32"):
+    for fn in ("sagnn_gnn_stack_f32", "sagnn_gnn_stack_bwd_f32"):
         assert _stack(lib, p, good, fn, L=128) == -5 and "n_layers = 128" in _lib.last_error()
 
 

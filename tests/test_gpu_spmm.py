@@ -1,6 +1,7 @@
 """GPU parity: the HIP interval SpMM (through the C ABI) against the oracle on the same seeded
 inputs. fp32; tolerance 1e-4 relative / 1e-5 absolute (north_star: within 1e-4 fp32) — the only
 difference allowed is summation order."""
+import ctypes
 import os
 
 import numpy as np
@@ -234,7 +235,6 @@ def test_gnn_stack_one_launch_per_layer_vs_oracle(dev, d, L, T):
     lib = ops._lib.load()
     lib.sagnn_profile_enable(64)
     ops.gnn_stack(batch, ued, ied, L, 0.5, us.permute(1, 0, 2), its.permute(1, 0, 2))
-    import ctypes
     n, kinds = ctypes.c_int(0), (ctypes.c_int32 * 64)()
     ops.check(lib.sagnn_profile_read(None, kinds, None, None, 64, ctypes.byref(n)))
     lib.sagnn_profile_enable(0)
@@ -341,13 +341,18 @@ def _stack_entry_refusals(dev):
     p, ws = buf.data_ptr(), batch.workspace(d)
     wsp, wsb = ops._ptr(ws), 0 if ws is None else ws.numel() * 4
 
+    def args(in_u, d, L, scr_u, scr_i, mask_u, mask_i):
+        a = ops._lib.GnnArgs(d=d, n_layers=L, leaky=0.5, workspace=wsp, workspace_bytes=wsb)
+        for side, rows, x, scr, mask in ((a.user, U, in_u, scr_u, mask_u), (a.item, I, p, scr_i, mask_i)):
+            side.in_, side.ld_in, side.slab_in, side.out, side.ld_out, side.slab_out = x, d, rows * d, p, d, rows * d
+            side.scratch, side.mask = scr, mask
+        return ctypes.byref(a)
+
     def fwd(u0=p, d=d, L=1, scr_u=None, scr_i=None, mask_u=None, mask_i=None):
-        return lib.sagnn_gnn_stack_f32(b, u0, d, U * d, p, d, I * d, d, L, 0.5, scr_u, scr_i, p, d, U * d, p, d, I * d,
-                                       mask_u, mask_i, wsp, wsb, None)
+        return lib.sagnn_gnn_stack_f32(b, args(u0, d, L, scr_u, scr_i, mask_u, mask_i), None)
 
     def bwd(G_u=p, d=d, L=1, scr_u=p, scr_i=p, mask_u=m, mask_i=m):
-        return lib.sagnn_gnn_stack_bwd_f32(b, G_u, d, U * d, p, d, I * d, d, L, 0.5, mask_u, mask_i, scr_u, scr_i,
-                                           p, d, U * d, p, d, I * d, wsp, wsb, None)
+        return lib.sagnn_gnn_stack_bwd_f32(b, args(G_u, d, L, scr_u, scr_i, mask_u, mask_i), None)
 
     return [
         ("forward, NULL embedding", lambda: fwd(u0=None), -1, False),
@@ -371,3 +376,89 @@ def test_gnn_stack_entries_refuse_malformed_calls(dev):
     """The batched entries' argument checks (the per-interval entries' table is in tests/test_host.py)."""
     table, keep = _stack_entry_refusals(dev)
     assert [(name, call()) for name, call, _, _ in table] == [(name, want) for name, _, want, _ in table]
+
+
+def _padded(src, ld_extra):
+    """src [T, N, d] as a view with row stride d + ld_extra and slab stride (N + 1) rows of a tensor filled with NaN."""
+    T, N, d = src.shape
+    big = torch.full((T, N + 1, d + ld_extra), float("nan"), device=src.device)
+    view = big[:, :N, :d]
+    view.copy_(src)
+    return big, view
+
+
+def _padding_untouched(big, view):
+    T, N, d = view.shape
+    pad = big.clone()
+    pad[:, :N, :d] = float("nan")
+    return bool(pad.isnan().all()) and not bool(view.isnan().any())
+
+
+@pytest.mark.parametrize("form", ["plain", "drop", "time"])
+def test_gnn_args_every_field_reaches_the_operand_it_names(dev, form):
+    """The four entries through sagnn_gnn_args with all eight matrix operands as views of pairwise different row strides
+    (d + 4 ... d + 32) and slab strides that are not rows * ld, cut out of NaN-filled tensors; U != I, so a swapped side
+    cannot pass, and one row a side is past long_thresh, so the fix-up launch and the workspace take part. Outputs,
+    masks, gradients and dTE are byte-equal to the same calls on contiguous copies (summation order does not depend on
+    strides; the contiguous calls are checked against float64 elsewhere), the batch equals interval by interval, and no
+    byte outside an output view changes. No tolerance is involved."""
+    from sa_gnn_amd import ops
+    rng = np.random.default_rng(41)
+    T, U, I, d, L, M, leaky = 2, 5, 7, 32, 2, 3, 0.5
+    pu, pi = [], []
+    for k in range(T):
+        m = rng.random((U, I)) < 0.4
+        m[0, :] = m[:, 0] = True                                     # user 0 and item 0: 7 and 5 edges, past long_thresh = 4
+        B = rng.integers(0, M, (U, I)).astype(np.uint16)             # the bucket of edge (u, i), the same on both sides
+        for plans, mat, b in ((pu, sp.csr_matrix(m), B), (pi, sp.csr_matrix(m.T), B.T)):
+            rows = np.repeat(np.arange(mat.shape[0]), np.diff(mat.indptr))
+            plans.append(ops.SpmmPlan(mat.indptr.astype(np.int32), mat.indices.astype(np.int32), *mat.shape, device=dev,
+                                      tuning=(2, 4, 64), buckets=b[rows, mat.indices], n_buckets=M))
+        assert pu[k].info.n_long_rows == 1 and pi[k].info.n_long_rows == 1
+    batch = ops.SpmmBatch(pu, pi)
+    assert batch.workspace(d) is not None
+    drop = ops.EdgeDrop(0xD0, 3, 0.5) if form == "drop" else None
+    rand = lambda *shape: torch.from_numpy(rng.standard_normal(shape).astype(np.float32)).to(dev)   # noqa: E731
+    te = rand(T, L, 2, M, d) if form == "time" else None
+    src = [rand(T, U, d), rand(T, I, d), rand(T, U, d), rand(T, I, d)]           # u0, i0, G_u, G_i
+
+    def run(stack, strided):
+        """(user_out, item_out, mask_u, mask_i, grad_u0, grad_i0, dTE), and the tensors the four outputs are views of"""
+        extra = iter(range(4, 36, 4)) if strided else iter([0] * 8)
+        view = lambda x: _padded(x, next(extra)) if strided else (x, x.clone())   # noqa: E731
+        (_, u0), (_, i0), (_, gu), (_, gi) = (view(x) for x in src)
+        outs = [view(torch.zeros_like(x)) for x in (src[0], src[1], src[0], src[1])]    # user_out, item_out, grad_u0, grad_i0
+        (ou, oi, du, di) = (v for _, v in outs)
+        mu = torch.zeros((T, L, U, d // 4), dtype=torch.uint8, device=dev)
+        mi = torch.zeros((T, L, I, d // 4), dtype=torch.uint8, device=dev)
+        dte = None if te is None else torch.full_like(te, float("nan"))
+        if stack:
+            ops.gnn_stack(batch, u0, i0, L, leaky, ou, oi, mask_u=mu, mask_i=mi, drop=drop, time=te)
+            ops.gnn_stack_bwd(batch, gu, gi, L, leaky, mu, mi, du, di, drop=drop, time=te, grad_time=dte)
+        else:
+            for k in range(T):
+                tk, dk = (None, None) if te is None else (te[k], dte[k])
+                ops.gnn_interval(pu[k], pi[k], u0[k], i0[k], L, leaky, ou[k], oi[k], mask_u=mu[k], mask_i=mi[k], drop=drop,
+                                 interval=k, time=tk)
+                ops.gnn_interval_bwd(pu[k], pi[k], gu[k], gi[k], L, leaky, mu[k], mi[k], grad_u0=du[k], grad_i0=di[k],
+                                     drop=drop, interval=k, time=tk, grad_time=dk)
+        torch.cuda.synchronize()
+        return [ou, oi, mu, mi, du, di] + ([] if te is None else [dte]), outs
+
+    want, _ = run(stack=True, strided=False)
+    assert all(bool(torch.isfinite(x.float()).all()) for x in want)
+    for stack in (True, False):
+        got, outs = run(stack, strided=True)
+        assert [bool(torch.equal(g, w)) for g, w in zip(got, want)] == [True] * len(want), stack
+        assert all(_padding_untouched(big, v) for big, v in outs), stack
+    got, _ = run(stack=False, strided=False)
+    assert [bool(torch.equal(g, w)) for g, w in zip(got, want)] == [True] * len(want)
+    if form == "plain":
+        # the item side's ld_in lands in the field C reads as i0's: refused before any launch (tests/test_host.py reaches
+        # the same field without a device only through the backward, which calls it G_i)
+        lib, x = ops._lib.load(), want[0].data_ptr()
+        a = ops._lib.GnnArgs(d=d, n_layers=1, leaky=leaky)
+        for side, ld in ((a.user, d), (a.item, d - 4)):
+            side.in_, side.ld_in, side.out, side.ld_out = x, ld, x, d
+        assert lib.sagnn_gnn_interval_f32(pu[0].handle, pi[0].handle, ctypes.byref(a), None) == -5
+        assert "i0: ld 28 < d 32" in ops._lib.last_error()

@@ -29,7 +29,7 @@ def test_library_exports_every_header_symbol():
     for n in names:
         assert hasattr(lib, n), f"{n} declared in sagnn.h but not exported by libsagnn.so"
     assert sorted(_lib.SIGNATURES) == names, "ctypes SIGNATURES table out of sync with sagnn.h"
-    assert lib.sagnn_version() == 10302
+    assert lib.sagnn_version() == 10400
 
 
 def test_csr_check_errors():
@@ -277,6 +277,15 @@ def test_round3_entries_reject_bad_arguments_without_gpu():
     assert b"null" in msg.value.lower()
 
 
+def _gnn_args(user, item, d, L, leaky=0.5, **over):
+    """A sagnn_gnn_args of plain edges; user / item: (in, ld_in, slab_in, out, ld_out, slab_out, scratch, mask)."""
+    a = _lib.GnnArgs(d=d, n_layers=L, leaky=leaky, **over)
+    for side, values in ((a.user, user), (a.item, item)):
+        for (name, _), v in zip(_lib.GnnSide._fields_, values):
+            setattr(side, name, v)
+    return a
+
+
 def test_gnn_stack_entries_reject_malformed_calls_without_gpu():
     """The four entries of the GNN stack (one interval / a batch, forward / backward) and the code each malformed call
     returns; every one of them returns before a launch. Plans built with device=None are host-only: a well-formed
@@ -294,13 +303,17 @@ def test_gnn_stack_entries_reject_malformed_calls_without_gpu():
     pu, pi, other = host_plan(3, 4), host_plan(4, 3), host_plan(5, 3)
     U, I = pu.handle, pi.handle
 
-    def fwd(plan_user=U, plan_item=I, u0=p, d=64, L=1, scratch=None, mask_u=None, mask_i=None):
-        return lib.sagnn_gnn_interval_ex_f32(plan_user, plan_item, u0, 64, p, 64, d, L, 0.5, scratch, scratch, p, 64, p, 64,
-                                             mask_u, mask_i, None, 0, None)
+    def fwd(plan_user=U, plan_item=I, u0=p, d=64, L=1, scratch=None, mask_u=None, mask_i=None, **over):
+        a = _gnn_args((u0, 64, 0, p, 64, 0, scratch, mask_u), (p, 64, 0, p, 64, 0, scratch, mask_i), d, L, **over)
+        return lib.sagnn_gnn_interval_f32(plan_user, plan_item, ctypes.byref(a), None)
 
     def bwd(plan_user=U, plan_item=I, G_u=p, d=64, L=1, scratch=p, mask_u=m, mask_i=m):
-        return lib.sagnn_gnn_interval_bwd_f32(plan_user, plan_item, G_u, 64, p, 64, d, L, 0.5, mask_u, mask_i, scratch, scratch,
-                                              p, 64, p, 64, None, 0, None)
+        a = _gnn_args((G_u, 64, 0, p, 64, 0, scratch, mask_u), (p, 64, 0, p, 64, 0, scratch, mask_i), d, L)
+        return lib.sagnn_gnn_interval_bwd_f32(plan_user, plan_item, ctypes.byref(a), None)
+
+    thin = ctypes.byref(_gnn_args((p, 64, 0, p, 64, 0, None, None), (p, 64, 0, p, 64, 0, None, None), 64, 1))
+    full = ctypes.byref(_gnn_args((p, 64, 0, p, 64, 0, p, m), (p, 64, 0, p, 64, 0, p, m), 64, 1))
+    drop, time = _lib.EdgeDropArgs(1, 1, 1 << 31, 2.0), _lib.EdgeTimeArgs()
 
     table = [
         ("forward, NULL plan", fwd(plan_user=None), -1),
@@ -319,13 +332,59 @@ def test_gnn_stack_entries_reject_malformed_calls_without_gpu():
         ("backward, no scratch", bwd(scratch=None), -1),
         ("backward, not a transposed pair", bwd(plan_item=other.handle), -5),
         ("batched forward, NULL batch",
-         lib.sagnn_gnn_stack_f32(None, p, 64, 0, p, 64, 0, 64, 1, 0.5, None, None, p, 64, 0, p, 64, 0, None, None, None, 0, None), -1),
-        ("batched backward, NULL batch",
-         lib.sagnn_gnn_stack_bwd_f32(None, p, 64, 0, p, 64, 0, 64, 1, 0.5, m, m, p, p, p, 64, 0, p, 64, 0, None, 0, None), -1),
+         lib.sagnn_gnn_stack_f32(None, thin, None), -1),
+        ("batched backward, NULL batch", lib.sagnn_gnn_stack_bwd_f32(None, full, None), -1),
+        # the struct itself: refused before the plans are looked at, like everything above before any launch
+        ("NULL args", lib.sagnn_gnn_interval_f32(U, I, None, None), -1),
+        ("NULL args, backward", lib.sagnn_gnn_interval_bwd_f32(U, I, None, None), -1),
+        ("NULL args, batched", lib.sagnn_gnn_stack_f32(None, None, None), -1),
+        ("NULL args, batched backward", lib.sagnn_gnn_stack_bwd_f32(None, None, None), -1),
+        ("edges outside the three forms", fwd(edges=3), -5),
+        ("edges negative", fwd(edges=-1), -5),
+        ("plain edges with a drop struct", fwd(drop=ctypes.pointer(drop)), -5),
+        ("plain edges with a time struct", fwd(time=ctypes.pointer(time)), -5),
     ]
     assert [(name, rc) for name, rc, _ in table] == [(name, want) for name, _, want in table]
     # the thin forward without masks goes the same way
-    assert lib.sagnn_gnn_interval_f32(U, I, p, 64, p, 64, 64, 0, 0.5, None, None, p, 64, p, 64, None, 0, None) == -5
+    assert fwd(L=0) == -5 and "n_layers = 0" in _lib.last_error()
+
+
+def test_gnn_args_layout_matches_the_header():
+    """GnnArgs / GnnSide mirror sagnn_gnn_args / sagnn_gnn_side field for field (names and order from the header's text),
+    and the library reads the fields where ctypes puts them: values from both ends of the struct come back in refusal
+    messages, on host-only plans."""
+    text = open(os.path.join(ROOT, "include", "sagnn.h")).read()
+
+    def fields(struct):
+        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), text, re.S).group(1)
+        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+        return [n for decl in body.split(";") for n in re.findall(r"(\w+)\s*(?:,|$)", decl.strip())]
+
+    assert fields("sagnn_gnn_side") == [n.rstrip("_") for n, _ in _lib.GnnSide._fields_]
+    assert fields("sagnn_gnn_args") == [n for n, _ in _lib.GnnArgs._fields_]
+    # LP64: 3 pointers + 4 int64 + 2 pointers a side; then 4 x 4 bytes, 2 pointers, int + padding, pointer, size_t
+    assert ctypes.sizeof(_lib.GnnSide) == 64 and ctypes.sizeof(_lib.GnnArgs) == 2 * 64 + 16 + 16 + 8 + 16
+    assert (_lib.EDGES_PLAIN, _lib.EDGES_DROP, _lib.EDGES_TIME) == tuple(
+        int(re.search(r"SAGNN_EDGES_%s = (\d+)" % n, text).group(1)) for n in ("PLAIN", "DROP", "TIME"))
+
+    lib = _lib.load()
+    buf = (ctypes.c_float * 4096)()
+    p = (ctypes.addressof(buf) + 15) & ~15
+    pu = SpmmPlan(np.arange(4, dtype=np.int32), np.zeros(3, np.int32), 3, 4)
+    pi = SpmmPlan(np.arange(5, dtype=np.int32), np.zeros(4, np.int32), 4, 3)
+    drop = ctypes.pointer(_lib.EdgeDropArgs(1, 1, 1 << 31, 2.0))
+    side = (p, 64, 0, p, 64, 0, p, p)
+    for entry in (lib.sagnn_gnn_interval_f32, lib.sagnn_gnn_interval_bwd_f32):
+        call = lambda a: entry(pu.handle, pi.handle, ctypes.byref(a), None)   # noqa: E731
+        assert call(_gnn_args(side, side, 64, 128, edges=_lib.EDGES_DROP, drop=drop)) == -5
+        assert "n_layers = 128" in _lib.last_error()
+        assert call(_gnn_args(side, side, 64, 2, edges=_lib.EDGES_DROP, drop=drop, interval=(1 << 23) + 5)) == -5
+        assert "interval %d" % ((1 << 23) + 5) in _lib.last_error()
+    # the item side's ld_in. The forward refuses a host-only plan before it looks at i0 (tests/test_gpu_spmm.py has that
+    # row on device plans); the backward reads the same field as G_i and reaches it here.
+    a = _gnn_args(side, (p, 60, 0, p, 64, 0, p, p), 64, 2)
+    assert lib.sagnn_gnn_interval_bwd_f32(pu.handle, pi.handle, ctypes.byref(a), None) == -5
+    assert "G_i: ld 60 < d 64" in _lib.last_error()
 
 
 def test_params_match_reference_flags():
