@@ -1,6 +1,7 @@
 """torch.autograd bindings for the hot path (reference: the gradients tf.train.AdamOptimizer
 .minimize builds for model.py:118-129, model.py:250). Forward and backward both run in
-libsagnn.so; torch only carries the graph."""
+libsagnn.so, through the checked wrappers of ops.py (the only caller of the library); torch only
+carries the graph."""
 from __future__ import annotations
 
 import torch
@@ -14,7 +15,7 @@ FUSED_BPTT = True
 DEFERRED_DW_LIMIT = 32 << 30   # bytes of gate gradients ([t, n, 4d]) a BPTT may keep for the separate weight-gradient pass
 SPLIT_DW = True                # one-launch BPTT (d = 32 / 64): weight gradient as a second pass on the f16 x 2 engine ...
 # Feature widths the fusion's backward runs at: multiples of 32 (the dense products) with 64 % d == 0 or d % 64 == 0
-# (sagnn_attn_bwd_f32, sagnn_layernorm_td_bwd_f32). The forward alone also runs at d = 96, 160, 224.
+# (ops.attn_bwd, ops.layernorm_td_bwd). The forward alone also runs at d = 96, 160, 224.
 TRAINABLE_D = (32, 64, 128, 192, 256)
 SPLIT_DW_MIN_T = 4              # ... from this many steps on (measured: T = 16 -13 %, T = 6 -8 %, T = 2 / 3 nothing: the gate gradients' HBM round trip)
 
@@ -23,8 +24,8 @@ class GnnStackFn(torch.autograd.Function):
     """(uEmbed [T, U, d], iEmbed [T, I, d]) -> (user slab [T, U, d], item slab [T, I, d]): the whole loop of
     model.py:118-129 as ONE autograd node. Interval outputs are written straight into the slabs the fusion reads
     as [N, T, d] views (no torch.stack copy). With an ops.SpmmBatch the loop over k happens INSIDE the launches
-    (one per layer, sagnn_gnn_stack_f32 / _bwd_f32); with plan lists every interval takes its own 2 L launches
-    (sagnn_gnn_interval_f32: graphs whose T-fold scratch would not fit).
+    (one per layer, ops.gnn_stack / gnn_stack_bwd); with plan lists every interval takes its own 2 L launches
+    (ops.gnn_interval: graphs whose T-fold scratch would not fit).
     TE: None, or the time-aware messages of DESIGN.md §20 as one more input [T, L, 2, M, d] — TE[k, l, dir] is added, row
     bucket[e], to what edge e of product (interval k, layer l, direction dir) gathers — with its gradient dTE. The
     gradients into the embeddings are the same either way: the adjoint chain does not see the time term. The plans carry
@@ -119,75 +120,56 @@ def _split_qkv_grads(dWqkv, dbqkv, d):
     return out
 
 
-def _attn_bwd_front(x, gamma, beta, Wq, bq, Wk, bk, Wv, bv, heads, g_out, want_y=True):
-    """sagnn_attn_bwd_front_f32: x [n, t, d] dense, g_out [n, d] -> (y [n*t, d] or None, dqkv [n*t, 3d]).
-    gamma None = no layer norm (y = x, not written)."""
-    lib = ops._lib.load()
-    n, t, d, ld_n, ld_t = ops._ntd("x", x)
-    dev = x.device
-    dqkv = torch.empty((n * t, 3 * d), dtype=torch.float32, device=dev)
-    y = torch.empty((n * t, d), dtype=torch.float32, device=dev) if (want_y and gamma is not None) else None
-    ops.check(lib.sagnn_attn_bwd_front_f32(
-        x.data_ptr(), ld_n, ld_t, n, t, d, int(heads), None if gamma is None else ops._vec("gamma", gamma.detach(), d),
-        None if beta is None else ops._vec("beta", beta.detach(), d), 1e-12, 0 if gamma is None else 1,
-        *ops._attn_ptrs(d, *(w.detach() for w in (Wq, bq, Wk, bk, Wv, bv))),
-        g_out.data_ptr(), int(g_out.stride(0)), dqkv.data_ptr(), ops._ptr(y), ops._stream()))
-    return y, dqkv
+_attn_bwd_front = ops.attn_bwd_front      # the fused front under the name it had while it lived in this file
 
 
 def _attn_bwd_qkv(x, gamma, beta, Wqkv, Wq, bq, Wk, bk, Wv, bv, heads, g_out):
     """Recompute y = LN(x) (gamma None: y = x) and Q|K|V of x [n, t, d] dense, attention backward for g_out [n, d]
     contiguous -> (y [n*t, d], dQ|dK|dV [n*t, 3d]): the fused front where it covers the shape and FUSED_ATTN_BWD is
-    set, otherwise [layernorm_td ->] dense_nn -> sagnn_attn_bwd_f32. Wqkv: [Wq | Wk | Wv], detached."""
-    lib = ops._lib.load()
+    set, otherwise [layernorm_td ->] dense_nn -> attn_bwd. Wqkv: [Wq | Wk | Wv], detached."""
     n, t, d = x.shape
-    if lib.sagnn_attn_bwd_front_supported(d, t, heads) and FUSED_ATTN_BWD:
-        y, qkv = _attn_bwd_front(x, gamma, beta, Wq, bq, Wk, bk, Wv, bv, heads, g_out)
+    if ops.attn_bwd_front_supported(d, t, heads) and FUSED_ATTN_BWD:
+        y, qkv = ops.attn_bwd_front(x, gamma, beta, *(w.detach() for w in (Wq, bq, Wk, bk, Wv, bv)), heads, g_out)
         return (x.view(n * t, d) if y is None else y), qkv
     y = x if gamma is None else ops.layernorm_td(x, gamma, beta)                     # [n, t, d]
     bqkv = torch.cat([bq, bk, bv]).detach().contiguous()
     y2 = y.view(n * t, d)
     qkv = ops.dense_nn(y2, Wqkv, bqkv)                                               # [n*t, 3d]
-    ops.check(lib.sagnn_attn_bwd_f32(qkv.data_ptr(), g_out.data_ptr(), d, n, t, d, heads, ops._stream()))
-    return y2, qkv
+    return y2, ops.attn_bwd(qkv, g_out, n, t, heads)
+
+
+def _qkv_grads(y2, dqkv, Wqkv, fused_tail: bool, in_place: bool):
+    """The gradients behind Q|K|V = y W + b for y2 [rows, d] and dqkv [rows, 3d]: dW = y2^T dqkv, db = colsum dqkv and
+    dy = dqkv W^T -> (dy [rows, d], dWqkv [d, 3d], dbqkv [3d]). fused_tail: all three in one pass over dqkv
+    (ops.attn_bwd_tail, which writes dy over y2) instead of two products; in_place: dy reuses y2's storage (always
+    with the fused tail), so y2 must be the caller's to overwrite."""
+    d = y2.shape[1]
+    dWqkv = torch.zeros((d, 3 * d), dtype=torch.float32, device=y2.device)
+    dbqkv = torch.zeros(3 * d, dtype=torch.float32, device=y2.device)
+    if fused_tail:
+        assert in_place
+        return ops.attn_bwd_tail(y2, dqkv, Wqkv, dWqkv, dbqkv), dWqkv, dbqkv
+    ops.dense_tn(y2, dqkv, dWqkv, dbqkv)
+    return ops.dense_nn(dqkv, Wqkv.t().contiguous(), None, out=y2 if in_place else None), dWqkv, dbqkv
 
 
 def lstm_bwd(x, h, gates, cell, dh, drop, W):
-    """Whole BPTT in one launch (sagnn_lstm_bwd_f32, d in {32, 64}): x [n, t, d] (any strides),
-    h / gates / cell as the training forward stored them, dh [n, t, d] dense = gradient at the
-    emitted h -> (dx [n, t, d], dW [2d, 4d], db [4d])."""
-    lib = ops._lib.load()
-    n, t, d, ld_n, ld_t = ops._ntd("x", x)
-    dev = x.device
-    dx = torch.empty((n, t, d), dtype=torch.float32, device=dev)
-    dW = torch.zeros((2 * d, 4 * d), dtype=torch.float32, device=dev)
-    db = torch.zeros(4 * d, dtype=torch.float32, device=dev)
-    # scratch for the gate gradients [t, n, 4d]: with it the weight gradient is a second pass on the f16 x 2 engine
-    # (sagnn_lstm_bwd_ws_f32) instead of the BPTT launch's fp32-MFMA product
-    need = int(lib.sagnn_lstm_bwd_workspace_bytes(n, t, d))
-    ws = torch.empty(need // 4, dtype=torch.float32, device=dev) if (SPLIT_DW and t >= SPLIT_DW_MIN_T and 0 < need <= DEFERRED_DW_LIMIT) else None
-    ops.check(lib.sagnn_lstm_bwd_ws_f32(x.data_ptr(), ld_n, ld_t, h.data_ptr(), gates.data_ptr(), cell.data_ptr(),
-                                        dh.data_ptr(), t * d, ops._ptr(drop), ops._vec("lstm_W", W, 8 * d * d),
-                                        dx.data_ptr(), dW.data_ptr(), db.data_ptr(), n, t, d, ops._ptr(ws),
-                                        need if ws is not None else 0, ops._stream()))
-    return dx, dW, db
+    """Whole BPTT in one launch (ops.lstm_bwd, d in {32, 64}): x [n, t, d] (any strides), h / gates / cell as the
+    training forward stored them, dh [n, t, d] dense = gradient at the emitted h -> (dx [n, t, d], dW [2d, 4d],
+    db [4d]). Decides here whether the weight gradient is deferred to a second pass over the stored gate gradients
+    (SPLIT_DW, from SPLIT_DW_MIN_T steps on, while they fit DEFERRED_DW_LIMIT)."""
+    n, t, d = x.shape
+    need = ops.lstm_bwd_workspace_bytes(n, t, d)
+    return ops.lstm_bwd(x, h, gates, cell, dh, drop, W,
+                        deferred_dw=SPLIT_DW and t >= SPLIT_DW_MIN_T and 0 < need <= DEFERRED_DW_LIMIT)
 
 
 def _fusion_forward(x, lstm_W, lstm_b, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, heads, drop_scale):
     """The training forward of the interval fusion on x [n, t, d] (any node/interval strides): returns
     (out [n, d], h, gates, cell), the last three as the backward reads them."""
-    lib = ops._lib.load()
-    n, t, d, ld_n, ld_t = ops._ntd("x", x)
-    dev = x.device
-    h = torch.empty((n, t, d), dtype=torch.float32, device=dev)
-    gates = torch.empty((n, t, 4 * d), dtype=torch.float32, device=dev)
-    cell = torch.empty((n, t, d), dtype=torch.float32, device=dev)
     # h is stored un-dropped (it is also the recurrent operand of the backward pass); the
     # DropoutWrapper scaling of the emitted output is a separate element-wise pass
-    ops.check(lib.sagnn_lstm_fwd_train_f32(
-        x.data_ptr(), ld_n, ld_t, n, t, d, ops._vec("lstm_W", lstm_W.detach(), 8 * d * d),
-        ops._vec("lstm_b", lstm_b.detach(), 4 * d), 1.0, None, h.data_ptr(), t * d,
-        gates.data_ptr(), cell.data_ptr(), ops._stream()))
+    h, gates, cell = ops.lstm_fwd_train(x, lstm_W.detach(), lstm_b.detach())
     h_emit = h if drop_scale is None else ops.mul(h, drop_scale.contiguous())
     out = ops.ln_mhsa_mean(h_emit, ln_gamma.detach(), ln_beta.detach(), Wq.detach(), bq.detach(), Wk.detach(),
                            bk.detach(), Wv.detach(), bv.detach(), heads)
@@ -197,34 +179,20 @@ def _fusion_forward(x, lstm_W, lstm_b, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv
 def _fusion_backward(x, lstm_W, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, h, gates, cell, drop, heads, g_out):
     """The backward of _fusion_forward for g_out [n, d]: returns (dx [n, t, d], then the gradients of lstm_W, lstm_b,
     ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv)."""
-    lib = ops._lib.load()
-    n, t, d, ld_n, ld_t = ops._ntd("x", x)
+    n, t, d = x.shape
     dev = x.device
-    st = ops._stream()
     g_out = g_out.contiguous()
     # ---- recompute y and Q|K|V, attention backward -> dQ|dK|dV -----------------------------
     h_emit = h if drop is None else ops.mul(h, drop.contiguous())
     Wqkv = torch.cat([Wq, Wk, Wv], dim=1).detach().contiguous()                      # [d, 3d]
     y2, qkv = _attn_bwd_qkv(h_emit, ln_gamma.detach(), ln_beta.detach(), Wqkv, Wq, bq, Wk, bk, Wv, bv, heads, g_out)
-    dWqkv = torch.zeros((d, 3 * d), dtype=torch.float32, device=dev)
-    dbqkv = torch.zeros(3 * d, dtype=torch.float32, device=dev)
-    if lib.sagnn_attn_bwd_tail_supported(d) and FUSED_ATTN_BWD:
-        # dW += y^T dQKV, db += colsum dQKV and dy = dQKV W^T (over y) in one pass over dQKV
-        ops.check(lib.sagnn_attn_bwd_tail_f32(y2.data_ptr(), qkv.data_ptr(), n * t, d, Wqkv.data_ptr(),
-                                              dWqkv.data_ptr(), dbqkv.data_ptr(), st))
-        dy = y2
-    else:
-        ops.dense_tn(y2, qkv, dWqkv, dbqkv)
-        dy = ops.dense_nn(qkv, Wqkv.t().contiguous(), None, out=y2)                  # reuses y's storage
+    # y2 is this function's own recompute: dy goes over it, by the one-pass tail where that runs at d
+    dy, dWqkv, dbqkv = _qkv_grads(y2, qkv, Wqkv, fused_tail=ops.attn_bwd_tail_supported(d) and FUSED_ATTN_BWD, in_place=True)
     # ---- layer norm backward (in place on dy) ----------------------------------------------
-    dgamma = torch.zeros(d, dtype=torch.float32, device=dev)
-    dbeta = torch.zeros(d, dtype=torch.float32, device=dev)
-    dh = dy.view(n, t, d)
-    ops.check(lib.sagnn_layernorm_td_bwd_f32(h_emit.data_ptr(), t * d, dh.data_ptr(), t * d, n, t, d,
-                                             ops._vec("gamma", ln_gamma.detach(), d), 1e-12, dh.data_ptr(),
-                                             t * d, dgamma.data_ptr(), dbeta.data_ptr(), st))
+    dy = dy.view(n, t, d)
+    dh, dgamma, dbeta = ops.layernorm_td_bwd(h_emit, dy, ln_gamma.detach(), out=dy)
     # ---- BPTT ----------------------------------------------------------------------------------
-    if lib.sagnn_lstm_bwd_supported(d) and FUSED_BPTT:
+    if ops.lstm_bwd_supported(d) and FUSED_BPTT:
         dx, dW, db = lstm_bwd(x, h, gates, cell, dh, drop, lstm_W.detach())
         return (dx, dW, db, dgamma, dbeta) + _split_qkv_grads(dWqkv, dbqkv, d)
     # generic BPTT (the widths of TRAINABLE_D beyond 32 / 64; d = 128 is BASELINE config 3). Per step: the element-wise gate
@@ -241,10 +209,8 @@ def _fusion_backward(x, lstm_W, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, h, ga
     for ts in range(t - 1, -1, -1):
         last = ts == t - 1
         dgates = dG[ts if defer else 0]
-        ops.check(lib.sagnn_lstm_bwd_step_f32(
-            gates.data_ptr(), cell.data_ptr(), dh.data_ptr(), t * d, ops._ptr(drop),
-            None if last else dxh[:, ts + 1, d:].data_ptr(), t * 2 * d, None if last else dc[(ts + 1) & 1].data_ptr(),
-            dgates.data_ptr(), dc[ts & 1].data_ptr(), n, t, d, ts, st))
+        ops.lstm_bwd_step(gates, cell, dh, drop, None if last else dxh[:, ts + 1, d:], None if last else dc[(ts + 1) & 1],
+                          dgates, dc[ts & 1], ts)
         if not defer:
             ops.dense_tn(x[:, ts, :], dgates, dW[:d], db)
             if ts > 0:
@@ -374,11 +340,8 @@ def _mhsa_mean_backward(y, Wq, bq, Wk, bk, Wv, bv, heads, g_out):
     n, t, d = y.shape
     Wqkv = torch.cat([Wq, Wk, Wv], dim=1).detach().contiguous()
     y2, qkv = _attn_bwd_qkv(y.contiguous(), None, None, Wqkv, Wq, bq, Wk, bk, Wv, bv, heads, g_out.contiguous())
-    dWqkv = torch.zeros((d, 3 * d), dtype=torch.float32, device=y.device)
-    dbqkv = torch.zeros(3 * d, dtype=torch.float32, device=y.device)
-    ops.dense_tn(y2, qkv, dWqkv, dbqkv)
-    dy = ops.dense_nn(qkv, Wqkv.t().contiguous(), None).view(n, t, d)
-    return (dy,) + _split_qkv_grads(dWqkv, dbqkv, d)
+    dy, dWqkv, dbqkv = _qkv_grads(y2, qkv, Wqkv, fused_tail=False, in_place=False)
+    return (dy.view(n, t, d),) + _split_qkv_grads(dWqkv, dbqkv, d)
 
 
 class SpmmFn(torch.autograd.Function):
@@ -426,15 +389,7 @@ class LayerNormFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, gamma = ctx.saved_tensors
-        n, t, d = x.shape
-        g = g.contiguous()
-        dx = torch.empty_like(x)
-        dgamma = torch.zeros(d, dtype=torch.float32, device=x.device)
-        dbeta = torch.zeros(d, dtype=torch.float32, device=x.device)
-        ops.check(ops._lib.load().sagnn_layernorm_td_bwd_f32(
-            x.data_ptr(), t * d, g.data_ptr(), t * d, n, t, d, ops._vec("gamma", gamma.detach(), d), 1e-12,
-            dx.data_ptr(), t * d, dgamma.data_ptr(), dbeta.data_ptr(), ops._stream()))
-        return dx, dgamma, dbeta
+        return ops.layernorm_td_bwd(x, g.contiguous(), gamma.detach())
 
 
 class MhsaMeanFn(torch.autograd.Function):
@@ -465,10 +420,7 @@ class LeakyAddFn(torch.autograd.Function):
     def backward(ctx, g):
         (a,) = ctx.saved_tensors
         g = g.contiguous()
-        da = torch.empty_like(a)
-        ops.check(ops._lib.load().sagnn_leaky_f32(a.data_ptr(), g.data_ptr(), da.data_ptr(), ctx.leaky, a.numel(), 1,
-                                                  ops._stream()))
-        return da, g, None
+        return ops.leaky_bwd(a, g, ctx.leaky), g, None
 
 
 class PairScoreFn(torch.autograd.Function):
@@ -484,13 +436,8 @@ class PairScoreFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         U, I, S, uids, iids, locs = ctx.saved_tensors
-        d = U.shape[1]
-        dU, dI, dS = torch.zeros_like(U), torch.zeros_like(I), torch.zeros_like(S)
-        g = g.contiguous()
-        ops.check(ops._lib.load().sagnn_pair_score_bwd_f32(
-            U.data_ptr(), d, I.data_ptr(), d, S.data_ptr(), d, I.data_ptr(), d, uids.data_ptr(), iids.data_ptr(),
-            locs.data_ptr(), ctx.leaky, g.data_ptr(), dU.data_ptr(), dI.data_ptr(), dS.data_ptr(), dI.data_ptr(),
-            uids.numel(), d, ops._stream()))
+        # A is I (iEmbed_att IS final_item_vector): dA is dI, both sums land in it
+        dU, dI, dS, _ = ops.pair_score_bwd(U, I, uids, iids, g.contiguous(), S=S, A=I, locs=locs, leaky=ctx.leaky)
         return dU, dI, dS, None, None, None, None
 
 
@@ -521,22 +468,12 @@ class ProdLeakySumFn(torch.autograd.Function):
         X, Y = X.detach().contiguous(), Y.detach().contiguous()
         ctx.save_for_backward(X, Y, uids, iids)
         ctx.leaky = leaky
-        d = X.shape[1]
-        out = torch.empty(uids.numel(), dtype=torch.float32, device=X.device)
-        ops.check(ops._lib.load().sagnn_prod_leaky_sum_f32(X.data_ptr(), d, Y.data_ptr(), d, uids.data_ptr(),
-                                                           iids.data_ptr(), leaky, out.data_ptr(), uids.numel(), d,
-                                                           ops._stream()))
-        return out
+        return ops.prod_leaky_sum(X, Y, uids, iids, leaky)
 
     @staticmethod
     def backward(ctx, g):
         X, Y, uids, iids = ctx.saved_tensors
-        d = X.shape[1]
-        dX, dY = torch.zeros_like(X), torch.zeros_like(Y)
-        g = g.contiguous()
-        ops.check(ops._lib.load().sagnn_prod_leaky_sum_bwd_f32(X.data_ptr(), d, Y.data_ptr(), d, uids.data_ptr(),
-                                                               iids.data_ptr(), ctx.leaky, g.data_ptr(), dX.data_ptr(),
-                                                               dY.data_ptr(), uids.numel(), d, ops._stream()))
+        dX, dY = ops.prod_leaky_sum_bwd(X, Y, uids, iids, ctx.leaky, g.contiguous())
         return dX, dY, None, None, None
 
 
@@ -554,49 +491,32 @@ class MetaWeightFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, F, V, uids, W2, b2, W3, b3, leaky):
-        lib = ops._lib.load()
         F, V = F.detach().contiguous(), V.detach().contiguous()
-        n, d, k = uids.numel(), F.shape[1], W2.shape[1]
+        k = W2.shape[1]
         kp = (k + 31) // 32 * 32
-        dev = F.device
-        m1 = torch.empty((n, 3 * d), dtype=torch.float32, device=dev)
-        ops.check(lib.sagnn_meta_features_f32(F.data_ptr(), d, V.data_ptr(), d, uids.data_ptr(), m1.data_ptr(), n, d,
-                                              ops._stream()))
+        m1 = ops.meta_features(F, V, uids)
         W2p = _pad_cols(W2.detach(), kp).contiguous()
         z1 = ops.dense_nn(m1, W2p, _pad_cols(b2.detach(), kp).contiguous())
-        a1 = torch.empty_like(z1)
-        ops.check(lib.sagnn_leaky_f32(z1.data_ptr(), None, a1.data_ptr(), leaky, z1.numel(), 0, ops._stream()))
-        w = torch.empty(n, dtype=torch.float32, device=dev)
+        a1 = ops.leaky(z1, leaky)
         w3 = W3.detach().reshape(-1).contiguous()
-        ops.check(lib.sagnn_rowdot_sigmoid_f32(a1.data_ptr(), kp, w3.data_ptr(), b3.detach().data_ptr(), w.data_ptr(),
-                                               n, k, ops._stream()))
+        w = ops.rowdot_sigmoid(a1, w3, b3.detach(), k)
         ctx.save_for_backward(F, V, uids, m1, z1, a1, w, W2p, w3)
         ctx.cfg = (leaky, k, kp)
         return w
 
     @staticmethod
     def backward(ctx, dw):
-        lib = ops._lib.load()
         F, V, uids, m1, z1, a1, w, W2p, w3 = ctx.saved_tensors
         leaky, k, kp = ctx.cfg
-        n, d = uids.numel(), F.shape[1]
+        d = F.shape[1]
         dev = F.device
-        dw = dw.contiguous()
-        dA = torch.zeros_like(a1)
-        dw3 = torch.zeros(k, dtype=torch.float32, device=dev)
-        db3 = torch.zeros(1, dtype=torch.float32, device=dev)
-        ops.check(lib.sagnn_rowdot_sigmoid_bwd_f32(a1.data_ptr(), kp, w3.data_ptr(), w.data_ptr(), dw.data_ptr(),
-                                                   dA.data_ptr(), kp, dw3.data_ptr(), db3.data_ptr(), n, k,
-                                                   ops._stream()))
-        dz1 = torch.empty_like(z1)
-        ops.check(lib.sagnn_leaky_f32(z1.data_ptr(), dA.data_ptr(), dz1.data_ptr(), leaky, z1.numel(), 1, ops._stream()))
+        dA, dw3, db3 = ops.rowdot_sigmoid_bwd(a1, w3, w, dw.contiguous(), k)
+        dz1 = ops.leaky_bwd(z1, dA, leaky)
         dW2p = torch.zeros((3 * d, kp), dtype=torch.float32, device=dev)
         db2p = torch.zeros(kp, dtype=torch.float32, device=dev)
         ops.dense_tn(m1, dz1, dW2p, db2p)
         dm1 = ops.dense_nn(dz1, W2p.t().contiguous(), None)
-        dF, dV = torch.zeros_like(F), torch.zeros_like(V)
-        ops.check(lib.sagnn_meta_features_bwd_f32(F.data_ptr(), d, V.data_ptr(), d, uids.data_ptr(), dm1.data_ptr(),
-                                                  dF.data_ptr(), dV.data_ptr(), n, d, ops._stream()))
+        dF, dV = ops.meta_features_bwd(F, V, uids, dm1)
         return dF, dV, None, dW2p[:, :k].contiguous(), db2p[:k].contiguous(), dw3.view(k, 1), db3, None
 
 
@@ -606,22 +526,9 @@ class HingeFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pos, neg, wp, wn, sp, sn, scale):
-        lib = ops._lib.load()
-        pos, neg = pos.detach().contiguous(), neg.detach().contiguous()
-        n = pos.numel()
-        dev = pos.device
-        loss = torch.zeros(1, dtype=torch.float32, device=dev)
-        dpos, dneg = torch.empty_like(pos), torch.empty_like(neg)
         weighted = wp is not None
-        if weighted:
-            wp, wn = wp.detach().contiguous(), wn.detach().contiguous()
-            sp, sn = sp.detach().contiguous(), sn.detach().contiguous()
-            dwp, dwn = torch.empty_like(wp), torch.empty_like(wn)
-        ops.check(lib.sagnn_hinge_f32(pos.data_ptr(), neg.data_ptr(), ops._ptr(wp) if weighted else None,
-                                      ops._ptr(wn) if weighted else None, ops._ptr(sp) if weighted else None,
-                                      ops._ptr(sn) if weighted else None, float(scale), loss.data_ptr(),
-                                      dpos.data_ptr(), dneg.data_ptr(), dwp.data_ptr() if weighted else None,
-                                      dwn.data_ptr() if weighted else None, n, ops._stream()))
+        pos, neg, wp, wn, sp, sn = (None if v is None else v.detach().contiguous() for v in (pos, neg, wp, wn, sp, sn))
+        loss, dpos, dneg, dwp, dwn = ops.hinge(pos, neg, wp, wn, sp, sn, scale)
         ctx.weighted = weighted
         ctx.save_for_backward(dpos, dneg, *((dwp, dwn) if weighted else ()))
         return loss
@@ -643,7 +550,7 @@ class HingeFn(torch.autograd.Function):
 
 class SeqGatherFn(torch.autograd.Function):
     """(fi, posEmbed) -> (item token slab, position token slab), both [n_slots * P, d] with zeros in the padding
-    (sagnn_seq_gather_f32). Slot b's token j is item seq_items[seg_begin[b] + j] at position seq_pos[seg_begin[b] + j],
+    (ops.seq_gather). Slot b's token j is item seq_items[seg_begin[b] + j] at position seq_pos[seg_begin[b] + j],
     or right-aligned (P - n_b + j) with seq_pos None."""
 
     @staticmethod
@@ -664,9 +571,9 @@ class SeqGatherFn(torch.autograd.Function):
 
 class SeqAttnFn(torch.autograd.Function):
     """One sequence-attention layer on a slab: x [n_slots * P, d] -> leaky(ctx) + x with y = LN(x) per token,
-    q|k|v = y [Wq|Wk|Wv] + b and ctx the ragged attention over each slot's real tokens (sagnn_seq_attn_f32).
+    q|k|v = y [Wq|Wk|Wv] + b and ctx the ragged attention over each slot's real tokens (ops.seq_attn).
     Saved for the backward: x and q|k|v. The backward recomputes ctx (for the slope of leaky) and y, then
-    sagnn_seq_attn_bwd_f32 -> dW, db (dense_tn) and dy (dense_nn) -> layer-norm backward. Padded rows of the incoming gradient must be zero (SeqPoolFn's and this class's are); the returned
+    ops.seq_attn_bwd -> dW, db (dense_tn) and dy (dense_nn) -> layer-norm backward. Padded rows of the incoming gradient must be zero (SeqPoolFn's and this class's are); the returned
     gradient's are."""
 
     @staticmethod
@@ -686,32 +593,24 @@ class SeqAttnFn(torch.autograd.Function):
     def backward(ctx, g):
         x, qkv, gamma, beta, Wqkv, seg_len = ctx.saved_tensors
         P, heads, leaky = ctx.cfg
-        lib = ops._lib.load()
         R, d = x.shape
-        dev, st = x.device, ops._stream()
         g = g.contiguous()
         att = ops.seq_attn(qkv, seg_len, P, heads)
-        g_att = torch.empty_like(att)
-        ops.check(lib.sagnn_leaky_f32(att.data_ptr(), g.data_ptr(), g_att.data_ptr(), leaky, att.numel(), 1, st))
+        g_att = ops.leaky_bwd(att, g, leaky)
         dqkv = ops.seq_attn_bwd(qkv, g_att, seg_len, P, heads)
         y = ops.layernorm_td(x.view(R, 1, d), gamma.detach(), beta.detach()).view(R, d)     # not saved: recomputed
-        dWqkv = torch.zeros((d, 3 * d), dtype=torch.float32, device=dev)
-        dbqkv = torch.zeros(3 * d, dtype=torch.float32, device=dev)
-        # dW, db and dy as two products, not sagnn_attn_bwd_tail_f32: the fused tail scales its chunks of 32 rows against
+        # dW, db and dy as two products, not the fused tail (ops.attn_bwd_tail): it scales its chunks of 32 rows against
         # the gradient rows it has met, and a workgroup whose FIRST chunk holds only zero rows (a slab's padding: any
         # slot shorter than P - 32) returns NaN bias gradients (measured on the Gowalla-shaped set)
-        ops.dense_tn(y, dqkv, dWqkv, dbqkv)
-        dy = ops.dense_nn(dqkv, Wqkv.t().contiguous(), None, out=y)
-        dgamma = torch.zeros(d, dtype=torch.float32, device=dev)
-        dbeta = torch.zeros(d, dtype=torch.float32, device=dev)
-        ops.check(lib.sagnn_layernorm_td_bwd_f32(x.data_ptr(), d, dy.data_ptr(), d, R, 1, d, ops._vec("gamma", gamma.detach(), d),
-                                                 1e-12, dy.data_ptr(), d, dgamma.data_ptr(), dbeta.data_ptr(), st))
-        dx = ops.leaky_add(dy, g, 1.0)                                     # slope 1: dy + g, the residual's share
+        dy, dWqkv, dbqkv = _qkv_grads(y, dqkv, Wqkv, fused_tail=False, in_place=True)
+        dy = dy.view(R, 1, d)
+        dy, dgamma, dbeta = ops.layernorm_td_bwd(x.view(R, 1, d), dy, gamma.detach(), out=dy)
+        dx = ops.leaky_add(dy.view(R, d), g, 1.0)                                     # slope 1: dy + g, the residual's share
         return (dx, dgamma, dbeta) + _split_qkv_grads(dWqkv, dbqkv, d) + (None, None, None, None)
 
 
 class SeqPoolFn(torch.autograd.Function):
-    """x [n_slots * P, d] -> [n_slots, d]: the sum over each slot's real tokens (sagnn_seq_pool_f32); the backward
+    """x [n_slots * P, d] -> [n_slots, d]: the sum over each slot's real tokens (ops.seq_pool); the backward
     broadcasts, with zeros into the padding."""
 
     @staticmethod

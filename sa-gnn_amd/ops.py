@@ -73,6 +73,28 @@ def _f32_rows(name: str, t: torch.Tensor | None, d: int, rows: int | None = None
     return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), d)
 
 
+def _f32_flat(name: str, t: torch.Tensor, numel: int) -> int:
+    """data_ptr of a contiguous float32 device tensor of `numel` elements (any shape), checked; a valid pointer also
+    for an empty one."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda:
+        raise TypeError(f"{name}: expected a float32 device tensor")
+    if not t.is_contiguous() or t.numel() != numel:
+        raise ValueError(f"{name}: expected {numel} contiguous elements, got shape {tuple(t.shape)} strides {t.stride()}")
+    return _ptr_or_empty(t)
+
+
+def _ptr_or_empty(t: torch.Tensor) -> int:
+    """data_ptr, or a valid stand-in for an empty tensor (whose data_ptr is 0): the entries refuse NULL at any count."""
+    return t.data_ptr() or _empty_ptr(t.device)
+
+
+def _one_device(ref: torch.Tensor, **others):
+    """Every tensor among `others` (None = not given) lives on ref's device."""
+    for name, t in others.items():
+        if t is not None and t.device != ref.device:
+            raise ValueError(f"{name} on {t.device}, expected {ref.device}")
+
+
 def _check_weights(weights, nnz: int) -> torch.Tensor:
     """The edge weights of a plan as a host float32 tensor: nnz finite values (TypeError / ValueError otherwise)."""
     w = torch.as_tensor(weights)
@@ -769,6 +791,85 @@ def lstm_fwd(x: torch.Tensor, W: torch.Tensor, b: torch.Tensor, forget_bias: flo
     return out
 
 
+def _ntd_dense(name: str, x: torch.Tensor, n: int, t: int, d: int) -> int:
+    """x [n, t, d] float32 on the device with each node's (t, d) block contiguous; returns its node stride."""
+    xn, xt, xd, ld_n, _ = _ntd(name, x, dense_td=True)
+    if (xn, xt, xd) != (n, t, d):
+        raise ValueError(f"{name}: expected shape [{n}, {t}, {d}], got {tuple(x.shape)}")
+    return ld_n if n > 1 else max(ld_n, t * d)
+
+
+def lstm_fwd_train(x: torch.Tensor, W: torch.Tensor, b: torch.Tensor, forget_bias: float = 1.0):
+    """The training forward of the LSTM (sagnn_lstm_fwd_train_f32): x [n, t, d] (any node / interval strides) ->
+    (h [n, t, d] un-dropped, gates [n, t, 4d], cell [n, t, d]) as lstm_bwd / lstm_bwd_step read them."""
+    n, t, d, ld_n, ld_t = _ntd("x", x)
+    W_p, b_p = _f32_flat("W", W, 8 * d * d), _f32_flat("b", b, 4 * d)
+    _one_device(x, W=W, b=b)
+    h = torch.empty((n, t, d), dtype=torch.float32, device=x.device)
+    gates = torch.empty((n, t, 4 * d), dtype=torch.float32, device=x.device)
+    cell = torch.empty((n, t, d), dtype=torch.float32, device=x.device)
+    check(_lib.load().sagnn_lstm_fwd_train_f32(x.data_ptr(), ld_n, ld_t, n, t, d, W_p, b_p, float(forget_bias), None,
+                                               h.data_ptr(), t * d, gates.data_ptr(), cell.data_ptr(), _stream()))
+    return h, gates, cell
+
+
+def lstm_bwd_supported(d: int) -> bool:
+    """Whether the one-launch BPTT (lstm_bwd) runs at this width under the calling thread's engine."""
+    return bool(_lib.load().sagnn_lstm_bwd_supported(int(d)))
+
+
+def lstm_bwd_workspace_bytes(n: int, t: int, d: int) -> int:
+    """Bytes of gate gradients ([t, n, 4d]) lstm_bwd keeps for a deferred weight gradient."""
+    return int(_lib.load().sagnn_lstm_bwd_workspace_bytes(int(n), int(t), int(d)))
+
+
+def lstm_bwd(x: torch.Tensor, h: torch.Tensor, gates: torch.Tensor, cell: torch.Tensor, dh: torch.Tensor,
+             drop: torch.Tensor | None, W: torch.Tensor, deferred_dw: bool):
+    """Whole BPTT in one launch (sagnn_lstm_bwd_ws_f32, d in {32, 64}): x [n, t, d] (any node / interval strides), h /
+    gates / cell as lstm_fwd_train stored them, dh [n, t, d] (each node's block contiguous) = the gradient at the emitted
+    h, drop None or the [n, t, d] scale of the emitted h -> (dx [n, t, d], dW [2d, 4d], db [4d]).
+    deferred_dw: keep the gate gradients ([t, n, 4d], allocated here) and take the weight gradient as a second pass on
+    the f16 x 2 engine instead of the BPTT launch's fp32-MFMA product."""
+    n, t, d, ld_n, ld_t = _ntd("x", x)
+    h_p, g_p, c_p = _f32_flat("h", h, n * t * d), _f32_flat("gates", gates, n * t * 4 * d), _f32_flat("cell", cell, n * t * d)
+    ld_dh = _ntd_dense("dh", dh, n, t, d)
+    drop_p = None if drop is None else _f32_flat("drop", drop, n * t * d)
+    W_p = _f32_flat("W", W, 8 * d * d)
+    _one_device(x, h=h, gates=gates, cell=cell, dh=dh, drop=drop, W=W)
+    dev = x.device
+    dx = torch.empty((n, t, d), dtype=torch.float32, device=dev)
+    dW = torch.zeros((2 * d, 4 * d), dtype=torch.float32, device=dev)
+    db = torch.zeros(4 * d, dtype=torch.float32, device=dev)
+    need = lstm_bwd_workspace_bytes(n, t, d) if deferred_dw else 0
+    ws = torch.empty(need // 4, dtype=torch.float32, device=dev) if need else None
+    check(_lib.load().sagnn_lstm_bwd_ws_f32(x.data_ptr(), ld_n, ld_t, h_p, g_p, c_p, dh.data_ptr(), ld_dh, drop_p, W_p,
+                                            dx.data_ptr(), dW.data_ptr(), db.data_ptr(), n, t, d, _ptr(ws), need, _stream()))
+    return dx, dW, db
+
+
+def lstm_bwd_step(gates: torch.Tensor, cell: torch.Tensor, dh: torch.Tensor, drop: torch.Tensor | None,
+                  dh_rec: torch.Tensor | None, dc_in: torch.Tensor | None, dgates: torch.Tensor, dc_out: torch.Tensor,
+                  ts: int):
+    """Step ts of the generic BPTT (sagnn_lstm_bwd_step_f32): gates [n, t, 4d] / cell [n, t, d] of lstm_fwd_train,
+    dh [n, t, d] the gradient at the emitted h (drop: its [n, t, d] scale, or None), dh_rec [n, d] (any row stride)
+    and dc_in [n, d] the recurrent gradients from step ts + 1 (both None at the last step) -> dgates [n, 4d] and
+    dc_out [n, d], written."""
+    if gates.dim() != 3 or gates.shape[2] % 4:
+        raise ValueError(f"gates: expected [n, t, 4d], got {tuple(gates.shape)}")
+    n, t, d = int(gates.shape[0]), int(gates.shape[1]), int(gates.shape[2]) // 4
+    g_p, c_p = _f32_flat("gates", gates, n * t * 4 * d), _f32_flat("cell", cell, n * t * d)
+    ld_dh = _ntd_dense("dh", dh, n, t, d)
+    drop_p = None if drop is None else _f32_flat("drop", drop, n * t * d)
+    if (dh_rec is None) != (dc_in is None):
+        raise ValueError("dh_rec and dc_in go together (both, or neither at the last step)")
+    ld_rec = _f32_rows("dh_rec", dh_rec, d, n)
+    dc_in_p = None if dc_in is None else _f32_flat("dc_in", dc_in, n * d)
+    dg_p, dc_p = _f32_flat("dgates", dgates, n * 4 * d), _f32_flat("dc_out", dc_out, n * d)
+    _one_device(gates, cell=cell, dh=dh, drop=drop, dh_rec=dh_rec, dc_in=dc_in, dgates=dgates, dc_out=dc_out)
+    check(_lib.load().sagnn_lstm_bwd_step_f32(g_p, c_p, dh.data_ptr(), ld_dh, drop_p, _ptr(dh_rec), ld_rec, dc_in_p, dg_p,
+                                              dc_p, n, t, d, int(ts), _stream()))
+
+
 def layernorm_td(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-12,
                  out: torch.Tensor | None = None):
     """layer_norm over (t, d) per node (reference model.py:152-153): sagnn_layernorm_td_f32."""
@@ -780,6 +881,28 @@ def layernorm_td(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: 
                                              _vec("beta", beta, d), float(eps), out.data_ptr(), ldy,
                                              _stream()))
     return out
+
+
+def layernorm_td_bwd(x: torch.Tensor, g: torch.Tensor, gamma: torch.Tensor, eps: float = 1e-12,
+                     out: torch.Tensor | None = None):
+    """Backward of layernorm_td (sagnn_layernorm_td_bwd_f32): x the forward's input and g the gradient at its output,
+    both [n, t, d] with each node's (t, d) block contiguous (any node stride) -> (dx, dgamma [d], dbeta [d]). dx goes
+    to `out` (the same layout; out=g runs in place) or to a new tensor."""
+    n, t, d, ld_x, _ = _ntd("x", x, dense_td=True)
+    if n == 1:
+        ld_x = max(ld_x, t * d)
+    ld_g = _ntd_dense("g", g, n, t, d)
+    gamma_p = _f32_flat("gamma", gamma, d)
+    _one_device(x, g=g, gamma=gamma, out=out)
+    if out is None:
+        out, ld_o = torch.empty((n, t, d), dtype=torch.float32, device=x.device), t * d
+    else:
+        ld_o = _ntd_dense("out", out, n, t, d)
+    dgamma = torch.zeros(d, dtype=torch.float32, device=x.device)
+    dbeta = torch.zeros(d, dtype=torch.float32, device=x.device)
+    check(_lib.load().sagnn_layernorm_td_bwd_f32(x.data_ptr(), ld_x, g.data_ptr(), ld_g, n, t, d, gamma_p, float(eps),
+                                                 out.data_ptr(), ld_o, dgamma.data_ptr(), dbeta.data_ptr(), _stream()))
+    return out, dgamma, dbeta
 
 
 def mhsa_mean(x: torch.Tensor, Wq, bq, Wk, bk, Wv, bv, heads: int, out: torch.Tensor | None = None):
@@ -818,6 +941,63 @@ def ln_mhsa_mean(x: torch.Tensor, gamma, beta, Wq, bq, Wk, bk, Wv, bv, heads: in
         x.data_ptr(), ld, ldt, n, t, d, int(heads), _vec("gamma", gamma, d), _vec("beta", beta, d), float(eps),
         *_attn_ptrs(d, Wq, bq, Wk, bk, Wv, bv), out.data_ptr(), ldo, _ptr(ws), need, _stream()))
     return out
+
+
+def attn_bwd_front_supported(d: int, t: int, heads: int) -> bool:
+    """Whether attn_bwd_front covers the shape under the calling thread's engine."""
+    return bool(_lib.load().sagnn_attn_bwd_front_supported(int(d), int(t), int(heads)))
+
+
+def attn_bwd_front(x: torch.Tensor, gamma, beta, Wq, bq, Wk, bk, Wv, bv, heads: int, g_out: torch.Tensor,
+                   want_y: bool = True):
+    """The front of the attention backward in one launch (sagnn_attn_bwd_front_f32): y = LN(x), Q|K|V = y W + b and the
+    attention backward for g_out [n, d] (any row stride). x [n, t, d] (any node / interval strides) ->
+    (y [n*t, d] or None, dqkv [n*t, 3d]). gamma None = no layer norm (y = x, not written)."""
+    n, t, d, ld_n, ld_t = _ntd("x", x)
+    if (gamma is None) != (beta is None):
+        raise ValueError("gamma and beta go together (both, or neither for no layer norm)")
+    gamma_p, beta_p = (None, None) if gamma is None else (_f32_flat("gamma", gamma, d), _f32_flat("beta", beta, d))
+    w_p = _attn_ptrs(d, Wq, bq, Wk, bk, Wv, bv)
+    ld_g = _f32_rows("g_out", g_out, d, n)
+    _one_device(x, gamma=gamma, beta=beta, Wq=Wq, bq=bq, Wk=Wk, bk=bk, Wv=Wv, bv=bv, g_out=g_out)
+    dqkv = torch.empty((n * t, 3 * d), dtype=torch.float32, device=x.device)
+    y = torch.empty((n * t, d), dtype=torch.float32, device=x.device) if (want_y and gamma is not None) else None
+    check(_lib.load().sagnn_attn_bwd_front_f32(x.data_ptr(), ld_n, ld_t, n, t, d, int(heads), gamma_p, beta_p, 1e-12,
+                                               0 if gamma is None else 1, *w_p, g_out.data_ptr(), ld_g, dqkv.data_ptr(),
+                                               _ptr(y), _stream()))
+    return y, dqkv
+
+
+def attn_bwd(qkv: torch.Tensor, g_out: torch.Tensor, n: int, t: int, heads: int):
+    """The attention backward of mhsa_mean (sagnn_attn_bwd_f32), in place: qkv [n*t, 3d] contiguous (Q | K | V rows as
+    y W + b produced them) becomes dQ | dK | dV for g_out [n, d] (any row stride). Returns qkv."""
+    if qkv.dim() != 2 or qkv.shape[1] % 3:
+        raise ValueError(f"qkv: expected [n*t, 3d], got {tuple(qkv.shape)}")
+    n, t, d = int(n), int(t), int(qkv.shape[1]) // 3
+    qkv_p = _f32_flat("qkv", qkv, n * t * 3 * d)
+    ld_g = _f32_rows("g_out", g_out, d, n)
+    _one_device(qkv, g_out=g_out)
+    check(_lib.load().sagnn_attn_bwd_f32(qkv_p, g_out.data_ptr(), ld_g, n, t, d, int(heads), _stream()))
+    return qkv
+
+
+def attn_bwd_tail_supported(d: int) -> bool:
+    """Whether attn_bwd_tail runs at this width under the calling thread's engine."""
+    return bool(_lib.load().sagnn_attn_bwd_tail_supported(int(d)))
+
+
+def attn_bwd_tail(y2: torch.Tensor, dqkv: torch.Tensor, Wqkv: torch.Tensor, dWqkv: torch.Tensor, dbqkv: torch.Tensor):
+    """The tail of the attention backward in one pass over dqkv [rows, 3d] (sagnn_attn_bwd_tail_f32): dWqkv [d, 3d] +=
+    y2^T dqkv, dbqkv [3d] += its column sums (zero both first) and dy = dqkv Wqkv^T written OVER y2 [rows, d]; all
+    contiguous, Wqkv = [Wq | Wk | Wv]. Returns y2, now dy."""
+    if y2.dim() != 2:
+        raise ValueError(f"y2: expected [rows, d], got {tuple(y2.shape)}")
+    rows, d = int(y2.shape[0]), int(y2.shape[1])
+    y_p, dqkv_p = _f32_flat("y2", y2, rows * d), _f32_flat("dqkv", dqkv, rows * 3 * d)
+    W_p, dW_p, db_p = _f32_flat("Wqkv", Wqkv, 3 * d * d), _f32_flat("dWqkv", dWqkv, 3 * d * d), _f32_flat("dbqkv", dbqkv, 3 * d)
+    _one_device(y2, dqkv=dqkv, Wqkv=Wqkv, dWqkv=dWqkv, dbqkv=dbqkv)
+    check(_lib.load().sagnn_attn_bwd_tail_f32(y_p, dqkv_p, rows, d, W_p, dW_p, db_p, _stream()))
+    return y2
 
 
 def interval_fusion(x: torch.Tensor, p: dict, heads: int, out: torch.Tensor | None = None,
@@ -980,6 +1160,26 @@ def leaky_add(a: torch.Tensor, b: torch.Tensor | None, leaky: float, out: torch.
     return out
 
 
+def leaky(a: torch.Tensor, leaky: float):
+    """out = max(leaky*a, a) (sagnn_leaky_f32, forward form); contiguous float32."""
+    n = int(a.numel()) if isinstance(a, torch.Tensor) else 0
+    a_p = _f32_flat("a", a, n)
+    out = torch.empty_like(a)
+    check(_lib.load().sagnn_leaky_f32(a_p, None, _ptr_or_empty(out), float(leaky), n, 0, _stream()))
+    return out
+
+
+def leaky_bwd(a: torch.Tensor, g: torch.Tensor, leaky: float):
+    """da = g * (the slope of max(leaky*a, a) at a: `leaky` wherever a <= leaky*a) (sagnn_leaky_f32, backward form); a the
+    pre-activation, contiguous float32 tensors of equal size."""
+    n = int(a.numel()) if isinstance(a, torch.Tensor) else 0
+    a_p, g_p = _f32_flat("a", a, n), _f32_flat("g", g, n)
+    _one_device(a, g=g)
+    out = torch.empty_like(a)
+    check(_lib.load().sagnn_leaky_f32(a_p, g_p, _ptr_or_empty(out), float(leaky), n, 1, _stream()))
+    return out
+
+
 def pair_score(U: torch.Tensor, I: torch.Tensor, uids: torch.Tensor, iids: torch.Tensor, S: torch.Tensor | None = None,
                A: torch.Tensor | None = None, locs: torch.Tensor | None = None, leaky: float = 1.0):
     """preds[e] = <U[uids[e]], I[iids[e]]> + <leaky(S[locs[e]]), A[iids[e]]> (sagnn_pair_score_f32)."""
@@ -994,6 +1194,159 @@ def pair_score(U: torch.Tensor, I: torch.Tensor, uids: torch.Tensor, iids: torch
         0 if S is None else _f32_rows("S", S, d), _ptr(A), 0 if A is None else _f32_rows("A", A, d),
         uids.data_ptr(), iids.data_ptr(), _ptr(locs), float(leaky), out.data_ptr(), n, d, _stream()))
     return out
+
+
+def _zeros_like_table(t: torch.Tensor) -> torch.Tensor:
+    """The dense zero gradient of a table (the kernels add into dense rows whatever the table's own stride)."""
+    return torch.zeros(tuple(t.shape), dtype=torch.float32, device=t.device)
+
+
+def pair_score_bwd(U: torch.Tensor, I: torch.Tensor, uids: torch.Tensor, iids: torch.Tensor, g: torch.Tensor,
+                   S: torch.Tensor | None = None, A: torch.Tensor | None = None, locs: torch.Tensor | None = None,
+                   leaky: float = 1.0):
+    """Gradients of pair_score for g [n_pairs] (sagnn_pair_score_bwd_f32, a scatter with float atomics): returns
+    (dU, dI, dS, dA), dense and shaped like their tables; dS and dA are None without the second term. S, A and locs are
+    given together or not at all. When A is I, dA IS dI: both sums land in the one tensor."""
+    if U.dim() != 2:
+        raise ValueError(f"U: expected a [rows, d] table, got {tuple(U.shape)}")
+    d, n = int(U.shape[1]), int(uids.numel())
+    ldu, ldi = _f32_rows("U", U, d), _f32_rows("I", I, d)
+    head = S is not None
+    if (A is not None) != head or (locs is not None) != head:
+        raise ValueError("S, A and locs go together (all or none)")
+    lds, lda = _f32_rows("S", S, d), _f32_rows("A", A, d)
+    uids_p, iids_p = _idx_ptr("uids", uids, torch.int32, n), _idx_ptr("iids", iids, torch.int32, n)
+    locs_p = _idx_ptr("locs", locs, torch.int32, n) if head else None
+    g_p = _f32_flat("g", g, n)
+    _one_device(U, I=I, S=S, A=A, uids=uids, iids=iids, locs=locs, g=g)
+    dU, dI = _zeros_like_table(U), _zeros_like_table(I)
+    dS = _zeros_like_table(S) if head else None
+    dA = (dI if A is I else _zeros_like_table(A)) if head else None
+    check(_lib.load().sagnn_pair_score_bwd_f32(U.data_ptr(), ldu, I.data_ptr(), ldi, _ptr(S), lds, _ptr(A), lda, uids_p, iids_p,
+                                               locs_p, float(leaky), g_p, dU.data_ptr(), dI.data_ptr(), _ptr(dS), _ptr(dA),
+                                               n, d, _stream()))
+    return dU, dI, dS, dA
+
+
+def _pair_args(X, Y, uids, iids):
+    """The checked leading arguments of the SSL pair entries and (n_pairs, d)."""
+    if X.dim() != 2:
+        raise ValueError(f"X: expected a [rows, d] table, got {tuple(X.shape)}")
+    d, n = int(X.shape[1]), int(uids.numel())
+    lead = (X.data_ptr(), _f32_rows("X", X, d), Y.data_ptr(), _f32_rows("Y", Y, d), _idx_ptr("uids", uids, torch.int32, n),
+            _idx_ptr("iids", iids, torch.int32, n))
+    _one_device(X, Y=Y, uids=uids, iids=iids)
+    return lead, n, d
+
+
+def prod_leaky_sum(X: torch.Tensor, Y: torch.Tensor, uids: torch.Tensor, iids: torch.Tensor, leaky: float):
+    """s[e] = sum_j leaky(X[uids[e]][j] * Y[iids[e]][j]) (sagnn_prod_leaky_sum_f32) -> [n_pairs]."""
+    lead, n, d = _pair_args(X, Y, uids, iids)
+    out = torch.empty(n, dtype=torch.float32, device=X.device)
+    check(_lib.load().sagnn_prod_leaky_sum_f32(*lead, float(leaky), _ptr_or_empty(out), n, d, _stream()))
+    return out
+
+
+def prod_leaky_sum_bwd(X: torch.Tensor, Y: torch.Tensor, uids: torch.Tensor, iids: torch.Tensor, leaky: float,
+                       g: torch.Tensor):
+    """Gradients of prod_leaky_sum for g [n_pairs] (sagnn_prod_leaky_sum_bwd_f32, a scatter with float atomics):
+    (dX, dY), dense and shaped like their tables."""
+    lead, n, d = _pair_args(X, Y, uids, iids)
+    g_p = _f32_flat("g", g, n)
+    _one_device(X, g=g)
+    dX, dY = _zeros_like_table(X), _zeros_like_table(Y)
+    check(_lib.load().sagnn_prod_leaky_sum_bwd_f32(*lead, float(leaky), g_p, dX.data_ptr(), dY.data_ptr(), n, d, _stream()))
+    return dX, dY
+
+
+def _meta_args(F, V, uids):
+    """The checked leading arguments of the meta-feature entries and (n, d). F and V are tables over the same users."""
+    if F.dim() != 2:
+        raise ValueError(f"F: expected a [rows, d] table, got {tuple(F.shape)}")
+    d, n = int(F.shape[1]), int(uids.numel())
+    ldf, ldv = _f32_rows("F", F, d), _f32_rows("V", V, d, int(F.shape[0]))
+    lead = (F.data_ptr(), ldf, V.data_ptr(), ldv, _idx_ptr("uids", uids, torch.int32, n))
+    _one_device(F, V=V, uids=uids)
+    return lead, n, d
+
+
+def meta_features(F: torch.Tensor, V: torch.Tensor, uids: torch.Tensor):
+    """m[e] = [F[u] * V[u] | F[u] | V[u]], u = uids[e] (sagnn_meta_features_f32) -> [n, 3d] contiguous."""
+    lead, n, d = _meta_args(F, V, uids)
+    out = torch.empty((n, 3 * d), dtype=torch.float32, device=F.device)
+    check(_lib.load().sagnn_meta_features_f32(*lead, _ptr_or_empty(out), n, d, _stream()))
+    return out
+
+
+def meta_features_bwd(F: torch.Tensor, V: torch.Tensor, uids: torch.Tensor, dm: torch.Tensor):
+    """Gradients of meta_features for dm [n, 3d] contiguous (sagnn_meta_features_bwd_f32, a scatter with float
+    atomics): (dF, dV), dense and shaped like their tables."""
+    lead, n, d = _meta_args(F, V, uids)
+    if dm.dim() != 2 or dm.shape[1] != 3 * d:
+        raise ValueError(f"dm: expected [{n}, {3 * d}], got {tuple(dm.shape)}")
+    dm_p = _f32_flat("dm", dm, n * 3 * d)
+    _one_device(F, dm=dm)
+    dF, dV = _zeros_like_table(F), _zeros_like_table(V)
+    check(_lib.load().sagnn_meta_features_bwd_f32(*lead, dm_p, dF.data_ptr(), dV.data_ptr(), n, d, _stream()))
+    return dF, dV
+
+
+def _rowdot_A(A: torch.Tensor, k: int) -> tuple[int, int]:
+    """A [n, kp] float32 with kp >= k columns and unit inner stride (the row-dot reads the first k): (n, row stride)."""
+    if not isinstance(A, torch.Tensor) or A.dim() != 2 or A.shape[1] < k:
+        raise ValueError(f"A: expected [n, at least {k}], got {tuple(A.shape) if isinstance(A, torch.Tensor) else type(A)}")
+    return int(A.shape[0]), _f32_rows("A", A, int(A.shape[1]))
+
+
+def rowdot_sigmoid(A: torch.Tensor, w3: torch.Tensor, b3: torch.Tensor, k: int):
+    """w[e] = sigmoid(<A[e, :k], w3> + b3) (sagnn_rowdot_sigmoid_f32): A [n, kp >= k] (any row stride), w3 [k], b3 [1]
+    -> [n]."""
+    k = int(k)
+    n, lda = _rowdot_A(A, k)
+    w3_p, b3_p = _f32_flat("w3", w3, k), _f32_flat("b3", b3, 1)
+    _one_device(A, w3=w3, b3=b3)
+    out = torch.empty(n, dtype=torch.float32, device=A.device)
+    check(_lib.load().sagnn_rowdot_sigmoid_f32(_ptr_or_empty(A), lda, w3_p, b3_p, _ptr_or_empty(out), n, k, _stream()))
+    return out
+
+
+def rowdot_sigmoid_bwd(A: torch.Tensor, w3: torch.Tensor, w: torch.Tensor, dw: torch.Tensor, k: int):
+    """Gradients of rowdot_sigmoid given its output w [n] and dw [n] (sagnn_rowdot_sigmoid_bwd_f32): (dA shaped like A,
+    contiguous, columns >= k zero; dw3 [k]; db3 [1])."""
+    k = int(k)
+    n, lda = _rowdot_A(A, k)
+    kp = int(A.shape[1])
+    w3_p, w_p, dw_p = _f32_flat("w3", w3, k), _f32_flat("w", w, n), _f32_flat("dw", dw, n)
+    _one_device(A, w3=w3, w=w, dw=dw)
+    dA = _zeros_like_table(A)
+    dw3 = torch.zeros(k, dtype=torch.float32, device=A.device)
+    db3 = torch.zeros(1, dtype=torch.float32, device=A.device)
+    check(_lib.load().sagnn_rowdot_sigmoid_bwd_f32(_ptr_or_empty(A), lda, w3_p, w_p, dw_p, _ptr_or_empty(dA), kp,
+                                                   dw3.data_ptr(), db3.data_ptr(), n, k, _stream()))
+    return dA, dw3, db3
+
+
+def hinge(pos: torch.Tensor, neg: torch.Tensor, wp: torch.Tensor | None = None, wn: torch.Tensor | None = None,
+          sp: torch.Tensor | None = None, sn: torch.Tensor | None = None, scale: float = 1.0):
+    """loss = scale * sum max(0, 1 - S * (pos - neg)), S = wp * sp - wn * sn, or 1 without weights (sagnn_hinge_f32);
+    contiguous float32 [n] each, the four weights given together or not at all (sp / sn are constants). Returns
+    (loss [1], dpos, dneg, dwp, dwn): the gradients of the loss, dwp / dwn None without weights."""
+    n = int(pos.numel()) if isinstance(pos, torch.Tensor) else 0
+    pos_p, neg_p = _f32_flat("pos", pos, n), _f32_flat("neg", neg, n)
+    weights = {"wp": wp, "wn": wn, "sp": sp, "sn": sn}
+    weighted = wp is not None
+    if any((v is not None) != weighted for v in weights.values()):
+        raise ValueError("wp, wn, sp and sn go together (all or none)")
+    w_p = [_f32_flat(k, v, n) for k, v in weights.items()] if weighted else [None] * 4
+    _one_device(pos, neg=neg, **weights)
+    dev = pos.device
+    loss = torch.zeros(1, dtype=torch.float32, device=dev)
+    dpos, dneg = torch.empty_like(pos), torch.empty_like(neg)
+    dwp, dwn = (torch.empty_like(wp), torch.empty_like(wn)) if weighted else (None, None)
+    check(_lib.load().sagnn_hinge_f32(pos_p, neg_p, *w_p, float(scale), loss.data_ptr(), _ptr_or_empty(dpos),
+                                      _ptr_or_empty(dneg), _ptr_or_empty(dwp) if weighted else None,
+                                      _ptr_or_empty(dwn) if weighted else None, n, _stream()))
+    return loss, dpos, dneg, dwp, dwn
 
 
 _topk_ws: dict = {}      # device -> workspace of sagnn_score_topk_f32, grown on demand (no allocation once warm)
@@ -1217,18 +1570,20 @@ def candidate_rank(U: torch.Tensor, I: torch.Tensor, uids: torch.Tensor, cand: t
 _empty_ptrs: dict = {}   # device -> a 16-byte buffer standing in for empty tensors (an empty tensor's data_ptr is 0)
 
 
+def _empty_ptr(device) -> int:
+    buf = _empty_ptrs.get(device)
+    if buf is None:
+        buf = _empty_ptrs[device] = torch.zeros(4, dtype=torch.int32, device=device)
+    return buf.data_ptr()
+
+
 def _idx_ptr(name: str, t: torch.Tensor, dtype, numel: int | None = None) -> int:
     """data_ptr of a contiguous index tensor on the device, checked; a valid pointer also for an empty one."""
     if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_cuda or not t.is_contiguous():
         raise TypeError(f"{name}: expected a contiguous {dtype} device tensor")
     if numel is not None and t.numel() != numel:
         raise ValueError(f"{name}: expected {numel} elements, got {t.numel()}")
-    if t.numel():
-        return t.data_ptr()
-    buf = _empty_ptrs.get(t.device)
-    if buf is None:
-        buf = _empty_ptrs[t.device] = torch.zeros(4, dtype=torch.int32, device=t.device)
-    return buf.data_ptr()
+    return t.data_ptr() if t.numel() else _empty_ptr(t.device)
 
 
 def _out(n: int, dtype, device) -> torch.Tensor:

@@ -87,16 +87,15 @@ def test_interval_fusion_backward_vs_autograd(dev, d, t, n, heads):
     """Every gradient of the fusion (x and all ten parameter tensors) against float64 autograd. The shapes of
     GENERIC_ROUTE must run the generic entries (test ids: "generic" selects the per-kernel tests below, these cases
     assert their route here)."""
-    from sa_gnn_amd import _lib
+    from sa_gnn_amd import _lib, ops
     from sa_gnn_amd import autograd as ag
     if (d, t, n, heads) in GENERIC_ROUTE:
-        lib = _lib.load()
         # the backward runs on PyTorch's autograd thread, whose engine is the default one, as this thread's is
-        assert ag.FUSED_ATTN_BWD and ag.FUSED_BPTT and lib.sagnn_get_engine() == 0
-        assert not lib.sagnn_attn_bwd_front_supported(d, t, heads), "layernorm_td + dense_nn + sagnn_attn_bwd_f32 must run"
+        assert ag.FUSED_ATTN_BWD and ag.FUSED_BPTT and _lib.load().sagnn_get_engine() == 0
+        assert not ops.attn_bwd_front_supported(d, t, heads), "layernorm_td + dense_nn + sagnn_attn_bwd_f32 must run"
         if d > 64:
-            assert not lib.sagnn_attn_bwd_tail_supported(d), "dense_tn + dense_nn must run"
-            assert not lib.sagnn_lstm_bwd_supported(d), "the sagnn_lstm_bwd_step_f32 loop must run"
+            assert not ops.attn_bwd_tail_supported(d), "dense_tn + dense_nn must run"
+            assert not ops.lstm_bwd_supported(d), "the sagnn_lstm_bwd_step_f32 loop must run"
     rng = np.random.default_rng(d + t + n)
     x = rng.standard_normal((n, t, d)).astype(np.float32)
     p = O.init_fusion_params(d, rng)
@@ -134,7 +133,7 @@ def test_interval_fusion_backward_generic_under_valu(dev, d, t, n, heads):
     """Under the VALU engine the attention backward has no fused kernels at any shape: layernorm_td + dense_nn +
     sagnn_attn_bwd_f32, then dense_tn / dense_nn. The engine is per calling thread and torch runs a backward on a
     thread of its own, so the two halves are called here directly, on the thread that selected the engine."""
-    from sa_gnn_amd import _lib, ops
+    from sa_gnn_amd import ops
     from sa_gnn_amd import autograd as ag
     rng = np.random.default_rng(d + t + n)
     x = rng.standard_normal((n, t, d)).astype(np.float32)
@@ -148,8 +147,7 @@ def test_interval_fusion_backward_generic_under_valu(dev, d, t, n, heads):
     pd = {k: torch.from_numpy(v).to(dev) for k, v in p.items()}
     names = ("lstm_W", "lstm_b", "ln_gamma", "ln_beta", "Wq", "bq", "Wk", "bk", "Wv", "bv")
     with ops.engine("valu"):
-        lib = _lib.load()
-        assert not lib.sagnn_attn_bwd_front_supported(d, t, heads) and not lib.sagnn_attn_bwd_tail_supported(d)
+        assert not ops.attn_bwd_front_supported(d, t, heads) and not ops.attn_bwd_tail_supported(d)
         got, h, gates, cell = ag._fusion_forward(xd, *(pd[k] for k in names), heads, None)
         grads = ag._fusion_backward(xd, *(pd[k] for k in names if k != "lstm_b"), h, gates, cell, None, heads,
                                     torch.from_numpy(gout).to(dev))

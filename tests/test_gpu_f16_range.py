@@ -159,11 +159,7 @@ def test_lstm_weight_gradient_pass_at_any_gradient_scale(dev, d, t, n, pattern):
     g = torch.Generator(device="cpu").manual_seed(d * 3 + t)
     x = (torch.rand((n, t, d), generator=g) * 2 - 1).to(dev)
     p = random_fusion_params(d, dev, 11)
-    h = torch.empty((n, t, d), device=dev)
-    gates = torch.empty((n, t, 4 * d), device=dev)
-    cell = torch.empty((n, t, d), device=dev)
-    ops.check(lib.sagnn_lstm_fwd_train_f32(x.data_ptr(), t * d, d, n, t, d, p["lstm_W"].data_ptr(), p["lstm_b"].data_ptr(), 1.0, None,
-                                           h.data_ptr(), t * d, gates.data_ptr(), cell.data_ptr(), None))
+    h, gates, cell = ops.lstm_fwd_train(x, p["lstm_W"], p["lstm_b"])
     scale = torch.from_numpy(_row_scales(n, rng, pattern).astype(np.float32)).to(dev)
     dh = torch.randn((n, t, d), generator=g).to(dev) * scale[:, None, None]
     outs = []
@@ -208,11 +204,7 @@ def test_lstm_weight_gradient_pass_with_an_output_dropout_mask(dev, d, t, n):
     x = (torch.rand((n, t, d), generator=g) * 2 - 1).to(dev)
     p = random_fusion_params(d, dev, 5)
     drop = ((torch.rand((n, t, d), generator=g) < 0.5).float() * 2.0).to(dev)
-    h = torch.empty((n, t, d), device=dev)
-    gates = torch.empty((n, t, 4 * d), device=dev)
-    cell = torch.empty((n, t, d), device=dev)
-    ops.check(lib.sagnn_lstm_fwd_train_f32(x.data_ptr(), t * d, d, n, t, d, p["lstm_W"].data_ptr(), p["lstm_b"].data_ptr(), 1.0, None,
-                                           h.data_ptr(), t * d, gates.data_ptr(), cell.data_ptr(), None))
+    h, gates, cell = ops.lstm_fwd_train(x, p["lstm_W"], p["lstm_b"])
     dh = torch.randn((n, t, d), generator=g).to(dev)
     outs = []
     for use_ws in (False, True):

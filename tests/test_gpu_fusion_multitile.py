@@ -120,9 +120,8 @@ def test_training_forward_and_backward_many_tiles_per_block(dev, d, t, n):
 def test_attn_bwd_front_many_tiles_per_block(dev, d, t, n):
     """sagnn_attn_bwd_front_f32 alone: y = LN(x) and dQ|dK|dV against float64 autograd (d = 128: d_k = 8, the two
     column halves of Q|K|V in separate workgroups, y stored by one of them)."""
-    from sa_gnn_amd import _lib
-    assert _lib.load().sagnn_attn_bwd_front_supported(d, t, 16)
-    from sa_gnn_amd import autograd as ag
+    from sa_gnn_amd import ops
+    assert ops.attn_bwd_front_supported(d, t, 16)
     rng = np.random.default_rng(d * 7 + t)
     heads, dk = 16, d // 16
     x = rng.standard_normal((n, t, d)).astype(np.float32)
@@ -137,7 +136,7 @@ def test_attn_bwd_front_many_tiles_per_block(dev, d, t, n):
     attn = scores / (scores.sum(dim=-1, keepdim=True) + 1e-8)
     out = (attn @ v).permute(0, 2, 1, 3).reshape(n, t, d).mean(dim=1)
     (out * torch.tensor(gout, dtype=torch.float64)).sum().backward()
-    y_got, dqkv = ag._attn_bwd_front(torch.from_numpy(x).to(dev), pd["ln_gamma"], pd["ln_beta"], pd["Wq"], pd["bq"],
+    y_got, dqkv = ops.attn_bwd_front(torch.from_numpy(x).to(dev), pd["ln_gamma"], pd["ln_beta"], pd["Wq"], pd["bq"],
                                      pd["Wk"], pd["bk"], pd["Wv"], pd["bv"], heads, torch.from_numpy(gout).to(dev))
     _check(y_got.view(n, t, d), y.numpy(), "y")
     want = qkv.grad.numpy().reshape(n * t, 3 * d)
@@ -232,13 +231,7 @@ def test_lstm_training_forward_beyond_the_f16_range(dev):
     x[100, 1, 5] = 7e4
     p, pd = _params(d, rng, dev)
     xd = torch.from_numpy(x).to(dev)
-    lib = ops._lib.load()
-    h = torch.empty((n, t, d), device=dev)
-    gates = torch.empty((n, t, 4 * d), device=dev)
-    cell = torch.empty((n, t, d), device=dev)
-    ops.check(lib.sagnn_lstm_fwd_train_f32(xd.data_ptr(), xd.stride(0), xd.stride(1), n, t, d, pd["lstm_W"].data_ptr(),
-                                           pd["lstm_b"].data_ptr(), 1.0, None, h.data_ptr(), t * d, gates.data_ptr(),
-                                           cell.data_ptr(), ops._stream()))
+    h, gates, cell = ops.lstm_fwd_train(xd, pd["lstm_W"], pd["lstm_b"])
     # the stored activations (sigmoid(i), tanh(j), sigmoid(f + 1), sigmoid(o)) and cell states, float64, as O.basic_lstm steps
     x64, W64, b64 = x.astype(np.float64), p["lstm_W"].astype(np.float64), p["lstm_b"].astype(np.float64)
     hh, cc = np.zeros((n, d)), np.zeros((n, d))
