@@ -7,6 +7,33 @@
 //   tn:  dW[DIN,DOUT] += X[n, DIN]^T @ G[n, DOUT], db += colsum(G)   reduction over the n rows
 //
 // DIN, DOUT are multiples of 32; W (DIN*DOUT*4 bytes) must fit LDS next to the staging tiles.
+//
+// Which kernel a call runs (tests/test_gpu_dense_routes.py restates this table and runs every row). Rows are tried top to
+// bottom; the first that holds is taken. CUs = cu_count_current(); 36864 = kLdsFloatsForW, the floats of W that fit the
+// 160 KiB of LDS next to the four 32 x 32 staging tiles.
+//
+// stage (function)                  taken when                          runs
+// ---------------------------------------------------------------------------------------------------------------------
+// nn  (dense_nn_any)                din * dout > 36864                  gemm_nn (dense_gemm.hip)
+//                                   dout <= 256                         dense_nn_kernel<dout / 32>, one launch ("resident")
+//                                   otherwise                           one dense_nn_kernel<cw / 32> launch per column slice
+//                                                                         c0 = 0, 256, ...; cw = min(256, dout - c0), with
+//                                                                         bias + c0, Y + c0 and W + c0 at ldw = dout ("sliced")
+// nn  piece (nn_piece, launch_nn)   always                              dense_nn_kernel<CT>, CT = cw / 32 in 1 .. 8;
+//                                                                         min(ceil(n / 128), CUs) blocks, a block walks the
+//                                                                         128-row tiles blockIdx.x, + gridDim.x, ...
+// tn  (dense_tn_any)                din > 128 or dout > 256             gemm_tn, one segment (dense_gemm.hip)
+//                                   otherwise                           tn_piece once (the r0 / c0 loops run one round)
+// tn  piece (tn_piece, launch_tn)   tiles = (din / 32) * (dout / 32),   dense_tn_kernel<TPW, 32, 12>, TPW the first of
+//                                     tpw = ceil(tiles / 4)               1, 2, 3, 4, 8 that is >= tpw; wave w owns tiles
+//                                                                         w * TPW .. w * TPW + TPW - 1, those past the last
+//                                                                         are recomputed as the last tile and dropped;
+//                                                                         min(ceil(n / 32), CUs * (2 if TPW <= 4 and
+//                                                                         LDS <= 72 KiB else 1)) blocks, 32-row chunks
+// tn  segments (sagnn_dense_tn_seg) always                              gemm_tn
+//
+// The k0 loop of dense_nn_any cannot run a second round: past the first row din * dout <= 36864, and cw <= dout gives
+// kmax = floor(36864 / cw / 32) * 32 >= din (din is a multiple of 32). So it is no route of its own, and k0 > 0 (no bias, accumulate forced on) never happens.
 #include "common.h"
 
 namespace {

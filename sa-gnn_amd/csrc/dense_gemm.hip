@@ -235,6 +235,13 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_tn_kernel(const float* __res
 namespace sagnn {
 
 // Y (+)= X [n, din] @ W [din, dout] (+ bias); din a multiple of 32, dout of 4, 16-byte aligned rows (checked by the callers)
+//
+// by = ceil(dout / 128) column tiles (the last may be narrower: col >= N guards the loads of B and the stores).
+//
+// taken when                                  runs
+// --------------------------------------------------------------------------------------------------------------------
+// ceil(n / 128) * by < 8 * CUs                gemm_nn_kernel<1>: 64 x 128 block tiles, grid (ceil(n / 64), by)
+// otherwise                                   gemm_nn_kernel<2>: 128 x 128 block tiles, grid (ceil(n / 128), by)
 int gemm_nn(const float* X, int64_t ldx, int64_t n, int din, int dout, const float* W, int64_t ldw, const float* bias, float* Y,
             int64_t ldy, int accumulate, hipStream_t s) {
   const int by = (dout + BN - 1) / BN;
@@ -260,6 +267,18 @@ int gemm_nn(const float* X, int64_t ldx, int64_t n, int din, int dout, const flo
 
 // dW [din, dout] += X^T @ G over n_seg segments of seg_rows rows (row i of segment s: X + s * xseg + i * ldx, G alike),
 // db [dout] += column sums of G (db may be NULL)
+//
+// One kernel, gemm_tn_kernel, on a grid (mt * nt, splits): mt = ceil(din / 128) row tiles and nt = ceil(dout / 128) column
+// tiles of dW (the last of either may be narrower), the n = seg_rows * n_seg rows cut into splits of k_per rows.
+//
+// step                taken when                                  gives
+// --------------------------------------------------------------------------------------------------------------------
+// splits wanted       always                                      ceil(2 * CUs / (mt * nt))
+// cap                 wanted > ceil(n / 128)                      splits = ceil(n / 128) ("capped": no more splits
+//                                                                   than n has pieces of 128 rows)
+// k_per               always                                      ceil(n / splits) rounded up to a multiple of 32
+// splits launched     always                                      ceil(n / k_per) (<= the above; the last may be ragged)
+// db                  db given                                    added by the blocks of row tile mt = 0 only
 int gemm_tn(const float* X, int64_t ldx, int64_t xseg, const float* G, int64_t ldg, int64_t gseg, int64_t seg_rows, int64_t n_seg,
             int din, int dout, float* dW, int64_t lddw, float* db, hipStream_t s) {
   const int64_t n = seg_rows * n_seg;
