@@ -997,6 +997,22 @@ int ln_mhsa_mean_mfma(const SeqView& v, const AttnParams& a, float* out, int64_t
   return fail(SAGNN_ERR_DIM, "MFMA attention supports d = 32 or 64, got %d", v.d);
 }
 
+// Which calls of sagnn_attn_bwd_front_f32 reach this kernel (select_attn_bwd_front, engine.cpp; tests/test_gpu_bwd_routes.py
+// restates the selector and runs every row): d in {32, 64}, t in MfmaBwdFrontT, d_k = d / heads in {2, 4}, behind the
+// Split row, which takes 16 heads under every engine but f32.
+//
+// engine        d    heads   d_k    runs
+// ---------------------------------------------------------------------------------------------------------------------
+// f32           32   16      2      ln_mhsa_mean_mfma_kernel<32, T, true>, attention_pairs_bwd<32, 2, QS, T>
+// f32           64   16      4      ln_mhsa_mean_mfma_kernel<64, T, true>, attention_pairs_bwd<64, 4, QS, T>
+// any           32   8       4      ln_mhsa_mean_mfma_kernel<32, T, true>, attention_pairs_bwd<32, 4, QS, T>
+// any           64   32      2      ln_mhsa_mean_mfma_kernel<64, T, true>, attention_pairs_bwd<64, 2, QS, T>
+// f16x2, valu   32, 64   16         the Split row (attn_split.hip), not this kernel
+//
+// T in {1, 2, 3, 4, 5, 6, 8}: 2 x 7 x 2 = 28 kernel / branch combinations. min(ceil(n / tile), CUs) blocks, a tile =
+// 4 waves x (32 / T) nodes; a wave's (32 / T) * heads (node, head) pairs go over its 64 lanes, so above 64 pairs a lane
+// takes its upstream gradient from gpre[1 ..] (every shape at d = 64 / d_k = 2; d_k = 4 at d = 32 up to T = 3; the
+// 16-head shapes up to T = 6).
 template <int D>
 static int attn_bwd_front_mfma_d(const SeqView& v, const AttnParams& a, const AttnBwdOut& b, hipStream_t s) {
   int rc;

@@ -104,7 +104,9 @@ def test_fusion_backward_dx_per_node_at_any_gradient_scale(dev, d, t, n, engine)
     """The whole fusion backward (attention-backward front and tail, layer-norm backward, BPTT) with the upstream
     gradient of node i scaled by 1, 1e-6, 1e-9 or 1e-12 (reference: --ssl_reg 1e-6 next to hinge rows, gowalla.sh:1).
     The fusion is independent per node, so dx[i] scales with its node's factor: every node's [t, d] block is judged at
-    1e-4 of its own largest entry against float64 autograd."""
+    1e-4 of its own largest entry against float64 autograd. The engine is per calling thread and torch runs a backward
+    on a thread of its own, so the two halves are called here directly, on the thread that selected the engine: under
+    "f32" that is the fp32-MFMA front, the fp32-MFMA tail and the one-launch BPTT."""
     from sa_gnn_amd import autograd as ag
     from sa_gnn_amd import ops
     rng = np.random.default_rng(d * 10 + t)
@@ -115,14 +117,18 @@ def test_fusion_backward_dx_per_node_at_any_gradient_scale(dev, d, t, n, engine)
     tx = torch.tensor(x, dtype=torch.float64, requires_grad=True)
     tp = {k: torch.tensor(v, dtype=torch.float64, requires_grad=True) for k, v in p.items()}
     (O.torch_interval_fusion(tx, tp, 16) * torch.tensor(gout, dtype=torch.float64)).sum().backward()
-    xd = torch.from_numpy(x).to(dev).requires_grad_(True)
-    pd = {k: torch.from_numpy(v).to(dev).requires_grad_(True) for k, v in p.items()}
+    xd = torch.from_numpy(x).to(dev)
+    pd = {k: torch.from_numpy(v).to(dev) for k, v in p.items()}
+    names = ("lstm_W", "lstm_b", "ln_gamma", "ln_beta", "Wq", "bq", "Wk", "bk", "Wv", "bv")
     with ops.engine(engine):
-        ag.interval_fusion(xd, pd, 16).backward(torch.from_numpy(gout).to(dev))
-    _per_row_ok(xd.grad.cpu().numpy(), tx.grad.numpy(), "dx")
+        _, h, gates, cell = ag._fusion_forward(xd, *(pd[k] for k in names), 16, None)
+        grads = ag._fusion_backward(xd, *(pd[k] for k in names if k != "lstm_b"), h, gates, cell, None, 16,
+                                    torch.from_numpy(gout).to(dev))
+    assert ops.get_engine() == "f16x2"
+    _per_row_ok(grads[0].cpu().numpy(), tx.grad.numpy(), "dx")
     # parameter gradients: sums over all nodes, dominated by the ordinary-sized ones
-    for k in p:
-        a, b = pd[k].grad.cpu().numpy().astype(np.float64), tp[k].grad.numpy()
+    for k, g in zip(names, grads[1:]):
+        a, b = g.cpu().numpy().astype(np.float64), tp[k].grad.numpy()
         floor = 5e-6 * max(1.0, np.sqrt(n * t / 1000.0))      # accumulation noise of sums that cancel to ~0 (test_gpu_backward)
         assert (np.abs(a - b) <= 1e-4 * np.abs(b) + max(2e-5 * np.abs(b).max(), floor)).all(), k
 

@@ -115,6 +115,23 @@ def test_training_forward_and_backward_many_tiles_per_block(dev, d, t, n):
         assert not bad.any(), f"{name}: {int(bad.sum())}/{bad.size} off, worst {np.abs(a - b)[bad].max():.3e} (scale {np.abs(b).max():.3e})"
 
 
+def attn_bwd_front_reference(x, p, gout, heads, dtype=torch.float64, layer_norm=True):
+    """What sagnn_attn_bwd_front_f32 computes, by torch autograd in `dtype`: y = LN(x) [n, t, d] (x itself without layer
+    norm) and the gradient [n*t, 3d] of sum(out * gout) at Q|K|V = y W + b, out the mean over t of the attention."""
+    n, t, d = x.shape
+    dk = d // heads
+    tx = torch.tensor(x, dtype=dtype)
+    tp = {k: torch.tensor(v, dtype=dtype) for k, v in p.items()}
+    y = O.torch_layer_norm_td(tx, tp["ln_gamma"], tp["ln_beta"]) if layer_norm else tx
+    qkv = torch.cat([y @ tp["Wq"] + tp["bq"], y @ tp["Wk"] + tp["bk"], y @ tp["Wv"] + tp["bv"]], dim=2).requires_grad_(True)
+    q, k, v = (qkv[:, :, i * d:(i + 1) * d].reshape(n, t, heads, dk).permute(0, 2, 1, 3) for i in range(3))
+    scores = torch.exp((q @ k.transpose(-1, -2)) / float(np.sqrt(dk)))      # Utils/attention.py:38-44
+    attn = scores / (scores.sum(dim=-1, keepdim=True) + 1e-8)
+    out = (attn @ v).permute(0, 2, 1, 3).reshape(n, t, d).mean(dim=1)
+    (out * torch.tensor(gout, dtype=dtype)).sum().backward()
+    return y.numpy(), qkv.grad.numpy().reshape(n * t, 3 * d)
+
+
 @pytest.mark.parametrize("d,t,n", [(64, 2, 100_003), (64, 8, 70_001), (32, 3, 100_003), (128, 6, 20_011), (128, 1, 5_003),
                                    (64, 12, 20_011), (64, 16, 30_001), (32, 16, 9_001), (32, 8, 20_011), (32, 12, 5_003)])
 def test_attn_bwd_front_many_tiles_per_block(dev, d, t, n):
@@ -123,23 +140,14 @@ def test_attn_bwd_front_many_tiles_per_block(dev, d, t, n):
     from sa_gnn_amd import ops
     assert ops.attn_bwd_front_supported(d, t, 16)
     rng = np.random.default_rng(d * 7 + t)
-    heads, dk = 16, d // 16
+    heads = 16
     x = rng.standard_normal((n, t, d)).astype(np.float32)
     p, pd = _params(d, rng, dev)
     gout = rng.standard_normal((n, d)).astype(np.float32)
-    tx = torch.tensor(x, dtype=torch.float64)
-    tp = {k: torch.tensor(v, dtype=torch.float64) for k, v in p.items()}
-    y = O.torch_layer_norm_td(tx, tp["ln_gamma"], tp["ln_beta"])
-    qkv = torch.cat([y @ tp["Wq"] + tp["bq"], y @ tp["Wk"] + tp["bk"], y @ tp["Wv"] + tp["bv"]], dim=2).requires_grad_(True)
-    q, k, v = (qkv[:, :, i * d:(i + 1) * d].reshape(n, t, heads, dk).permute(0, 2, 1, 3) for i in range(3))
-    scores = torch.exp((q @ k.transpose(-1, -2)) / float(np.sqrt(dk)))      # Utils/attention.py:38-44
-    attn = scores / (scores.sum(dim=-1, keepdim=True) + 1e-8)
-    out = (attn @ v).permute(0, 2, 1, 3).reshape(n, t, d).mean(dim=1)
-    (out * torch.tensor(gout, dtype=torch.float64)).sum().backward()
+    y, want = attn_bwd_front_reference(x, p, gout, heads)
     y_got, dqkv = ops.attn_bwd_front(torch.from_numpy(x).to(dev), pd["ln_gamma"], pd["ln_beta"], pd["Wq"], pd["bq"],
                                      pd["Wk"], pd["bk"], pd["Wv"], pd["bv"], heads, torch.from_numpy(gout).to(dev))
-    _check(y_got.view(n, t, d), y.numpy(), "y")
-    want = qkv.grad.numpy().reshape(n * t, 3 * d)
+    _check(y_got.view(n, t, d), y, "y")
     err = np.abs(dqkv.cpu().numpy() - want)
     assert (err <= 1e-4 * np.abs(want) + 2e-5 * np.abs(want).max()).all(), f"dqkv worst {err.max():.3e}"
 

@@ -28,6 +28,7 @@ def x_layout(name, n, t, d):
             "shift": ((t * d, d, 1), 5),                 # base one float past a 16-byte boundary
             "ld_n+1": ((t * d + 1, d, 1), 4),            # ld_n = t*d + 1
             "time_major": ((d, n * d + 2, 1), 4),        # [t, n, d] storage, ld_t = n*d + 2
+            "time_major,vec": ((d, n * d + 4, 1), 4),    # [t, n, d] storage with 16-byte rows: ld_t = n*d + 4
             "shift,ld_n+1": ((t * d + 1, d, 1), 5)}[name]
 
 
