@@ -77,8 +77,8 @@ size_t sagnn_last_error(char* buf, size_t cap);
  * recorded events, returns up to `cap` records in issue order and clears the log.
  * kind: 0 = SpMM row/chunk kernel (units_a = nnz, units_b = n_rows), 1 = SpMM fix-up,
  *       2 = LSTM, 3 = layer-norm, 4 = MHSA+mean (units_a = n, units_b = t),
- *       5 = an entry of the sequence attention (seq_attn.hip: gather, attention, pool and their
- *       backwards; units_a = n_slots, units_b = pos_length),
+ *       5 = an entry of the sequence attention (seq_attn.hip: gather, attention, pool, additive pool and
+ *       their backwards; units_a = n_slots, units_b = pos_length),
  *       6 = sagnn_softmax_loss_f32 or its backward (units_a = n_queries, units_b = n_items).
  * -------------------------------------------------------------------------------- */
 int sagnn_profile_enable(int capacity);
@@ -832,6 +832,41 @@ int sagnn_seq_pool_f32(const float* x, int64_t ldx, const int32_t* seg_len, int6
                        float* out, int64_t ldo, void* stream);
 int sagnn_seq_pool_bwd_f32(const float* g, int64_t ldg, const int32_t* seg_len, int64_t n_slots, int pos_length, int d,
                            float* dx, int64_t ldx, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Additive-attention pooling of the sequence head (seq_attn.hip; --seqPool additive, not in the reference's graph: it
+ * constructs AdditiveAttention(query_vector_dim, latdim), model.py:147, and comments its call out, model.py:168).
+ * On the slab layout above, with u = x Wa + ba [n_slots * P, q] computed by the caller (sagnn_dense_nn_f32 over all
+ * rows) and v [q] the query vector, for slot b over its n_b real tokens only:
+ *   s_j = sum_c tanh(u[b * P + j, c]) v[c],  w = softmax_j(s) (evaluated with the slot's largest s subtracted),
+ *   out[b] = sum_j w_j x[b * P + j].
+ * sagnn_seq_addpool_f32: out [n_slots, d] is WRITTEN, a zero row for an empty slot. w (nullable, [n_slots * P]) is
+ *   WRITTEN for every row, zeros in the padding: the weight the head gives each item. Padded rows of x and u are never
+ *   read. Finite for any finite x, u, v: tanh saturates to +-1, and the shift keeps scores beyond fp32's exp range (88)
+ *   from overflowing.
+ * sagnn_seq_addpool_bwd_f32: given x, u, v and the upstream g [n_slots, d] (t, s and w are recomputed; the forward saves
+ *   nothing else), with a_j = <g[b], x_j>, abar = sum_j w_j a_j and ds_j = w_j (a_j - abar):
+ *   dx[b * P + j] = w_j g[b] (the direct part only: the caller adds du Wa^T with sagnn_dense_nn_f32, accumulate = 1),
+ *   du[b * P + j, c] = ds_j v[c] (1 - t_j[c]^2),  dv_part[b, c] = sum_j ds_j t_j[c],  dv[c] = sum_b dv_part[b, c] (b
+ *   ascending; a second launch). Every row of dx, du and dv_part ([n_slots, q] dense workspace) and dv [q] is WRITTEN:
+ *   exact zeros in the padding and for an empty slot. dWa = x^T du and dba = colsum(du) are the caller's
+ *   sagnn_dense_tn_f32 over the slab. Padded rows of x and u and the rows of g of empty slots are never read.
+ * No atomics: every sum across lanes, token groups and slots has one fixed order, so out, w, dx, du and dv are
+ *   bit-identical between runs.
+ * sagnn_seq_addpool_supported(d, q, pos_length): SAGNN_OK when the two entries take the shape, SAGNN_ERR_DIM otherwise
+ *   (the reason in sagnn_last_error). Never touches the device.
+ * fp32 VALU under every engine. Profile kind 5.
+ * Limits: d and q multiples of 4 in [4, 256], 1 <= pos_length <= 256 (one workgroup per slot); x, u, g, out, dx, du, v and
+ *   dv_part 16-byte aligned, strides multiples of 4 and >= the row width; n_slots >= 0 (n_slots = 0 returns SAGNN_OK at
+ *   once, except that sagnn_seq_addpool_bwd_f32 still writes its zero dv). Every argument is checked before any device
+ *   work. One launch (two for the backward) on `stream`, no allocation, no synchronisation (capturable).
+ * -------------------------------------------------------------------------------- */
+int sagnn_seq_addpool_supported(int d, int q, int pos_length);
+int sagnn_seq_addpool_f32(const float* x, int64_t ldx, const float* u, int64_t ldu, const float* v, const int32_t* seg_len,
+                          int64_t n_slots, int pos_length, int d, int q, float* out, int64_t ldo, float* w, void* stream);
+int sagnn_seq_addpool_bwd_f32(const float* x, int64_t ldx, const float* u, int64_t ldu, const float* v, const float* g,
+                              int64_t ldg, const int32_t* seg_len, int64_t n_slots, int pos_length, int d, int q, float* dx,
+                              int64_t ld_dx, float* du, int64_t ld_du, float* dv_part, float* dv, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Full-catalogue softmax cross-entropy (softmax_loss.hip; --predLoss softmax, not in the reference, which trains the

@@ -26,7 +26,8 @@ _FLAGS = [
     ("sampNum", int, 40, "unused"),
     ("testSize", int, 100, "candidates per test user"),
     ("sslNum", int, 20, "SSL pairs per user"),
-    ("query_vector_dim", int, 64, "AdditiveAttention width (constructed, never applied)"),
+    ("query_vector_dim", int, 64, "AdditiveAttention width: read under --seqPool additive (a multiple of 32 in [32, 256]); constructed "
+                                   "and never applied in the reference and under --seqPool sum"),
     ("num_attention_heads", int, 16, "MHSA heads"),
     ("hyperNum", int, 128, "unused"),
     ("gnn_layer", int, 2, "L: GNN layers per interval"),
@@ -84,6 +85,12 @@ _FLAGS = [
                            "in the reference's graph: it multiplies the mask in before the attention layers "
                            "(model.py:161-162) and never passes attn_mask (Utils/attention.py:35-45)",
      ("sum", "full")),
+    ("seqPool", str, "sum", "how the head pools the tokens of --seqAtt full into the user's row: sum (the plain sum over "
+                            "the real tokens, as the reference's graph computes) or additive (the softmax-weighted sum of "
+                            "additive attention, weights from <tanh(x Wa + ba), v>; three more variables of width "
+                            "--query_vector_dim; part of the model; needs --seqAtt full and latdim, query_vector_dim "
+                            "multiples of 32). Not in the reference's graph: it constructs the AdditiveAttention "
+                            "(model.py:147) and comments its call out (model.py:168)", ("sum", "additive")),
     ("predLoss", str, "hinge", "the training loss of the prediction head: hinge (one positive against 40 sampled "
                                "negatives, the reference's loss) or softmax (cross-entropy of the user's next item "
                                "against every item the sampler may draw as its negative, over the whole catalogue; the "

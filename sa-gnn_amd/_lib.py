@@ -205,6 +205,12 @@ SIGNATURES = {
     "sagnn_seq_attn_bwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p]),
     "sagnn_seq_pool_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p]),
     "sagnn_seq_pool_bwd_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p]),
+    "sagnn_seq_addpool_supported": (c_int, [c_int, c_int, c_int]),
+    "sagnn_seq_addpool_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
+                                      c_void_p, c_int64, c_void_p, c_void_p]),
+    "sagnn_seq_addpool_bwd_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
+                                          c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
+                                          c_void_p]),
     "sagnn_softmax_loss_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int]),
     "sagnn_softmax_loss_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_float,
                                        c_float, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,

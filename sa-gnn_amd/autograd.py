@@ -623,3 +623,28 @@ class SeqPoolFn(torch.autograd.Function):
     def backward(ctx, g):
         (seg_len,) = ctx.saved_tensors
         return ops.seq_pool_bwd(g.contiguous(), seg_len, ctx.P), None, None
+
+
+class SeqAddPoolFn(torch.autograd.Function):
+    """x [n_slots * P, d] -> [n_slots, d]: additive-attention pooling over each slot's real tokens (--seqPool additive,
+    DESIGN.md §21): u = x Wa + ba over the slab (ops.dense_nn), out[b] = sum_j w_j x_j with w the softmax of
+    <tanh(u_j), v> (ops.seq_addpool). Saved for the backward: x and u. The backward is ops.seq_addpool_bwd (w_j g, du,
+    dv) -> dWa, dba (dense_tn) and dx += du Wa^T (dense_nn, accumulating); zeros into the padding."""
+
+    @staticmethod
+    def forward(ctx, x, Wa, ba, v, seg_len, P):
+        x = x.detach().contiguous()
+        Wa, v = Wa.detach().contiguous(), v.detach().contiguous()
+        u = ops.dense_nn(x, Wa, ba.detach().contiguous())
+        ctx.save_for_backward(x, u, Wa, v, seg_len)
+        ctx.P = int(P)
+        return ops.seq_addpool(x, u, v, seg_len, P)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, u, Wa, v, seg_len = ctx.saved_tensors
+        dx, du, dv = ops.seq_addpool_bwd(x, u, v, g.contiguous(), seg_len, ctx.P)
+        dWa, dba = torch.zeros_like(Wa), torch.zeros(Wa.shape[1], dtype=torch.float32, device=Wa.device)
+        ops.dense_tn(x, du, dWa, dba)
+        ops.dense_nn(du, Wa.t().contiguous(), None, out=dx, accumulate=True)
+        return dx, dWa, dba, dv, None, None

@@ -2,7 +2,7 @@
 // item of a batch slot's sequence is a token and the attention layers run over the slot's real tokens only.
 // Activations live in a padded slab [n_slots * P, d] (token j of slot b at row b * P + j, P = pos_length) with the
 // per-slot lengths on the device. Three kernels and their backwards: the token gather, the ragged attention on a
-// q|k|v slab and the pooling sum. Layer norm, the q|k|v projection and the weight gradients between them go through
+// q|k|v slab and the pooling sum, plus the opt-in additive-attention pooling (--seqPool additive, §21). Layer norm, the q|k|v projection and the weight gradients between them go through
 // the row-wise entries of fusion.hip / dense.hip / attn_bwd_tail.hip on all n_slots * P rows; for that, padded rows
 // hold finite values in every activation and exact zeros in every gradient written here.
 // Reference for the arithmetic: Utils/attention.py:35-45 with the attn_mask the reference never passes; fp32 VALU
@@ -324,6 +324,170 @@ __global__ void seq_pool_bwd_kernel(const float* __restrict__ g, int64_t ldg, co
   *reinterpret_cast<float4*>(dx + row * ldx + col) = v;
 }
 
+// ---- additive-attention pooling (--seqPool additive) ------------------------------------------------
+// att_user[b] = sum_j w_j x_j, w = softmax over the slot's real tokens of s_j = <tanh(u_j), v>, u = x Wa + ba (the
+// projection is a dense_nn over the slab). One workgroup per slot; every loop runs over n_b. Rows are read by
+// sub-groups of G lanes (G the power of two >= row width / 4, a float4 per lane: whole rows, coalesced), 64 / G tokens
+// per wave; sums across lanes are xor butterflies and sums across token groups go through LDS in ascending group
+// order, so every reduction has one fixed order and the kernels have no atomics.
+constexpr int kWaves = kBlock / 64;
+
+__device__ __forceinline__ int lanes_for(int n4) {    // n4 <= 64
+  int g = 1;
+  while (g < n4) g <<= 1;
+  return g;
+}
+
+__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ void st4(float* p, const float4& v) { *reinterpret_cast<float4*>(p) = v; }
+
+__device__ __forceinline__ float4 tanh4(const float4& u) { return make_float4(tanhf(u.x), tanhf(u.y), tanhf(u.z), tanhf(u.w)); }
+
+// S[j] = sum_c f(row_j[c]) * vec[c] for j < len: rows of n floats at `rows + j * ld`; f = tanh or the identity
+template <bool TANH>
+__device__ __forceinline__ void row_dots(const float* __restrict__ rows, int64_t ld, const float* __restrict__ vec, int n,
+                                         int len, float* S) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int n4 = n >> 2, G = lanes_for(n4), per = 64 / G, sub = lane & (G - 1), tok = lane / G;
+  const float4 vv = sub < n4 ? ld4(vec + sub * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int j0 = 0; j0 < len; j0 += kWaves * per) {       // a block-uniform trip count: every lane reaches the shuffles
+    const int j = j0 + wave * per + tok;
+    float p = 0.f;
+    if (j < len && sub < n4) {
+      float4 r = ld4(rows + j * ld + sub * 4);
+      if (TANH) r = tanh4(r);
+      p = fmaf(r.w, vv.w, fmaf(r.z, vv.z, fmaf(r.y, vv.y, r.x * vv.x)));
+    }
+    for (int off = G >> 1; off; off >>= 1) p += __shfl_xor(p, off);
+    if (j < len && sub == 0) S[j] = p;
+  }
+}
+
+// W[j] = softmax over j < len of S (the largest score subtracted), zeros for len <= j < P. Every wave evaluates the
+// two reductions alike, so no wave waits for another's result. Ends with a barrier; S must be complete on entry.
+__device__ __forceinline__ void slot_softmax(const float* S, int len, int P, float* W) {
+  const int lane = threadIdx.x & 63;
+  float m = -INFINITY, z = 0.f;
+  for (int j = lane; j < len; j += 64) m = fmaxf(m, S[j]);
+  for (int off = 32; off; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+  for (int j = lane; j < len; j += 64) z += expf(S[j] - m);
+  for (int off = 32; off; off >>= 1) z += __shfl_xor(z, off);
+  const int j = threadIdx.x;
+  if (j < P) W[j] = j < len ? expf(S[j] - m) / z : 0.f;       // z >= 1: the largest score's term
+  __syncthreads();
+}
+
+// partial sums of token groups, merged in ascending group order: thread t < n4 returns float4 column t of the sum
+__device__ __forceinline__ float4 merge_groups(float4 acc, int n4, float4* Part) {
+  __syncthreads();                                       // Part may still be read from an earlier merge
+  Part[threadIdx.x] = acc;
+  __syncthreads();
+  float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (threadIdx.x < n4)
+    for (int g = 0; g < kBlock / n4; ++g) add4(o, Part[g * n4 + threadIdx.x]);
+  return o;
+}
+
+__global__ void __launch_bounds__(kBlock) seq_addpool_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ u,
+                                                             int64_t ldu, const float* __restrict__ v,
+                                                             const int32_t* __restrict__ seg_len, int P, int d, int q,
+                                                             float* __restrict__ out, int64_t ldo, float* __restrict__ w) {
+  __shared__ float S[kMaxP], W[kMaxP];
+  __shared__ __attribute__((aligned(16))) float4 Part[kBlock];
+  const int64_t b = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int len = clamp_len(seg_len, b, P);
+  row_dots<true>(u + b * P * ldu, ldu, v, q, len, S);
+  __syncthreads();
+  slot_softmax(S, len, P, W);
+  if (w && tid < P) w[b * P + tid] = W[tid];
+  const int d4 = d >> 2, groups = kBlock / d4, col = tid % d4, grp = tid / d4;
+  const float* xs = x + b * P * ldx + col * 4;
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (grp < groups)
+    for (int j = grp; j < len; j += groups) {
+      const float4 r = ld4(xs + j * ldx);
+      const float wj = W[j];
+      acc.x = fmaf(wj, r.x, acc.x);
+      acc.y = fmaf(wj, r.y, acc.y);
+      acc.z = fmaf(wj, r.z, acc.z);
+      acc.w = fmaf(wj, r.w, acc.w);
+    }
+  const float4 o = merge_groups(acc, d4, Part);
+  if (tid < d4) st4(out + b * ldo + tid * 4, o);
+}
+
+// Backward: t, s and w are recomputed from x and u. a_j = <g, x_j>, abar = sum_j w_j a_j, ds_j = w_j (a_j - abar);
+// dx_j = w_j g (the direct part; du Wa^T is the caller's product), du_j = ds_j v (1 - t_j^2), dv_part[b] = sum_j ds_j t_j.
+__global__ void __launch_bounds__(kBlock) seq_addpool_bwd_kernel(const float* __restrict__ x, int64_t ldx,
+                                                                 const float* __restrict__ u, int64_t ldu,
+                                                                 const float* __restrict__ v, const float* __restrict__ g,
+                                                                 int64_t ldg, const int32_t* __restrict__ seg_len, int P, int d,
+                                                                 int q, float* __restrict__ dx, int64_t ld_dx,
+                                                                 float* __restrict__ du, int64_t ld_du,
+                                                                 float* __restrict__ dv_part) {
+  __shared__ float S[kMaxP], W[kMaxP], A[kMaxP], Ds[kMaxP];
+  __shared__ __attribute__((aligned(16))) float4 Part[kBlock];
+  const int64_t b = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int len = clamp_len(seg_len, b, P);
+  const float* us = u + b * P * ldu;
+  const float* gb = g + b * ldg;
+  row_dots<true>(us, ldu, v, q, len, S);
+  row_dots<false>(x + b * P * ldx, ldx, gb, d, len, A);
+  __syncthreads();
+  slot_softmax(S, len, P, W);
+  float abar = 0.f;
+  for (int j = lane; j < len; j += 64) abar = fmaf(W[j], A[j], abar);
+  for (int off = 32; off; off >>= 1) abar += __shfl_xor(abar, off);
+  if (tid < P) Ds[tid] = tid < len ? W[tid] * (A[tid] - abar) : 0.f;
+  __syncthreads();
+  const int d4 = d >> 2, q4 = q >> 2;
+  float* dxs = dx + b * P * ld_dx;
+  for (int i = tid; i < P * d4; i += kBlock) {            // every row of dx: w_j g, zeros in the padding (W is 0 there)
+    const int j = i / d4, c = (i - j * d4) * 4;
+    float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (j < len) {
+      const float4 gg = ld4(gb + c);
+      const float wj = W[j];
+      r = make_float4(wj * gg.x, wj * gg.y, wj * gg.z, wj * gg.w);
+    }
+    st4(dxs + j * ld_dx + c, r);
+  }
+  float* dus = du + b * P * ld_du;
+  const int groups = kBlock / q4, col = tid % q4, grp = tid / q4;
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (grp < groups) {
+    const float4 vv = ld4(v + col * 4);
+    for (int j = grp; j < len; j += groups) {
+      const float4 t = tanh4(ld4(us + j * ldu + col * 4));
+      const float ds = Ds[j];
+      acc.x = fmaf(ds, t.x, acc.x);
+      acc.y = fmaf(ds, t.y, acc.y);
+      acc.z = fmaf(ds, t.z, acc.z);
+      acc.w = fmaf(ds, t.w, acc.w);
+      st4(dus + j * ld_du + col * 4, make_float4(ds * vv.x * (1.f - t.x * t.x), ds * vv.y * (1.f - t.y * t.y),
+                                                 ds * vv.z * (1.f - t.z * t.z), ds * vv.w * (1.f - t.w * t.w)));
+    }
+  }
+  for (int i = tid; i < (P - len) * q4; i += kBlock) {    // the padding of du
+    const int j = len + i / q4, c = (i % q4) * 4;
+    st4(dus + j * ld_du + c, make_float4(0.f, 0.f, 0.f, 0.f));
+  }
+  const float4 o = merge_groups(acc, q4, Part);
+  if (tid < q4) st4(dv_part + b * q + tid * 4, o);
+}
+
+// dv[c] = sum over slots b (ascending) of dv_part[b, c]: one thread per column, no atomics
+__global__ void seq_addpool_dv_kernel(const float* __restrict__ dv_part, int64_t n_slots, int q, float* __restrict__ dv) {
+  const int c = threadIdx.x;
+  if (c >= q) return;
+  float acc = 0.f;
+#pragma unroll 16
+  for (int64_t b = 0; b < n_slots; ++b) acc += dv_part[b * q + c];
+  dv[c] = acc;
+}
+
 // ---- host-side argument checks: every entry rejects a bad call before any device work ------------------------------
 int check_slab_dims(const char* who, int d, int P, int64_t n_slots) {
   if (d < 4 || d > 256 || (d & 3)) return sagnn::fail(SAGNN_ERR_DIM, "%s: d = %d, need a multiple of 4 in [4, 256]", who, d);
@@ -500,6 +664,77 @@ extern "C" int sagnn_seq_pool_bwd_f32(const float* g, int64_t ldg, const int32_t
   hipStream_t s = static_cast<hipStream_t>(stream);
   sagnn::ProfileScope prof(sagnn::kProfSeqAtt, s, n_slots, pos_length);
   hipLaunchKernelGGL(seq_pool_bwd_kernel, dim3(blocks), dim3(kBlock), 0, s, g, ldg, seg_len, n_slots, pos_length, d, dx, ldx);
+  SAGNN_HIP_TRY(hipGetLastError());
+  return SAGNN_OK;
+}
+
+namespace {
+
+int addpool_shape(const char* who, int d, int q, int P) {
+  if (d < 4 || d > 256 || (d & 3)) return sagnn::fail(SAGNN_ERR_DIM, "%s: d = %d, need a multiple of 4 in [4, 256]", who, d);
+  if (q < 4 || q > 256 || (q & 3)) return sagnn::fail(SAGNN_ERR_DIM, "%s: q = %d, need a multiple of 4 in [4, 256]", who, q);
+  if (P < 1 || P > kMaxP) return sagnn::fail(SAGNN_ERR_DIM, "%s: pos_length = %d, need 1 <= pos_length <= %d", who, P, kMaxP);
+  return SAGNN_OK;
+}
+
+int check_addpool(const char* who, int d, int q, int P, int64_t n_slots) {
+  if (int rc = addpool_shape(who, d, q, P)) return rc;
+  if (n_slots < 0) return sagnn::fail(SAGNN_ERR_ARG, "%s: negative count (n_slots = %lld)", who, (long long)n_slots);
+  if (n_slots > INT_MAX) return sagnn::fail(SAGNN_ERR_ARG, "%s: grid too large (%lld slots)", who, (long long)n_slots);
+  return SAGNN_OK;
+}
+
+int check_vec16(const char* who, const void* p, const char* name) {
+  if (!sagnn::aligned16(p)) return sagnn::fail(SAGNN_ERR_ALIGN, "%s: %s must be 16-byte aligned", who, name);
+  return SAGNN_OK;
+}
+
+}  // namespace
+
+extern "C" int sagnn_seq_addpool_supported(int d, int q, int pos_length) {
+  return addpool_shape("seq_addpool", d, q, pos_length);
+}
+
+extern "C" int sagnn_seq_addpool_f32(const float* x, int64_t ldx, const float* u, int64_t ldu, const float* v,
+                                     const int32_t* seg_len, int64_t n_slots, int pos_length, int d, int q, float* out,
+                                     int64_t ldo, float* w, void* stream) {
+  const char* who = "seq_addpool";
+  if (!x || !u || !v || !seg_len || !out) return sagnn::fail(SAGNN_ERR_NULL, "%s: null pointer (x, u, v, seg_len, out)", who);
+  if (int rc = check_addpool(who, d, q, pos_length, n_slots)) return rc;
+  if (int rc = check_rows(who, d, ldx, x, "x")) return rc;
+  if (int rc = check_rows(who, q, ldu, u, "u")) return rc;
+  if (int rc = check_rows(who, d, ldo, out, "out")) return rc;
+  if (int rc = check_vec16(who, v, "v")) return rc;
+  if (n_slots == 0) return SAGNN_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  sagnn::ProfileScope prof(sagnn::kProfSeqAtt, s, n_slots, pos_length);
+  hipLaunchKernelGGL(seq_addpool_kernel, dim3((unsigned)n_slots), dim3(kBlock), 0, s, x, ldx, u, ldu, v, seg_len, pos_length,
+                     d, q, out, ldo, w);
+  SAGNN_HIP_TRY(hipGetLastError());
+  return SAGNN_OK;
+}
+
+extern "C" int sagnn_seq_addpool_bwd_f32(const float* x, int64_t ldx, const float* u, int64_t ldu, const float* v,
+                                         const float* g, int64_t ldg, const int32_t* seg_len, int64_t n_slots,
+                                         int pos_length, int d, int q, float* dx, int64_t ld_dx, float* du, int64_t ld_du,
+                                         float* dv_part, float* dv, void* stream) {
+  const char* who = "seq_addpool_bwd";
+  if (!x || !u || !v || !g || !seg_len || !dx || !du || !dv_part || !dv)
+    return sagnn::fail(SAGNN_ERR_NULL, "%s: null pointer (x, u, v, g, seg_len, dx, du, dv_part, dv)", who);
+  if (int rc = check_addpool(who, d, q, pos_length, n_slots)) return rc;
+  if (int rc = check_rows(who, d, ldx, x, "x")) return rc;
+  if (int rc = check_rows(who, q, ldu, u, "u")) return rc;
+  if (int rc = check_rows(who, d, ldg, g, "g")) return rc;
+  if (int rc = check_rows(who, d, ld_dx, dx, "dx")) return rc;
+  if (int rc = check_rows(who, q, ld_du, du, "du")) return rc;
+  if (int rc = check_vec16(who, v, "v")) return rc;
+  if (int rc = check_vec16(who, dv_part, "dv_part")) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  sagnn::ProfileScope prof(sagnn::kProfSeqAtt, s, n_slots, pos_length);
+  if (n_slots)
+    hipLaunchKernelGGL(seq_addpool_bwd_kernel, dim3((unsigned)n_slots), dim3(kBlock), 0, s, x, ldx, u, ldu, v, g, ldg, seg_len,
+                       pos_length, d, q, dx, ld_dx, du, ld_du, dv_part);
+  hipLaunchKernelGGL(seq_addpool_dv_kernel, dim3(1), dim3((unsigned)((q + 63) / 64 * 64)), 0, s, dv_part, n_slots, q, dv);
   SAGNN_HIP_TRY(hipGetLastError());
   return SAGNN_OK;
 }

@@ -24,6 +24,7 @@ from .graph import NORMS, interval_pair
 
 
 SEQ_ATT = ("sum", "full")      # --seqAtt: the reference's collapsed head, or attention over every sequence item
+SEQ_POOL = ("sum", "additive")  # --seqPool: the reference's sum over the tokens, or its dead AdditiveAttention applied
 EDGE_TIME = ("none", "slot")   # --edgeTime: the reference's graph, or messages that add their edge's time-bucket row
 PRED_LOSS = ("hinge", "softmax")   # --predLoss: the reference's sampled hinge loss, or softmax over the whole catalogue
 
@@ -390,7 +391,22 @@ class Recommender:
         self._define_fusion_params()
         self._define_head_params()
         self._define_ssl_params()
+        self._define_seq_pool_params()
         return self.forward()
+
+    def _define_seq_pool_params(self):
+        """The additive-attention pooling of --seqPool additive (the reference's additive_attention0, model.py:147, whose
+        call model.py:168 comments out): a tf.layers.dense kernel and bias, not L2-regularised like the MHSA
+        kernels, and the query vector, here a trained variable (Utils/attention.py:9 re-draws a tensor per run). Defined
+        after every other variable, so those start where they start under --seqPool sum; nothing is defined under sum."""
+        self.additive_attention0 = None
+        if args.seqPool != "additive":
+            return
+        d, q = args.latdim, args.query_vector_dim
+        Wa = NNs.defineParam("additive_attention0_kernel", [d, q])
+        ba = NNs.defineParam("additive_attention0_bias", [q], initializer="zeros")
+        query = torch.rand(q, generator=NNs._generator, dtype=torch.float32) * 0.2 - 0.1
+        self.additive_attention0 = (Wa, ba, NNs.defineParam("additive_attention0_query", [q], initializer=query))
 
     def _define_ssl_params(self):
         """The SSL meta-net (model.py:179-182): FC(3d -> ssldim, bias, leakyRelu, reg) named 'meta2'
@@ -499,6 +515,8 @@ class Recommender:
             w = mh.weights()
             x = ag.SeqAttnFn.apply(x, *self.head_ln[2 + i], w["Wq"], w["bq"], w["Wk"], w["bk"], w["Wv"], w["bv"], seg_len, P,
                                    heads, leaky)
+        if args.seqPool == "additive":
+            return ag.SeqAddPoolFn.apply(x, *self.additive_attention0, seg_len, P)
         return ag.SeqPoolFn.apply(x, seg_len, P)
 
     def _head_att_tokens(self, seq_items, seq_pos, seg_begin, seg_len):
@@ -1099,7 +1117,7 @@ class Recommender:
         with open(os.path.join(directory, "History", args.save_path + ".his"), "wb") as fs:
             pickle.dump(self.metrics, fs)
         state = {"params": {k: v.detach().cpu() for k, v in NNs.params.items()}, "adjNorm": args.adjNorm,
-                 "seqAtt": args.seqAtt, "edgeTime": self._edge_time_state()}
+                 "seqAtt": args.seqAtt, "seqPool": args.seqPool, "edgeTime": self._edge_time_state()}
         if getattr(self, "optimizer", None) is not None:
             state["optimizer"] = self.optimizer.state_dict()
         torch.save(state, os.path.join(directory, "Models", args.save_path))
@@ -1124,6 +1142,10 @@ class Recommender:
         if stored_att != args.seqAtt:
             raise ValueError(f"checkpoint was trained with --seqAtt {stored_att}, this run has --seqAtt {args.seqAtt}: "
                              "the head's attention is part of the model")
+        stored_pool = state.get("seqPool", "sum")        # a checkpoint from before --seqPool pools with the plain sum
+        if stored_pool != args.seqPool:
+            raise ValueError(f"checkpoint was trained with --seqPool {stored_pool}, this run has --seqPool {args.seqPool}: "
+                             "the head's pooling is part of the model")
         stored_time = state.get("edgeTime", {"mode": "none"})      # a checkpoint from before --edgeTime has no time term
         if stored_time != self._edge_time_state():
             raise ValueError(f"checkpoint was trained with --edgeTime {stored_time}, this run has {self._edge_time_state()}: "
@@ -1155,6 +1177,8 @@ class Recommender:
             raise ValueError(f"--adjNorm {args.adjNorm}: one of {NORMS}")
         if args.seqAtt not in SEQ_ATT:
             raise ValueError(f"--seqAtt {args.seqAtt}: one of {SEQ_ATT}")
+        if args.seqPool not in SEQ_POOL:
+            raise ValueError(f"--seqPool {args.seqPool}: one of {SEQ_POOL}")
         if args.predLoss not in PRED_LOSS:
             raise ValueError(f"--predLoss {args.predLoss}: one of {PRED_LOSS}")
         if args.edgeTime not in EDGE_TIME:
@@ -1175,6 +1199,16 @@ class Recommender:
                                  "row of the fused table, so there is no row subset to fuse")
             if args.latdim not in (32, 64, 128):
                 raise ValueError(f"--predLoss softmax needs latdim in (32, 64, 128), got {args.latdim}")
+        if args.seqPool == "additive":     # refused before any forward; ahead of --seqAtt full, whose limits it shares
+            if args.seqAtt != "full":
+                raise ValueError("--seqPool additive needs --seqAtt full: under --seqAtt sum a slot holds one token, the "
+                                 "softmax over it is 1 and the pooling is the identity")
+            why = ops.seq_addpool_supported(args.latdim, args.query_vector_dim, args.pos_length)
+            if why is not None:
+                raise ValueError(f"--seqPool additive is not available for this configuration: {why}")
+            if args.latdim % 32 or args.query_vector_dim % 32:       # the projection and its gradients: the dense entries
+                raise ValueError(f"--seqPool additive needs latdim and query_vector_dim to be multiples of 32, got "
+                                 f"{args.latdim} and {args.query_vector_dim}")
         if args.seqAtt == "full":          # refused before any forward: the attention kernels take these shapes only
             why = ops.seq_attn_supported(args.latdim, args.num_attention_heads, args.pos_length)
             if why is not None:

@@ -1823,3 +1823,41 @@ def seq_pool_bwd(g: torch.Tensor, seg_len: torch.Tensor, pos_length: int):
     check(_lib.load().sagnn_seq_pool_bwd_f32(g.data_ptr(), _f32_rows("g", g, d, n), _idx_ptr("seg_len", seg_len, torch.int32),
                                              n, P, d, dx.data_ptr(), d, _stream()))
     return dx
+
+
+# ---- additive-attention pooling of the sequence head (seq_attn.hip; --seqPool additive) ----------------------------
+def seq_addpool_supported(d: int, q: int, pos_length: int) -> str | None:
+    """None when sagnn_seq_addpool_f32 / _bwd_f32 take the shape (sagnn_seq_addpool_supported), else the library's reason."""
+    return None if _lib.load().sagnn_seq_addpool_supported(int(d), int(q), int(pos_length)) == 0 else _lib.last_error()
+
+
+def seq_addpool(x: torch.Tensor, u: torch.Tensor, v: torch.Tensor, seg_len: torch.Tensor, pos_length: int,
+                want_weights: bool = False):
+    """out[b] = sum_j w_j x[b * P + j], w the softmax over slot b's real tokens of <tanh(u[b * P + j]), v>
+    (sagnn_seq_addpool_f32): x [n_slots * P, d], u [n_slots * P, q], v [q] -> [n_slots, d]; with want_weights also
+    w [n_slots * P] (zeros in the padding)."""
+    n, P, d, q = int(seg_len.numel()), int(pos_length), int(x.shape[1]), int(u.shape[1])
+    out = torch.empty((n, d), dtype=torch.float32, device=x.device)
+    w = torch.empty(n * P, dtype=torch.float32, device=x.device) if want_weights else None
+    check(_lib.load().sagnn_seq_addpool_f32(_ptr_or_empty(x), _f32_rows("x", x, d, n * P), _ptr_or_empty(u), _f32_rows("u", u, q, n * P),
+                                            _vec("v", v, q), _idx_ptr("seg_len", seg_len, torch.int32), n, P, d, q,
+                                            _ptr_or_empty(out), d, None if w is None else _ptr_or_empty(w), _stream()))
+    return (out, w) if want_weights else out
+
+
+def seq_addpool_bwd(x: torch.Tensor, u: torch.Tensor, v: torch.Tensor, g: torch.Tensor, seg_len: torch.Tensor,
+                    pos_length: int):
+    """(x, u, v, g [n_slots, d]) -> (dx [n_slots * P, d], the direct part w_j g; du [n_slots * P, q]; dv [q])
+    (sagnn_seq_addpool_bwd_f32): zeros in the padding, bit-identical between runs."""
+    n, P, d, q = int(seg_len.numel()), int(pos_length), int(x.shape[1]), int(u.shape[1])
+    dev = x.device
+    dx = torch.empty((n * P, d), dtype=torch.float32, device=dev)
+    du = torch.empty((n * P, q), dtype=torch.float32, device=dev)
+    dv_part = torch.empty((max(n, 1), q), dtype=torch.float32, device=dev)
+    dv = torch.empty(q, dtype=torch.float32, device=dev)
+    check(_lib.load().sagnn_seq_addpool_bwd_f32(
+        _ptr_or_empty(x), _f32_rows("x", x, d, n * P), _ptr_or_empty(u), _f32_rows("u", u, q, n * P), _vec("v", v, q),
+        _ptr_or_empty(g), _f32_rows("g", g, d, n), _idx_ptr("seg_len", seg_len, torch.int32), n, P, d, q, _ptr_or_empty(dx), d,
+        _ptr_or_empty(du), q,
+        dv_part.data_ptr(), dv.data_ptr(), _stream()))
+    return dx, du, dv

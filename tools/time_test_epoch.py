@@ -4,7 +4,8 @@ synthetic dataset and hyper-parameters of tools/time_train_epoch.py (U = 48,653,
 d = 64, batch 512, 10,000 test users, testSize 1000). The evaluators run in the same process, alternated epoch by
 epoch after warm-up; every device result is checked equal (==) to the host result of the same parameters. --seqAtt
 both times the head's two forms (the collapsed sum / attention over every sequence item) one after the other in the
-same process."""
+same process; --seqPool both does so for the full head's two poolings (the plain sum / additive attention; it implies
+--seqAtt full) on one model that holds the additive variables."""
 import argparse
 import sys
 import time
@@ -24,7 +25,11 @@ def main():
     ap.add_argument("--epoch-only", action="store_true", help="one warm-up and one device test epoch (for a profiler)")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--seqAtt", choices=("sum", "full", "both"), default="sum", help="the head's form(s) to time")
+    ap.add_argument("--seqPool", choices=("sum", "additive", "both"), default="sum",
+                    help="the full head's pooling(s) to time (implies --seqAtt full)")
     opt = ap.parse_args()
+    if opt.seqPool != "sum" and opt.seqAtt == "sum":
+        opt.seqAtt = "full"
     Params.parse_args("--data gowalla --lr 2e-3 --reg 1e-2 --ssl_reg 1e-6 --epoch 150 --batch 512 --sslNum 40 --graphNum 3 "
                       "--gnn_layer 2 --att_layer 1 --testSize 1000 --ssldim 48 --keepRate 0.5".split(), namespace=args)
     np.random.seed(100)
@@ -38,21 +43,27 @@ def main():
     test_dict = {u + 1: list(rng.integers(1, I + 1, size=1000)) for u in range(U)}
     h = DataHandler.from_memory(tmt, seq, tst, test_dict)
     rec = Recommender(torch.device("cuda:0"), h)
+    if opt.seqPool != "sum":       # the additive variables are defined last: every other one starts where it always does
+        args.seqAtt, args.seqPool = "full", "additive"
     rec.prepareModel()
+    args.seqAtt = "sum"
     if opt.epoch_only:
         args.evaluator = "device"
         args.seqAtt = "full" if opt.seqAtt == "full" else "sum"
+        args.seqPool = "additive" if opt.seqPool == "additive" else "sum"
         for _ in range(2):
             rec.testEpoch()
         torch.cuda.synchronize()
         print("two device test epochs done")
         return
+    pools = ("sum", "additive") if opt.seqPool == "both" else (opt.seqPool,)
     for att in (("sum", "full") if opt.seqAtt == "both" else (opt.seqAtt,)):
-        args.seqAtt = att
-        if opt.seqAtt != "sum":
-            print(f"---- --seqAtt {att}")
-        time_evaluators(rec, h, opt)
-    args.seqAtt = "sum"
+        for pool in (pools if att == "full" else ("sum",)):
+            args.seqAtt, args.seqPool = att, pool
+            if opt.seqAtt != "sum":
+                print(f"---- --seqAtt {att}" + (f" --seqPool {pool}" if opt.seqPool != "sum" else ""))
+            time_evaluators(rec, h, opt)
+    args.seqAtt, args.seqPool = "sum", "sum"
 
 
 def time_evaluators(rec, h, opt):

@@ -8,7 +8,9 @@ fusion modes as well (all rows / the rows the batch reads) and reports the touch
 kernels' fp32 re-evaluations per epoch of each mode. --seqAtt both alternates the head's two forms (the collapsed sum /
 attention over every sequence item) and reports the device time of the sequence-attention entries per step
 (sagnn_profile_read, kind 5). --predLoss both alternates the head's two training losses (the sampled hinge loss / the
-full-catalogue softmax) and reports the device time of the softmax entries per step (kind 6)."""
+full-catalogue softmax) and reports the device time of the softmax entries per step (kind 6). --seqPool both alternates
+the two poolings of the full head (the plain sum / additive attention; it implies --seqAtt full) on one model that holds
+the additive variables, every timed epoch from the initial parameters, and reports kind 5 per step for each."""
 import argparse
 import ctypes
 import sys
@@ -36,7 +38,11 @@ def main():
                     help="the head's form(s) to time; both alternates them in one process")
     ap.add_argument("--predLoss", choices=("hinge", "softmax", "both"), default="hinge",
                     help="the head's training loss(es) to time; both alternates them in one process")
+    ap.add_argument("--seqPool", choices=("sum", "additive", "both"), default="sum",
+                    help="the full head's pooling(s) to time (implies --seqAtt full); both alternates them in one process")
     opt = ap.parse_args()
+    if opt.seqPool != "sum" and opt.seqAtt == "sum":
+        opt.seqAtt = "full"
     Params.parse_args("--data gowalla --lr 2e-3 --reg 1e-2 --ssl_reg 1e-6 --epoch 150 --batch 512 --sslNum 40 --graphNum 3 "
                       "--gnn_layer 2 --att_layer 1 --testSize 1000 --ssldim 48 --keepRate 0.5".split(), namespace=args)
     args.edgeKeepRate = opt.edge_keep
@@ -51,27 +57,34 @@ def main():
     test_dict = {u + 1: list(rng.integers(1, I + 1, size=1000)) for u in range(U)}
     h = DataHandler.from_memory(tmt, seq, tst, test_dict)
     rec = Recommender(torch.device("cuda:0"), h)
+    if opt.seqPool != "sum":       # the additive variables are defined last: every other one starts where it always does
+        args.seqAtt, args.seqPool = "full", "additive"
     rec.prepareModel()
+    args.seqAtt = "sum"
     if opt.epoch_only:
         args.sampler = "device"
         args.fusion_rows = "batch" if opt.fusion_rows == "batch" else "all"
         args.seqAtt = "full" if opt.seqAtt == "full" else "sum"
         args.predLoss = "softmax" if opt.predLoss == "softmax" else "hinge"
+        args.seqPool = "additive" if opt.seqPool == "additive" else "sum"
         for _ in range(2):
             rec.trainEpoch()
         torch.cuda.synchronize()
         print(f"two device-sampler epochs done (--fusion_rows {args.fusion_rows}, --edge_keep {args.edgeKeepRate}, "
-              f"--seqAtt {args.seqAtt}, --predLoss {args.predLoss}); every parameter finite:",
+              f"--seqAtt {args.seqAtt}, --seqPool {args.seqPool}, --predLoss {args.predLoss}); every parameter finite:",
               all(bool(torch.isfinite(p).all()) for p in NNs.params.values()))
         return
     modes = ("all", "batch") if opt.fusion_rows == "both" else (opt.fusion_rows,)
     atts = ("sum", "full") if opt.seqAtt == "both" else (opt.seqAtt,)
     losses = ("hinge", "softmax") if opt.predLoss == "both" else (opt.predLoss,)
+    pools = ("sum", "additive") if opt.seqPool == "both" else (opt.seqPool,)
     if "softmax" in losses and "batch" in modes:
         sys.exit("--predLoss softmax does not combine with --fusion_rows batch")
-    configs = [(sampler, mode, att, loss) for loss in losses for att in atts for mode in modes for sampler in ("host", "device")]
+    configs = [(sampler, mode, att, loss, pool) for loss in losses for att in atts for pool in pools for mode in modes
+               for sampler in ("host", "device") if att == "full" or pool == "sum"]
     label = lambda c: ", ".join([c[0]] + ([f"{c[1]} rows"] if len(modes) > 1 else []) +   # noqa: E731
                                 ([f"seqAtt {c[2]}"] if atts != ("sum",) else []) +
+                                ([f"seqPool {c[4]}"] if pools != ("sum",) else []) +
                                 ([f"predLoss {c[3]}"] if losses != ("hinge",) else []))
 
     initial = {k: p.detach().clone() for k, p in NNs.params.items()}
@@ -84,8 +97,8 @@ def main():
         # forms every timed epoch is therefore the first epoch of its own training (profiles/seq_att_epoch.txt holds a
         # parent-commit run that shows the default path's divergence). A run without --seqAtt both keeps training its
         # parameters as before, so its lines, not a `both` run's sum lines, are what compares with an earlier commit.
-        args.sampler, args.fusion_rows, args.seqAtt, args.predLoss = c
-        if fresh and len(atts) * len(losses) > 1:
+        args.sampler, args.fusion_rows, args.seqAtt, args.predLoss, args.seqPool = c
+        if fresh and len(atts) * len(losses) * len(pools) > 1:
             with torch.no_grad():
                 for k, p in NNs.params.items():
                     p.copy_(initial[k])
@@ -158,9 +171,9 @@ def main():
             tu, ti = np.mean(np.asarray(touched[c], dtype=np.float64), axis=0)
             print(f"[{label(c)}] touched rows per step (mean of {len(touched[c])}): users {tu:.1f} of {args.user} "
                   f"({100 * tu / args.user:.2f} %), items {ti:.1f} of {args.item} ({100 * ti / args.item:.2f} %)")
-    if "full" in atts:        # device time of the sequence-attention entries (profile kind 5), one device-sampler epoch
+    for pool in pools if "full" in atts else ():   # device time of the sequence-attention entries (kind 5), one device-sampler epoch
         lib = ops._lib.load()
-        use(("device", modes[0], "full", losses[0]), fresh=True)
+        use(("device", modes[0], "full", losses[0], pool), fresh=True)
         cap = 4096 * steps
         lib.sagnn_profile_enable(cap)
         rec.trainEpoch()
@@ -168,13 +181,13 @@ def main():
         ops.check(lib.sagnn_profile_read(ms.ctypes.data, kind.ctypes.data, None, None, cap, ctypes.byref(n)))
         lib.sagnn_profile_enable(0)
         sel = kind[:n.value] == 5
-        print(f"[device, seqAtt full] sequence-attention entries (gather, attention, pool and their backwards): "
+        print(f"[device, seqAtt full{', seqPool ' + pool if pools != ('sum',) else ''}] sequence-attention entries (gather, attention, pool and their backwards): "
               f"{int(sel.sum()) / steps:.0f} calls and {float(ms[:n.value][sel].sum()) / steps:.3f} ms of device time per step; "
               f"layer-norm entries (profile kind 3): {float(ms[:n.value][kind[:n.value] == 3].sum()) / steps:.3f} ms per step")
         print("every parameter finite after that epoch:", all(bool(torch.isfinite(p).all()) for p in NNs.params.values()))
     if "softmax" in losses:   # device time of the softmax-loss entries (profile kind 6), one device-sampler epoch
         lib = ops._lib.load()
-        use(("device", modes[0], atts[0], "softmax"), fresh=True)
+        use(("device", modes[0], atts[0], "softmax", pools[0] if atts[0] == "full" else "sum"), fresh=True)
         cap = 4096 * steps
         lib.sagnn_profile_enable(cap)
         rec.trainEpoch()
@@ -190,6 +203,7 @@ def main():
     args.predLoss = "hinge"
     args.sampler = "host"
     args.seqAtt = "sum"
+    args.seqPool = "sum"
     t0 = time.perf_counter()
     res = rec.testEpoch()
     torch.cuda.synchronize()
