@@ -109,8 +109,24 @@ def main():
         ops.gnn_stack(batch, ued, ied, L, 0.5, us2.permute(1, 0, 2), its2.permute(1, 0, 2))
         assert torch.equal(us, us2) and torch.equal(its, its2), "batched entry differs from the per-interval entry"
 
+    def spmm_rows_case():
+        """The row block of a wave is chosen on the row count: draw it on both sides of 262,144, any width and form, on
+        the sparse-window graphs of tests/test_gpu_spmm_routes.py (every row empty but three windows, so a case costs
+        what its few thousand edges cost); every entry against float64, forward and adjoint."""
+        import spmm_routes_ref as R
+        import test_gpu_spmm_routes as tr_
+        d = rnd.choice([4, 8, 16, 32, 48, 64, 96, 128, 192, 256])
+        form = rnd.choice(R.FORMS)
+        n_rows = R.K_SMALL_ROWS + rnd.choice([-1, 1]) * rnd.randint(0, 4096) - rnd.choice([0, 0, 200_000])
+        n_src, M = rnd.choice([rnd.randint(1, 15), rnd.randint(16, 5000)]), rnd.choice([3, 300])
+        last["call"] = f"spmm_rows_case(d={d}, form={form!r}, n_rows={n_rows} ({R.variant(n_rows)}), n_src={n_src}, M={M})"
+        wide = d in R.WIDE_WIDTHS and rnd.random() < 0.5      # the second tuning of d = 256: short rows past 64 lanes
+        last["call"] += f" wide={wide}"
+        tr_._case(dev, d, form, n_rows, M, n_src, twin=False, bwd=True, wide=wide)
+
     cases.append(("spmm", spmm_case))
     cases.append(("spmm", spmm_case))            # the path's own kernel: drawn twice as often
+    cases.append(("spmm_rows", spmm_rows_case))
     eng = lambda: rnd.choice(["f16x2", "f16x2", "f32"])   # noqa: E731
     cases += [
         ("dx_any_scale", lambda: tr.test_fusion_backward_dx_per_node_at_any_gradient_scale(dev, rnd.choice([32, 64]), rnd.choice([1, 2, 3, 4, 5, 6]), n_(40, 4000), eng())),
