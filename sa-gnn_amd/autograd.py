@@ -599,9 +599,10 @@ class SeqAttnFn(torch.autograd.Function):
         g_att = ops.leaky_bwd(att, g, leaky)
         dqkv = ops.seq_attn_bwd(qkv, g_att, seg_len, P, heads)
         y = ops.layernorm_td(x.view(R, 1, d), gamma.detach(), beta.detach()).view(R, d)     # not saved: recomputed
-        # dW, db and dy as two products, not the fused tail (ops.attn_bwd_tail): it scales its chunks of 32 rows against
-        # the gradient rows it has met, and a workgroup whose FIRST chunk holds only zero rows (a slab's padding: any
-        # slot shorter than P - 32) returns NaN bias gradients (measured on the Gowalla-shaped set)
+        # dW, db and dy as two products, not the fused tail (ops.attn_bwd_tail). This layer was written while the tail
+        # returned NaN bias gradients for a workgroup whose first chunk held only zero rows (a slab's padding: any slot
+        # shorter than P - 32). The tail now gives a zero gradient row the factor 0
+        # (tests/test_gpu_zero_grad_rows.py); moving this layer onto it is a performance change that has not been measured
         dy, dWqkv, dbqkv = _qkv_grads(y, dqkv, Wqkv, fused_tail=False, in_place=True)
         dy = dy.view(R, 1, d)
         dy, dgamma, dbeta = ops.layernorm_td_bwd(x.view(R, 1, d), dy, gamma.detach(), out=dy)

@@ -108,6 +108,9 @@ __device__ __forceinline__ float pow2_field(int field) {   // 2^(field - 127), 0
 //     chunks holding a non-finite gradient, a y segment below 2^-14, or a W out of range. One chunk raises E by at
 //     most 2^kJump (the first chunk: at most that much above its 4th largest row), so an isolated absurd entry
 //     (2e30 in a field of ones) goes through the fp32 path without wiping out the rows after it.
+//   * A gradient row that is exactly ZERO (a node outside the batch, a padding slot: most rows of a training step) has no
+//     scale and contributes nothing: its y factor is 0 whatever E is, and a block that has met only such rows takes E
+//     from the first chunk that holds data, as from a first chunk.
 constexpr int kUp = 6, kJump = 16;
 constexpr float kUpInv = 1.f / 64.f;   // 2^-kUp
 // A gradient row enters the images with its maximum in [2^kGUp, 2^(kGUp + 1)), not in [1, 2): the split's absolute floor
@@ -230,12 +233,13 @@ __global__ __launch_bounds__(D == 64 ? 512 : 256, D == 64 ? 1 : 2) void attn_bwd
       stage[v] = make_float4(have ? val.x : 0.f, have ? val.y : 0.f, have ? val.z : 0.f, have ? val.w : 0.f);
     }
   };
-  // biased exponent of the largest |gradient| of my staged row (all lanes of the row agree)
-  auto row_exponent = [&]() -> int {
+  // bits of the largest |gradient| of my staged row (all lanes of the row agree): >> 23 is its biased exponent, 0 says
+  // that the row is exactly zero
+  auto row_max_bits = [&]() -> int {
     float mx = 0.f;
 #pragma unroll
     for (int v = NX; v < NS; ++v) mx = max3abs(max3abs(mx, stage[v].x, stage[v].y), stage[v].z, stage[v].w);
-    return group_max<LPRW>(__builtin_bit_cast(int, mx)) >> 23;
+    return group_max<LPRW>(__builtin_bit_cast(int, mx));
   };
   // What the running scale E follows. The attention tail's left operand is a layer-normed row (O(1)): the gradient row's
   // exponent alone. The LSTM's x | h rows have no such scale (hub rows of a propagated embedding reach 1e4): E follows the
@@ -250,14 +254,23 @@ __global__ __launch_bounds__(D == 64 ? 512 : 256, D == 64 ? 1 : 2) void attn_bwd
     const int kx = group_max<LPRW>(__builtin_bit_cast(int, mx)) >> 23;
     return kx == 0 ? 0 : e + kx - 127;                  // an all-zero left row weighs nothing
   };
-  // split the staged row into buffer `b` at the scales described above; `id` = chunk number + 1 marks the buffer for the fp32 path
-  auto commit = [&](int b, int id, int e, int E) {
+  // split the staged row into buffer `b` at the scales described above; `id` = chunk number + 1 marks the buffer for the fp32 path.
+  // A gradient row that is exactly zero (mbits == 0: a node outside the batch, a padding slot) has no terms in dW or db and
+  // a zero dy. Its y factor is 0, whatever E is: at the E of a block that has met nothing but such rows the factor of the
+  // clamped exponent would be 2^18, an inf as an f16 piece, and inf x 0 a NaN in every db. With the factor 0 the row's y
+  // image and its "ones" entry are zeros, its gradient image is zeros already, and nothing about its y can send the chunk
+  // to the fp32 path.
+  auto commit = [&](int b, int id, int mbits, int E) {
     char* const buf = lds + b * BUF;
+    const int e = mbits >> 23;
+    const bool zero_row = mbits == 0;
     const int k = e > 253 ? 253 : e < kGUp + 1 ? kGUp + 1 : e;
     const float s = pow2_field(254 - k + kGUp);        // dQKV row scale: 2^(127 - k + kGUp)
-    const float f = pow2_field(127 + k - E + kUp);     // y row scale
+    const float f = zero_row ? 0.f : pow2_field(127 + k - E + kUp);     // y row scale
     char* const dst = buf + img_off<D>(sr, sc >> 1) + (sc & 1) * 8;
-    bool bad = e == 255;
+    // f itself goes into the "ones" operand: from 2^16 on it is inf as an f16 piece, whatever the row's y is (a row 2^10 above
+    // E whose y stays below 2^-1 would pass the checks below)
+    bool bad = e == 255 || (DB && f >= 65536.f);
 #pragma unroll
     for (int v = 0; v < NX; ++v) {
       const float4 yr = stage[v];
@@ -270,7 +283,7 @@ __global__ __launch_bounds__(D == 64 ? 512 : 256, D == 64 ? 1 : 2) void attn_bwd
       // DY: y's scale is not part of what E follows, so a y segment that is small as a whole would lose its terms to the split's
       // floor. LSTM form: E follows the weight of the PRODUCT, a small x | h segment (a saturated gate leaves h = 1e-14 next
       // to 0.9) is small against the heaviest row's terms, which is all the floor is measured against.
-      bad = bad || yt >= kF16Lim || (DY && ys > 0.f && ys < 6.103515625e-05f);
+      bad = bad || (!zero_row && (yt >= kF16Lim || (DY && ys > 0.f && ys < 6.103515625e-05f)));
     }
 #pragma unroll
     for (int v = NX; v < NS; ++v) {
@@ -294,13 +307,14 @@ __global__ __launch_bounds__(D == 64 ? 512 : 256, D == 64 ? 1 : 2) void attn_bwd
   int cur = 0, slot = 0;   // buffer of chunk ch; emax slot its rows posted to
   int e_run = 1;           // E the y rows of chunk ch were scaled against
   int e_acc = 0;           // E the accumulators are at (0: nothing accumulated yet)
-  if (ch < n_chunks) {
-    fetch(ch);
-    const int e = row_exponent();
-    const int ew = row_weight(e);
-    if (sc == 0) ktab[sr] = ew > 253 ? 253 : ew < 1 ? 1 : ew;
+  bool seeded = false;     // attention tail: E has been taken from a chunk that holds data (block-uniform)
+  // The staged chunk's rows post their weights to ktab (0: a zero gradient row, which has no scale). Then every thread takes
+  // E for a block that has no scale yet: the chunk's largest row, but no more than 2^kJump above its 4th largest row that has
+  // data. 0: the chunk is all zeros and leaves the block as it was. One barrier inside; ktab is free again at the caller's next one.
+  auto seed_scale = [&](int mbits) -> int {
+    const int ew = row_weight(mbits >> 23);
+    if (sc == 0) ktab[sr] = mbits == 0 ? 0 : ew > 253 ? 253 : ew < 1 ? 1 : ew;
     __syncthreads();
-    // the first chunk is scaled against its own largest row, but no more than 2^kJump above its 4th largest
     int t0 = 0, t1 = 0, t2 = 0, t3 = 0;
 #pragma unroll
     for (int j = 0; j < kRows; ++j) {
@@ -310,11 +324,21 @@ __global__ __launch_bounds__(D == 64 ? 512 : 256, D == 64 ? 1 : 2) void attn_bwd
       a = t2 > v ? t2 : v, v = t2 > v ? v : t2, t2 = a;
       t3 = t3 > v ? t3 : v;
     }
+    // Zero and padding rows measure nothing: with fewer than four rows of data (a batch node's t rows among zeros, a ragged
+    // last chunk) the smallest of them stands for the 4th largest. An absurd row next to an ordinary one still goes through
+    // the fp32 path; a chunk whose only rows are absurd sets E by them, as a first chunk of 32 such rows always has.
+    t3 = t3 > 0 ? t3 : t2 > 0 ? t2 : t1 > 0 ? t1 : t0;
     // (the LSTM form scales every chunk against a maximum that includes its OWN rows — see the loop — and needs no cap)
-    // (a ragged last chunk of fewer than four rows that is a block's FIRST chunk has padding rows standing in for its 4th
-    // largest: its rows then take the fp32 path — exact, and the only safe choice with nothing to measure an absurd row against)
-    e_run = (!DY || t0 < t3 + kJump) ? t0 : t3 + kJump;
-    commit(0, (int)(ch + 1), e, e_run);
+    return (!DY || t0 < t3 + kJump) ? t0 : t3 + kJump;
+  };
+  if (ch < n_chunks) {
+    fetch(ch);
+    const int mb = row_max_bits();
+    // the first chunk is scaled against its own rows; if it is all zeros, the first chunk with data will be (see the loop)
+    const int e0 = seed_scale(mb);
+    seeded = e0 > 0;
+    e_run = seeded ? e0 : 1;
+    commit(0, (int)(ch + 1), mb, e_run);
   }
   __syncthreads();
   for (; ch < n_chunks; ch += gridDim.x) {
@@ -445,9 +469,16 @@ __global__ __launch_bounds__(D == 64 ? 512 : 256, D == 64 ? 1 : 2) void attn_bwd
     if (nxt < n_chunks) {
       const int ec = emax[slot];                        // chunk ch's own rows: complete since the barrier that closed its commit
       e_next = ec > e_run ? ec : e_run;
-      const int e = row_exponent();
+      const int mb = row_max_bits();
+      const int e = mb >> 23;
       const int ew = row_weight(e);
       if constexpr (DY) {
+        // a block that has met only zero rows has no scale to defend: it takes E from chunk nxt as a first chunk would,
+        // instead of climbing to it by 2^kJump per chunk through the fp32 path
+        if (!seeded) {
+          const int e0 = seed_scale(mb);
+          if (e0 > 0) seeded = true, e_next = e0;
+        }
         if (sc == 0) {                                    // what chunk nxt's rows ask of the chunk after it
           const int k = ew > 253 ? 253 : ew < 1 ? 1 : ew;
           atomicMax(emax + nslot, k < e_next + kJump ? k : e_next + kJump);
@@ -463,7 +494,7 @@ __global__ __launch_bounds__(D == 64 ? 512 : 256, D == 64 ? 1 : 2) void attn_bwd
         const int own = emax[nslot];
         e_next = own > e_next ? own : e_next;
       }
-      commit(cur ^ 1, (int)(nxt + 1), e, e_next);
+      commit(cur ^ 1, (int)(nxt + 1), mb, e_next);
     }
     if (tid == 0) emax[nslot == 2 ? 0 : nslot + 1] = 0;   // last read one iteration ago, next posted to one iteration ahead
     __syncthreads();  // next buffer complete and marked; this one free next time round
@@ -473,7 +504,7 @@ __global__ __launch_bounds__(D == 64 ? 512 : 256, D == 64 ? 1 : 2) void attn_bwd
   }
 
   // ---- flush: the accumulators hold the sums times 2^(127 - e_acc + kUp) --------------------------------------
-  if (e_acc == 0) return;   // nothing went through the matrix cores
+  if (e_acc == 0 || (DY && !seeded)) return;   // nothing, or nothing but zero rows, went through the matrix cores
   const float u1 = pow2_field(e_acc), u2 = kUpInv * kGUpInv;
 #pragma unroll
   for (int a = 0; a < MB; ++a)

@@ -136,7 +136,7 @@ X_LAYOUTS = ("padded", "time_major,vec")                 # both keep x's rows 16
 
 # ---- tail cases: (engine, d, rows, route) ----------------------------------------------------------------------------------
 # attn bwd tail, "f32 / d in {32, 64} / F32Mfma" and "f16x2,valu / d in {32, 64} / F16x2". Chunks of 32 rows: 1 and 3 rows
-# (one chunk of fewer than four, which the F16x2 kernel evaluates in fp32), 31, 32, 33 and 35 (a last chunk of 1 and of 3),
+# (one chunk of fewer than four: the F16x2 kernel measures its largest row against its smallest), 31, 32, 33 and 35 (a last chunk of 1 and of 3),
 # 66 (of 2), and the steady state.
 TAIL_ROWS = (1, 3, 31, 32, 33, 35, 64 + 2, "steady")
 TAIL_CASES = [(e, d, rows, tail_route(e, d)) for e in ENGINES for d in (32, 64) for rows in TAIL_ROWS]

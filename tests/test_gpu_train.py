@@ -10,7 +10,7 @@ from oracle import selfgnn_oracle as O
 pytestmark = pytest.mark.gpu
 
 
-def _setup(dev, d, ssldim, att_layer):
+def _setup(dev, d, ssldim, att_layer, U=70, I=60, nnz=(700, 650)):
     from sa_gnn_amd import synthetic
     from sa_gnn_amd.DataHandler import DataHandler
     from sa_gnn_amd.Params import args
@@ -20,8 +20,7 @@ def _setup(dev, d, ssldim, att_layer):
     args.graphNum, args.gnn_layer, args.latdim, args.leaky, args.ssldim = 2, 2, d, 0.5, ssldim
     args.att_layer, args.batch, args.pos_length, args.testSize, args.test = att_layer, 16, 12, 20, True
     args.sslNum, args.pred_num, args.keepRate, args.ssl_reg, args.reg = 3, 2, 1.0, 0.5, 1e-2
-    U, I = 70, 60
-    tmt = synthetic.make_trn_mat_time(U, I, [700, 650])
+    tmt = synthetic.make_trn_mat_time(U, I, list(nnz))
     seq = synthetic.make_sequence(tmt)
     tst_int = [int(rng.integers(0, I)) if u % 2 else None for u in range(U)]
     handler = DataHandler.from_memory(tmt, seq, tst_int, {u + 1: list(rng.integers(1, I + 1, size=30)) for u in range(U)})

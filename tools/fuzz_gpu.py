@@ -26,7 +26,8 @@ def main():
     import test_gpu_f16_range as tr
     import test_gpu_fusion as tf
     import test_gpu_fusion_multitile as tm
-    dev = torch.device("cuda:0")
+    import test_gpu_zero_grad_rows as tz
+    dev =torch.device("cuda:0")
     rnd = random.Random(a.seed)
     T_FAST = [1, 2, 3, 4, 5, 6, 8, 12, 16]
 
@@ -47,6 +48,8 @@ def main():
         ("attn_bwd_tail", lambda: td.test_attn_bwd_tail(dev, n_(1, 50000), rnd.choice([32, 64]), rnd.choice(["f16x2", "f32"]))),
         ("tail_any_scale", lambda: tr.test_attn_bwd_tail_rows_of_any_scale(dev, n_(33, 30000), rnd.choice([32, 64]),
                                                                            rnd.choice(["blocks", "mixed", "rising", "falling", "tiny", "needle"]), "f16x2")),
+        ("tail_zero_rows", lambda: tz.test_tail_zero_gradient_rows(dev, rnd.choice([32, 64]), n_(1, 30000), rnd.choice(tz.LAYOUTS),
+                                                                   rnd.choice(["ones", "mixed"]), rnd.choice(tz.Y_KINDS), rnd.choice(["f16x2", "f32"]))),
         ("lstm_dw_any_scale", lambda: tr.test_lstm_weight_gradient_pass_at_any_gradient_scale(dev, rnd.choice([32, 64]), rnd.randint(1, 9), n_(1, 9000),
                                                                                               rnd.choice(["blocks", "mixed", "tiny"]))),
         ("lstm_dw_dropout", lambda: tr.test_lstm_weight_gradient_pass_with_an_output_dropout_mask(dev, rnd.choice([32, 64]), rnd.randint(1, 8), n_(1, 5000))),
@@ -66,7 +69,7 @@ def main():
                 setattr(mod, nm, functools.wraps(f)(w))
 
     last = {"call": ""}
-    for m in (tb, td, tr, tf, tm):
+    for m in (tb, td, tr, tf, tm, tz):
         traced(m)
     def spmm_case():
         """Random interval graphs (hub rows / columns, empty rows, an empty interval now and then), random plan thresholds, any
