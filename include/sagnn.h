@@ -76,7 +76,7 @@ size_t sagnn_last_error(char* buf, size_t cap);
  * issues then takes one slot until they run out. sagnn_profile_read synchronises on the
  * recorded events, returns up to `cap` records in issue order and clears the log.
  * kind: 0 = SpMM row/chunk kernel (units_a = nnz, units_b = n_rows), 1 = SpMM fix-up,
- *       2 = LSTM, 3 = layer-norm, 4 = MHSA+mean (units_a = n, units_b = t),
+ *       2 = LSTM (or the GRU forward of sagnn_gru_fwd_f32), 3 = layer-norm, 4 = MHSA+mean (units_a = n, units_b = t),
  *       5 = an entry of the sequence attention (seq_attn.hip: gather, attention, pool, additive pool and
  *       their backwards; units_a = n_slots, units_b = pos_length),
  *       6 = sagnn_softmax_loss_f32 or its backward (units_a = n_queries, units_b = n_items).
@@ -537,6 +537,54 @@ int sagnn_lstm_bwd_ws_f32(const float* x, int64_t ld_n, int64_t ld_t, const floa
                           const float* cell, const float* dh_ext, int64_t ld_dhe, const float* drop_scale,
                           const float* W, float* dx, float* dW, float* db, int64_t n, int t, int d, void* workspace,
                           size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * GRU cell of the interval fusion (opt-in, --rnnCell gru). The reference builds its recurrent cell in a
+ * function it names gru_cell() (model.py:135-136) that returns BasicLSTMCell; these entries run TF 1.14 GRUCell in its
+ * place, with the same strides, outputs and dropout meaning as the LSTM block above. Per row, zero initial state,
+ * s = 0 .. t-1:
+ *     [r | u] = sigmoid([x_s | h] Wg + bg)       Wg [2d, 2d], bg [2d]; block order r, u
+ *     c       = tanh([x_s | r.h] Wc + bc)        Wc [2d, d],  bc [d]
+ *     h'      = u.h + (1 - u).c
+ *   Wg / Wc row-major; rows 0..d-1 multiply x_s, rows d..2d-1 the state (the layout of the LSTM's W). drop_scale
+ *   (nullable) [n, t, d] multiplies the EMITTED h only. d: a multiple of 32 up to 256 (SAGNN_ERR_DIM otherwise); x, h,
+ *   the weights and every optional tensor 16-byte aligned with ld_n, ld_t, ld_h multiples of 4 (SAGNN_ERR_ALIGN).
+ *   TensorFlow cannot be run beside this library: like the LSTM's, the floating-point side of this cell restates TF's
+ *   documented source and is pinned by no reference run.
+ *
+ * ARITHMETIC: exact fp32 (v_mfma_f32_32x32x2_f32, an fmaf chain) under EVERY engine: sagnn_set_engine does not reach
+ *   these entries, there is no f16 x 2 form of the GRU. Results are deterministic run to run, and a row's result does
+ *   not depend on which other rows the call holds.
+ *
+ * sagnn_gru_fused_supported — 1 where sagnn_gru_fwd_f32 runs as ONE launch persistent over t (d = 32, 64), else 0:
+ *   there the call runs one step at a time (two products by sagnn_dense_nn_f32's kernels and two element-wise launches
+ *   per step; the counterpart of the LSTM's generic route, not built for speed) in a caller workspace of
+ *   sagnn_gru_workspace_bytes = n * 3d floats, 16-byte aligned (0 where the fused kernel runs; SAGNN_ERR_WORKSPACE).
+ * sagnn_gru_fwd_f32 — h [n, t, d] (node stride ld_h) for every step. gates / cand (both or neither): the training
+ *   form, which also stores gates [n, t, 2d] = r | u after the sigmoid and cand [n, t, d] = c after the tanh, and h
+ *   un-dropped as the backward reads it: drop_scale must then be NULL (SAGNN_ERR_ARG).
+ *
+ * Backward: per step, for every supported d (a one-launch BPTT is not built). For s = t-1 .. 0, the host runs
+ *   sagnn_gru_bwd_cand_f32   dh = dh_ext[:, s] (. drop_scale) + dh_rec (NULL at the last step; row stride ld_dhr)
+ *                            -> da_c = dh (1-u)(1-c^2), du = dh (h_{s-1} - c), dh_u = dh u, each [n, d] dense
+ *   sagnn_dense_nn_f32       [dx_s | d(r.h)] = da_c Wc^T
+ *   sagnn_gru_bwd_gates_f32  d_rh [n, d] (row stride ld_drh) holds d(r.h) on entry; -> da_g [n, 2d] =
+ *                            [d(r.h) h_{s-1} r(1-r) | du u(1-u)], d_rh = dh_rec' = dh_u + d(r.h) r, and, when rh is not
+ *                            NULL, rh [n, d] = r.h_{s-1} (the operand of Wc's recurrent weight gradient)
+ *   sagnn_dense_nn_f32       [dx_s | dh_rec'] += da_g Wg^T (accumulate)
+ *   with gates / cand / h as the training form stored them and h_{-1} = 0. The weight and bias gradients are
+ *   sagnn_dense_tn(_seg)_f32 products of da_g / da_c against x_s, h_{s-1} and r.h_{s-1}.
+ * -------------------------------------------------------------------------------- */
+int sagnn_gru_fused_supported(int d);
+size_t sagnn_gru_workspace_bytes(int64_t n, int t, int d);
+int sagnn_gru_fwd_f32(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int d, const float* Wg,
+                      const float* bg, const float* Wc, const float* bc, const float* drop_scale, float* h,
+                      int64_t ld_h, float* gates, float* cand, void* workspace, size_t workspace_bytes, void* stream);
+int sagnn_gru_bwd_cand_f32(const float* gates, const float* cand, const float* h, const float* dh_ext, int64_t ld_dhe,
+                           const float* drop_scale, const float* dh_rec, int64_t ld_dhr, float* da_c, float* du,
+                           float* dh_u, int64_t n, int t, int d, int ts, void* stream);
+int sagnn_gru_bwd_gates_f32(const float* gates, const float* h, const float* du, const float* dh_u, float* d_rh,
+                            int64_t ld_drh, float* da_g, float* rh, int64_t n, int t, int d, int ts, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Prediction head (reference model.py:156-173). The masked sum of item /

@@ -91,6 +91,11 @@ _FLAGS = [
                             "--query_vector_dim; part of the model; needs --seqAtt full and latdim, query_vector_dim "
                             "multiples of 32). Not in the reference's graph: it constructs the AdditiveAttention "
                             "(model.py:147) and comments its call out (model.py:168)", ("sum", "additive")),
+    ("rnnCell", str, "lstm", "the recurrent cell of the interval fusion: lstm (BasicLSTMCell, what the reference's graph "
+                             "runs) or gru (TF 1.14 GRUCell: kernels [2d, 2d] and [2d, d] in place of the LSTM's [2d, 4d], "
+                             "one state; part of the model; exact fp32 under every engine; needs latdim a multiple of 32 up "
+                             "to 256; not with the interval-parallel path). Not in the reference's graph: it builds the cell "
+                             "in a function named gru_cell() that returns BasicLSTMCell (model.py:135-136)", ("lstm", "gru")),
     ("predLoss", str, "hinge", "the training loss of the prediction head: hinge (one positive against 40 sampled "
                                "negatives, the reference's loss) or softmax (cross-entropy of the user's next item "
                                "against every item the sampler may draw as its negative, over the whole catalogue; the "

@@ -164,23 +164,31 @@ def lstm_bwd(x, h, gates, cell, dh, drop, W):
                         deferred_dw=SPLIT_DW and t >= SPLIT_DW_MIN_T and 0 < need <= DEFERRED_DW_LIMIT)
 
 
+def _emit_and_attend(h, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, heads, drop_scale):
+    """The stages behind the recurrent cell, shared by both cells: the DropoutWrapper scaling of the emitted h (h itself is
+    stored un-dropped: it is also the recurrent operand of the backward pass), layer norm + attention + mean -> out [n, d]."""
+    h_emit = h if drop_scale is None else ops.mul(h, drop_scale.contiguous())
+    return ops.ln_mhsa_mean(h_emit, ln_gamma.detach(), ln_beta.detach(), Wq.detach(), bq.detach(), Wk.detach(),
+                            bk.detach(), Wv.detach(), bv.detach(), heads)
+
+
 def _fusion_forward(x, lstm_W, lstm_b, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, heads, drop_scale):
     """The training forward of the interval fusion on x [n, t, d] (any node/interval strides): returns
     (out [n, d], h, gates, cell), the last three as the backward reads them."""
-    # h is stored un-dropped (it is also the recurrent operand of the backward pass); the
-    # DropoutWrapper scaling of the emitted output is a separate element-wise pass
     h, gates, cell = ops.lstm_fwd_train(x, lstm_W.detach(), lstm_b.detach())
-    h_emit = h if drop_scale is None else ops.mul(h, drop_scale.contiguous())
-    out = ops.ln_mhsa_mean(h_emit, ln_gamma.detach(), ln_beta.detach(), Wq.detach(), bq.detach(), Wk.detach(),
-                           bk.detach(), Wv.detach(), bv.detach(), heads)
-    return out, h, gates, cell
+    return _emit_and_attend(h, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, heads, drop_scale), h, gates, cell
 
 
-def _fusion_backward(x, lstm_W, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, h, gates, cell, drop, heads, g_out):
-    """The backward of _fusion_forward for g_out [n, d]: returns (dx [n, t, d], then the gradients of lstm_W, lstm_b,
-    ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv)."""
-    n, t, d = x.shape
-    dev = x.device
+def _fusion_forward_gru(x, gru, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, heads, drop_scale):
+    """_fusion_forward under --rnnCell gru; gru = (Wg, bg, Wc, bc): returns (out [n, d], h, gates [n, t, 2d], cand)."""
+    h, gates, cand = ops.gru_fwd_train(x, *(w.detach() for w in gru))
+    return _emit_and_attend(h, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, heads, drop_scale), h, gates, cand
+
+
+def _attention_backward(h, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, drop, heads, g_out):
+    """The backward of _emit_and_attend for g_out [n, d], shared by both cells: returns (dh [n, t, d], the gradient at the
+    EMITTED h, then dgamma, dbeta, dWqkv [d, 3d], dbqkv [3d])."""
+    n, t, d = h.shape
     g_out = g_out.contiguous()
     # ---- recompute y and Q|K|V, attention backward -> dQ|dK|dV -----------------------------
     h_emit = h if drop is None else ops.mul(h, drop.contiguous())
@@ -191,6 +199,15 @@ def _fusion_backward(x, lstm_W, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, h, ga
     # ---- layer norm backward (in place on dy) ----------------------------------------------
     dy = dy.view(n, t, d)
     dh, dgamma, dbeta = ops.layernorm_td_bwd(h_emit, dy, ln_gamma.detach(), out=dy)
+    return dh, dgamma, dbeta, dWqkv, dbqkv
+
+
+def _fusion_backward(x, lstm_W, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, h, gates, cell, drop, heads, g_out):
+    """The backward of _fusion_forward for g_out [n, d]: returns (dx [n, t, d], then the gradients of lstm_W, lstm_b,
+    ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv)."""
+    n, t, d = x.shape
+    dev = x.device
+    dh, dgamma, dbeta, dWqkv, dbqkv = _attention_backward(h, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, drop, heads, g_out)
     # ---- BPTT ----------------------------------------------------------------------------------
     if ops.lstm_bwd_supported(d) and FUSED_BPTT:
         dx, dW, db = lstm_bwd(x, h, gates, cell, dh, drop, lstm_W.detach())
@@ -223,6 +240,74 @@ def _fusion_backward(x, lstm_W, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, h, ga
     return (dxh[:, :, :d].contiguous(), dW, db, dgamma, dbeta) + _split_qkv_grads(dWqkv, dbqkv, d)
 
 
+def _fusion_backward_gru(x, Wg, Wc, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, h, gates, cand, drop, heads, g_out):
+    """The backward of _fusion_forward_gru: returns (dx [n, t, d], then the gradients of Wg, bg, Wc, bc, ln_gamma, ln_beta,
+    Wq, bq, Wk, bk, Wv, bv). The BPTT is the per-step loop at every width, shaped like the LSTM's generic
+    one: per step two element-wise launches around [dx_s | d(r.h)] = da_c Wc^T and [dx_s | dh_{s-1}] += da_g Wg^T; the
+    pre-activation gradients of all steps and r.h_{s-1} stay in HBM ([t, n, 4d] in all) and the weight gradients are four
+    segmented products after the loop, or per-step products where that would pass DEFERRED_DW_LIMIT."""
+    n, t, d = x.shape
+    dev = x.device
+    dh, dgamma, dbeta, dWqkv, dbqkv = _attention_backward(h, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, drop, heads, g_out)
+
+    def new(*shape, zero=False):
+        return (torch.zeros if zero else torch.empty)(shape, dtype=torch.float32, device=dev)
+
+    WgT, WcT = Wg.detach().t().contiguous(), Wc.detach().t().contiguous()            # [2d, 2d], [d, 2d]
+    dWg, dbg, dWc, dbc = new(2 * d, 2 * d, zero=True), new(2 * d, zero=True), new(2 * d, d, zero=True), new(d, zero=True)
+    defer = n * t * 4 * d * 4 <= DEFERRED_DW_LIMIT
+    k = t if defer else 1
+    dAg, dAc, RH = new(k, n, 2 * d), new(k, n, d), new(k, n, d)                      # da_g, da_c and r.h_{s-1} per step
+    du, dhu = new(n, d), new(n, d)
+    dxh = new(n, t, 2 * d)                                                           # [dx_s | dh_{s-1}] per step
+    for ts in range(t - 1, -1, -1):
+        j = ts if defer else 0
+        ops.gru_bwd_cand(gates, cand, h, dh, drop, None if ts == t - 1 else dxh[:, ts + 1, d:], dAc[j], du, dhu, ts)
+        ops.dense_nn(dAc[j], WcT, None, out=dxh[:, ts, :])                           # [dx_s | d(r.h)]
+        ops.gru_bwd_gates(gates, h, du, dhu, dxh[:, ts, d:], dAg[j], RH[j], ts)      # d(r.h) -> dh_u + d(r.h) r
+        ops.dense_nn(dAg[j], WgT, None, out=dxh[:, ts, :], accumulate=True)
+        if not defer:
+            ops.dense_tn(x[:, ts, :], dAg[j], dWg[:d], dbg)
+            ops.dense_tn(x[:, ts, :], dAc[j], dWc[:d], dbc)
+            if ts > 0:                                                               # h_{-1} = 0: no recurrent term at step 0
+                ops.dense_tn(h[:, ts - 1, :], dAg[j], dWg[d:], None)
+                ops.dense_tn(RH[j], dAc[j], dWc[d:], None)
+    if defer:
+        xt = x.permute(1, 0, 2)
+        ops.dense_tn_seg(xt, dAg, dWg[:d], dbg)
+        ops.dense_tn_seg(xt, dAc, dWc[:d], dbc)
+        if t > 1:
+            ops.dense_tn_seg(h.permute(1, 0, 2)[:t - 1], dAg[1:], dWg[d:], None)
+            ops.dense_tn_seg(RH[1:], dAc[1:], dWc[d:], None)
+    return (dxh[:, :, :d].contiguous(), dWg, dbg, dWc, dbc, dgamma, dbeta) + _split_qkv_grads(dWqkv, dbqkv, d)
+
+
+def _cell_args(p: dict):
+    """The cell's parameters as the fusion nodes take them, from a parameter dict as ops.interval_fusion reads it:
+    (lstm_W, lstm_b) and no GRU tail, or (None, None) and the tail (gru_Wg, gru_bg, gru_Wc, gru_bc)."""
+    if ops.fusion_cell(p) == "gru":
+        return (None, None), (p["gru_Wg"], p["gru_bg"], p["gru_Wc"], p["gru_bc"])
+    return (p["lstm_W"], p["lstm_b"]), ()
+
+
+def _cell_forward(x, lstm_W, lstm_b, gru, attn, heads, drop_scale):
+    """(out, h, gates, cell or cand) under whichever cell is given: gru = () or (Wg, bg, Wc, bc); attn = the eight
+    layer-norm / attention parameters."""
+    if gru:
+        return _fusion_forward_gru(x, gru, *attn, heads, drop_scale)
+    return _fusion_forward(x, lstm_W, lstm_b, *attn, heads, drop_scale)
+
+
+def _cell_backward(x, cell_w, attn, h, gates, cell, drop, heads, g_out):
+    """cell_w: (lstm_W,) or (Wg, Wc), as saved. Returns (dx, (dlstm_W, dlstm_b), (the GRU tail's four gradients or ()),
+    the eight gradients of attn)."""
+    if len(cell_w) == 2:
+        grads = _fusion_backward_gru(x, *cell_w, *attn, h, gates, cell, drop, heads, g_out)
+        return grads[0], (None, None), grads[1:5], grads[5:]
+    grads = _fusion_backward(x, *cell_w, *attn, h, gates, cell, drop, heads, g_out)
+    return grads[0], grads[1:3], (), grads[3:]
+
+
 class IntervalFusionFn(torch.autograd.Function):
     """x [n, t, d] (any node/interval strides) + fusion parameters -> out [n, d]
     (reference model.py:135-155), differentiable in x and every parameter.
@@ -232,13 +317,15 @@ class IntervalFusionFn(torch.autograd.Function):
       attention backward (per node) -> dQ|dK|dV -> dW_qkv / db_qkv (dense tn) and dy (dense nn)
       -> layer-norm backward -> BPTT: per step an element-wise gate backward, dW_lstm += [x_t|h_{t-1}]^T
       dgates (dense tn) and d[x_t | h_{t-1}] = dgates @ W^T (dense nn).
-    Parameter order: lstm_W, lstm_b, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv."""
+    Parameter order: lstm_W, lstm_b, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv.
+    --rnnCell gru: lstm_W and lstm_b are None and the cell's Wg, bg, Wc, bc follow drop_scale (the GRU tail); the
+    recurrence and its BPTT are then _fusion_forward_gru / _fusion_backward_gru."""
 
     @staticmethod
-    def forward(ctx, x, lstm_W, lstm_b, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, heads, drop_scale):
-        out, h, gates, cell = _fusion_forward(x, lstm_W, lstm_b, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, heads,
-                                              drop_scale)
-        ctx.save_for_backward(x, lstm_W, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, h, gates, cell,
+    def forward(ctx, x, lstm_W, lstm_b, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, heads, drop_scale, *gru):
+        attn = (ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv)
+        out, h, gates, cell = _cell_forward(x, lstm_W, lstm_b, gru, attn, heads, drop_scale)
+        ctx.save_for_backward(x, *((gru[0], gru[2]) if gru else (lstm_W,)), *attn, h, gates, cell,
                               drop_scale if drop_scale is not None else torch.empty(0, device=x.device))
         ctx.heads = heads
         ctx.has_drop = drop_scale is not None
@@ -246,17 +333,19 @@ class IntervalFusionFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_out):
-        (x, lstm_W, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, h, gates, cell, drop) = ctx.saved_tensors
+        x, *cell_w, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, h, gates, cell, drop = ctx.saved_tensors
         drop = drop if ctx.has_drop else None
-        return _fusion_backward(x, lstm_W, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, h, gates, cell, drop, ctx.heads,
-                                g_out) + (None, None)
+        dx, d_lstm, d_gru, d_attn = _cell_backward(x, cell_w, (ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv), h, gates, cell, drop,
+                                                   ctx.heads, g_out)
+        return (dx,) + d_lstm + d_attn + (None, None) + d_gru
 
 
 def interval_fusion(x, p: dict, heads: int, drop_scale=None):
-    """Differentiable interval fusion; p as in ops.interval_fusion. d must be one of TRAINABLE_D."""
+    """Differentiable interval fusion; p as in ops.interval_fusion (either cell). d must be one of TRAINABLE_D."""
     _check_trainable(x)
-    return IntervalFusionFn.apply(x, p["lstm_W"], p["lstm_b"], p["ln_gamma"], p["ln_beta"], p["Wq"], p["bq"],
-                                  p["Wk"], p["bk"], p["Wv"], p["bv"], heads, drop_scale)
+    lstm, gru = _cell_args(p)
+    return IntervalFusionFn.apply(x, *lstm, p["ln_gamma"], p["ln_beta"], p["Wq"], p["bq"],
+                                  p["Wk"], p["bk"], p["Wv"], p["bv"], heads, drop_scale, *gru)
 
 
 class IntervalFusionRowsFn(torch.autograd.Function):
@@ -267,19 +356,20 @@ class IntervalFusionRowsFn(torch.autograd.Function):
     upstream gradient's rows (zeros in the padding slots j >= count), _fusion_backward, scatter dx into a zero
     [N, t, d] gradient. The fusion is independent per node, so an untouched row has no gradient to give.
     drop_scale: None, a full-size [N, t, d] mask (gathered with the rows) or a [cap, t, d] mask for the slots
-    (cap != N)."""
+    (cap != N). The cell's parameters as in IntervalFusionFn (the GRU tail follows drop_scale)."""
 
     @staticmethod
-    def forward(ctx, x, rows, count, lstm_W, lstm_b, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, heads, drop_scale):
+    def forward(ctx, x, rows, count, lstm_W, lstm_b, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, heads, drop_scale, *gru):
         N, t, d = (int(v) for v in x.shape)
         cap = int(rows.numel())
         dev = x.device
+        attn = (ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv)
         ctx.heads, ctx.shape, ctx.x_layout = heads, (N, t, d), x.stride(1) == N * d and x.stride(0) == d
         out = torch.zeros((N, d), dtype=torch.float32, device=dev)
         ctx.has_drop = drop_scale is not None
         if cap == 0:
             ctx.empty = True
-            ctx.save_for_backward(lstm_W, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv)
+            ctx.save_for_backward(*(gru or (lstm_W,)), *attn)
             return out
         ctx.empty = False
         xs = ops.rows_gather(x.detach(), rows)                                           # [cap, t, d] dense
@@ -291,9 +381,9 @@ class IntervalFusionRowsFn(torch.autograd.Function):
                 drop = drop_scale.contiguous()
             else:
                 raise ValueError(f"drop_scale: expected [{N}, {t}, {d}] or [{cap}, {t}, {d}], got {tuple(drop_scale.shape)}")
-        fused, h, gates, cell = _fusion_forward(xs, lstm_W, lstm_b, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, heads, drop)
+        fused, h, gates, cell = _cell_forward(xs, lstm_W, lstm_b, gru, attn, heads, drop)
         ops.rows_scatter(fused, rows, count, out)
-        ctx.save_for_backward(xs, rows, count, lstm_W, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, h, gates, cell,
+        ctx.save_for_backward(xs, rows, count, *((gru[0], gru[2]) if gru else (lstm_W,)), *attn, h, gates, cell,
                               drop if drop is not None else torch.empty(0, device=dev))
         return out
 
@@ -301,32 +391,37 @@ class IntervalFusionRowsFn(torch.autograd.Function):
     def backward(ctx, g_out):
         N, t, d = ctx.shape
         if ctx.empty:
-            params = ctx.saved_tensors
-            lstm_W = params[0]
-            zeros = (torch.zeros_like(lstm_W), torch.zeros(4 * d, dtype=torch.float32, device=lstm_W.device)) + \
-                tuple(torch.zeros_like(p) for p in params[1:])
-            return (torch.zeros((N, t, d), dtype=torch.float32, device=lstm_W.device), None, None) + zeros + (None, None)
-        (xs, rows, count, lstm_W, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, h, gates, cell, drop) = ctx.saved_tensors
+            *cell_w, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv = ctx.saved_tensors
+            dev = Wq.device
+            d_attn = tuple(torch.zeros_like(p) for p in (ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv))
+            if len(cell_w) == 4:
+                d_lstm, d_gru = (None, None), tuple(torch.zeros_like(p) for p in cell_w)
+            else:
+                d_lstm, d_gru = (torch.zeros_like(cell_w[0]), torch.zeros(4 * d, dtype=torch.float32, device=dev)), ()
+            return (torch.zeros((N, t, d), dtype=torch.float32, device=dev), None, None) + d_lstm + d_attn + (None, None) + d_gru
+        xs, rows, count, *cell_w, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, h, gates, cell, drop = ctx.saved_tensors
         drop = drop if ctx.has_drop else None
         g = ops.rows_gather(g_out if g_out.stride(1) == 1 else g_out.contiguous(), rows, count)   # [cap, d]
-        grads = _fusion_backward(xs, lstm_W, ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv, h, gates, cell, drop, ctx.heads, g)
+        dxs, d_lstm, d_gru, d_attn = _cell_backward(xs, cell_w, (ln_gamma, ln_beta, Wq, bq, Wk, bk, Wv, bv), h, gates, cell,
+                                                    drop, ctx.heads, g)
         dev = xs.device
         # in the slab's own layout ([t, N, d] storage seen as [N, t, d]) when x is that view
         dx = torch.zeros((t, N, d), dtype=torch.float32, device=dev).permute(1, 0, 2) if ctx.x_layout else \
             torch.zeros((N, t, d), dtype=torch.float32, device=dev)
-        ops.rows_scatter(grads[0].contiguous(), rows, count, dx)
-        return (dx, None, None) + grads[1:] + (None, None)
+        ops.rows_scatter(dxs.contiguous(), rows, count, dx)
+        return (dx, None, None) + d_lstm + d_attn + (None, None) + d_gru
 
 
 def interval_fusion_rows(x, rows, count, cap: int, p: dict, heads: int, drop_scale=None):
     """Differentiable interval fusion of rows[:cap] of x (IntervalFusionRowsFn): [N, d] with exact zeros in every row
     not among the first `count` slots. rows / count as ops.rows_compact returns them (count on the device; cap, the
-    number of slots to run, from the host, at least the count); p as in ops.interval_fusion."""
+    number of slots to run, from the host, at least the count); p as in ops.interval_fusion (either cell)."""
     _check_trainable(x)
     if int(cap) > rows.numel():
         raise ValueError(f"cap = {int(cap)} > {rows.numel()} row slots")
-    return IntervalFusionRowsFn.apply(x, rows[:int(cap)], count, p["lstm_W"], p["lstm_b"], p["ln_gamma"], p["ln_beta"],
-                                      p["Wq"], p["bq"], p["Wk"], p["bk"], p["Wv"], p["bv"], heads, drop_scale)
+    lstm, gru = _cell_args(p)
+    return IntervalFusionRowsFn.apply(x, rows[:int(cap)], count, *lstm, p["ln_gamma"], p["ln_beta"],
+                                      p["Wq"], p["bq"], p["Wk"], p["bk"], p["Wv"], p["bv"], heads, drop_scale, *gru)
 
 
 # ----------------------------------------------------------------------------------------------

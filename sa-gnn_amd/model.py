@@ -26,13 +26,15 @@ from .graph import NORMS, interval_pair
 SEQ_ATT = ("sum", "full")      # --seqAtt: the reference's collapsed head, or attention over every sequence item
 SEQ_POOL = ("sum", "additive")  # --seqPool: the reference's sum over the tokens, or its dead AdditiveAttention applied
 EDGE_TIME = ("none", "slot")   # --edgeTime: the reference's graph, or messages that add their edge's time-bucket row
+RNN_CELL = ("lstm", "gru")      # --rnnCell: the reference's BasicLSTMCell, or the GRU its gru_cell() is named after
 PRED_LOSS = ("hinge", "softmax")   # --predLoss: the reference's sampled hinge loss, or softmax over the whole catalogue
 
 
-def random_fusion_params(d: int, device, seed: int = 0) -> dict:
+def random_fusion_params(d: int, device, seed: int = 0, cell: str = "lstm") -> dict:
     """Random-init fusion parameters with the shapes TF creates (BasicLSTMCell kernel [2d, 4d] and
     bias [4d]; layer_norm gamma/beta [d]; three dense kernels [d, d] with bias [d]). Kernels are
-    xavier-uniform; biases/beta get small random values so benchmarks and tests exercise them."""
+    xavier-uniform; biases/beta get small random values so benchmarks and tests exercise them.
+    cell="gru": GRUCell's gate kernel [2d, 2d] / bias [2d] and candidate kernel [2d, d] / bias [d] in the LSTM's place."""
     g = torch.Generator(device="cpu")
     g.manual_seed(seed)
 
@@ -43,7 +45,11 @@ def random_fusion_params(d: int, device, seed: int = 0) -> dict:
     def small(n, mean=0.0):
         return (mean + 0.1 * torch.randn(n, generator=g)).to(device)
 
-    return {"lstm_W": xavier(2 * d, 4 * d), "lstm_b": small(4 * d), "ln_gamma": small(d, 1.0),
+    if cell not in RNN_CELL:
+        raise ValueError(f"cell {cell!r}: one of {RNN_CELL}")
+    rnn = {"lstm_W": xavier(2 * d, 4 * d), "lstm_b": small(4 * d)} if cell == "lstm" else \
+        {"gru_Wg": xavier(2 * d, 2 * d), "gru_bg": small(2 * d, 1.0), "gru_Wc": xavier(2 * d, d), "gru_bc": small(d)}
+    return {**rnn, "ln_gamma": small(d, 1.0),
             "ln_beta": small(d), "Wq": xavier(d, d), "bq": small(d), "Wk": xavier(d, d), "bk": small(d),
             "Wv": xavier(d, d), "bv": small(d)}
 
@@ -289,8 +295,17 @@ class Recommender:
         d = args.latdim
         # tf.contrib.rnn.BasicLSTMCell(d) shared by users and items (model.py:135-144):
         # kernel [2d, 4d] glorot-uniform (TF's default initializer), bias zeros.
-        self.lstm_kernel = NNs.defineParam("rnn_lstm_kernel", [2 * d, 4 * d])
-        self.lstm_bias = NNs.defineParam("rnn_lstm_bias", [4 * d], initializer="zeros")
+        if args.rnnCell == "gru":
+            # --rnnCell gru: TF 1.14 GRUCell's four variables in the LSTM's place: both kernels
+            # glorot-uniform, the gate bias 1.0 (GRUCell's bias_initializer default for r | u), the candidate bias zeros
+            self.rnn_cell = {"gru_Wg": NNs.defineParam("rnn_gru_gates_kernel", [2 * d, 2 * d]),
+                             "gru_bg": NNs.defineParam("rnn_gru_gates_bias", [2 * d], initializer="ones"),
+                             "gru_Wc": NNs.defineParam("rnn_gru_candidate_kernel", [2 * d, d]),
+                             "gru_bc": NNs.defineParam("rnn_gru_candidate_bias", [d], initializer="zeros")}
+        else:
+            self.lstm_kernel = NNs.defineParam("rnn_lstm_kernel", [2 * d, 4 * d])
+            self.lstm_bias = NNs.defineParam("rnn_lstm_bias", [4 * d], initializer="zeros")
+            self.rnn_cell = {"lstm_W": self.lstm_kernel, "lstm_b": self.lstm_bias}   # as ops.interval_fusion's p names them
         # two layer_norm calls -> separate gamma/beta (model.py:152-153)
         self.ln = []
         for tag in ("LayerNorm", "LayerNorm_1"):
@@ -370,8 +385,7 @@ class Recommender:
         outs = []
         for x, (gamma, beta), att in ((user_vector_tensor, self.ln[0], self.multihead_self_attention0),
                                       (item_vector_tensor, self.ln[1], self.multihead_self_attention1)):
-            p = {"lstm_W": self.lstm_kernel.detach(), "lstm_b": self.lstm_bias.detach(),
-                 "ln_gamma": gamma.detach(), "ln_beta": beta.detach()}
+            p = {**{k: v.detach() for k, v in self.rnn_cell.items()}, "ln_gamma": gamma.detach(), "ln_beta": beta.detach()}
             p.update({k: v.detach() for k, v in att.weights().items()})
             outs.append(ops.interval_fusion(x, p, heads))
         return outs[0], outs[1]
@@ -798,7 +812,7 @@ class Recommender:
             n_run = max(counts[side], 1) if subset else x.shape[0]
             if drop is None and keep < 1.0:                               # DropoutWrapper(output_keep_prob)
                 drop = (torch.rand((n_run, T, d), device=self.device) < keep).float() / keep
-            p = {"lstm_W": self.lstm_kernel, "lstm_b": self.lstm_bias, "ln_gamma": gamma, "ln_beta": beta}
+            p = {**self.rnn_cell, "ln_gamma": gamma, "ln_beta": beta}
             p.update(att.weights())
             if subset:
                 rows, count = touched["rows"][side]
@@ -1117,7 +1131,7 @@ class Recommender:
         with open(os.path.join(directory, "History", args.save_path + ".his"), "wb") as fs:
             pickle.dump(self.metrics, fs)
         state = {"params": {k: v.detach().cpu() for k, v in NNs.params.items()}, "adjNorm": args.adjNorm,
-                 "seqAtt": args.seqAtt, "seqPool": args.seqPool, "edgeTime": self._edge_time_state()}
+                 "seqAtt": args.seqAtt, "seqPool": args.seqPool, "edgeTime": self._edge_time_state(), "rnnCell": args.rnnCell}
         if getattr(self, "optimizer", None) is not None:
             state["optimizer"] = self.optimizer.state_dict()
         torch.save(state, os.path.join(directory, "Models", args.save_path))
@@ -1146,6 +1160,10 @@ class Recommender:
         if stored_pool != args.seqPool:
             raise ValueError(f"checkpoint was trained with --seqPool {stored_pool}, this run has --seqPool {args.seqPool}: "
                              "the head's pooling is part of the model")
+        stored_cell = state.get("rnnCell", "lstm")       # a checkpoint from before --rnnCell is an LSTM model
+        if stored_cell != args.rnnCell:
+            raise ValueError(f"checkpoint was trained with --rnnCell {stored_cell}, this run has --rnnCell {args.rnnCell}: "
+                             "the recurrent cell is part of the model")
         stored_time = state.get("edgeTime", {"mode": "none"})      # a checkpoint from before --edgeTime has no time term
         if stored_time != self._edge_time_state():
             raise ValueError(f"checkpoint was trained with --edgeTime {stored_time}, this run has {self._edge_time_state()}: "
@@ -1181,6 +1199,10 @@ class Recommender:
             raise ValueError(f"--seqPool {args.seqPool}: one of {SEQ_POOL}")
         if args.predLoss not in PRED_LOSS:
             raise ValueError(f"--predLoss {args.predLoss}: one of {PRED_LOSS}")
+        if args.rnnCell not in RNN_CELL:
+            raise ValueError(f"--rnnCell {args.rnnCell}: one of {RNN_CELL}")
+        if args.rnnCell == "gru" and (args.latdim % 32 or not 32 <= args.latdim <= 256):   # the GRU entries' widths
+            raise ValueError(f"--rnnCell gru needs latdim to be a multiple of 32 up to 256, got {args.latdim}")
         if args.edgeTime not in EDGE_TIME:
             raise ValueError(f"--edgeTime {args.edgeTime}: one of {EDGE_TIME}")
         time = None

@@ -870,6 +870,80 @@ def lstm_bwd_step(gates: torch.Tensor, cell: torch.Tensor, dh: torch.Tensor, dro
                                               dc_p, n, t, d, int(ts), _stream()))
 
 
+def gru_fused_supported(d: int) -> bool:
+    """Whether the GRU forward runs as one launch persistent over t at this width (sagnn_gru_fused_supported: d = 32,
+    64); elsewhere gru_fwd runs one step at a time."""
+    return bool(_lib.load().sagnn_gru_fused_supported(int(d)))
+
+
+def _gru_fwd(x, Wg, bg, Wc, bc, drop_scale, out, gates, cand):
+    n, t, d, ld_n, ld_t = _ntd("x", x)
+    w_p = (_f32_flat("Wg", Wg, 4 * d * d), _f32_flat("bg", bg, 2 * d), _f32_flat("Wc", Wc, 2 * d * d), _f32_flat("bc", bc, d))
+    drop_p = None if drop_scale is None else _f32_flat("drop_scale", drop_scale, n * t * d)
+    ld_h = _ntd_dense("out", out, n, t, d)
+    _one_device(x, Wg=Wg, bg=bg, Wc=Wc, bc=bc, drop_scale=drop_scale, out=out)
+    lib = _lib.load()
+    need = int(lib.sagnn_gru_workspace_bytes(n, t, d))
+    ws = torch.empty(need // 4, dtype=torch.float32, device=x.device) if need else None
+    check(lib.sagnn_gru_fwd_f32(x.data_ptr(), ld_n, ld_t, n, t, d, *w_p, drop_p, _ptr_or_empty(out), ld_h, _ptr(gates),
+                                _ptr(cand), _ptr(ws), need, _stream()))
+
+
+def gru_fwd(x: torch.Tensor, Wg: torch.Tensor, bg: torch.Tensor, Wc: torch.Tensor, bc: torch.Tensor,
+            drop_scale: torch.Tensor | None = None, out: torch.Tensor | None = None):
+    """TF 1.14 GRUCell over T, zero initial state (--rnnCell gru): sagnn_gru_fwd_f32. x [n, t, d] (any
+    node / interval strides), Wg [2d, 2d] (r | u), bg [2d], Wc [2d, d], bc [d], drop_scale None or [n, t, d] contiguous
+    (scales the emitted h only) -> h [n, t, d] (`out`: each node's block contiguous). Exact fp32 under every engine."""
+    n, t, d = (int(v) for v in x.shape)
+    if out is None:
+        out = torch.empty((n, t, d), dtype=torch.float32, device=x.device)
+    _gru_fwd(x, Wg, bg, Wc, bc, drop_scale, out, None, None)
+    return out
+
+
+def gru_fwd_train(x: torch.Tensor, Wg: torch.Tensor, bg: torch.Tensor, Wc: torch.Tensor, bc: torch.Tensor):
+    """The training forward of the GRU: -> (h [n, t, d] un-dropped, gates [n, t, 2d] = r | u, cand [n, t, d]) as
+    gru_bwd_cand / gru_bwd_gates read them. h is gru_fwd's bit for bit."""
+    n, t, d = (int(v) for v in x.shape)
+    h = torch.empty((n, t, d), dtype=torch.float32, device=x.device)
+    gates = torch.empty((n, t, 2 * d), dtype=torch.float32, device=x.device)
+    cand = torch.empty((n, t, d), dtype=torch.float32, device=x.device)
+    _gru_fwd(x, Wg, bg, Wc, bc, None, h, gates, cand)
+    return h, gates, cand
+
+
+def gru_bwd_cand(gates: torch.Tensor, cand: torch.Tensor, h: torch.Tensor, dh: torch.Tensor, drop: torch.Tensor | None,
+                 dh_rec: torch.Tensor | None, da_c: torch.Tensor, du: torch.Tensor, dh_u: torch.Tensor, ts: int):
+    """Step ts of the GRU's BPTT, candidate half (sagnn_gru_bwd_cand_f32): gates / cand / h of gru_fwd_train, dh
+    [n, t, d] the gradient at the emitted h (drop: its scale or None), dh_rec [n, d] (any row stride) the recurrent
+    gradient from step ts + 1 (None at the last step) -> da_c, du, dh_u, each [n, d] contiguous, written."""
+    n, t, d = (int(v) for v in cand.shape)
+    g_p, c_p, h_p = _f32_flat("gates", gates, n * t * 2 * d), _f32_flat("cand", cand, n * t * d), _f32_flat("h", h, n * t * d)
+    ld_dh = _ntd_dense("dh", dh, n, t, d)
+    drop_p = None if drop is None else _f32_flat("drop", drop, n * t * d)
+    ld_rec = _f32_rows("dh_rec", dh_rec, d, n)
+    outs = (_f32_flat("da_c", da_c, n * d), _f32_flat("du", du, n * d), _f32_flat("dh_u", dh_u, n * d))
+    _one_device(gates, cand=cand, h=h, dh=dh, drop=drop, dh_rec=dh_rec, da_c=da_c, du=du, dh_u=dh_u)
+    check(_lib.load().sagnn_gru_bwd_cand_f32(g_p, c_p, h_p, _ptr_or_empty(dh), ld_dh, drop_p, _ptr(dh_rec), ld_rec, *outs,
+                                             n, t, d, int(ts), _stream()))
+
+
+def gru_bwd_gates(gates: torch.Tensor, h: torch.Tensor, du: torch.Tensor, dh_u: torch.Tensor, d_rh: torch.Tensor,
+                  da_g: torch.Tensor, rh: torch.Tensor | None, ts: int):
+    """Step ts of the GRU's BPTT, gate half (sagnn_gru_bwd_gates_f32): d_rh [n, d] (any row stride) holds d(r.h_prev)
+    and becomes the recurrent gradient dh_u + d(r.h_prev) r; da_g [n, 2d] and, when given, rh [n, d] = r.h_prev are
+    written (both contiguous)."""
+    n, t, d = (int(v) for v in h.shape)
+    g_p, h_p = _f32_flat("gates", gates, n * t * 2 * d), _f32_flat("h", h, n * t * d)
+    du_p, dhu_p = _f32_flat("du", du, n * d), _f32_flat("dh_u", dh_u, n * d)
+    ld_drh = _f32_rows("d_rh", d_rh, d, n)
+    dag_p = _f32_flat("da_g", da_g, n * 2 * d)
+    rh_p = None if rh is None else _f32_flat("rh", rh, n * d)
+    _one_device(gates, h=h, du=du, dh_u=dh_u, d_rh=d_rh, da_g=da_g, rh=rh)
+    check(_lib.load().sagnn_gru_bwd_gates_f32(g_p, h_p, du_p, dhu_p, _ptr_or_empty(d_rh), ld_drh, dag_p, rh_p, n, t, d, int(ts),
+                                              _stream()))
+
+
 def layernorm_td(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-12,
                  out: torch.Tensor | None = None):
     """layer_norm over (t, d) per node (reference model.py:152-153): sagnn_layernorm_td_f32."""
@@ -1000,15 +1074,39 @@ def attn_bwd_tail(y2: torch.Tensor, dqkv: torch.Tensor, Wqkv: torch.Tensor, dWqk
     return y2
 
 
+LSTM_KEYS = ("lstm_W", "lstm_b")
+GRU_KEYS = ("gru_Wg", "gru_bg", "gru_Wc", "gru_bc")
+
+
+def fusion_cell(p: dict) -> str:
+    """"lstm" or "gru": which recurrent cell a fusion parameter dict carries (all of LSTM_KEYS, or all of GRU_KEYS).
+    Both cells: ValueError; neither, or part of one: KeyError, as reading the missing key would raise."""
+    has = [any(k in p for k in keys) for keys in (LSTM_KEYS, GRU_KEYS)]
+    if has[0] and has[1]:
+        raise ValueError("fusion parameters: give the LSTM's (lstm_W, lstm_b) or the GRU's (gru_Wg, gru_bg, gru_Wc, gru_bc), not both")
+    keys = GRU_KEYS if has[1] else LSTM_KEYS
+    missing = [k for k in keys if k not in p]
+    if missing:
+        raise KeyError(f"fusion parameters: missing {missing}" + ("" if any(has) else " (found neither cell)"))
+    return "gru" if has[1] else "lstm"
+
+
 def interval_fusion(x: torch.Tensor, p: dict, heads: int, out: torch.Tensor | None = None,
                     workspace: torch.Tensor | None = None):
     """LSTM -> layer_norm -> MHSA -> mean (reference model.py:135-155): sagnn_interval_fusion_f32.
-    p: lstm_W [2d,4d], lstm_b [4d], ln_gamma [d], ln_beta [d], Wq/bq/Wk/bk/Wv/bv."""
+    p: lstm_W [2d,4d], lstm_b [4d], ln_gamma [d], ln_beta [d], Wq/bq/Wk/bk/Wv/bv.
+    With gru_Wg [2d,2d], gru_bg [2d], gru_Wc [2d,d], gru_bc [d] in place of lstm_W / lstm_b (--rnnCell gru): the GRU
+    (gru_fwd) into the workspace, then ln_mhsa_mean on it. A dict with both cells or neither is refused."""
     lib = _lib.load()
     n, t, d, ld, ldt = _ntd("x", x)
     if out is None:
         out = torch.empty((n, d), dtype=torch.float32, device=x.device)
     ldo = _f32_rows("out", out, d, n)
+    if fusion_cell(p) == "gru":
+        if workspace is None or workspace.numel() * workspace.element_size() < n * t * d * 4 or workspace.dtype != torch.float32:
+            workspace = torch.empty(max(n * t * d, 1), dtype=torch.float32, device=x.device)
+        h = gru_fwd(x, *(p[k] for k in GRU_KEYS), out=workspace.view(-1)[:n * t * d].view(n, t, d))
+        return ln_mhsa_mean(h, p["ln_gamma"], p["ln_beta"], *(p[k] for k in ("Wq", "bq", "Wk", "bk", "Wv", "bv")), heads, out=out)
     need = int(lib.sagnn_interval_fusion_workspace_bytes(n, t, d))
     if workspace is None or workspace.numel() * workspace.element_size() < need:
         workspace = torch.empty(max(need // 4, 1), dtype=torch.float32, device=x.device)

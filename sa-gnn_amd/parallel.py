@@ -59,6 +59,9 @@ class IntervalSharding:
         if getattr(args, "edgeTime", "none") != "none":
             # the runners' row slices carry no buckets: they would run without the time term
             raise ValueError(f"--edgeTime {args.edgeTime} is not supported by the interval-parallel path")
+        if getattr(args, "rnnCell", "lstm") != "lstm":
+            # RoundFusion continues the LSTM's state across exchange rounds: the GRU has no state-continuation entry
+            raise ValueError(f"--rnnCell {args.rnnCell} is not supported by the interval-parallel path")
         self.T, self.world, self.rank = int(n_intervals), int(world), int(rank)
         self.rounds = -(-self.T // self.world)            # all-to-all calls every rank takes part in
 

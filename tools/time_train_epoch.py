@@ -27,6 +27,23 @@ from sa_gnn_amd.Utils import NNLayers as NNs  # noqa: E402
 from sa_gnn_amd.model import Recommender      # noqa: E402
 
 
+def gowalla_shaped_handler():
+    """Sets gowalla.sh's hyper-parameters in Params.args and returns the Gowalla-shaped synthetic DataHandler (also what
+    tools/bench_gru.py trains on)."""
+    Params.parse_args("--data gowalla --lr 2e-3 --reg 1e-2 --ssl_reg 1e-6 --epoch 150 --batch 512 --sslNum 40 --graphNum 3 "
+                      "--gnn_layer 2 --att_layer 1 --testSize 1000 --ssldim 48 --keepRate 0.5".split(), namespace=args)
+    np.random.seed(100)
+    U, I = 48653, 52619
+    tmt = synthetic.make_trn_mat_time(U, I, [600000] * 3)
+    seq = synthetic.make_sequence(tmt)
+    rng = np.random.default_rng(1)
+    tst = [None] * U
+    for u in rng.choice(U, 10000, replace=False):
+        tst[u] = int(rng.integers(0, I))
+    test_dict = {u + 1: list(rng.integers(1, I + 1, size=1000)) for u in range(U)}
+    return DataHandler.from_memory(tmt, seq, tst, test_dict)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("--epoch-only", action="store_true", help="one warm-up and one device-sampler epoch (for a profiler)")
@@ -43,19 +60,8 @@ def main():
     opt = ap.parse_args()
     if opt.seqPool != "sum" and opt.seqAtt == "sum":
         opt.seqAtt = "full"
-    Params.parse_args("--data gowalla --lr 2e-3 --reg 1e-2 --ssl_reg 1e-6 --epoch 150 --batch 512 --sslNum 40 --graphNum 3 "
-                      "--gnn_layer 2 --att_layer 1 --testSize 1000 --ssldim 48 --keepRate 0.5".split(), namespace=args)
+    h = gowalla_shaped_handler()
     args.edgeKeepRate = opt.edge_keep
-    np.random.seed(100)
-    U, I = 48653, 52619
-    tmt = synthetic.make_trn_mat_time(U, I, [600000] * 3)
-    seq = synthetic.make_sequence(tmt)
-    rng = np.random.default_rng(1)
-    tst = [None] * U
-    for u in rng.choice(U, 10000, replace=False):
-        tst[u] = int(rng.integers(0, I))
-    test_dict = {u + 1: list(rng.integers(1, I + 1, size=1000)) for u in range(U)}
-    h = DataHandler.from_memory(tmt, seq, tst, test_dict)
     rec = Recommender(torch.device("cuda:0"), h)
     if opt.seqPool != "sum":       # the additive variables are defined last: every other one starts where it always does
         args.seqAtt, args.seqPool = "full", "additive"
