@@ -808,6 +808,8 @@ class Recommender:
                                                               (iv, self.ln[1], self.multihead_self_attention1, "drop_i"))):
             x = xs.permute(1, 0, 2)                                       # [N, T, d] view of [T, N, d]: no copy
             drop = batch.get(key)
+            if drop is not None and drop.device != x.device:              # the kernels take its pointer as it is
+                raise ValueError(f'batch["{key}"] is on {drop.device}, the model on {x.device}')
             # the slots the fusion runs on: at least one, so that an empty set still runs (on padding, to zeros)
             n_run = max(counts[side], 1) if subset else x.shape[0]
             if drop is None and keep < 1.0:                               # DropoutWrapper(output_keep_prob)

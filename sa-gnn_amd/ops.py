@@ -1172,6 +1172,8 @@ def mul(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor | None = None):
     for name, x in (("a", a), ("b", b), ("out", out)):
         if x.dtype != torch.float32 or not x.is_contiguous() or x.numel() != a.numel():
             raise ValueError(f"{name}: need contiguous float32 tensors of equal size")
+        if x.device != a.device:          # e.g. a dropout mask left on the host: its pointer would fault the kernel
+            raise ValueError(f"{name} is on {x.device}, a on {a.device}: need all three on one device")
     check(_lib.load().sagnn_mul_f32(a.data_ptr(), b.data_ptr(), out.data_ptr(), a.numel(), _stream()))
     return out
 
