@@ -79,7 +79,8 @@ size_t sagnn_last_error(char* buf, size_t cap);
  *       2 = LSTM (or the GRU forward of sagnn_gru_fwd_f32), 3 = layer-norm, 4 = MHSA+mean (units_a = n, units_b = t),
  *       5 = an entry of the sequence attention (seq_attn.hip: gather, attention, pool, additive pool and
  *       their backwards; units_a = n_slots, units_b = pos_length),
- *       6 = sagnn_softmax_loss_f32 or its backward (units_a = n_queries, units_b = n_items).
+ *       6 = sagnn_softmax_loss_f32 or its backward (units_a = n_queries, units_b = n_items),
+ *       7 = sagnn_softmax_loss_cand_f32 or its backward (units_a = n_queries, units_b = n_cand).
  * -------------------------------------------------------------------------------- */
 int sagnn_profile_enable(int capacity);
 int sagnn_profile_read(float* ms, int32_t* kind, int64_t* units_a, int64_t* units_b, int cap,
@@ -954,6 +955,58 @@ int sagnn_softmax_loss_bwd_f32(const float* Q, int64_t ldq, const float* I, int6
                                const int64_t* excl_ptr, const int32_t* excl_items, const int32_t* excl_row,
                                int64_t n_lists, const float* lse, const float* g, float* dQ, int64_t lddq, float* dI,
                                int64_t lddi, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Sampled-candidate softmax cross-entropy (softmax_loss.hip, sampler.hip; --softmaxNegs, not in the reference): the
+ * loss above over a candidate list shared by the batch, so that a step reads n_cand + n_queries item rows only.
+ * sagnn_sample_strata_i32: a stratified draw of n_cand ids from [0, n_items). Candidate j is one uniform draw from
+ *   the stratum [lo_j, lo_{j+1}), lo_j = floor(j * n_items / n_cand) in 64-bit arithmetic: cand[j] = lo_j + the high half
+ *   of ((w0 << 32) | w1) * (lo_{j+1} - lo_j), with (w0, w1, ..) = philox4x32_10(counter = (j, 0, step, 0xFFFFFFFF),
+ *   key = seed); the batch samplers use the stream words 0, 1 and 2 + k. The list has exactly n_cand ids, strictly
+ *   ascending and distinct, and is a pure function of (seed, step, j); every item is drawn with probability 1 / (its
+ *   stratum's size), and the sizes differ by at most one. n_cand == n_items gives 0, 1, .., n_items - 1.
+ *   Refused before any launch: n_items < 1 or >= 2^31, n_cand < 0 or > n_items, a NULL cand with n_cand > 0. One launch
+ *   on `stream` (none when n_cand == 0).
+ * sagnn_softmax_loss_cand_f32: I is the full [n_items, d] table, cand int32 [n_cand] (DEVICE) strictly ascending ids
+ *   in [0, n_items); its contents are the caller's responsibility, they are used as row addresses. z, lse, tscore,
+ *   loss, the exclusion lists and the skipped rows are those of sagnn_softmax_loss_f32, with the eligible set
+ *     E_b = { c in cand : c not on row b's list, c != target[b] } + { target[b] }:
+ *   the target enters exactly once, through its own term, whether or not it is a candidate or on the list.
+ *   n_cand == 0 is legal: lse[b] = z(b, target[b]), no loss, no gradient.
+ * sagnn_softmax_loss_cand_bwd_f32: with g(b, i) as above over E_b,
+ *   dQ[b]  = sum_{i in E_b} g(b, i) I[i], the target's term included;
+ *   dIc[j] = sum over rows b with cand[j] in E_b and cand[j] != target[b] of g(b, cand[j]) Q[b]: row j of
+ *            dIc [n_cand, d] belongs to item cand[j];
+ *   dT[b]  = g(b, target[b]) Q[b], [n_queries, d]: the target's share of dI, one row per query (several rows may share
+ *            a target; adding them into dI is the caller's).
+ *   Every row of dQ, dIc and dT is WRITTEN (zeros where nothing contributes, skipped rows included).
+ * lse[b], tscore[b], dQ[b] and dT[b] depend on row b's inputs only; chunks depend on n_cand only; no atomics, all
+ *   outputs are bit-identical between runs.
+ * Limits: those of sagnn_softmax_loss_f32, and 0 <= n_cand <= n_items, cand non-NULL when n_cand > 0, lddic and lddt
+ *   multiples of 4 and >= d, dIc and dT 16-byte aligned, workspace_bytes >=
+ *   sagnn_softmax_loss_cand_workspace_bytes(n_queries, n_cand, d) (grows with each argument). Every argument is checked
+ *   before any device work. At most three launches each on `stream`, no allocation, no synchronisation (capturable).
+ *   Profile kind 7 (units_a = n_queries, units_b = n_cand).
+ * sagnn_softmax_target_add_f32: dI[target[b]] += dT[b] for every row b with a target in [0, n_items), the rows that
+ *   share a target added in ascending b by one thread per element (no atomics: bit-identical between runs). Meant
+ *   for a batch: a thread compares its target with all n_queries. Same limits on d, n_queries, n_items, strides and
+ *   alignment; one launch on `stream`, not recorded by the profile.
+ * -------------------------------------------------------------------------------- */
+int sagnn_softmax_target_add_f32(const float* dT, int64_t lddt, const int32_t* target, int64_t n_queries, int64_t n_items,
+                                 int d, float* dI, int64_t lddi, void* stream);
+int sagnn_sample_strata_i32(int64_t n_items, int64_t n_cand, uint64_t seed, uint32_t step, int32_t* cand, void* stream);
+size_t sagnn_softmax_loss_cand_workspace_bytes(int64_t n_queries, int64_t n_cand, int d);
+int sagnn_softmax_loss_cand_f32(const float* Q, int64_t ldq, const float* I, int64_t ldi, int64_t n_queries,
+                                int64_t n_items, int d, const int32_t* cand, int64_t n_cand, const int32_t* target,
+                                float inv_temp, float scale, const int64_t* excl_ptr, const int32_t* excl_items,
+                                const int32_t* excl_row, int64_t n_lists, float* loss, float* lse, float* tscore,
+                                void* workspace, size_t workspace_bytes, void* stream);
+int sagnn_softmax_loss_cand_bwd_f32(const float* Q, int64_t ldq, const float* I, int64_t ldi, int64_t n_queries,
+                                    int64_t n_items, int d, const int32_t* cand, int64_t n_cand, const int32_t* target,
+                                    float inv_temp, float scale, const int64_t* excl_ptr, const int32_t* excl_items,
+                                    const int32_t* excl_row, int64_t n_lists, const float* lse, const float* g, float* dQ,
+                                    int64_t lddq, float* dIc, int64_t lddic, float* dT, int64_t lddt, void* workspace,
+                                    size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

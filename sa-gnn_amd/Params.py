@@ -99,8 +99,8 @@ _FLAGS = [
     ("predLoss", str, "hinge", "the training loss of the prediction head: hinge (one positive against 40 sampled "
                                "negatives, the reference's loss) or softmax (cross-entropy of the user's next item "
                                "against every item the sampler may draw as its negative, over the whole catalogue; the "
-                               "same variables, so checkpoints carry over; needs --fusion_rows all and latdim in "
-                               "{32, 64, 128}). Not in the reference, which has the sampled hinge loss only "
+                               "same variables, so checkpoints carry over; needs --fusion_rows all, or --softmaxNegs > 0, "
+                               "and latdim in {32, 64, 128}). Not in the reference, which has the sampled hinge loss only "
                                "(model.py:241-246)", ("hinge", "softmax")),
     ("edgeTime", str, "none", "time inside the interval graphs: none (an edge's timestamp only decides which interval graph "
                               "holds it, as the reference's graph computes) or slot (every message adds the row of "
@@ -110,6 +110,11 @@ _FLAGS = [
                               "weights (model.py:81, :117) and comments the term out (model.py:86)", ("none", "slot")),
     ("softmaxTemp", float, 1.0, "temperature of --predLoss softmax: the logits are <q, item> / softmaxTemp, > 0 (not in "
                                 "the reference)"),
+    ("softmaxNegs", int, 0, "candidates of --predLoss softmax: 0 (the whole catalogue) or N > 0 (the softmax runs over N "
+                            "items drawn per step on the device, one uniformly from each of N equal strata of the "
+                            "catalogue and shared by the batch, minus the user's banned items, plus the slot's own "
+                            "target; N <= the item count; lifts the need for --fusion_rows all; not part of the model). "
+                            "Not in the reference, which has the sampled hinge loss only (model.py:241-246)"),
 ]
 
 

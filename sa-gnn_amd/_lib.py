@@ -226,6 +226,16 @@ SIGNATURES = {
     "sagnn_softmax_loss_bwd_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_float,
                                            c_float, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                            c_int64, c_void_p, c_int64, c_void_p, c_size_t, c_void_p]),
+    "sagnn_sample_strata_i32": (c_int, [c_int64, c_int64, c_uint64, c_uint32, c_void_p, c_void_p]),
+    "sagnn_softmax_target_add_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p]),
+    "sagnn_softmax_loss_cand_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int]),
+    "sagnn_softmax_loss_cand_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_int64,
+                                            c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                            c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "sagnn_softmax_loss_cand_bwd_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p,
+                                                c_int64, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_int64,
+                                                c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                                                c_void_p, c_size_t, c_void_p]),
 }
 
 

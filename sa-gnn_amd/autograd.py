@@ -555,6 +555,31 @@ class SoftmaxLossFn(torch.autograd.Function):
         return dQ, dI, None, None, None, None, None
 
 
+class SoftmaxLossCandFn(torch.autograd.Function):
+    """SoftmaxLossFn over a candidate list (ops.softmax_loss_cand, --softmaxNegs). The backward returns a full-size dI:
+    zeros, the candidates' rows copied to rows `cand` (distinct ids), then every slot's target row added at its target
+    by ops.softmax_target_add, which orders the slots that share a target: bit-identical between runs."""
+
+    @staticmethod
+    def forward(ctx, Q, I, cand, target, inv_temp, scale, excl, excl_row):
+        Q, I = Q.detach().contiguous(), I.detach().contiguous()
+        loss, lse, _ = ops.softmax_loss_cand(Q, I, cand, target, inv_temp, scale, excl, excl_row)
+        ctx.save_for_backward(Q, I, cand, target, lse)
+        ctx.args = (inv_temp, scale, excl, excl_row)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        Q, I, cand, target, lse = ctx.saved_tensors
+        dQ, dIc, dT = ops.softmax_loss_cand_bwd(Q, I, cand, target, lse, g.detach().reshape(1).float().contiguous(),
+                                                *ctx.args)
+        dI = torch.zeros_like(I)
+        if cand.numel():
+            dI.index_copy_(0, cand.long(), dIc)
+        ops.softmax_target_add(dI, dT, target)
+        return dQ, dI, None, None, None, None, None, None
+
+
 class ProdLeakySumFn(torch.autograd.Function):
     """s[e] = sum_j leaky(X[u][j] * Y[i][j]) (model.py:191, :199)."""
 

@@ -109,7 +109,7 @@ int gemm_tn(const float* X, int64_t ldx, int64_t xseg, const float* G, int64_t l
 
 // ---- optional per-launch timing (sagnn_profile_*) -------------------------------------------
 enum ProfileKind { kProfSpmmRows = 0, kProfSpmmFixup = 1, kProfLstm = 2, kProfLayerNorm = 3, kProfMhsa = 4, kProfSeqAtt = 5,
-                   kProfSoftmaxLoss = 6 };
+                   kProfSoftmaxLoss = 6, kProfSoftmaxLossCand = 7 };
 
 // Records a hipEvent pair around the launches issued during its lifetime, on the launch stream,
 // when profiling is enabled; otherwise does nothing.

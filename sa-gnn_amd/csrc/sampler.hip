@@ -108,6 +108,17 @@ __global__ void sample_ssl_kernel(const int32_t* __restrict__ bat, int64_t n_bat
   locs[off] = locs[off + 1] = (int32_t)b;
 }
 
+// cand[j] = lo_j + one uniform draw on [0, lo_{j+1} - lo_j), lo_j = floor(j * n_items / n_cand): one thread per
+// candidate, stream word 0xFFFFFFFF (the batch samplers use 0, 1 and 2 + k). Ascending and distinct by construction.
+__global__ void sample_strata_kernel(int64_t n_items, int64_t n_cand, uint64_t seed, uint32_t step,
+                                     int32_t* __restrict__ cand) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n_cand) return;
+  const int64_t lo = j * n_items / n_cand;
+  const int64_t up = (j + 1) * n_items / n_cand;
+  cand[j] = (int32_t)(lo + draw(seed, (uint32_t)j, 0, step, 0xFFFFFFFFu, (uint32_t)(up - lo)));
+}
+
 __device__ __forceinline__ void add4(float4& a, const float4& b) {
   a.x += b.x;
   a.y += b.y;
@@ -309,6 +320,23 @@ extern "C" int sagnn_seq_sum_bwd_f32(const float* g_seq, const float* g_pos, int
                        seg_len, n_slots, pos_length, d, d_fi, ld_dfi, n_items);
   hipLaunchKernelGGL(pos_grad_kernel, dim3(b_pos), dim3(kBlock), 0, s, g_pos, ldg, seg_len, n_slots, pos_length, d, d_pos,
                      ld_dpos);
+  SAGNN_HIP_TRY(hipGetLastError());
+  return SAGNN_OK;
+}
+
+extern "C" int sagnn_sample_strata_i32(int64_t n_items, int64_t n_cand, uint64_t seed, uint32_t step, int32_t* cand,
+                                       void* stream) {
+  if (n_items < 1 || n_items >= ((int64_t)1 << 31))
+    return sagnn::fail(SAGNN_ERR_ARG, "sample_strata: n_items = %lld, need 1 <= n_items < 2^31", (long long)n_items);
+  if (n_cand < 0 || n_cand > n_items)
+    return sagnn::fail(SAGNN_ERR_ARG, "sample_strata: n_cand = %lld, need 0 <= n_cand <= n_items = %lld", (long long)n_cand,
+                       (long long)n_items);
+  if (n_cand > 0 && !cand) return sagnn::fail(SAGNN_ERR_NULL, "sample_strata: null cand");
+  unsigned blocks = 0;
+  if (int rc = blocks_for(n_cand, &blocks)) return rc;
+  if (blocks == 0) return SAGNN_OK;
+  hipLaunchKernelGGL(sample_strata_kernel, dim3(blocks), dim3(kBlock), 0, static_cast<hipStream_t>(stream), n_items, n_cand,
+                     seed, step, cand);
   SAGNN_HIP_TRY(hipGetLastError());
   return SAGNN_OK;
 }

@@ -782,10 +782,16 @@ class Recommender:
         model (forward, evaluators, recommend, parallel) never drops.
         Under --predLoss softmax preLoss is the full-catalogue softmax cross-entropy of every active slot's positive
         (_softmax_pre_loss) and the batch's sampled negatives are not read. The flag is not part of the model: the
-        variables are the same, and checkpoints neither store nor check it."""
+        variables are the same, and checkpoints neither store nor check it. With --softmaxNegs N > 0 the softmax runs
+        over N candidates shared by the batch, drawn on the device at the top of the step (ops.sample_strata keyed by
+        batch["cand_seed"] = (seed, step), default (0, 0)) under either sampler, plus each slot's own target; under
+        --fusion_rows batch the candidates are marked as touched item rows."""
         T, L, d, heads, leaky = args.graphNum, args.gnn_layer, args.latdim, args.num_attention_heads, NNs.leaky
         keep = args.keepRate if keep_rate is None else keep_rate
         subset = args.fusion_rows == "batch"
+        if args.predLoss == "softmax" and args.softmaxNegs > 0:
+            batch = dict(batch, cand=ops.sample_strata(args.item, args.softmaxNegs, *batch.get("cand_seed", (0, 0)),
+                                                       self.device))
         if subset:        # the rows the loss reads, compacted on the device before the GNN stack is queued
             batch = dict(batch, uids=self._i32(batch["uids"]), iids=self._i32(batch["iids"]),
                          suids=[self._i32(v) for v in batch["suids"]], siids=[self._i32(v) for v in batch["siids"]])
@@ -866,7 +872,8 @@ class Recommender:
         with z_bi = <leaky(att[b]) + fu[u_b], fi[i]> / softmaxTemp and E_b = every item outside user u_b's banned list
         (the items negSamp never draws), plus the target t_b. One (slot, user, target) triple per active slot, from the
         positive half of the batch without a read-back: the first pair of each slot (host batch) or the pair at the
-        slot's pair offset (device batch: batch["active"] = (slots, offsets), host tables of sample_batch_device)."""
+        slot's pair offset (device batch: batch["active"] = (slots, offsets), host tables of sample_batch_device).
+        With batch["cand"] (--softmaxNegs, drawn by train_loss) E_b is the candidates outside the banned list plus t_b."""
         dev = self.device
         if "active" in batch:
             slots, first = batch["active"]
@@ -881,8 +888,11 @@ class Recommender:
         u = self._i32(batch["uids"]).index_select(0, first)
         t = self._i32(batch["iids"]).index_select(0, first)
         q = ag.LeakyAddFn.apply(att.index_select(0, slots), fu.index_select(0, u.long()), NNs.leaky)
-        return ag.SoftmaxLossFn.apply(q, fi, t, 1.0 / args.softmaxTemp, 1.0 / max(int(slots.numel()), 1),
-                                      self._banned_device(), u)
+        scale = 1.0 / max(int(slots.numel()), 1)
+        if "cand" in batch:     # --softmaxNegs: E_b = the step's candidates outside the banned list, plus the target
+            return ag.SoftmaxLossCandFn.apply(q, fi, batch["cand"], t, 1.0 / args.softmaxTemp, scale,
+                                              self._banned_device(), u)
+        return ag.SoftmaxLossFn.apply(q, fi, t, 1.0 / args.softmaxTemp, scale, self._banned_device(), u)
 
     def _head_att_sum_train(self, fi, batch):
         """The reference's collapsed head (--seqAtt sum) as autograd nodes: the masked sums make ONE token per slot and
@@ -908,15 +918,17 @@ class Recommender:
 
     def _touched_rows(self, batch) -> dict:
         """--fusion_rows batch: the user rows (uids, suids[k]) and item rows (iids, siids[k], the head's sequence items)
-        the loss reads, marked and compacted on the device (ops.rows_mark / rows_compact) into capacities known on the
-        host, and the two counts copied to pinned host memory without waiting. Returns {"rows": [(rows, count)] * 2,
-        "caps", "host": the pinned counts, "done": the event after their copy}."""
+        the loss reads (with --softmaxNegs also the step's candidates), marked and compacted on the device
+        (ops.rows_mark / rows_compact) into capacities known on the host, and the two counts copied to pinned host
+        memory without waiting. Returns {"rows": [(rows, count)] * 2, "caps", "host": the pinned counts, "done": the
+        event after their copy}."""
         U, I, dev = args.user, args.item, self.device
         flags_u, flags_i, host = self._cached(
             "_rows_bufs", (U, I, str(dev)), lambda: (torch.zeros(U, dtype=torch.uint8, device=dev),
                                                      torch.zeros(I, dtype=torch.uint8, device=dev),
                                                      torch.zeros(2, dtype=torch.int32, pin_memory=True)))
-        for ids in [batch["iids"]] + list(batch["siids"]):
+        cand = batch.get("cand")                                          # --softmaxNegs: the step's candidate rows
+        for ids in [batch["iids"]] + list(batch["siids"]) + ([] if cand is None else [cand]):
             ops.rows_mark(ids, flags_i)
         if "seq_seg" in batch:
             seg_begin, seg_len = batch["seq_seg"]
@@ -929,7 +941,8 @@ class Recommender:
         for ids in [batch["uids"]] + list(batch["suids"]):
             ops.rows_mark(ids, flags_u)
         cap_u = min(U, int(batch["uids"].numel()) + sum(int(v.numel()) for v in batch["suids"]))
-        cap_i = min(I, int(batch["iids"].numel()) + sum(int(v.numel()) for v in batch["siids"]) + n_seq)
+        cap_i = min(I, int(batch["iids"].numel()) + sum(int(v.numel()) for v in batch["siids"]) + n_seq
+                    + (0 if cand is None else int(cand.numel())))
         rows_u, count_u = ops.rows_compact(flags_u, max(cap_u, 1) if U else 0)
         rows_i, count_i = ops.rows_compact(flags_i, max(cap_i, 1) if I else 0)
         host[0:1].copy_(count_u, non_blocking=True)
@@ -1095,6 +1108,9 @@ class Recommender:
         edge_drop = args.edgeKeepRate < 1.0
         if edge_drop:     # its own seed per epoch, drawn only when the flag is on: a seeded run without it sees the
             edge_seed = int(np.random.randint(0, 2 ** 63, dtype=np.int64))      # np.random stream it always saw
+        cand_draw = args.predLoss == "softmax" and args.softmaxNegs > 0
+        if cand_draw:     # likewise, and after the edge-drop seed
+            cand_seed = int(np.random.randint(0, 2 ** 63, dtype=np.int64))
         # losses stay on the device until the epoch ends: a float() per step would make the host wait for the
         # step's kernels before it samples the next batch (host sampling and device work overlap this way)
         loss_sum = torch.zeros(1, dtype=torch.float32, device=self.device)
@@ -1104,6 +1120,8 @@ class Recommender:
             batch = self.sample_batch_device(batIds, seed, i) if device else self._host_train_batch(batIds)
             if edge_drop:
                 batch["edge_seed"] = (edge_seed, i)
+            if cand_draw:
+                batch["cand_seed"] = (cand_seed, i)
             params = self._trainable()
             for p in params.values():
                 p.grad = None
@@ -1217,8 +1235,15 @@ class Recommender:
             time = (self.handler.timeMin, args.slot, ops.check_n_buckets(self.handler.maxTime + 1))
         if not args.softmaxTemp > 0.0 or not np.isfinite(args.softmaxTemp):
             raise ValueError(f"--softmaxTemp {args.softmaxTemp}: need a finite temperature > 0")
+        if args.softmaxNegs < 0:
+            raise ValueError(f"--softmaxNegs {args.softmaxNegs}: need a count >= 0 (0 = the whole catalogue)")
+        if args.softmaxNegs > 0 and args.predLoss != "softmax":
+            raise ValueError(f"--softmaxNegs {args.softmaxNegs} needs --predLoss softmax: --predLoss {args.predLoss} "
+                             "draws its own negatives")
+        if args.softmaxNegs > args.item:
+            raise ValueError(f"--softmaxNegs {args.softmaxNegs} exceeds the {args.item} items of the catalogue")
         if args.predLoss == "softmax":
-            if args.fusion_rows == "batch":
+            if args.fusion_rows == "batch" and args.softmaxNegs == 0:
                 raise ValueError("--predLoss softmax does not combine with --fusion_rows batch: the loss reads every item "
                                  "row of the fused table, so there is no row subset to fuse")
             if args.latdim not in (32, 64, 128):

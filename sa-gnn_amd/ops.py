@@ -1640,6 +1640,102 @@ def softmax_loss_bwd(Q: torch.Tensor, I: torch.Tensor, target: torch.Tensor, lse
     return dQ, dI
 
 
+def sample_strata(n_items: int, n_cand: int, seed: int, step: int, device) -> torch.Tensor:
+    """The candidate list of --softmaxNegs (sagnn_sample_strata_i32): int32 [n_cand] on `device`, candidate j one
+    uniform draw from [floor(j n_items / n_cand), floor((j + 1) n_items / n_cand)) keyed by (seed, step, j): strictly
+    ascending and distinct, a pure function of its arguments, arange(n_items) when n_cand == n_items."""
+    n_items, n_cand, seed, step = int(n_items), int(n_cand), int(seed), int(step)
+    if n_items < 1 or n_items >= 2 ** 31:
+        raise ValueError(f"sample_strata: n_items = {n_items}, need 1 <= n_items < 2^31")
+    if n_cand < 0 or n_cand > n_items:
+        raise ValueError(f"sample_strata: n_cand = {n_cand}, need 0 <= n_cand <= n_items = {n_items}")
+    if not 0 <= seed < 2 ** 64 or not 0 <= step < 2 ** 32:
+        raise ValueError(f"sample_strata: seed = {seed}, step = {step}, need 0 <= seed < 2^64 and 0 <= step < 2^32")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise TypeError(f"sample_strata: expected a GPU device, got {device}")
+    cand = _out(n_cand, torch.int32, device)
+    check(_lib.load().sagnn_sample_strata_i32(n_items, n_cand, seed, step, cand.data_ptr(), _stream()))
+    return cand
+
+
+_softmax_cand_ws: dict = {}   # (device, n_queries, n_cand, d) -> workspace of sagnn_softmax_loss_cand_f32 and its backward
+
+
+def _softmax_cand_workspace(device: torch.device, B: int, n_cand: int, d: int):
+    key = (device, B, n_cand, d)
+    ws = _softmax_cand_ws.get(key)
+    if ws is None:
+        need = int(_lib.load().sagnn_softmax_loss_cand_workspace_bytes(B, n_cand, d))
+        if len(_softmax_cand_ws) >= 8:
+            _softmax_cand_ws.clear()
+        ws = _softmax_cand_ws[key] = (torch.empty(max(need, 256), dtype=torch.uint8, device=device), need)
+    return ws
+
+
+def _softmax_cand_args(Q, I, cand, target, inv_temp, scale, excl, excl_row):
+    """_softmax_args with the candidate list spliced in where the cand entries take it."""
+    if not isinstance(cand, torch.Tensor) or cand.dim() != 1:
+        raise ValueError("cand: expected int32 [n_cand]")
+    lead, (B, n_items, d) = _softmax_args(Q, I, target, inv_temp, scale, excl, excl_row)
+    n_cand = int(cand.numel())
+    if n_cand > n_items:
+        raise ValueError(f"cand: {n_cand} candidates for {n_items} items")
+    cand_p = _idx_ptr("cand", cand, torch.int32)
+    if cand.device != Q.device:
+        raise ValueError(f"cand on {cand.device}, Q on {Q.device}")
+    return lead[:7] + (cand_p, n_cand) + lead[7:], (B, n_items, d, n_cand)
+
+
+def softmax_loss_cand(Q: torch.Tensor, I: torch.Tensor, cand: torch.Tensor, target: torch.Tensor, inv_temp: float = 1.0,
+                      scale: float | None = None, excl=None, excl_row: torch.Tensor | None = None):
+    """softmax_loss over a candidate list (sagnn_softmax_loss_cand_f32): cand int32 [n_cand], strictly ascending ids of
+    [0, n_items) (not checked: they address rows of I); row b sums over the candidates outside its exclusion list and
+    other than target[b], plus target[b] itself, exactly once. n_cand == 0 is legal. The other arguments and the
+    returned (loss [1], lse [B], tscore [B]) are those of softmax_loss."""
+    lead, (B, n_items, d, n_cand) = _softmax_cand_args(Q, I, cand, target, inv_temp, scale, excl, excl_row)
+    dev = Q.device
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    lse, tscore = (torch.empty(max(B, 1), dtype=torch.float32, device=dev) for _ in range(2))
+    ws, need = _softmax_cand_workspace(dev, B, n_cand, d)
+    check(_lib.load().sagnn_softmax_loss_cand_f32(*lead, loss.data_ptr(), lse.data_ptr(), tscore.data_ptr(), ws.data_ptr(),
+                                                  need, _stream()))
+    return loss, lse[:B], tscore[:B]
+
+
+def softmax_loss_cand_bwd(Q: torch.Tensor, I: torch.Tensor, cand: torch.Tensor, target: torch.Tensor, lse: torch.Tensor,
+                          g: torch.Tensor, inv_temp: float = 1.0, scale: float | None = None, excl=None,
+                          excl_row: torch.Tensor | None = None):
+    """Gradients of softmax_loss_cand (sagnn_softmax_loss_cand_bwd_f32) given the forward's lse [B] and the upstream
+    scalar g (a 1-element float32 device tensor): returns (dQ [B, d], dIc [n_cand, d], dT [B, d]), every row written.
+    Row j of dIc is the candidates' share of dI[cand[j]], dT[b] the target's share of dI[target[b]]."""
+    lead, (B, n_items, d, n_cand) = _softmax_cand_args(Q, I, cand, target, inv_temp, scale, excl, excl_row)
+    dev = Q.device
+    for name, t, n in (("lse", lse, B), ("g", g, 1)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous() \
+                or t.numel() != n:
+            raise ValueError(f"{name}: need a contiguous float32 tensor of {n} elements on {dev}")
+    # one row at least behind every output: an empty tensor's data_ptr is 0 and the entry refuses NULL at any count
+    dQ = torch.empty((max(B, 1), d), dtype=torch.float32, device=dev)
+    dT = torch.empty((max(B, 1), d), dtype=torch.float32, device=dev)
+    dIc = torch.empty((max(n_cand, 1), d), dtype=torch.float32, device=dev)
+    ws, need = _softmax_cand_workspace(dev, B, n_cand, d)
+    lse_p = lse.data_ptr() if B else dQ.data_ptr()
+    check(_lib.load().sagnn_softmax_loss_cand_bwd_f32(*lead, lse_p, g.data_ptr(), dQ.data_ptr(), d, dIc.data_ptr(), d,
+                                                      dT.data_ptr(), d, ws.data_ptr(), need, _stream()))
+    return dQ[:B], dIc[:n_cand], dT[:B]
+
+
+def softmax_target_add(dI: torch.Tensor, dT: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    """dI[target[b]] += dT[b] in place for every row with a target in [0, n_items) (sagnn_softmax_target_add_f32): rows
+    that share a target are added in ascending b by one thread, so the result is the same in every run."""
+    B, d = int(dT.shape[0]), int(dT.shape[1])
+    check(_lib.load().sagnn_softmax_target_add_f32(dT.data_ptr() if B else dI.data_ptr(), _f32_rows("dT", dT, d) if B else d,
+                                                   _idx_ptr("target", target, torch.int32, B), B, int(dI.shape[0]), d,
+                                                   dI.data_ptr(), _f32_rows("dI", dI, d), _stream()))
+    return dI
+
+
 def candidate_rank(U: torch.Tensor, I: torch.Tensor, uids: torch.Tensor, cand: torch.Tensor, target: torch.Tensor,
                    S: torch.Tensor | None = None, A: torch.Tensor | None = None, leaky: float = 1.0,
                    want_scores: bool = False):

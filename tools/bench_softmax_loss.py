@@ -3,11 +3,15 @@ backward) at 512 queries, forward and forward + backward, beside the materialise
 cross_entropy(Q @ I.T / temp + mask) in the same process, and prints one JSON line per case. Needs a GPU.
 
   python tools/bench_softmax_loss.py [--iters 20] [--warmup 3] [--rounds 5] [--cases gowalla,movielens,synthetic]
+                                     [--cand 4096] [--d 64]
 
 Cases: Gowalla-shaped (52,619 items, d 32), MovieLens-shaped (3,706 items, d 128), synthetic (5 M items, d 64). Every
 user excludes 100 random items. The two forms alternate round by round; the figures are medians over the rounds. The
 torch form runs where its [512, n_items] logits, mask and softmax fit (not at 5 M items). The per-kernel split comes
 from sagnn_profile_read (kind 6: one record per entry) and, kernel by kernel, from a profiler's kernel trace.
+--cand N adds the candidate mode (--softmaxNegs: ops.softmax_loss_cand and its backward over N candidates drawn by
+ops.sample_strata, the backward followed by the assembly of the full-size dI as autograd.SoftmaxLossCandFn does it),
+alternated with the full form in the same rounds; cases with fewer than N items skip it.
 Rates count 2 * queries * items * d flops per product: one product forward, four backward (the scores twice, dQ, dI)."""
 import argparse
 import json
@@ -45,6 +49,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--cases", default=",".join(CASES))
     ap.add_argument("--temp", type=float, default=1.0)
+    ap.add_argument("--cand", type=int, default=0, help="also time the candidate mode over this many sampled candidates")
+    ap.add_argument("--d", type=int, default=0, help="override the cases' width (32, 64 or 128)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_softmax_loss: no GPU visible")
@@ -54,6 +60,7 @@ def main():
     inv_temp = 1.0 / a.temp
     for name in a.cases.split(","):
         n_items, d, B = CASES[name]
+        d = a.d or d
         I = torch.randn((n_items, d), generator=g, device=dev) * 0.3
         Q = torch.randn((B, d), generator=g, device=dev) * 0.3
         tgt = torch.randint(0, n_items, (B,), generator=g, device=dev, dtype=torch.int32)
@@ -70,6 +77,24 @@ def main():
             _, lse, _ = fwd()
             return ops.softmax_loss_bwd(Q, I, tgt, lse, one, inv_temp, None, excl)
 
+        n_cand = a.cand if 0 < a.cand <= n_items else 0
+        if n_cand:
+            cand = ops.sample_strata(n_items, n_cand, 0, 0, dev)
+
+            def c_fwd():
+                return ops.softmax_loss_cand(Q, I, cand, tgt, inv_temp, None, excl)
+
+            def c_fwd_bwd():
+                _, lse, _ = c_fwd()
+                dQ, dIc, dT = ops.softmax_loss_cand_bwd(Q, I, cand, tgt, lse, one, inv_temp, None, excl)
+                dI = torch.zeros_like(I)
+                dI.index_copy_(0, cand.long(), dIc)
+                return dQ, ops.softmax_target_add(dI, dT, tgt)
+
+            def c_kernels():     # the two entries alone, without the full-size dI
+                _, lse, _ = c_fwd()
+                return ops.softmax_loss_cand_bwd(Q, I, cand, tgt, lse, one, inv_temp, None, excl)
+
         torch_fits = B * n_items * 4 * 6 < (8 << 30)
         if torch_fits:
             mask = torch.zeros((B, n_items), device=dev)
@@ -85,10 +110,14 @@ def main():
                 Qt.grad = It.grad = None
                 torch.nn.functional.cross_entropy(Qt @ It.T * inv_temp + mask, tgt.long()).backward()
 
-        res = {k: [] for k in ("fwd", "fwd_bwd", "torch_fwd", "torch_fwd_bwd")}
+        res = {k: [] for k in ("fwd", "fwd_bwd", "torch_fwd", "torch_fwd_bwd", "cand_fwd", "cand_fwd_bwd", "cand_kernels")}
         for _ in range(a.rounds):          # alternated: both forms see the same machine state
             res["fwd"].append(timed(fwd, a.iters, a.warmup))
             res["fwd_bwd"].append(timed(fwd_bwd, a.iters, a.warmup))
+            if n_cand:
+                res["cand_fwd"].append(timed(c_fwd, a.iters, a.warmup))
+                res["cand_fwd_bwd"].append(timed(c_fwd_bwd, a.iters, a.warmup))
+                res["cand_kernels"].append(timed(c_kernels, a.iters, a.warmup))
             if torch_fits:
                 res["torch_fwd"].append(timed(t_fwd, a.iters, a.warmup))
                 res["torch_fwd_bwd"].append(timed(t_fwd_bwd, a.iters, a.warmup))
@@ -99,6 +128,13 @@ def main():
                "fwd_bwd_ms": round(med["fwd_bwd"], 4), "fwd_tflops": round(flop / med["fwd"] / 1e9, 2),
                "fwd_frac_of_155": round(flop / med["fwd"] / 1e9 / PEAK_TF, 4),
                "bwd_tflops": round(4 * flop / bwd_ms / 1e9, 2), "bwd_frac_of_155": round(4 * flop / bwd_ms / 1e9 / PEAK_TF, 4)}
+        if n_cand:
+            rec.update({"n_cand": n_cand, "cand_fwd_ms": round(med["cand_fwd"], 4),
+                        "cand_fwd_bwd_entries_ms": round(med["cand_kernels"], 4),
+                        "cand_fwd_bwd_with_full_dI_ms": round(med["cand_fwd_bwd"], 4),
+                        "cand_fwd_speedup": round(med["fwd"] / med["cand_fwd"], 2),
+                        "cand_fwd_bwd_speedup": round(med["fwd_bwd"] / med["cand_fwd_bwd"], 2),
+                        "cand_loss": float(c_fwd()[0])})
         if torch_fits:
             loss = float(fwd()[0])
             rec.update({"torch_fwd_ms": round(med["torch_fwd"], 4), "torch_fwd_bwd_ms": round(med["torch_fwd_bwd"], 4),

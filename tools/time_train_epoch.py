@@ -10,7 +10,10 @@ attention over every sequence item) and reports the device time of the sequence-
 (sagnn_profile_read, kind 5). --predLoss both alternates the head's two training losses (the sampled hinge loss / the
 full-catalogue softmax) and reports the device time of the softmax entries per step (kind 6). --seqPool both alternates
 the two poolings of the full head (the plain sum / additive attention; it implies --seqAtt full) on one model that holds
-the additive variables, every timed epoch from the initial parameters, and reports kind 5 per step for each."""
+the additive variables, every timed epoch from the initial parameters, and reports kind 5 per step for each.
+--softmaxNegs N runs the softmax loss over N sampled candidates (kind 7 instead of 6), which also lets --predLoss softmax
+combine with --fusion_rows batch; with --predLoss both it is a third loss beside the hinge loss and the full-catalogue
+softmax (which then runs under --fusion_rows all only). --sampler restricts the run to one sampler."""
 import argparse
 import ctypes
 import sys
@@ -57,6 +60,9 @@ def main():
                     help="the head's training loss(es) to time; both alternates them in one process")
     ap.add_argument("--seqPool", choices=("sum", "additive", "both"), default="sum",
                     help="the full head's pooling(s) to time (implies --seqAtt full); both alternates them in one process")
+    ap.add_argument("--softmaxNegs", type=int, default=0,
+                    help="candidates of --predLoss softmax (0 = the whole catalogue); > 0 allows --fusion_rows batch with it")
+    ap.add_argument("--sampler", choices=("host", "device", "both"), default="both", help="the sampler(s) to time")
     opt = ap.parse_args()
     if opt.seqPool != "sum" and opt.seqAtt == "sum":
         opt.seqAtt = "full"
@@ -67,27 +73,35 @@ def main():
         args.seqAtt, args.seqPool = "full", "additive"
     rec.prepareModel()
     args.seqAtt = "sum"
+    if opt.softmaxNegs < 0 or opt.softmaxNegs > args.item:
+        sys.exit(f"--softmaxNegs {opt.softmaxNegs}: need 0 <= N <= {args.item}")
     if opt.epoch_only:
         args.sampler = "device"
         args.fusion_rows = "batch" if opt.fusion_rows == "batch" else "all"
         args.seqAtt = "full" if opt.seqAtt == "full" else "sum"
         args.predLoss = "softmax" if opt.predLoss == "softmax" else "hinge"
+        args.softmaxNegs = opt.softmaxNegs if args.predLoss == "softmax" else 0
         args.seqPool = "additive" if opt.seqPool == "additive" else "sum"
         for _ in range(2):
             rec.trainEpoch()
         torch.cuda.synchronize()
         print(f"two device-sampler epochs done (--fusion_rows {args.fusion_rows}, --edge_keep {args.edgeKeepRate}, "
-              f"--seqAtt {args.seqAtt}, --seqPool {args.seqPool}, --predLoss {args.predLoss}); every parameter finite:",
+              f"--seqAtt {args.seqAtt}, --seqPool {args.seqPool}, --predLoss {args.predLoss}, --softmaxNegs {args.softmaxNegs}); "
+              "every parameter finite:",
               all(bool(torch.isfinite(p).all()) for p in NNs.params.values()))
         return
     modes = ("all", "batch") if opt.fusion_rows == "both" else (opt.fusion_rows,)
     atts = ("sum", "full") if opt.seqAtt == "both" else (opt.seqAtt,)
+    negs = f"softmax, softmaxNegs {opt.softmaxNegs}"       # the third loss: the softmax over sampled candidates
     losses = ("hinge", "softmax") if opt.predLoss == "both" else (opt.predLoss,)
+    if opt.softmaxNegs and "softmax" in losses:
+        losses = losses + (negs,) if opt.predLoss == "both" else (negs,)
     pools = ("sum", "additive") if opt.seqPool == "both" else (opt.seqPool,)
-    if "softmax" in losses and "batch" in modes:
-        sys.exit("--predLoss softmax does not combine with --fusion_rows batch")
+    if "softmax" in losses and modes == ("batch",):
+        sys.exit("--predLoss softmax does not combine with --fusion_rows batch without --softmaxNegs")
+    samplers = ("host", "device") if opt.sampler == "both" else (opt.sampler,)
     configs = [(sampler, mode, att, loss, pool) for loss in losses for att in atts for pool in pools for mode in modes
-               for sampler in ("host", "device") if att == "full" or pool == "sum"]
+               for sampler in samplers if (att == "full" or pool == "sum") and not (loss == "softmax" and mode == "batch")]
     label = lambda c: ", ".join([c[0]] + ([f"{c[1]} rows"] if len(modes) > 1 else []) +   # noqa: E731
                                 ([f"seqAtt {c[2]}"] if atts != ("sum",) else []) +
                                 ([f"seqPool {c[4]}"] if pools != ("sum",) else []) +
@@ -103,7 +117,9 @@ def main():
         # forms every timed epoch is therefore the first epoch of its own training (profiles/seq_att_epoch.txt holds a
         # parent-commit run that shows the default path's divergence). A run without --seqAtt both keeps training its
         # parameters as before, so its lines, not a `both` run's sum lines, are what compares with an earlier commit.
-        args.sampler, args.fusion_rows, args.seqAtt, args.predLoss, args.seqPool = c
+        args.sampler, args.fusion_rows, args.seqAtt, loss, args.seqPool = c
+        args.predLoss = "hinge" if loss == "hinge" else "softmax"
+        args.softmaxNegs = opt.softmaxNegs if loss == negs else 0
         if fresh and len(atts) * len(losses) * len(pools) > 1:
             with torch.no_grad():
                 for k, p in NNs.params.items():
@@ -191,22 +207,24 @@ def main():
               f"{int(sel.sum()) / steps:.0f} calls and {float(ms[:n.value][sel].sum()) / steps:.3f} ms of device time per step; "
               f"layer-norm entries (profile kind 3): {float(ms[:n.value][kind[:n.value] == 3].sum()) / steps:.3f} ms per step")
         print("every parameter finite after that epoch:", all(bool(torch.isfinite(p).all()) for p in NNs.params.values()))
-    if "softmax" in losses:   # device time of the softmax-loss entries (profile kind 6), one device-sampler epoch
+    # device time of the softmax-loss entries (kind 6; 7 over candidates), one device-sampler epoch per loss and mode
+    for loss, mode in [(lo, m) for lo in losses for m in modes if lo != "hinge" and not (lo == "softmax" and m == "batch")]:
         lib = ops._lib.load()
-        use(("device", modes[0], atts[0], "softmax", pools[0] if atts[0] == "full" else "sum"), fresh=True)
+        use(("device", mode, atts[0], loss, pools[0] if atts[0] == "full" else "sum"), fresh=True)
         cap = 4096 * steps
         lib.sagnn_profile_enable(cap)
         rec.trainEpoch()
         ms, kind, n = np.zeros(cap, np.float32), np.zeros(cap, np.int32), ctypes.c_int(0)
         ops.check(lib.sagnn_profile_read(ms.ctypes.data, kind.ctypes.data, None, None, cap, ctypes.byref(n)))
         lib.sagnn_profile_enable(0)
-        sel = np.flatnonzero(kind[:n.value] == 6)
-        print(f"[device, predLoss softmax] softmax-loss entries: {len(sel) / steps:.0f} calls per step; forward "
+        sel = np.flatnonzero(kind[:n.value] == (7 if loss == negs else 6))
+        print(f"[device, {mode} rows, predLoss {loss}] softmax-loss entries: {len(sel) / steps:.0f} calls per step; forward "
               f"{float(ms[sel[0::2]].sum()) / steps:.3f} ms and backward {float(ms[sel[1::2]].sum()) / steps:.3f} ms of device "
               f"time per step")
     print("every parameter finite after every timed epoch above:", finite)
     args.fusion_rows = "all"
     args.predLoss = "hinge"
+    args.softmaxNegs = 0
     args.sampler = "host"
     args.seqAtt = "sum"
     args.seqPool = "sum"
