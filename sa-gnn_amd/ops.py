@@ -1541,18 +1541,30 @@ def score_topk(Q: torch.Tensor, I: torch.Tensor, k: int, excl=None, target=None)
     return items, scores, rank
 
 
-_softmax_ws: dict = {}   # (device, n_queries, n_items, d) -> workspace of sagnn_softmax_loss_f32 and its backward
+_softmax_ws: dict = {}   # (cand, device, n_queries, positions, d) -> workspace of a softmax-loss entry and its backward
 
 
-def _softmax_workspace(device: torch.device, B: int, n_items: int, d: int):
-    key = (device, B, n_items, d)
+def _softmax_workspace(device: torch.device, B: int, n_pos: int, d: int, cand: bool = False):
+    """The cached workspace of sagnn_softmax_loss_f32 over n_pos = n_items positions, or with `cand` that of
+    sagnn_softmax_loss_cand_f32 over n_pos = n_cand, shared with the entry's backward, and its size in bytes."""
+    key = (cand, device, B, n_pos, d)
     ws = _softmax_ws.get(key)
     if ws is None:
-        need = int(_lib.load().sagnn_softmax_loss_workspace_bytes(B, n_items, d))
+        lib = _lib.load()
+        bytes_fn = lib.sagnn_softmax_loss_cand_workspace_bytes if cand else lib.sagnn_softmax_loss_workspace_bytes
+        need = int(bytes_fn(B, n_pos, d))
         if len(_softmax_ws) >= 8:      # a training run has one or two sizes (the last batch of an epoch is shorter)
             _softmax_ws.clear()
         ws = _softmax_ws[key] = (torch.empty(max(need, 256), dtype=torch.uint8, device=device), need)
     return ws
+
+
+def _lse_g_check(lse, g, B: int, dev):
+    """The backward wrappers' check of the forward's lse [B] and the upstream scalar g."""
+    for name, t, n in (("lse", lse, B), ("g", g, 1)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous() \
+                or t.numel() != n:
+            raise ValueError(f"{name}: need a contiguous float32 tensor of {n} elements on {dev}")
 
 
 def _softmax_args(Q, I, target, inv_temp, scale, excl, excl_row):
@@ -1627,10 +1639,7 @@ def softmax_loss_bwd(Q: torch.Tensor, I: torch.Tensor, target: torch.Tensor, lse
     1-element float32 device tensor): returns (dQ [B, d], dI [n_items, d]), every row written, the logits recomputed."""
     lead, (B, n_items, d) = _softmax_args(Q, I, target, inv_temp, scale, excl, excl_row)
     dev = Q.device
-    for name, t, n in (("lse", lse, B), ("g", g, 1)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous() \
-                or t.numel() != n:
-            raise ValueError(f"{name}: need a contiguous float32 tensor of {n} elements on {dev}")
+    _lse_g_check(lse, g, B, dev)
     dQ = torch.empty((max(B, 1), d), dtype=torch.float32, device=dev)[:B]
     dI = torch.empty((n_items, d), dtype=torch.float32, device=dev)
     ws, need = _softmax_workspace(dev, B, n_items, d)
@@ -1659,20 +1668,6 @@ def sample_strata(n_items: int, n_cand: int, seed: int, step: int, device) -> to
     return cand
 
 
-_softmax_cand_ws: dict = {}   # (device, n_queries, n_cand, d) -> workspace of sagnn_softmax_loss_cand_f32 and its backward
-
-
-def _softmax_cand_workspace(device: torch.device, B: int, n_cand: int, d: int):
-    key = (device, B, n_cand, d)
-    ws = _softmax_cand_ws.get(key)
-    if ws is None:
-        need = int(_lib.load().sagnn_softmax_loss_cand_workspace_bytes(B, n_cand, d))
-        if len(_softmax_cand_ws) >= 8:
-            _softmax_cand_ws.clear()
-        ws = _softmax_cand_ws[key] = (torch.empty(max(need, 256), dtype=torch.uint8, device=device), need)
-    return ws
-
-
 def _softmax_cand_args(Q, I, cand, target, inv_temp, scale, excl, excl_row):
     """_softmax_args with the candidate list spliced in where the cand entries take it."""
     if not isinstance(cand, torch.Tensor) or cand.dim() != 1:
@@ -1697,7 +1692,7 @@ def softmax_loss_cand(Q: torch.Tensor, I: torch.Tensor, cand: torch.Tensor, targ
     dev = Q.device
     loss = torch.empty(1, dtype=torch.float32, device=dev)
     lse, tscore = (torch.empty(max(B, 1), dtype=torch.float32, device=dev) for _ in range(2))
-    ws, need = _softmax_cand_workspace(dev, B, n_cand, d)
+    ws, need = _softmax_workspace(dev, B, n_cand, d, cand=True)
     check(_lib.load().sagnn_softmax_loss_cand_f32(*lead, loss.data_ptr(), lse.data_ptr(), tscore.data_ptr(), ws.data_ptr(),
                                                   need, _stream()))
     return loss, lse[:B], tscore[:B]
@@ -1711,15 +1706,12 @@ def softmax_loss_cand_bwd(Q: torch.Tensor, I: torch.Tensor, cand: torch.Tensor, 
     Row j of dIc is the candidates' share of dI[cand[j]], dT[b] the target's share of dI[target[b]]."""
     lead, (B, n_items, d, n_cand) = _softmax_cand_args(Q, I, cand, target, inv_temp, scale, excl, excl_row)
     dev = Q.device
-    for name, t, n in (("lse", lse, B), ("g", g, 1)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous() \
-                or t.numel() != n:
-            raise ValueError(f"{name}: need a contiguous float32 tensor of {n} elements on {dev}")
+    _lse_g_check(lse, g, B, dev)
     # one row at least behind every output: an empty tensor's data_ptr is 0 and the entry refuses NULL at any count
     dQ = torch.empty((max(B, 1), d), dtype=torch.float32, device=dev)
     dT = torch.empty((max(B, 1), d), dtype=torch.float32, device=dev)
     dIc = torch.empty((max(n_cand, 1), d), dtype=torch.float32, device=dev)
-    ws, need = _softmax_cand_workspace(dev, B, n_cand, d)
+    ws, need = _softmax_workspace(dev, B, n_cand, d, cand=True)
     lse_p = lse.data_ptr() if B else dQ.data_ptr()
     check(_lib.load().sagnn_softmax_loss_cand_bwd_f32(*lead, lse_p, g.data_ptr(), dQ.data_ptr(), d, dIc.data_ptr(), d,
                                                       dT.data_ptr(), d, ws.data_ptr(), need, _stream()))
