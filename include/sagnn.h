@@ -1008,6 +1008,57 @@ int sagnn_softmax_loss_cand_bwd_f32(const float* Q, int64_t ldq, const float* I,
                                     int64_t lddq, float* dIc, int64_t lddic, float* dT, int64_t lddt, void* workspace,
                                     size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Popularity-weighted candidates with the logQ correction (sampler.hip, softmax_loss.hip; --softmaxNegDist pop, not in
+ * the reference): the sampled softmax of word2vec and two-tower retrieval over the candidate entries above.
+ * sagnn_sample_strata_w_i32: a stratified draw of n_cand ids with replacement, item i drawn in proportion to its
+ *   integer weight w_i. cum int64 [n_items] (DEVICE) is the inclusive prefix sum of the weights, non-decreasing with
+ *   cum[0] >= 1; total = cum[n_items - 1] = W is the caller's HOST copy of its last entry (the entry reads nothing
+ *   back). The mass [0, W) is cut into n_cand strata [lo_j, lo_{j+1}), lo_j = j * (W / n_cand) + (j * (W % n_cand)) /
+ *   n_cand in 64-bit arithmetic (no 128-bit division; every product is below 2^62), and
+ *     r_j = lo_j + the high half of ((w0 << 32) | w1) * (lo_{j+1} - lo_j),
+ *     (w0, w1, ..) = philox4x32_10(counter = (j, 1, step, 0xFFFFFFFF), key = seed):
+ *   the strata stream of sagnn_sample_strata_i32 with counter word 1 set, so none of its blocks is reused.
+ *   cand[j] = #{ i : cum[i] <= r_j }, the item whose mass holds r_j. The list is non-decreasing, repeats are adjacent,
+ *   and it is a pure function of (cum, n_cand, seed, step, j). The run of id c is the positions [lb, ub) that hold it:
+ *   position lb is LIVE with bias[lb] = ln(m) - ln(e), m = ub - lb, e = n_cand * w_c / W the expected number of draws
+ *   of c (w_c = cum[c] - cum[c - 1]), the logs in double, rounded once to float, and exactly 0.0f when
+ *   m * W == n_cand * w_c as integers; the other positions of the run are DEAD, bias = -inf. Then
+ *     sum_{live j} exp(z(cand[j]) + bias[j]) = sum_{draws} exp(z(c)) / e_c,
+ *   whose expectation is the sum of exp(z(i)) over the whole catalogue, e_c within a relative n_cand / W of the exact
+ *   expected count. Equal weights and n_cand == n_items give 0, 1, .., n_items - 1 with every bias exactly 0.
+ *   Refused before any launch: n_items < 1 or >= 2^31, total < 1 or >= 2^62, n_cand < 0, >= 2^31 or > total, a NULL cum,
+ *   a NULL cand or bias with n_cand > 0. Two launches on `stream` (none when n_cand == 0), no allocation, no
+ *   synchronisation (capturable). A cum that breaks the contract still yields ids inside [0, n_items).
+ * sagnn_softmax_loss_candb_f32 / sagnn_softmax_loss_candb_bwd_f32: sagnn_softmax_loss_cand_f32 and its backward with a
+ *   per-position offset bias float [n_cand] (DEVICE) and a NON-DECREASING cand whose repeats are adjacent. Position j
+ *   is eligible for row b when cand[j] is (above) AND bias[j] > -inf, and its logit is z(b, cand[j]) + bias[j], one
+ *   fp32 add; the target's own term takes no offset and tscore is unchanged. With the first position of each run the
+ *   only one above -inf (what the draw writes) an id enters a row's sum once. The dIc rows of dead positions are exact
+ *   zeros. A zero bias on a strictly ascending list gives the bits of the entries without it. The same limits,
+ *   workspace (sagnn_softmax_loss_cand_workspace_bytes), launches and profile kind; a NULL bias with n_cand > 0 is
+ *   refused.
+ * sagnn_softmax_cand_scatter_f32: dI[cand[j]] = dIc[j] for every position j with bias[j] > -inf and cand[j] inside
+ *   [0, n_items): the live rows into a full-size dI. The live ids are distinct, so every row has one writer and the
+ *   result does not depend on the order of execution. Limits on d, n_items, n_cand, strides and alignment as above;
+ *   one launch on `stream` (none when n_cand == 0), not recorded by the profile.
+ * -------------------------------------------------------------------------------- */
+int sagnn_sample_strata_w_i32(const int64_t* cum, int64_t n_items, int64_t total, int64_t n_cand, uint64_t seed,
+                              uint32_t step, int32_t* cand, float* bias, void* stream);
+int sagnn_softmax_loss_candb_f32(const float* Q, int64_t ldq, const float* I, int64_t ldi, int64_t n_queries,
+                                 int64_t n_items, int d, const int32_t* cand, int64_t n_cand, const float* bias,
+                                 const int32_t* target, float inv_temp, float scale, const int64_t* excl_ptr,
+                                 const int32_t* excl_items, const int32_t* excl_row, int64_t n_lists, float* loss, float* lse,
+                                 float* tscore, void* workspace, size_t workspace_bytes, void* stream);
+int sagnn_softmax_loss_candb_bwd_f32(const float* Q, int64_t ldq, const float* I, int64_t ldi, int64_t n_queries,
+                                     int64_t n_items, int d, const int32_t* cand, int64_t n_cand, const float* bias,
+                                     const int32_t* target, float inv_temp, float scale, const int64_t* excl_ptr,
+                                     const int32_t* excl_items, const int32_t* excl_row, int64_t n_lists, const float* lse,
+                                     const float* g, float* dQ, int64_t lddq, float* dIc, int64_t lddic, float* dT,
+                                     int64_t lddt, void* workspace, size_t workspace_bytes, void* stream);
+int sagnn_softmax_cand_scatter_f32(const float* dIc, int64_t lddic, const int32_t* cand, const float* bias, int64_t n_cand,
+                                   int64_t n_items, int d, float* dI, int64_t lddi, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -115,6 +115,16 @@ _FLAGS = [
                             "catalogue and shared by the batch, minus the user's banned items, plus the slot's own "
                             "target; N <= the item count; lifts the need for --fusion_rows all; not part of the model). "
                             "Not in the reference, which has the sampled hinge loss only (model.py:241-246)"),
+    ("softmaxNegDist", str, "uniform", "how the --softmaxNegs candidates are drawn: uniform (one from each of N equal strata "
+                                       "of the catalogue; the reported loss is lower than the full-catalogue one by about "
+                                       "ln(items / N)) or pop (N draws with replacement in proportion to (train degree + 1)"
+                                       "^softmaxNegPow, each distinct item's logit corrected by ln(times drawn / expected "
+                                       "draws), the logQ correction of sampled softmax: the loss estimates the "
+                                       "full-catalogue one; needs --predLoss softmax and --softmaxNegs > 0; not part of "
+                                       "the model). Not in the reference", ("uniform", "pop")),
+    ("softmaxNegPow", float, 0.75, "exponent a of --softmaxNegDist pop, 0 <= a <= 1: 0 draws uniformly with replacement, 1 "
+                                   "in proportion to the degree, 0.75 is word2vec's; read only under pop (not in the "
+                                   "reference)"),
 ]
 
 

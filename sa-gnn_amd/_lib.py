@@ -236,6 +236,17 @@ SIGNATURES = {
                                                 c_int64, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_int64,
                                                 c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
                                                 c_void_p, c_size_t, c_void_p]),
+    "sagnn_sample_strata_w_i32": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_uint64, c_uint32, c_void_p, c_void_p,
+                                          c_void_p]),
+    "sagnn_softmax_loss_candb_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_int64,
+                                             c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_int64,
+                                             c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "sagnn_softmax_loss_candb_bwd_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p,
+                                                 c_int64, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p,
+                                                 c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                                 c_int64, c_void_p, c_size_t, c_void_p]),
+    "sagnn_softmax_cand_scatter_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p,
+                                               c_int64, c_void_p]),
 }
 
 

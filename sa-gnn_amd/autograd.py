@@ -558,26 +558,32 @@ class SoftmaxLossFn(torch.autograd.Function):
 class SoftmaxLossCandFn(torch.autograd.Function):
     """SoftmaxLossFn over a candidate list (ops.softmax_loss_cand, --softmaxNegs). The backward returns a full-size dI:
     zeros, the candidates' rows copied to rows `cand` (distinct ids), then every slot's target row added at its target
-    by ops.softmax_target_add, which orders the slots that share a target: bit-identical between runs."""
+    by ops.softmax_target_add, which orders the slots that share a target: bit-identical between runs.
+    With bias (--softmaxNegDist pop: the offsets of ops.sample_strata_weighted, whose list repeats ids) the rows of the
+    live positions alone are scattered (ops.softmax_cand_scatter): their ids are distinct, so no row has two writers."""
 
     @staticmethod
-    def forward(ctx, Q, I, cand, target, inv_temp, scale, excl, excl_row):
+    def forward(ctx, Q, I, cand, target, inv_temp, scale, excl, excl_row, bias=None):
         Q, I = Q.detach().contiguous(), I.detach().contiguous()
-        loss, lse, _ = ops.softmax_loss_cand(Q, I, cand, target, inv_temp, scale, excl, excl_row)
-        ctx.save_for_backward(Q, I, cand, target, lse)
+        loss, lse, _ = ops.softmax_loss_cand(Q, I, cand, target, inv_temp, scale, excl, excl_row, bias)
+        ctx.save_for_backward(Q, I, cand, target, lse, *(() if bias is None else (bias,)))
         ctx.args = (inv_temp, scale, excl, excl_row)
         return loss
 
     @staticmethod
     def backward(ctx, g):
-        Q, I, cand, target, lse = ctx.saved_tensors
+        Q, I, cand, target, lse, *bias = ctx.saved_tensors
+        bias = bias[0] if bias else None
         dQ, dIc, dT = ops.softmax_loss_cand_bwd(Q, I, cand, target, lse, g.detach().reshape(1).float().contiguous(),
-                                                *ctx.args)
+                                                *ctx.args, bias)
         dI = torch.zeros_like(I)
         if cand.numel():
-            dI.index_copy_(0, cand.long(), dIc)
+            if bias is None:
+                dI.index_copy_(0, cand.long(), dIc)
+            else:
+                ops.softmax_cand_scatter(dI, dIc, cand, bias)
         ops.softmax_target_add(dI, dT, target)
-        return dQ, dI, None, None, None, None, None, None
+        return dQ, dI, None, None, None, None, None, None, None
 
 
 class ProdLeakySumFn(torch.autograd.Function):

@@ -119,6 +119,61 @@ __global__ void sample_strata_kernel(int64_t n_items, int64_t n_cand, uint64_t s
   cand[j] = (int32_t)(lo + draw(seed, (uint32_t)j, 0, step, 0xFFFFFFFFu, (uint32_t)(up - lo)));
 }
 
+// The weighted draw (sagnn_sample_strata_w_i32) over the integer mass [0, W), W = cum[n_items - 1]: stratum j is
+// [lo_j, lo_{j+1}), lo_j = j * (W / n_cand) + j * (W % n_cand) / n_cand, every product below 2^62.
+__device__ __forceinline__ int64_t stratum_lo(int64_t j, int64_t q, int64_t rem, int64_t n_cand) {
+  return j * q + j * rem / n_cand;
+}
+
+// cand[j] = #{i : cum[i] <= r_j}, r_j = lo_j + one uniform draw on [0, lo_{j+1} - lo_j) from the strata stream's block
+// with counter word 1 set: one thread per candidate. r_j < W, so the count is below n_items for the cum of the
+// contract; it is clamped there, so that a cum which breaks the contract still yields row addresses inside the table.
+__global__ void sample_strata_w_kernel(const int64_t* __restrict__ cum, int64_t n_items, int64_t W, int64_t n_cand,
+                                       uint64_t seed, uint32_t step, int32_t* __restrict__ cand) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n_cand) return;
+  const int64_t q = W / n_cand, rem = W % n_cand;
+  const int64_t lo = stratum_lo(j, q, rem, n_cand);
+  const int64_t up = stratum_lo(j + 1, q, rem, n_cand);
+  const Word4 w = philox4x32_10(Word4{(uint32_t)j, 1u, step, 0xFFFFFFFFu}, (uint32_t)seed, (uint32_t)(seed >> 32));
+  const int64_t r = lo + (int64_t)__umul64hi(((uint64_t)w.x << 32) | w.y, (uint64_t)(up - lo));
+  int64_t a = 0, b = n_items;                                        // the first i with cum[i] > r
+  while (a < b) {
+    const int64_t mid = (a + b) >> 1;
+    if (cum[mid] <= r) a = mid + 1;
+    else b = mid;
+  }
+  cand[j] = (int32_t)min(a, n_items - 1);
+}
+
+// The runs of the drawn list and their offsets, one thread per position. The run of id c is [lb, ub): position lb is
+// live, bias = ln(m) - ln(n_cand * w_c / W) with m = ub - lb and w_c = cum[c] - cum[c - 1], the logs in double and one
+// rounding to float, exactly 0 when m * W == n_cand * w_c (compared as 128-bit products); the others are dead, -inf.
+__global__ void strata_w_bias_kernel(const int64_t* __restrict__ cum, int64_t W, int64_t n_cand,
+                                     const int32_t* __restrict__ cand, float* __restrict__ bias) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n_cand) return;
+  const int32_t c = cand[j];
+  if (j > 0 && cand[j - 1] == c) {
+    bias[j] = -INFINITY;
+    return;
+  }
+  int64_t a = j + 1, b = n_cand;                                     // ub: the first position past j with another id
+  while (a < b) {
+    const int64_t mid = (a + b) >> 1;
+    if (cand[mid] <= c) a = mid + 1;
+    else b = mid;
+  }
+  const uint64_t m = (uint64_t)(a - j);
+  const uint64_t wc = (uint64_t)(cum[c] - (c > 0 ? cum[c - 1] : 0));
+  const bool even = m * (uint64_t)W == (uint64_t)n_cand * wc && __umul64hi(m, (uint64_t)W) == __umul64hi((uint64_t)n_cand, wc);
+  if (wc == 0) {                                                     // an item without mass is never drawn under the contract
+    bias[j] = -INFINITY;
+    return;
+  }
+  bias[j] = even ? 0.f : (float)(log((double)m) - log((double)n_cand * (double)wc / (double)W));
+}
+
 __device__ __forceinline__ void add4(float4& a, const float4& b) {
   a.x += b.x;
   a.y += b.y;
@@ -337,6 +392,28 @@ extern "C" int sagnn_sample_strata_i32(int64_t n_items, int64_t n_cand, uint64_t
   if (blocks == 0) return SAGNN_OK;
   hipLaunchKernelGGL(sample_strata_kernel, dim3(blocks), dim3(kBlock), 0, static_cast<hipStream_t>(stream), n_items, n_cand,
                      seed, step, cand);
+  SAGNN_HIP_TRY(hipGetLastError());
+  return SAGNN_OK;
+}
+
+extern "C" int sagnn_sample_strata_w_i32(const int64_t* cum, int64_t n_items, int64_t total, int64_t n_cand, uint64_t seed,
+                                         uint32_t step, int32_t* cand, float* bias, void* stream) {
+  if (n_items < 1 || n_items >= ((int64_t)1 << 31))
+    return sagnn::fail(SAGNN_ERR_ARG, "sample_strata_w: n_items = %lld, need 1 <= n_items < 2^31", (long long)n_items);
+  if (total < 1 || total >= ((int64_t)1 << 62))
+    return sagnn::fail(SAGNN_ERR_ARG, "sample_strata_w: total = %lld, need 1 <= total < 2^62", (long long)total);
+  if (n_cand < 0 || n_cand >= ((int64_t)1 << 31) || n_cand > total)
+    return sagnn::fail(SAGNN_ERR_ARG, "sample_strata_w: n_cand = %lld, need 0 <= n_cand <= total = %lld and n_cand < 2^31",
+                       (long long)n_cand, (long long)total);
+  if (!cum) return sagnn::fail(SAGNN_ERR_NULL, "sample_strata_w: null cum");
+  if (n_cand > 0 && (!cand || !bias)) return sagnn::fail(SAGNN_ERR_NULL, "sample_strata_w: null cand or bias");
+  unsigned blocks = 0;
+  if (int rc = blocks_for(n_cand, &blocks)) return rc;
+  if (blocks == 0) return SAGNN_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(sample_strata_w_kernel, dim3(blocks), dim3(kBlock), 0, s, cum, n_items, total, n_cand, seed, step, cand);
+  SAGNN_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(strata_w_bias_kernel, dim3(blocks), dim3(kBlock), 0, s, cum, total, n_cand, cand, bias);
   SAGNN_HIP_TRY(hipGetLastError());
   return SAGNN_OK;
 }

@@ -15,6 +15,20 @@
 //      NI = 1 in di_kernel, and has dq_row_kernel where full mode has dq_merge_kernel.
 // A full instantiation loads no cand, shuffles no ids and uses no LDS.
 //
+// Candidate mode has one more compile-time property, the per-position logit offset (sagnn_softmax_loss_candb_f32 /
+// _bwd_f32, --softmaxNegDist pop), stated once in Offset<BIAS> below: position j adds bias[j] to its logit, and a
+// position with bias[j] = -inf is dead, never eligible. The list may then repeat ids (non-decreasing, repeats adjacent,
+// the first position of a run the only live one), and the id matching above stays right for these reasons alone:
+//   - the chunk kernels' walk passes every list entry <= the tile's last id, so a run that goes on into the next tile
+//     (or chunk: the next chunk's walk starts at its first id again) may be matched there or not: those positions are
+//     dead, and eligibility is all the match decides;
+//   - di_kernel finds a list entry's first occurrence among the span's ids: the run's live position when the run
+//     starts in the span, a dead one when it started before it;
+//   - a tile, span or chunk without a live position merges as the empty (-inf, 0): a dead position's -inf is never added
+//     to a score, its accumulator row gets g = 0 and its dIc row is written as zeros;
+//   - the target's own term (lse_row_kernel, dq_row_kernel) takes no offset.
+// An instantiation without the offset loads no bias and is the code it was.
+//
 // Forward pass 1 (lse_chunk_kernel): one wavefront per (kNT query tiles of 16 rows, chunk of positions), laid out as
 // retrieval.hip's topk_chunk_kernel: item rows are the A operand, the Q fragments stay in registers, acc[r] is the
 // score of position s0 + 4 * (lane >> 4) + r for query lane & 15. One item fragment feeds kNT query tiles. A lane keeps
@@ -212,6 +226,48 @@ struct Tile<true> {
   __device__ __forceinline__ unsigned excl_bits(const Problem& p, Walk& w) const { return walk_bits(p, w, ids, last); }
 };
 
+// Candidate mode's logit offset, the LAST argument of the three kernels that take it: empty without the offset, so
+// that those instantiations keep their arguments and their code. at(): the offset of one position, -inf past the list
+// (never read out of bounds). live(): the position may be eligible. add(): x + the offset, for x = a logit or a logit
+// minus a maximum / the row's lse: written with the offset last, so that a zero offset gives the bits of the
+// instantiation without one whichever way the compiler contracts the multiply by inv_temp into the subtraction.
+template <bool BIAS>
+struct Offset;
+
+template <>
+struct Offset<false> {
+  __device__ __forceinline__ float at(const Problem&, int64_t) const { return 0.f; }
+  static __device__ __forceinline__ bool live(float) { return true; }
+  static __device__ __forceinline__ float add(float x, float) { return x; }
+};
+
+template <>
+struct Offset<true> {
+  const float* bias;                                     // one per position
+  __device__ __forceinline__ float at(const Problem& p, int64_t pos) const { return pos < p.n_cand ? bias[pos] : -INFINITY; }
+  static __device__ __forceinline__ bool live(float b) { return b > -INFINITY; }
+  static __device__ __forceinline__ float add(float x, float b) { return x + b; }
+};
+
+// The offsets of a chunk kernel's tile, as Tile<true> holds its ids: lane q loads position s0 + q's, b[r] is that of
+// position s0 + 4g + r. Empty without the offset.
+template <bool BIAS>
+struct TileOffset {
+  __device__ __forceinline__ TileOffset(const Problem&, const Offset<BIAS>&, int64_t, int, int) {}
+  __device__ __forceinline__ float operator[](int) const { return 0.f; }
+};
+
+template <>
+struct TileOffset<true> {
+  float b[4];
+  __device__ __forceinline__ TileOffset(const Problem& p, const Offset<true>& ob, int64_t s0, int q, int g) {
+    const float mine = ob.at(p, s0 + q);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) b[r] = __shfl(mine, 4 * g + r);
+  }
+  __device__ __forceinline__ float operator[](int r) const { return b[r]; }
+};
+
 // acc[r] = <row 4 * (lane >> 4) + r of the A side, row lane & 15 of the B side>; a[t] / b[t] are the lane's float4 of
 // its A / B row at columns 16t + 4 * (lane >> 4). A fixed fmaf chain over the columns.
 template <int D>
@@ -256,37 +312,44 @@ __device__ __forceinline__ void query_init(const Problem& p, int64_t b, int64_t 
 }
 
 // One tile into a lane's running (m, s): the tile's maximum first, then one exp per eligible element and one for the
-// rescale. Nothing eligible so far and nothing here leaves (-inf, 0) alone.
-__device__ __forceinline__ void lse_update(float& m, float& s, const float (&z)[4], const bool (&e)[4]) {
+// rescale. Nothing eligible so far and nothing here leaves (-inf, 0) alone. With the offset the logit of element r is
+// z[r] + off[r]; an eligible element's offset is finite.
+template <bool BIAS, class Off>
+__device__ __forceinline__ void lse_update(float& m, float& s, const float (&z)[4], const bool (&e)[4], const Off& off) {
+  typedef Offset<BIAS> B;
   float mx = m;
 #pragma unroll
   for (int r = 0; r < 4; ++r)
-    if (e[r]) mx = fmaxf(mx, z[r]);
+    if (e[r]) mx = fmaxf(mx, B::add(z[r], off[r]));
   if (mx > -INFINITY) {
     float sum = s * __expf(m - mx);
 #pragma unroll
     for (int r = 0; r < 4; ++r)
-      if (e[r]) sum += __expf(z[r] - mx);
+      if (e[r]) sum += __expf(B::add(z[r] - mx, off[r]));
     s = sum;
     m = mx;
   }
 }
 
-// g(b, i) of one accumulator element: z = acc * inv_temp
-__device__ __forceinline__ float grad_elem(float acc, float inv_temp, float lse, float coef, bool elig, bool is_target) {
-  const float pr = elig ? __expf(acc * inv_temp - lse) : 0.f;
+// g(b, i) of one accumulator element: z = acc * inv_temp (+ off with the offset, finite where elig)
+template <bool BIAS = false>
+__device__ __forceinline__ float grad_elem(float acc, float inv_temp, float lse, float coef, bool elig, bool is_target,
+                                           float off = 0.f) {
+  const float pr = elig ? __expf(Offset<BIAS>::add(acc * inv_temp - lse, off)) : 0.f;
   return coef * (pr - (is_target ? 1.f : 0.f));
 }
 
 // grad_elem under the mode's rules. Full mode writes an exact zero for a query without a target; candidate mode's
 // coef * 0 there keeps what its kernels always wrote.
-template <bool CAND>
+// `off`: the position's offset (BIAS only), which also decides whether it is live.
+template <bool CAND, bool BIAS>
 __device__ __forceinline__ float grad_at(float acc, const Problem& p, float lse, float coef, bool ok, bool inside, bool ex,
-                                         typename Mode<CAND>::id_t id, int ti) {
+                                         typename Mode<CAND>::id_t id, int ti, float off) {
   typedef Mode<CAND> M;
   if constexpr (!CAND)
     if (!ok) return 0.f;
-  return grad_elem(acc, p.inv_temp, lse, coef, M::eligible(ok, inside, ex, id, ti), M::is_target(ok, id, ti));
+  return grad_elem<BIAS>(acc, p.inv_temp, lse, coef, M::eligible(ok, inside && Offset<BIAS>::live(off), ex, id, ti),
+                         M::is_target(ok, id, ti), off);
 }
 
 // out[n][f] += row x G[n][r] over the features 16f .. 16f + 15: one MFMA of the second product per (f, n), which
@@ -310,8 +373,9 @@ __device__ __forceinline__ void store_row(float* __restrict__ out, const f32x4 (
     *reinterpret_cast<float4*>(out + 16 * f) = make_float4(acc[f][0], acc[f][1], acc[f][2], acc[f][3]);
 }
 
-template <int D, bool CAND>
-__global__ __launch_bounds__(64) void lse_chunk_kernel(Problem p, float2* __restrict__ part) {
+template <int D, bool CAND, bool BIAS>
+__global__ __launch_bounds__(64) void lse_chunk_kernel(Problem p, float2* __restrict__ part, Offset<BIAS> ob) {
+  static_assert(CAND || !BIAS, "the offset is a property of candidate mode");
   typedef Mode<CAND> M;
   const int lane = threadIdx.x;
   const int q = lane & 15, g = lane >> 4;
@@ -327,6 +391,7 @@ __global__ __launch_bounds__(64) void lse_chunk_kernel(Problem p, float2* __rest
   }
   for (int64_t s0 = c0; s0 < c1; s0 += 16) {
     const Tile<CAND> t(p, s0, q, g);
+    const TileOffset<BIAS> off(p, ob, s0, q, g);
     float4 a[D / 16];
     load_frag<D>(p.I + M::row(p, t.lane_id) * p.ldi, g, a);
 #pragma unroll
@@ -337,10 +402,10 @@ __global__ __launch_bounds__(64) void lse_chunk_kernel(Problem p, float2* __rest
       bool e[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        e[r] = M::eligible(ql[u].ok, s0 + 4 * g + r < c1, (xm >> r) & 1, t.id(r), ql[u].ti);
+        e[r] = M::eligible(ql[u].ok, s0 + 4 * g + r < c1 && Offset<BIAS>::live(off[r]), (xm >> r) & 1, t.id(r), ql[u].ti);
         z[r] = acc[r] * p.inv_temp;
       }
-      lse_update(m[u], s[u], z, e);
+      lse_update<BIAS>(m[u], s[u], z, e, off);
     }
   }
 #pragma unroll
@@ -395,9 +460,9 @@ __global__ __launch_bounds__(256) void loss_sum_kernel(const float* __restrict__
   if (threadIdx.x == 0) loss[0] = scale * sh[0];
 }
 
-template <int D, bool CAND>
+template <int D, bool CAND, bool BIAS>
 __global__ __launch_bounds__(64) void dq_chunk_kernel(Problem p, const float* __restrict__ lse, const float* __restrict__ gup,
-                                                      float* __restrict__ part) {
+                                                      float* __restrict__ part, Offset<BIAS> ob) {
   typedef Mode<CAND> M;
   const int lane = threadIdx.x;
   const int q = lane & 15, g = lane >> 4;
@@ -416,6 +481,7 @@ __global__ __launch_bounds__(64) void dq_chunk_kernel(Problem p, const float* __
   }
   for (int64_t s0 = c0; s0 < c1; s0 += 16) {
     const Tile<CAND> t(p, s0, q, g);
+    const TileOffset<BIAS> off(p, ob, s0, q, g);
     float4 a[D / 16];
     load_frag<D>(p.I + M::row(p, t.lane_id) * p.ldi, g, a);
     f32x4 G[kNT];
@@ -425,7 +491,8 @@ __global__ __launch_bounds__(64) void dq_chunk_kernel(Problem p, const float* __
       const unsigned xm = t.excl_bits(p, ql[u].w);
 #pragma unroll
       for (int r = 0; r < 4; ++r)
-        G[u][r] = grad_at<CAND>(acc[r], p, row_lse[u], coef, ql[u].ok, s0 + 4 * g + r < c1, (xm >> r) & 1, t.id(r), ql[u].ti);
+        G[u][r] = grad_at<CAND, BIAS>(acc[r], p, row_lse[u], coef, ql[u].ok, s0 + 4 * g + r < c1, (xm >> r) & 1, t.id(r),
+                                      ql[u].ti, off[r]);
     }
     // dQ^T += I^T G: MFMA r contracts over the positions s0 + 4g + r
 #pragma unroll
@@ -490,9 +557,9 @@ __global__ __launch_bounds__(64) void dq_row_kernel(Problem p, const float* __re
 // One wavefront per span of 16 * NI positions from i0; row j of dI belongs to position j. Lane l finds the exclusions
 // of query qg + l inside the span as a bit mask over its positions: in full mode by the entries' offsets from i0, in
 // candidate mode by a lower bound of each entry among the span's ids, which sit in LDS for that.
-template <int D, int NI, bool CAND>
+template <int D, int NI, bool CAND, bool BIAS>
 __global__ __launch_bounds__(64) void di_kernel(Problem p, const float* __restrict__ lse, const float* __restrict__ gup,
-                                                float* __restrict__ dI, int64_t lddi) {
+                                                float* __restrict__ dI, int64_t lddi, Offset<BIAS> ob) {
   typedef Mode<CAND> M;
   __shared__ int sid[16 * NI];                           // touched, and so allocated, in candidate mode only
   const int lane = threadIdx.x;
@@ -515,8 +582,10 @@ __global__ __launch_bounds__(64) void di_kernel(Problem p, const float* __restri
   }
   float4 ib[NI][D / 16];                                 // item rows as the B side of the scores
   f32x4 di[NI][D / 16];
+  [[maybe_unused]] float offv[NI];                       // the offset of position i0 + 16v + c, -inf past the span
 #pragma unroll
   for (int v = 0; v < NI; ++v) {
+    offv[v] = ob.at(p, i0 + 16 * v + c);
     load_frag<D>(p.I + M::row(p, idv[v]) * p.ldi, g, ib[v]);
 #pragma unroll
     for (int f = 0; f < D / 16; ++f) di[v][f] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -586,7 +655,7 @@ __global__ __launch_bounds__(64) void di_kernel(Problem p, const float* __restri
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const bool ex = ((off < 32 ? xl[r] >> off : xh[r] >> (off - 32)) & 1) != 0;
-          G[v][r] = grad_at<CAND>(acc[r], p, row_lse[r], coef, ti[r] >= 0 && inside, true, ex, idv[v], ti[r]);
+          G[v][r] = grad_at<CAND, BIAS>(acc[r], p, row_lse[r], coef, ti[r] >= 0 && inside, true, ex, idv[v], ti[r], offv[v]);
         }
       }
       // dI^T += Q^T G: MFMA r contracts over queries qb + 4g + r
@@ -635,6 +704,23 @@ __global__ __launch_bounds__(64) void target_add_kernel(const float* __restrict_
   if (col) *reinterpret_cast<float4*>(out) = acc;
 }
 
+// The dIc rows of the live positions into a full-size dI (sagnn_softmax_cand_scatter_f32): dI[cand[j]] = dIc[j] where
+// bias[j] > -inf. One thread per (position, float4 column); the live positions' ids are distinct, so a dI row has one
+// writer at most and the result does not depend on the order of the threads.
+__global__ __launch_bounds__(256) void cand_scatter_kernel(const float* __restrict__ dIc, int64_t lddic,
+                                                           const int32_t* __restrict__ cand, const float* __restrict__ bias,
+                                                           int64_t n_cand, int64_t n_items, int d, float* __restrict__ dI,
+                                                           int64_t lddi) {
+  const int per_row = d / 4;
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= n_cand * per_row) return;
+  const int64_t j = e / per_row;
+  const int c = (int)(e - j * per_row);
+  const int64_t id = cand[j];
+  if (!(bias[j] > -INFINITY) || id < 0 || id >= n_items) return;
+  *reinterpret_cast<float4*>(dI + id * lddi + 4 * c) = *reinterpret_cast<const float4*>(dIc + j * lddic + 4 * c);
+}
+
 // Workspace: forward = (max, sum) per (query, chunk) then one loss term per query; backward = dQ partials per chunk.
 struct Layout {
   int64_t chunk, n_chunks;
@@ -655,14 +741,15 @@ inline Layout layout(int64_t n_queries, int64_t n_items, int d) {
   return L;
 }
 
-template <int D, bool CAND>
-int launch_fwd(const Problem& p, const Layout& L, float* loss, float* lse, float* tscore, void* workspace, hipStream_t s) {
+template <int D, bool CAND, bool BIAS>
+int launch_fwd(const Problem& p, const Offset<BIAS>& ob, const Layout& L, float* loss, float* lse, float* tscore,
+               void* workspace, hipStream_t s) {
   float2* part = reinterpret_cast<float2*>(workspace);
   float* terms = reinterpret_cast<float*>(static_cast<unsigned char*>(workspace) + L.terms_off);
   if (p.n_queries > 0) {
     if (L.n_chunks > 0) {                                // an empty candidate list has no chunk
       const dim3 grid1((unsigned)((p.n_queries + 16 * kNT - 1) / (16 * kNT)), (unsigned)L.n_chunks);
-      hipLaunchKernelGGL((lse_chunk_kernel<D, CAND>), grid1, dim3(64), 0, s, p, part);
+      hipLaunchKernelGGL((lse_chunk_kernel<D, CAND, BIAS>), grid1, dim3(64), 0, s, p, part, ob);
       SAGNN_HIP_TRY(hipGetLastError());
     }
     hipLaunchKernelGGL((lse_row_kernel<D, CAND>), dim3((unsigned)p.n_queries), dim3(64), 0, s, p, part, lse, tscore, terms);
@@ -674,15 +761,15 @@ int launch_fwd(const Problem& p, const Layout& L, float* loss, float* lse, float
 }
 
 // dI has one row per position; dT is candidate mode's
-template <int D, bool CAND>
-int launch_bwd(const Problem& p, const Layout& L, const float* lse, const float* g, float* dQ, int64_t lddq, float* dI,
-               int64_t lddi, float* dT, int64_t lddt, void* workspace, hipStream_t s) {
+template <int D, bool CAND, bool BIAS>
+int launch_bwd(const Problem& p, const Offset<BIAS>& ob, const Layout& L, const float* lse, const float* g, float* dQ,
+               int64_t lddq, float* dI, int64_t lddi, float* dT, int64_t lddt, void* workspace, hipStream_t s) {
   constexpr int NI = D == 128 ? 2 : 4;
   float* part = reinterpret_cast<float*>(workspace);
   if (p.n_queries > 0) {
     if (L.n_chunks > 0) {
       const dim3 grid1((unsigned)((p.n_queries + 16 * kNT - 1) / (16 * kNT)), (unsigned)L.n_chunks);
-      hipLaunchKernelGGL((dq_chunk_kernel<D, CAND>), grid1, dim3(64), 0, s, p, lse, g, part);
+      hipLaunchKernelGGL((dq_chunk_kernel<D, CAND, BIAS>), grid1, dim3(64), 0, s, p, lse, g, part, ob);
       SAGNN_HIP_TRY(hipGetLastError());
     }
     if constexpr (CAND) {
@@ -701,11 +788,11 @@ int launch_bwd(const Problem& p, const Layout& L, const float* lse, const float*
       // a short list at 16 positions per wavefront, so that it still fills the part; an item's sum over the queries has
       // the same order in both forms
       if (spans < kSmallSpans)
-        hipLaunchKernelGGL((di_kernel<D, 1, true>), dim3((unsigned)((n + 15) / 16)), dim3(64), 0, s, p, lse, g, dI, lddi);
+        hipLaunchKernelGGL((di_kernel<D, 1, true, BIAS>), dim3((unsigned)((n + 15) / 16)), dim3(64), 0, s, p, lse, g, dI, lddi, ob);
       else
-        hipLaunchKernelGGL((di_kernel<D, NI, true>), dim3((unsigned)spans), dim3(64), 0, s, p, lse, g, dI, lddi);
+        hipLaunchKernelGGL((di_kernel<D, NI, true, BIAS>), dim3((unsigned)spans), dim3(64), 0, s, p, lse, g, dI, lddi, ob);
     } else {
-      hipLaunchKernelGGL((di_kernel<D, NI, false>), dim3((unsigned)spans), dim3(64), 0, s, p, lse, g, dI, lddi);
+      hipLaunchKernelGGL((di_kernel<D, NI, false, false>), dim3((unsigned)spans), dim3(64), 0, s, p, lse, g, dI, lddi, ob);
     }
     SAGNN_HIP_TRY(hipGetLastError());
   }
@@ -749,11 +836,12 @@ int check_common(const char* who, const float* Q, int64_t ldq, const float* I, i
   return SAGNN_OK;
 }
 
-int check_cand(const char* who, int64_t n_items, const int32_t* cand, int64_t n_cand) {
+int check_cand(const char* who, int64_t n_items, const int32_t* cand, int64_t n_cand, bool with_bias, const float* bias) {
   if (n_cand < 0 || n_cand > n_items)
     return sagnn::fail(SAGNN_ERR_ARG, "%s: n_cand = %lld, need 0 <= n_cand <= n_items = %lld", who, (long long)n_cand,
                        (long long)n_items);
   if (n_cand > 0 && !cand) return sagnn::fail(SAGNN_ERR_NULL, "%s: null cand", who);
+  if (with_bias && n_cand > 0 && !bias) return sagnn::fail(SAGNN_ERR_NULL, "%s: null bias", who);
   return SAGNN_OK;
 }
 
@@ -786,23 +874,71 @@ int check_outputs(const char* who, int d, int n, float* const* out, const int64_
 }
 
 // What the entries of one mode share up to the launch: the checks in the order of their messages, the workspace, the
-// problem. `outputs` checks the entry's own pointers between the two; full mode passes cand = nullptr, n_cand = 0.
-template <bool CAND, class Outputs>
+// problem. `outputs` checks the entry's own pointers between the two; full mode passes cand = nullptr, n_cand = 0, and
+// only an entry with the offset (BIAS) passes a bias.
+template <bool CAND, bool BIAS, class Outputs>
 int prepare(const char* who, const float* Q, int64_t ldq, const float* I, int64_t ldi, int64_t n_queries, int64_t n_items,
-            int d, const int32_t* cand, int64_t n_cand, const int32_t* target, float inv_temp, float scale,
+            int d, const int32_t* cand, int64_t n_cand, const float* bias, const int32_t* target, float inv_temp, float scale,
             const int64_t* excl_ptr, const int32_t* excl_items, const int32_t* excl_row, int64_t n_lists, Outputs outputs,
             const void* workspace, size_t workspace_bytes, Layout& L, Problem& p) {
   if (int rc = check_common(who, Q, ldq, I, ldi, n_queries, n_items, d, target, inv_temp, scale, excl_ptr, excl_items,
                             excl_row, n_lists))
     return rc;
   if constexpr (CAND)
-    if (int rc = check_cand(who, n_items, cand, n_cand)) return rc;
+    if (int rc = check_cand(who, n_items, cand, n_cand, BIAS, bias)) return rc;
   if (int rc = outputs()) return rc;
   L = layout(n_queries, CAND ? n_cand : n_items, d);
   if (int rc = check_workspace(who, L.bytes, workspace, workspace_bytes)) return rc;
   p = Problem{Q, ldq, I, ldi, n_queries, n_items, target, inv_temp, scale, excl_ptr, excl_items, excl_row, n_lists,
               L.chunk, L.n_chunks, cand, n_cand};
   return SAGNN_OK;
+}
+
+// The candidate entries, with and without the offset: the extern "C" pairs below differ in `who`, BIAS and bias only.
+template <bool BIAS>
+int cand_fwd(const char* who, const float* Q, int64_t ldq, const float* I, int64_t ldi, int64_t n_queries, int64_t n_items,
+             int d, const int32_t* cand, int64_t n_cand, const float* bias, const int32_t* target, float inv_temp,
+             float scale, const int64_t* excl_ptr, const int32_t* excl_items, const int32_t* excl_row, int64_t n_lists,
+             float* loss, float* lse, float* tscore, void* workspace, size_t workspace_bytes, void* stream) {
+  Layout L;
+  Problem p;
+  const auto outputs = [&] { return check_fwd_outputs(who, loss, lse, tscore); };
+  if (int rc = prepare<true, BIAS>(who, Q, ldq, I, ldi, n_queries, n_items, d, cand, n_cand, bias, target, inv_temp, scale,
+                                   excl_ptr, excl_items, excl_row, n_lists, outputs, workspace, workspace_bytes, L, p))
+    return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  sagnn::ProfileScope prof(sagnn::kProfSoftmaxLossCand, s, n_queries, n_cand);
+  Offset<BIAS> ob;
+  if constexpr (BIAS) ob.bias = bias;
+  return dispatch_d(d, [&](auto D) {
+    return launch_fwd<decltype(D)::value, true, BIAS>(p, ob, L, loss, lse, tscore, workspace, s);
+  });
+}
+
+template <bool BIAS>
+int cand_bwd(const char* who, const float* Q, int64_t ldq, const float* I, int64_t ldi, int64_t n_queries, int64_t n_items,
+             int d, const int32_t* cand, int64_t n_cand, const float* bias, const int32_t* target, float inv_temp,
+             float scale, const int64_t* excl_ptr, const int32_t* excl_items, const int32_t* excl_row, int64_t n_lists,
+             const float* lse, const float* g, float* dQ, int64_t lddq, float* dIc, int64_t lddic, float* dT, int64_t lddt,
+             void* workspace, size_t workspace_bytes, void* stream) {
+  Layout L;
+  Problem p;
+  const auto outputs = [&] {
+    if (!lse || !g) return sagnn::fail(SAGNN_ERR_NULL, "%s: null lse or g", who);
+    float* const out[] = {dQ, dIc, dT};
+    const int64_t ld[] = {lddq, lddic, lddt};
+    return check_outputs(who, d, 3, out, ld, "dQ, dIc or dT", "lddq / lddic / lddt", "dQ, dIc and dT");
+  };
+  if (int rc = prepare<true, BIAS>(who, Q, ldq, I, ldi, n_queries, n_items, d, cand, n_cand, bias, target, inv_temp, scale,
+                                   excl_ptr, excl_items, excl_row, n_lists, outputs, workspace, workspace_bytes, L, p))
+    return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  sagnn::ProfileScope prof(sagnn::kProfSoftmaxLossCand, s, n_queries, n_cand);
+  Offset<BIAS> ob;
+  if constexpr (BIAS) ob.bias = bias;
+  return dispatch_d(d, [&](auto D) {
+    return launch_bwd<decltype(D)::value, true, BIAS>(p, ob, L, lse, g, dQ, lddq, dIc, lddic, dT, lddt, workspace, s);
+  });
 }
 
 }  // namespace
@@ -826,12 +962,12 @@ extern "C" int sagnn_softmax_loss_f32(const float* Q, int64_t ldq, const float* 
   Layout L;
   Problem p;
   const auto outputs = [&] { return check_fwd_outputs(who, loss, lse, tscore); };
-  if (int rc = prepare<false>(who, Q, ldq, I, ldi, n_queries, n_items, d, nullptr, 0, target, inv_temp, scale, excl_ptr,
+  if (int rc = prepare<false, false>(who, Q, ldq, I, ldi, n_queries, n_items, d, nullptr, 0, nullptr, target, inv_temp, scale, excl_ptr,
                               excl_items, excl_row, n_lists, outputs, workspace, workspace_bytes, L, p))
     return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   sagnn::ProfileScope prof(sagnn::kProfSoftmaxLoss, s, n_queries, n_items);
-  return dispatch_d(d, [&](auto D) { return launch_fwd<decltype(D)::value, false>(p, L, loss, lse, tscore, workspace, s); });
+  return dispatch_d(d, [&](auto D) { return launch_fwd<decltype(D)::value, false, false>(p, Offset<false>{}, L, loss, lse, tscore, workspace, s); });
 }
 
 extern "C" int sagnn_softmax_loss_bwd_f32(const float* Q, int64_t ldq, const float* I, int64_t ldi, int64_t n_queries,
@@ -848,13 +984,13 @@ extern "C" int sagnn_softmax_loss_bwd_f32(const float* Q, int64_t ldq, const flo
     const int64_t ld[] = {lddq, lddi};
     return check_outputs(who, d, 2, out, ld, "dQ or dI", "lddq / lddi", "dQ and dI");
   };
-  if (int rc = prepare<false>(who, Q, ldq, I, ldi, n_queries, n_items, d, nullptr, 0, target, inv_temp, scale, excl_ptr,
+  if (int rc = prepare<false, false>(who, Q, ldq, I, ldi, n_queries, n_items, d, nullptr, 0, nullptr, target, inv_temp, scale, excl_ptr,
                               excl_items, excl_row, n_lists, outputs, workspace, workspace_bytes, L, p))
     return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   sagnn::ProfileScope prof(sagnn::kProfSoftmaxLoss, s, n_queries, n_items);
   return dispatch_d(d, [&](auto D) {
-    return launch_bwd<decltype(D)::value, false>(p, L, lse, g, dQ, lddq, dI, lddi, nullptr, 0, workspace, s);
+    return launch_bwd<decltype(D)::value, false, false>(p, Offset<false>{}, L, lse, g, dQ, lddq, dI, lddi, nullptr, 0, workspace, s);
   });
 }
 
@@ -863,16 +999,8 @@ extern "C" int sagnn_softmax_loss_cand_f32(const float* Q, int64_t ldq, const fl
                                            const int32_t* target, float inv_temp, float scale, const int64_t* excl_ptr,
                                            const int32_t* excl_items, const int32_t* excl_row, int64_t n_lists, float* loss,
                                            float* lse, float* tscore, void* workspace, size_t workspace_bytes, void* stream) {
-  const char* who = "softmax_loss_cand";
-  Layout L;
-  Problem p;
-  const auto outputs = [&] { return check_fwd_outputs(who, loss, lse, tscore); };
-  if (int rc = prepare<true>(who, Q, ldq, I, ldi, n_queries, n_items, d, cand, n_cand, target, inv_temp, scale, excl_ptr,
-                             excl_items, excl_row, n_lists, outputs, workspace, workspace_bytes, L, p))
-    return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  sagnn::ProfileScope prof(sagnn::kProfSoftmaxLossCand, s, n_queries, n_cand);
-  return dispatch_d(d, [&](auto D) { return launch_fwd<decltype(D)::value, true>(p, L, loss, lse, tscore, workspace, s); });
+  return cand_fwd<false>("softmax_loss_cand", Q, ldq, I, ldi, n_queries, n_items, d, cand, n_cand, nullptr, target, inv_temp,
+                         scale, excl_ptr, excl_items, excl_row, n_lists, loss, lse, tscore, workspace, workspace_bytes, stream);
 }
 
 extern "C" int sagnn_softmax_loss_cand_bwd_f32(const float* Q, int64_t ldq, const float* I, int64_t ldi, int64_t n_queries,
@@ -882,25 +1010,31 @@ extern "C" int sagnn_softmax_loss_cand_bwd_f32(const float* Q, int64_t ldq, cons
                                                const float* lse, const float* g, float* dQ, int64_t lddq, float* dIc,
                                                int64_t lddic, float* dT, int64_t lddt, void* workspace,
                                                size_t workspace_bytes, void* stream) {
-  const char* who = "softmax_loss_cand_bwd";
-  Layout L;
-  Problem p;
-  const auto outputs = [&] {
-    if (!lse || !g) return sagnn::fail(SAGNN_ERR_NULL, "%s: null lse or g", who);
-    float* const out[] = {dQ, dIc, dT};
-    const int64_t ld[] = {lddq, lddic, lddt};
-    return check_outputs(who, d, 3, out, ld, "dQ, dIc or dT", "lddq / lddic / lddt", "dQ, dIc and dT");
-  };
-  if (int rc = prepare<true>(who, Q, ldq, I, ldi, n_queries, n_items, d, cand, n_cand, target, inv_temp, scale, excl_ptr,
-                             excl_items, excl_row, n_lists, outputs, workspace, workspace_bytes, L, p))
-    return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  sagnn::ProfileScope prof(sagnn::kProfSoftmaxLossCand, s, n_queries, n_cand);
-  return dispatch_d(d, [&](auto D) {
-    return launch_bwd<decltype(D)::value, true>(p, L, lse, g, dQ, lddq, dIc, lddic, dT, lddt, workspace, s);
-  });
+  return cand_bwd<false>("softmax_loss_cand_bwd", Q, ldq, I, ldi, n_queries, n_items, d, cand, n_cand, nullptr, target,
+                         inv_temp, scale, excl_ptr, excl_items, excl_row, n_lists, lse, g, dQ, lddq, dIc, lddic, dT, lddt,
+                         workspace, workspace_bytes, stream);
 }
 
+extern "C" int sagnn_softmax_loss_candb_f32(const float* Q, int64_t ldq, const float* I, int64_t ldi, int64_t n_queries,
+                                            int64_t n_items, int d, const int32_t* cand, int64_t n_cand, const float* bias,
+                                            const int32_t* target, float inv_temp, float scale, const int64_t* excl_ptr,
+                                            const int32_t* excl_items, const int32_t* excl_row, int64_t n_lists, float* loss,
+                                            float* lse, float* tscore, void* workspace, size_t workspace_bytes, void* stream) {
+  return cand_fwd<true>("softmax_loss_candb", Q, ldq, I, ldi, n_queries, n_items, d, cand, n_cand, bias, target, inv_temp,
+                        scale, excl_ptr, excl_items, excl_row, n_lists, loss, lse, tscore, workspace, workspace_bytes, stream);
+}
+
+extern "C" int sagnn_softmax_loss_candb_bwd_f32(const float* Q, int64_t ldq, const float* I, int64_t ldi, int64_t n_queries,
+                                                int64_t n_items, int d, const int32_t* cand, int64_t n_cand,
+                                                const float* bias, const int32_t* target, float inv_temp, float scale,
+                                                const int64_t* excl_ptr, const int32_t* excl_items, const int32_t* excl_row,
+                                                int64_t n_lists, const float* lse, const float* g, float* dQ, int64_t lddq,
+                                                float* dIc, int64_t lddic, float* dT, int64_t lddt, void* workspace,
+                                                size_t workspace_bytes, void* stream) {
+  return cand_bwd<true>("softmax_loss_candb_bwd", Q, ldq, I, ldi, n_queries, n_items, d, cand, n_cand, bias, target,
+                        inv_temp, scale, excl_ptr, excl_items, excl_row, n_lists, lse, g, dQ, lddq, dIc, lddic, dT, lddt,
+                        workspace, workspace_bytes, stream);
+}
 
 extern "C" int sagnn_softmax_target_add_f32(const float* dT, int64_t lddt, const int32_t* target, int64_t n_queries,
                                             int64_t n_items, int d, float* dI, int64_t lddi, void* stream) {
@@ -917,6 +1051,28 @@ extern "C" int sagnn_softmax_target_add_f32(const float* dT, int64_t lddt, const
   if (n_queries == 0) return SAGNN_OK;
   hipLaunchKernelGGL(target_add_kernel, dim3((unsigned)n_queries), dim3(64), 0, static_cast<hipStream_t>(stream), dT, lddt,
                      target, n_queries, n_items, d, dI, lddi);
+  SAGNN_HIP_TRY(hipGetLastError());
+  return SAGNN_OK;
+}
+
+extern "C" int sagnn_softmax_cand_scatter_f32(const float* dIc, int64_t lddic, const int32_t* cand, const float* bias,
+                                              int64_t n_cand, int64_t n_items, int d, float* dI, int64_t lddi, void* stream) {
+  const char* who = "softmax_cand_scatter";
+  if (d != 32 && d != 64 && d != 128) return sagnn::fail(SAGNN_ERR_DIM, "%s: d = %d, need 32, 64 or 128", who, d);
+  if (n_items < 1 || n_items >= ((int64_t)1 << 31))
+    return sagnn::fail(SAGNN_ERR_ARG, "%s: n_items = %lld, need 1 <= n_items < 2^31", who, (long long)n_items);
+  if (n_cand < 0 || n_cand > n_items)
+    return sagnn::fail(SAGNN_ERR_ARG, "%s: n_cand = %lld, need 0 <= n_cand <= n_items = %lld", who, (long long)n_cand,
+                       (long long)n_items);
+  if (!dI || (n_cand > 0 && (!dIc || !cand || !bias))) return sagnn::fail(SAGNN_ERR_NULL, "%s: null dIc, cand, bias or dI", who);
+  if ((lddic & 3) || (lddi & 3)) return sagnn::fail(SAGNN_ERR_ALIGN, "%s: strides lddic / lddi must be multiples of 4", who);
+  if (lddic < d || lddi < d) return sagnn::fail(SAGNN_ERR_ARG, "%s: strides lddic / lddi must be >= d", who);
+  if (!sagnn::aligned16(dI) || (n_cand > 0 && !sagnn::aligned16(dIc)))
+    return sagnn::fail(SAGNN_ERR_ALIGN, "%s: dIc and dI must be 16-byte aligned", who);
+  if (n_cand == 0) return SAGNN_OK;
+  const int64_t vecs = n_cand * (d / 4);
+  hipLaunchKernelGGL(cand_scatter_kernel, dim3((unsigned)((vecs + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     dIc, lddic, cand, bias, n_cand, n_items, d, dI, lddi);
   SAGNN_HIP_TRY(hipGetLastError());
   return SAGNN_OK;
 }

@@ -28,6 +28,7 @@ SEQ_POOL = ("sum", "additive")  # --seqPool: the reference's sum over the tokens
 EDGE_TIME = ("none", "slot")   # --edgeTime: the reference's graph, or messages that add their edge's time-bucket row
 RNN_CELL = ("lstm", "gru")      # --rnnCell: the reference's BasicLSTMCell, or the GRU its gru_cell() is named after
 PRED_LOSS = ("hinge", "softmax")   # --predLoss: the reference's sampled hinge loss, or softmax over the whole catalogue
+NEG_DIST = ("uniform", "pop")      # --softmaxNegDist: the uniform strata of --softmaxNegs, or a popularity-weighted draw
 
 
 def random_fusion_params(d: int, device, seed: int = 0, cell: str = "lstm") -> dict:
@@ -141,6 +142,35 @@ def banned_table(handler, n_items: int, flat=None, ptr=None):
     ban_ptr = np.zeros(U + 1, dtype=np.int64)
     np.cumsum(np.bincount(keys // I, minlength=U)[:U], out=ban_ptr[1:])
     return ban_ptr, (keys % I).astype(np.int32)
+
+
+def item_degrees(trn_mat, n_items: int) -> np.ndarray:
+    """int64 [n_items]: the stored non-zero entries per column of trnMat (duplicates summed, explicit zeros dropped)."""
+    trn = sp.csc_matrix(trn_mat, copy=True)
+    trn.sum_duplicates()
+    trn.eliminate_zeros()
+    deg = np.zeros(int(n_items), dtype=np.int64)
+    n = min(int(n_items), trn.shape[1])
+    deg[:n] = np.diff(trn.indptr)[:n]
+    return deg
+
+
+def pop_cum(deg, a: float):
+    """The integer mass of --softmaxNegDist pop: w_i = max(1, rint(2^20 (deg_i + 1)^a)) in float64 as int64, returned as
+    (cum int64 [n_items], the inclusive prefix sum; W = cum[-1] as a Python int). Integer mass makes the stratified draw
+    exact in 64-bit arithmetic, on the device and in its numpy restatement alike. Raises ValueError for an exponent
+    outside [0, 1] and for W >= 2^62 (the draw's products j * (W / n_cand) must stay inside int64)."""
+    a = float(a)
+    if not np.isfinite(a) or not 0.0 <= a <= 1.0:
+        raise ValueError(f"--softmaxNegPow {a}: need a finite exponent in [0, 1]")
+    deg = np.asarray(deg, dtype=np.int64)
+    if deg.ndim != 1 or deg.size < 1 or (deg < 0).any():
+        raise ValueError("pop_cum: need one non-negative degree per item")
+    w = np.maximum(1.0, np.rint(2.0 ** 20 * (deg.astype(np.float64) + 1.0) ** a))
+    total = sum(int(v) for v in w) if float(w.sum()) >= 2.0 ** 61 else int(w.astype(np.int64).sum())
+    if total >= 2 ** 62:
+        raise ValueError(f"--softmaxNegDist pop: the total weight {total} reaches 2^62; lower --softmaxNegPow")
+    return np.cumsum(w.astype(np.int64)), total
 
 
 class DeviceSampler:
@@ -785,13 +815,20 @@ class Recommender:
         variables are the same, and checkpoints neither store nor check it. With --softmaxNegs N > 0 the softmax runs
         over N candidates shared by the batch, drawn on the device at the top of the step (ops.sample_strata keyed by
         batch["cand_seed"] = (seed, step), default (0, 0)) under either sampler, plus each slot's own target; under
-        --fusion_rows batch the candidates are marked as touched item rows."""
+        --fusion_rows batch the candidates are marked as touched item rows. Under --softmaxNegDist pop the N candidates are
+        a popularity-weighted draw with repeats (ops.sample_strata_weighted over _pop_cum_device) and batch["cand_bias"]
+        carries their logQ offsets; nothing else in the step differs."""
         T, L, d, heads, leaky = args.graphNum, args.gnn_layer, args.latdim, args.num_attention_heads, NNs.leaky
         keep = args.keepRate if keep_rate is None else keep_rate
         subset = args.fusion_rows == "batch"
         if args.predLoss == "softmax" and args.softmaxNegs > 0:
-            batch = dict(batch, cand=ops.sample_strata(args.item, args.softmaxNegs, *batch.get("cand_seed", (0, 0)),
-                                                       self.device))
+            if args.softmaxNegDist == "pop":     # the same seed, the same place in the step
+                cand, bias = ops.sample_strata_weighted(*self._pop_cum_device(), args.softmaxNegs,
+                                                        *batch.get("cand_seed", (0, 0)))
+                batch = dict(batch, cand=cand, cand_bias=bias)
+            else:
+                batch = dict(batch, cand=ops.sample_strata(args.item, args.softmaxNegs, *batch.get("cand_seed", (0, 0)),
+                                                           self.device))
         if subset:        # the rows the loss reads, compacted on the device before the GNN stack is queued
             batch = dict(batch, uids=self._i32(batch["uids"]), iids=self._i32(batch["iids"]),
                          suids=[self._i32(v) for v in batch["suids"]], siids=[self._i32(v) for v in batch["siids"]])
@@ -867,13 +904,25 @@ class Recommender:
             return torch.from_numpy(ptr).to(self.device), torch.from_numpy(items).to(self.device)
         return self._cached("_banned_dev", (h.sequence, h.trnMat, h.tstInt, args.item, str(self.device)), build)
 
+    def _pop_cum_device(self):
+        """--softmaxNegDist pop: (cum int64 [items] on the device, W) of pop_cum over the stored non-zero entries per
+        column of the handler's trnMat, built and uploaded once."""
+        h = self.handler
+
+        def build():
+            cum, total = pop_cum(item_degrees(h.trnMat, args.item), args.softmaxNegPow)
+            return torch.from_numpy(cum).to(self.device), total
+        return self._cached("_pop_cum_dev", (h.trnMat, args.item, float(args.softmaxNegPow), str(self.device)), build)
+
     def _softmax_pre_loss(self, fu, fi, att, batch):
         """--predLoss softmax: (1 / max(n_active, 1)) * sum over the active slots b of ln sum_{i in E_b} exp(z_bi) - z_{b,t_b}
         with z_bi = <leaky(att[b]) + fu[u_b], fi[i]> / softmaxTemp and E_b = every item outside user u_b's banned list
         (the items negSamp never draws), plus the target t_b. One (slot, user, target) triple per active slot, from the
         positive half of the batch without a read-back: the first pair of each slot (host batch) or the pair at the
         slot's pair offset (device batch: batch["active"] = (slots, offsets), host tables of sample_batch_device).
-        With batch["cand"] (--softmaxNegs, drawn by train_loss) E_b is the candidates outside the banned list plus t_b."""
+        With batch["cand"] (--softmaxNegs, drawn by train_loss) E_b is the candidates outside the banned list plus t_b;
+        with batch["cand_bias"] (--softmaxNegDist pop) candidate position j adds cand_bias[j] to its logit, which makes
+        the sum an estimator of the full-catalogue one, and a position at -inf does not count."""
         dev = self.device
         if "active" in batch:
             slots, first = batch["active"]
@@ -891,7 +940,7 @@ class Recommender:
         scale = 1.0 / max(int(slots.numel()), 1)
         if "cand" in batch:     # --softmaxNegs: E_b = the step's candidates outside the banned list, plus the target
             return ag.SoftmaxLossCandFn.apply(q, fi, batch["cand"], t, 1.0 / args.softmaxTemp, scale,
-                                              self._banned_device(), u)
+                                              self._banned_device(), u, batch.get("cand_bias"))
         return ag.SoftmaxLossFn.apply(q, fi, t, 1.0 / args.softmaxTemp, scale, self._banned_device(), u)
 
     def _head_att_sum_train(self, fi, batch):
@@ -1242,6 +1291,15 @@ class Recommender:
                              "draws its own negatives")
         if args.softmaxNegs > args.item:
             raise ValueError(f"--softmaxNegs {args.softmaxNegs} exceeds the {args.item} items of the catalogue")
+        if args.softmaxNegDist not in NEG_DIST:
+            raise ValueError(f"--softmaxNegDist {args.softmaxNegDist}: one of {NEG_DIST}")
+        if args.softmaxNegDist == "pop":
+            if args.predLoss != "softmax" or args.softmaxNegs <= 0:
+                raise ValueError(f"--softmaxNegDist pop needs --predLoss softmax and --softmaxNegs > 0: it weights the "
+                                 f"draw of the shared candidates (got --predLoss {args.predLoss}, --softmaxNegs "
+                                 f"{args.softmaxNegs})")
+            if not np.isfinite(args.softmaxNegPow) or not 0.0 <= args.softmaxNegPow <= 1.0:
+                raise ValueError(f"--softmaxNegPow {args.softmaxNegPow}: need a finite exponent in [0, 1]")
         if args.predLoss == "softmax":
             if args.fusion_rows == "batch" and args.softmaxNegs == 0:
                 raise ValueError("--predLoss softmax does not combine with --fusion_rows batch: the loss reads every item "

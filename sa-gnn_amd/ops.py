@@ -1668,8 +1668,31 @@ def sample_strata(n_items: int, n_cand: int, seed: int, step: int, device) -> to
     return cand
 
 
-def _softmax_cand_args(Q, I, cand, target, inv_temp, scale, excl, excl_row):
-    """_softmax_args with the candidate list spliced in where the cand entries take it."""
+def sample_strata_weighted(cum: torch.Tensor, total: int, n_cand: int, seed: int, step: int):
+    """The candidate list of --softmaxNegDist pop (sagnn_sample_strata_w_i32): cum int64 [n_items] on the device, the
+    inclusive prefix sum of the items' integer weights, total = its last entry W as a host int (no read-back here).
+    Returns (cand int32 [n_cand], bias float32 [n_cand]): candidate j is the item whose mass holds one uniform draw from
+    stratum j of [0, W), keyed by (seed, step, j); the list is non-decreasing, the first position of a run of equal ids
+    carries bias = ln(run length) - ln(n_cand w_c / W), the others -inf. A pure function of its arguments."""
+    total, n_cand, seed, step = int(total), int(n_cand), int(seed), int(step)
+    if not isinstance(cum, torch.Tensor) or cum.dim() != 1 or cum.dtype != torch.int64 or not cum.is_cuda \
+            or not cum.is_contiguous() or not 1 <= cum.numel() < 2 ** 31:
+        raise ValueError("sample_strata_weighted: cum: need a contiguous int64 device vector [n_items], 1 <= n_items < 2^31")
+    if not 1 <= total < 2 ** 62:
+        raise ValueError(f"sample_strata_weighted: total = {total}, need 1 <= total < 2^62")
+    if n_cand < 0 or n_cand >= 2 ** 31 or n_cand > total:
+        raise ValueError(f"sample_strata_weighted: n_cand = {n_cand}, need 0 <= n_cand <= total = {total} and n_cand < 2^31")
+    if not 0 <= seed < 2 ** 64 or not 0 <= step < 2 ** 32:
+        raise ValueError(f"sample_strata_weighted: seed = {seed}, step = {step}, need 0 <= seed < 2^64 and 0 <= step < 2^32")
+    cand, bias = _out(n_cand, torch.int32, cum.device), _out(n_cand, torch.float32, cum.device)
+    check(_lib.load().sagnn_sample_strata_w_i32(cum.data_ptr(), int(cum.numel()), total, n_cand, seed, step, cand.data_ptr(),
+                                                bias.data_ptr(), _stream()))
+    return cand, bias
+
+
+def _softmax_cand_args(Q, I, cand, target, inv_temp, scale, excl, excl_row, bias=None):
+    """_softmax_args with the candidate list spliced in where the cand entries take it, and behind it the offsets
+    where the candb entries take them."""
     if not isinstance(cand, torch.Tensor) or cand.dim() != 1:
         raise ValueError("cand: expected int32 [n_cand]")
     lead, (B, n_items, d) = _softmax_args(Q, I, target, inv_temp, scale, excl, excl_row)
@@ -1679,32 +1702,45 @@ def _softmax_cand_args(Q, I, cand, target, inv_temp, scale, excl, excl_row):
     cand_p = _idx_ptr("cand", cand, torch.int32)
     if cand.device != Q.device:
         raise ValueError(f"cand on {cand.device}, Q on {Q.device}")
-    return lead[:7] + (cand_p, n_cand) + lead[7:], (B, n_items, d, n_cand)
+    offs = ()
+    if bias is not None:
+        if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or bias.dim() != 1 or bias.numel() != n_cand \
+                or not bias.is_contiguous() or bias.device != Q.device:
+            raise ValueError(f"bias: need a contiguous float32 vector of {n_cand} elements on {Q.device}")
+        # an empty tensor's data_ptr is 0; the entry reads no offset at n_cand == 0
+        offs = (bias.data_ptr() if n_cand else None,)
+    return lead[:7] + (cand_p, n_cand) + offs + lead[7:], (B, n_items, d, n_cand)
 
 
 def softmax_loss_cand(Q: torch.Tensor, I: torch.Tensor, cand: torch.Tensor, target: torch.Tensor, inv_temp: float = 1.0,
-                      scale: float | None = None, excl=None, excl_row: torch.Tensor | None = None):
+                      scale: float | None = None, excl=None, excl_row: torch.Tensor | None = None,
+                      bias: torch.Tensor | None = None):
     """softmax_loss over a candidate list (sagnn_softmax_loss_cand_f32): cand int32 [n_cand], strictly ascending ids of
     [0, n_items) (not checked: they address rows of I); row b sums over the candidates outside its exclusion list and
     other than target[b], plus target[b] itself, exactly once. n_cand == 0 is legal. The other arguments and the
-    returned (loss [1], lse [B], tscore [B]) are those of softmax_loss."""
-    lead, (B, n_items, d, n_cand) = _softmax_cand_args(Q, I, cand, target, inv_temp, scale, excl, excl_row)
+    returned (loss [1], lse [B], tscore [B]) are those of softmax_loss.
+    With bias float32 [n_cand] (sagnn_softmax_loss_candb_f32, what sample_strata_weighted draws) cand is non-decreasing
+    with adjacent repeats, position j adds bias[j] to its logit and counts only where bias[j] > -inf; the target's own
+    term takes no offset."""
+    lead, (B, n_items, d, n_cand) = _softmax_cand_args(Q, I, cand, target, inv_temp, scale, excl, excl_row, bias)
     dev = Q.device
     loss = torch.empty(1, dtype=torch.float32, device=dev)
     lse, tscore = (torch.empty(max(B, 1), dtype=torch.float32, device=dev) for _ in range(2))
     ws, need = _softmax_workspace(dev, B, n_cand, d, cand=True)
-    check(_lib.load().sagnn_softmax_loss_cand_f32(*lead, loss.data_ptr(), lse.data_ptr(), tscore.data_ptr(), ws.data_ptr(),
-                                                  need, _stream()))
+    lib = _lib.load()
+    entry = lib.sagnn_softmax_loss_cand_f32 if bias is None else lib.sagnn_softmax_loss_candb_f32
+    check(entry(*lead, loss.data_ptr(), lse.data_ptr(), tscore.data_ptr(), ws.data_ptr(), need, _stream()))
     return loss, lse[:B], tscore[:B]
 
 
 def softmax_loss_cand_bwd(Q: torch.Tensor, I: torch.Tensor, cand: torch.Tensor, target: torch.Tensor, lse: torch.Tensor,
                           g: torch.Tensor, inv_temp: float = 1.0, scale: float | None = None, excl=None,
-                          excl_row: torch.Tensor | None = None):
+                          excl_row: torch.Tensor | None = None, bias: torch.Tensor | None = None):
     """Gradients of softmax_loss_cand (sagnn_softmax_loss_cand_bwd_f32) given the forward's lse [B] and the upstream
     scalar g (a 1-element float32 device tensor): returns (dQ [B, d], dIc [n_cand, d], dT [B, d]), every row written.
-    Row j of dIc is the candidates' share of dI[cand[j]], dT[b] the target's share of dI[target[b]]."""
-    lead, (B, n_items, d, n_cand) = _softmax_cand_args(Q, I, cand, target, inv_temp, scale, excl, excl_row)
+    Row j of dIc is the candidates' share of dI[cand[j]], dT[b] the target's share of dI[target[b]]. With the forward's
+    bias (sagnn_softmax_loss_candb_bwd_f32) the dIc rows of the positions at -inf are zeros."""
+    lead, (B, n_items, d, n_cand) = _softmax_cand_args(Q, I, cand, target, inv_temp, scale, excl, excl_row, bias)
     dev = Q.device
     _lse_g_check(lse, g, B, dev)
     # one row at least behind every output: an empty tensor's data_ptr is 0 and the entry refuses NULL at any count
@@ -1713,9 +1749,25 @@ def softmax_loss_cand_bwd(Q: torch.Tensor, I: torch.Tensor, cand: torch.Tensor, 
     dIc = torch.empty((max(n_cand, 1), d), dtype=torch.float32, device=dev)
     ws, need = _softmax_workspace(dev, B, n_cand, d, cand=True)
     lse_p = lse.data_ptr() if B else dQ.data_ptr()
-    check(_lib.load().sagnn_softmax_loss_cand_bwd_f32(*lead, lse_p, g.data_ptr(), dQ.data_ptr(), d, dIc.data_ptr(), d,
-                                                      dT.data_ptr(), d, ws.data_ptr(), need, _stream()))
+    lib = _lib.load()
+    entry = lib.sagnn_softmax_loss_cand_bwd_f32 if bias is None else lib.sagnn_softmax_loss_candb_bwd_f32
+    check(entry(*lead, lse_p, g.data_ptr(), dQ.data_ptr(), d, dIc.data_ptr(), d, dT.data_ptr(), d, ws.data_ptr(), need,
+                _stream()))
     return dQ[:B], dIc[:n_cand], dT[:B]
+
+
+def softmax_cand_scatter(dI: torch.Tensor, dIc: torch.Tensor, cand: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """dI[cand[j]] = dIc[j] in place for every position with bias[j] > -inf (sagnn_softmax_cand_scatter_f32): the live
+    rows of softmax_loss_cand_bwd's dIc into a full-size dI. The live ids are distinct, so every row has one writer."""
+    n_cand, d = int(dIc.shape[0]), int(dIc.shape[1])
+    if bias.dtype != torch.float32 or bias.numel() != n_cand or not bias.is_contiguous() or cand.numel() != n_cand:
+        raise ValueError(f"softmax_cand_scatter: need cand and a contiguous float32 bias of {n_cand} elements")
+    _one_device(dI, dIc=dIc, cand=cand, bias=bias)
+    check(_lib.load().sagnn_softmax_cand_scatter_f32(dIc.data_ptr() if n_cand else None, _f32_rows("dIc", dIc, d) if n_cand else d,
+                                                     _idx_ptr("cand", cand, torch.int32), bias.data_ptr() if n_cand else None,
+                                                     n_cand, int(dI.shape[0]), d, dI.data_ptr(), _f32_rows("dI", dI, d),
+                                                     _stream()))
+    return dI
 
 
 def softmax_target_add(dI: torch.Tensor, dT: torch.Tensor, target: torch.Tensor) -> torch.Tensor:

@@ -3,7 +3,7 @@ backward) at 512 queries, forward and forward + backward, beside the materialise
 cross_entropy(Q @ I.T / temp + mask) in the same process, and prints one JSON line per case. Needs a GPU.
 
   python tools/bench_softmax_loss.py [--iters 20] [--warmup 3] [--rounds 5] [--cases gowalla,movielens,synthetic]
-                                     [--cand 4096] [--d 64]
+                                     [--cand 4096] [--dist pop] [--d 64]
 
 Cases: Gowalla-shaped (52,619 items, d 32), MovieLens-shaped (3,706 items, d 128), synthetic (5 M items, d 64). Every
 user excludes 100 random items. The two forms alternate round by round; the figures are medians over the rounds. The
@@ -12,6 +12,9 @@ from sagnn_profile_read (kind 6: one record per entry) and, kernel by kernel, fr
 --cand N adds the candidate mode (--softmaxNegs: ops.softmax_loss_cand and its backward over N candidates drawn by
 ops.sample_strata, the backward followed by the assembly of the full-size dI as autograd.SoftmaxLossCandFn does it),
 alternated with the full form in the same rounds; cases with fewer than N items skip it.
+--dist pop (with --cand) adds the popularity-weighted form (--softmaxNegDist pop) to the same rounds: N candidates drawn
+by ops.sample_strata_weighted over weights (degree + 1)^0.75 of Zipf(1.3) degrees, the entries with the per-position
+offset, and the live rows scattered into the full-size dI (ops.softmax_cand_scatter); it also times the two draws.
 Rates count 2 * queries * items * d flops per product: one product forward, four backward (the scores twice, dQ, dI)."""
 import argparse
 import json
@@ -50,6 +53,8 @@ def main():
     ap.add_argument("--cases", default=",".join(CASES))
     ap.add_argument("--temp", type=float, default=1.0)
     ap.add_argument("--cand", type=int, default=0, help="also time the candidate mode over this many sampled candidates")
+    ap.add_argument("--dist", choices=("uniform", "pop"), default="uniform",
+                    help="pop: also time the popularity-weighted candidate form beside the uniform one (needs --cand)")
     ap.add_argument("--d", type=int, default=0, help="override the cases' width (32, 64 or 128)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -95,6 +100,31 @@ def main():
                 _, lse, _ = c_fwd()
                 return ops.softmax_loss_cand_bwd(Q, I, cand, tgt, lse, one, inv_temp, None, excl)
 
+        pop = bool(n_cand) and a.dist == "pop"
+        if pop:
+            from sa_gnn_amd.model import pop_cum
+            cum_h, total = pop_cum(np.minimum(rng.zipf(1.3, n_items), n_items), 0.75)
+            cum = torch.from_numpy(cum_h).to(dev)
+            pcand, pbias = ops.sample_strata_weighted(cum, total, n_cand, 0, 0)
+
+            def p_fwd():
+                return ops.softmax_loss_cand(Q, I, pcand, tgt, inv_temp, None, excl, bias=pbias)
+
+            def p_kernels():
+                _, lse, _ = p_fwd()
+                return ops.softmax_loss_cand_bwd(Q, I, pcand, tgt, lse, one, inv_temp, None, excl, bias=pbias)
+
+            def p_fwd_bwd():
+                dQ, dIc, dT = p_kernels()
+                dI = ops.softmax_cand_scatter(torch.zeros_like(I), dIc, pcand, pbias)
+                return dQ, ops.softmax_target_add(dI, dT, tgt)
+
+            def draw_u():
+                return ops.sample_strata(n_items, n_cand, 0, 1, dev)
+
+            def draw_p():
+                return ops.sample_strata_weighted(cum, total, n_cand, 0, 1)
+
         torch_fits = B * n_items * 4 * 6 < (8 << 30)
         if torch_fits:
             mask = torch.zeros((B, n_items), device=dev)
@@ -110,7 +140,8 @@ def main():
                 Qt.grad = It.grad = None
                 torch.nn.functional.cross_entropy(Qt @ It.T * inv_temp + mask, tgt.long()).backward()
 
-        res = {k: [] for k in ("fwd", "fwd_bwd", "torch_fwd", "torch_fwd_bwd", "cand_fwd", "cand_fwd_bwd", "cand_kernels")}
+        res = {k: [] for k in ("fwd", "fwd_bwd", "torch_fwd", "torch_fwd_bwd", "cand_fwd", "cand_fwd_bwd", "cand_kernels",
+                               "pop_fwd", "pop_fwd_bwd", "pop_kernels", "draw_uniform", "draw_pop")}
         for _ in range(a.rounds):          # alternated: both forms see the same machine state
             res["fwd"].append(timed(fwd, a.iters, a.warmup))
             res["fwd_bwd"].append(timed(fwd_bwd, a.iters, a.warmup))
@@ -118,6 +149,12 @@ def main():
                 res["cand_fwd"].append(timed(c_fwd, a.iters, a.warmup))
                 res["cand_fwd_bwd"].append(timed(c_fwd_bwd, a.iters, a.warmup))
                 res["cand_kernels"].append(timed(c_kernels, a.iters, a.warmup))
+            if pop:
+                res["pop_fwd"].append(timed(p_fwd, a.iters, a.warmup))
+                res["pop_fwd_bwd"].append(timed(p_fwd_bwd, a.iters, a.warmup))
+                res["pop_kernels"].append(timed(p_kernels, a.iters, a.warmup))
+                res["draw_uniform"].append(timed(draw_u, a.iters, a.warmup))
+                res["draw_pop"].append(timed(draw_p, a.iters, a.warmup))
             if torch_fits:
                 res["torch_fwd"].append(timed(t_fwd, a.iters, a.warmup))
                 res["torch_fwd_bwd"].append(timed(t_fwd_bwd, a.iters, a.warmup))
@@ -135,6 +172,14 @@ def main():
                         "cand_fwd_speedup": round(med["fwd"] / med["cand_fwd"], 2),
                         "cand_fwd_bwd_speedup": round(med["fwd_bwd"] / med["cand_fwd_bwd"], 2),
                         "cand_loss": float(c_fwd()[0])})
+        if pop:
+            spread = lambda k: [round(min(res[k]), 4), round(max(res[k]), 4)]      # noqa: E731
+            rec.update({"pop_fwd_ms": round(med["pop_fwd"], 4), "pop_fwd_bwd_entries_ms": round(med["pop_kernels"], 4),
+                        "pop_fwd_bwd_with_full_dI_ms": round(med["pop_fwd_bwd"], 4),
+                        "draw_uniform_ms": round(med["draw_uniform"], 4), "draw_pop_ms": round(med["draw_pop"], 4),
+                        "pop_live": int(torch.isfinite(pbias).sum()), "pop_loss": float(p_fwd()[0]),
+                        "min_max_over_rounds": {k: spread(k) for k in ("cand_fwd", "pop_fwd", "cand_kernels", "pop_kernels",
+                                                                       "cand_fwd_bwd", "pop_fwd_bwd")}})
         if torch_fits:
             loss = float(fwd()[0])
             rec.update({"torch_fwd_ms": round(med["torch_fwd"], 4), "torch_fwd_bwd_ms": round(med["torch_fwd_bwd"], 4),

@@ -13,7 +13,9 @@ the two poolings of the full head (the plain sum / additive attention; it implie
 the additive variables, every timed epoch from the initial parameters, and reports kind 5 per step for each.
 --softmaxNegs N runs the softmax loss over N sampled candidates (kind 7 instead of 6), which also lets --predLoss softmax
 combine with --fusion_rows batch; with --predLoss both it is a third loss beside the hinge loss and the full-catalogue
-softmax (which then runs under --fusion_rows all only). --sampler restricts the run to one sampler."""
+softmax (which then runs under --fusion_rows all only). --softmaxNegDist pop draws those candidates by popularity with
+the logQ offsets; both alternates the uniform and the weighted draw as two losses. --sampler restricts the run to one
+sampler."""
 import argparse
 import ctypes
 import sys
@@ -62,6 +64,8 @@ def main():
                     help="the full head's pooling(s) to time (implies --seqAtt full); both alternates them in one process")
     ap.add_argument("--softmaxNegs", type=int, default=0,
                     help="candidates of --predLoss softmax (0 = the whole catalogue); > 0 allows --fusion_rows batch with it")
+    ap.add_argument("--softmaxNegDist", choices=("uniform", "pop", "both"), default="uniform",
+                    help="how the --softmaxNegs candidates are drawn; both alternates the two in one process")
     ap.add_argument("--sampler", choices=("host", "device", "both"), default="both", help="the sampler(s) to time")
     opt = ap.parse_args()
     if opt.seqPool != "sum" and opt.seqAtt == "sum":
@@ -75,27 +79,33 @@ def main():
     args.seqAtt = "sum"
     if opt.softmaxNegs < 0 or opt.softmaxNegs > args.item:
         sys.exit(f"--softmaxNegs {opt.softmaxNegs}: need 0 <= N <= {args.item}")
+    if opt.softmaxNegDist != "uniform" and (opt.softmaxNegs == 0 or opt.predLoss == "hinge"):
+        sys.exit(f"--softmaxNegDist {opt.softmaxNegDist} needs --softmaxNegs > 0 and --predLoss softmax or both")
     if opt.epoch_only:
         args.sampler = "device"
         args.fusion_rows = "batch" if opt.fusion_rows == "batch" else "all"
         args.seqAtt = "full" if opt.seqAtt == "full" else "sum"
         args.predLoss = "softmax" if opt.predLoss == "softmax" else "hinge"
         args.softmaxNegs = opt.softmaxNegs if args.predLoss == "softmax" else 0
+        args.softmaxNegDist = "pop" if opt.softmaxNegDist == "pop" and args.softmaxNegs else "uniform"
         args.seqPool = "additive" if opt.seqPool == "additive" else "sum"
         for _ in range(2):
             rec.trainEpoch()
         torch.cuda.synchronize()
         print(f"two device-sampler epochs done (--fusion_rows {args.fusion_rows}, --edge_keep {args.edgeKeepRate}, "
-              f"--seqAtt {args.seqAtt}, --seqPool {args.seqPool}, --predLoss {args.predLoss}, --softmaxNegs {args.softmaxNegs}); "
+              f"--seqAtt {args.seqAtt}, --seqPool {args.seqPool}, --predLoss {args.predLoss}, --softmaxNegs {args.softmaxNegs}, "
+              f"--softmaxNegDist {args.softmaxNegDist}); "
               "every parameter finite:",
               all(bool(torch.isfinite(p).all()) for p in NNs.params.values()))
         return
     modes = ("all", "batch") if opt.fusion_rows == "both" else (opt.fusion_rows,)
     atts = ("sum", "full") if opt.seqAtt == "both" else (opt.seqAtt,)
     negs = f"softmax, softmaxNegs {opt.softmaxNegs}"       # the third loss: the softmax over sampled candidates
+    negs_pop = negs + ", pop"                              # a fourth: those candidates drawn by popularity
+    cand_losses = {"uniform": (negs,), "pop": (negs_pop,), "both": (negs, negs_pop)}[opt.softmaxNegDist]
     losses = ("hinge", "softmax") if opt.predLoss == "both" else (opt.predLoss,)
     if opt.softmaxNegs and "softmax" in losses:
-        losses = losses + (negs,) if opt.predLoss == "both" else (negs,)
+        losses = losses + cand_losses if opt.predLoss == "both" else cand_losses
     pools = ("sum", "additive") if opt.seqPool == "both" else (opt.seqPool,)
     if "softmax" in losses and modes == ("batch",):
         sys.exit("--predLoss softmax does not combine with --fusion_rows batch without --softmaxNegs")
@@ -119,7 +129,8 @@ def main():
         # parameters as before, so its lines, not a `both` run's sum lines, are what compares with an earlier commit.
         args.sampler, args.fusion_rows, args.seqAtt, loss, args.seqPool = c
         args.predLoss = "hinge" if loss == "hinge" else "softmax"
-        args.softmaxNegs = opt.softmaxNegs if loss == negs else 0
+        args.softmaxNegs = opt.softmaxNegs if loss in cand_losses else 0
+        args.softmaxNegDist = "pop" if loss == negs_pop else "uniform"
         if fresh and len(atts) * len(losses) * len(pools) > 1:
             with torch.no_grad():
                 for k, p in NNs.params.items():
@@ -217,7 +228,7 @@ def main():
         ms, kind, n = np.zeros(cap, np.float32), np.zeros(cap, np.int32), ctypes.c_int(0)
         ops.check(lib.sagnn_profile_read(ms.ctypes.data, kind.ctypes.data, None, None, cap, ctypes.byref(n)))
         lib.sagnn_profile_enable(0)
-        sel = np.flatnonzero(kind[:n.value] == (7 if loss == negs else 6))
+        sel = np.flatnonzero(kind[:n.value] == (7 if loss in cand_losses else 6))
         print(f"[device, {mode} rows, predLoss {loss}] softmax-loss entries: {len(sel) / steps:.0f} calls per step; forward "
               f"{float(ms[sel[0::2]].sum()) / steps:.3f} ms and backward {float(ms[sel[1::2]].sum()) / steps:.3f} ms of device "
               f"time per step")
@@ -225,6 +236,7 @@ def main():
     args.fusion_rows = "all"
     args.predLoss = "hinge"
     args.softmaxNegs = 0
+    args.softmaxNegDist = "uniform"
     args.sampler = "host"
     args.seqAtt = "sum"
     args.seqPool = "sum"
