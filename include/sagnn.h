@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define SAGNN_VERSION 10400 /* 1.4.0 */
+#define SAGNN_VERSION 10500 /* 1.5.0 */
 
 enum {
   SAGNN_OK = 0,
@@ -79,8 +79,8 @@ size_t sagnn_last_error(char* buf, size_t cap);
  *       2 = LSTM (or the GRU forward of sagnn_gru_fwd_f32), 3 = layer-norm, 4 = MHSA+mean (units_a = n, units_b = t),
  *       5 = an entry of the sequence attention (seq_attn.hip: gather, attention, pool, additive pool and
  *       their backwards; units_a = n_slots, units_b = pos_length),
- *       6 = sagnn_softmax_loss_f32 or its backward (units_a = n_queries, units_b = n_items),
- *       7 = sagnn_softmax_loss_cand_f32 or its backward (units_a = n_queries, units_b = n_cand).
+ *       6 = sagnn_softmax_loss_f32 or its backward in SAGNN_SOFTMAX_FULL (units_a = n_queries, units_b = n_items),
+ *       7 = the same entries in a candidate mode (units_a = n_queries, units_b = n_cand).
  * -------------------------------------------------------------------------------- */
 int sagnn_profile_enable(int capacity);
 int sagnn_profile_read(float* ms, int32_t* kind, int64_t* units_a, int64_t* units_b, int cap,
@@ -919,7 +919,9 @@ int sagnn_seq_addpool_bwd_f32(const float* x, int64_t ldx, const float* u, int64
 
 /* ------------------------------------------------------------------------------------
  * Full-catalogue softmax cross-entropy (softmax_loss.hip; --predLoss softmax, not in the reference, which trains the
- * head with a sampled hinge loss only: model.py:241-246).
+ * head with a sampled hinge loss only: model.py:241-246): sagnn_softmax_loss_f32 and sagnn_softmax_loss_bwd_f32 with
+ * mode = SAGNN_SOFTMAX_FULL. The operands are the fields of sagnn_softmax_args, declared with the two entries below the
+ * three blocks that state what each mode computes.
  *   z(b, i) = <Q[b], I[i]> * inv_temp, the product in fp32 on the exact-fp32 matrix cores (v_mfma_f32_16x16x4_f32): a
  *   fixed fmaf chain over k, a function of the query row and the item row alone. sagnn_set_engine does NOT apply.
  *   loss[0] = scale * sum over rows b with a target of ( lse[b] - z(b, target[b]) ),
@@ -939,22 +941,13 @@ int sagnn_seq_addpool_bwd_f32(const float* x, int64_t ldx, const float* u, int64
  * lse[b], tscore[b] and dQ[b] depend on row b's inputs only: not on n_queries, the row's position or the strides. All
  *   outputs are bit-identical between runs (no atomics: chunk partials are merged in a fixed order).
  * Logits beyond fp32's exp range are fine (running maximum); a side without eligible items merges as empty.
- * Limits: d in {32, 64, 128}; n_queries >= 0; 1 <= n_items < 2^31; ldq, ldi, lddq, lddi multiples of 4 and >= d; Q, I, dQ,
- *   dI and workspace 16-byte aligned; inv_temp > 0 and finite, scale finite; workspace_bytes >=
+ * Limits, on the struct's fields: d in {32, 64, 128}; n_queries >= 0; 1 <= n_items < 2^31; ldq, ldi, lddq, lddi multiples
+ *   of 4 and >= d; Q, I, dQ, dI and workspace 16-byte aligned; inv_temp > 0 and finite, scale finite; workspace_bytes >=
  *   sagnn_softmax_loss_workspace_bytes(n_queries, n_items, d) (one size serves both entries; it grows with each
- *   argument). Every argument is checked before any device work. Three launches each on `stream`, no allocation, no
+ *   argument). Every field is checked before any device work. Three launches each on `stream`, no allocation, no
  *   synchronisation (capturable). Profile kind 6.
  * -------------------------------------------------------------------------------- */
 size_t sagnn_softmax_loss_workspace_bytes(int64_t n_queries, int64_t n_items, int d);
-int sagnn_softmax_loss_f32(const float* Q, int64_t ldq, const float* I, int64_t ldi, int64_t n_queries, int64_t n_items,
-                           int d, const int32_t* target, float inv_temp, float scale, const int64_t* excl_ptr,
-                           const int32_t* excl_items, const int32_t* excl_row, int64_t n_lists, float* loss, float* lse,
-                           float* tscore, void* workspace, size_t workspace_bytes, void* stream);
-int sagnn_softmax_loss_bwd_f32(const float* Q, int64_t ldq, const float* I, int64_t ldi, int64_t n_queries,
-                               int64_t n_items, int d, const int32_t* target, float inv_temp, float scale,
-                               const int64_t* excl_ptr, const int32_t* excl_items, const int32_t* excl_row,
-                               int64_t n_lists, const float* lse, const float* g, float* dQ, int64_t lddq, float* dI,
-                               int64_t lddi, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Sampled-candidate softmax cross-entropy (softmax_loss.hip, sampler.hip; --softmaxNegs, not in the reference): the
@@ -967,24 +960,25 @@ int sagnn_softmax_loss_bwd_f32(const float* Q, int64_t ldq, const float* I, int6
  *   stratum's size), and the sizes differ by at most one. n_cand == n_items gives 0, 1, .., n_items - 1.
  *   Refused before any launch: n_items < 1 or >= 2^31, n_cand < 0 or > n_items, a NULL cand with n_cand > 0. One launch
  *   on `stream` (none when n_cand == 0).
- * sagnn_softmax_loss_cand_f32: I is the full [n_items, d] table, cand int32 [n_cand] (DEVICE) strictly ascending ids
- *   in [0, n_items); its contents are the caller's responsibility, they are used as row addresses. z, lse, tscore,
- *   loss, the exclusion lists and the skipped rows are those of sagnn_softmax_loss_f32, with the eligible set
+ * sagnn_softmax_loss_f32 with mode = SAGNN_SOFTMAX_CAND: I is the full [n_items, d] table, cand int32 [n_cand] (DEVICE)
+ *   strictly ascending ids in [0, n_items); its contents are the caller's responsibility, they are used as row
+ *   addresses. z, lse, tscore, loss, the exclusion lists and the skipped rows are those of SAGNN_SOFTMAX_FULL, with the
+ *   eligible set
  *     E_b = { c in cand : c not on row b's list, c != target[b] } + { target[b] }:
  *   the target enters exactly once, through its own term, whether or not it is a candidate or on the list.
  *   n_cand == 0 is legal: lse[b] = z(b, target[b]), no loss, no gradient.
- * sagnn_softmax_loss_cand_bwd_f32: with g(b, i) as above over E_b,
+ * sagnn_softmax_loss_bwd_f32 with mode = SAGNN_SOFTMAX_CAND: with g(b, i) as above over E_b,
  *   dQ[b]  = sum_{i in E_b} g(b, i) I[i], the target's term included;
  *   dIc[j] = sum over rows b with cand[j] in E_b and cand[j] != target[b] of g(b, cand[j]) Q[b]: row j of
- *            dIc [n_cand, d] belongs to item cand[j];
+ *            dIc [n_cand, d] belongs to item cand[j]. dIc and its stride lddic are the struct's dI and lddi;
  *   dT[b]  = g(b, target[b]) Q[b], [n_queries, d]: the target's share of dI, one row per query (several rows may share
  *            a target; adding them into dI is the caller's).
  *   Every row of dQ, dIc and dT is WRITTEN (zeros where nothing contributes, skipped rows included).
  * lse[b], tscore[b], dQ[b] and dT[b] depend on row b's inputs only; chunks depend on n_cand only; no atomics, all
  *   outputs are bit-identical between runs.
- * Limits: those of sagnn_softmax_loss_f32, and 0 <= n_cand <= n_items, cand non-NULL when n_cand > 0, lddic and lddt
- *   multiples of 4 and >= d, dIc and dT 16-byte aligned, workspace_bytes >=
- *   sagnn_softmax_loss_cand_workspace_bytes(n_queries, n_cand, d) (grows with each argument). Every argument is checked
+ * Limits, on the struct's fields: those of SAGNN_SOFTMAX_FULL, and 0 <= n_cand <= n_items, cand non-NULL when n_cand > 0,
+ *   lddi (lddic) and lddt multiples of 4 and >= d, dI (dIc) and dT 16-byte aligned, workspace_bytes >=
+ *   sagnn_softmax_loss_cand_workspace_bytes(n_queries, n_cand, d) (grows with each argument). Every field is checked
  *   before any device work. At most three launches each on `stream`, no allocation, no synchronisation (capturable).
  *   Profile kind 7 (units_a = n_queries, units_b = n_cand).
  * sagnn_softmax_target_add_f32: dI[target[b]] += dT[b] for every row b with a target in [0, n_items), the rows that
@@ -996,21 +990,10 @@ int sagnn_softmax_target_add_f32(const float* dT, int64_t lddt, const int32_t* t
                                  int d, float* dI, int64_t lddi, void* stream);
 int sagnn_sample_strata_i32(int64_t n_items, int64_t n_cand, uint64_t seed, uint32_t step, int32_t* cand, void* stream);
 size_t sagnn_softmax_loss_cand_workspace_bytes(int64_t n_queries, int64_t n_cand, int d);
-int sagnn_softmax_loss_cand_f32(const float* Q, int64_t ldq, const float* I, int64_t ldi, int64_t n_queries,
-                                int64_t n_items, int d, const int32_t* cand, int64_t n_cand, const int32_t* target,
-                                float inv_temp, float scale, const int64_t* excl_ptr, const int32_t* excl_items,
-                                const int32_t* excl_row, int64_t n_lists, float* loss, float* lse, float* tscore,
-                                void* workspace, size_t workspace_bytes, void* stream);
-int sagnn_softmax_loss_cand_bwd_f32(const float* Q, int64_t ldq, const float* I, int64_t ldi, int64_t n_queries,
-                                    int64_t n_items, int d, const int32_t* cand, int64_t n_cand, const int32_t* target,
-                                    float inv_temp, float scale, const int64_t* excl_ptr, const int32_t* excl_items,
-                                    const int32_t* excl_row, int64_t n_lists, const float* lse, const float* g, float* dQ,
-                                    int64_t lddq, float* dIc, int64_t lddic, float* dT, int64_t lddt, void* workspace,
-                                    size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Popularity-weighted candidates with the logQ correction (sampler.hip, softmax_loss.hip; --softmaxNegDist pop, not in
- * the reference): the sampled softmax of word2vec and two-tower retrieval over the candidate entries above.
+ * the reference): the sampled softmax of word2vec and two-tower retrieval over the candidate mode above.
  * sagnn_sample_strata_w_i32: a stratified draw of n_cand ids with replacement, item i drawn in proportion to its
  *   integer weight w_i. cum int64 [n_items] (DEVICE) is the inclusive prefix sum of the weights, non-decreasing with
  *   cum[0] >= 1; total = cum[n_items - 1] = W is the caller's HOST copy of its last entry (the entry reads nothing
@@ -1030,12 +1013,12 @@ int sagnn_softmax_loss_cand_bwd_f32(const float* Q, int64_t ldq, const float* I,
  *   Refused before any launch: n_items < 1 or >= 2^31, total < 1 or >= 2^62, n_cand < 0, >= 2^31 or > total, a NULL cum,
  *   a NULL cand or bias with n_cand > 0. Two launches on `stream` (none when n_cand == 0), no allocation, no
  *   synchronisation (capturable). A cum that breaks the contract still yields ids inside [0, n_items).
- * sagnn_softmax_loss_candb_f32 / sagnn_softmax_loss_candb_bwd_f32: sagnn_softmax_loss_cand_f32 and its backward with a
+ * sagnn_softmax_loss_f32 / sagnn_softmax_loss_bwd_f32 with mode = SAGNN_SOFTMAX_CAND_BIAS: SAGNN_SOFTMAX_CAND with a
  *   per-position offset bias float [n_cand] (DEVICE) and a NON-DECREASING cand whose repeats are adjacent. Position j
  *   is eligible for row b when cand[j] is (above) AND bias[j] > -inf, and its logit is z(b, cand[j]) + bias[j], one
  *   fp32 add; the target's own term takes no offset and tscore is unchanged. With the first position of each run the
  *   only one above -inf (what the draw writes) an id enters a row's sum once. The dIc rows of dead positions are exact
- *   zeros. A zero bias on a strictly ascending list gives the bits of the entries without it. The same limits,
+ *   zeros. A zero bias on a strictly ascending list gives the bits of SAGNN_SOFTMAX_CAND. The same limits,
  *   workspace (sagnn_softmax_loss_cand_workspace_bytes), launches and profile kind; a NULL bias with n_cand > 0 is
  *   refused.
  * sagnn_softmax_cand_scatter_f32: dI[cand[j]] = dIc[j] for every position j with bias[j] > -inf and cand[j] inside
@@ -1045,19 +1028,53 @@ int sagnn_softmax_loss_cand_bwd_f32(const float* Q, int64_t ldq, const float* I,
  * -------------------------------------------------------------------------------- */
 int sagnn_sample_strata_w_i32(const int64_t* cum, int64_t n_items, int64_t total, int64_t n_cand, uint64_t seed,
                               uint32_t step, int32_t* cand, float* bias, void* stream);
-int sagnn_softmax_loss_candb_f32(const float* Q, int64_t ldq, const float* I, int64_t ldi, int64_t n_queries,
-                                 int64_t n_items, int d, const int32_t* cand, int64_t n_cand, const float* bias,
-                                 const int32_t* target, float inv_temp, float scale, const int64_t* excl_ptr,
-                                 const int32_t* excl_items, const int32_t* excl_row, int64_t n_lists, float* loss, float* lse,
-                                 float* tscore, void* workspace, size_t workspace_bytes, void* stream);
-int sagnn_softmax_loss_candb_bwd_f32(const float* Q, int64_t ldq, const float* I, int64_t ldi, int64_t n_queries,
-                                     int64_t n_items, int d, const int32_t* cand, int64_t n_cand, const float* bias,
-                                     const int32_t* target, float inv_temp, float scale, const int64_t* excl_ptr,
-                                     const int32_t* excl_items, const int32_t* excl_row, int64_t n_lists, const float* lse,
-                                     const float* g, float* dQ, int64_t lddq, float* dIc, int64_t lddic, float* dT,
-                                     int64_t lddt, void* workspace, size_t workspace_bytes, void* stream);
 int sagnn_softmax_cand_scatter_f32(const float* dIc, int64_t lddic, const int32_t* cand, const float* bias, int64_t n_cand,
                                    int64_t n_items, int d, float* dI, int64_t lddi, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * The two softmax-loss entries and their operands. `mode` names the form; it is not inferred from which pointer is set:
+ *   SAGNN_SOFTMAX_FULL       the whole catalogue; cand and bias must be NULL and n_cand 0.
+ *   SAGNN_SOFTMAX_CAND       the candidate list cand [n_cand]; bias must be NULL.
+ *   SAGNN_SOFTMAX_CAND_BIAS  the list with the offsets bias [n_cand]; a NULL bias with n_cand > 0 is refused.
+ * A NULL args (SAGNN_ERR_NULL), a `mode` outside these three and a field that contradicts the mode (SAGNN_ERR_ARG) are
+ * refused before anything else is looked at; then the shared fields, the candidate fields, the entry's own pointers and
+ * the workspace are checked in that order, all of it before any launch. A field that an entry or a mode does not read
+ * may hold anything, the ones the mode rules name excepted. The messages in sagnn_last_error start with softmax_loss,
+ * softmax_loss_cand or softmax_loss_candb by the mode, with _bwd appended by the backward.
+ * -------------------------------------------------------------------------------- */
+enum { SAGNN_SOFTMAX_FULL = 0, SAGNN_SOFTMAX_CAND = 1, SAGNN_SOFTMAX_CAND_BIAS = 2 };
+
+typedef struct sagnn_softmax_args {
+  /* both entries, every mode */
+  const float* Q;  int64_t ldq;               /* [n_queries, d] */
+  const float* I;  int64_t ldi;               /* [n_items, d], the full table in every mode */
+  int64_t n_queries, n_items;
+  int d;
+  const int32_t* target;                      /* [n_queries] */
+  float inv_temp, scale;
+  const int64_t* excl_ptr;                    /* [n_lists + 1], or the three NULL */
+  const int32_t* excl_items;
+  const int32_t* excl_row;                    /* [n_queries], or NULL: row b uses list b */
+  int64_t n_lists;
+  int mode;                                   /* SAGNN_SOFTMAX_* */
+  /* both entries, the candidate modes */
+  const int32_t* cand;  int64_t n_cand;       /* SAGNN_SOFTMAX_CAND and _CAND_BIAS */
+  const float* bias;                          /* SAGNN_SOFTMAX_CAND_BIAS: [n_cand] */
+  /* the forward writes these; the backward reads lse alone */
+  float* loss;                                /* [1] */
+  float* lse;                                 /* [n_queries] */
+  float* tscore;                              /* [n_queries] */
+  /* the backward alone */
+  const float* g;                             /* the upstream scalar, DEVICE [1] */
+  float* dQ;  int64_t lddq;                   /* [n_queries, d] */
+  float* dI;  int64_t lddi;                   /* SAGNN_SOFTMAX_FULL: dI [n_items, d]; candidate modes: dIc [n_cand, d] */
+  float* dT;  int64_t lddt;                   /* candidate modes: [n_queries, d]; SAGNN_SOFTMAX_FULL does not read them */
+  /* both entries: sagnn_softmax_loss_workspace_bytes in SAGNN_SOFTMAX_FULL, _cand_workspace_bytes in the candidate modes */
+  void* workspace;  size_t workspace_bytes;
+} sagnn_softmax_args;
+
+int sagnn_softmax_loss_f32(const sagnn_softmax_args* args, void* stream);
+int sagnn_softmax_loss_bwd_f32(const sagnn_softmax_args* args, void* stream);
 
 #ifdef __cplusplus
 }

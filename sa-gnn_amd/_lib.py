@@ -58,6 +58,20 @@ class GnnArgs(ctypes.Structure):
                 ("workspace", c_void_p), ("workspace_bytes", c_size_t)]
 
 
+SOFTMAX_FULL, SOFTMAX_CAND, SOFTMAX_CAND_BIAS = 0, 1, 2       # SAGNN_SOFTMAX_*
+
+
+class SoftmaxArgs(ctypes.Structure):
+    """sagnn_softmax_args"""
+    _fields_ = [("Q", c_void_p), ("ldq", c_int64), ("I", c_void_p), ("ldi", c_int64), ("n_queries", c_int64),
+                ("n_items", c_int64), ("d", c_int), ("target", c_void_p), ("inv_temp", c_float), ("scale", c_float),
+                ("excl_ptr", c_void_p), ("excl_items", c_void_p), ("excl_row", c_void_p), ("n_lists", c_int64),
+                ("mode", c_int), ("cand", c_void_p), ("n_cand", c_int64), ("bias", c_void_p), ("loss", c_void_p),
+                ("lse", c_void_p), ("tscore", c_void_p), ("g", c_void_p), ("dQ", c_void_p), ("lddq", c_int64),
+                ("dI", c_void_p), ("lddi", c_int64), ("dT", c_void_p), ("lddt", c_int64), ("workspace", c_void_p),
+                ("workspace_bytes", c_size_t)]
+
+
 class PlanInfo(ctypes.Structure):
     _fields_ = [("n_rows", c_int64), ("n_src", c_int64), ("nnz", c_int64),
                 ("n_long_rows", c_int64), ("n_chunks", c_int64), ("short_thresh", c_int32),
@@ -220,31 +234,13 @@ SIGNATURES = {
                                           c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
                                           c_void_p]),
     "sagnn_softmax_loss_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int]),
-    "sagnn_softmax_loss_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_float,
-                                       c_float, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
-                                       c_void_p, c_size_t, c_void_p]),
-    "sagnn_softmax_loss_bwd_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_float,
-                                           c_float, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
-                                           c_int64, c_void_p, c_int64, c_void_p, c_size_t, c_void_p]),
+    "sagnn_softmax_loss_f32": (c_int, [POINTER(SoftmaxArgs), c_void_p]),
+    "sagnn_softmax_loss_bwd_f32": (c_int, [POINTER(SoftmaxArgs), c_void_p]),
     "sagnn_sample_strata_i32": (c_int, [c_int64, c_int64, c_uint64, c_uint32, c_void_p, c_void_p]),
     "sagnn_softmax_target_add_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p]),
     "sagnn_softmax_loss_cand_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int]),
-    "sagnn_softmax_loss_cand_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_int64,
-                                            c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
-                                            c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "sagnn_softmax_loss_cand_bwd_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p,
-                                                c_int64, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_int64,
-                                                c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
-                                                c_void_p, c_size_t, c_void_p]),
     "sagnn_sample_strata_w_i32": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_uint64, c_uint32, c_void_p, c_void_p,
                                           c_void_p]),
-    "sagnn_softmax_loss_candb_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_int64,
-                                             c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_int64,
-                                             c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "sagnn_softmax_loss_candb_bwd_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p,
-                                                 c_int64, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p,
-                                                 c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
-                                                 c_int64, c_void_p, c_size_t, c_void_p]),
     "sagnn_softmax_cand_scatter_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p,
                                                c_int64, c_void_p]),
 }
@@ -263,8 +259,8 @@ def load() -> ctypes.CDLL:
             "g.build()'` (or `make -C sa-gnn_amd/csrc`). There is no fallback path.")
     lib = ctypes.CDLL(LIB_PATH)
     lib.sagnn_version.restype = c_int
-    if lib.sagnn_version() < 10400:     # before 1.4.0 the GNN stack entries took positional arguments under the same names
-        raise ImportError(f"{LIB_PATH} is libsagnn {lib.sagnn_version()}: this binding needs >= 10400 (sagnn_gnn_args)")
+    if lib.sagnn_version() < 10500:     # before 1.5.0 the softmax-loss entries took positional arguments under the same names
+        raise ImportError(f"{LIB_PATH} is libsagnn {lib.sagnn_version()}: this binding needs >= 10500 (sagnn_softmax_args)")
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch
         fn.restype = res

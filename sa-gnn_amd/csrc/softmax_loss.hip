@@ -2,8 +2,8 @@
 // exact-fp32 matrix cores (v_mfma_f32_16x16x4_f32), loss = scale * sum_b (ln sum_{i eligible} exp z(b, i) - z(b, t_b)).
 // The [queries x items] logits are never stored: the forward streams a log-sum-exp, the backward recomputes them.
 //
-// The kernels run over POSITIONS. Full mode (sagnn_softmax_loss_f32 / _bwd_f32): position j is item j, there are n_items
-// of them. Candidate mode (sagnn_softmax_loss_cand_f32 / _bwd_f32, --softmaxNegs): position j is item cand[j] of an
+// The kernels run over POSITIONS. Full mode (SAGNN_SOFTMAX_FULL of sagnn_softmax_loss_f32 / _bwd_f32): position j is item
+// j, there are n_items of them. Candidate mode (SAGNN_SOFTMAX_CAND, --softmaxNegs): position j is item cand[j] of an
 // ascending id list shared by the batch, there are n_cand of them, and a position past the list reads the last
 // candidate's row and is never eligible. The mode is a template argument, never a runtime branch, and all it decides
 // is stated once, in Mode<CAND> and Tile<CAND> below:
@@ -15,8 +15,8 @@
 //      NI = 1 in di_kernel, and has dq_row_kernel where full mode has dq_merge_kernel.
 // A full instantiation loads no cand, shuffles no ids and uses no LDS.
 //
-// Candidate mode has one more compile-time property, the per-position logit offset (sagnn_softmax_loss_candb_f32 /
-// _bwd_f32, --softmaxNegDist pop), stated once in Offset<BIAS> below: position j adds bias[j] to its logit, and a
+// Candidate mode has one more compile-time property, the per-position logit offset (SAGNN_SOFTMAX_CAND_BIAS,
+// --softmaxNegDist pop), stated once in Offset<BIAS> below: position j adds bias[j] to its logit, and a
 // position with bias[j] = -inf is dead, never eligible. The list may then repeat ids (non-decreasing, repeats adjacent,
 // the first position of a run the only live one), and the id matching above stays right for these reasons alone:
 //   - the chunk kernels' walk passes every list entry <= the tile's last id, so a run that goes on into the next tile
@@ -809,135 +809,138 @@ int dispatch_d(int d, F f) {
   }
 }
 
-// The checks all four entries share; `who` prefixes the message.
-int check_common(const char* who, const float* Q, int64_t ldq, const float* I, int64_t ldi, int64_t n_queries,
-                 int64_t n_items, int d, const int32_t* target, float inv_temp, float scale, const int64_t* excl_ptr,
-                 const int32_t* excl_items, const int32_t* excl_row, int64_t n_lists) {
-  if (!Q || !I) return sagnn::fail(SAGNN_ERR_NULL, "%s: null Q or I", who);
-  if (!target) return sagnn::fail(SAGNN_ERR_NULL, "%s: null target", who);
-  if ((excl_ptr == nullptr) != (excl_items == nullptr))
+// f(CAND, BIAS) as std::bool_constant for a mode that check_mode let through
+template <class F>
+int dispatch_mode(int mode, F f) {
+  switch (mode) {
+    case SAGNN_SOFTMAX_FULL: return f(std::false_type(), std::false_type());
+    case SAGNN_SOFTMAX_CAND: return f(std::true_type(), std::false_type());
+    default: return f(std::true_type(), std::true_type());
+  }
+}
+
+// The struct itself and the form args->mode names, ahead of everything else: the mode decides the name in the messages.
+int check_mode(const sagnn_softmax_args* a) {
+  if (!a) return sagnn::fail(SAGNN_ERR_NULL, "the sagnn_softmax_args is NULL");
+  switch (a->mode) {
+    case SAGNN_SOFTMAX_FULL:
+      if (a->cand) return sagnn::fail(SAGNN_ERR_ARG, "mode = SAGNN_SOFTMAX_FULL with a cand");
+      if (a->bias) return sagnn::fail(SAGNN_ERR_ARG, "mode = SAGNN_SOFTMAX_FULL with a bias");
+      if (a->n_cand != 0) return sagnn::fail(SAGNN_ERR_ARG, "mode = SAGNN_SOFTMAX_FULL with n_cand = %lld", (long long)a->n_cand);
+      return SAGNN_OK;
+    case SAGNN_SOFTMAX_CAND:
+      if (a->bias) return sagnn::fail(SAGNN_ERR_ARG, "mode = SAGNN_SOFTMAX_CAND with a bias");
+      return SAGNN_OK;
+    case SAGNN_SOFTMAX_CAND_BIAS: return SAGNN_OK;
+  }
+  return sagnn::fail(SAGNN_ERR_ARG, "mode = %d: not a SAGNN_SOFTMAX_* value", a->mode);
+}
+
+// The checks both entries share in every mode; `who` prefixes the message.
+int check_common(const char* who, const sagnn_softmax_args& a) {
+  if (!a.Q || !a.I) return sagnn::fail(SAGNN_ERR_NULL, "%s: null Q or I", who);
+  if (!a.target) return sagnn::fail(SAGNN_ERR_NULL, "%s: null target", who);
+  if ((a.excl_ptr == nullptr) != (a.excl_items == nullptr))
     return sagnn::fail(SAGNN_ERR_NULL, "%s: excl_ptr and excl_items go together", who);
-  if (excl_row && !excl_ptr) return sagnn::fail(SAGNN_ERR_NULL, "%s: excl_row without excl_ptr / excl_items", who);
-  if (d != 32 && d != 64 && d != 128) return sagnn::fail(SAGNN_ERR_DIM, "%s: d = %d, need 32, 64 or 128", who, d);
-  if (n_queries < 0 || n_queries > INT32_MAX) return sagnn::fail(SAGNN_ERR_ARG, "%s: n_queries = %lld", who, (long long)n_queries);
-  if (n_items < 1 || n_items >= ((int64_t)1 << 31))
-    return sagnn::fail(SAGNN_ERR_ARG, "%s: n_items = %lld, need 1 <= n_items < 2^31", who, (long long)n_items);
-  if (!(inv_temp > 0.f) || !isfinite(inv_temp))
-    return sagnn::fail(SAGNN_ERR_ARG, "%s: inv_temp = %g, need a finite value > 0", who, (double)inv_temp);
-  if (!isfinite(scale)) return sagnn::fail(SAGNN_ERR_ARG, "%s: scale = %g is not finite", who, (double)scale);
-  if (excl_ptr && n_lists < 0) return sagnn::fail(SAGNN_ERR_ARG, "%s: n_lists = %lld", who, (long long)n_lists);
-  if (excl_ptr && !excl_row && n_lists < n_queries)
-    return sagnn::fail(SAGNN_ERR_ARG, "%s: %lld exclusion lists for %lld rows and no excl_row", who, (long long)n_lists,
-                       (long long)n_queries);
-  if ((ldq & 3) || (ldi & 3)) return sagnn::fail(SAGNN_ERR_ALIGN, "%s: strides ldq / ldi must be multiples of 4", who);
-  if (ldq < d || ldi < d) return sagnn::fail(SAGNN_ERR_ARG, "%s: strides ldq / ldi must be >= d", who);
-  if (!sagnn::aligned16(Q) || !sagnn::aligned16(I))
+  if (a.excl_row && !a.excl_ptr) return sagnn::fail(SAGNN_ERR_NULL, "%s: excl_row without excl_ptr / excl_items", who);
+  if (a.d != 32 && a.d != 64 && a.d != 128) return sagnn::fail(SAGNN_ERR_DIM, "%s: d = %d, need 32, 64 or 128", who, a.d);
+  if (a.n_queries < 0 || a.n_queries > INT32_MAX)
+    return sagnn::fail(SAGNN_ERR_ARG, "%s: n_queries = %lld", who, (long long)a.n_queries);
+  if (a.n_items < 1 || a.n_items >= ((int64_t)1 << 31))
+    return sagnn::fail(SAGNN_ERR_ARG, "%s: n_items = %lld, need 1 <= n_items < 2^31", who, (long long)a.n_items);
+  if (!(a.inv_temp > 0.f) || !isfinite(a.inv_temp))
+    return sagnn::fail(SAGNN_ERR_ARG, "%s: inv_temp = %g, need a finite value > 0", who, (double)a.inv_temp);
+  if (!isfinite(a.scale)) return sagnn::fail(SAGNN_ERR_ARG, "%s: scale = %g is not finite", who, (double)a.scale);
+  if (a.excl_ptr && a.n_lists < 0) return sagnn::fail(SAGNN_ERR_ARG, "%s: n_lists = %lld", who, (long long)a.n_lists);
+  if (a.excl_ptr && !a.excl_row && a.n_lists < a.n_queries)
+    return sagnn::fail(SAGNN_ERR_ARG, "%s: %lld exclusion lists for %lld rows and no excl_row", who, (long long)a.n_lists,
+                       (long long)a.n_queries);
+  if ((a.ldq & 3) || (a.ldi & 3)) return sagnn::fail(SAGNN_ERR_ALIGN, "%s: strides ldq / ldi must be multiples of 4", who);
+  if (a.ldq < a.d || a.ldi < a.d) return sagnn::fail(SAGNN_ERR_ARG, "%s: strides ldq / ldi must be >= d", who);
+  if (!sagnn::aligned16(a.Q) || !sagnn::aligned16(a.I))
     return sagnn::fail(SAGNN_ERR_ALIGN, "%s: Q and I must be 16-byte aligned", who);
   return SAGNN_OK;
 }
 
-int check_cand(const char* who, int64_t n_items, const int32_t* cand, int64_t n_cand, bool with_bias, const float* bias) {
-  if (n_cand < 0 || n_cand > n_items)
-    return sagnn::fail(SAGNN_ERR_ARG, "%s: n_cand = %lld, need 0 <= n_cand <= n_items = %lld", who, (long long)n_cand,
-                       (long long)n_items);
-  if (n_cand > 0 && !cand) return sagnn::fail(SAGNN_ERR_NULL, "%s: null cand", who);
-  if (with_bias && n_cand > 0 && !bias) return sagnn::fail(SAGNN_ERR_NULL, "%s: null bias", who);
+// The candidate modes' own checks.
+int check_cand(const char* who, const sagnn_softmax_args& a) {
+  if (a.n_cand < 0 || a.n_cand > a.n_items)
+    return sagnn::fail(SAGNN_ERR_ARG, "%s: n_cand = %lld, need 0 <= n_cand <= n_items = %lld", who, (long long)a.n_cand,
+                       (long long)a.n_items);
+  if (a.n_cand > 0 && !a.cand) return sagnn::fail(SAGNN_ERR_NULL, "%s: null cand", who);
+  if (a.mode == SAGNN_SOFTMAX_CAND_BIAS && a.n_cand > 0 && !a.bias) return sagnn::fail(SAGNN_ERR_NULL, "%s: null bias", who);
   return SAGNN_OK;
 }
 
-int check_workspace(const char* who, size_t need, const void* workspace, size_t workspace_bytes) {
+int check_workspace(const char* who, size_t need, const sagnn_softmax_args& a) {
   if (need == 0) return SAGNN_OK;
-  if (!workspace || workspace_bytes < need)
-    return sagnn::fail(SAGNN_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
-  if (!sagnn::aligned16(workspace)) return sagnn::fail(SAGNN_ERR_ALIGN, "%s: workspace must be 16-byte aligned", who);
+  if (!a.workspace || a.workspace_bytes < need)
+    return sagnn::fail(SAGNN_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, a.workspace_bytes, need);
+  if (!sagnn::aligned16(a.workspace)) return sagnn::fail(SAGNN_ERR_ALIGN, "%s: workspace must be 16-byte aligned", who);
   return SAGNN_OK;
 }
 
-int check_fwd_outputs(const char* who, const float* loss, const float* lse, const float* tscore) {
-  if (!loss || !lse || !tscore) return sagnn::fail(SAGNN_ERR_NULL, "%s: null loss, lse or tscore", who);
+int check_fwd_outputs(const char* who, const sagnn_softmax_args& a) {
+  if (!a.loss || !a.lse || !a.tscore) return sagnn::fail(SAGNN_ERR_NULL, "%s: null loss, lse or tscore", who);
   return SAGNN_OK;
 }
 
-// The backward's n output matrices of d columns. The messages name them: `any` as in "dQ or dI", `strides` as in
-// "lddq / lddi", `all` as in "dQ and dI".
-int check_outputs(const char* who, int d, int n, float* const* out, const int64_t* ld, const char* any, const char* strides,
-                  const char* all) {
+// The backward's inputs and its output matrices of d columns: dQ and dI, and in the candidate modes, where dI is the
+// [n_cand, d] dIc, dT as well. The messages name them.
+int check_bwd_outputs(const char* who, const sagnn_softmax_args& a) {
+  const bool cand = a.mode != SAGNN_SOFTMAX_FULL;
+  const int n = cand ? 3 : 2;
+  const char* any = cand ? "dQ, dIc or dT" : "dQ or dI";
+  const char* strides = cand ? "lddq / lddic / lddt" : "lddq / lddi";
+  const char* all = cand ? "dQ, dIc and dT" : "dQ and dI";
+  float* const out[] = {a.dQ, a.dI, a.dT};
+  const int64_t ld[] = {a.lddq, a.lddi, a.lddt};
+  if (!a.lse || !a.g) return sagnn::fail(SAGNN_ERR_NULL, "%s: null lse or g", who);
   for (int k = 0; k < n; ++k)
     if (!out[k]) return sagnn::fail(SAGNN_ERR_NULL, "%s: null %s", who, any);
   for (int k = 0; k < n; ++k)
     if (ld[k] & 3) return sagnn::fail(SAGNN_ERR_ALIGN, "%s: strides %s must be multiples of 4", who, strides);
   for (int k = 0; k < n; ++k)
-    if (ld[k] < d) return sagnn::fail(SAGNN_ERR_ARG, "%s: strides %s must be >= d", who, strides);
+    if (ld[k] < a.d) return sagnn::fail(SAGNN_ERR_ARG, "%s: strides %s must be >= d", who, strides);
   for (int k = 0; k < n; ++k)
     if (!sagnn::aligned16(out[k])) return sagnn::fail(SAGNN_ERR_ALIGN, "%s: %s must be 16-byte aligned", who, all);
   return SAGNN_OK;
 }
 
-// What the entries of one mode share up to the launch: the checks in the order of their messages, the workspace, the
-// problem. `outputs` checks the entry's own pointers between the two; full mode passes cand = nullptr, n_cand = 0, and
-// only an entry with the offset (BIAS) passes a bias.
-template <bool CAND, bool BIAS, class Outputs>
-int prepare(const char* who, const float* Q, int64_t ldq, const float* I, int64_t ldi, int64_t n_queries, int64_t n_items,
-            int d, const int32_t* cand, int64_t n_cand, const float* bias, const int32_t* target, float inv_temp, float scale,
-            const int64_t* excl_ptr, const int32_t* excl_items, const int32_t* excl_row, int64_t n_lists, Outputs outputs,
-            const void* workspace, size_t workspace_bytes, Layout& L, Problem& p) {
-  if (int rc = check_common(who, Q, ldq, I, ldi, n_queries, n_items, d, target, inv_temp, scale, excl_ptr, excl_items,
-                            excl_row, n_lists))
-    return rc;
-  if constexpr (CAND)
-    if (int rc = check_cand(who, n_items, cand, n_cand, BIAS, bias)) return rc;
-  if (int rc = outputs()) return rc;
-  L = layout(n_queries, CAND ? n_cand : n_items, d);
-  if (int rc = check_workspace(who, L.bytes, workspace, workspace_bytes)) return rc;
-  p = Problem{Q, ldq, I, ldi, n_queries, n_items, target, inv_temp, scale, excl_ptr, excl_items, excl_row, n_lists,
-              L.chunk, L.n_chunks, cand, n_cand};
-  return SAGNN_OK;
-}
-
-// The candidate entries, with and without the offset: the extern "C" pairs below differ in `who`, BIAS and bias only.
-template <bool BIAS>
-int cand_fwd(const char* who, const float* Q, int64_t ldq, const float* I, int64_t ldi, int64_t n_queries, int64_t n_items,
-             int d, const int32_t* cand, int64_t n_cand, const float* bias, const int32_t* target, float inv_temp,
-             float scale, const int64_t* excl_ptr, const int32_t* excl_items, const int32_t* excl_row, int64_t n_lists,
-             float* loss, float* lse, float* tscore, void* workspace, size_t workspace_bytes, void* stream) {
-  Layout L;
-  Problem p;
-  const auto outputs = [&] { return check_fwd_outputs(who, loss, lse, tscore); };
-  if (int rc = prepare<true, BIAS>(who, Q, ldq, I, ldi, n_queries, n_items, d, cand, n_cand, bias, target, inv_temp, scale,
-                                   excl_ptr, excl_items, excl_row, n_lists, outputs, workspace, workspace_bytes, L, p))
-    return rc;
+// Both entries: the checks in the order of their messages (the mode, the shared ones, the candidates, the entry's own
+// pointers, the workspace), the problem, then the launches of the mode and of d.
+int run(const sagnn_softmax_args* args, bool backward, void* stream) {
+  static const char* const names[3][2] = {{"softmax_loss", "softmax_loss_bwd"},
+                                          {"softmax_loss_cand", "softmax_loss_cand_bwd"},
+                                          {"softmax_loss_candb", "softmax_loss_candb_bwd"}};
+  if (int rc = check_mode(args)) return rc;
+  const sagnn_softmax_args& a = *args;
+  const char* who = names[a.mode][backward];
+  const bool cand = a.mode != SAGNN_SOFTMAX_FULL;
+  if (int rc = check_common(who, a)) return rc;
+  if (cand)
+    if (int rc = check_cand(who, a)) return rc;
+  if (int rc = backward ? check_bwd_outputs(who, a) : check_fwd_outputs(who, a)) return rc;
+  const int64_t n_pos = cand ? a.n_cand : a.n_items;
+  const Layout L = layout(a.n_queries, n_pos, a.d);
+  if (int rc = check_workspace(who, L.bytes, a)) return rc;
+  const Problem p{a.Q, a.ldq, a.I, a.ldi, a.n_queries, a.n_items, a.target, a.inv_temp, a.scale, a.excl_ptr, a.excl_items,
+                  a.excl_row, a.n_lists, L.chunk, L.n_chunks, a.cand, a.n_cand};
   hipStream_t s = static_cast<hipStream_t>(stream);
-  sagnn::ProfileScope prof(sagnn::kProfSoftmaxLossCand, s, n_queries, n_cand);
-  Offset<BIAS> ob;
-  if constexpr (BIAS) ob.bias = bias;
-  return dispatch_d(d, [&](auto D) {
-    return launch_fwd<decltype(D)::value, true, BIAS>(p, ob, L, loss, lse, tscore, workspace, s);
-  });
-}
-
-template <bool BIAS>
-int cand_bwd(const char* who, const float* Q, int64_t ldq, const float* I, int64_t ldi, int64_t n_queries, int64_t n_items,
-             int d, const int32_t* cand, int64_t n_cand, const float* bias, const int32_t* target, float inv_temp,
-             float scale, const int64_t* excl_ptr, const int32_t* excl_items, const int32_t* excl_row, int64_t n_lists,
-             const float* lse, const float* g, float* dQ, int64_t lddq, float* dIc, int64_t lddic, float* dT, int64_t lddt,
-             void* workspace, size_t workspace_bytes, void* stream) {
-  Layout L;
-  Problem p;
-  const auto outputs = [&] {
-    if (!lse || !g) return sagnn::fail(SAGNN_ERR_NULL, "%s: null lse or g", who);
-    float* const out[] = {dQ, dIc, dT};
-    const int64_t ld[] = {lddq, lddic, lddt};
-    return check_outputs(who, d, 3, out, ld, "dQ, dIc or dT", "lddq / lddic / lddt", "dQ, dIc and dT");
-  };
-  if (int rc = prepare<true, BIAS>(who, Q, ldq, I, ldi, n_queries, n_items, d, cand, n_cand, bias, target, inv_temp, scale,
-                                   excl_ptr, excl_items, excl_row, n_lists, outputs, workspace, workspace_bytes, L, p))
-    return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  sagnn::ProfileScope prof(sagnn::kProfSoftmaxLossCand, s, n_queries, n_cand);
-  Offset<BIAS> ob;
-  if constexpr (BIAS) ob.bias = bias;
-  return dispatch_d(d, [&](auto D) {
-    return launch_bwd<decltype(D)::value, true, BIAS>(p, ob, L, lse, g, dQ, lddq, dIc, lddic, dT, lddt, workspace, s);
+  sagnn::ProfileScope prof(cand ? sagnn::kProfSoftmaxLossCand : sagnn::kProfSoftmaxLoss, s, a.n_queries, n_pos);
+  return dispatch_mode(a.mode, [&](auto C, auto B) {
+    constexpr bool CAND = decltype(C)::value, BIAS = decltype(B)::value;
+    Offset<BIAS> ob;
+    if constexpr (BIAS) ob.bias = a.bias;
+    // a mode's three forwards are named before its three backwards: that is the kernels' order in the code object
+    if (!backward)
+      return dispatch_d(a.d, [&](auto D) {
+        return launch_fwd<decltype(D)::value, CAND, BIAS>(p, ob, L, a.loss, a.lse, a.tscore, a.workspace, s);
+      });
+    return dispatch_d(a.d, [&](auto D) {
+      return launch_bwd<decltype(D)::value, CAND, BIAS>(p, ob, L, a.lse, a.g, a.dQ, a.lddq, a.dI, a.lddi, a.dT, a.lddt,
+                                                        a.workspace, s);
+    });
   });
 }
 
@@ -953,88 +956,9 @@ extern "C" size_t sagnn_softmax_loss_cand_workspace_bytes(int64_t n_queries, int
   return layout(n_queries, n_cand, d).bytes;
 }
 
-extern "C" int sagnn_softmax_loss_f32(const float* Q, int64_t ldq, const float* I, int64_t ldi, int64_t n_queries,
-                                      int64_t n_items, int d, const int32_t* target, float inv_temp, float scale,
-                                      const int64_t* excl_ptr, const int32_t* excl_items, const int32_t* excl_row,
-                                      int64_t n_lists, float* loss, float* lse, float* tscore, void* workspace,
-                                      size_t workspace_bytes, void* stream) {
-  const char* who = "softmax_loss";
-  Layout L;
-  Problem p;
-  const auto outputs = [&] { return check_fwd_outputs(who, loss, lse, tscore); };
-  if (int rc = prepare<false, false>(who, Q, ldq, I, ldi, n_queries, n_items, d, nullptr, 0, nullptr, target, inv_temp, scale, excl_ptr,
-                              excl_items, excl_row, n_lists, outputs, workspace, workspace_bytes, L, p))
-    return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  sagnn::ProfileScope prof(sagnn::kProfSoftmaxLoss, s, n_queries, n_items);
-  return dispatch_d(d, [&](auto D) { return launch_fwd<decltype(D)::value, false, false>(p, Offset<false>{}, L, loss, lse, tscore, workspace, s); });
-}
+extern "C" int sagnn_softmax_loss_f32(const sagnn_softmax_args* args, void* stream) { return run(args, false, stream); }
 
-extern "C" int sagnn_softmax_loss_bwd_f32(const float* Q, int64_t ldq, const float* I, int64_t ldi, int64_t n_queries,
-                                          int64_t n_items, int d, const int32_t* target, float inv_temp, float scale,
-                                          const int64_t* excl_ptr, const int32_t* excl_items, const int32_t* excl_row,
-                                          int64_t n_lists, const float* lse, const float* g, float* dQ, int64_t lddq,
-                                          float* dI, int64_t lddi, void* workspace, size_t workspace_bytes, void* stream) {
-  const char* who = "softmax_loss_bwd";
-  Layout L;
-  Problem p;
-  const auto outputs = [&] {
-    if (!lse || !g) return sagnn::fail(SAGNN_ERR_NULL, "%s: null lse or g", who);
-    float* const out[] = {dQ, dI};
-    const int64_t ld[] = {lddq, lddi};
-    return check_outputs(who, d, 2, out, ld, "dQ or dI", "lddq / lddi", "dQ and dI");
-  };
-  if (int rc = prepare<false, false>(who, Q, ldq, I, ldi, n_queries, n_items, d, nullptr, 0, nullptr, target, inv_temp, scale, excl_ptr,
-                              excl_items, excl_row, n_lists, outputs, workspace, workspace_bytes, L, p))
-    return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  sagnn::ProfileScope prof(sagnn::kProfSoftmaxLoss, s, n_queries, n_items);
-  return dispatch_d(d, [&](auto D) {
-    return launch_bwd<decltype(D)::value, false, false>(p, Offset<false>{}, L, lse, g, dQ, lddq, dI, lddi, nullptr, 0, workspace, s);
-  });
-}
-
-extern "C" int sagnn_softmax_loss_cand_f32(const float* Q, int64_t ldq, const float* I, int64_t ldi, int64_t n_queries,
-                                           int64_t n_items, int d, const int32_t* cand, int64_t n_cand,
-                                           const int32_t* target, float inv_temp, float scale, const int64_t* excl_ptr,
-                                           const int32_t* excl_items, const int32_t* excl_row, int64_t n_lists, float* loss,
-                                           float* lse, float* tscore, void* workspace, size_t workspace_bytes, void* stream) {
-  return cand_fwd<false>("softmax_loss_cand", Q, ldq, I, ldi, n_queries, n_items, d, cand, n_cand, nullptr, target, inv_temp,
-                         scale, excl_ptr, excl_items, excl_row, n_lists, loss, lse, tscore, workspace, workspace_bytes, stream);
-}
-
-extern "C" int sagnn_softmax_loss_cand_bwd_f32(const float* Q, int64_t ldq, const float* I, int64_t ldi, int64_t n_queries,
-                                               int64_t n_items, int d, const int32_t* cand, int64_t n_cand,
-                                               const int32_t* target, float inv_temp, float scale, const int64_t* excl_ptr,
-                                               const int32_t* excl_items, const int32_t* excl_row, int64_t n_lists,
-                                               const float* lse, const float* g, float* dQ, int64_t lddq, float* dIc,
-                                               int64_t lddic, float* dT, int64_t lddt, void* workspace,
-                                               size_t workspace_bytes, void* stream) {
-  return cand_bwd<false>("softmax_loss_cand_bwd", Q, ldq, I, ldi, n_queries, n_items, d, cand, n_cand, nullptr, target,
-                         inv_temp, scale, excl_ptr, excl_items, excl_row, n_lists, lse, g, dQ, lddq, dIc, lddic, dT, lddt,
-                         workspace, workspace_bytes, stream);
-}
-
-extern "C" int sagnn_softmax_loss_candb_f32(const float* Q, int64_t ldq, const float* I, int64_t ldi, int64_t n_queries,
-                                            int64_t n_items, int d, const int32_t* cand, int64_t n_cand, const float* bias,
-                                            const int32_t* target, float inv_temp, float scale, const int64_t* excl_ptr,
-                                            const int32_t* excl_items, const int32_t* excl_row, int64_t n_lists, float* loss,
-                                            float* lse, float* tscore, void* workspace, size_t workspace_bytes, void* stream) {
-  return cand_fwd<true>("softmax_loss_candb", Q, ldq, I, ldi, n_queries, n_items, d, cand, n_cand, bias, target, inv_temp,
-                        scale, excl_ptr, excl_items, excl_row, n_lists, loss, lse, tscore, workspace, workspace_bytes, stream);
-}
-
-extern "C" int sagnn_softmax_loss_candb_bwd_f32(const float* Q, int64_t ldq, const float* I, int64_t ldi, int64_t n_queries,
-                                                int64_t n_items, int d, const int32_t* cand, int64_t n_cand,
-                                                const float* bias, const int32_t* target, float inv_temp, float scale,
-                                                const int64_t* excl_ptr, const int32_t* excl_items, const int32_t* excl_row,
-                                                int64_t n_lists, const float* lse, const float* g, float* dQ, int64_t lddq,
-                                                float* dIc, int64_t lddic, float* dT, int64_t lddt, void* workspace,
-                                                size_t workspace_bytes, void* stream) {
-  return cand_bwd<true>("softmax_loss_candb_bwd", Q, ldq, I, ldi, n_queries, n_items, d, cand, n_cand, bias, target,
-                        inv_temp, scale, excl_ptr, excl_items, excl_row, n_lists, lse, g, dQ, lddq, dIc, lddic, dT, lddt,
-                        workspace, workspace_bytes, stream);
-}
+extern "C" int sagnn_softmax_loss_bwd_f32(const sagnn_softmax_args* args, void* stream) { return run(args, true, stream); }
 
 extern "C" int sagnn_softmax_target_add_f32(const float* dT, int64_t lddt, const int32_t* target, int64_t n_queries,
                                             int64_t n_items, int d, float* dI, int64_t lddi, void* stream) {

@@ -1545,8 +1545,8 @@ _softmax_ws: dict = {}   # (cand, device, n_queries, positions, d) -> workspace 
 
 
 def _softmax_workspace(device: torch.device, B: int, n_pos: int, d: int, cand: bool = False):
-    """The cached workspace of sagnn_softmax_loss_f32 over n_pos = n_items positions, or with `cand` that of
-    sagnn_softmax_loss_cand_f32 over n_pos = n_cand, shared with the entry's backward, and its size in bytes."""
+    """The cached workspace of sagnn_softmax_loss_f32 over n_pos = n_items positions, or with `cand` that of its
+    candidate modes over n_pos = n_cand, shared with the entry's backward, and its size in bytes."""
     key = (cand, device, B, n_pos, d)
     ws = _softmax_ws.get(key)
     if ws is None:
@@ -1567,9 +1567,13 @@ def _lse_g_check(lse, g, B: int, dev):
             raise ValueError(f"{name}: need a contiguous float32 tensor of {n} elements on {dev}")
 
 
-def _softmax_args(Q, I, target, inv_temp, scale, excl, excl_row):
-    """Host checks shared by softmax_loss and softmax_loss_bwd, before any device call. Returns the leading arguments
-    of both entries, (B, n_items, d) and the tensors that must stay alive over the call."""
+def _softmax_struct(mode, Q, I, target, inv_temp, scale, excl, excl_row, cand=None, bias=None):
+    """Host checks of the four softmax-loss wrappers, once and before any device call. Returns a SoftmaxArgs with the
+    mode, the shared operands and, in a candidate mode, cand / n_cand / bias set (the outputs and the workspace are the
+    caller's), and (B, n_items, d, n_cand)."""
+    full = mode == _lib.SOFTMAX_FULL
+    if not full and (not isinstance(cand, torch.Tensor) or cand.dim() != 1):
+        raise ValueError("cand: expected int32 [n_cand]")
     if not isinstance(Q, torch.Tensor) or Q.dim() != 2:
         raise ValueError(f"Q: expected [B, d], got {tuple(Q.shape) if isinstance(Q, torch.Tensor) else type(Q)}")
     B, d = int(Q.shape[0]), int(Q.shape[1])
@@ -1611,8 +1615,31 @@ def _softmax_args(Q, I, target, inv_temp, scale, excl, excl_row):
                 raise ValueError(f"excl_row on {excl_row.device}, Q on {dev}")
         elif n_lists < B:
             raise ValueError(f"excl: {n_lists} lists for {B} rows and no excl_row")
-    lead = (Q.data_ptr(), ldq, I.data_ptr(), ldi, B, n_items, d, tgt, inv_temp, scale, ptr_p, items_p, row_p, n_lists)
-    return lead, (B, n_items, d)
+    a = _lib.SoftmaxArgs(mode=mode, Q=Q.data_ptr(), ldq=ldq, I=I.data_ptr(), ldi=ldi, n_queries=B, n_items=n_items, d=d,
+                         target=tgt, inv_temp=inv_temp, scale=scale, excl_ptr=ptr_p, excl_items=items_p, excl_row=row_p,
+                         n_lists=n_lists)
+    if full:
+        return a, (B, n_items, d, 0)
+    n_cand = int(cand.numel())
+    if n_cand > n_items:
+        raise ValueError(f"cand: {n_cand} candidates for {n_items} items")
+    a.cand, a.n_cand = _idx_ptr("cand", cand, torch.int32), n_cand
+    if cand.device != dev:
+        raise ValueError(f"cand on {cand.device}, Q on {dev}")
+    if bias is not None:
+        if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or bias.dim() != 1 or bias.numel() != n_cand \
+                or not bias.is_contiguous() or bias.device != dev:
+            raise ValueError(f"bias: need a contiguous float32 vector of {n_cand} elements on {dev}")
+        # an empty tensor's data_ptr is 0; the entry reads no offset at n_cand == 0
+        a.bias = bias.data_ptr() if n_cand else None
+    return a, (B, n_items, d, n_cand)
+
+
+def _softmax_call(entry, a, dev, B: int, n_pos: int, d: int) -> None:
+    """Sets the workspace of n_pos positions on the filled struct and calls one of the two entries with it."""
+    ws, need = _softmax_workspace(dev, B, n_pos, d, cand=a.mode != _lib.SOFTMAX_FULL)
+    a.workspace, a.workspace_bytes = ws.data_ptr(), need
+    check(entry(ctypes.byref(a), _stream()))
 
 
 def softmax_loss(Q: torch.Tensor, I: torch.Tensor, target: torch.Tensor, inv_temp: float = 1.0, scale: float | None = None,
@@ -1623,13 +1650,12 @@ def softmax_loss(Q: torch.Tensor, I: torch.Tensor, target: torch.Tensor, inv_tem
     [0, n_items) are skipped. excl = (ptr int64 [n_lists + 1], items int32) device tensors, lists ascending; row b uses
     list excl_row[b] (int32 [B]) or list b. scale defaults to 1 / max(B, 1).
     Returns (loss [1], lse [B], tscore [B] = <Q[b], I[target[b]]>); the logits are never stored."""
-    lead, (B, n_items, d) = _softmax_args(Q, I, target, inv_temp, scale, excl, excl_row)
+    a, (B, n_items, d, _) = _softmax_struct(_lib.SOFTMAX_FULL, Q, I, target, inv_temp, scale, excl, excl_row)
     dev = Q.device
     loss = torch.empty(1, dtype=torch.float32, device=dev)
     lse, tscore = _out(B, torch.float32, dev), _out(B, torch.float32, dev)
-    ws, need = _softmax_workspace(dev, B, n_items, d)
-    check(_lib.load().sagnn_softmax_loss_f32(*lead, loss.data_ptr(), lse.data_ptr(), tscore.data_ptr(), ws.data_ptr(), need,
-                                             _stream()))
+    a.loss, a.lse, a.tscore = loss.data_ptr(), lse.data_ptr(), tscore.data_ptr()
+    _softmax_call(_lib.load().sagnn_softmax_loss_f32, a, dev, B, n_items, d)
     return loss, lse, tscore
 
 
@@ -1637,15 +1663,14 @@ def softmax_loss_bwd(Q: torch.Tensor, I: torch.Tensor, target: torch.Tensor, lse
                      inv_temp: float = 1.0, scale: float | None = None, excl=None, excl_row: torch.Tensor | None = None):
     """Gradients of softmax_loss (sagnn_softmax_loss_bwd_f32) given the forward's lse [B] and the upstream scalar g (a
     1-element float32 device tensor): returns (dQ [B, d], dI [n_items, d]), every row written, the logits recomputed."""
-    lead, (B, n_items, d) = _softmax_args(Q, I, target, inv_temp, scale, excl, excl_row)
+    a, (B, n_items, d, _) = _softmax_struct(_lib.SOFTMAX_FULL, Q, I, target, inv_temp, scale, excl, excl_row)
     dev = Q.device
     _lse_g_check(lse, g, B, dev)
     dQ = torch.empty((max(B, 1), d), dtype=torch.float32, device=dev)[:B]
     dI = torch.empty((n_items, d), dtype=torch.float32, device=dev)
-    ws, need = _softmax_workspace(dev, B, n_items, d)
-    lse_p = lse.data_ptr() if B else dQ.data_ptr()
-    check(_lib.load().sagnn_softmax_loss_bwd_f32(*lead, lse_p, g.data_ptr(), dQ.data_ptr(), d, dI.data_ptr(), d,
-                                                 ws.data_ptr(), need, _stream()))
+    a.lse, a.g = lse.data_ptr() if B else dQ.data_ptr(), g.data_ptr()
+    a.dQ, a.lddq, a.dI, a.lddi = dQ.data_ptr(), d, dI.data_ptr(), d
+    _softmax_call(_lib.load().sagnn_softmax_loss_bwd_f32, a, dev, B, n_items, d)
     return dQ, dI
 
 
@@ -1690,69 +1715,44 @@ def sample_strata_weighted(cum: torch.Tensor, total: int, n_cand: int, seed: int
     return cand, bias
 
 
-def _softmax_cand_args(Q, I, cand, target, inv_temp, scale, excl, excl_row, bias=None):
-    """_softmax_args with the candidate list spliced in where the cand entries take it, and behind it the offsets
-    where the candb entries take them."""
-    if not isinstance(cand, torch.Tensor) or cand.dim() != 1:
-        raise ValueError("cand: expected int32 [n_cand]")
-    lead, (B, n_items, d) = _softmax_args(Q, I, target, inv_temp, scale, excl, excl_row)
-    n_cand = int(cand.numel())
-    if n_cand > n_items:
-        raise ValueError(f"cand: {n_cand} candidates for {n_items} items")
-    cand_p = _idx_ptr("cand", cand, torch.int32)
-    if cand.device != Q.device:
-        raise ValueError(f"cand on {cand.device}, Q on {Q.device}")
-    offs = ()
-    if bias is not None:
-        if not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or bias.dim() != 1 or bias.numel() != n_cand \
-                or not bias.is_contiguous() or bias.device != Q.device:
-            raise ValueError(f"bias: need a contiguous float32 vector of {n_cand} elements on {Q.device}")
-        # an empty tensor's data_ptr is 0; the entry reads no offset at n_cand == 0
-        offs = (bias.data_ptr() if n_cand else None,)
-    return lead[:7] + (cand_p, n_cand) + offs + lead[7:], (B, n_items, d, n_cand)
-
-
 def softmax_loss_cand(Q: torch.Tensor, I: torch.Tensor, cand: torch.Tensor, target: torch.Tensor, inv_temp: float = 1.0,
                       scale: float | None = None, excl=None, excl_row: torch.Tensor | None = None,
                       bias: torch.Tensor | None = None):
-    """softmax_loss over a candidate list (sagnn_softmax_loss_cand_f32): cand int32 [n_cand], strictly ascending ids of
-    [0, n_items) (not checked: they address rows of I); row b sums over the candidates outside its exclusion list and
+    """softmax_loss over a candidate list (sagnn_softmax_loss_f32, SAGNN_SOFTMAX_CAND): cand int32 [n_cand], strictly ascending
+    ids of [0, n_items) (not checked: they address rows of I); row b sums over the candidates outside its exclusion list and
     other than target[b], plus target[b] itself, exactly once. n_cand == 0 is legal. The other arguments and the
     returned (loss [1], lse [B], tscore [B]) are those of softmax_loss.
-    With bias float32 [n_cand] (sagnn_softmax_loss_candb_f32, what sample_strata_weighted draws) cand is non-decreasing
+    With bias float32 [n_cand] (SAGNN_SOFTMAX_CAND_BIAS, what sample_strata_weighted draws) cand is non-decreasing
     with adjacent repeats, position j adds bias[j] to its logit and counts only where bias[j] > -inf; the target's own
     term takes no offset."""
-    lead, (B, n_items, d, n_cand) = _softmax_cand_args(Q, I, cand, target, inv_temp, scale, excl, excl_row, bias)
+    mode = _lib.SOFTMAX_CAND if bias is None else _lib.SOFTMAX_CAND_BIAS
+    a, (B, n_items, d, n_cand) = _softmax_struct(mode, Q, I, target, inv_temp, scale, excl, excl_row, cand, bias)
     dev = Q.device
     loss = torch.empty(1, dtype=torch.float32, device=dev)
     lse, tscore = (torch.empty(max(B, 1), dtype=torch.float32, device=dev) for _ in range(2))
-    ws, need = _softmax_workspace(dev, B, n_cand, d, cand=True)
-    lib = _lib.load()
-    entry = lib.sagnn_softmax_loss_cand_f32 if bias is None else lib.sagnn_softmax_loss_candb_f32
-    check(entry(*lead, loss.data_ptr(), lse.data_ptr(), tscore.data_ptr(), ws.data_ptr(), need, _stream()))
+    a.loss, a.lse, a.tscore = loss.data_ptr(), lse.data_ptr(), tscore.data_ptr()
+    _softmax_call(_lib.load().sagnn_softmax_loss_f32, a, dev, B, n_cand, d)
     return loss, lse[:B], tscore[:B]
 
 
 def softmax_loss_cand_bwd(Q: torch.Tensor, I: torch.Tensor, cand: torch.Tensor, target: torch.Tensor, lse: torch.Tensor,
                           g: torch.Tensor, inv_temp: float = 1.0, scale: float | None = None, excl=None,
                           excl_row: torch.Tensor | None = None, bias: torch.Tensor | None = None):
-    """Gradients of softmax_loss_cand (sagnn_softmax_loss_cand_bwd_f32) given the forward's lse [B] and the upstream
+    """Gradients of softmax_loss_cand (sagnn_softmax_loss_bwd_f32, same mode) given the forward's lse [B] and the upstream
     scalar g (a 1-element float32 device tensor): returns (dQ [B, d], dIc [n_cand, d], dT [B, d]), every row written.
     Row j of dIc is the candidates' share of dI[cand[j]], dT[b] the target's share of dI[target[b]]. With the forward's
-    bias (sagnn_softmax_loss_candb_bwd_f32) the dIc rows of the positions at -inf are zeros."""
-    lead, (B, n_items, d, n_cand) = _softmax_cand_args(Q, I, cand, target, inv_temp, scale, excl, excl_row, bias)
+    bias (SAGNN_SOFTMAX_CAND_BIAS) the dIc rows of the positions at -inf are zeros."""
+    mode = _lib.SOFTMAX_CAND if bias is None else _lib.SOFTMAX_CAND_BIAS
+    a, (B, n_items, d, n_cand) = _softmax_struct(mode, Q, I, target, inv_temp, scale, excl, excl_row, cand, bias)
     dev = Q.device
     _lse_g_check(lse, g, B, dev)
     # one row at least behind every output: an empty tensor's data_ptr is 0 and the entry refuses NULL at any count
     dQ = torch.empty((max(B, 1), d), dtype=torch.float32, device=dev)
     dT = torch.empty((max(B, 1), d), dtype=torch.float32, device=dev)
     dIc = torch.empty((max(n_cand, 1), d), dtype=torch.float32, device=dev)
-    ws, need = _softmax_workspace(dev, B, n_cand, d, cand=True)
-    lse_p = lse.data_ptr() if B else dQ.data_ptr()
-    lib = _lib.load()
-    entry = lib.sagnn_softmax_loss_cand_bwd_f32 if bias is None else lib.sagnn_softmax_loss_candb_bwd_f32
-    check(entry(*lead, lse_p, g.data_ptr(), dQ.data_ptr(), d, dIc.data_ptr(), d, dT.data_ptr(), d, ws.data_ptr(), need,
-                _stream()))
+    a.lse, a.g = lse.data_ptr() if B else dQ.data_ptr(), g.data_ptr()
+    a.dQ, a.lddq, a.dI, a.lddi, a.dT, a.lddt = dQ.data_ptr(), d, dIc.data_ptr(), d, dT.data_ptr(), d
+    _softmax_call(_lib.load().sagnn_softmax_loss_bwd_f32, a, dev, B, n_cand, d)
     return dQ[:B], dIc[:n_cand], dT[:B]
 
 

@@ -1,5 +1,5 @@
 """GPU suite of the sampled-candidate softmax loss (--softmaxNegs): the stratified draw against its numpy
-restatement, sagnn_softmax_loss_cand_f32 and its backward against the float64 restatement (softmax_cand_ref: the
+restatement, sagnn_softmax_loss_f32's candidate mode and its backward against the float64 restatement (softmax_cand_ref: the
 full-table reference with every non-candidate put on the row's list), their contracts (row independence, bit-identical
 runs, skipped rows), then the flag inside the Recommender.
 

@@ -1,5 +1,5 @@
 """GPU suite of the popularity-weighted candidate softmax (--softmaxNegDist pop): the weighted draw
-against its restatement (softmax_pop_ref.draw), sagnn_softmax_loss_candb_f32 and its backward against float64 over lists
+against its restatement (softmax_pop_ref.draw), sagnn_softmax_loss_f32's offset mode and its backward against float64 over lists
 with repeated ids, the contracts (dead rows, row independence, bit-identical runs, the zero-offset case against the
 entries without an offset), then the flag inside the Recommender.
 

@@ -29,7 +29,7 @@ def test_library_exports_every_header_symbol():
     for n in names:
         assert hasattr(lib, n), f"{n} declared in sagnn.h but not exported by libsagnn.so"
     assert sorted(_lib.SIGNATURES) == names, "ctypes SIGNATURES table out of sync with sagnn.h"
-    assert lib.sagnn_version() == 10400
+    assert lib.sagnn_version() == 10500
 
 
 def test_csr_check_errors():
@@ -385,6 +385,33 @@ def test_gnn_args_layout_matches_the_header():
     a = _gnn_args(side, (p, 60, 0, p, 64, 0, p, p), 64, 2)
     assert lib.sagnn_gnn_interval_bwd_f32(pu.handle, pi.handle, ctypes.byref(a), None) == -5
     assert "G_i: ld 60 < d 64" in _lib.last_error()
+
+
+def test_softmax_args_layout_matches_the_header():
+    """SoftmaxArgs mirrors sagnn_softmax_args field for field (names and order from the header's text), and the library
+    reads the fields where ctypes puts them: a value from the first field and one from the last come back in refusals."""
+    import softmax_args_host as H
+    text = open(os.path.join(ROOT, "include", "sagnn.h")).read()
+    body = re.search(r"typedef struct sagnn_softmax_args \{(.*?)\} sagnn_softmax_args;", text, re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    names = [n for decl in body.split(";") for n in re.findall(r"(\w+)\s*(?:,|$)", decl.strip())]
+    assert names == [n for n, _ in _lib.SoftmaxArgs._fields_] and names[0] == "Q" and names[-1] == "workspace_bytes"
+    # LP64, every member 8 bytes but d and mode (4 + 4 padding each) and the two floats (one 8-byte slot together):
+    # Q ldq I ldi n_queries n_items = 48; d = 8; target = 8; inv_temp scale = 8; excl_ptr excl_items excl_row n_lists = 32;
+    # mode = 8; cand n_cand bias = 24; loss lse tscore = 24; g dQ lddq dI lddi dT lddt = 56; workspace workspace_bytes = 16
+    assert ctypes.sizeof(_lib.SoftmaxArgs) == 48 + 8 + 8 + 8 + 32 + 8 + 24 + 24 + 56 + 16 == 232
+    assert (_lib.SOFTMAX_FULL, _lib.SOFTMAX_CAND, _lib.SOFTMAX_CAND_BIAS) == tuple(
+        int(re.search(r"SAGNN_SOFTMAX_%s = (\d+)" % n, text).group(1)) for n in ("FULL", "CAND", "CAND_BIAS"))
+
+    lib = _lib.load()
+    buf, p = H.aligned_buffer()
+    for backward in (False, True):
+        for mode in (_lib.SOFTMAX_FULL, _lib.SOFTMAX_CAND, _lib.SOFTMAX_CAND_BIAS):
+            assert H.call(lib, backward, H.softmax_args(p, mode, Q=p + 4)) == -3
+            assert "Q and I must be 16-byte aligned" in _lib.last_error()
+            assert H.call(lib, backward, H.softmax_args(p, mode, workspace_bytes=48)) == -6      # 512 are needed at least
+            assert "workspace of 48 bytes" in _lib.last_error()
+    del buf
 
 
 def test_params_match_reference_flags():

@@ -2,13 +2,12 @@
 against torch autograd, the flags, prepareModel's refusals, the argument checks of both C entries and of the ops
 wrappers (each rejected before any device work, so no GPU is needed), the workspace size, and the banned-table helper
 the device sampler and the loss share."""
-import ctypes
-
 import numpy as np
 import pytest
 import scipy.sparse as sp
 import torch
 
+import softmax_args_host as H
 import softmax_loss_ref as R
 from sa_gnn_amd import _lib, ops
 
@@ -86,25 +85,17 @@ def test_prepare_model_refuses_bad_flag_combinations(monkeypatch):
 
 
 def _fwd(lib, p, **o):
-    a = dict(Q=p, ldq=64, I=p, ldi=64, nq=8, ni=100, d=64, target=p, inv_temp=1.0, scale=0.125, ptr=None, items=None,
-             row=None, n_lists=0, loss=p, lse=p, tscore=p, ws=p, ws_bytes=1 << 30)
-    a.update(o)
-    return lib.sagnn_softmax_loss_f32(*a.values(), None)
+    return H.call(lib, False, H.softmax_args(p, _lib.SOFTMAX_FULL, **o))
 
 
 def _bwd(lib, p, **o):
-    a = dict(Q=p, ldq=64, I=p, ldi=64, nq=8, ni=100, d=64, target=p, inv_temp=1.0, scale=0.125, ptr=None, items=None,
-             row=None, n_lists=0, lse=p, g=p, dQ=p, lddq=64, dI=p, lddi=64, ws=p, ws_bytes=1 << 30)
-    a.update(o)
-    return lib.sagnn_softmax_loss_bwd_f32(*a.values(), None)
+    return H.call(lib, True, H.softmax_args(p, _lib.SOFTMAX_FULL, **o))
 
 
 @pytest.mark.parametrize("name", ["fwd", "bwd"])
 def test_both_entries_reject_every_invalid_argument_without_a_device(name):
     lib = _lib.load()
-    buf = (ctypes.c_float * 4096)()
-    p = ctypes.addressof(buf)
-    p += (-p) % 16
+    buf, p = H.aligned_buffer()
     fn = _fwd if name == "fwd" else _bwd
     cases = [
         (dict(Q=None), -1, "q or i"), (dict(I=None), -1, "q or i"), (dict(target=None), -1, "target"),
@@ -128,7 +119,28 @@ def test_both_entries_reject_every_invalid_argument_without_a_device(name):
     for over, code, text in cases:
         assert fn(lib, p, **over) == code, (name, over, _lib.last_error())
         assert text in _lib.last_error().lower(), (name, over, _lib.last_error())
-    # a valid argument set gets past the checks only with a GPU: none of the above touched one
+        assert _lib.last_error().startswith("softmax_loss_bwd: " if name == "bwd" else "softmax_loss: ")
+    del buf     # a valid argument set gets past the checks only with a GPU: none of the above touched one
+
+
+@pytest.mark.parametrize("backward", [False, True])
+def test_the_mode_is_named_by_its_field_and_a_contradiction_is_refused_without_a_device(backward):
+    """A NULL struct, a mode outside the three, and candidate fields that the mode does not take: each refused with its
+    code and a message naming the field, ahead of every other check (the struct's other fields are all NULL here)."""
+    lib = _lib.load()
+    buf, p = H.aligned_buffer()
+    F, C = _lib.SOFTMAX_FULL, _lib.SOFTMAX_CAND
+    assert H.call(lib, backward, None) == -1 and "sagnn_softmax_args is null" in _lib.last_error().lower()
+    for mode, fields, code, text in [(3, {}, -5, "mode = 3"), (-1, {}, -5, "mode = -1"),
+                                     (F, dict(cand=p), -5, "softmax_full with a cand"),
+                                     (F, dict(bias=p), -5, "softmax_full with a bias"),
+                                     (F, dict(n_cand=5), -5, "n_cand = 5"),
+                                     (C, dict(bias=p), -5, "softmax_cand with a bias")]:
+        # on a struct with nothing else set, then on an otherwise valid one
+        for args in (_lib.SoftmaxArgs(mode=mode, **fields), H.softmax_args(p, mode, **fields)):
+            assert H.call(lib, backward, args) == code, (mode, fields, _lib.last_error())
+            assert text in _lib.last_error().lower(), (mode, fields, _lib.last_error())
+    del buf
 
 
 def test_workspace_is_monotone():

@@ -2,12 +2,11 @@
 and the one combination it now lets through, the argument checks of the C entries (each rejected before any device
 work, so no GPU is needed), the workspace size, the numpy restatement of the stratified draw and its inclusion
 frequencies, and the augmented-list reference against torch float64 autograd on a direct masked logsumexp."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
+import softmax_args_host as H
 import softmax_cand_ref as C
 import softmax_loss_ref as R
 from sa_gnn_amd import _lib, ops
@@ -67,30 +66,17 @@ def test_prepare_model_refusals_and_the_combination_it_now_allows(monkeypatch):
 
 
 def _fwd(lib, p, **o):
-    a = dict(Q=p, ldq=64, I=p, ldi=64, nq=8, ni=100, d=64, cand=p, n_cand=40, target=p, inv_temp=1.0, scale=0.125, ptr=None,
-             items=None, row=None, n_lists=0, loss=p, lse=p, tscore=p, ws=p, ws_bytes=1 << 30)
-    a.update(o)
-    return lib.sagnn_softmax_loss_cand_f32(*a.values(), None)
+    return H.call(lib, False, H.softmax_args(p, _lib.SOFTMAX_CAND, **o))
 
 
 def _bwd(lib, p, **o):
-    a = dict(Q=p, ldq=64, I=p, ldi=64, nq=8, ni=100, d=64, cand=p, n_cand=40, target=p, inv_temp=1.0, scale=0.125, ptr=None,
-             items=None, row=None, n_lists=0, lse=p, g=p, dQ=p, lddq=64, dIc=p, lddic=64, dT=p, lddt=64, ws=p,
-             ws_bytes=1 << 30)
-    a.update(o)
-    return lib.sagnn_softmax_loss_cand_bwd_f32(*a.values(), None)
-
-
-def _aligned_buffer():
-    buf = (ctypes.c_float * 4096)()
-    p = ctypes.addressof(buf)
-    return buf, p + (-p) % 16
+    return H.call(lib, True, H.softmax_args(p, _lib.SOFTMAX_CAND, **o))
 
 
 @pytest.mark.parametrize("name", ["fwd", "bwd"])
 def test_both_cand_entries_reject_every_invalid_argument_without_a_device(name):
     lib = _lib.load()
-    buf, p = _aligned_buffer()
+    buf, p = H.aligned_buffer()
     fn = _fwd if name == "fwd" else _bwd
     cases = [
         (dict(Q=None), -1, "q or i"), (dict(I=None), -1, "q or i"), (dict(target=None), -1, "target"),
@@ -117,12 +103,13 @@ def test_both_cand_entries_reject_every_invalid_argument_without_a_device(name):
     for over, code, text in cases:
         assert fn(lib, p, **over) == code, (name, over, _lib.last_error())
         assert text in _lib.last_error().lower(), (name, over, _lib.last_error())
+        assert _lib.last_error().startswith("softmax_loss_cand_bwd: " if name == "bwd" else "softmax_loss_cand: ")
     del buf     # a valid argument set gets past the checks only with a GPU: none of the above touched one
 
 
 def test_sample_strata_rejects_every_invalid_argument_without_a_device():
     lib = _lib.load()
-    buf, p = _aligned_buffer()
+    buf, p = H.aligned_buffer()
     f = lib.sagnn_sample_strata_i32
     for a, code, text in [((0, 0, 1, 0, p), -5, "n_items"), ((-3, 0, 1, 0, p), -5, "n_items"), ((1 << 31, 5, 1, 0, p), -5, "n_items"),
                           ((10, -1, 1, 0, p), -5, "n_cand"), ((10, 11, 1, 0, p), -5, "n_cand"), ((10, 5, 1, 0, None), -1, "null cand")]:
@@ -139,7 +126,7 @@ def test_sample_strata_rejects_every_invalid_argument_without_a_device():
 
 def test_target_add_rejects_every_invalid_argument_without_a_device():
     lib = _lib.load()
-    buf, p = _aligned_buffer()
+    buf, p = H.aligned_buffer()
 
     def f(**o):
         a = dict(dT=p, lddt=64, target=p, nq=8, ni=100, d=64, dI=p, lddi=64)

@@ -2,12 +2,11 @@
 prepareModel's refusals, the integer item weights, the argument checks of the new C entries (each rejected before any
 device work, so no GPU is needed), and the properties of the restated draw: non-decreasing, run lengths that add up to
 n_cand, the exact expected draw count against n_cand w_i / W, and the identity list under equal weights."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
+import softmax_args_host as H
 import softmax_pop_ref as P
 from sa_gnn_amd import _lib, ops
 
@@ -108,15 +107,9 @@ def test_item_degrees_count_stored_non_zero_entries():
     assert model.item_degrees(m.tocsr(), 7).tolist() == [2, 0, 0, 2, 0, 0, 0]
 
 
-def _aligned_buffer():
-    buf = (ctypes.c_float * 4096)()
-    p = ctypes.addressof(buf)
-    return buf, p + (-p) % 16
-
-
 def test_weighted_draw_rejects_every_invalid_argument_without_a_device():
     lib = _lib.load()
-    buf, p = _aligned_buffer()
+    buf, p = H.aligned_buffer()
 
     def f(**o):
         a = dict(cum=p, ni=100, total=1 << 30, n_cand=40, seed=1, step=0, cand=p, bias=p)
@@ -139,29 +132,21 @@ def test_weighted_draw_rejects_every_invalid_argument_without_a_device():
 @pytest.mark.parametrize("name", ["fwd", "bwd"])
 def test_the_offset_entries_reject_what_the_plain_ones_do_and_a_null_bias(name):
     lib = _lib.load()
-    buf, p = _aligned_buffer()
-    base = dict(Q=p, ldq=64, I=p, ldi=64, nq=8, ni=100, d=64, cand=p, n_cand=40, bias=p, target=p, inv_temp=1.0, scale=0.125,
-                ptr=None, items=None, row=None, n_lists=0)
-    if name == "fwd":
-        base.update(loss=p, lse=p, tscore=p, ws=p, ws_bytes=1 << 30)
-        fn = lib.sagnn_softmax_loss_candb_f32
-    else:
-        base.update(lse=p, g=p, dQ=p, lddq=64, dIc=p, lddic=64, dT=p, lddt=64, ws=p, ws_bytes=1 << 30)
-        fn = lib.sagnn_softmax_loss_candb_bwd_f32
+    buf, p = H.aligned_buffer()
     for over, code, text in [(dict(bias=None), -1, "null bias"), (dict(cand=None), -1, "null cand"), (dict(Q=None), -1, "q or i"),
                              (dict(n_cand=101), -5, "n_cand"), (dict(d=48, ldq=48, ldi=48), -2, "d = 48"),
                              (dict(inv_temp=0.0), -5, "inv_temp"), (dict(ws_bytes=16), -6, "workspace"),
                              (dict(ldq=66), -3, "ldq")]:
-        a = dict(base)
-        a.update(over)
-        assert fn(*a.values(), None) == code, (over, _lib.last_error())
+        base = H.softmax_args(p, _lib.SOFTMAX_CAND_BIAS, **over)       # every field by name, the entry's own and the other's
+        assert H.call(lib, name == "bwd", base) == code, (over, _lib.last_error())
         assert text in _lib.last_error().lower() and "softmax_loss_candb" in _lib.last_error(), (over, _lib.last_error())
+        assert _lib.last_error().startswith("softmax_loss_candb_bwd: " if name == "bwd" else "softmax_loss_candb: ")
     del buf
 
 
 def test_scatter_rejects_every_invalid_argument_without_a_device():
     lib = _lib.load()
-    buf, p = _aligned_buffer()
+    buf, p = H.aligned_buffer()
 
     def f(**o):
         a = dict(dIc=p, lddic=64, cand=p, bias=p, n_cand=40, ni=100, d=64, dI=p, lddi=64)
