@@ -883,6 +883,45 @@ int sagnn_seq_pool_bwd_f32(const float* g, int64_t ldg, const int32_t* seg_len, 
                            float* dx, int64_t ldx, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Causal sequence attention and a query per prefix (seq_attn.hip; --seqAtt causal, --seqTargets all; neither is in the
+ * reference, whose head collapses the sequence into one token trained against one target, model.py:161-168). The slab
+ * layout, the padding rule, the token description and the limits are those of the block above.
+ * sagnn_seq_attn_masked_f32 / sagnn_seq_attn_masked_bwd_f32: sagnn_seq_attn_f32 / sagnn_seq_attn_bwd_f32 with a mask
+ *   choice. causal = 0: those two entries, bit for bit (they forward here). causal = 1: token j attends to tokens
+ *   0..j of its slot only: e[j, s] is defined for s <= j, a = e / (sum_{s <= j} e + 1e-8) with the row's largest score
+ *   among s <= j as the shift, ctx_j = sum_{s <= j} a[j, s] v_s (s ascending); backward dq_j over s <= j, dk_s and dv_s
+ *   over the queries j = s .. n_b - 1 (j ascending). ctx_j does not depend on any token after j, and a gradient that is
+ *   non-zero in row j alone gives exact zeros in dk_s, dv_s for s > j. No atomics, bit-identical between runs. On a
+ *   slot of one token both choices give the same bits. Any other value of causal: SAGNN_ERR_ARG.
+ * sagnn_seq_prefix_query_f32: Q[b * P + j] = max(leaky * pre, pre) + U[b] for j < n_b, pre = sum_{i <= j} x[b * P + i]
+ *   (i ascending from 0.0f: the partial sums of sagnn_seq_pool_f32, so that row n_b - 1 has the bits of
+ *   sagnn_leaky_add_f32 on that entry's output and U[b]); exact zeros in the padding, every row WRITTEN. U [n_slots, d].
+ * sagnn_seq_prefix_query_bwd_f32: dx[b * P + i] = sum_{j >= i} dQ[b * P + j] slope(pre[b, j]) (j descending from
+ *   n_b - 1), zeros in the padding, and dU[b] = sum_{j < n_b} dQ[b * P + j] (j ascending; an empty slot: zeros); both
+ *   WRITTEN. pre is recomputed by the forward's additions, slope is sagnn_leaky_f32's (leaky on ties). Padded rows of dQ
+ *   are not read. No atomics, bit-identical between runs. dx must not alias dQ.
+ * sagnn_seq_targets_i32: target[b * P + j] = seq_items[seg_begin[b] + j + 1] for j < n_b - 1, slot_target[b] for
+ *   j = n_b - 1, and -1 in the padding, in every row of a slot with slot_target[b] < 0, and for an id outside
+ *   [0, n_items) or an entry outside [0, n_flat). excl_row[b * P + j] = slot_user[b] in every row. All int32, on the
+ *   device; what sagnn_softmax_loss_f32 takes as target / excl_row for the slab as its query rows.
+ * Limits as above (d a multiple of 4 in [4, 256], 1 <= pos_length <= 256, 16-byte aligned rows, strides multiples of 4
+ *   and >= d); n_slots = 0 returns SAGNN_OK at once. One launch each on `stream`, no allocation, no synchronisation
+ *   (capturable). Profile kind 5.
+ * -------------------------------------------------------------------------------- */
+int sagnn_seq_attn_masked_f32(const float* qkv, const int32_t* seg_len, int64_t n_slots, int pos_length, int d, int heads,
+                              int causal, float* ctx, void* stream);
+int sagnn_seq_attn_masked_bwd_f32(const float* qkv, const float* g_ctx, const int32_t* seg_len, int64_t n_slots,
+                                  int pos_length, int d, int heads, int causal, float* dqkv, void* stream);
+int sagnn_seq_prefix_query_f32(const float* x, int64_t ldx, const int32_t* seg_len, const float* U, int64_t ldu,
+                               int64_t n_slots, int pos_length, int d, float leaky, float* Q, int64_t ldq, void* stream);
+int sagnn_seq_prefix_query_bwd_f32(const float* x, int64_t ldx, const int32_t* seg_len, const float* dQ, int64_t lddq,
+                                   int64_t n_slots, int pos_length, int d, float leaky, float* dx, int64_t ld_dx, float* dU,
+                                   int64_t ld_du, void* stream);
+int sagnn_seq_targets_i32(const int32_t* seq_items, int64_t n_flat, const int64_t* seg_begin, const int32_t* seg_len,
+                          const int32_t* slot_user, const int32_t* slot_target, int64_t n_slots, int pos_length,
+                          int64_t n_items, int32_t* target, int32_t* excl_row, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Additive-attention pooling of the sequence head (seq_attn.hip; --seqPool additive, not in the reference's graph: it
  * constructs AdditiveAttention(query_vector_dim, latdim), model.py:147, and comments its call out, model.py:168).
  * On the slab layout above, with u = x Wa + ba [n_slots * P, q] computed by the caller (sagnn_dense_nn_f32 over all
@@ -985,9 +1024,16 @@ size_t sagnn_softmax_loss_workspace_bytes(int64_t n_queries, int64_t n_items, in
  *   share a target added in ascending b by one thread per element (no atomics: bit-identical between runs). Meant
  *   for a batch: a thread compares its target with all n_queries. Same limits on d, n_queries, n_items, strides and
  *   alignment; one launch on `stream`, not recorded by the profile.
+ * sagnn_softmax_target_scatter_f32: the same sum, dI[target[r]] += dT[r] for every row r with a target in [0, n_items),
+ *   for row counts far beyond a batch (--seqTargets all: a row per sequence token): one thread per (row, float4 column)
+ *   and float atomics, so rows that share a target are added in no fixed order and dI is equal between runs up to the
+ *   order of summation, as sagnn_seq_gather_bwd_f32's d_fi is. Same limits (n_rows <= INT32_MAX); one launch on
+ *   `stream`, not recorded by the profile. The full-catalogue mode needs neither entry: it writes dI itself.
  * -------------------------------------------------------------------------------- */
 int sagnn_softmax_target_add_f32(const float* dT, int64_t lddt, const int32_t* target, int64_t n_queries, int64_t n_items,
                                  int d, float* dI, int64_t lddi, void* stream);
+int sagnn_softmax_target_scatter_f32(const float* dT, int64_t lddt, const int32_t* target, int64_t n_rows, int64_t n_items,
+                                     int d, float* dI, int64_t lddi, void* stream);
 int sagnn_sample_strata_i32(int64_t n_items, int64_t n_cand, uint64_t seed, uint32_t step, int32_t* cand, void* stream);
 size_t sagnn_softmax_loss_cand_workspace_bytes(int64_t n_queries, int64_t n_cand, int d);
 

@@ -83,8 +83,25 @@ _FLAGS = [
                            "item of the sequence is a token and the layers attend over the real items, padding masked; "
                            "same variables; needs latdim / num_attention_heads in {2, 4, 8} and pos_length <= 256). Not "
                            "in the reference's graph: it multiplies the mask in before the attention layers "
-                           "(model.py:161-162) and never passes attn_mask (Utils/attention.py:35-45)",
+                           "(model.py:161-162) and never passes attn_mask (Utils/attention.py:35-45). The causal form of full "
+                           "is chosen with --seqMask causal",
      ("sum", "full")),
+    ("seqMask", str, "none", "the mask of --seqAtt full's attention: none (every token of a slot attends to every token of "
+                             "the slot) or causal (a token attends to itself and the tokens before it only, what training "
+                             "on every position, --seqTargets all, needs; same variables and limits as full). --seqAtt "
+                             "full --seqMask causal selects the head form the model knows, stores in checkpoints and "
+                             "checks on load as seqAtt causal (args.seqAtt == \"causal\"), so a full checkpoint is "
+                             "refused under it and the reverse; it needs --seqAtt full. Not in the reference, which "
+                             "never passes an attention mask",
+     ("none", "causal")),
+    ("seqTargets", str, "last", "which next-item events of a slot's sequence the head trains on: last (the slot's pooled row "
+                                "against its one sampled positive, as the reference's graph computes, model.py:161-168: one "
+                                "collapsed token, one target) or all (every real token a query: the running sum of the "
+                                "tokens up to it against the item that follows it, the sampled positive after the last; as "
+                                "many loss terms as tokens, averaged; a slot with a positive and no tokens contributes "
+                                "nothing, under last it contributes one term; needs --seqAtt full --seqMask causal, --seqPool sum and "
+                                "--predLoss softmax; a training flag, not part of the model). Not in the reference",
+     ("last", "all")),
     ("seqPool", str, "sum", "how the head pools the tokens of --seqAtt full into the user's row: sum (the plain sum over "
                             "the real tokens, as the reference's graph computes) or additive (the softmax-weighted sum of "
                             "additive attention, weights from <tanh(x Wa + ba), v>; three more variables of width "
@@ -137,7 +154,12 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 def parse_args(argv=None, namespace=None):
-    ns = build_parser().parse_args([] if argv is None else argv, namespace)
+    parser = build_parser()
+    ns = parser.parse_args([] if argv is None else argv, namespace)
+    if ns.seqMask == "causal":                     # the causal form of full is the head form seqAtt "causal" (model.SEQ_ATT)
+        if ns.seqAtt not in ("full", "causal"):
+            parser.error(f"--seqMask causal needs --seqAtt full (got --seqAtt {ns.seqAtt})")
+        ns.seqAtt = "causal"
     ns.decay_step = ns.trnNum // ns.batch          # reference Params.py:53
     return ns
 

@@ -227,6 +227,17 @@ SIGNATURES = {
     "sagnn_seq_attn_bwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p]),
     "sagnn_seq_pool_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p]),
     "sagnn_seq_pool_bwd_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p]),
+    "sagnn_seq_attn_masked_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "sagnn_seq_attn_masked_bwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p,
+                                              c_void_p]),
+    "sagnn_seq_prefix_query_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_float,
+                                           c_void_p, c_int64, c_void_p]),
+    "sagnn_seq_prefix_query_bwd_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_float,
+                                               c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "sagnn_seq_targets_i32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64,
+                                      c_void_p, c_void_p, c_void_p]),
+    "sagnn_softmax_target_scatter_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64,
+                                                 c_void_p]),
     "sagnn_seq_addpool_supported": (c_int, [c_int, c_int, c_int]),
     "sagnn_seq_addpool_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
                                       c_void_p, c_int64, c_void_p, c_void_p]),

@@ -560,14 +560,17 @@ class SoftmaxLossCandFn(torch.autograd.Function):
     zeros, the candidates' rows copied to rows `cand` (distinct ids), then every slot's target row added at its target
     by ops.softmax_target_add, which orders the slots that share a target: bit-identical between runs.
     With bias (--softmaxNegDist pop: the offsets of ops.sample_strata_weighted, whose list repeats ids) the rows of the
-    live positions alone are scattered (ops.softmax_cand_scatter): their ids are distinct, so no row has two writers."""
+    live positions alone are scattered (ops.softmax_cand_scatter): their ids are distinct, so no row has two writers.
+    scatter_targets (--seqTargets all: a row per sequence token, far more than the batch softmax_target_add is meant
+    for): the target rows go through ops.softmax_target_scatter, float atomics, equal up to the order of summation."""
 
     @staticmethod
-    def forward(ctx, Q, I, cand, target, inv_temp, scale, excl, excl_row, bias=None):
+    def forward(ctx, Q, I, cand, target, inv_temp, scale, excl, excl_row, bias=None, scatter_targets=False):
         Q, I = Q.detach().contiguous(), I.detach().contiguous()
         loss, lse, _ = ops.softmax_loss_cand(Q, I, cand, target, inv_temp, scale, excl, excl_row, bias)
         ctx.save_for_backward(Q, I, cand, target, lse, *(() if bias is None else (bias,)))
         ctx.args = (inv_temp, scale, excl, excl_row)
+        ctx.scatter_targets = bool(scatter_targets)
         return loss
 
     @staticmethod
@@ -582,8 +585,11 @@ class SoftmaxLossCandFn(torch.autograd.Function):
                 dI.index_copy_(0, cand.long(), dIc)
             else:
                 ops.softmax_cand_scatter(dI, dIc, cand, bias)
-        ops.softmax_target_add(dI, dT, target)
-        return dQ, dI, None, None, None, None, None, None, None
+        if ctx.scatter_targets:
+            ops.softmax_target_scatter(dI, dT, target)
+        else:
+            ops.softmax_target_add(dI, dT, target)
+        return dQ, dI, None, None, None, None, None, None, None, None
 
 
 class ProdLeakySumFn(torch.autograd.Function):
@@ -703,16 +709,18 @@ class SeqAttnFn(torch.autograd.Function):
     gradient's are."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, Wq, bq, Wk, bk, Wv, bv, seg_len, P, heads, leaky):
+    def forward(ctx, x, gamma, beta, Wq, bq, Wk, bk, Wv, bv, seg_len, P, heads, leaky, causal=False):
         x = x.detach().contiguous()
         R, d = x.shape
         y = ops.layernorm_td(x.view(R, 1, d), gamma.detach(), beta.detach()).view(R, d)
         Wqkv = torch.cat([Wq, Wk, Wv], dim=1).detach().contiguous()
         bqkv = torch.cat([bq, bk, bv]).detach().contiguous()
         qkv = ops.dense_nn(y, Wqkv, bqkv)
-        att = ops.seq_attn(qkv, seg_len, P, heads)
+        causal = bool(causal)
+        att = ops.seq_attn(qkv, seg_len, P, heads, causal) if causal else ops.seq_attn(qkv, seg_len, P, heads)
         ctx.save_for_backward(x, qkv, gamma, beta, Wqkv, seg_len)
         ctx.cfg = (int(P), int(heads), float(leaky))
+        ctx.causal = causal
         return ops.leaky_add(att, x, leaky)
 
     @staticmethod
@@ -721,9 +729,10 @@ class SeqAttnFn(torch.autograd.Function):
         P, heads, leaky = ctx.cfg
         R, d = x.shape
         g = g.contiguous()
-        att = ops.seq_attn(qkv, seg_len, P, heads)
+        mask = (True,) if ctx.causal else ()          # the default path's calls stay what they were
+        att = ops.seq_attn(qkv, seg_len, P, heads, *mask)
         g_att = ops.leaky_bwd(att, g, leaky)
-        dqkv = ops.seq_attn_bwd(qkv, g_att, seg_len, P, heads)
+        dqkv = ops.seq_attn_bwd(qkv, g_att, seg_len, P, heads, *mask)
         y = ops.layernorm_td(x.view(R, 1, d), gamma.detach(), beta.detach()).view(R, d)     # not saved: recomputed
         # dW, db and dy as two products, not the fused tail (ops.attn_bwd_tail). This layer was written while the tail
         # returned NaN bias gradients for a workgroup whose first chunk held only zero rows (a slab's padding: any slot
@@ -733,7 +742,7 @@ class SeqAttnFn(torch.autograd.Function):
         dy = dy.view(R, 1, d)
         dy, dgamma, dbeta = ops.layernorm_td_bwd(x.view(R, 1, d), dy, gamma.detach(), out=dy)
         dx = ops.leaky_add(dy.view(R, d), g, 1.0)                                     # slope 1: dy + g, the residual's share
-        return (dx, dgamma, dbeta) + _split_qkv_grads(dWqkv, dbqkv, d) + (None, None, None, None)
+        return (dx, dgamma, dbeta) + _split_qkv_grads(dWqkv, dbqkv, d) + (None, None, None, None, None)
 
 
 class SeqPoolFn(torch.autograd.Function):
@@ -750,6 +759,25 @@ class SeqPoolFn(torch.autograd.Function):
     def backward(ctx, g):
         (seg_len,) = ctx.saved_tensors
         return ops.seq_pool_bwd(g.contiguous(), seg_len, ctx.P), None, None
+
+
+class SeqPrefixQueryFn(torch.autograd.Function):
+    """(x [n_slots * P, d], U [n_slots, d]) -> Q [n_slots * P, d]: a query per prefix of each slot's sequence
+    (--seqTargets all), Q[b, j] = leaky(sum_{i <= j} x[b, i]) + U[b] with zero rows in the padding
+    (ops.seq_prefix_query). Saved for the backward: x; the prefix sums are recomputed (ops.seq_prefix_query_bwd)."""
+
+    @staticmethod
+    def forward(ctx, x, U, seg_len, P, leaky):
+        x = x.detach().contiguous()
+        ctx.save_for_backward(x, seg_len)
+        ctx.cfg = (int(P), float(leaky))
+        return ops.seq_prefix_query(x, U.detach().contiguous(), seg_len, P, leaky)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, seg_len = ctx.saved_tensors
+        dx, dU = ops.seq_prefix_query_bwd(x, g.contiguous(), seg_len, *ctx.cfg)
+        return dx, dU, None, None, None
 
 
 class SeqAddPoolFn(torch.autograd.Function):

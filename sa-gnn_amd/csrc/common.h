@@ -16,6 +16,10 @@ int hip_fail(hipError_t e, const char* what);
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// max(leaky * a, a) + b (model.py:166): the one form sagnn_leaky_add_f32 and the prefix queries of seq_attn.hip evaluate,
+// so that the two give the same bits
+__device__ __forceinline__ float leaky_addf(float a, float b, float leaky) { return fmaxf(leaky * a, a) + b; }
+
 #define SAGNN_HIP_TRY(expr)                                   \
   do {                                                        \
     hipError_t _e = (expr);                                   \

@@ -457,8 +457,7 @@ __global__ void leaky_add_kernel(const float* __restrict__ a, const float* __res
                                  float leaky, int64_t count) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= count) return;
-  const float x = a[i];
-  out[i] = fmaxf(leaky * x, x) + (b ? b[i] : 0.f);
+  out[i] = sagnn::leaky_addf(a[i], b ? b[i] : 0.f, leaky);
 }
 
 // preds[e] = <U[uid_e], I[iid_e]> + <leaky(S[loc_e]), A[iid_e]>   (second term optional)

@@ -5,6 +5,8 @@
 // q|k|v slab and the pooling sum, plus the opt-in additive-attention pooling (--seqPool additive, §21). Layer norm, the q|k|v projection and the weight gradients between them go through
 // the row-wise entries of fusion.hip / dense.hip / attn_bwd_tail.hip on all n_slots * P rows; for that, padded rows
 // hold finite values in every activation and exact zeros in every gradient written here.
+// The attention also runs causally (--seqAtt causal: a CAUSAL template flag on its two kernels), and every prefix of a
+// slot can be a query (--seqTargets all: the prefix-query and target kernels); DESIGN.md §26.
 // Reference for the arithmetic: Utils/attention.py:35-45 with the attn_mask the reference never passes; fp32 VALU
 // under every engine.
 #include <limits.h>
@@ -136,7 +138,9 @@ __device__ __forceinline__ float row_max(const float (&q)[DK], const float* __re
 // LDS (every lane reads the same key: broadcast reads); q, the row sum and ctx stay in registers. e = exp2 of the
 // score with log2(e) / sqrt(d_k) folded into q; the contract has no max subtraction (Utils/attention.py:38-39) and
 // the shift by the row's largest score (row_max) leaves its quotient what it is.
-template <int DK>
+// CAUSAL (--seqAtt causal): query j sees keys 0..j only, so the trip counts differ per lane; the barrier
+// stays ahead of every lane-dependent branch.
+template <int DK, bool CAUSAL>
 __global__ void __launch_bounds__(kBlock) seq_attn_kernel(const float* __restrict__ qkv, const int32_t* __restrict__ seg_len,
                                                           int P, int d, float* __restrict__ ctx) {
   __shared__ __attribute__((aligned(16))) float Ks[kMaxP * DK];
@@ -169,9 +173,10 @@ __global__ void __launch_bounds__(kBlock) seq_attn_kernel(const float* __restric
     q[c] = row[c] * fold;
     acc[c] = 0.f;
   }
-  const float m = row_max<DK>(q, Ks, len);
+  const int keys = CAUSAL ? j + 1 : len;                 // j < len here
+  const float m = row_max<DK>(q, Ks, keys);
   float z = 0.f;
-  for (int s = 0; s < len; ++s) {
+  for (int s = 0; s < keys; ++s) {
     float dot = 0.f;
 #pragma unroll
     for (int c = 0; c < DK; ++c) dot = fmaf(q[c], Ks[s * DK + c], dot);
@@ -190,7 +195,8 @@ __global__ void __launch_bounds__(kBlock) seq_attn_kernel(const float* __restric
 //   dq_j = sum_s p_js k_s / sqrt(d_k),  dk_s = sum_j p_js q_j / sqrt(d_k),  dv_s = sum_j a_js g_j.
 // Pass 1, a thread per query: Z_j and ctx_j, then dq_j; the folded q, g, rz, D and the row's shift go to LDS. Pass 2, a thread per
 // key: dk_s and dv_s over the queries in ascending j. No atomics: the same bits in every run.
-template <int DK>
+// CAUSAL: pass 1 runs over the keys s <= j, pass 2 over the queries i = s .. len - 1 (the ones that see key s).
+template <int DK, bool CAUSAL>
 __global__ void __launch_bounds__(kBlock) seq_attn_bwd_kernel(const float* __restrict__ qkv, const float* __restrict__ g,
                                                               const int32_t* __restrict__ seg_len, int P, int d,
                                                               float* __restrict__ dqkv) {
@@ -229,9 +235,10 @@ __global__ void __launch_bounds__(kBlock) seq_attn_bwd_kernel(const float* __res
       gj[c] = Gs[j * DK + c];
       acc[c] = 0.f;
     }
-    const float m = row_max<DK>(q, Ks, len);
+    const int keys = CAUSAL ? j + 1 : len;
+    const float m = row_max<DK>(q, Ks, keys);
     float z = 0.f;
-    for (int s = 0; s < len; ++s) {
+    for (int s = 0; s < keys; ++s) {
       float dot = 0.f;
 #pragma unroll
       for (int c = 0; c < DK; ++c) dot = fmaf(q[c], Ks[s * DK + c], dot);
@@ -247,7 +254,7 @@ __global__ void __launch_bounds__(kBlock) seq_attn_bwd_kernel(const float* __res
     float dq[DK];
 #pragma unroll
     for (int c = 0; c < DK; ++c) dq[c] = 0.f;
-    for (int s = 0; s < len; ++s) {
+    for (int s = 0; s < keys; ++s) {
       float dot = 0.f, gv = 0.f;
 #pragma unroll
       for (int c = 0; c < DK; ++c) {
@@ -274,7 +281,7 @@ __global__ void __launch_bounds__(kBlock) seq_attn_bwd_kernel(const float* __res
   float dk[DK], dv[DK];
 #pragma unroll
   for (int c = 0; c < DK; ++c) dk[c] = dv[c] = 0.f;
-  for (int i = 0; i < len; ++i) {                        // queries in ascending order
+  for (int i = CAUSAL ? j : 0; i < len; ++i) {           // queries in ascending order
     float dot = 0.f, gv = 0.f;
 #pragma unroll
     for (int c = 0; c < DK; ++c) {
@@ -322,6 +329,91 @@ __global__ void seq_pool_bwd_kernel(const float* __restrict__ g, int64_t ldg, co
   const float4 v = j < clamp_len(seg_len, b, P) ? *reinterpret_cast<const float4*>(g + b * ldg + col)
                                                 : make_float4(0.f, 0.f, 0.f, 0.f);
   *reinterpret_cast<float4*>(dx + row * ldx + col) = v;
+}
+
+// ---- every prefix a query (--seqTargets all) --------------------------------------------------------
+// Q[b, j] = leaky(pre[b, j]) + U[b], pre[b, j] = sum_{i <= j} x[b, i] (i ascending from 0.0f: seq_pool_kernel's sum,
+// kept at every step), exact zeros in the padding. One thread per (slot, float4 column), walking j upwards.
+__global__ void seq_prefix_query_kernel(const float* __restrict__ x, int64_t ldx, const int32_t* __restrict__ seg_len,
+                                        const float* __restrict__ U, int64_t ldu, int64_t n_slots, int P, int d, float leaky,
+                                        float* __restrict__ Q, int64_t ldq) {
+  const int lpr = d >> 2;
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_slots * lpr) return;
+  const int64_t b = t / lpr;
+  const int col = (int)(t - b * lpr) * 4;
+  const int len = clamp_len(seg_len, b, P);
+  const float4 u = *reinterpret_cast<const float4*>(U + b * ldu + col);
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int j = 0; j < len; ++j) {
+    add4(acc, *reinterpret_cast<const float4*>(x + (b * P + j) * ldx + col));
+    *reinterpret_cast<float4*>(Q + (b * P + j) * ldq + col) =
+        make_float4(sagnn::leaky_addf(acc.x, u.x, leaky), sagnn::leaky_addf(acc.y, u.y, leaky),
+                    sagnn::leaky_addf(acc.z, u.z, leaky), sagnn::leaky_addf(acc.w, u.w, leaky));
+  }
+  for (int j = len; j < P; ++j) *reinterpret_cast<float4*>(Q + (b * P + j) * ldq + col) = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// the slope of max(leaky * a, a) at a, as sagnn_leaky_f32's backward form takes it: the gradient goes to leaky * a on ties
+__device__ __forceinline__ float leaky_slope(float a, float leaky) { return (a > leaky * a) ? 1.f : leaky; }
+
+// dx[b, i] = sum_{j >= i} dQ[b, j] slope(pre[b, j]), dU[b] = sum_{j < n_b} dQ[b, j]. The same thread layout. Upwards:
+// pre is rebuilt by the forward's own additions (never by subtraction, so every slope is the forward's), the term
+// dQ slope goes to dx[b, j] and dU sums in ascending j. Downwards from n_b - 1: the running suffix sum replaces the
+// terms, each read back by the thread that wrote it. One fixed order each, no atomics, zeros in the padding.
+__global__ void seq_prefix_query_bwd_kernel(const float* __restrict__ x, int64_t ldx, const int32_t* __restrict__ seg_len,
+                                            const float* __restrict__ dQ, int64_t lddq, int64_t n_slots, int P, int d,
+                                            float leaky, float* __restrict__ dx, int64_t ld_dx, float* __restrict__ dU,
+                                            int64_t ld_du) {
+  const int lpr = d >> 2;
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_slots * lpr) return;
+  const int64_t b = t / lpr;
+  const int col = (int)(t - b * lpr) * 4;
+  const int len = clamp_len(seg_len, b, P);
+  float4 pre = make_float4(0.f, 0.f, 0.f, 0.f), du = pre;
+  for (int j = 0; j < len; ++j) {
+    add4(pre, *reinterpret_cast<const float4*>(x + (b * P + j) * ldx + col));
+    const float4 g = *reinterpret_cast<const float4*>(dQ + (b * P + j) * lddq + col);
+    add4(du, g);
+    *reinterpret_cast<float4*>(dx + (b * P + j) * ld_dx + col) =
+        make_float4(g.x * leaky_slope(pre.x, leaky), g.y * leaky_slope(pre.y, leaky), g.z * leaky_slope(pre.z, leaky),
+                    g.w * leaky_slope(pre.w, leaky));
+  }
+  *reinterpret_cast<float4*>(dU + b * ld_du + col) = du;
+  float4 suf = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int j = len - 1; j >= 0; --j) {
+    float4* o = reinterpret_cast<float4*>(dx + (b * P + j) * ld_dx + col);
+    add4(suf, *o);
+    *o = suf;
+  }
+  for (int j = len; j < P; ++j) *reinterpret_cast<float4*>(dx + (b * P + j) * ld_dx + col) = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// target[b * P + j] = the item after token j of slot b (the slot's sampled positive after its last token), -1 in the
+// padding, in a slot without a positive and for an id outside [0, n_items); excl_row = the slot's user. One thread per
+// slab row.
+__global__ void seq_targets_kernel(const int32_t* __restrict__ items, int64_t n_flat, const int64_t* __restrict__ seg_begin,
+                                   const int32_t* __restrict__ seg_len, const int32_t* __restrict__ slot_user,
+                                   const int32_t* __restrict__ slot_target, int64_t n_slots, int P, int64_t n_items,
+                                   int32_t* __restrict__ target, int32_t* __restrict__ excl_row) {
+  const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= n_slots * P) return;
+  const int64_t b = row / P;
+  const int j = (int)(row - b * P);
+  const int len = clamp_len(seg_len, b, P);
+  const int32_t last = slot_target[b];
+  int64_t tgt = -1;
+  if (j < len && last >= 0) {
+    if (j == len - 1) {
+      tgt = last;
+    } else {
+      const int64_t e = seg_begin[b] + j + 1;
+      if (e >= 0 && e < n_flat) tgt = items[e];
+    }
+  }
+  target[row] = (tgt >= 0 && tgt < n_items) ? (int32_t)tgt : -1;
+  excl_row[row] = slot_user[b];
 }
 
 // ---- additive-attention pooling (--seqPool additive) ------------------------------------------------
@@ -591,10 +683,40 @@ extern "C" int sagnn_seq_gather_bwd_f32(const float* g_seq, const float* g_pos, 
   return SAGNN_OK;
 }
 
-extern "C" int sagnn_seq_attn_f32(const float* qkv, const int32_t* seg_len, int64_t n_slots, int pos_length, int d,
-                                  int heads, float* ctx, void* stream) {
+namespace {
+
+template <bool CAUSAL>
+void launch_attn(int dk, dim3 grid, unsigned threads, hipStream_t s, const float* qkv, const int32_t* seg_len, int P, int d,
+                 float* ctx) {
+  switch (dk) {
+    case 2: hipLaunchKernelGGL((seq_attn_kernel<2, CAUSAL>), grid, dim3(threads), 0, s, qkv, seg_len, P, d, ctx); break;
+    case 4: hipLaunchKernelGGL((seq_attn_kernel<4, CAUSAL>), grid, dim3(threads), 0, s, qkv, seg_len, P, d, ctx); break;
+    default: hipLaunchKernelGGL((seq_attn_kernel<8, CAUSAL>), grid, dim3(threads), 0, s, qkv, seg_len, P, d, ctx); break;
+  }
+}
+
+template <bool CAUSAL>
+void launch_attn_bwd(int dk, dim3 grid, unsigned threads, hipStream_t s, const float* qkv, const float* g,
+                     const int32_t* seg_len, int P, int d, float* dqkv) {
+  switch (dk) {
+    case 2: hipLaunchKernelGGL((seq_attn_bwd_kernel<2, CAUSAL>), grid, dim3(threads), 0, s, qkv, g, seg_len, P, d, dqkv); break;
+    case 4: hipLaunchKernelGGL((seq_attn_bwd_kernel<4, CAUSAL>), grid, dim3(threads), 0, s, qkv, g, seg_len, P, d, dqkv); break;
+    default: hipLaunchKernelGGL((seq_attn_bwd_kernel<8, CAUSAL>), grid, dim3(threads), 0, s, qkv, g, seg_len, P, d, dqkv); break;
+  }
+}
+
+int check_causal(const char* who, int causal) {
+  if (causal != 0 && causal != 1) return sagnn::fail(SAGNN_ERR_ARG, "%s: causal = %d, need 0 or 1", who, causal);
+  return SAGNN_OK;
+}
+
+}  // namespace
+
+extern "C" int sagnn_seq_attn_masked_f32(const float* qkv, const int32_t* seg_len, int64_t n_slots, int pos_length, int d,
+                                         int heads, int causal, float* ctx, void* stream) {
   const char* who = "seq_attn";
   if (!qkv || !seg_len || !ctx) return sagnn::fail(SAGNN_ERR_NULL, "%s: null pointer (qkv, seg_len, ctx)", who);
+  if (int rc = check_causal(who, causal)) return rc;
   unsigned threads = 0;
   if (int rc = check_attn(who, d, heads, pos_length, n_slots, &threads)) return rc;
   if (int rc = check_rows(who, 3 * d, 3 * (int64_t)d, qkv, "qkv")) return rc;
@@ -603,19 +725,24 @@ extern "C" int sagnn_seq_attn_f32(const float* qkv, const int32_t* seg_len, int6
   hipStream_t s = static_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)n_slots, (unsigned)heads);
   sagnn::ProfileScope prof(sagnn::kProfSeqAtt, s, n_slots, pos_length);
-  switch (d / heads) {
-    case 2: hipLaunchKernelGGL(seq_attn_kernel<2>, grid, dim3(threads), 0, s, qkv, seg_len, pos_length, d, ctx); break;
-    case 4: hipLaunchKernelGGL(seq_attn_kernel<4>, grid, dim3(threads), 0, s, qkv, seg_len, pos_length, d, ctx); break;
-    default: hipLaunchKernelGGL(seq_attn_kernel<8>, grid, dim3(threads), 0, s, qkv, seg_len, pos_length, d, ctx); break;
-  }
+  if (causal)
+    launch_attn<true>(d / heads, grid, threads, s, qkv, seg_len, pos_length, d, ctx);
+  else
+    launch_attn<false>(d / heads, grid, threads, s, qkv, seg_len, pos_length, d, ctx);
   SAGNN_HIP_TRY(hipGetLastError());
   return SAGNN_OK;
 }
 
-extern "C" int sagnn_seq_attn_bwd_f32(const float* qkv, const float* g_ctx, const int32_t* seg_len, int64_t n_slots,
-                                      int pos_length, int d, int heads, float* dqkv, void* stream) {
+extern "C" int sagnn_seq_attn_f32(const float* qkv, const int32_t* seg_len, int64_t n_slots, int pos_length, int d,
+                                  int heads, float* ctx, void* stream) {
+  return sagnn_seq_attn_masked_f32(qkv, seg_len, n_slots, pos_length, d, heads, 0, ctx, stream);
+}
+
+extern "C" int sagnn_seq_attn_masked_bwd_f32(const float* qkv, const float* g_ctx, const int32_t* seg_len, int64_t n_slots,
+                                             int pos_length, int d, int heads, int causal, float* dqkv, void* stream) {
   const char* who = "seq_attn_bwd";
   if (!qkv || !g_ctx || !seg_len || !dqkv) return sagnn::fail(SAGNN_ERR_NULL, "%s: null pointer (qkv, g_ctx, seg_len, dqkv)", who);
+  if (int rc = check_causal(who, causal)) return rc;
   unsigned threads = 0;
   if (int rc = check_attn(who, d, heads, pos_length, n_slots, &threads)) return rc;
   if (int rc = check_rows(who, 3 * d, 3 * (int64_t)d, qkv, "qkv")) return rc;
@@ -625,13 +752,17 @@ extern "C" int sagnn_seq_attn_bwd_f32(const float* qkv, const float* g_ctx, cons
   hipStream_t s = static_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)n_slots, (unsigned)heads);
   sagnn::ProfileScope prof(sagnn::kProfSeqAtt, s, n_slots, pos_length);
-  switch (d / heads) {
-    case 2: hipLaunchKernelGGL(seq_attn_bwd_kernel<2>, grid, dim3(threads), 0, s, qkv, g_ctx, seg_len, pos_length, d, dqkv); break;
-    case 4: hipLaunchKernelGGL(seq_attn_bwd_kernel<4>, grid, dim3(threads), 0, s, qkv, g_ctx, seg_len, pos_length, d, dqkv); break;
-    default: hipLaunchKernelGGL(seq_attn_bwd_kernel<8>, grid, dim3(threads), 0, s, qkv, g_ctx, seg_len, pos_length, d, dqkv); break;
-  }
+  if (causal)
+    launch_attn_bwd<true>(d / heads, grid, threads, s, qkv, g_ctx, seg_len, pos_length, d, dqkv);
+  else
+    launch_attn_bwd<false>(d / heads, grid, threads, s, qkv, g_ctx, seg_len, pos_length, d, dqkv);
   SAGNN_HIP_TRY(hipGetLastError());
   return SAGNN_OK;
+}
+
+extern "C" int sagnn_seq_attn_bwd_f32(const float* qkv, const float* g_ctx, const int32_t* seg_len, int64_t n_slots,
+                                      int pos_length, int d, int heads, float* dqkv, void* stream) {
+  return sagnn_seq_attn_masked_bwd_f32(qkv, g_ctx, seg_len, n_slots, pos_length, d, heads, 0, dqkv, stream);
 }
 
 extern "C" int sagnn_seq_pool_f32(const float* x, int64_t ldx, const int32_t* seg_len, int64_t n_slots, int pos_length,
@@ -664,6 +795,70 @@ extern "C" int sagnn_seq_pool_bwd_f32(const float* g, int64_t ldg, const int32_t
   hipStream_t s = static_cast<hipStream_t>(stream);
   sagnn::ProfileScope prof(sagnn::kProfSeqAtt, s, n_slots, pos_length);
   hipLaunchKernelGGL(seq_pool_bwd_kernel, dim3(blocks), dim3(kBlock), 0, s, g, ldg, seg_len, n_slots, pos_length, d, dx, ldx);
+  SAGNN_HIP_TRY(hipGetLastError());
+  return SAGNN_OK;
+}
+
+extern "C" int sagnn_seq_prefix_query_f32(const float* x, int64_t ldx, const int32_t* seg_len, const float* U, int64_t ldu,
+                                          int64_t n_slots, int pos_length, int d, float leaky, float* Q, int64_t ldq,
+                                          void* stream) {
+  const char* who = "seq_prefix_query";
+  if (!x || !seg_len || !U || !Q) return sagnn::fail(SAGNN_ERR_NULL, "%s: null pointer (x, seg_len, U, Q)", who);
+  if (int rc = check_slab_dims(who, d, pos_length, n_slots)) return rc;
+  if (int rc = check_rows(who, d, ldx, x, "x")) return rc;
+  if (int rc = check_rows(who, d, ldu, U, "U")) return rc;
+  if (int rc = check_rows(who, d, ldq, Q, "Q")) return rc;
+  unsigned blocks = 0;
+  if (int rc = blocks_for(who, n_slots * (d / 4), &blocks)) return rc;
+  if (blocks == 0) return SAGNN_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  sagnn::ProfileScope prof(sagnn::kProfSeqAtt, s, n_slots, pos_length);
+  hipLaunchKernelGGL(seq_prefix_query_kernel, dim3(blocks), dim3(kBlock), 0, s, x, ldx, seg_len, U, ldu, n_slots, pos_length, d,
+                     leaky, Q, ldq);
+  SAGNN_HIP_TRY(hipGetLastError());
+  return SAGNN_OK;
+}
+
+extern "C" int sagnn_seq_prefix_query_bwd_f32(const float* x, int64_t ldx, const int32_t* seg_len, const float* dQ,
+                                              int64_t lddq, int64_t n_slots, int pos_length, int d, float leaky, float* dx,
+                                              int64_t ld_dx, float* dU, int64_t ld_du, void* stream) {
+  const char* who = "seq_prefix_query_bwd";
+  if (!x || !seg_len || !dQ || !dx || !dU) return sagnn::fail(SAGNN_ERR_NULL, "%s: null pointer (x, seg_len, dQ, dx, dU)", who);
+  if (int rc = check_slab_dims(who, d, pos_length, n_slots)) return rc;
+  if (int rc = check_rows(who, d, ldx, x, "x")) return rc;
+  if (int rc = check_rows(who, d, lddq, dQ, "dQ")) return rc;
+  if (int rc = check_rows(who, d, ld_dx, dx, "dx")) return rc;
+  if (int rc = check_rows(who, d, ld_du, dU, "dU")) return rc;
+  unsigned blocks = 0;
+  if (int rc = blocks_for(who, n_slots * (d / 4), &blocks)) return rc;
+  if (blocks == 0) return SAGNN_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  sagnn::ProfileScope prof(sagnn::kProfSeqAtt, s, n_slots, pos_length);
+  hipLaunchKernelGGL(seq_prefix_query_bwd_kernel, dim3(blocks), dim3(kBlock), 0, s, x, ldx, seg_len, dQ, lddq, n_slots,
+                     pos_length, d, leaky, dx, ld_dx, dU, ld_du);
+  SAGNN_HIP_TRY(hipGetLastError());
+  return SAGNN_OK;
+}
+
+extern "C" int sagnn_seq_targets_i32(const int32_t* seq_items, int64_t n_flat, const int64_t* seg_begin, const int32_t* seg_len,
+                                     const int32_t* slot_user, const int32_t* slot_target, int64_t n_slots, int pos_length,
+                                     int64_t n_items, int32_t* target, int32_t* excl_row, void* stream) {
+  const char* who = "seq_targets";
+  if (!seq_items || !seg_begin || !seg_len || !slot_user || !slot_target || !target || !excl_row)
+    return sagnn::fail(SAGNN_ERR_NULL, "%s: null pointer (seq_items, seg_begin, seg_len, slot_user, slot_target, target, excl_row)",
+                       who);
+  if (pos_length < 1 || pos_length > kMaxP)
+    return sagnn::fail(SAGNN_ERR_DIM, "%s: pos_length = %d, need 1 <= pos_length <= %d", who, pos_length, kMaxP);
+  if (n_slots < 0) return sagnn::fail(SAGNN_ERR_ARG, "%s: negative count (n_slots = %lld)", who, (long long)n_slots);
+  if (int rc = check_tables(who, n_flat, n_items)) return rc;
+  if (n_items >= ((int64_t)1 << 31)) return sagnn::fail(SAGNN_ERR_ARG, "%s: n_items = %lld, need < 2^31", who, (long long)n_items);
+  unsigned blocks = 0;
+  if (int rc = blocks_for(who, n_slots * pos_length, &blocks)) return rc;
+  if (blocks == 0) return SAGNN_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  sagnn::ProfileScope prof(sagnn::kProfSeqAtt, s, n_slots, pos_length);
+  hipLaunchKernelGGL(seq_targets_kernel, dim3(blocks), dim3(kBlock), 0, s, seq_items, n_flat, seg_begin, seg_len, slot_user,
+                     slot_target, n_slots, pos_length, n_items, target, excl_row);
   SAGNN_HIP_TRY(hipGetLastError());
   return SAGNN_OK;
 }

@@ -721,6 +721,27 @@ __global__ __launch_bounds__(256) void cand_scatter_kernel(const float* __restri
   *reinterpret_cast<float4*>(dI + id * lddi + 4 * c) = *reinterpret_cast<const float4*>(dIc + j * lddic + 4 * c);
 }
 
+// dT into a full-size dI where the rows number far more than a batch (sagnn_softmax_target_scatter_f32, --seqTargets
+// all: every token of the slab is a row): dI[target[r]] += dT[r] with float atomics, one thread per (row, float4
+// column), the scatter of seq_gather_scatter_kernel. target_add_kernel compares every row's target with every other's.
+__global__ __launch_bounds__(256) void target_scatter_kernel(const float* __restrict__ dT, int64_t lddt,
+                                                             const int32_t* __restrict__ target, int64_t n_rows,
+                                                             int64_t n_items, int d, float* __restrict__ dI, int64_t lddi) {
+  const int per_row = d / 4;
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= n_rows * per_row) return;
+  const int64_t r = e / per_row;
+  const int c = (int)(e - r * per_row);
+  const int64_t t = target[r];
+  if (t < 0 || t >= n_items) return;
+  const float4 v = *reinterpret_cast<const float4*>(dT + r * lddt + 4 * c);
+  float* o = dI + t * lddi + 4 * c;
+  atomicAdd(o + 0, v.x);
+  atomicAdd(o + 1, v.y);
+  atomicAdd(o + 2, v.z);
+  atomicAdd(o + 3, v.w);
+}
+
 // Workspace: forward = (max, sum) per (query, chunk) then one loss term per query; backward = dQ partials per chunk.
 struct Layout {
   int64_t chunk, n_chunks;
@@ -975,6 +996,27 @@ extern "C" int sagnn_softmax_target_add_f32(const float* dT, int64_t lddt, const
   if (n_queries == 0) return SAGNN_OK;
   hipLaunchKernelGGL(target_add_kernel, dim3((unsigned)n_queries), dim3(64), 0, static_cast<hipStream_t>(stream), dT, lddt,
                      target, n_queries, n_items, d, dI, lddi);
+  SAGNN_HIP_TRY(hipGetLastError());
+  return SAGNN_OK;
+}
+
+extern "C" int sagnn_softmax_target_scatter_f32(const float* dT, int64_t lddt, const int32_t* target, int64_t n_rows,
+                                                int64_t n_items, int d, float* dI, int64_t lddi, void* stream) {
+  const char* who = "softmax_target_scatter";
+  if (!dT || !target || !dI) return sagnn::fail(SAGNN_ERR_NULL, "%s: null dT, target or dI", who);
+  if (d != 32 && d != 64 && d != 128) return sagnn::fail(SAGNN_ERR_DIM, "%s: d = %d, need 32, 64 or 128", who, d);
+  if (n_rows < 0 || n_rows > INT32_MAX) return sagnn::fail(SAGNN_ERR_ARG, "%s: n_rows = %lld", who, (long long)n_rows);
+  if (n_items < 1 || n_items >= ((int64_t)1 << 31))
+    return sagnn::fail(SAGNN_ERR_ARG, "%s: n_items = %lld, need 1 <= n_items < 2^31", who, (long long)n_items);
+  if ((lddt & 3) || (lddi & 3)) return sagnn::fail(SAGNN_ERR_ALIGN, "%s: strides lddt / lddi must be multiples of 4", who);
+  if (lddt < d || lddi < d) return sagnn::fail(SAGNN_ERR_ARG, "%s: strides lddt / lddi must be >= d", who);
+  if (!sagnn::aligned16(dT) || !sagnn::aligned16(dI))
+    return sagnn::fail(SAGNN_ERR_ALIGN, "%s: dT and dI must be 16-byte aligned", who);
+  if (n_rows == 0) return SAGNN_OK;
+  const int64_t blocks = (n_rows * (d / 4) + 255) / 256;
+  if (blocks > INT32_MAX) return sagnn::fail(SAGNN_ERR_ARG, "%s: %lld rows exceed one launch", who, (long long)n_rows);
+  hipLaunchKernelGGL(target_scatter_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), dT, lddt,
+                     target, n_rows, n_items, d, dI, lddi);
   SAGNN_HIP_TRY(hipGetLastError());
   return SAGNN_OK;
 }

@@ -23,7 +23,10 @@ from .Utils.attention import MultiHeadSelfAttention
 from .graph import NORMS, interval_pair
 
 
-SEQ_ATT = ("sum", "full")      # --seqAtt: the reference's collapsed head, or attention over every sequence item
+SEQ_ATT = ("sum", "full", "causal")   # args.seqAtt: the reference's collapsed head, attention over every sequence item, or
+                                      # that attention under a causal mask (--seqAtt full --seqMask causal, Params.parse_args)
+SEQ_TOKEN_MODES = ("full", "causal")  # the modes in which every sequence item is a token (causal: a token sees no later one)
+SEQ_TARGETS = ("last", "all")  # --seqTargets: one loss term per slot, or one per sequence token (every prefix a query)
 SEQ_POOL = ("sum", "additive")  # --seqPool: the reference's sum over the tokens, or its dead AdditiveAttention applied
 EDGE_TIME = ("none", "slot")   # --edgeTime: the reference's graph, or messages that add their edge's time-bucket row
 RNN_CELL = ("lstm", "gru")      # --rnnCell: the reference's BasicLSTMCell, or the GRU its gru_cell() is named after
@@ -281,7 +284,7 @@ class DeviceEvaluator:
         self.uids_d, self.users_d = as_dev(self.users.astype(np.int32)), as_dev(self.users)
         self.cand_d, self.target_d = as_dev(self.cand), as_dev(self.target)
         self.plans = self.tokens = None
-        if args.seqAtt == "full":
+        if args.seqAtt in SEQ_TOKEN_MODES:
             self.tokens = [Recommender._csr_tokens(rp, it, pos, device) for _, _, rp, it, pos in self.chunks]
         else:
             self.plans = [(ops.SpmmPlan(rp, it, self.batch, self.n_items, device=device, validate=False),
@@ -532,7 +535,7 @@ class Recommender:
 
     def _head_att(self, sequence, mask):
         """The head's sequence representation att [args.batch, d] (model.py:158-168) on the cached final vectors."""
-        if args.seqAtt == "full":
+        if args.seqAtt in SEQ_TOKEN_MODES:
             return self._head_att_tokens(*self._csr_tokens(*self._masked_sum_csr(sequence, mask), self.device))
         return self._head_att_plans(*self._masked_sum_plans(sequence, mask))
 
@@ -543,14 +546,17 @@ class Recommender:
         as_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
         return (as_dev(items), as_dev(pos), as_dev(rowptr[:-1].astype(np.int64)), as_dev(np.diff(rowptr).astype(np.int32)))
 
-    def _seq_att_full(self, fi, seq_items, seq_pos, seg_begin, seg_len):
-        """--seqAtt full (not in the reference's graph): att [args.batch, d] with every item of a slot's
+    def _seq_att_full(self, fi, seq_items, seq_pos, seg_begin, seg_len, pooled=True):
+        """--seqAtt full / causal (not in the reference's graph): att [args.batch, d] with every item of a slot's
         sequence a token and the att_layer attention layers run over the slot's real tokens, as the attn_mask of
         Utils/attention.py:35-45 would have it. Token j of slot b is item seq_items[seg_begin[b] + j] at position
         seq_pos[...] (None: right-aligned); activations are padded slabs [args.batch * pos_length, d]. The one place
         that builds it: differentiable in fi and the head's parameters (train_loss), and called without a graph by the
-        inference paths. Same variables as the collapsed head."""
+        inference paths. Same variables as the collapsed head. Under causal a token attends to itself and the tokens
+        before it. pooled=False returns the last layer's slab [args.batch * pos_length, d] instead of the pooled rows
+        (--seqTargets all)."""
         heads, leaky, P = args.num_attention_heads, NNs.leaky, args.pos_length
+        mask = (True,) if args.seqAtt == "causal" else ()     # full: SeqAttnFn's call stays what it was
         seq, pos = ag.SeqGatherFn.apply(fi, self.posEmbed, seq_items, seq_pos, seg_begin, seg_len)
         R, d = seq.shape
         ln = lambda x, gb: ag.LayerNormFn.apply(x.view(R, 1, d), gb[0], gb[1]).view(R, d)
@@ -558,7 +564,9 @@ class Recommender:
         for i, mh in enumerate(self.multihead_self_attention_sequence):
             w = mh.weights()
             x = ag.SeqAttnFn.apply(x, *self.head_ln[2 + i], w["Wq"], w["bq"], w["Wk"], w["bk"], w["Wv"], w["bv"], seg_len, P,
-                                   heads, leaky)
+                                   heads, leaky, *mask)
+        if not pooled:
+            return x
         if args.seqPool == "additive":
             return ag.SeqAddPoolFn.apply(x, *self.additive_attention0, seg_len, P)
         return ag.SeqPoolFn.apply(x, seg_len, P)
@@ -817,7 +825,9 @@ class Recommender:
         batch["cand_seed"] = (seed, step), default (0, 0)) under either sampler, plus each slot's own target; under
         --fusion_rows batch the candidates are marked as touched item rows. Under --softmaxNegDist pop the N candidates are
         a popularity-weighted draw with repeats (ops.sample_strata_weighted over _pop_cum_device) and batch["cand_bias"]
-        carries their logQ offsets; nothing else in the step differs."""
+        carries their logQ offsets; nothing else in the step differs.
+        Under --seqTargets all (with --seqAtt causal) the softmax loss runs on every real token of every
+        active slot instead of the slot's pooled row (_softmax_pre_loss_all); like the loss flags it is not part of the model."""
         T, L, d, heads, leaky = args.graphNum, args.gnn_layer, args.latdim, args.num_attention_heads, NNs.leaky
         keep = args.keepRate if keep_rate is None else keep_rate
         subset = args.fusion_rows == "batch"
@@ -866,15 +876,18 @@ class Recommender:
                 finals.append(ag.interval_fusion(x, p, heads, drop_scale=drop))
         fu, fi = finals
         # ---- head (model.py:156-173)
-        if args.seqAtt == "full":                                         # every sequence item a token (_seq_att_full)
+        tokens = None
+        if args.seqAtt in SEQ_TOKEN_MODES:                                # every sequence item a token (_seq_att_full)
             if "seq_seg" in batch:
                 tokens = (self._device_sampler().seq_items, None) + tuple(batch["seq_seg"])
             else:
                 tokens = self._csr_tokens(*self._masked_sum_csr(batch["sequence"], batch["mask"]), self.device)
-            att = self._seq_att_full(fi, *tokens)
+            att = self._seq_att_full(fi, *tokens, pooled=args.seqTargets != "all")       # all: the slab before pooling
         else:
             att = self._head_att_sum_train(fi, batch)
-        if args.predLoss == "softmax":
+        if args.predLoss == "softmax" and args.seqTargets == "all":
+            pre_loss = self._softmax_pre_loss_all(fu, fi, att, batch, tokens)
+        elif args.predLoss == "softmax":
             pre_loss = self._softmax_pre_loss(fu, fi, att, batch)
         else:
             preds = ag.PairScoreFn.apply(fu, fi, att, self._i32(batch["uids"]), self._i32(batch["iids"]),
@@ -914,6 +927,32 @@ class Recommender:
             return torch.from_numpy(cum).to(self.device), total
         return self._cached("_pop_cum_dev", (h.trnMat, args.item, float(args.softmaxNegPow), str(self.device)), build)
 
+    def _active_slots(self, batch):
+        """The (slot, user, target) triples of the positive half of a batch, without a read-back: device tensors (slots
+        int64, users int32, targets int32), one entry per active slot in ascending slot order, from the first pair of each
+        slot (host batch) or the pair at the slot's pair offset (device batch: batch["active"] = (slots, offsets), host
+        tables of sample_batch_device). None when no slot holds a pair."""
+        if "active" in batch:
+            slots, first = batch["active"]
+        else:
+            locs = batch["uLocs_seq"]
+            locs = locs.cpu().numpy() if isinstance(locs, torch.Tensor) else np.asarray(locs)
+            slots, first = np.unique(locs[:len(locs) // 2], return_index=True)
+        if len(slots) == 0:
+            return None
+        first = torch.as_tensor(np.asarray(first, dtype=np.int64), device=self.device)
+        slots = torch.as_tensor(np.asarray(slots, dtype=np.int64), device=self.device)
+        return slots, self._i32(batch["uids"]).index_select(0, first), self._i32(batch["iids"]).index_select(0, first)
+
+    def _slot_users_targets(self, slots, users, targets):
+        """_active_slots' triples spread over the batch's slots, as ops.seq_targets reads them: (slot_user, slot_target)
+        int32 [args.batch]; an inactive slot keeps user 0 (a valid exclusion list) and target -1 (no loss term)."""
+        slot_user = torch.zeros(args.batch, dtype=torch.int32, device=self.device)
+        slot_target = torch.full((args.batch,), -1, dtype=torch.int32, device=self.device)
+        slot_user.index_copy_(0, slots, users)
+        slot_target.index_copy_(0, slots, targets)
+        return slot_user, slot_target
+
     def _softmax_pre_loss(self, fu, fi, att, batch):
         """--predLoss softmax: (1 / max(n_active, 1)) * sum over the active slots b of ln sum_{i in E_b} exp(z_bi) - z_{b,t_b}
         with z_bi = <leaky(att[b]) + fu[u_b], fi[i]> / softmaxTemp and E_b = every item outside user u_b's banned list
@@ -923,25 +962,40 @@ class Recommender:
         With batch["cand"] (--softmaxNegs, drawn by train_loss) E_b is the candidates outside the banned list plus t_b;
         with batch["cand_bias"] (--softmaxNegDist pop) candidate position j adds cand_bias[j] to its logit, which makes
         the sum an estimator of the full-catalogue one, and a position at -inf does not count."""
-        dev = self.device
-        if "active" in batch:
-            slots, first = batch["active"]
-        else:
-            locs = batch["uLocs_seq"]
-            locs = locs.cpu().numpy() if isinstance(locs, torch.Tensor) else np.asarray(locs)
-            slots, first = np.unique(locs[:len(locs) // 2], return_index=True)
-        if len(slots) == 0:
+        active = self._active_slots(batch)
+        if active is None:
             return att.sum().reshape(1) * 0.0
-        first = torch.as_tensor(np.asarray(first, dtype=np.int64), device=dev)
-        slots = torch.as_tensor(np.asarray(slots, dtype=np.int64), device=dev)
-        u = self._i32(batch["uids"]).index_select(0, first)
-        t = self._i32(batch["iids"]).index_select(0, first)
+        slots, u, t = active
         q = ag.LeakyAddFn.apply(att.index_select(0, slots), fu.index_select(0, u.long()), NNs.leaky)
         scale = 1.0 / max(int(slots.numel()), 1)
         if "cand" in batch:     # --softmaxNegs: E_b = the step's candidates outside the banned list, plus the target
             return ag.SoftmaxLossCandFn.apply(q, fi, batch["cand"], t, 1.0 / args.softmaxTemp, scale,
                                               self._banned_device(), u, batch.get("cand_bias"))
         return ag.SoftmaxLossFn.apply(q, fi, t, 1.0 / args.softmaxTemp, scale, self._banned_device(), u)
+
+    def _softmax_pre_loss_all(self, fu, fi, x, batch, tokens):
+        """--seqTargets all: _softmax_pre_loss with every real token of every active slot a query. x is
+        the last attention layer's slab [args.batch * pos_length, d] under --seqAtt causal, tokens the batch's token arrays.
+        Row (b, j) is q = leaky(sum_{i <= j} x[b, i]) + fu[u_b] (ag.SeqPrefixQueryFn) against the item after token j, the
+        slot's sampled positive after the last token (ops.seq_targets); its eligible set is user u_b's, as under last.
+        preLoss = the sum of the rows' terms over their count. The count stays on the device: the loss entries run with
+        scale 1 and the sum is divided by a device scalar, which the backward hands them as their upstream gradient. A
+        slot with a positive and no tokens has no row."""
+        P = args.pos_length
+        active = self._active_slots(batch)
+        if active is None:
+            return x.sum().reshape(1) * 0.0
+        slot_user, slot_target = self._slot_users_targets(*active)
+        seq_items, _, seg_begin, seg_len = tokens
+        target, excl_row = ops.seq_targets(seq_items, seg_begin, seg_len, slot_user, slot_target, P, args.item)
+        q = ag.SeqPrefixQueryFn.apply(x, fu.index_select(0, slot_user.long()), seg_len, P, NNs.leaky)
+        count = (target >= 0).sum().clamp(min=1).to(torch.float32)
+        if "cand" in batch:
+            total = ag.SoftmaxLossCandFn.apply(q, fi, batch["cand"], target, 1.0 / args.softmaxTemp, 1.0, self._banned_device(),
+                                               excl_row, batch.get("cand_bias"), True)
+        else:
+            total = ag.SoftmaxLossFn.apply(q, fi, target, 1.0 / args.softmaxTemp, 1.0, self._banned_device(), excl_row)
+        return total / count
 
     def _head_att_sum_train(self, fi, batch):
         """The reference's collapsed head (--seqAtt sum) as autograd nodes: the masked sums make ONE token per slot and
@@ -1266,6 +1320,19 @@ class Recommender:
             raise ValueError(f"--seqAtt {args.seqAtt}: one of {SEQ_ATT}")
         if args.seqPool not in SEQ_POOL:
             raise ValueError(f"--seqPool {args.seqPool}: one of {SEQ_POOL}")
+        if args.seqTargets not in SEQ_TARGETS:
+            raise ValueError(f"--seqTargets {args.seqTargets}: one of {SEQ_TARGETS}")
+        if args.seqTargets == "all":       # refused before any forward, naming the flag that is missing
+            if args.seqAtt != "causal":
+                raise ValueError(f"--seqTargets all needs --seqAtt causal (--seqAtt full --seqMask causal on the command line; "
+                                 f"got --seqAtt {args.seqAtt}): under bidirectional "
+                                 "attention a prefix's row has seen its own target")
+            if args.seqPool != "sum":
+                raise ValueError(f"--seqTargets all needs --seqPool sum (got --seqPool {args.seqPool}): the prefix queries "
+                                 "are running sums of the token rows")
+            if args.predLoss != "softmax":
+                raise ValueError(f"--seqTargets all needs --predLoss softmax (got --predLoss {args.predLoss}): the prefixes "
+                                 "have no sampled negatives for the hinge loss")
         if args.predLoss not in PRED_LOSS:
             raise ValueError(f"--predLoss {args.predLoss}: one of {PRED_LOSS}")
         if args.rnnCell not in RNN_CELL:
@@ -1307,8 +1374,8 @@ class Recommender:
             if args.latdim not in (32, 64, 128):
                 raise ValueError(f"--predLoss softmax needs latdim in (32, 64, 128), got {args.latdim}")
         if args.seqPool == "additive":     # refused before any forward; ahead of --seqAtt full, whose limits it shares
-            if args.seqAtt != "full":
-                raise ValueError("--seqPool additive needs --seqAtt full: under --seqAtt sum a slot holds one token, the "
+            if args.seqAtt not in SEQ_TOKEN_MODES:
+                raise ValueError("--seqPool additive needs --seqAtt full or causal: under --seqAtt sum a slot holds one token, the "
                                  "softmax over it is 1 and the pooling is the identity")
             why = ops.seq_addpool_supported(args.latdim, args.query_vector_dim, args.pos_length)
             if why is not None:
@@ -1316,10 +1383,10 @@ class Recommender:
             if args.latdim % 32 or args.query_vector_dim % 32:       # the projection and its gradients: the dense entries
                 raise ValueError(f"--seqPool additive needs latdim and query_vector_dim to be multiples of 32, got "
                                  f"{args.latdim} and {args.query_vector_dim}")
-        if args.seqAtt == "full":          # refused before any forward: the attention kernels take these shapes only
+        if args.seqAtt in SEQ_TOKEN_MODES:  # refused before any forward: the attention kernels take these shapes only
             why = ops.seq_attn_supported(args.latdim, args.num_attention_heads, args.pos_length)
             if why is not None:
-                raise ValueError(f"--seqAtt full is not available for this configuration: {why}")
+                raise ValueError(f"--seqAtt {args.seqAtt} is not available for this configuration: {why}")
         NNs.reset(self.device)
         NNs.leaky = args.leaky
         self.actFunc = "leakyRelu"

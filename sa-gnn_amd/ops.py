@@ -1780,6 +1780,17 @@ def softmax_target_add(dI: torch.Tensor, dT: torch.Tensor, target: torch.Tensor)
     return dI
 
 
+def softmax_target_scatter(dI: torch.Tensor, dT: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    """softmax_target_add for row counts far beyond a batch (sagnn_softmax_target_scatter_f32, --seqTargets all): the same
+    sum dI[target[r]] += dT[r] in place, with float atomics, so equal between runs up to the order of summation."""
+    B, d = int(dT.shape[0]), int(dT.shape[1])
+    _one_device(dI, dT=dT, target=target)
+    check(_lib.load().sagnn_softmax_target_scatter_f32(dT.data_ptr() if B else dI.data_ptr(), _f32_rows("dT", dT, d) if B else d,
+                                                       _idx_ptr("target", target, torch.int32, B), B, int(dI.shape[0]), d,
+                                                       dI.data_ptr(), _f32_rows("dI", dI, d), _stream()))
+    return dI
+
+
 def candidate_rank(U: torch.Tensor, I: torch.Tensor, uids: torch.Tensor, cand: torch.Tensor, target: torch.Tensor,
                    S: torch.Tensor | None = None, A: torch.Tensor | None = None, leaky: float = 1.0,
                    want_scores: bool = False):
@@ -2026,21 +2037,40 @@ def _slab_rows(name: str, t: torch.Tensor, cols: int, rows: int) -> int:
     return t.data_ptr()
 
 
-def seq_attn(qkv: torch.Tensor, seg_len: torch.Tensor, pos_length: int, heads: int):
+def _causal_flag(causal) -> int:
+    if causal not in (False, True, 0, 1):
+        raise ValueError(f"causal = {causal!r}: need a bool")
+    return int(causal)
+
+
+def seq_attn(qkv: torch.Tensor, seg_len: torch.Tensor, pos_length: int, heads: int, causal: bool = False):
     """The ragged attention over each slot's real tokens (sagnn_seq_attn_f32): qkv [n_slots * P, 3d] contiguous ->
-    ctx [n_slots * P, d], zero rows in the padding."""
+    ctx [n_slots * P, d], zero rows in the padding. causal=True (sagnn_seq_attn_masked_f32, --seqAtt causal): token j
+    attends to tokens 0..j of its slot only."""
     n, P, d = int(seg_len.numel()), int(pos_length), int(qkv.shape[1]) // 3
     ctx = torch.empty((n * P, d), dtype=torch.float32, device=qkv.device)
+    if _causal_flag(causal):
+        check(_lib.load().sagnn_seq_attn_masked_f32(_slab_rows("qkv", qkv, 3 * d, n * P),
+                                                    _idx_ptr("seg_len", seg_len, torch.int32), n, P, d, int(heads), 1,
+                                                    ctx.data_ptr(), _stream()))
+        return ctx
     check(_lib.load().sagnn_seq_attn_f32(_slab_rows("qkv", qkv, 3 * d, n * P), _idx_ptr("seg_len", seg_len, torch.int32), n, P,
                                          d, int(heads), ctx.data_ptr(), _stream()))
     return ctx
 
 
-def seq_attn_bwd(qkv: torch.Tensor, g_ctx: torch.Tensor, seg_len: torch.Tensor, pos_length: int, heads: int):
-    """(qkv, g_ctx [n_slots * P, d]) -> dqkv [n_slots * P, 3d] (sagnn_seq_attn_bwd_f32): zero rows in the padding,
-    bit-identical between runs."""
+def seq_attn_bwd(qkv: torch.Tensor, g_ctx: torch.Tensor, seg_len: torch.Tensor, pos_length: int, heads: int,
+                 causal: bool = False):
+    """(qkv, g_ctx [n_slots * P, d]) -> dqkv [n_slots * P, 3d] (sagnn_seq_attn_bwd_f32; causal=True:
+    sagnn_seq_attn_masked_bwd_f32): zero rows in the padding, bit-identical between runs."""
     n, P, d = int(seg_len.numel()), int(pos_length), int(qkv.shape[1]) // 3
     dqkv = torch.empty((n * P, 3 * d), dtype=torch.float32, device=qkv.device)
+    if _causal_flag(causal):
+        check(_lib.load().sagnn_seq_attn_masked_bwd_f32(_slab_rows("qkv", qkv, 3 * d, n * P),
+                                                        _slab_rows("g_ctx", g_ctx, d, n * P),
+                                                        _idx_ptr("seg_len", seg_len, torch.int32), n, P, d, int(heads), 1,
+                                                        dqkv.data_ptr(), _stream()))
+        return dqkv
     check(_lib.load().sagnn_seq_attn_bwd_f32(_slab_rows("qkv", qkv, 3 * d, n * P), _slab_rows("g_ctx", g_ctx, d, n * P),
                                              _idx_ptr("seg_len", seg_len, torch.int32), n, P, d, int(heads), dqkv.data_ptr(),
                                              _stream()))
@@ -2063,6 +2093,49 @@ def seq_pool_bwd(g: torch.Tensor, seg_len: torch.Tensor, pos_length: int):
     check(_lib.load().sagnn_seq_pool_bwd_f32(g.data_ptr(), _f32_rows("g", g, d, n), _idx_ptr("seg_len", seg_len, torch.int32),
                                              n, P, d, dx.data_ptr(), d, _stream()))
     return dx
+
+
+# ---- a query per prefix of the sequence (seq_attn.hip; --seqTargets all) ------------------------------------------
+def seq_prefix_query(x: torch.Tensor, U: torch.Tensor, seg_len: torch.Tensor, pos_length: int, leaky: float):
+    """Q[b * P + j] = max(leaky * pre, pre) + U[b], pre = the sum of slot b's token rows 0..j of x [n_slots * P, d]
+    (sagnn_seq_prefix_query_f32) -> [n_slots * P, d], zero rows in the padding. U [n_slots, d]. The slot's last real row
+    has the bits of leaky_add(seq_pool(x), U, leaky)."""
+    n, P, d = int(seg_len.numel()), int(pos_length), int(x.shape[1])
+    _one_device(x, U=U, seg_len=seg_len)
+    Q = torch.empty((n * P, d), dtype=torch.float32, device=x.device)
+    check(_lib.load().sagnn_seq_prefix_query_f32(x.data_ptr(), _f32_rows("x", x, d, n * P),
+                                                 _idx_ptr("seg_len", seg_len, torch.int32), U.data_ptr(),
+                                                 _f32_rows("U", U, d, n), n, P, d, float(leaky), Q.data_ptr(), d, _stream()))
+    return Q
+
+
+def seq_prefix_query_bwd(x: torch.Tensor, dQ: torch.Tensor, seg_len: torch.Tensor, pos_length: int, leaky: float):
+    """Gradients of seq_prefix_query (sagnn_seq_prefix_query_bwd_f32): (dx [n_slots * P, d] with zero rows in the padding,
+    dU [n_slots, d]); no atomics, bit-identical between runs."""
+    n, P, d = int(seg_len.numel()), int(pos_length), int(x.shape[1])
+    _one_device(x, dQ=dQ, seg_len=seg_len)
+    dx = torch.empty((n * P, d), dtype=torch.float32, device=x.device)
+    dU = torch.empty((n, d), dtype=torch.float32, device=x.device)
+    check(_lib.load().sagnn_seq_prefix_query_bwd_f32(x.data_ptr(), _f32_rows("x", x, d, n * P),
+                                                     _idx_ptr("seg_len", seg_len, torch.int32), dQ.data_ptr(),
+                                                     _f32_rows("dQ", dQ, d, n * P), n, P, d, float(leaky), dx.data_ptr(), d,
+                                                     dU.data_ptr(), d, _stream()))
+    return dx, dU
+
+
+def seq_targets(seq_items: torch.Tensor, seg_begin: torch.Tensor, seg_len: torch.Tensor, slot_user: torch.Tensor,
+                slot_target: torch.Tensor, pos_length: int, n_items: int):
+    """The next-item target of every slab row (sagnn_seq_targets_i32): target[b * P + j] = the item after token j of slot
+    b, slot_target[b] after its last token, -1 in the padding, in a slot with slot_target[b] < 0 and for an id outside
+    [0, n_items); excl_row[b * P + j] = slot_user[b]. All int32 device tensors; returns (target, excl_row), [n_slots * P]."""
+    n, P = int(seg_len.numel()), int(pos_length)
+    items, n_flat, _, beg, ln, _ = _seq_tokens(seq_items, None, seg_begin, seg_len)
+    _one_device(seq_items, seg_begin=seg_begin, seg_len=seg_len, slot_user=slot_user, slot_target=slot_target)
+    target, excl_row = _out(n * P, torch.int32, seg_len.device), _out(n * P, torch.int32, seg_len.device)
+    check(_lib.load().sagnn_seq_targets_i32(items, n_flat, beg, ln, _idx_ptr("slot_user", slot_user, torch.int32, n),
+                                            _idx_ptr("slot_target", slot_target, torch.int32, n), n, P, int(n_items),
+                                            target.data_ptr(), excl_row.data_ptr(), _stream()))
+    return target, excl_row
 
 
 # ---- additive-attention pooling of the sequence head (seq_attn.hip; --seqPool additive) ----------------------------

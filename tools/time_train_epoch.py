@@ -15,7 +15,9 @@ the additive variables, every timed epoch from the initial parameters, and repor
 combine with --fusion_rows batch; with --predLoss both it is a third loss beside the hinge loss and the full-catalogue
 softmax (which then runs under --fusion_rows all only). --softmaxNegDist pop draws those candidates by popularity with
 the logQ offsets; both alternates the uniform and the weighted draw as two losses. --sampler restricts the run to one
-sampler."""
+sampler. --seqAtt causal runs the token head with causal attention; with it --seqTargets all trains every sequence
+position (it needs --predLoss softmax) and both alternates the two target modes; the loss terms per step of every softmax
+configuration are reported beside the loss entries' device time."""
 import argparse
 import ctypes
 import sys
@@ -56,8 +58,11 @@ def main():
                     help="fusion mode(s) to time; both alternates them in one process")
     ap.add_argument("--edge_keep", type=float, default=1.0,
                     help="--edgeKeepRate of the run: below 1 the training steps drop edges of the interval graphs")
-    ap.add_argument("--seqAtt", choices=("sum", "full", "both"), default="sum",
-                    help="the head's form(s) to time; both alternates them in one process")
+    ap.add_argument("--seqAtt", choices=("sum", "full", "causal", "both"), default="sum",
+                    help="the head's form(s) to time; both alternates sum and full in one process")
+    ap.add_argument("--seqTargets", choices=("last", "all", "both"), default="last",
+                    help="the positions the head trains on (all needs --seqAtt causal and --predLoss softmax); both "
+                         "alternates them in one process")
     ap.add_argument("--predLoss", choices=("hinge", "softmax", "both"), default="hinge",
                     help="the head's training loss(es) to time; both alternates them in one process")
     ap.add_argument("--seqPool", choices=("sum", "additive", "both"), default="sum",
@@ -70,6 +75,8 @@ def main():
     opt = ap.parse_args()
     if opt.seqPool != "sum" and opt.seqAtt == "sum":
         opt.seqAtt = "full"
+    if opt.seqTargets != "last" and (opt.seqAtt != "causal" or opt.predLoss != "softmax" or opt.seqPool != "sum"):
+        sys.exit(f"--seqTargets {opt.seqTargets} needs --seqAtt causal, --predLoss softmax and --seqPool sum")
     h = gowalla_shaped_handler()
     args.edgeKeepRate = opt.edge_keep
     rec = Recommender(torch.device("cuda:0"), h)
@@ -84,7 +91,8 @@ def main():
     if opt.epoch_only:
         args.sampler = "device"
         args.fusion_rows = "batch" if opt.fusion_rows == "batch" else "all"
-        args.seqAtt = "full" if opt.seqAtt == "full" else "sum"
+        args.seqAtt = opt.seqAtt if opt.seqAtt in ("full", "causal") else "sum"
+        args.seqTargets = "all" if opt.seqTargets == "all" else "last"
         args.predLoss = "softmax" if opt.predLoss == "softmax" else "hinge"
         args.softmaxNegs = opt.softmaxNegs if args.predLoss == "softmax" else 0
         args.softmaxNegDist = "pop" if opt.softmaxNegDist == "pop" and args.softmaxNegs else "uniform"
@@ -93,7 +101,7 @@ def main():
             rec.trainEpoch()
         torch.cuda.synchronize()
         print(f"two device-sampler epochs done (--fusion_rows {args.fusion_rows}, --edge_keep {args.edgeKeepRate}, "
-              f"--seqAtt {args.seqAtt}, --seqPool {args.seqPool}, --predLoss {args.predLoss}, --softmaxNegs {args.softmaxNegs}, "
+              f"--seqAtt {args.seqAtt}, --seqTargets {args.seqTargets}, --seqPool {args.seqPool}, --predLoss {args.predLoss}, --softmaxNegs {args.softmaxNegs}, "
               f"--softmaxNegDist {args.softmaxNegDist}); "
               "every parameter finite:",
               all(bool(torch.isfinite(p).all()) for p in NNs.params.values()))
@@ -110,12 +118,16 @@ def main():
     if "softmax" in losses and modes == ("batch",):
         sys.exit("--predLoss softmax does not combine with --fusion_rows batch without --softmaxNegs")
     samplers = ("host", "device") if opt.sampler == "both" else (opt.sampler,)
-    configs = [(sampler, mode, att, loss, pool) for loss in losses for att in atts for pool in pools for mode in modes
-               for sampler in samplers if (att == "full" or pool == "sum") and not (loss == "softmax" and mode == "batch")]
+    tgts = ("last", "all") if opt.seqTargets == "both" else (opt.seqTargets,)
+    tokens = ("full", "causal")                            # the head forms in which every sequence item is a token
+    configs = [(sampler, mode, att, loss, pool, tgt) for loss in losses for att in atts for pool in pools for tgt in tgts
+               for mode in modes for sampler in samplers
+               if (att in tokens or pool == "sum") and not (loss == "softmax" and mode == "batch")]
     label = lambda c: ", ".join([c[0]] + ([f"{c[1]} rows"] if len(modes) > 1 else []) +   # noqa: E731
                                 ([f"seqAtt {c[2]}"] if atts != ("sum",) else []) +
                                 ([f"seqPool {c[4]}"] if pools != ("sum",) else []) +
-                                ([f"predLoss {c[3]}"] if losses != ("hinge",) else []))
+                                ([f"predLoss {c[3]}"] if losses != ("hinge",) else []) +
+                                ([f"seqTargets {c[5]}"] if tgts != ("last",) else []))
 
     initial = {k: p.detach().clone() for k, p in NNs.params.items()}
     finite = {}
@@ -127,11 +139,11 @@ def main():
         # forms every timed epoch is therefore the first epoch of its own training (profiles/seq_att_epoch.txt holds a
         # parent-commit run that shows the default path's divergence). A run without --seqAtt both keeps training its
         # parameters as before, so its lines, not a `both` run's sum lines, are what compares with an earlier commit.
-        args.sampler, args.fusion_rows, args.seqAtt, loss, args.seqPool = c
+        args.sampler, args.fusion_rows, args.seqAtt, loss, args.seqPool, args.seqTargets = c
         args.predLoss = "hinge" if loss == "hinge" else "softmax"
         args.softmaxNegs = opt.softmaxNegs if loss in cand_losses else 0
         args.softmaxNegDist = "pop" if loss == negs_pop else "uniform"
-        if fresh and len(atts) * len(losses) * len(pools) > 1:
+        if fresh and len(atts) * len(losses) * len(pools) * len(tgts) > 1:
             with torch.no_grad():
                 for k, p in NNs.params.items():
                     p.copy_(initial[k])
@@ -204,9 +216,10 @@ def main():
             tu, ti = np.mean(np.asarray(touched[c], dtype=np.float64), axis=0)
             print(f"[{label(c)}] touched rows per step (mean of {len(touched[c])}): users {tu:.1f} of {args.user} "
                   f"({100 * tu / args.user:.2f} %), items {ti:.1f} of {args.item} ({100 * ti / args.item:.2f} %)")
-    for pool in pools if "full" in atts else ():   # device time of the sequence-attention entries (kind 5), one device-sampler epoch
+    # device time of the sequence-attention entries (kind 5), one device-sampler epoch per token form, pooling and target mode
+    for att, pool, tgt in [(a, po, t) for a in atts if a in tokens for po in pools for t in tgts]:
         lib = ops._lib.load()
-        use(("device", modes[0], "full", losses[0], pool), fresh=True)
+        use(("device", modes[0], att, losses[0], pool, tgt), fresh=True)
         cap = 4096 * steps
         lib.sagnn_profile_enable(cap)
         rec.trainEpoch()
@@ -214,24 +227,38 @@ def main():
         ops.check(lib.sagnn_profile_read(ms.ctypes.data, kind.ctypes.data, None, None, cap, ctypes.byref(n)))
         lib.sagnn_profile_enable(0)
         sel = kind[:n.value] == 5
-        print(f"[device, seqAtt full{', seqPool ' + pool if pools != ('sum',) else ''}] sequence-attention entries (gather, attention, pool and their backwards): "
+        print(f"[device, seqAtt {att}{', seqPool ' + pool if pools != ('sum',) else ''}{', seqTargets ' + tgt if tgts != ('last',) else ''}] "
+              f"sequence-attention entries (gather, attention, pool or prefix queries and their backwards): "
               f"{int(sel.sum()) / steps:.0f} calls and {float(ms[:n.value][sel].sum()) / steps:.3f} ms of device time per step; "
               f"layer-norm entries (profile kind 3): {float(ms[:n.value][kind[:n.value] == 3].sum()) / steps:.3f} ms per step")
         print("every parameter finite after that epoch:", all(bool(torch.isfinite(p).all()) for p in NNs.params.values()))
     # device time of the softmax-loss entries (kind 6; 7 over candidates), one device-sampler epoch per loss and mode
-    for loss, mode in [(lo, m) for lo in losses for m in modes if lo != "hinge" and not (lo == "softmax" and m == "batch")]:
+    for loss, mode, tgt in [(lo, m, t) for lo in losses for m in modes for t in tgts
+                            if lo != "hinge" and not (lo == "softmax" and m == "batch")]:
         lib = ops._lib.load()
-        use(("device", mode, atts[0], loss, pools[0] if atts[0] == "full" else "sum"), fresh=True)
+        use(("device", mode, atts[0], loss, pools[0] if atts[0] in tokens else "sum", tgt), fresh=True)
         cap = 4096 * steps
+        terms, entries = [], {k: getattr(ops, k) for k in ("softmax_loss", "softmax_loss_cand")}
+
+        def counted(fn, at):           # the loss terms of a call: its rows with a target (a read-back of this tool's own)
+            def call(*a, **k):
+                terms.append(int((a[at] >= 0).sum()))
+                return fn(*a, **k)
+            return call
+        ops.softmax_loss, ops.softmax_loss_cand = counted(entries["softmax_loss"], 2), counted(entries["softmax_loss_cand"], 3)
         lib.sagnn_profile_enable(cap)
-        rec.trainEpoch()
+        try:
+            rec.trainEpoch()
+        finally:
+            ops.softmax_loss, ops.softmax_loss_cand = entries["softmax_loss"], entries["softmax_loss_cand"]
         ms, kind, n = np.zeros(cap, np.float32), np.zeros(cap, np.int32), ctypes.c_int(0)
         ops.check(lib.sagnn_profile_read(ms.ctypes.data, kind.ctypes.data, None, None, cap, ctypes.byref(n)))
         lib.sagnn_profile_enable(0)
         sel = np.flatnonzero(kind[:n.value] == (7 if loss in cand_losses else 6))
-        print(f"[device, {mode} rows, predLoss {loss}] softmax-loss entries: {len(sel) / steps:.0f} calls per step; forward "
+        print(f"[device, {mode} rows, predLoss {loss}{', seqTargets ' + tgt if tgts != ('last',) else ''}] softmax-loss entries: "
+              f"{len(sel) / steps:.0f} calls per step; forward "
               f"{float(ms[sel[0::2]].sum()) / steps:.3f} ms and backward {float(ms[sel[1::2]].sum()) / steps:.3f} ms of device "
-              f"time per step")
+              f"time per step; loss terms per step {np.mean(terms):.1f}")
     print("every parameter finite after every timed epoch above:", finite)
     args.fusion_rows = "all"
     args.predLoss = "hinge"
@@ -240,6 +267,7 @@ def main():
     args.sampler = "host"
     args.seqAtt = "sum"
     args.seqPool = "sum"
+    args.seqTargets = "last"
     t0 = time.perf_counter()
     res = rec.testEpoch()
     torch.cuda.synchronize()
