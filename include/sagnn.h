@@ -972,7 +972,10 @@ int sagnn_seq_addpool_bwd_f32(const float* x, int64_t ldx, const float* u, int64
  *   addresses. An excl_row value outside [0, n_lists) means an empty list. All three pointers NULL: no exclusions
  *   (excl_ptr and excl_items go together, excl_row needs them).
  * A target outside [0, n_items) (the model passes -1) skips the row: its loss term, lse[b] and tscore[b] are 0, its dQ
- *   row is 0 and it adds nothing to dI.
+ *   row is 0 and it adds nothing to dI. The row's Q values must still be FINITE (any finite value, +-FLT_MAX included,
+ *   gives the bits of a zero row in every output): the backward's dI product takes the row against a zero factor, and
+ *   an infinity or a NaN there makes every dI row NaN, in all three modes. The model's slab meets this by construction:
+ *   sagnn_seq_prefix_query_f32 writes exact zeros into the padding, and an inactive slot's rows are finite queries.
  * sagnn_softmax_loss_bwd_f32: given lse as the forward wrote it and the upstream scalar g (DEVICE float [1]), with
  *   g(b, i) = g * scale * inv_temp * (p(b, i) - [i == target[b]]), p = exp(z - lse[b]) on eligible items and 0 elsewhere,
  *   dQ[b] = sum_i g(b, i) I[i] and dI[i] = sum_b g(b, i) Q[b]. The logits are recomputed, never stored. Every row of

@@ -27,6 +27,8 @@ def touched_sources(batch, P=None, seq_items=None):
     else:
         seq, mask = np.asarray(batch["sequence"], dtype=np.int64), np.asarray(batch["mask"]) != 0
         items["sequence"] = seq[mask]
+    if "cand" in batch:                                   # --softmaxNegs: the step's candidate rows
+        items["cand"] = _ids(batch["cand"])
     return {"users": users, "items": items}
 
 

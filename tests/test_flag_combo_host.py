@@ -14,8 +14,10 @@ import torch
 import edge_time_ref as ET
 import flag_combo_ref as C
 import seq_att_ref as SA
+import seq_causal_ref as SC
 import seq_pool_ref as SP
 import softmax_loss_ref as SL
+import softmax_pop_ref as POP
 from oracle import selfgnn_oracle as O
 
 
@@ -52,17 +54,22 @@ def host_batch(letters, rec, handler, args):
     batch = _batch(rec, handler, args)
     if "E" in letters:
         batch["edge_seed"] = C.EDGE_SEED
+    if "K" in letters:
+        batch["cand_seed"] = C.CAND_SEED
     obatch = dict(batch)
     if "D" in letters:
-        dev, full = C.output_drop(letters, batch, args.user, args.item, args.graphNum, args.latdim)
+        cand = C.step_candidates(letters, handler, args.item)[0]          # under B the candidates are touched rows too
+        rows_of = batch if cand is None else dict(batch, cand=cand)
+        dev, full = C.output_drop(letters, rows_of, args.user, args.item, args.graphNum, args.latdim)
         batch.update({k: v.to(rec.device) for k, v in dev.items()})      # train_loss reads them where the model lives
         obatch.update(full)
     return batch, obatch
 
 
-def oracle_run(letters, rec, handler, NNs, args, obatch, monkeypatch, dtype=torch.float64):
+def oracle_run(letters, rec, handler, NNs, args, obatch, monkeypatch, dtype=torch.float64, candidates=None):
     """The composed objective and its gradients: (preLoss, sslloss, {variable name: float64 gradient array or None}), one
-    entry per registered variable. The patches of the oracle module last for this call only."""
+    entry per registered variable. The patches of the oracle module last for this call only. candidates: the step's
+    (cand, bias) where the caller read them back from the device; flag_combo_ref.step_candidates otherwise."""
     from sa_gnn_amd.model import banned_table
     from test_gpu_gru import _oracle_params_gru
     from test_gpu_train import _oracle_params
@@ -76,9 +83,10 @@ def oracle_run(letters, rec, handler, NNs, args, obatch, monkeypatch, dtype=torc
            "temp": args.softmaxTemp}
     slot_info = (handler.timeMin, args.slot, handler.maxTime + 1) if "T" in letters else None
     banned = banned_table(handler, args.item) if "S" in letters else None
+    cand, bias = C.step_candidates(letters, handler, args.item) if candidates is None else candidates
     with monkeypatch.context() as m:
         pre, ssl = C.objective(letters, P, leaves, handler.subMat, obatch, cfg, m.setattr, C.time_names(rec, NNs.params),
-                               slot_info, banned)
+                               slot_info, banned, cand, bias)
         (pre + args.ssl_reg * ssl).backward()
     grads = {k: None if v.grad is None else v.grad.detach().double().numpy() for k, v in leaves.items()}
     return float(pre.detach()), float(ssl.detach()), grads
@@ -86,16 +94,21 @@ def oracle_run(letters, rec, handler, NNs, args, obatch, monkeypatch, dtype=torc
 
 # ---- the case table ---------------------------------------------------------------------------------------------------
 def test_the_case_table_is_a_pairwise_cover_of_the_legal_pairs():
-    assert set(C.LETTERS) == set(C.ON) and len(C.LETTERS) == 9
+    assert set(C.LETTERS) == set(C.ON) and len(C.LETTERS) == 13
     for case, (letters, latdim) in C.CASES.items():
         assert not C.illegal(letters), f"case {case} holds an illegal set"
         assert all(a + b in C.legal_pairs() for a, b in itertools.combinations(sorted(letters, key=C.LETTERS.index), 2)), case
         assert len(set(letters)) == len(letters) and set(letters) <= set(C.LETTERS) and latdim in (32, 64, 128)
     illegal_pairs = {a + b for a, b in itertools.combinations(C.LETTERS, 2)} - set(C.legal_pairs())
-    assert illegal_pairs == {"TE", "SB"}                  # A without F is a set of one
+    # A without F or C, K without S and P without K are sets of one or two that a third value makes legal; S with B is
+    # legal under K; L excludes F because it needs C
+    assert illegal_pairs == {"TE", "FC", "FL", "AL"}
     assert C.illegal("A") and not C.illegal("FA") and C.illegal("GA") and not C.illegal("F")
+    assert not C.illegal("CA") and C.illegal("K") and not C.illegal("SK") and C.illegal("SP") and not C.illegal("SKP")
+    assert C.illegal("SB") and not C.illegal("SKB") and C.illegal("CL") and C.illegal("SL") and not C.illegal("CLS")
+    assert C.illegal("CLSA") and C.illegal("FCS")
     pairs = C.legal_pairs()
-    assert len(pairs) == 36 - 2
+    assert len(pairs) == 78 - 4
     missing = [p for p in pairs if not any(set(p) <= set(letters) for letters, _ in C.CASES.values())]
     assert not missing, f"legal pairs in no case: {missing}"
     # every value of its own, too, and the three kernel widths
@@ -103,11 +116,15 @@ def test_the_case_table_is_a_pairwise_cover_of_the_legal_pairs():
     assert {d for _, d in C.CASES.values()} == {32, 64, 128}
 
 
-@pytest.mark.parametrize("letters,match", [("TE", "edgeKeepRate"), ("SB", "fusion_rows"), ("A", "seqAtt full")])
+@pytest.mark.parametrize("letters,match", [("TE", "edgeKeepRate"), ("SB", "fusion_rows"), ("A", "seqAtt full"),
+                                           ("K", "softmaxNegs 16 needs --predLoss softmax"), ("SP", "softmaxNegDist pop needs"),
+                                           ("L", "seqTargets all needs --seqAtt causal"), ("SL", "seqTargets all needs --seqAtt causal"),
+                                           ("CL", "seqTargets all needs --predLoss softmax"),
+                                           ("CLSA", "seqTargets all needs --seqPool sum")])
 def test_the_model_refuses_what_the_table_calls_illegal(monkeypatch, letters, match):
     from sa_gnn_amd.Params import args
     from sa_gnn_amd.model import Recommender
-    assert C.illegal(letters)
+    assert C.illegal(letters)                             # F with C is one flag's two values: nothing to refuse
     for k, v in dict(C.model_flags(letters, 32), user=10, item=10).items():
         monkeypatch.setattr(args, k, v, raising=False)
     with pytest.raises(ValueError, match=match):
@@ -178,14 +195,30 @@ def _single_flag_restatement(letters, rec, handler, NNs, args, obatch, m):
     elif letters == "S":                                  # test_gpu_softmax_loss.py
         pre, ssl, _, _ = SL.torch_train_loss_softmax(P, adj, tp, obatch, dict(cfg, temp=args.softmaxTemp),
                                                      banned_table(handler, args.item), head=SL.torch_head_collapsed)
+    elif letters == "SK":                                 # test_gpu_softmax_negs.py
+        from test_gpu_softmax_negs import _cand_banned
+        cand, _ = C.step_candidates(letters, handler, args.item)
+        pre, ssl, _, _ = SL.torch_train_loss_softmax(P, adj, tp, obatch, dict(cfg, temp=args.softmaxTemp),
+                                                     _cand_banned(handler, args, cand))
+    elif letters == "SKP":                                # test_gpu_softmax_pop.py
+        cand, bias = C.step_candidates(letters, handler, args.item)
+        pre, ssl, _, _ = POP.torch_train_loss_pop(P, adj, tp, obatch, dict(cfg, temp=args.softmaxTemp),
+                                                  banned_table(handler, args.item), cand, bias)
+    elif letters == "C":                                  # the hinge loss on the causal head
+        pre, ssl, _, _ = SA.torch_train_loss_full(P, adj, tp, obatch, cfg, head=SC.torch_head_causal)
+    elif letters == "CS":                                 # test_gpu_seq_causal.py, --seqTargets last
+        pre, ssl, _, _ = SL.torch_train_loss_softmax(P, adj, tp, obatch, dict(cfg, temp=args.softmaxTemp),
+                                                     banned_table(handler, args.item), head=SC.torch_head_causal)
+    elif letters == "CLS":                                # test_gpu_seq_causal.py, --seqTargets all
+        pre, ssl, _ = SC.torch_train_loss_all(P, adj, tp, obatch, dict(cfg, temp=args.softmaxTemp), banned_table(handler, args.item))
     else:
         raise AssertionError(letters)
     return pre, ssl, leaves
 
 
-@pytest.mark.parametrize("letters", ["", "G", "N", "T", "E", "F", "FA", "S", "B", "D"])
+@pytest.mark.parametrize("letters", ["", "G", "N", "T", "E", "F", "FA", "S", "B", "D", "SK", "SKP", "C", "CS", "CLS"])
 def test_composer_equals_the_single_flag_restatement(monkeypatch, letters):
-    """No flag, each flag alone (A with the F it needs): the losses and every leaf gradient agree to 1e-12 relative; a
+    """No flag, each flag alone (A with the F it needs, K with S, P with S and K, L with C and S): the losses and every leaf gradient agree to 1e-12 relative; a
     variable the restatement does not hold has no gradient in the composed objective either."""
     cpu_model(monkeypatch)
     rec, handler, NNs, args = setup_case("cpu", monkeypatch, letters, 32)
@@ -226,8 +259,8 @@ def test_float32_on_the_cpu_stays_within_a_quarter_of_the_gradient_tolerance(mon
     error over the tolerance of test_gpu_flag_combos.py, printed, and at most 0.25 for every leaf not named in
     flag_combo_ref.F32_EXCEPTIONS[case]: those the GPU suite judges at max(tolerance, four times the float32 error), as
     test_gpu_zero_grad_rows.py does, which widens nothing where a named leaf holds the quarter after all. Cases 1, 2
-    and 4 name no leaf (worst 0.031, 0.007, 0.047); case 3 names the user side of the fusion. The losses stay within a
-    quarter of 1e-4 max(|want|, 1) as well."""
+    and 4 name no leaf (worst 0.031, 0.007, 0.047), nor do cases 5 to 8 (0.041, 0.040, 0.011, 0.047); case 3 names the
+    user side of the fusion. The losses stay within a quarter of 1e-4 max(|want|, 1) as well."""
     letters, latdim = C.CASES[case]
     cpu_model(monkeypatch)
     rec, handler, NNs, args = setup_case("cpu", monkeypatch, letters, latdim)

@@ -1,11 +1,15 @@
 """GPU suite of the training objective under COMBINED opt-in flags: Recommender.train_loss and every
-parameter gradient against the composed float64 objective of flag_combo_ref, on the four cases that cover every legal
+parameter gradient against the composed float64 objective of flag_combo_ref, on the eight cases that cover every legal
 pair of non-default values (test_flag_combo_host.py asserts the cover):
 
   1  G N T F A S D  d = 64   fused GRU, weighted + time SpMM, softmax through the additive pool
   2  G N E F A B D  d = 32   fused GRU, drop + weighted SpMM, compacted rows, hinge
   3  T B D          d = 32   LSTM, unweighted time form under compacted rows
   4  G S E          d = 128  per-step GRU route, softmax with edge drop, collapsed head
+  5  G N T C L S K P D  d = 64   every position against popularity candidates: the target scatter's dI into the weighted + time SpMM
+  6  E C L S K B D      d = 32   every position against uniform candidates under compacted rows and edge drop
+  7  N F A S K P B      d = 32   the candidate loss's backward through the additive pool into compacted rows
+  8  G E C A S K P      d = 128  causal attention under the additive pool, the popularity draw next to edge drop
 
 on the 70-user, 60-item, 2-interval timestamped dataset of test_gpu_edge_time.py. Tolerances are the sibling tests':
 losses at 1e-4 max(|want|, 1), gradients at test_gpu_seq_att._grad_close with the key biases' floor. Only case 3 has
@@ -24,7 +28,24 @@ pytestmark = pytest.mark.gpu
 
 # compared leaves at least: the 37 (LSTM) / 39 (GRU) variables every case has and a loss reaches, + 9 under T (timeEmbed
 # and the 2 T L time weights, without a gradient on both sides otherwise), + 3 under A
-MIN_COMPARED = {1: 39 + 9 + 3, 2: 39 + 3, 3: 37 + 9, 4: 39}
+MIN_COMPARED = {1: 39 + 9 + 3, 2: 39 + 3, 3: 37 + 9, 4: 39, 5: 39 + 9, 6: 37, 7: 37 + 3, 8: 39 + 3}
+
+
+def _device_candidates(rec, handler, args, letters, dev):
+    """The step's list as the device draws it under CAND_SEED, read back (test_gpu_seq_causal._compare_all): equal to the
+    restatement's ids and live positions; the device's own offsets go into the float64 objective."""
+    from sa_gnn_amd import ops
+    cand, bias = C.step_candidates(letters, handler, args.item)
+    if cand is None:
+        return None
+    if bias is None:
+        got = ops.sample_strata(args.item, args.softmaxNegs, *C.CAND_SEED, dev).cpu().numpy()
+        assert got.tolist() == cand.tolist()
+        return got, None
+    got, gb = (v.cpu().numpy() for v in ops.sample_strata_weighted(*rec._pop_cum_device(), args.softmaxNegs, *C.CAND_SEED))
+    assert got.tolist() == cand.tolist() and np.array_equal(np.isfinite(gb), np.isfinite(bias))
+    assert np.allclose(gb[np.isfinite(gb)], bias[np.isfinite(bias)], rtol=1e-6, atol=1e-6)
+    return got, gb
 
 
 def _loss_and_grads(rec, NNs, args, batch):
@@ -43,17 +64,19 @@ def test_train_loss_and_every_gradient_against_the_composed_float64_objective(de
     letters, latdim = C.CASES[case]
     rec, handler, NNs, args = setup_case(dev, monkeypatch, letters, latdim)
     batch, obatch = host_batch(letters, rec, handler, args)
+    cands = _device_candidates(rec, handler, args, letters, dev)
     pre, ssl, grads = _loss_and_grads(rec, NNs, args, batch)
     if "B" in letters:                                    # the compacted rows are the reference's, and a real subset
-        users, items, _ = FR.touched_rows(batch, args.user, args.item)
-        assert rec.fusion_rows_counts == (len(users), len(items)) and len(items) < args.item
+        users, items, _ = FR.touched_rows(batch if cands is None else dict(batch, cand=cands[0]), args.user, args.item)
+        assert rec.fusion_rows_counts == (len(users), len(items)) and len(users) < args.user
+        assert len(items) < args.item or "K" in letters   # 16 candidates can complete the 60 items: case 6 touches them all
         assert "D" not in letters or tuple(batch["drop_u"].shape) == (len(users), args.graphNum, latdim)
-    opre, ossl, want = oracle_run(letters, rec, handler, NNs, args, obatch, monkeypatch)
+    opre, ossl, want = oracle_run(letters, rec, handler, NNs, args, obatch, monkeypatch, candidates=cands)
     print(f"flag_combos|gpu|case {case} {letters} d={latdim}|preLoss {pre!r} vs {opre!r}; sslloss {ssl!r} vs {ossl!r}")
     assert abs(pre - opre) <= 1e-4 * max(abs(opre), 1.0) and abs(ssl - ossl) <= 1e-4 * max(abs(ossl), 1.0)
     err32 = {}
     if C.F32_EXCEPTIONS[case]:
-        _, _, g32 = oracle_run(letters, rec, handler, NNs, args, obatch, monkeypatch, dtype=torch.float32)
+        _, _, g32 = oracle_run(letters, rec, handler, NNs, args, obatch, monkeypatch, dtype=torch.float32, candidates=cands)
         err32 = {n: np.abs(g32[n] - want[n]) for n in C.F32_EXCEPTIONS[case]}
     assert set(want) == set(NNs.params) == set(grads)
     compared, worst = 0, {}
@@ -92,7 +115,7 @@ def test_train_loss_and_every_gradient_against_the_composed_float64_objective(de
         assert all(want[n] is None for n in time)
     if "A" in letters:
         assert all(trains(n) for n in C.ADD_NAMES)
-    if "F" in letters:                                    # above the noise under which the collapsed head's stay
+    if "F" in letters or "C" in letters:                  # above the noise under which the collapsed head's stay
         qk, v = _head_qk_names(rec, NNs)
         v_scale = max(float(grads[n].abs().max()) for n in v)
         assert all(float(grads[n].abs().max()) > QK_NOISE * v_scale and float(np.abs(want[n]).max()) > QK_NOISE * v_scale for n in qk)
@@ -103,7 +126,9 @@ def test_each_flag_of_the_case_moves_the_result(dev, monkeypatch, case):
     """Any one flag of the case back at its default: preLoss or sslloss moves by more than 1e-3 relative. Two flags cannot
     be judged that way. F under A is judged without A on both sides (A alone without F is refused). B must NOT move the
     result (it fuses the rows the loss reads, test_gpu_fusion_rows.py): there the losses agree to that file's 1e-6 and the
-    run is shown to have compacted."""
+    run is shown to have compacted. What a newer flag needs stays legal on both sides: P is judged against uniform
+    candidates and L against last as they are; C against F, without the L that needs C; K without the P that needs it and
+    the B that S takes only under K; S without K, P, L and B."""
     letters, latdim = C.CASES[case]
     seen = {}
 
@@ -125,15 +150,22 @@ def test_each_flag_of_the_case_moves_the_result(dev, monkeypatch, case):
             assert abs(off[0] - base[0]) <= 1e-6 * max(abs(base[0]), 1.0) and abs(off[1] - base[1]) <= 1e-6 * max(abs(base[1]), 1.0)
             assert base[2][1] < base[3][1] or base[2][0] < base[3][0]
             continue
+        drop = lambda s, cs: "".join(x for x in s if x not in cs)      # noqa: E731
         if c == "F" and "A" in letters:
             on, off = losses(rest.replace("A", "") + "F"), losses(rest.replace("A", ""))
+        elif c == "C":
+            on, off = losses(drop(letters, "L")), losses(drop(letters, "LC") + "F")
+        elif c == "K":
+            on, off = losses(drop(letters, "PB")), losses(drop(letters, "PBK"))
+        elif c == "S" and set(letters) & set("KPLB"):
+            on, off = losses(drop(letters, "KPLB")), losses(drop(letters, "KPLBS"))
         else:
             on, off = base, losses(rest)
         print(f"flag_combos|gpu|case {case} {letters}|{c} off: preLoss {on[0]:.6g} -> {off[0]:.6g}, sslloss {on[1]:.6g} -> {off[1]:.6g}")
         assert _moved(on, off), f"case {case}: switching {c} off moves neither loss"
 
 
-@pytest.mark.parametrize("case", [1, 2])
+@pytest.mark.parametrize("case", [1, 2, 5, 7])
 def test_device_sampled_batch_gives_the_host_forms_loss(dev, monkeypatch, case):
     """The segment path into the full head, not the CSR path: a device-sampled batch against its host form, at the bound
     of test_gpu_seq_pool.py's test of the same name, under the same edge seed and output-dropout masks."""
@@ -150,18 +182,21 @@ def test_device_sampled_batch_gives_the_host_forms_loss(dev, monkeypatch, case):
     rows_h = FR.touched_rows(hb, args.user, args.item)
     assert np.array_equal(rows_d[0], rows_h[0]) and np.array_equal(rows_d[1], rows_h[1])
     for batch in (b, hb):
-        batch.update({k: v.to(dev) for k, v in masks.items()})
+        if "D" in letters:
+            batch.update({k: v.to(dev) for k, v in masks.items()})
         if "E" in letters:
             batch["edge_seed"] = C.EDGE_SEED
+        if "K" in letters:
+            batch["cand_seed"] = C.CAND_SEED
     pre_d, ssl_d, gd = _loss_and_grads(rec, NNs, args, b)
     pre_h, ssl_h, gh = _loss_and_grads(rec, NNs, args, hb)
     print(f"flag_combos|gpu|case {case} {letters}|device batch: preLoss {pre_d!r} host form {pre_h!r}; sslloss {ssl_d!r} {ssl_h!r}")
     assert abs(pre_d - pre_h) <= 1e-4 * abs(pre_h) + 1e-5 and abs(ssl_d - ssl_h) <= 1e-4 * abs(ssl_h) + 1e-5
-    for name in ("posEmbed", "iEmbed") + C.ADD_NAMES:
+    for name in ("posEmbed", "iEmbed") + (C.ADD_NAMES if "A" in letters else ()):
         _grad_close(gd[name].cpu().double().numpy(), gh[name].cpu().double().numpy(), name)
 
 
-@pytest.mark.parametrize("case", [1, 3])
+@pytest.mark.parametrize("case", [1, 3, 5])
 def test_captured_forward_and_device_evaluators(dev, monkeypatch, case):
     """The captured forward replays what forward() computes, bit for bit, after a row of timeEmbed is edited in place (the
     time tables are part of the capture), and the device evaluator gives the host evaluator's results."""
