@@ -419,6 +419,18 @@ int sagnn_gnn_stack_bwd_f32(const sagnn_spmm_batch* batch, const sagnn_gnn_args*
  *       largest gradient, from 1e-38 to 1e38), dW / db relative to the sum of the magnitudes of their terms.
  *   sagnn_set_engine(SAGNN_ENGINE_F32) selects the exact-fp32 kernels instead. Results are deterministic run to run
  *   under every engine.
+ *
+ * STRIDE LIMITS of the LSTM forward entries (sagnn_lstm_fwd_f32, _state_f32, _train_f32, and sagnn_interval_fusion_f32
+ *   through its LSTM). n, and with it every offset n * ld, is 64-bit everywhere; what is limited is the ROW STRIDE where
+ *   a kernel takes a 64-bit base per tile of rows and addresses inside the tile with 32-bit byte offsets:
+ *     - the f16 x 2 kernel (d = 32, 64 under SAGNN_ENGINE_F16X2; 96-row tiles) takes ld_h < 2^22 and t * d < 2^18. This
+ *       limit REROUTES: from ld_h = 2^22 on the same call runs the fp32 matrix-core kernel, results to the same bounds.
+ *       ld_n and ld_t are not limited on this kernel.
+ *     - the fp32 matrix-core kernel (d = 32, 64; 32-row tiles) takes ld_n < 2^24, ld_h < 2^24 and t * d < 2^20. This
+ *       limit REFUSES: SAGNN_ERR_ARG before any device work, under both matrix engines.
+ *   The d = 128 and VALU kernels, h_init (ld_hi), every attention entry (ld_n, ld_t, ld_out, ld_g), the dense products,
+ *   the SpMM and the row gather / scatter address with 64-bit offsets and have no such limit. The GRU's and the BPTT's
+ *   limits are stated at their entries below. tests/test_gpu_far_offsets.py runs each kernel at the last stride admitted.
  * -------------------------------------------------------------------------------- */
 int sagnn_lstm_fwd_f32(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int d, const float* W,
                        const float* b, float forget_bias, const float* drop_scale, float* h,
@@ -494,6 +506,9 @@ size_t sagnn_interval_fusion_workspace_bytes(int64_t n, int t, int d);
  *   [n, t, d] dense), dh_ext [n, t, d] with row stride ld_dhe -> dx [n, t, d] dense, and
  *   dW [2d, 4d] / db [4d] ACCUMULATED with float atomics (zero them first). Gate gradients stay
  *   on chip: per 32-row chunk and step, d[x|h] = dG W^T and dW += [x|h]^T dG run as MFMA tiles.
+ *   STRIDE LIMIT (sagnn_lstm_bwd_f32 and sagnn_lstm_bwd_ws_f32, both forms): ld_n < 2^25, ld_dhe < 2^25 and
+ *   t * d < 2^20; a 32-row chunk is addressed with 32-bit element offsets from a 64-bit base. This limit REFUSES:
+ *   SAGNN_ERR_ARG before any device work. n, and the contiguous h / gates / cell / dx with it, is not limited.
  * -------------------------------------------------------------------------------- */
 int sagnn_lstm_fwd_train_f32(const float* x, int64_t ld_n, int64_t ld_t, int64_t n, int t, int d,
                              const float* W, const float* b, float forget_bias, const float* drop_scale,
@@ -561,6 +576,9 @@ int sagnn_lstm_bwd_ws_f32(const float* x, int64_t ld_n, int64_t ld_t, const floa
  *   there the call runs one step at a time (two products by sagnn_dense_nn_f32's kernels and two element-wise launches
  *   per step; the counterpart of the LSTM's generic route, not built for speed) in a caller workspace of
  *   sagnn_gru_workspace_bytes = n * 3d floats, 16-byte aligned (0 where the fused kernel runs; SAGNN_ERR_WORKSPACE).
+ *   STRIDE LIMIT of the one-launch form (d = 32, 64): ld_n < 2^24, ld_h < 2^24 and t * d < 2^19 (32-row tiles addressed
+ *   with 32-bit byte offsets from a 64-bit base). This limit REFUSES: SAGNN_ERR_ARG before any device work. The per-step
+ *   route and the two backward entries address with 64-bit offsets and have no such limit.
  * sagnn_gru_fwd_f32 — h [n, t, d] (node stride ld_h) for every step. gates / cand (both or neither): the training
  *   form, which also stores gates [n, t, 2d] = r | u after the sigmoid and cand [n, t, d] = c after the tanh, and h
  *   un-dropped as the backward reads it: drop_scale must then be NULL (SAGNN_ERR_ARG).
