@@ -940,6 +940,39 @@ int sagnn_seq_targets_i32(const int32_t* seq_items, int64_t n_flat, const int64_
                           int64_t n_items, int32_t* target, int32_t* excl_row, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Sequence attention at head widths 16, 32 and 64 (seq_attn_wide.hip; --seqHeads, not in the reference): the layout and
+ * the contract of sagnn_seq_attn_masked_f32 / sagnn_seq_attn_masked_bwd_f32 above for few wide heads, with every
+ * product (Q K^T, P V; backward G V^T, dS K, dS^T Q, P^T G) on the fp32 matrix cores (v_mfma_f32_16x16x4_f32).
+ * sagnn_seq_attn_wide_f32: qkv [n_slots * P, 3d] dense (q | k | v per row, head h in columns h * d_k .. of each third,
+ *   d_k = d / heads) -> ctx [n_slots * P, d] dense. Over slot b's n_b = clamp(seg_len[b], 0, P) tokens only (s <= j under
+ *   causal = 1): e[j, s] = exp(<q_j, k_s> / sqrt(d_k)), a = e / (sum_s e + 1e-8), ctx_j = sum_s a[j, s] v_s. The quotient
+ *   is evaluated as e' / (sum e' + 1e-8 * 2^-m), shifted by the row's largest score m (a running maximum over tiles of 16
+ *   keys in ascending order, the partial sums rescaled when it moves), so results are finite for any finite q|k|v. Padded
+ *   rows of ctx are exact zeros; padded rows of qkv are never read, and a tile row at or beyond n_b is loaded as zeros,
+ *   so the rows past the end of the buffer that a tile of the last slot covers when P % 16 != 0 are not touched. A masked
+ *   score is removed by a select, not by a product with 0. ctx_j does not depend on any token after j under causal = 1.
+ * sagnn_seq_attn_wide_bwd_f32: (qkv, g_ctx [n_slots * P, d]) -> dqkv [n_slots * P, 3d], every row WRITTEN, padded rows
+ *   exact zeros; e is recomputed from qkv. dk_s and dv_s are summed over the query tiles in ascending order inside the
+ *   one workgroup that owns the (slot, head): no atomics, bit-identical between runs, forward and backward. Padded rows
+ *   of g_ctx are not read. Under causal = 1 a gradient that is non-zero in rows <= j only gives exact zeros in dk_s, dv_s
+ *   for s > j.
+ * sagnn_seq_attn_wide_supported(d, heads, pos_length): SAGNN_OK iff d > 0, d % 4 == 0, heads > 0, d % heads == 0,
+ *   d / heads in {16, 32, 64} and 1 <= pos_length <= 256; SAGNN_ERR_DIM otherwise (the reason in sagnn_last_error).
+ *   Never touches the device. The widths 2, 4 and 8 stay with sagnn_seq_attn_supported's entries; the two sets are disjoint.
+ * causal outside {0, 1}: SAGNN_ERR_ARG. qkv, g_ctx, ctx, dqkv 16-byte aligned and dense. n_slots >= 0 (0 returns SAGNN_OK
+ *   at once), n_slots < 2^31. Every argument is checked before any device work. One workgroup of 256 threads per (slot,
+ *   head); dynamic LDS 2 * ceil16(P) * (d_k + 4) floats (K and V of the head; backward 3 * ceil16(P) floats more and the
+ *   same buffer re-used for q and g): 136 KB (139 KB backward) at d_k = 64, P = 256. Exact fp32 under every engine
+ *   (sagnn_set_engine does not change these kernels). One launch each on `stream`, no allocation, no synchronisation
+ *   (capturable). Profile kind 5.
+ * -------------------------------------------------------------------------------- */
+int sagnn_seq_attn_wide_supported(int d, int heads, int pos_length);
+int sagnn_seq_attn_wide_f32(const float* qkv, const int32_t* seg_len, int64_t n_slots, int pos_length, int d, int heads,
+                            int causal, float* ctx, void* stream);
+int sagnn_seq_attn_wide_bwd_f32(const float* qkv, const float* g_ctx, const int32_t* seg_len, int64_t n_slots,
+                                int pos_length, int d, int heads, int causal, float* dqkv, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Additive-attention pooling of the sequence head (seq_attn.hip; --seqPool additive, not in the reference's graph: it
  * constructs AdditiveAttention(query_vector_dim, latdim), model.py:147, and comments its call out, model.py:168).
  * On the slab layout above, with u = x Wa + ba [n_slots * P, q] computed by the caller (sagnn_dense_nn_f32 over all

@@ -81,7 +81,8 @@ _FLAGS = [
     ("seqAtt", str, "sum", "what the head's attention layers see of the user's item sequence: sum (the masked sum "
                            "collapses the sequence into one token, as the reference's graph computes) or full (every "
                            "item of the sequence is a token and the layers attend over the real items, padding masked; "
-                           "same variables; needs latdim / num_attention_heads in {2, 4, 8} and pos_length <= 256). Not "
+                           "same variables; needs latdim / num_attention_heads in {2, 4, 8} and pos_length <= 256; "
+                           "--seqHeads gives these layers a head count of their own, up to a head width of 64). Not "
                            "in the reference's graph: it multiplies the mask in before the attention layers "
                            "(model.py:161-162) and never passes attn_mask (Utils/attention.py:35-45). The causal form of full "
                            "is chosen with --seqMask causal",
@@ -94,6 +95,12 @@ _FLAGS = [
                              "refused under it and the reverse; it needs --seqAtt full. Not in the reference, which "
                              "never passes an attention mask",
      ("none", "causal")),
+    ("seqHeads", int, 0, "the head count of --seqAtt full's attention layers: 0 follows --num_attention_heads, H > 0 gives "
+                         "the sequence head H heads of its own while the interval fusion keeps --num_attention_heads "
+                         "(SASRec-style heads: 1 or 2 at latdim 64); needs --seqAtt full (with or without --seqMask "
+                         "causal), H a divisor of latdim and latdim / H in {2, 4, 8, 16, 32, 64}; widths 16 to 64 run on the "
+                         "fp32 matrix cores; same variables; part of the model (stored in checkpoints, checked on load). "
+                         "Not in the reference"),
     ("seqTargets", str, "last", "which next-item events of a slot's sequence the head trains on: last (the slot's pooled row "
                                 "against its one sampled positive, as the reference's graph computes, model.py:161-168: one "
                                 "collapsed token, one target) or all (every real token a query: the running sum of the "

@@ -230,6 +230,10 @@ SIGNATURES = {
     "sagnn_seq_attn_masked_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "sagnn_seq_attn_masked_bwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p,
                                               c_void_p]),
+    "sagnn_seq_attn_wide_supported": (c_int, [c_int, c_int, c_int]),
+    "sagnn_seq_attn_wide_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "sagnn_seq_attn_wide_bwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p,
+                                            c_void_p]),
     "sagnn_seq_prefix_query_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_float,
                                            c_void_p, c_int64, c_void_p]),
     "sagnn_seq_prefix_query_bwd_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_float,

@@ -717,7 +717,10 @@ class SeqAttnFn(torch.autograd.Function):
         bqkv = torch.cat([bq, bk, bv]).detach().contiguous()
         qkv = ops.dense_nn(y, Wqkv, bqkv)
         causal = bool(causal)
-        att = ops.seq_attn(qkv, seg_len, P, heads, causal) if causal else ops.seq_attn(qkv, seg_len, P, heads)
+        if d // int(heads) >= 16:                     # --seqHeads: few wide heads, on the matrix cores
+            att = ops.seq_attn_wide(qkv, seg_len, P, heads, causal)
+        else:
+            att = ops.seq_attn(qkv, seg_len, P, heads, causal) if causal else ops.seq_attn(qkv, seg_len, P, heads)
         ctx.save_for_backward(x, qkv, gamma, beta, Wqkv, seg_len)
         ctx.cfg = (int(P), int(heads), float(leaky))
         ctx.causal = causal
@@ -729,10 +732,12 @@ class SeqAttnFn(torch.autograd.Function):
         P, heads, leaky = ctx.cfg
         R, d = x.shape
         g = g.contiguous()
+        wide = d // heads >= 16
         mask = (True,) if ctx.causal else ()          # the default path's calls stay what they were
-        att = ops.seq_attn(qkv, seg_len, P, heads, *mask)
+        att = ops.seq_attn_wide(qkv, seg_len, P, heads, ctx.causal) if wide else ops.seq_attn(qkv, seg_len, P, heads, *mask)
         g_att = ops.leaky_bwd(att, g, leaky)
-        dqkv = ops.seq_attn_bwd(qkv, g_att, seg_len, P, heads, *mask)
+        dqkv = (ops.seq_attn_wide_bwd(qkv, g_att, seg_len, P, heads, ctx.causal) if wide
+                else ops.seq_attn_bwd(qkv, g_att, seg_len, P, heads, *mask))
         y = ops.layernorm_td(x.view(R, 1, d), gamma.detach(), beta.detach()).view(R, d)     # not saved: recomputed
         # dW, db and dy as two products, not the fused tail (ops.attn_bwd_tail). This layer was written while the tail
         # returned NaN bias gradients for a workgroup whose first chunk held only zero rows (a slab's padding: any slot

@@ -34,6 +34,12 @@ PRED_LOSS = ("hinge", "softmax")   # --predLoss: the reference's sampled hinge l
 NEG_DIST = ("uniform", "pop")      # --softmaxNegDist: the uniform strata of --softmaxNegs, or a popularity-weighted draw
 
 
+def seq_heads() -> int:
+    """The head count of the sequence head's attention over tokens (_seq_att_full): --seqHeads, or --num_attention_heads
+    when it is 0. Nothing else reads --seqHeads: the interval fusion and the collapsed head keep num_attention_heads."""
+    return args.seqHeads or args.num_attention_heads
+
+
 def random_fusion_params(d: int, device, seed: int = 0, cell: str = "lstm") -> dict:
     """Random-init fusion parameters with the shapes TF creates (BasicLSTMCell kernel [2d, 4d] and
     bias [4d]; layer_norm gamma/beta [d]; three dense kernels [d, d] with bias [d]). Kernels are
@@ -555,7 +561,7 @@ class Recommender:
         inference paths. Same variables as the collapsed head. Under causal a token attends to itself and the tokens
         before it. pooled=False returns the last layer's slab [args.batch * pos_length, d] instead of the pooled rows
         (--seqTargets all)."""
-        heads, leaky, P = args.num_attention_heads, NNs.leaky, args.pos_length
+        heads, leaky, P = seq_heads(), NNs.leaky, args.pos_length
         mask = (True,) if args.seqAtt == "causal" else ()     # full: SeqAttnFn's call stays what it was
         seq, pos = ag.SeqGatherFn.apply(fi, self.posEmbed, seq_items, seq_pos, seg_begin, seg_len)
         R, d = seq.shape
@@ -1255,6 +1261,8 @@ class Recommender:
             pickle.dump(self.metrics, fs)
         state = {"params": {k: v.detach().cpu() for k, v in NNs.params.items()}, "adjNorm": args.adjNorm,
                  "seqAtt": args.seqAtt, "seqPool": args.seqPool, "edgeTime": self._edge_time_state(), "rnnCell": args.rnnCell}
+        if args.seqAtt in SEQ_TOKEN_MODES:
+            state["seqHeads"] = seq_heads()        # the effective head count of the attention over tokens
         if getattr(self, "optimizer", None) is not None:
             state["optimizer"] = self.optimizer.state_dict()
         torch.save(state, os.path.join(directory, "Models", args.save_path))
@@ -1279,6 +1287,11 @@ class Recommender:
         if stored_att != args.seqAtt:
             raise ValueError(f"checkpoint was trained with --seqAtt {stored_att}, this run has --seqAtt {args.seqAtt}: "
                              "the head's attention is part of the model")
+        stored_heads = state.get("seqHeads")             # a checkpoint from before --seqHeads is not checked
+        if stored_heads is not None and args.seqAtt in SEQ_TOKEN_MODES and stored_heads != seq_heads():
+            raise ValueError(f"checkpoint was trained with {stored_heads} heads in the sequence attention, this run has "
+                             f"{seq_heads()} (--seqHeads {args.seqHeads}, --num_attention_heads {args.num_attention_heads}): "
+                             "the head count is part of the model")
         stored_pool = state.get("seqPool", "sum")        # a checkpoint from before --seqPool pools with the plain sum
         if stored_pool != args.seqPool:
             raise ValueError(f"checkpoint was trained with --seqPool {stored_pool}, this run has --seqPool {args.seqPool}: "
@@ -1383,8 +1396,18 @@ class Recommender:
             if args.latdim % 32 or args.query_vector_dim % 32:       # the projection and its gradients: the dense entries
                 raise ValueError(f"--seqPool additive needs latdim and query_vector_dim to be multiples of 32, got "
                                  f"{args.latdim} and {args.query_vector_dim}")
+        if args.seqHeads < 0:
+            raise ValueError(f"--seqHeads {args.seqHeads}: need a count >= 0 (0 = follow --num_attention_heads)")
+        if args.seqHeads > 0 and args.seqAtt not in SEQ_TOKEN_MODES:
+            raise ValueError(f"--seqHeads {args.seqHeads} needs --seqAtt full (with or without --seqMask causal; got --seqAtt "
+                             f"{args.seqAtt}): it is the head count of the attention over the sequence's tokens")
         if args.seqAtt in SEQ_TOKEN_MODES:  # refused before any forward: the attention kernels take these shapes only
-            why = ops.seq_attn_supported(args.latdim, args.num_attention_heads, args.pos_length)
+            heads = seq_heads()
+            why = ops.seq_attn_supported(args.latdim, heads, args.pos_length)
+            if why is not None and args.seqHeads > 0:        # few wide heads: the matrix-core entries
+                wide = ops.seq_attn_wide_supported(args.latdim, heads, args.pos_length)
+                why = None if wide is None else (f"--seqHeads {args.seqHeads} needs latdim / seqHeads in (2, 4, 8, 16, 32, 64) "
+                                                 f"and pos_length <= 256 ({why}; {wide})")
             if why is not None:
                 raise ValueError(f"--seqAtt {args.seqAtt} is not available for this configuration: {why}")
         NNs.reset(self.device)

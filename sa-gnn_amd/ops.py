@@ -2077,6 +2077,33 @@ def seq_attn_bwd(qkv: torch.Tensor, g_ctx: torch.Tensor, seg_len: torch.Tensor, 
     return dqkv
 
 
+def seq_attn_wide_supported(d: int, heads: int, pos_length: int) -> str | None:
+    """None when sagnn_seq_attn_wide_f32 / _bwd_f32 take the shape (d / heads in {16, 32, 64}; --seqHeads), else the
+    library's reason."""
+    return None if _lib.load().sagnn_seq_attn_wide_supported(int(d), int(heads), int(pos_length)) == 0 else _lib.last_error()
+
+
+def seq_attn_wide(qkv: torch.Tensor, seg_len: torch.Tensor, pos_length: int, heads: int, causal: bool = False):
+    """seq_attn at head widths 16, 32 and 64, on the fp32 matrix cores (sagnn_seq_attn_wide_f32): the same contract."""
+    n, P, d = int(seg_len.numel()), int(pos_length), int(qkv.shape[1]) // 3
+    ctx = torch.empty((n * P, d), dtype=torch.float32, device=qkv.device)
+    check(_lib.load().sagnn_seq_attn_wide_f32(_slab_rows("qkv", qkv, 3 * d, n * P), _idx_ptr("seg_len", seg_len, torch.int32),
+                                              n, P, d, int(heads), _causal_flag(causal), ctx.data_ptr(), _stream()))
+    return ctx
+
+
+def seq_attn_wide_bwd(qkv: torch.Tensor, g_ctx: torch.Tensor, seg_len: torch.Tensor, pos_length: int, heads: int,
+                      causal: bool = False):
+    """seq_attn_bwd at head widths 16, 32 and 64 (sagnn_seq_attn_wide_bwd_f32): zero rows in the padding, bit-identical
+    between runs."""
+    n, P, d = int(seg_len.numel()), int(pos_length), int(qkv.shape[1]) // 3
+    dqkv = torch.empty((n * P, 3 * d), dtype=torch.float32, device=qkv.device)
+    check(_lib.load().sagnn_seq_attn_wide_bwd_f32(_slab_rows("qkv", qkv, 3 * d, n * P), _slab_rows("g_ctx", g_ctx, d, n * P),
+                                                  _idx_ptr("seg_len", seg_len, torch.int32), n, P, d, int(heads),
+                                                  _causal_flag(causal), dqkv.data_ptr(), _stream()))
+    return dqkv
+
+
 def seq_pool(x: torch.Tensor, seg_len: torch.Tensor, pos_length: int):
     """out[b] = the sum of slot b's real token rows of x [n_slots * P, d] (sagnn_seq_pool_f32) -> [n_slots, d]."""
     n, P, d = int(seg_len.numel()), int(pos_length), int(x.shape[1])

@@ -27,7 +27,10 @@ def main():
     ap.add_argument("--seqAtt", choices=("sum", "full", "both"), default="sum", help="the head's form(s) to time")
     ap.add_argument("--seqPool", choices=("sum", "additive", "both"), default="sum",
                     help="the full head's pooling(s) to time (implies --seqAtt full)")
+    ap.add_argument("--seqHeads", type=int, default=0, help="--seqHeads of the full head (needs --seqAtt full or both)")
     opt = ap.parse_args()
+    if opt.seqHeads and opt.seqAtt == "sum" and opt.seqPool == "sum":
+        sys.exit(f"--seqHeads {opt.seqHeads} needs --seqAtt full or both")
     if opt.seqPool != "sum" and opt.seqAtt == "sum":
         opt.seqAtt = "full"
     Params.parse_args("--data gowalla --lr 2e-3 --reg 1e-2 --ssl_reg 1e-6 --epoch 150 --batch 512 --sslNum 40 --graphNum 3 "
@@ -51,6 +54,7 @@ def main():
         args.evaluator = "device"
         args.seqAtt = "full" if opt.seqAtt == "full" else "sum"
         args.seqPool = "additive" if opt.seqPool == "additive" else "sum"
+        args.seqHeads = opt.seqHeads if args.seqAtt == "full" else 0
         for _ in range(2):
             rec.testEpoch()
         torch.cuda.synchronize()
@@ -60,10 +64,12 @@ def main():
     for att in (("sum", "full") if opt.seqAtt == "both" else (opt.seqAtt,)):
         for pool in (pools if att == "full" else ("sum",)):
             args.seqAtt, args.seqPool = att, pool
+            args.seqHeads = opt.seqHeads if att == "full" else 0
             if opt.seqAtt != "sum":
-                print(f"---- --seqAtt {att}" + (f" --seqPool {pool}" if opt.seqPool != "sum" else ""))
+                print(f"---- --seqAtt {att}" + (f" --seqPool {pool}" if opt.seqPool != "sum" else "") +
+                      (f" --seqHeads {args.seqHeads}" if args.seqHeads else ""))
             time_evaluators(rec, h, opt)
-    args.seqAtt, args.seqPool = "sum", "sum"
+    args.seqAtt, args.seqPool, args.seqHeads = "sum", "sum", 0
 
 
 def time_evaluators(rec, h, opt):

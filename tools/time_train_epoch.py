@@ -72,11 +72,17 @@ def main():
     ap.add_argument("--softmaxNegDist", choices=("uniform", "pop", "both"), default="uniform",
                     help="how the --softmaxNegs candidates are drawn; both alternates the two in one process")
     ap.add_argument("--sampler", choices=("host", "device", "both"), default="both", help="the sampler(s) to time")
+    ap.add_argument("--seqHeads", default="0",
+                    help="--seqHeads of the token head (needs --seqAtt full or causal): one count, or a comma-separated "
+                         "list such as 0,2 whose entries alternate in one process")
     opt = ap.parse_args()
     if opt.seqPool != "sum" and opt.seqAtt == "sum":
         opt.seqAtt = "full"
     if opt.seqTargets != "last" and (opt.seqAtt != "causal" or opt.predLoss != "softmax" or opt.seqPool != "sum"):
         sys.exit(f"--seqTargets {opt.seqTargets} needs --seqAtt causal, --predLoss softmax and --seqPool sum")
+    heads = tuple(int(v) for v in opt.seqHeads.split(","))
+    if any(heads) and opt.seqAtt not in ("full", "causal"):
+        sys.exit(f"--seqHeads {opt.seqHeads} needs --seqAtt full or causal")
     h = gowalla_shaped_handler()
     args.edgeKeepRate = opt.edge_keep
     rec = Recommender(torch.device("cuda:0"), h)
@@ -97,11 +103,12 @@ def main():
         args.softmaxNegs = opt.softmaxNegs if args.predLoss == "softmax" else 0
         args.softmaxNegDist = "pop" if opt.softmaxNegDist == "pop" and args.softmaxNegs else "uniform"
         args.seqPool = "additive" if opt.seqPool == "additive" else "sum"
+        args.seqHeads = heads[0]
         for _ in range(2):
             rec.trainEpoch()
         torch.cuda.synchronize()
         print(f"two device-sampler epochs done (--fusion_rows {args.fusion_rows}, --edge_keep {args.edgeKeepRate}, "
-              f"--seqAtt {args.seqAtt}, --seqTargets {args.seqTargets}, --seqPool {args.seqPool}, --predLoss {args.predLoss}, --softmaxNegs {args.softmaxNegs}, "
+              f"--seqAtt {args.seqAtt}, --seqHeads {args.seqHeads}, --seqTargets {args.seqTargets}, --seqPool {args.seqPool}, --predLoss {args.predLoss}, --softmaxNegs {args.softmaxNegs}, "
               f"--softmaxNegDist {args.softmaxNegDist}); "
               "every parameter finite:",
               all(bool(torch.isfinite(p).all()) for p in NNs.params.values()))
@@ -120,14 +127,15 @@ def main():
     samplers = ("host", "device") if opt.sampler == "both" else (opt.sampler,)
     tgts = ("last", "all") if opt.seqTargets == "both" else (opt.seqTargets,)
     tokens = ("full", "causal")                            # the head forms in which every sequence item is a token
-    configs = [(sampler, mode, att, loss, pool, tgt) for loss in losses for att in atts for pool in pools for tgt in tgts
-               for mode in modes for sampler in samplers
+    configs = [(sampler, mode, att, loss, pool, tgt, hd) for loss in losses for att in atts for pool in pools for tgt in tgts
+               for hd in heads for mode in modes for sampler in samplers
                if (att in tokens or pool == "sum") and not (loss == "softmax" and mode == "batch")]
     label = lambda c: ", ".join([c[0]] + ([f"{c[1]} rows"] if len(modes) > 1 else []) +   # noqa: E731
                                 ([f"seqAtt {c[2]}"] if atts != ("sum",) else []) +
                                 ([f"seqPool {c[4]}"] if pools != ("sum",) else []) +
                                 ([f"predLoss {c[3]}"] if losses != ("hinge",) else []) +
-                                ([f"seqTargets {c[5]}"] if tgts != ("last",) else []))
+                                ([f"seqTargets {c[5]}"] if tgts != ("last",) else []) +
+                                ([f"seqHeads {c[6]}"] if heads != (0,) else []))
 
     initial = {k: p.detach().clone() for k, p in NNs.params.items()}
     finite = {}
@@ -139,11 +147,12 @@ def main():
         # forms every timed epoch is therefore the first epoch of its own training (profiles/seq_att_epoch.txt holds a
         # parent-commit run that shows the default path's divergence). A run without --seqAtt both keeps training its
         # parameters as before, so its lines, not a `both` run's sum lines, are what compares with an earlier commit.
-        args.sampler, args.fusion_rows, args.seqAtt, loss, args.seqPool, args.seqTargets = c
+        args.sampler, args.fusion_rows, args.seqAtt, loss, args.seqPool, args.seqTargets, hd = c
+        args.seqHeads = hd if args.seqAtt in tokens else 0
         args.predLoss = "hinge" if loss == "hinge" else "softmax"
         args.softmaxNegs = opt.softmaxNegs if loss in cand_losses else 0
         args.softmaxNegDist = "pop" if loss == negs_pop else "uniform"
-        if fresh and len(atts) * len(losses) * len(pools) * len(tgts) > 1:
+        if fresh and len(atts) * len(losses) * len(pools) * len(tgts) * len(heads) > 1:
             with torch.no_grad():
                 for k, p in NNs.params.items():
                     p.copy_(initial[k])
@@ -217,9 +226,9 @@ def main():
             print(f"[{label(c)}] touched rows per step (mean of {len(touched[c])}): users {tu:.1f} of {args.user} "
                   f"({100 * tu / args.user:.2f} %), items {ti:.1f} of {args.item} ({100 * ti / args.item:.2f} %)")
     # device time of the sequence-attention entries (kind 5), one device-sampler epoch per token form, pooling and target mode
-    for att, pool, tgt in [(a, po, t) for a in atts if a in tokens for po in pools for t in tgts]:
+    for att, pool, tgt, hd in [(a, po, t, hd) for a in atts if a in tokens for po in pools for t in tgts for hd in heads]:
         lib = ops._lib.load()
-        use(("device", modes[0], att, losses[0], pool, tgt), fresh=True)
+        use(("device", modes[0], att, losses[0], pool, tgt, hd), fresh=True)
         cap = 4096 * steps
         lib.sagnn_profile_enable(cap)
         rec.trainEpoch()
@@ -227,7 +236,7 @@ def main():
         ops.check(lib.sagnn_profile_read(ms.ctypes.data, kind.ctypes.data, None, None, cap, ctypes.byref(n)))
         lib.sagnn_profile_enable(0)
         sel = kind[:n.value] == 5
-        print(f"[device, seqAtt {att}{', seqPool ' + pool if pools != ('sum',) else ''}{', seqTargets ' + tgt if tgts != ('last',) else ''}] "
+        print(f"[device, seqAtt {att}{', seqPool ' + pool if pools != ('sum',) else ''}{', seqTargets ' + tgt if tgts != ('last',) else ''}{', seqHeads ' + str(hd) if heads != (0,) else ''}] "
               f"sequence-attention entries (gather, attention, pool or prefix queries and their backwards): "
               f"{int(sel.sum()) / steps:.0f} calls and {float(ms[:n.value][sel].sum()) / steps:.3f} ms of device time per step; "
               f"layer-norm entries (profile kind 3): {float(ms[:n.value][kind[:n.value] == 3].sum()) / steps:.3f} ms per step")
@@ -236,7 +245,7 @@ def main():
     for loss, mode, tgt in [(lo, m, t) for lo in losses for m in modes for t in tgts
                             if lo != "hinge" and not (lo == "softmax" and m == "batch")]:
         lib = ops._lib.load()
-        use(("device", mode, atts[0], loss, pools[0] if atts[0] in tokens else "sum", tgt), fresh=True)
+        use(("device", mode, atts[0], loss, pools[0] if atts[0] in tokens else "sum", tgt, heads[0]), fresh=True)
         cap = 4096 * steps
         terms, entries = [], {k: getattr(ops, k) for k in ("softmax_loss", "softmax_loss_cand")}
 
@@ -268,6 +277,7 @@ def main():
     args.seqAtt = "sum"
     args.seqPool = "sum"
     args.seqTargets = "last"
+    args.seqHeads = 0
     t0 = time.perf_counter()
     res = rec.testEpoch()
     torch.cuda.synchronize()
