@@ -973,6 +973,57 @@ int sagnn_seq_attn_wide_bwd_f32(const float* qkv, const float* g_ctx, const int3
                                 int pos_length, int d, int heads, int causal, float* dqkv, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Position-wise feed-forward block of the sequence head (seq_ffn.hip; --seqFFN, not in the reference): the second half
+ * of a self-attentive block, on the slab layout above. For every real token row x_j of every slot
+ *   z = LN(x_j; gamma, beta, ln_eps)   (per token over d: z = (x - mean) * rsqrt(var + ln_eps) * gamma + beta, the
+ *                                       function sagnn_layernorm_td_f32 evaluates at t = 1)
+ *   a = z W1 + b1 [f],  h = act(a) with act(a) = leaky * a where leaky * a >= a, else a (sagnn_leaky_f32's convention),
+ *   out = x_j + h W2 + b2.
+ * The operands are the fields of sagnn_seq_ffn_args: x [n_slots * P, d] with row stride ldx, seg_len [n_slots] (clamped
+ * to [0, P]), W1 [d, f] and W2 [f, d] dense, gamma, beta, b2 [d], b1 [f].
+ * sagnn_seq_ffn_f32: every row of out [n_slots * P, d] (row stride ld_out) is WRITTEN, exact zeros in the padding; padded
+ *   rows of x are never read. One launch: a persistent grid whose workgroups hold W1 and W2 in LDS; a wave takes tiles
+ *   of 16 tokens of one slot and skips (zero-fills) those at or beyond n_b; h stays in registers.
+ * sagnn_seq_ffn_bwd_f32: given x and the upstream g [n_slots * P, d] (z, a and h are recomputed; the forward saves
+ *   nothing else): dx = g + LN^T((g W2^T . act'(a)) W1^T), every row WRITTEN with exact zeros in the padding, and the six
+ *   parameter gradients dgamma, dbeta [d], dW1 [d, f], db1 [f], dW2 [f, d], db2 [d], WRITTEN, not accumulated. Padded rows
+ *   of x and g are never read. Three launches: the data path (which stores h | da of the real rows in the workspace,
+ *   slab-addressed [n_slots * P, 2f], and per-wave partial sums of dgamma | dbeta), the weight gradients (tokens as the
+ *   matrix cores' k index; one partial of dW1 | dW2 | db1 | db2 per workgroup, the grid a function of the shape only) and
+ *   the sum of the partials in one fixed order. workspace: sagnn_seq_ffn_bwd_workspace_bytes(n_slots, P, d, f) bytes,
+ *   16-byte aligned; SAGNN_ERR_WORKSPACE when missing or smaller (0 from the query: a shape the entries refuse).
+ * No atomics: every output, the six parameter gradients included, has the same bits in every run. A row's out and dx do
+ *   not depend on its position in a tile or on any other row. Exact fp32 under every engine: all products are chains of
+ *   v_mfma_f32_16x16x4_f32, and sagnn_set_engine does not reach them. Every offset is 64-bit.
+ * sagnn_seq_ffn_supported(d, f, pos_length): SAGNN_OK iff d in {32, 64, 128}, f % 16 == 0, 16 <= f <= 256,
+ *   d * f <= 16384 and 1 <= pos_length <= 256; SAGNN_ERR_DIM otherwise (the reason in sagnn_last_error). d * f bounds the
+ *   LDS the two weight matrices take: (d (f + 4) + f (d + 4) + f) floats, 134 KB at (64, 256) of the compute unit's
+ *   160 KB; (128, 256) is refused. Never touches the device.
+ * Every argument is checked before any device work: NULL (args and every pointer; SAGNN_ERR_NULL), 16-byte alignment of
+ *   every float pointer, row strides multiples of 4 and >= d (SAGNN_ERR_ALIGN), leaky in [0, 1), ln_eps in (0, 1],
+ *   n_slots >= 0 (SAGNN_ERR_ARG). n_slots = 0 returns SAGNN_OK at once, except that the backward still writes its zero
+ *   parameter gradients. No allocation, no synchronisation (capturable). Profile kind 5.
+ * -------------------------------------------------------------------------------- */
+typedef struct sagnn_seq_ffn_args {
+  const float* x;
+  int64_t ldx;
+  const int32_t* seg_len;
+  int64_t n_slots;
+  int pos_length, d, f;
+  const float *gamma, *beta;
+  float ln_eps;
+  const float *W1, *b1, *W2, *b2;
+  float leaky;
+} sagnn_seq_ffn_args;
+
+int sagnn_seq_ffn_supported(int d, int f, int pos_length);
+int sagnn_seq_ffn_f32(const sagnn_seq_ffn_args* args, float* out, int64_t ld_out, void* stream);
+size_t sagnn_seq_ffn_bwd_workspace_bytes(int64_t n_slots, int pos_length, int d, int f);
+int sagnn_seq_ffn_bwd_f32(const sagnn_seq_ffn_args* args, const float* g, int64_t ldg, float* dx, int64_t ld_dx, float* dgamma,
+                          float* dbeta, float* dW1, float* db1, float* dW2, float* db2, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Additive-attention pooling of the sequence head (seq_attn.hip; --seqPool additive, not in the reference's graph: it
  * constructs AdditiveAttention(query_vector_dim, latdim), model.py:147, and comments its call out, model.py:168).
  * On the slab layout above, with u = x Wa + ba [n_slots * P, q] computed by the caller (sagnn_dense_nn_f32 over all

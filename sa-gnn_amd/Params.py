@@ -101,6 +101,13 @@ _FLAGS = [
                          "causal), H a divisor of latdim and latdim / H in {2, 4, 8, 16, 32, 64}; widths 16 to 64 run on the "
                          "fp32 matrix cores; same variables; part of the model (stored in checkpoints, checked on load). "
                          "Not in the reference"),
+    ("seqFFN", int, 0, "the hidden width F of a position-wise feed-forward block after each of --seqAtt full's attention "
+                       "layers: x + act(LN(x) W1 + b1) W2 + b2 per real token, the second half of a SASRec block (0 = off, "
+                       "the head as it was); six more variables per attention layer (seq_ffn{i}_*), none L2-regularised; "
+                       "part of the model (stored in checkpoints, checked on load); needs --seqAtt full (with or without "
+                       "--seqMask causal), latdim in {32, 64, 128}, F a multiple of 16 in [16, 256] with latdim * F <= "
+                       "16384 and pos_length <= 256; one fused ragged kernel family on the fp32 matrix cores; no dropout "
+                       "inside the block. Not in the reference"),
     ("seqTargets", str, "last", "which next-item events of a slot's sequence the head trains on: last (the slot's pooled row "
                                 "against its one sampled positive, as the reference's graph computes, model.py:161-168: one "
                                 "collapsed token, one target) or all (every real token a query: the running sum of the "

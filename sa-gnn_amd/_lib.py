@@ -72,6 +72,13 @@ class SoftmaxArgs(ctypes.Structure):
                 ("workspace_bytes", c_size_t)]
 
 
+class SeqFfnArgs(ctypes.Structure):
+    """sagnn_seq_ffn_args"""
+    _fields_ = [("x", c_void_p), ("ldx", c_int64), ("seg_len", c_void_p), ("n_slots", c_int64), ("pos_length", c_int),
+                ("d", c_int), ("f", c_int), ("gamma", c_void_p), ("beta", c_void_p), ("ln_eps", c_float), ("W1", c_void_p),
+                ("b1", c_void_p), ("W2", c_void_p), ("b2", c_void_p), ("leaky", c_float)]
+
+
 class PlanInfo(ctypes.Structure):
     _fields_ = [("n_rows", c_int64), ("n_src", c_int64), ("nnz", c_int64),
                 ("n_long_rows", c_int64), ("n_chunks", c_int64), ("short_thresh", c_int32),
@@ -234,6 +241,11 @@ SIGNATURES = {
     "sagnn_seq_attn_wide_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "sagnn_seq_attn_wide_bwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p,
                                             c_void_p]),
+    "sagnn_seq_ffn_supported": (c_int, [c_int, c_int, c_int]),
+    "sagnn_seq_ffn_f32": (c_int, [POINTER(SeqFfnArgs), c_void_p, c_int64, c_void_p]),
+    "sagnn_seq_ffn_bwd_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int]),
+    "sagnn_seq_ffn_bwd_f32": (c_int, [POINTER(SeqFfnArgs), c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "sagnn_seq_prefix_query_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_float,
                                            c_void_p, c_int64, c_void_p]),
     "sagnn_seq_prefix_query_bwd_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_float,

@@ -750,6 +750,26 @@ class SeqAttnFn(torch.autograd.Function):
         return (dx, dgamma, dbeta) + _split_qkv_grads(dWqkv, dbqkv, d) + (None, None, None, None, None)
 
 
+class SeqFfnFn(torch.autograd.Function):
+    """The position-wise feed-forward block after a sequence-attention layer (--seqFFN): x [n_slots * P,
+    d] -> x + act(LN(x) W1 + b1) W2 + b2 on the real token rows, zero rows in the padding (ops.seq_ffn). Saved for the
+    backward: x and the parameters; the backward is one ops.seq_ffn_bwd call, which recomputes the hidden activations.
+    Padded rows of the incoming gradient must be zero (SeqPoolFn's and SeqAttnFn's are); the returned gradient's are."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, W1, b1, W2, b2, seg_len, P, leaky):
+        x = x.detach().contiguous()
+        params = tuple(p.detach().contiguous() for p in (gamma, beta, W1, b1, W2, b2))
+        ctx.save_for_backward(x, *params, seg_len)
+        ctx.cfg = (int(P), float(leaky))
+        return ops.seq_ffn(x, *params, seg_len, P, leaky)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, gamma, beta, W1, b1, W2, b2, seg_len = ctx.saved_tensors
+        return ops.seq_ffn_bwd(x, g.contiguous(), gamma, beta, W1, b1, W2, b2, seg_len, *ctx.cfg) + (None, None, None)
+
+
 class SeqPoolFn(torch.autograd.Function):
     """x [n_slots * P, d] -> [n_slots, d]: the sum over each slot's real tokens (ops.seq_pool); the backward
     broadcasts, with zeros into the padding."""

@@ -445,7 +445,24 @@ class Recommender:
         self._define_head_params()
         self._define_ssl_params()
         self._define_seq_pool_params()
+        self._define_seq_ffn_params()
         return self.forward()
+
+    def _define_seq_ffn_params(self):
+        """The position-wise feed-forward blocks of --seqFFN F, one per attention layer of the token head:
+        a layer norm (gamma ones, beta zeros), W1 [d, F] and W2 [F, d] with the default initialiser and zero biases; none
+        L2-regularised, like the MHSA kernels. Defined after every other variable, so those start where they start under
+        --seqFFN 0; nothing is defined at 0."""
+        self.seq_ffn = []
+        if args.seqFFN <= 0:
+            return
+        d, F = args.latdim, args.seqFFN
+        for i in range(args.att_layer):
+            n = f"seq_ffn{i}_"
+            self.seq_ffn.append((NNs.defineParam(n + "ln_gamma", [d], initializer="ones"),
+                                 NNs.defineParam(n + "ln_beta", [d], initializer="zeros"),
+                                 NNs.defineParam(n + "W1", [d, F]), NNs.defineParam(n + "b1", [F], initializer="zeros"),
+                                 NNs.defineParam(n + "W2", [F, d]), NNs.defineParam(n + "b2", [d], initializer="zeros")))
 
     def _define_seq_pool_params(self):
         """The additive-attention pooling of --seqPool additive (the reference's additive_attention0, model.py:147, whose
@@ -571,6 +588,8 @@ class Recommender:
             w = mh.weights()
             x = ag.SeqAttnFn.apply(x, *self.head_ln[2 + i], w["Wq"], w["bq"], w["Wk"], w["bk"], w["Wv"], w["bv"], seg_len, P,
                                    heads, leaky, *mask)
+            if args.seqFFN > 0:                               # --seqFFN: the block's second half
+                x = ag.SeqFfnFn.apply(x, *self.seq_ffn[i], seg_len, P, leaky)
         if not pooled:
             return x
         if args.seqPool == "additive":
@@ -1263,6 +1282,7 @@ class Recommender:
                  "seqAtt": args.seqAtt, "seqPool": args.seqPool, "edgeTime": self._edge_time_state(), "rnnCell": args.rnnCell}
         if args.seqAtt in SEQ_TOKEN_MODES:
             state["seqHeads"] = seq_heads()        # the effective head count of the attention over tokens
+            state["seqFFN"] = int(args.seqFFN)     # the hidden width of the feed-forward blocks, 0 = none
         if getattr(self, "optimizer", None) is not None:
             state["optimizer"] = self.optimizer.state_dict()
         torch.save(state, os.path.join(directory, "Models", args.save_path))
@@ -1292,6 +1312,10 @@ class Recommender:
             raise ValueError(f"checkpoint was trained with {stored_heads} heads in the sequence attention, this run has "
                              f"{seq_heads()} (--seqHeads {args.seqHeads}, --num_attention_heads {args.num_attention_heads}): "
                              "the head count is part of the model")
+        stored_ffn = state.get("seqFFN", 0)              # a checkpoint from before --seqFFN has no feed-forward blocks
+        if stored_ffn != args.seqFFN:
+            raise ValueError(f"checkpoint was trained with --seqFFN {stored_ffn}, this run has --seqFFN {args.seqFFN}: "
+                             "the feed-forward blocks are part of the model")
         stored_pool = state.get("seqPool", "sum")        # a checkpoint from before --seqPool pools with the plain sum
         if stored_pool != args.seqPool:
             raise ValueError(f"checkpoint was trained with --seqPool {stored_pool}, this run has --seqPool {args.seqPool}: "
@@ -1401,6 +1425,15 @@ class Recommender:
         if args.seqHeads > 0 and args.seqAtt not in SEQ_TOKEN_MODES:
             raise ValueError(f"--seqHeads {args.seqHeads} needs --seqAtt full (with or without --seqMask causal; got --seqAtt "
                              f"{args.seqAtt}): it is the head count of the attention over the sequence's tokens")
+        if args.seqFFN < 0:
+            raise ValueError(f"--seqFFN {args.seqFFN}: need a hidden width >= 0 (0 = no feed-forward blocks)")
+        if args.seqFFN > 0:                 # refused before any forward, with the library's reason
+            if args.seqAtt not in SEQ_TOKEN_MODES:
+                raise ValueError(f"--seqFFN {args.seqFFN} needs --seqAtt full (with or without --seqMask causal; got --seqAtt "
+                                 f"{args.seqAtt}): the blocks follow the attention layers over the sequence's tokens")
+            why = ops.seq_ffn_supported(args.latdim, args.seqFFN, args.pos_length)
+            if why is not None:
+                raise ValueError(f"--seqFFN {args.seqFFN} is not available for this configuration: {why}")
         if args.seqAtt in SEQ_TOKEN_MODES:  # refused before any forward: the attention kernels take these shapes only
             heads = seq_heads()
             why = ops.seq_attn_supported(args.latdim, heads, args.pos_length)

@@ -2104,6 +2104,62 @@ def seq_attn_wide_bwd(qkv: torch.Tensor, g_ctx: torch.Tensor, seg_len: torch.Ten
     return dqkv
 
 
+# ---- position-wise feed-forward block of the sequence head (seq_ffn.hip; --seqFFN) ---------------------------------
+def seq_ffn_supported(d: int, f: int, pos_length: int) -> str | None:
+    """None when sagnn_seq_ffn_f32 / _bwd_f32 take the shape (d in {32, 64, 128}, f a multiple of 16 in [16, 256],
+    d * f <= 16384, 1 <= pos_length <= 256), else the library's reason."""
+    return None if _lib.load().sagnn_seq_ffn_supported(int(d), int(f), int(pos_length)) == 0 else _lib.last_error()
+
+
+def _seq_ffn_args(x, gamma, beta, W1, b1, W2, b2, seg_len, pos_length, leaky, eps):
+    """The checked sagnn_seq_ffn_args of a call, with (n_slots, P, d, f)."""
+    n, P = int(seg_len.numel()), int(pos_length)
+    if not isinstance(x, torch.Tensor) or x.dim() != 2:
+        raise ValueError("x: expected a [n_slots * pos_length, d] tensor")
+    d = int(x.shape[1])
+    if not isinstance(W1, torch.Tensor) or W1.dim() != 2 or int(W1.shape[0]) != d:
+        raise ValueError(f"W1: expected a [{d}, f] tensor")
+    f = int(W1.shape[1])
+    ldx = _f32_rows("x", x, d, n * P)
+    _one_device(x, gamma=gamma, beta=beta, W1=W1, b1=b1, W2=W2, b2=b2, seg_len=seg_len)
+    args = _lib.SeqFfnArgs(_ptr_or_empty(x), ldx, _idx_ptr("seg_len", seg_len, torch.int32), n, P, d, f, _vec("gamma", gamma, d),
+                           _vec("beta", beta, d), float(eps), _vec("W1", W1, d * f), _vec("b1", b1, f), _vec("W2", W2, f * d),
+                           _vec("b2", b2, d), float(leaky))
+    if tuple(W2.shape) != (f, d):
+        raise ValueError(f"W2: expected shape [{f}, {d}], got {tuple(W2.shape)}")
+    return args, n, P, d, f
+
+
+def seq_ffn(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, W1: torch.Tensor, b1: torch.Tensor, W2: torch.Tensor,
+            b2: torch.Tensor, seg_len: torch.Tensor, pos_length: int, leaky: float, eps: float = 1e-12):
+    """out = x + act(LN(x) W1 + b1) W2 + b2 on every real token row of the slab x [n_slots * P, d], exact zeros in the
+    padding (sagnn_seq_ffn_f32); act(a) = leaky * a where leaky * a >= a, else a. W1 [d, f], W2 [f, d]."""
+    args, n, P, d, _ = _seq_ffn_args(x, gamma, beta, W1, b1, W2, b2, seg_len, pos_length, leaky, eps)
+    out = torch.empty((n * P, d), dtype=torch.float32, device=x.device)
+    check(_lib.load().sagnn_seq_ffn_f32(ctypes.byref(args), _ptr_or_empty(out), d, _stream()))
+    return out
+
+
+def seq_ffn_bwd(x: torch.Tensor, g: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, W1: torch.Tensor, b1: torch.Tensor,
+                W2: torch.Tensor, b2: torch.Tensor, seg_len: torch.Tensor, pos_length: int, leaky: float, eps: float = 1e-12):
+    """Gradients of seq_ffn (sagnn_seq_ffn_bwd_f32): (dx [n_slots * P, d] with zero rows in the padding, dgamma, dbeta,
+    dW1, db1, dW2, db2), all written; no atomics, bit-identical between runs. Padded rows of x and g are not read."""
+    args, n, P, d, f = _seq_ffn_args(x, gamma, beta, W1, b1, W2, b2, seg_len, pos_length, leaky, eps)
+    ldg = _f32_rows("g", g, d, n * P)
+    _one_device(x, g=g)
+    dev = x.device
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    dx, dgamma, dbeta, dW1, db1, dW2, db2 = new(n * P, d), new(d), new(d), new(d, f), new(f), new(f, d), new(d)
+    need = int(_lib.load().sagnn_seq_ffn_bwd_workspace_bytes(n, P, d, f))
+    if need == 0:
+        raise _lib.SagnnError(-2, _lib.last_error())
+    ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=dev)
+    check(_lib.load().sagnn_seq_ffn_bwd_f32(ctypes.byref(args), _ptr_or_empty(g), ldg, _ptr_or_empty(dx), d, dgamma.data_ptr(),
+                                            dbeta.data_ptr(), dW1.data_ptr(), db1.data_ptr(), dW2.data_ptr(), db2.data_ptr(),
+                                            ws.data_ptr(), need, _stream()))
+    return dx, dgamma, dbeta, dW1, db1, dW2, db2
+
+
 def seq_pool(x: torch.Tensor, seg_len: torch.Tensor, pos_length: int):
     """out[b] = the sum of slot b's real token rows of x [n_slots * P, d] (sagnn_seq_pool_f32) -> [n_slots, d]."""
     n, P, d = int(seg_len.numel()), int(pos_length), int(x.shape[1])

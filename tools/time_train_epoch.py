@@ -75,6 +75,9 @@ def main():
     ap.add_argument("--seqHeads", default="0",
                     help="--seqHeads of the token head (needs --seqAtt full or causal): one count, or a comma-separated "
                          "list such as 0,2 whose entries alternate in one process")
+    ap.add_argument("--seqFFN", default="0",
+                    help="--seqFFN of the token head (needs --seqAtt full or causal): one hidden width, or 0,F whose "
+                         "entries alternate in one process (the blocks' variables are defined once, at width F)")
     opt = ap.parse_args()
     if opt.seqPool != "sum" and opt.seqAtt == "sum":
         opt.seqAtt = "full"
@@ -83,11 +86,18 @@ def main():
     heads = tuple(int(v) for v in opt.seqHeads.split(","))
     if any(heads) and opt.seqAtt not in ("full", "causal"):
         sys.exit(f"--seqHeads {opt.seqHeads} needs --seqAtt full or causal")
+    ffns = tuple(int(v) for v in opt.seqFFN.split(","))
+    if any(ffns) and opt.seqAtt not in ("full", "causal"):
+        sys.exit(f"--seqFFN {opt.seqFFN} needs --seqAtt full or causal")
+    if len({v for v in ffns if v}) > 1:
+        sys.exit(f"--seqFFN {opt.seqFFN}: one hidden width besides 0")
     h = gowalla_shaped_handler()
     args.edgeKeepRate = opt.edge_keep
     rec = Recommender(torch.device("cuda:0"), h)
     if opt.seqPool != "sum":       # the additive variables are defined last: every other one starts where it always does
         args.seqAtt, args.seqPool = "full", "additive"
+    if any(ffns):                  # the blocks' variables are defined after those: the same holds for them
+        args.seqAtt, args.seqFFN = opt.seqAtt, max(ffns)
     rec.prepareModel()
     args.seqAtt = "sum"
     if opt.softmaxNegs < 0 or opt.softmaxNegs > args.item:
@@ -104,11 +114,12 @@ def main():
         args.softmaxNegDist = "pop" if opt.softmaxNegDist == "pop" and args.softmaxNegs else "uniform"
         args.seqPool = "additive" if opt.seqPool == "additive" else "sum"
         args.seqHeads = heads[0]
+        args.seqFFN = ffns[0]      # _seq_att_full reads it at every call: 0 runs the head without the blocks
         for _ in range(2):
             rec.trainEpoch()
         torch.cuda.synchronize()
         print(f"two device-sampler epochs done (--fusion_rows {args.fusion_rows}, --edge_keep {args.edgeKeepRate}, "
-              f"--seqAtt {args.seqAtt}, --seqHeads {args.seqHeads}, --seqTargets {args.seqTargets}, --seqPool {args.seqPool}, --predLoss {args.predLoss}, --softmaxNegs {args.softmaxNegs}, "
+              f"--seqAtt {args.seqAtt}, --seqHeads {args.seqHeads}, --seqFFN {args.seqFFN}, --seqTargets {args.seqTargets}, --seqPool {args.seqPool}, --predLoss {args.predLoss}, --softmaxNegs {args.softmaxNegs}, "
               f"--softmaxNegDist {args.softmaxNegDist}); "
               "every parameter finite:",
               all(bool(torch.isfinite(p).all()) for p in NNs.params.values()))
@@ -127,15 +138,16 @@ def main():
     samplers = ("host", "device") if opt.sampler == "both" else (opt.sampler,)
     tgts = ("last", "all") if opt.seqTargets == "both" else (opt.seqTargets,)
     tokens = ("full", "causal")                            # the head forms in which every sequence item is a token
-    configs = [(sampler, mode, att, loss, pool, tgt, hd) for loss in losses for att in atts for pool in pools for tgt in tgts
-               for hd in heads for mode in modes for sampler in samplers
+    configs = [(sampler, mode, att, loss, pool, tgt, hd, fw) for loss in losses for att in atts for pool in pools for tgt in tgts
+               for hd in heads for fw in ffns for mode in modes for sampler in samplers
                if (att in tokens or pool == "sum") and not (loss == "softmax" and mode == "batch")]
     label = lambda c: ", ".join([c[0]] + ([f"{c[1]} rows"] if len(modes) > 1 else []) +   # noqa: E731
                                 ([f"seqAtt {c[2]}"] if atts != ("sum",) else []) +
                                 ([f"seqPool {c[4]}"] if pools != ("sum",) else []) +
                                 ([f"predLoss {c[3]}"] if losses != ("hinge",) else []) +
                                 ([f"seqTargets {c[5]}"] if tgts != ("last",) else []) +
-                                ([f"seqHeads {c[6]}"] if heads != (0,) else []))
+                                ([f"seqHeads {c[6]}"] if heads != (0,) else []) +
+                                ([f"seqFFN {c[7]}"] if ffns != (0,) else []))
 
     initial = {k: p.detach().clone() for k, p in NNs.params.items()}
     finite = {}
@@ -147,12 +159,13 @@ def main():
         # forms every timed epoch is therefore the first epoch of its own training (profiles/seq_att_epoch.txt holds a
         # parent-commit run that shows the default path's divergence). A run without --seqAtt both keeps training its
         # parameters as before, so its lines, not a `both` run's sum lines, are what compares with an earlier commit.
-        args.sampler, args.fusion_rows, args.seqAtt, loss, args.seqPool, args.seqTargets, hd = c
+        args.sampler, args.fusion_rows, args.seqAtt, loss, args.seqPool, args.seqTargets, hd, fw = c
         args.seqHeads = hd if args.seqAtt in tokens else 0
+        args.seqFFN = fw if args.seqAtt in tokens else 0
         args.predLoss = "hinge" if loss == "hinge" else "softmax"
         args.softmaxNegs = opt.softmaxNegs if loss in cand_losses else 0
         args.softmaxNegDist = "pop" if loss == negs_pop else "uniform"
-        if fresh and len(atts) * len(losses) * len(pools) * len(tgts) * len(heads) > 1:
+        if fresh and len(atts) * len(losses) * len(pools) * len(tgts) * len(heads) * len(ffns) > 1:
             with torch.no_grad():
                 for k, p in NNs.params.items():
                     p.copy_(initial[k])
@@ -226,9 +239,10 @@ def main():
             print(f"[{label(c)}] touched rows per step (mean of {len(touched[c])}): users {tu:.1f} of {args.user} "
                   f"({100 * tu / args.user:.2f} %), items {ti:.1f} of {args.item} ({100 * ti / args.item:.2f} %)")
     # device time of the sequence-attention entries (kind 5), one device-sampler epoch per token form, pooling and target mode
-    for att, pool, tgt, hd in [(a, po, t, hd) for a in atts if a in tokens for po in pools for t in tgts for hd in heads]:
+    for att, pool, tgt, hd, fw in [(a, po, t, hd, fw) for a in atts if a in tokens for po in pools for t in tgts for hd in heads
+                                   for fw in ffns]:
         lib = ops._lib.load()
-        use(("device", modes[0], att, losses[0], pool, tgt, hd), fresh=True)
+        use(("device", modes[0], att, losses[0], pool, tgt, hd, fw), fresh=True)
         cap = 4096 * steps
         lib.sagnn_profile_enable(cap)
         rec.trainEpoch()
@@ -236,8 +250,8 @@ def main():
         ops.check(lib.sagnn_profile_read(ms.ctypes.data, kind.ctypes.data, None, None, cap, ctypes.byref(n)))
         lib.sagnn_profile_enable(0)
         sel = kind[:n.value] == 5
-        print(f"[device, seqAtt {att}{', seqPool ' + pool if pools != ('sum',) else ''}{', seqTargets ' + tgt if tgts != ('last',) else ''}{', seqHeads ' + str(hd) if heads != (0,) else ''}] "
-              f"sequence-attention entries (gather, attention, pool or prefix queries and their backwards): "
+        print(f"[device, seqAtt {att}{', seqPool ' + pool if pools != ('sum',) else ''}{', seqTargets ' + tgt if tgts != ('last',) else ''}{', seqHeads ' + str(hd) if heads != (0,) else ''}{', seqFFN ' + str(fw) if ffns != (0,) else ''}] "
+              f"sequence-attention entries (gather, attention, feed-forward blocks, pool or prefix queries and their backwards): "
               f"{int(sel.sum()) / steps:.0f} calls and {float(ms[:n.value][sel].sum()) / steps:.3f} ms of device time per step; "
               f"layer-norm entries (profile kind 3): {float(ms[:n.value][kind[:n.value] == 3].sum()) / steps:.3f} ms per step")
         print("every parameter finite after that epoch:", all(bool(torch.isfinite(p).all()) for p in NNs.params.values()))
@@ -245,7 +259,7 @@ def main():
     for loss, mode, tgt in [(lo, m, t) for lo in losses for m in modes for t in tgts
                             if lo != "hinge" and not (lo == "softmax" and m == "batch")]:
         lib = ops._lib.load()
-        use(("device", mode, atts[0], loss, pools[0] if atts[0] in tokens else "sum", tgt, heads[0]), fresh=True)
+        use(("device", mode, atts[0], loss, pools[0] if atts[0] in tokens else "sum", tgt, heads[0], ffns[0]), fresh=True)
         cap = 4096 * steps
         terms, entries = [], {k: getattr(ops, k) for k in ("softmax_loss", "softmax_loss_cand")}
 
@@ -278,6 +292,7 @@ def main():
     args.seqPool = "sum"
     args.seqTargets = "last"
     args.seqHeads = 0
+    args.seqFFN = 0
     t0 = time.perf_counter()
     res = rec.testEpoch()
     torch.cuda.synchronize()
